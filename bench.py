@@ -2,7 +2,8 @@
 """bench.py -- KinectFusion frames/s (640x480 depth -> 512^3 TSDF) on MI355X, plus the SdfFuse
 HBM roofline and the CPU baseline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scene full|room] [--math fast|exact] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scene full|room] [--math fast|exact] [--full [--no-cpu-baseline]]
+                    [--dump-outputs DIR]
 
 A "step" is one frame of the headless KinectFusion loop on synthetic depth that is already
 resident in HBM: BilateralFilter -> DepthToVbo -> NormalsFromVbo -> SdfFuse -> RaycastSdf
@@ -19,7 +20,19 @@ device events around its parts, so neither the launch rate nor the kernel times 
 warm-up steps the stream runs untimed until its frame time is stationary (blocks of 60 frames: the last three within 2 %,
 at least --prime-seconds of GPU work, at most --prime-cap-seconds); --summary auto decides between the tracked and the plain
 pair of kernels on whole frames AFTER that (three blocks of 60 frames: tracked, plain, tracked), then the stream settles
-again.  The number of untimed frames is in the line ("prime").
+again.  The number of untimed frames is in the line ("prime").  Then the volume is reset and the stream restarts from the
+first pose of the orbit for RESTART_FRAMES untimed frames, so that the W warm-up and the K timed steps see the same volume
+and the same poses in every run, however long the priming took.
+
+1 GPU, plain run (the default): set-up, the untimed frames, the W warm-up steps, the K timed steps, the outputs of the last
+timed step if --dump-outputs is given, the line.  --full: everything else the line reports beside the headline as well --
+the parts of a frame, the SdfFuse / RaycastSdf rooflines, the other numerics mode and pair of kernels, the CPU baseline and
+the legs on other scenes and sizes.  N > 1: the line is the same either way.
+
+--dump-outputs DIR: after the timed steps, what the last one computed -- the frame's images (filtered depth, vertices,
+normals, the three raycast images) and a fixed sample of the volume's cells -- as DIR/<name>.npy, float32 (float64 for the
+sample's cell indices), for comparing two builds output for output.  Every array is finite: where the operators leave NaN (no
+depth, no hit, a cell never observed) it holds 0, and DIR/<name>_finite.npy is 1 where the pixel / cell was finite, 0 where not.
 
 Prints ONE JSON line on rank 0.
 """
@@ -39,6 +52,9 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/
 N_ORBIT = 30
 PMC_TRAFFIC_FILES = ("profiles/r06_pmc_traffic.json", "profiles/r05_pmc_traffic.json")   # the first that was taken on the loaded kernels
 BLOCK = 60   # frames per priming / calibration block: two orbits (launch times depend on the pose)
+RESTART_FRAMES = 60 * BLOCK   # untimed frames between the volume reset and the warm-up (the priming of a default run is ~6000)
+DUMP_SAMPLE_CELLS, DUMP_SEED = 1 << 20, 1234   # --dump-outputs: cells of the volume sampled (fixed seed), at most 8 MiB of them
+DUMP_LIMIT_BYTES = 64 << 20
 
 
 def parse():
@@ -98,9 +114,15 @@ def parse():
                     help="untimed frames run until the frame time is stationary AND at least this much GPU time has passed: a GPU "
                          "that was idle takes on the order of a second of work to settle its clocks (KFX_BENCH_DUMP=1 prints the blocks)")
     ap.add_argument("--prime-cap-seconds", type=float, default=8.0, help="give up waiting for a stationary frame time after this much GPU time")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="1 GPU: also measure what the line reports beside the headline (parts of a frame, rooflines, the other numerics mode and "
+                         "pair of kernels, ceilings of the GPU, the CPU baseline, the legs below); off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="1 GPU: write what the last timed step computed (the frame's images, a fixed sample of the volume) as DIR/<name>.npy; "
+                         "NaN (no depth / hit, a cell never observed) is written as 0, with DIR/<name>_finite.npy marking the finite entries")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="1 GPU, default configuration: skip the reported legs that follow the headline in the same process -- `room_variant` "
+                    help="--full, 1 GPU, default configuration: skip the reported legs that follow the headline in the same process -- `room_variant` "
                          "(the same loop on scene S_room, the fps scene of SURVEY 8(d)), `tracked_variant` (the application's loop with the "
                          "projective ICP between rendering and integration: TrackingPipeline(device_icp=True) on S_room; + the drop-in application "
                          "itself as a child process), `noise_variant` (S_room with 2 mm depth noise), `c3_variant` (1280x960), `c4_one_gpu_variant` "
@@ -202,9 +224,10 @@ def workload_text(args, n_prime, distributed):
     N, w, h = args.res, args.width, args.height
     return ("BASELINE configs[%d]: %d^3 TSDF (SDF_t f32 val+weight, %.2f GiB), %dx%d synthetic depth resident in HBM, scene S_%s, "
             "%d-pose orbit with known poses; per frame: BilateralFilter(7x7) -> DepthToVbo -> NormalsFromVbo -> SdfFuse -> RaycastSdf%s; "
-            "%d untimed frames of the stream precede the warm-up steps" % (
+            "%d untimed frames of the stream precede the warm-up steps%s" % (
                 2 if args.config == "c3" else 1, N, 8.0 * N ** 3 / 2 ** 30, w, h, args.scene, N_ORBIT,
-                "" if distributed else " (one kfx_frame_step call per frame)", n_prime))
+                "" if distributed else " (one kfx_frame_step call per frame)", n_prime,
+                "" if distributed else ", the last %d of them after a reset of the volume, from the first pose" % RESTART_FRAMES))
 
 
 MATH_TEXT = {"fast": "fast (fp32 rcp/rsq + FMA: the reference's own -use_fast_math regime, running average as old + (new - old) w / (w + old.w); whole chain against the exact oracle at this size, "
@@ -476,8 +499,52 @@ def tracked_leg(args, torch, roo, scenes, n_steps, noise=False):
     return out
 
 
+def finite_split(name, a, channels):
+    """{name: a with its non-finite entries as 0, name_finite: 1 where every channel of the pixel / cell is finite, else 0}: NaN
+    is what the operators write where there is no depth or hit and what a never-observed cell holds; the dump stays finite."""
+    ok = np.isfinite(a)
+    return {name: np.where(ok, a, np.float32(0)).astype(a.dtype),
+            name + "_finite": (ok.all(axis=-1) if channels else ok).astype(np.float32)}
+
+
+def snapshot_outputs(torch, pipe):
+    """What the last frame left in the caller's containers, copied to the host: the frame's images and the cells (val, w) of a
+    fixed sample of the volume (DUMP_SEED: the same cells in every run of the same size), each beside its `_finite` mask (see
+    finite_split).  Images too large for DUMP_LIMIT_BYTES beside the sample keep every k-th row only.  Returns (arrays, row stride)."""
+    vol = pipe.vol
+    n_cells = vol.w * vol.h * vol.d
+    if n_cells <= DUMP_SAMPLE_CELLS:
+        cells = np.arange(n_cells, dtype=np.int64)
+    else:
+        cells = np.sort(np.random.default_rng(DUMP_SEED).choice(n_cells, DUMP_SAMPLE_CELLS, replace=False)).astype(np.int64)
+    t = torch.from_numpy(cells).to(vol.storage.device)
+    x, y, z = t % vol.w, (t // vol.w) % vol.h, t // (vol.w * vol.h)
+    out = finite_split("volume_sample", vol.tensor()[z, y, x].float().cpu().numpy(), True)   # (n, 2): val, w
+    out["volume_sample_cells"] = cells.astype(np.float64)                                      # x + w (y + h z)
+    images = {"filtered_depth": pipe.filtered, "vertices": pipe.vbo, "normals": pipe.normals,
+              "raycast_depth": pipe.ray_d, "raycast_normals": pipe.ray_n, "raycast_image": pipe.ray_i}
+    split = {}
+    for name, im in images.items():
+        split.update(finite_split(name, np.ascontiguousarray(im.MemcpyToHost(), dtype=np.float32), im.channels > 1))
+    room = DUMP_LIMIT_BYTES - sum(a.nbytes for a in out.values())
+    stride = max(1, -(-sum(a.nbytes for a in split.values()) // room))
+    out.update({name: np.ascontiguousarray(a[::stride]) for name, a in split.items()})
+    return out, stride
+
+
+def write_outputs(outputs, stride, directory):
+    total = sum(a.nbytes for a in outputs.values())
+    assert total <= DUMP_LIMIT_BYTES, "outputs of %d bytes exceed the dump limit" % total
+    os.makedirs(directory, exist_ok=True)
+    for name, a in outputs.items():
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), name
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return {"dir": directory, "files": sorted(n + ".npy" for n in outputs), "bytes": int(total), "image_row_stride": int(stride),
+            "volume_sample_seed": DUMP_SEED}
+
+
 def run_single(args, torch, roo, scenes, rank):
-    """1 GPU: the headline and everything reported beside it.  Returns the JSON object (without cpu_baseline)."""
+    """1 GPU: the headline, and with --full everything reported beside it.  Returns the JSON object (without cpu_baseline)."""
     import gc
     from kangaroo_amd.pipeline import FramePipeline
     N, w, h, scene = args.res, args.width, args.height, args.scene
@@ -506,12 +573,13 @@ def run_single(args, torch, roo, scenes, rank):
         frames.append(im)
 
     # algorithmic bytes: 16 B x N_updated + 20 B x w*h per SdfFuse launch; N_updated counted per pose by
-    # the diagnostics kernel (same predicate, no volume traffic), outside timing
+    # the diagnostics kernel (same predicate, no volume traffic), outside timing (--full: the roofline)
     n_updated = []
-    for i in range(N_ORBIT):
-        pipe.preprocess(frames[i])
-        n_updated.append(roo.SdfFuseCount(pipe.vol, pipe.filtered, pipe.normals, scenes.se3_inverse(poses[i]), K, pipe.trunc, pipe.mincostheta))
-    alg = [16.0 * n_updated[i] + 20.0 * w * h for i in range(N_ORBIT)]
+    if args.full:
+        for i in range(N_ORBIT):
+            pipe.preprocess(frames[i])
+            n_updated.append(roo.SdfFuseCount(pipe.vol, pipe.filtered, pipe.normals, scenes.se3_inverse(poses[i]), K, pipe.trunc, pipe.mincostheta))
+    alg = [16.0 * n_updated[i] + 20.0 * w * h for i in range(len(n_updated))]
 
     cursor = [0]   # the stream's frame counter: poses / depth images cycle through the orbit
 
@@ -533,9 +601,16 @@ def run_single(args, torch, roo, scenes, rank):
             guard += 1
         prime_log.append(prime_stream(kf, step, 0.25, 2.0, 3 * BLOCK))
     use_summary = bool(pipe.track)   # what the timed frames run with
+    # ---- restart: how many frames the priming took depends on the clocks; the volume the timed steps see must not.  Reset
+    # (cells and, with the tables, the summary), then RESTART_FRAMES frames from the first pose, the warm-up, the timed steps ----
+    n_primed = cursor[0]
+    kf.reset()
+    cursor[0] = 0
+    for _ in range(RESTART_FRAMES):
+        step()
     for _ in range(args.warmup):
         step()
-    n_prime = cursor[0] - args.warmup
+    n_prime = n_primed + RESTART_FRAMES
     torch.cuda.synchronize()
     # ---- the timed region: exactly K steps between two synchronisations ----
     first = kf.count
@@ -547,6 +622,53 @@ def run_single(args, torch, roo, scenes, rank):
 
     t = kf.timings(first, args.steps)   # device events recorded by kfx_frame_step on the launch stream around SdfFuse
     fuse_ms = t[:, 1]
+    fuse_avg_ms = float(np.mean(fuse_ms))
+    hits = int(torch.isfinite(pipe.ray_d.tensor()).sum())
+    assert hits > 0, "raycast produced no hits"
+    dumped = write_outputs(*snapshot_outputs(torch, pipe), args.dump_outputs) if args.dump_outputs else None
+    if os.environ.get("KFX_BENCH_DUMP"):   # per-step windows of the timed region and the priming blocks (transients)
+        for pl in prime_log:
+            print("prime_blocks_ms " + " ".join("%.4f" % v for v in pl["block_mean_frame_ms"]), file=sys.stderr)
+        print("fuse_ms " + " ".join("%.3f" % v for v in fuse_ms[:64]), file=sys.stderr)
+        print("period_ms " + " ".join("%.3f" % v for v in t[:64, 4]), file=sys.stderr)
+    restart = {"frames": RESTART_FRAMES, "after_priming_frames": n_primed,
+               "note": "the volume is reset after the priming and the stream restarts from the first pose: the warm-up and the timed steps "
+                       "see the same volume in every run"}
+    kernels_ms = {"sdf_fuse": round(fuse_avg_ms, 5), "frame_total": round(1e3 * elapsed / args.steps, 5),
+                  "frame_period_events": round(float(np.nanmean(t[:, 4])), 5)}
+    out = {
+        "metric": "kinectfusion_frames_per_sec_640x480_to_512cubed_tsdf",
+        "value": round(args.steps / elapsed, 3),
+        "unit": "frames/s",
+        "n_gpus": 1,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "prime": n_prime,
+        "ms_per_step": round(1e3 * elapsed / args.steps, 4),
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {
+            "workload": workload_text(args, n_prime, False),
+            "volume": [N, N, N], "image": [w, h], "scene": scene, "backend": None, "ranks_agree": None,
+            "raycast": ("march through the class tables of the brick summary, kept current by the tracked SdfFuse (kfx_sdf_fuse_tracked + kfx_raycast_sdf_tracked)"
+                        if use_summary else "plain march (kfx_raycast_sdf)"),
+            "summary_policy": {"requested": args.summary if args.math == "fast" else "off (exact numerics)", "decision": pipe.track_decision},
+            "priming": prime_log,
+            "restart": restart,
+            "partition": "single volume",
+            "math": MATH_TEXT[args.math],
+        },
+        "kernels_ms": kernels_ms,
+    }
+    if dumped is not None:
+        out["outputs"] = dumped
+    if not args.full:
+        return out
+
+    # ==== --full: everything below is reported beside the headline; none of it is `value` ====
     # the parts of the same frames, from 60 more of them with all four events (untimed; they cost 2-3 % of the frame rate)
     pipe.set_timing(kf.EVENTS_ALL)
     for _ in range(N_ORBIT):
@@ -555,21 +677,14 @@ def run_single(args, torch, roo, scenes, rank):
     i_parts = [step() for _ in range(2 * N_ORBIT)]
     tp = kf.timings(f_parts, 2 * N_ORBIT)
     pre_ms, ray_ms, frame_ms = tp[:, 0], tp[:, 2], tp[:, 3]
-    if os.environ.get("KFX_BENCH_DUMP"):   # per-step windows of the timed region and the priming blocks (transients)
-        for pl in prime_log:
-            print("prime_blocks_ms " + " ".join("%.4f" % v for v in pl["block_mean_frame_ms"]), file=sys.stderr)
-        print("fuse_ms " + " ".join("%.3f" % v for v in fuse_ms[:64]), file=sys.stderr)
-        print("period_ms " + " ".join("%.3f" % v for v in t[:64, 4]), file=sys.stderr)
+    if os.environ.get("KFX_BENCH_DUMP"):
         print("parts: ray_ms " + " ".join("%.3f" % v for v in ray_ms[:30]), file=sys.stderr)
         print("parts: pre_ms " + " ".join("%.3f" % v for v in pre_ms[:30]), file=sys.stderr)
-    fuse_avg_ms = float(np.mean(fuse_ms))
     ray_avg_ms = float(np.mean(ray_ms))
     ray_idx = i_parts   # the poses RaycastSdf's figures are averaged over
     bytes_avg = float(np.mean([alg[i] for i in idx]))
     achieved = bytes_avg / (fuse_avg_ms * 1e-3) / 1e9
     voxels = pipe.vol.w * pipe.vol.h * pipe.vol.d
-    hits = int(torch.isfinite(pipe.ray_d.tensor()).sum())
-    assert hits > 0, "raycast produced no hits"
 
     def timed_steps(n, untimed):
         """`untimed` frames, a synchronisation, n frames between two host clock readings; (frames/s, per-frame timings)."""
@@ -781,11 +896,9 @@ def run_single(args, torch, roo, scenes, rank):
         rmw_probe = {"error": repr(e)[:200]}
 
     traffic, traffic_source = pmc_traffic("%s_%s%s" % (scene, args.math, "_tracked" if use_summary else "")) if (N, w, h) == (512, 640, 480) else (None, None)
-    n_prime_total = n_prime
     # ---- the two legs SURVEY 8(d) / 8(f) name beside the roofline scene, driver-timed in the default command: S_room (the fps scene)
     # through the same loop, and the tracked loop (ICP between rendering and integration).  Reported extras: never `value`. ----
     room_variant, tracked_variant, noise_variant, c3_variant, c4_variant, c5_variant = None, None, None, None, None, None
-    track_decision = pipe.track_decision
     if args.config == "c2" and scene == "full" and not args.no_extra_legs:
         del pipe, kf, frames   # (one 512^3 volume at a time is plenty; the legs build their own pipelines)
         torch.cuda.empty_cache()
@@ -832,30 +945,9 @@ def run_single(args, torch, roo, scenes, rank):
             c5_variant = c5_leg(args, torch, roo, scenes, n_short)
         except Exception as e:   # noqa: BLE001
             c5_variant = {"error": repr(e)[:300]}
-    out = {
-        "metric": "kinectfusion_frames_per_sec_640x480_to_512cubed_tsdf",
-        "value": round(args.steps / elapsed, 3),
-        "unit": "frames/s",
-        "n_gpus": 1,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "prime": n_prime_total,
-        "ms_per_step": round(1e3 * elapsed / args.steps, 4),
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {
-            "workload": workload_text(args, n_prime_total, False),
-            "volume": [N, N, N], "image": [w, h], "scene": scene, "backend": None, "ranks_agree": None,
-            "raycast": ("march through the class tables of the brick summary, kept current by the tracked SdfFuse (kfx_sdf_fuse_tracked + kfx_raycast_sdf_tracked)"
-                        if use_summary else "plain march (kfx_raycast_sdf)"),
-            "summary_policy": {"requested": args.summary if args.math == "fast" else "off (exact numerics)", "decision": track_decision},
-            "priming": prime_log,
-            "partition": "single volume",
-            "math": MATH_TEXT[args.math],
-        },
+    outputs = out.pop("outputs", None)
+    del out["kernels_ms"]   # (re-inserted after the roofline: the order of the line's keys)
+    out.update({
         "roofline": {
             "kernel": "k_sdf_fuse_tiled<%s%s> (SdfFuse, %s math%s)" % ("true" if args.math == "fast" else "false", ", TRACK" if use_summary else "", args.math,
                                                                         ", keeping the brick summary current" if use_summary else ""),
@@ -879,16 +971,17 @@ def run_single(args, torch, roo, scenes, rank):
             "torch_copy_GBps": None if copy_GBps is None else round(copy_GBps, 1),
             "note": "whole volume",
         },
-        "kernels_ms": {"sdf_fuse": round(fuse_avg_ms, 5), "frame_total": round(1e3 * elapsed / args.steps, 5),
-                       "frame_period_events": round(float(np.nanmean(t[:, 4])), 5),
-                       "parts": {"preprocess": round(float(np.mean(pre_ms)), 5), "sdf_fuse": round(float(np.mean(tp[:, 1])), 5),
-                                 "raycast_sdf": round(ray_avg_ms, 5), "frame_events": round(float(np.mean(frame_ms)), 5),
-                                 "period": round(float(np.nanmean(tp[:, 4])), 5),
-                                 "note": "%d frames of the same stream with all four events recorded, right after the timed region; the timed "
-                                         "steps record the two around SdfFuse only (an event is a marker between launches: four per frame cost "
-                                         "2-3 %% of the frame rate)" % (2 * N_ORBIT)}},
+        "kernels_ms": dict(kernels_ms,
+                           parts={"preprocess": round(float(np.mean(pre_ms)), 5), "sdf_fuse": round(float(np.mean(tp[:, 1])), 5),
+                                  "raycast_sdf": round(ray_avg_ms, 5), "frame_events": round(float(np.mean(frame_ms)), 5),
+                                  "period": round(float(np.nanmean(tp[:, 4])), 5),
+                                  "note": "%d frames of the same stream with all four events recorded, right after the timed region; the timed "
+                                          "steps record the two around SdfFuse only (an event is a marker between launches: four per frame cost "
+                                          "2-3 %% of the frame rate)" % (2 * N_ORBIT)}),
         "sdf_fuse_other_mode": other_line,
-    }
+    })
+    if outputs is not None:
+        out["outputs"] = outputs
     for key, val in (("roofline_raycast", roofline_raycast), ("bilateral", bilateral_line), ("transfer_inclusive", transfer_line),
                      ("brick_summary_variant", summary_variant), ("plain_variant", plain_variant), ("room_variant", room_variant),
                      ("tracked_variant", tracked_variant), ("noise_variant", noise_variant), ("c3_variant", c3_variant),
@@ -1369,6 +1462,8 @@ def run_slabs(args, torch, dist, roo, scenes, rank, world):
 
 def main():
     args = parse()
+    if args.dump_outputs and args.gpus > 1:
+        sys.exit("bench.py: --dump-outputs is an option of --gpus 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         spawn_ranks(args)   # does not return
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1417,12 +1512,12 @@ def main():
     else:
         out = run_single(args, torch, roo, scenes, rank)
     if rank == 0:
-        if not args.no_cpu_baseline and not distributed:
+        if args.full and not args.no_cpu_baseline and not distributed:
             try:
                 out["cpu_baseline"] = cpu_baseline(args, args.scene, args.cpu_frames)
             except Exception as e:  # the baseline is a reported extra; never lose the GPU number
                 out["cpu_baseline"] = {"value": None, "unit": "frames/s", "cores": 0, "kind": "port", "sample": "failed: %r" % (e,)}
-        if not distributed:
+        if args.full and not distributed:
             out["summary"] = make_summary(out)   # last key of the line
         print(json.dumps(out), flush=True)
     if distributed:

@@ -1,5 +1,5 @@
 #!/bin/bash
-# fresh_runs.sh TAG [N] [IDLE_S] [extra bench.py args...] -- the driver's command, N times, each as a fresh process after
+# fresh_runs.sh TAG [N] [IDLE_S] [extra bench.py args...] -- the driver's command with --full, N times, each as a fresh process after
 # IDLE_S seconds of GPU idle (round-3 verdict item 1: the headline has to hold on a cold box).  Keeps every JSON line and the
 # per-step dumps (KFX_BENCH_DUMP=1) under gpurun_out/TAG/ and prints a one-line summary per run.
 TAG=${1:-fresh}; N=${2:-10}; IDLE=${3:-30}
@@ -8,7 +8,7 @@ OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 for i in $(seq 1 "$N"); do
     sleep "$IDLE"
-    KFX_BENCH_DUMP=1 python3 bench.py --gpus 1 --steps 20 --warmup 5 "$@" > "$OUT/run_$i.json" 2> "$OUT/run_$i.err"
+    KFX_BENCH_DUMP=1 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full "$@" > "$OUT/run_$i.json" 2> "$OUT/run_$i.err"
     python3 - "$OUT/run_$i.json" "$i" <<'EOF'
 import json, sys
 try:

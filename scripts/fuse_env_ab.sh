@@ -12,7 +12,7 @@ for r in $(seq 1 $ROUNDS); do
     name=${cfg%%|*}; args=${cfg#*|}
     for v in 0 1; do
       export $VAR=$v
-      python3 bench.py --steps 120 --warmup 10 --prime-seconds 1 --no-extra-legs --no-cpu-baseline $args > $OUT/${name}_v${v}_$r.json 2> $OUT/${name}_v${v}_$r.err
+      python3 bench.py --full --steps 120 --warmup 10 --prime-seconds 1 --no-extra-legs --no-cpu-baseline $args > $OUT/${name}_v${v}_$r.json 2> $OUT/${name}_v${v}_$r.err
     done
   done
 done

@@ -14,7 +14,7 @@ for r in $(seq 1 $ROUNDS); do
     name=${cfg%%|*}; args=${cfg#*|}
     for lib in dma regstage; do
       if [ $lib = regstage ]; then export KFX_LIB_PATH=$ROOT/build_ab/$AB/libkfx.so; else unset KFX_LIB_PATH; fi
-      python3 bench.py --steps 120 --warmup 10 --prime-seconds 1 --no-extra-legs --no-cpu-baseline $args > $OUT/${name}_${lib}_$r.json 2> $OUT/${name}_${lib}_$r.err
+      python3 bench.py --full --steps 120 --warmup 10 --prime-seconds 1 --no-extra-legs --no-cpu-baseline $args > $OUT/${name}_${lib}_$r.json 2> $OUT/${name}_${lib}_$r.err
     done
   done
 done

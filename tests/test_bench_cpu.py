@@ -1,11 +1,12 @@
 """bench.py's launcher logic, checked without a GPU: `--gpus N` must either run N ranks or fail -- never report a
-1-GPU number for an N-GPU request (round-1 finding) --, and the CPU-baseline build tuned for the host computes the
-same bits as the portable parity build."""
+1-GPU number for an N-GPU request (round-1 finding) --, the CPU-baseline build tuned for the host computes the
+same bits as the portable parity build, and --dump-outputs writes what it promises (on host containers)."""
 import os
 import subprocess
 import sys
 
 import numpy as np
+import pytest
 
 import kfx_testlib as T
 
@@ -118,3 +119,69 @@ def test_cpu_baseline_is_a_median_of_three_blocks():
     assert abs(out["value"] - float(np.median(out["blocks_fps"]))) < 1e-3
     assert abs(out["spread"] - (max(out["blocks_fps"]) - min(out["blocks_fps"])) / out["value"]) < 1e-3
     assert "median of 3 blocks of 6 full frames" in out["sample"] and out["single_thread"]["cores"] == 1
+
+
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    """`bench.py --gpus 1 --steps K --warmup W` times the headline alone; what the line reports beside it takes --full."""
+    sys.path.insert(0, T.ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 3 and a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_is_refused_for_several_gpus():
+    out = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dump-outputs", "d"], capture_output=True, text=True, timeout=120, env=_env())
+    assert out.returncode != 0 and "--dump-outputs" in out.stderr and not out.stdout.strip()
+
+
+@pytest.mark.parametrize("N,w,h", [(32, 80, 60), (512, 640, 480), (128, 1280, 960)])
+def test_dump_outputs_are_the_frame_images_and_a_fixed_volume_sample(tmp_path, N, w, h):
+    """--dump-outputs: the frame's six images and the same seeded sample of cells in every run, float32 / float64 only, every
+    value finite (NaN -- no depth, no hit, a cell never observed -- as 0 beside a `_finite` mask), at most 64 MiB in all (images
+    that would not fit keep every k-th row).  Host containers stand in for the pipeline's device ones."""
+    import types
+    import torch
+    sys.path.insert(0, T.ROOT)
+    import bench
+    from kangaroo_amd import roo
+
+    def with_nans(x, g):   # about a third of the pixels / cells NaN, as the operators leave them
+        x[torch.rand(x.shape[:-1], generator=g) < 0.3] = float("nan")
+        return x
+
+    def pipe(seed):
+        g = torch.Generator().manual_seed(seed)
+        ims = {}
+        for name, kind in (("filtered", "f32"), ("vbo", "f32x4"), ("normals", "f32x4"), ("ray_d", "f32"), ("ray_n", "f32x4"), ("ray_i", "f32")):
+            im = roo.Image(w, h, kind, device="cpu")
+            im.MemcpyFromHost(with_nans(torch.rand(im.h, im.w, im.channels, generator=g), g).numpy())
+            ims[name] = im
+        vol = roo.BoundedVolume(N, N, N, device="cpu")
+        vol.tensor().copy_(with_nans(torch.rand(N, N, N, 2, generator=g), g))
+        return types.SimpleNamespace(vol=vol, **ims)
+
+    p = pipe(1)
+    arrays, stride = bench.snapshot_outputs(torch, p)
+    info = bench.write_outputs(arrays, stride, str(tmp_path))
+    assert info["bytes"] <= 64 << 20 and info["image_row_stride"] == stride
+    names = ["filtered_depth", "vertices", "normals", "raycast_depth", "raycast_normals", "raycast_image", "volume_sample"]
+    assert sorted(os.listdir(str(tmp_path))) == info["files"] == sorted(
+        [n + ".npy" for n in names] + [n + "_finite.npy" for n in names] + ["volume_sample_cells.npy"])
+    loaded = {f[:-4]: np.load(str(tmp_path / f)) for f in info["files"]}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in loaded.values())
+    assert sum(a.nbytes for a in loaded.values()) == info["bytes"]
+    assert (stride > 1) == (w == 1280)
+    cells = loaded["volume_sample_cells"].astype(np.int64)
+    assert len(np.unique(cells)) == len(cells) == min(N ** 3, 1 << 20) and 0 <= cells.min() and cells.max() < N ** 3
+    for name, src in (("raycast_normals", p.ray_n.MemcpyToHost()[::stride]), ("filtered_depth", p.filtered.MemcpyToHost()[::stride]),
+                      ("volume_sample", p.vol.tensor().numpy().reshape(-1, 2)[cells])):
+        ok = np.isfinite(src)
+        mask = ok.all(axis=-1) if name != "filtered_depth" else ok
+        assert np.array_equal(loaded[name + "_finite"], mask.astype(np.float32)) and 0 < mask.mean() < 1
+        assert np.array_equal(loaded[name][ok], src[ok]) and not loaded[name][~ok].any()
+    again, _ = bench.snapshot_outputs(torch, pipe(2))   # another volume of the same size: the same cells
+    assert np.array_equal(again["volume_sample_cells"], loaded["volume_sample_cells"])
