@@ -15,6 +15,7 @@
 #include <kangaroo/Mat.h>
 #include <kangaroo/Sdf.h>
 #include <kangaroo/launch_utils.h>
+#include <kfx_summary_h.h>
 
 namespace roo
 {
@@ -26,6 +27,12 @@ public:
     explicit SdfSummary(const BoundedVolume<SDF_t, TargetDevice, Management>& vol) : handle_(0)
     {
         GpuCheckStatus(kfx_sdf_summary_create(&handle_, vol.abi()));
+    }
+    // half cells (BoundedVolume<SDF_h>, config C5): takes the SDF_h overloads below (include/kfx_summary_h.h)
+    template<typename Management>
+    explicit SdfSummary(const BoundedVolume<SDF_h, TargetDevice, Management>& vol) : handle_(0)
+    {
+        GpuCheckStatus(kfx_sdf_summary_create_h(&handle_, vol.abi()));
     }
     ~SdfSummary() { kfx_sdf_summary_destroy(handle_); }
     SdfSummary(const SdfSummary&) = delete;
@@ -73,6 +80,42 @@ inline void RaycastSdfLevels(const Image<float>* depth, const Image<float4>* nor
     }
     GpuCheckStatus(kfx_raycast_sdf_levels_tracked((int)n, d, nn, im, vbo ? vb : 0, vol.abi(), summary.get(), T_wc.m, k, near, far, trunc_dist,
                                                   subpix ? 1 : 0, 0));
+}
+
+// the same on half cells (BoundedVolume<SDF_h>): exact numerics bit-identical to the plain SDF_h calls; fast numerics within the
+// fast-mode tolerance (KFX_SUMMARY_HALF_BAND)
+inline void SdfReset(BoundedVolume<SDF_h> vol, float trunc_dist, SdfSummary& summary)
+{
+    GpuCheckStatus(kfx_sdf_reset_tracked_h(vol.abi(), summary.get(), trunc_dist, 0));
+}
+
+inline void SdfFuse(BoundedVolume<SDF_h> vol, SdfSummary& summary, Image<float> depth, Image<float4> norm, Mat<float,3,4> T_cw, ImageIntrinsics K,
+                    float trunc_dist, float maxw, float mincostheta)
+{
+    GpuCheckStatus(kfx_sdf_fuse_tracked_h(vol.abi(), summary.get(), depth.abi(), norm.abi(), T_cw.m, &K.fu, trunc_dist, maxw, mincostheta, 0, 0));
+}
+
+inline void RaycastSdf(Image<float> depth, Image<float4> norm, Image<float> img, const BoundedVolume<SDF_h> vol, SdfSummary& summary,
+                       const Mat<float,3,4> T_wc, ImageIntrinsics K, float near, float far, float trunc_dist, bool subpix = true)
+{
+    GpuCheckStatus(kfx_raycast_sdf_tracked_h(depth.abi(), norm.abi(), img.abi(), vol.abi(), summary.get(), T_wc.m, &K.fu, near, far, trunc_dist,
+                                             subpix ? 1 : 0, 0));
+}
+
+inline void RaycastSdfLevels(const Image<float>* depth, const Image<float4>* norm, const Image<float>* img, unsigned n,
+                             const BoundedVolume<SDF_h> vol, SdfSummary& summary, const Mat<float,3,4> T_wc, const ImageIntrinsics* K,
+                             float near, float far, float trunc_dist, bool subpix = true, const Image<float4>* vbo = 0)
+{
+    const kfx_image *d[8], *nn[8], *im[8], *vb[8];
+    float k[32];
+    if (n > 8) GpuCheckStatus(KFX_E_RANGE);
+    for (unsigned l = 0; l < n && l < 8; ++l) {
+        d[l] = depth[l].abi(); nn[l] = norm[l].abi(); im[l] = img[l].abi();
+        vb[l] = vbo ? vbo[l].abi() : 0;
+        k[4 * l] = K[l].fu; k[4 * l + 1] = K[l].fv; k[4 * l + 2] = K[l].u0; k[4 * l + 3] = K[l].v0;
+    }
+    GpuCheckStatus(kfx_raycast_sdf_levels_tracked_h((int)n, d, nn, im, vbo ? vb : 0, vol.abi(), summary.get(), T_wc.m, k, near, far, trunc_dist,
+                                                    subpix ? 1 : 0, 0));
 }
 
 }

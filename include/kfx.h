@@ -434,8 +434,10 @@ int kfx_raycast_sdf_levels_tracked(int n_levels, const kfx_image* const* depth, 
 /* Recompute the summary from what the volume holds (one pass over the parent volume: 8 B x cells of reads): the way back to a
  * summary that describes the volume after writers that do not track (untracked kfx_sdf_fuse, copies, LoadPXM, kfx_sdf_sphere)
  * -- every brick gets the exact range of its valued cells and the exact state, instead of kfx_sdf_summary_invalidate's
- * "nothing is known".  fp32 cells. */
+ * "nothing is known".  fp32 and half cells (the summary knows which; half: 4 B x cells of reads). */
 int kfx_sdf_summary_rebuild(kfx_sdf_summary* s, kfx_stream stream);
+
+/* The same summary for half-cell volumes (roo::SDF_h): include/kfx_summary_h.h. */
 
 /* ---- one frame of the application's loop as ONE call (no reference counterpart in the operator API) ----------------
  * The per-frame sequence of applications/kinectfusion/main.cpp:200-356 for a stream with known poses, enqueued by the

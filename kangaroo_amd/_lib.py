@@ -145,6 +145,12 @@ SIGNATURES = {
     "kfx_sdf_fuse_tracked": (C.c_int, [PV, C.c_void_p, PI, PI, PF, PF, C.c_float, C.c_float, C.c_float, C.c_uint, C.c_void_p]),
     "kfx_raycast_sdf_tracked": (C.c_int, [PI, PI, PI, PV, C.c_void_p, PF, PF, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p]),
     "kfx_sdf_summary_rebuild": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "kfx_sdf_summary_create_h": (C.c_int, [C.POINTER(C.c_void_p), PV]),
+    "kfx_sdf_reset_tracked_h": (C.c_int, [PV, C.c_void_p, C.c_float, C.c_void_p]),
+    "kfx_sdf_fuse_tracked_h": (C.c_int, [PV, C.c_void_p, PI, PI, PF, PF, C.c_float, C.c_float, C.c_float, C.c_uint, C.c_void_p]),
+    "kfx_raycast_sdf_tracked_h": (C.c_int, [PI, PI, PI, PV, C.c_void_p, PF, PF, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p]),
+    "kfx_raycast_sdf_count_tracked_h": (C.c_int, [PV, C.c_void_p, C.c_uint, C.c_uint, PF, PF, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kfx_raycast_sdf_levels_tracked_h": (C.c_int, [C.c_int, C.POINTER(PI), C.POINTER(PI), C.POINTER(PI), C.POINTER(PI), PV, C.c_void_p, PF, PF, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p]),
     "kfx_raycast_sdf_count_tracked": (C.c_int, [PV, C.c_void_p, C.c_uint, C.c_uint, PF, PF, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kfx_frame_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(KfxFrameConfig)]),
     "kfx_frame_destroy": (C.c_int, [C.c_void_p]),

@@ -841,6 +841,8 @@ __global__ __launch_bounds__(64 * NW, (FAST && ZU == 2) ? 8 : (!FAST ? 6 : 1)) v
         // (the idiom of RayF32::issue / finish, sampling.h); tests/test_gpu_chain.py and test_gpu_summary.py compare the
         // tracked volume with the untracked one bit for bit, at sizes where all and where a quarter of the planes take this path.
         auto load_cells = [&](float4 (&c)[ZU], const bool (&any)[ZU], const unsigned char* at) {
+            // (half cells take the streamed loads on the keep planes too: the same asm for their 8-byte pairs left the fast tracked
+            // half kernels waiting for the previous iteration's stores inside the observation blocks, scripts/check_fuse_codegen.py)
             if constexpr (TRACK && FAST && CELL::BYTES == 8 && ZU <= 2) {   // (the bit-exact kernels are bound by issue, not by memory)
                 if (keep) { // uniform
                     v4f raw[ZU];
@@ -1846,6 +1848,8 @@ static int fuse_launch(const kfx_volume* vol, const kfx_image* depth, const kfx_
     FuseParams p;
     bool small_images = false;
     if (int e = fuse_params(p, &small_images, vol, depth, norm, T_cw, K, trunc_dist, max_w, mincostheta, flags, CELL::BYTES, slab)) return e;
+    if (summary && summary->cell_bytes != CELL::BYTES)
+        return set_error(KFX_E_SHAPE, "SdfFuse(tracked): the summary was created for the other cell type (kfx_sdf_summary_create / _create_h)");
     p.sum_R = nullptr;
     p.zoff_local = 0;
     bool track = false;
@@ -1867,7 +1871,7 @@ static int fuse_launch(const kfx_volume* vol, const kfx_image* depth, const kfx_
     // KFX_FUSE_CAP sets the LDS tile capacity in texels (16 B each, at most 3968)
     static const int tiled = [] { const char* e = getenv("KFX_FUSE_TILED"); return e ? atoi(e) : 1; }();
     static const int cap_env = [] { const char* e = getenv("KFX_FUSE_CAP"); const int v = e ? atoi(e) : 0; return v <= 0 ? 0 : (v < 64 ? 64 : (v > 3968 ? 3968 : v)); }();  // <= 62 KiB: dynamic + static LDS stay below the 64 KiB launch limit
-    if (summary && !(track && tiled && vec2 && small_images && CELL::BYTES == 8)) {
+    if (summary && !(track && tiled && vec2 && small_images)) {
         // this launch cannot keep the summary current (unaligned view, untiled kernel): nothing is known afterwards
         if (int e = kfx_sdf_summary_invalidate(summary, stream)) return e;
         track = false;
@@ -1971,15 +1975,13 @@ static int fuse_launch(const kfx_volume* vol, const kfx_image* depth, const kfx_
             q.zoff_local = z0;
             q.Z = z1 - z0;
             const size_t lds = (size_t)cap_px * sizeof(float4) * (plan.dxt ? 2 : 1);
-            if constexpr (CELL::BYTES == 8) {
-                if (track) { // the same kernels with the summary epilogue (ZU = 2 fast, 1 exact)
-                    const dim3 gw(ceil_div(q.X, TB_X), ceil_div(q.Y, TB_Y), ceil_div(q.Z, FUSE_ZC)), gn(ceil_div(q.X, 32), ceil_div(q.Y, 8), ceil_div(q.Z, 16));
-                    if (plan.small_brick && fast) hipLaunchKernelGGL((k_sdf_fuse_tiled<true, 2, CELL, 16, 2, 16, true>), gn, dim3(256), lds, s, q, cap_px);
-                    else if (plan.small_brick) hipLaunchKernelGGL((k_sdf_fuse_tiled<false, 1, CELL, 16, 2, 16, true>), gn, dim3(256), lds, s, q, cap_px);
-                    else if (fast) hipLaunchKernelGGL((k_sdf_fuse_tiled<true, 2, CELL, 32, 4, FUSE_ZC, true>), gw, dim3(256), lds, s, q, cap_px);
-                    else hipLaunchKernelGGL((k_sdf_fuse_tiled<false, 1, CELL, 32, 4, FUSE_ZC, true>), gw, dim3(256), lds, s, q, cap_px);
-                    continue;
-                }
+            if (track) { // the same kernels with the summary epilogue (ZU = 2 fast, 1 exact), fp32 and half cells
+                const dim3 gw(ceil_div(q.X, TB_X), ceil_div(q.Y, TB_Y), ceil_div(q.Z, FUSE_ZC)), gn(ceil_div(q.X, 32), ceil_div(q.Y, 8), ceil_div(q.Z, 16));
+                if (plan.small_brick && fast) hipLaunchKernelGGL((k_sdf_fuse_tiled<true, 2, CELL, 16, 2, 16, true>), gn, dim3(256), lds, s, q, cap_px);
+                else if (plan.small_brick) hipLaunchKernelGGL((k_sdf_fuse_tiled<false, 1, CELL, 16, 2, 16, true>), gn, dim3(256), lds, s, q, cap_px);
+                else if (fast) hipLaunchKernelGGL((k_sdf_fuse_tiled<true, 2, CELL, 32, 4, FUSE_ZC, true>), gw, dim3(256), lds, s, q, cap_px);
+                else hipLaunchKernelGGL((k_sdf_fuse_tiled<false, 1, CELL, 32, 4, FUSE_ZC, true>), gw, dim3(256), lds, s, q, cap_px);
+                continue;
             }
             if (plan.small_brick) {
                 dim3 grid(ceil_div(q.X, 32), ceil_div(q.Y, 8), ceil_div(q.Z, 16));
@@ -2075,6 +2077,14 @@ extern "C" int kfx_sdf_fuse_h(const kfx_volume* vol, const kfx_image* depth, con
                               float mincostheta, unsigned flags, kfx_stream stream)
 {
     return fuse_launch<CellF16>(vol, depth, norm, T_cw, K, trunc_dist, max_w, mincostheta, flags, stream);
+}
+
+extern "C" int kfx_sdf_fuse_tracked_h(const kfx_volume* vol, kfx_sdf_summary* summary, const kfx_image* depth, const kfx_image* norm,
+                                      const float T_cw[12], const float K[4], float trunc_dist, float max_w, float mincostheta,
+                                      unsigned flags, kfx_stream stream)
+{
+    if (!summary) return set_error(KFX_E_NULL, "kfx_sdf_fuse_tracked_h: null summary");
+    return fuse_launch<CellF16>(vol, depth, norm, T_cw, K, trunc_dist, max_w, mincostheta, flags, stream, nullptr, summary);
 }
 
 extern "C" int kfx_sdf_fuse_count(const kfx_volume* vol, const kfx_image* depth, const kfx_image* norm,

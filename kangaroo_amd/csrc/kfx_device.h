@@ -13,6 +13,7 @@
 
 #include "../../include/kfx.h"
 #include "../../include/kfx_extras.h"
+#include "../../include/kfx_summary_h.h"
 
 namespace kfx {
 
@@ -194,6 +195,7 @@ struct kfx_sdf_summary {
     float4* R;
     int nbx, nby, nbz;
     int w, h, d;                 // parent volume (cells)
+    int cell_bytes;              // 8: SDF_t cells (kfx_sdf_summary_create), 4: SDF_h cells (kfx_sdf_summary_create_h)
     const unsigned char* base;   // parent volume storage
     size_t pitch, img_pitch;
     // class tables of the march (ClassView below): two bit planes per entry, fine level (8^3 or 16^3 cells) then 32^3 cells
@@ -201,6 +203,7 @@ struct kfx_sdf_summary {
     int c_dirty;                 // R changed since C was built
     float c_tol, c_vref;         // what C was built with
     int c_shift;                 // fine level C was built for (log2 of its cells per entry)
+    int c_global;                // C also holds the 64^3- and 128^3-cell levels (the global-table mode, raycast.hip class_view)
     int n_coarse;                // 32^3-cell entries
     int* d_count;                // device: {running count of 32^3-cell entries of class != 0, workgroups that have added theirs}
     // The table builds publish their count of 32^3-cell entries of class != 0 in a host-visible ring (pinned, mapped): build b
@@ -241,6 +244,11 @@ struct ClassView {
     // cells), behind the staged words.  nx5 / nz5: entries of the 32^3-cell level along x / z (ny5 = coarse.ny); top_n: how
     // many coarser levels there are (0-2); lds_words: staged words + the derived levels.
     int nx5, nz5, top_n, lds_words;
+    // Global-table mode (class tables larger than the LDS budget, or KFX_RAYCAST_GLOBAL_TABLES=1): the table build also writes the
+    // 64^3- and 128^3-cell levels to global memory behind the 32^3-cell level (top_first); a workgroup stages only those two
+    // (stage_words from word top_first) and looks the fine and 32^3-cell levels up in global memory, coarse level first.
+    // LDS mode: the staged words are [0, words).
+    int global, top_first, stage_words;
 };
 // geometry of a level derived from a finer one with nx x ny x nz entries, placed at word `first`
 inline __host__ __device__ void class_level_up(const int nx, const int ny, const int nz, const int shift, const int first, ClassLevel& L, int& ux, int& uz, int& words)
@@ -249,8 +257,11 @@ inline __host__ __device__ void class_level_up(const int nx, const int ny, const
     L.shift = shift; L.ny = (ny + 1) >> 1; L.rw = 2 * ((ux + 31) >> 5); L.first = first;
     words = (L.rw * L.ny * uz + 3) & ~3;
 }
-int summary_classes_prepare(kfx_sdf_summary* s, float tol, float vref, int fine_shift, hipStream_t stream);
+// global = 1: also build the 64^3- and 128^3-cell levels in global memory (at word summary_top_first)
+int summary_classes_prepare(kfx_sdf_summary* s, float tol, float vref, int fine_shift, hipStream_t stream, int global = 0);
 void summary_class_layout(const kfx_sdf_summary* s, int fine_shift, ClassView& cv);
+// words of the table with the two derived levels behind the 32^3-cell level: first word of the 64^3 level, the two levels' words
+void summary_top_layout(const ClassView& cv, ClassLevel& l6, ClassLevel& l7, int& w6, int& w7);
 // cell offset of a view of the summary's parent volume (same pitches, pointer inside the parent): 0 on success
 int summary_view_offset(const kfx_sdf_summary* s, const kfx_volume* view, int* ox, int* oy, int* oz);
 } // namespace kfx

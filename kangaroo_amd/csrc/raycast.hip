@@ -156,7 +156,11 @@ __device__ __forceinline__ int class_lookup(const unsigned* tab, const ClassLeve
 // COUNT (kfx_raycast_sdf_count_tracked): the same march with every cell it reads marked in a bitmap and its samples, table
 // look-ups and hits counted in cnt[] = {samples, look-ups, hit, newly marked cells}; writes no image.
 __device__ __forceinline__ unsigned touch(unsigned* bitmap, const VolView& v, int x, int y, int z);
-template <typename CELL, bool COLOR, bool COUNT = false>
+// GT (global-table mode, ClassView::global): the fine and 32^3-cell levels are read from global memory (cl.C), the 64^3 and
+// 128^3 levels from LDS, and the levels are consulted coarse-first: a coarse entry of class != 0 implies that every entry below
+// it is != 0, so the coarsest level with class != 0 is the one the fine-first order of the LDS mode arrives at -- the same
+// runs, the same images -- and a ray in wide free space does not touch the global tables.
+template <typename CELL, bool COLOR, bool COUNT = false, bool GT = false>
 __device__ __forceinline__ float raycast_pixel_classes(const RayParams& p, const RayParams& q, const ColorGeom& cv, const int u, const int v, const ClassView& cl, const unsigned* tab,
                                                        const TopLevels& top, unsigned* bitmap = nullptr, unsigned* cnt = nullptr)
 {
@@ -204,10 +208,10 @@ __device__ __forceinline__ float raycast_pixel_classes(const RayParams& p, const
         while (lambda < min_tmax) {
             const bool look = consult && wait == 0 && lambda >= lam_retry;
             CellPos c{};
-            RayF32::InFlight fl;
+            typename CELL::InFlight fl;
             if (!look) {
                 c = cell_of(p, c_w + ray_w * lambda);
-                trilinear_issue(fl, p, c);
+                trilinear_issue<CELL>(fl, p, c);
                 if constexpr (COUNT) {
                     cnt[0] += 1;
                     for (int k = 0; k < 8; ++k) cnt[3] += touch(bitmap, p.vol, c.ix + (k & 1), c.iy + ((k >> 1) & 1), c.iz + (k >> 2));
@@ -223,9 +227,33 @@ __device__ __forceinline__ float raycast_pixel_classes(const RayParams& p, const
                 bool run = false;
                 if (fminf(fminf(ex, ey), ez) > eps && ex < p.dims1.x - eps && ey < p.dims1.y - eps && ez < p.dims1.z - eps && lo_f > eps && hi_f < 1.0f - eps) {
                     const int gx = (int)flx + cl.ox, gy = (int)fly + cl.oy, gz = (int)flz + cl.oz;
+                    int cls = 0, shift = cl.fine.shift;
+                    if constexpr (GT) {
+                        // coarse-first: 128^3 and 64^3 cells (LDS), then 32^3 cells and the fine level (global, uint2 loads)
+                        if (cl.top_n > 1) {
+                            int c7 = class_lookup(tab, top.lv[1], gx, gy, gz);
+                            if (c7 == 3 && !cl.amb_ok) c7 = 0;
+                            if (c7 != 0) { cls = c7; shift = 7; }
+                        }
+                        if (cls == 0 && cl.top_n > 0) {
+                            int c6 = class_lookup(tab, top.lv[0], gx, gy, gz);
+                            if (c6 == 3 && !cl.amb_ok) c6 = 0;
+                            if (c6 != 0) { cls = c6; shift = 6; }
+                        }
+                        if (cls == 0) {
+                            int c5 = class_lookup(cl.C, cl.coarse, gx, gy, gz);
+                            if (c5 == 3 && !cl.amb_ok) c5 = 0;
+                            if (c5 != 0) { cls = c5; shift = 5; }
+                        }
+                        if (cls == 0) {
+                            cls = class_lookup(cl.C, cl.fine, gx, gy, gz);
+                            if (cls == 3 && !cl.amb_ok) cls = 0;
+                            shift = cl.fine.shift;
+                        }
+                    } else {
                     // the fine level answers "sample here?"; only a positive answer is worth the second look that may extend
                     // the run to the whole 32^3-cell entry
-                    int cls = class_lookup(tab, cl.fine, gx, gy, gz), shift = cl.fine.shift;
+                    cls = class_lookup(tab, cl.fine, gx, gy, gz);
                     if (cls == 3 && !cl.amb_ok) cls = 0;
                     if (cls != 0 && cl.fine.shift < 5) {
                         int c5 = class_lookup(tab, cl.coarse, gx, gy, gz);
@@ -246,6 +274,7 @@ __device__ __forceinline__ float raycast_pixel_classes(const RayParams& p, const
                             }
                         }
                     }
+                    }
                     // the entry's cells are [lo, lo + L) per axis in the view's coordinates; its far side along the ray, pulled in
                     // by the margin: positions up to there certainly have their base cell in the entry
                     const float L = (float)(1 << shift);
@@ -259,7 +288,9 @@ __device__ __forceinline__ float raycast_pixel_classes(const RayParams& p, const
                         // this position and from the following ones that still start inside the entry (and the box): n steps,
                         // n - 1 <= (lam_last - lambda) / delta less a hundredth for the quotient's rounding
                         delta = cls == 1 ? step_free : p.trunc;
-                        pending = cls == 3;
+                        // (half cells, fast numerics: the band is wide enough to take cells just inside the truncation band in
+                        // front of a surface, so a crossing right after a class-1 run settles last_sdf with one sample too)
+                        pending = cls == 3 || (CELL::BYTES == 4 && cls == 1 && cl.tol > 0.f);
                         last_sdf = cls == 1 ? cl.vref : __builtin_nanf("");
                         const float lam_last = fminf(lam_exit, min_tmax);
                         const float more = fminf(floorf((lam_last - lambda) * (cls == 1 ? inv_step_free : inv_trunc) - 0.01f), 4096.f);
@@ -287,7 +318,7 @@ __device__ __forceinline__ float raycast_pixel_classes(const RayParams& p, const
                 }
             }
             if (!look) {
-                const float sdf = trilinear_finish(fl, c);
+                const float sdf = trilinear_finish<CELL>(fl, c);
                 wait = max(wait - 1, 0);
                 if (sdf <= 0) {
                     // a crossing needs the previous sample's value: the one thing a class-3 step left open
@@ -396,18 +427,21 @@ __device__ __forceinline__ void classes_level_up(unsigned* tab, const ClassLevel
 
 // workgroup prologue of the class-table kernels: the tables into LDS (16-byte loads, all in flight together), then the
 // coarser levels derived from the 32^3-cell level
+// (GT: only the 64^3- and 128^3-cell levels, which the table build wrote to global memory, staged at word 0)
+template <bool GT = false>
 __device__ __forceinline__ void classes_stage(const ClassView& cl, unsigned* tab, TopLevels& top)
 {
-    const uint4* src = reinterpret_cast<const uint4*>(cl.C);
+    const uint4* src = reinterpret_cast<const uint4*>(cl.C + (GT ? cl.top_first : 0));
     uint4* dst = reinterpret_cast<uint4*>(tab);
-    for (int i = threadIdx.x; i < (cl.words >> 2); i += blockDim.x) dst[i] = src[i];
+    for (int i = threadIdx.x; i < (cl.stage_words >> 2); i += blockDim.x) dst[i] = src[i];
     ClassLevel l6, l7;
     int nx6, nz6, nx7, nz7, w6, w7;
-    class_level_up(cl.nx5, cl.coarse.ny, cl.nz5, 6, cl.words, l6, nx6, nz6, w6);
-    class_level_up(nx6, l6.ny, nz6, 7, cl.words + w6, l7, nx7, nz7, w7);
+    const int at = GT ? 0 : cl.words;
+    class_level_up(cl.nx5, cl.coarse.ny, cl.nz5, 6, at, l6, nx6, nz6, w6);
+    class_level_up(nx6, l6.ny, nz6, 7, at + w6, l7, nx7, nz7, w7);
     if (threadIdx.x == 0) { top.lv[0] = l6; top.lv[1] = l7; top.n = cl.top_n; }
     __syncthreads();
-    if (cl.top_n > 0) {   // launch-uniform
+    if (!GT && cl.top_n > 0) {   // launch-uniform
         classes_level_up(tab, cl.coarse, cl.nx5, cl.nz5, l6, nx6, nz6);
         __syncthreads();
         if (cl.top_n > 1) {
@@ -417,14 +451,14 @@ __device__ __forceinline__ void classes_stage(const ClassView& cl, unsigned* tab
     }
 }
 
-template <typename CELL>
+template <typename CELL, bool GT = false>
 __global__ __launch_bounds__(256) void k_raycast_sdf_classes(const RayParams p, const ClassView cl)
 {
     extern __shared__ unsigned s_tab[];
     __shared__ RayParams s_p;
     __shared__ TopLevels s_top;
     if (threadIdx.x == 0) s_p = p;
-    classes_stage(cl, s_tab, s_top);   // (barriers inside)
+    classes_stage<GT>(cl, s_tab, s_top);   // (barriers inside)
     int u, v;
     if (p.sparse_lanes) {
         const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -434,7 +468,7 @@ __global__ __launch_bounds__(256) void k_raycast_sdf_classes(const RayParams p, 
     } else {
         ray_pixel_of(p, blockIdx.x, blockIdx.y, threadIdx.x, u, v);
     }
-    raycast_pixel_classes<CELL, false>(p, s_p, ColorGeom{}, u, v, cl, s_tab, s_top);
+    raycast_pixel_classes<CELL, false, false, GT>(p, s_p, ColorGeom{}, u, v, cl, s_tab, s_top);
 }
 
 template <typename CELL, bool COLOR>
@@ -526,7 +560,7 @@ __global__ __launch_bounds__(256) void k_raycast_sdf_count(const RayParams p, un
 }
 
 // the same for the march through the class tables: counters = {samples, rays that enter the box, hits, U, table look-ups, table bytes}
-template <typename CELL>
+template <typename CELL, bool GT = false>
 __global__ __launch_bounds__(256) void k_raycast_sdf_classes_count(const RayParams p, const ClassView cl, unsigned* __restrict__ bitmap,
                                                                    unsigned long long* __restrict__ counters)
 {
@@ -534,7 +568,7 @@ __global__ __launch_bounds__(256) void k_raycast_sdf_classes_count(const RayPara
     __shared__ RayParams s_p;
     __shared__ TopLevels s_top;
     if (threadIdx.x == 0) s_p = p;
-    classes_stage(cl, s_tab, s_top);   // (barriers inside)
+    classes_stage<GT>(cl, s_tab, s_top);   // (barriers inside)
     int u, v;
     ray_pixel_of(p, blockIdx.x, blockIdx.y, threadIdx.x, u, v);
     unsigned cnt[4] = {0u, 0u, 0u, 0u}, entered = 0;
@@ -547,7 +581,7 @@ __global__ __launch_bounds__(256) void k_raycast_sdf_classes_count(const RayPara
         const V3 tmin = v3(fminf(ta.x, tb.x), fminf(ta.y, tb.y), fminf(ta.z, tb.z));
         const V3 tmax = v3(fmaxf(ta.x, tb.x), fmaxf(ta.y, tb.y), fmaxf(ta.z, tb.z));
         entered = fmaxf(fmaxf(fmaxf(tmin.x, tmin.y), tmin.z), p.near) < fminf(fminf(fminf(tmax.x, tmax.y), tmax.z), p.far) ? 1u : 0u;
-        raycast_pixel_classes<CELL, false, true>(p, s_p, ColorGeom{}, u, v, cl, s_tab, s_top, bitmap, cnt);
+        raycast_pixel_classes<CELL, false, true, GT>(p, s_p, ColorGeom{}, u, v, cl, s_tab, s_top, bitmap, cnt);
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -562,7 +596,7 @@ __global__ __launch_bounds__(256) void k_raycast_sdf_classes_count(const RayPara
         if (cnt[3]) atomicAdd(&counters[3], (unsigned long long)cnt[3]);
         if (cnt[1]) atomicAdd(&counters[4], (unsigned long long)cnt[1]);
     }
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(&counters[5], (unsigned long long)cl.words * 4ull);
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(&counters[5], (unsigned long long)cl.stage_words * 4ull);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -876,20 +910,64 @@ static int ray_params(RayParams& p, const kfx_image* depth, const kfx_image* nor
 // The class-table march's view of a summary for a launch on `vol` with camera T_wc: brings the tables up to date on `stream`,
 // evaluates the margin that covers the affine cell estimate, reports the LDS bytes.  *usable = 0: march plainly (the margin
 // would be too wide, or trunc is not positive).
-static int class_view(ClassView& cl, size_t* lds_bytes, int* usable, kfx_sdf_summary* summary, const kfx_volume* vol, const RayParams& p, kfx_stream stream)
+// Half cells (SDF_h): class 1 means "every cell holds vref = trunc rounded to half" -- what the plain march samples in untouched
+// free space -- and the fast-numerics band is KFX_SUMMARY_HALF_BAND (include/kfx.h) instead of 1e-5.
+// Tables larger than the LDS budget (fp32 or half cells at ~2000^3), or KFX_RAYCAST_GLOBAL_TABLES=1: the global-table mode
+// (ClassView::global): a 16^3-cell fine level, the 32^3-cell level and the two derived levels in global memory, the latter two
+// staged.  The levels march (RaycastSdfLevels) runs the plain march in that mode (*usable = 2: the caller decides).
+// allow_global = false (the levels call, which has no global-table kernel): where the global-table mode would be needed, return
+// unusable before any table is built and before the plain / table choice is touched.
+template <typename CELL>
+static int class_view(ClassView& cl, size_t* lds_bytes, int* usable, kfx_sdf_summary* summary, const kfx_volume* vol, const RayParams& p, kfx_stream stream,
+                      bool allow_global = true)
 {
     *usable = 0;
     if (int e = summary_view_offset(summary, vol, &cl.ox, &cl.oy, &cl.oz)) return e;
     if (!(p.trunc > 0.f) || !(p.trunc < __builtin_inff())) return 0;
     static const int kb_env = [] { const char* e = getenv("KFX_RAYCAST_CLASS_KB"); const int v = e ? atoi(e) : 16; return v < 1 ? 1 : (v > 60 ? 60 : v); }();
+    static const int gt_env = [] { const char* e = getenv("KFX_RAYCAST_GLOBAL_TABLES"); return e ? atoi(e) : 0; }();
+    static const int top_env = [] { const char* e = getenv("KFX_RAYCAST_TOP_LEVELS"); const int v = e ? atoi(e) : 2; return v < 0 ? 0 : (v > 2 ? 2 : v); }();
     int fine = 3;
     for (; fine < 5; ++fine) {
         summary_class_layout(summary, fine, cl);
         if ((size_t)cl.words * 4 <= (size_t)kb_env * 1024) break;
     }
-    summary_class_layout(summary, fine, cl);
-    if ((size_t)cl.words * 4 > 60 * 1024) return 0;
-    const float tol = math_mode() == KFX_MATH_FAST ? 1e-5f : 0.f;
+    // the coarser levels (64^3 cells where the 32^3-cell level has more than one entry along some axis, 128^3 cells likewise on
+    // top of that): derived in LDS by every workgroup (classes_stage), or -- global-table mode -- built in global memory
+    auto top_levels = [&](int& w6, int& w7) {
+        summary_class_layout(summary, fine, cl);
+        cl.nx5 = ceil_div(summary->w, 32); cl.nz5 = ceil_div(summary->d, 32);
+        ClassLevel l6, l7;
+        summary_top_layout(cl, l6, l7, w6, w7);
+        const int nx6 = (cl.nx5 + 1) >> 1, nz6 = (cl.nz5 + 1) >> 1;
+        cl.top_n = 0;
+        if (cl.nx5 > 1 || cl.coarse.ny > 1 || cl.nz5 > 1) cl.top_n = 1;
+        if (cl.top_n && (nx6 > 1 || l6.ny > 1 || nz6 > 1)) cl.top_n = 2;
+        if (cl.top_n > top_env) cl.top_n = top_env;
+    };
+    int w6, w7;
+    top_levels(w6, w7);
+    // the launch asks for the staged tables PLUS the derived levels PLUS the kernels' static LDS (RayParams, TopLevels, the
+    // levels kernel's table): the whole must stay below the 64 KiB a launch may have (round-4 advice)
+    const size_t lds_static = sizeof(RayParams) + sizeof(TopLevels) + 2048;
+    const int derived = (cl.top_n > 0 ? w6 : 0) + (cl.top_n > 1 ? w7 : 0);
+    cl.global = gt_env > 0 || (size_t)cl.words * 4 > 60 * 1024 || (size_t)(cl.words + derived) * 4 + lds_static > 64 * 1024;
+    if (cl.global) {
+        fine = 4;
+        top_levels(w6, w7);
+        cl.top_first = cl.words;
+        cl.stage_words = (cl.top_n > 0 ? w6 : 0) + (cl.top_n > 1 ? w7 : 0);
+        cl.lds_words = cl.stage_words;
+        if ((size_t)cl.lds_words * 4 + lds_static > 64 * 1024) return 0;
+    } else {
+        cl.top_first = 0;
+        cl.stage_words = cl.words;
+        cl.lds_words = cl.words + derived;
+    }
+    if (cl.global && !allow_global) return 0;
+    const bool half = CELL::BYTES == 4;
+    const float vref = half ? __half2float(__float2half_rn(p.trunc)) : p.trunc;
+    const float tol = math_mode() == KFX_MATH_FAST ? (half ? KFX_SUMMARY_HALF_BAND : 1e-5f) : 0.f;
     // Worth it?  The march through the tables costs ~8 % per sampled step (table look-ups, staging); it pays where a fair part
     // of the volume can be crossed without sampling: at least a quarter of the 32^3-cell entries of class != 0.  Every table
     // build publishes that count in a host-visible ring; the choice is made from the count of the build BEFORE THE PREVIOUS ONE
@@ -902,7 +980,7 @@ static int class_view(ClassView& cl, size_t* lds_bytes, int* usable, kfx_sdf_sum
     if (force_env < 0) return 0;
     const bool steer = force_env == 0 && summary->h_skippable;
     if (steer && summary->plain_calls && (summary->plain_calls++ % 8u) != 0u) return 0;   // still plain: no build, no look
-    if (int e = summary_classes_prepare(summary, tol, p.trunc, fine, (hipStream_t)stream)) return e;
+    if (int e = summary_classes_prepare(summary, tol, vref, fine, (hipStream_t)stream, cl.global)) return e;
     if (steer && summary->builds >= 3) {
         const unsigned ref = (summary->builds - 3) % KFX_SUMMARY_RING;   // builds - 1 is the one just issued (or the last one)
         (void)hipEventSynchronize(summary->build_done[ref]);
@@ -914,8 +992,10 @@ static int class_view(ClassView& cl, size_t* lds_bytes, int* usable, kfx_sdf_sum
         summary->plain_calls = 0;
     }
     cl.C = summary->C;
-    cl.vref = p.trunc;
-    cl.amb_ok = p.trunc >= p.voxel.x ? 1 : 0;   // class 3 needs equal steps for a vref and a NaN sample: max(trunc, min_delta) = trunc
+    cl.vref = vref;
+    // class 3 needs equal steps for a vref and a NaN sample: max(vref, min_delta) = trunc (fp32: trunc >= min_delta; half cells
+    // only where trunc is a half value)
+    cl.amb_ok = fmaxf(vref, p.voxel.x) == p.trunc ? 1 : 0;
     cl.tol = tol;
     // margin: |cell_of()'s coordinate - the affine estimate| per axis, from the roundings of both (u = 2^-24):
     //   cell_of:   pos = c + ray lambda (2 roundings of magnitudes <= |pos| + |c|), - bmin, / size, * dims1
@@ -938,24 +1018,7 @@ static int class_view(ClassView& cl, size_t* lds_bytes, int* usable, kfx_sdf_sum
     eps *= 2.0;   // twice the bound
     if (!(eps < 0.05)) return 0;
     cl.eps = (float)std::fmax(eps, 1e-4);
-    // the coarser levels every workgroup derives in LDS (classes_stage): 64^3 cells where the 32^3-cell level has more than one
-    // entry along some axis, 128^3 cells likewise on top of that
-    cl.nx5 = ceil_div(summary->w, 32); cl.nz5 = ceil_div(summary->d, 32);
-    static const int top_env = [] { const char* e = getenv("KFX_RAYCAST_TOP_LEVELS"); const int v = e ? atoi(e) : 2; return v < 0 ? 0 : (v > 2 ? 2 : v); }();
-    ClassLevel l6, l7;
-    int nx6, nz6, nx7, nz7, w6, w7;
-    class_level_up(cl.nx5, cl.coarse.ny, cl.nz5, 6, cl.words, l6, nx6, nz6, w6);
-    class_level_up(nx6, l6.ny, nz6, 7, cl.words + w6, l7, nx7, nz7, w7);
-    cl.top_n = 0;
-    if (cl.nx5 > 1 || cl.coarse.ny > 1 || cl.nz5 > 1) cl.top_n = 1;
-    if (cl.top_n && (nx6 > 1 || l6.ny > 1 || nz6 > 1)) cl.top_n = 2;
-    if (cl.top_n > top_env) cl.top_n = top_env;
-    cl.lds_words = cl.words + (cl.top_n > 0 ? w6 : 0) + (cl.top_n > 1 ? w7 : 0);
     *lds_bytes = (size_t)cl.lds_words * sizeof(unsigned);
-    // the launch asks for the staged tables PLUS the derived levels PLUS the kernels' static LDS (RayParams, TopLevels, the
-    // levels kernel's table): the whole must stay below the 64 KiB a launch may have, or the launch fails where the plain march
-    // would have worked (round-4 advice: the 60 KiB test above sees the staged words only)
-    if (*lds_bytes + sizeof(RayParams) + sizeof(TopLevels) + 2048 > 64 * 1024) return 0;
     *usable = 1;
     return 0;
 }
@@ -996,19 +1059,17 @@ static int raycast_levels_launch(int n_levels, const kfx_image* const* depth, co
         blocks += lv.blocks_x * (lv.sparse ? ceil_div(p.h, 2) : ceil_div(p.h, 4));
         base = p;
     }
+    if (summary && summary->cell_bytes != CELL::BYTES)
+        return set_error(KFX_E_SHAPE, "RaycastSdf(levels, tracked): the summary was created for the other cell type (kfx_sdf_summary_create / _create_h)");
     if (L.n == 0) return 0;
     if (summary) {
-        if constexpr (CELL::BYTES == 8) {
-            ClassView cl;
-            size_t cl_bytes = 0;
-            int usable = 0;
-            if (int e = class_view(cl, &cl_bytes, &usable, summary, vol, base, stream)) return e;
-            if (usable) {
-                hipLaunchKernelGGL((k_raycast_sdf_levels_classes<CELL>), dim3(blocks), dim3(256), cl_bytes, (hipStream_t)stream, base, L, cl);
-                return check_launch("kfx_raycast_sdf_levels_tracked");
-            }
-        } else {
-            return set_error(KFX_E_RANGE, "kfx_raycast_sdf_levels_tracked: fp32 cells only");
+        ClassView cl;
+        size_t cl_bytes = 0;
+        int usable = 0;
+        if (int e = class_view<CELL>(cl, &cl_bytes, &usable, summary, vol, base, stream, false)) return e;
+        if (usable) {   // (the global-table mode has no levels kernel: class_view said unusable, the plain march below)
+            hipLaunchKernelGGL((k_raycast_sdf_levels_classes<CELL>), dim3(blocks), dim3(256), cl_bytes, (hipStream_t)stream, base, L, cl);
+            return check_launch("kfx_raycast_sdf_levels_tracked");
         }
     }
     hipLaunchKernelGGL((k_raycast_sdf_levels<CELL>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, base, L);
@@ -1023,6 +1084,8 @@ static int raycast_launch(const kfx_image* depth, const kfx_image* norm, const k
 {
     RayParams p;
     if (int e = ray_params<CELL>(p, depth, norm, img, vol, T_wc, K, near, far, trunc_dist, subpix)) return e;
+    if (summary && summary->cell_bytes != CELL::BYTES)
+        return set_error(KFX_E_SHAPE, "RaycastSdf(tracked): the summary was created for the other cell type (kfx_sdf_summary_create / _create_h)");
     if (p.w == 0 || p.h == 0) return 0;
 
     static const int tile_env = [] { const char* e = getenv("KFX_RAYCAST_TILE"); const int v = e ? atoi(e) : 5; return v < 0 ? 0 : (v > 6 ? 6 : v); }();
@@ -1047,17 +1110,14 @@ static int raycast_launch(const kfx_image* depth, const kfx_image* norm, const k
         set_geometry(cv, colorvol);
         hipLaunchKernelGGL((k_raycast_sdf<CELL, true>), grid, dim3(256), 0, (hipStream_t)stream, p, cv);
     } else if (summary) {
-        if constexpr (CELL::BYTES == 8) {
-            ClassView cl;
-            size_t cl_bytes = 0;
-            int usable = 0;
-            if (int e = class_view(cl, &cl_bytes, &usable, summary, vol, p, stream)) return e;
-            if (usable) hipLaunchKernelGGL((k_raycast_sdf_classes<CELL>), grid, dim3(256), cl_bytes, (hipStream_t)stream, p, cl);
-            else hipLaunchKernelGGL((k_raycast_sdf<CELL, false>), grid, dim3(256), 0, (hipStream_t)stream, p, cv);
-            return check_launch("kfx_raycast_sdf_tracked");
-        } else {
-            return set_error(KFX_E_RANGE, "kfx_raycast_sdf_tracked: fp32 cells only");
-        }
+        ClassView cl;
+        size_t cl_bytes = 0;
+        int usable = 0;
+        if (int e = class_view<CELL>(cl, &cl_bytes, &usable, summary, vol, p, stream)) return e;
+        if (usable && cl.global) hipLaunchKernelGGL((k_raycast_sdf_classes<CELL, true>), grid, dim3(256), cl_bytes, (hipStream_t)stream, p, cl);
+        else if (usable) hipLaunchKernelGGL((k_raycast_sdf_classes<CELL>), grid, dim3(256), cl_bytes, (hipStream_t)stream, p, cl);
+        else hipLaunchKernelGGL((k_raycast_sdf<CELL, false>), grid, dim3(256), 0, (hipStream_t)stream, p, cv);
+        return check_launch("kfx_raycast_sdf_tracked");
     } else {
         hipLaunchKernelGGL((k_raycast_sdf<CELL, false>), grid, dim3(256), 0, (hipStream_t)stream, p, cv);
     }
@@ -1098,14 +1158,17 @@ extern "C" int kfx_raycast_sdf_count_h(const kfx_volume* vol, unsigned w, unsign
     return raycast_count_launch<RayF16>(vol, w, h, T_wc, K, near, far, trunc_dist, subpix, d_bitmap, d_counters, stream);
 }
 
-extern "C" int kfx_raycast_sdf_count_tracked(const kfx_volume* vol, kfx_sdf_summary* summary, unsigned w, unsigned h, const float T_wc[12], const float K[4],
-                                             float near, float far, float trunc_dist, int subpix, unsigned* d_bitmap, unsigned long long* d_counters,
-                                             kfx_stream stream)
+template <typename CELL>
+static int raycast_count_tracked_launch(const kfx_volume* vol, kfx_sdf_summary* summary, unsigned w, unsigned h, const float T_wc[12], const float K[4],
+                                        float near, float far, float trunc_dist, int subpix, unsigned* d_bitmap, unsigned long long* d_counters,
+                                        kfx_stream stream)
 {
     if (!d_bitmap || !d_counters || !summary) return set_error(KFX_E_NULL, "kfx_raycast_sdf_count_tracked: null argument");
     kfx_image dummy = {(size_t)w * 16, (void*)(uintptr_t)16, w, h};
     RayParams p;
-    if (int e = ray_params<RayF32>(p, &dummy, &dummy, &dummy, vol, T_wc, K, near, far, trunc_dist, subpix)) return e;
+    if (int e = ray_params<CELL>(p, &dummy, &dummy, &dummy, vol, T_wc, K, near, far, trunc_dist, subpix)) return e;
+    if (summary->cell_bytes != CELL::BYTES)
+        return set_error(KFX_E_SHAPE, "kfx_raycast_sdf_count_tracked: the summary was created for the other cell type (kfx_sdf_summary_create / _create_h)");
     if (p.w == 0 || p.h == 0) return 0;
     p.dptr = p.nptr = p.iptr = nullptr;
     ClassView cl;
@@ -1114,13 +1177,29 @@ extern "C" int kfx_raycast_sdf_count_tracked(const kfx_volume* vol, kfx_sdf_summ
     // a diagnostics call must not steer the calls that follow: class_view() advances the plain / table choice's call counter
     // (the tables it may build are a pure function of the summary: harmless)
     const unsigned plain_calls = summary->plain_calls;
-    const int ce = class_view(cl, &cl_bytes, &usable, summary, vol, p, stream);
+    const int ce = class_view<CELL>(cl, &cl_bytes, &usable, summary, vol, p, stream);
     summary->plain_calls = plain_calls;
     if (ce) return ce;
     const dim3 grid(ceil_div(p.w, 64), ceil_div(p.h, 4));
-    if (usable) hipLaunchKernelGGL(k_raycast_sdf_classes_count<RayF32>, grid, dim3(256), cl_bytes, (hipStream_t)stream, p, cl, d_bitmap, d_counters);
-    else hipLaunchKernelGGL(k_raycast_sdf_count<RayF32>, grid, dim3(256), 0, (hipStream_t)stream, p, d_bitmap, d_counters);   // what the tracked call would launch
+    if (usable && cl.global) hipLaunchKernelGGL((k_raycast_sdf_classes_count<CELL, true>), grid, dim3(256), cl_bytes, (hipStream_t)stream, p, cl, d_bitmap, d_counters);
+    else if (usable) hipLaunchKernelGGL((k_raycast_sdf_classes_count<CELL>), grid, dim3(256), cl_bytes, (hipStream_t)stream, p, cl, d_bitmap, d_counters);
+    else hipLaunchKernelGGL(k_raycast_sdf_count<CELL>, grid, dim3(256), 0, (hipStream_t)stream, p, d_bitmap, d_counters);   // what the tracked call would launch
     return check_launch("kfx_raycast_sdf_count_tracked");
+}
+
+extern "C" int kfx_raycast_sdf_count_tracked(const kfx_volume* vol, kfx_sdf_summary* summary, unsigned w, unsigned h, const float T_wc[12], const float K[4],
+                                             float near, float far, float trunc_dist, int subpix, unsigned* d_bitmap, unsigned long long* d_counters,
+                                             kfx_stream stream)
+{
+    return raycast_count_tracked_launch<RayF32>(vol, summary, w, h, T_wc, K, near, far, trunc_dist, subpix, d_bitmap, d_counters, stream);
+}
+
+extern "C" int kfx_raycast_sdf_count_tracked_h(const kfx_volume* vol, kfx_sdf_summary* summary, unsigned w, unsigned h, const float T_wc[12], const float K[4],
+                                               float near, float far, float trunc_dist, int subpix, unsigned* d_bitmap, unsigned long long* d_counters,
+                                               kfx_stream stream)
+{
+    if (!d_bitmap || !d_counters || !summary) return set_error(KFX_E_NULL, "kfx_raycast_sdf_count_tracked_h: null argument");
+    return raycast_count_tracked_launch<RayF16>(vol, summary, w, h, T_wc, K, near, far, trunc_dist, subpix, d_bitmap, d_counters, stream);
 }
 
 extern "C" int kfx_raycast_sdf_tracked(const kfx_image* depth, const kfx_image* norm, const kfx_image* img, const kfx_volume* vol,
@@ -1129,6 +1208,14 @@ extern "C" int kfx_raycast_sdf_tracked(const kfx_image* depth, const kfx_image* 
 {
     if (!summary) return set_error(KFX_E_NULL, "kfx_raycast_sdf_tracked: null summary");
     return raycast_launch<RayF32>(depth, norm, img, vol, T_wc, K, near, far, trunc_dist, subpix, stream, nullptr, summary);
+}
+
+extern "C" int kfx_raycast_sdf_tracked_h(const kfx_image* depth, const kfx_image* norm, const kfx_image* img, const kfx_volume* vol,
+                                         kfx_sdf_summary* summary, const float T_wc[12], const float K[4], float near, float far,
+                                         float trunc_dist, int subpix, kfx_stream stream)
+{
+    if (!summary) return set_error(KFX_E_NULL, "kfx_raycast_sdf_tracked_h: null summary");
+    return raycast_launch<RayF16>(depth, norm, img, vol, T_wc, K, near, far, trunc_dist, subpix, stream, nullptr, summary);
 }
 
 extern "C" int kfx_raycast_sdf_h(const kfx_image* depth, const kfx_image* norm, const kfx_image* img,
@@ -1159,6 +1246,14 @@ extern "C" int kfx_raycast_sdf_levels_h(int n_levels, const kfx_image* const* de
                                       float trunc_dist, int subpix, kfx_stream stream)
 {
     return raycast_levels_launch<RayF16>(n_levels, depth, norm, img, vbo, vol, T_wc, K, near, far, trunc_dist, subpix, stream);
+}
+
+extern "C" int kfx_raycast_sdf_levels_tracked_h(int n_levels, const kfx_image* const* depth, const kfx_image* const* norm, const kfx_image* const* img,
+                                                const kfx_image* const* vbo, const kfx_volume* vol, kfx_sdf_summary* summary, const float T_wc[12],
+                                                const float* K, float near, float far, float trunc_dist, int subpix, kfx_stream stream)
+{
+    if (!summary) return set_error(KFX_E_NULL, "kfx_raycast_sdf_levels_tracked_h: null summary");
+    return raycast_levels_launch<RayF16>(n_levels, depth, norm, img, vbo, vol, T_wc, K, near, far, trunc_dist, subpix, stream, summary);
 }
 
 extern "C" int kfx_raycast_sdf_color(const kfx_image* depth, const kfx_image* norm, const kfx_image* img, const kfx_volume* vol,

@@ -5,6 +5,8 @@
 #include <algorithm>
 #include <new>
 
+#include <hip/hip_fp16.h>
+
 #include "kfx_device.h"
 
 namespace kfx {
@@ -154,6 +156,9 @@ __global__ __launch_bounds__(256) void k_summary_classes_coarse(const ClassBuild
 // 16-byte loads: 64 contiguous bytes), keeps the range of the values and whether it saw a NaN / a value; DPP and permlane swaps
 // reduce the wave.  The states are the TRACK kernels' (kfx_device.h): 0 every cell valued, 1 every cell NaN, 2 both kinds --
 // with the exact range of the valued cells in every case, which is at least as tight as what tracking arrives at.
+// BYTES = 4 (SDF_h cells): a lane's row of eight half cells is 32 contiguous bytes, two 16-byte loads of {val, w} pairs; the
+// range is kept in fp32, where every half value is exact.
+template <int BYTES>
 __global__ __launch_bounds__(256) void k_summary_rebuild(float4* __restrict__ R, const unsigned char* __restrict__ base, size_t pitch, size_t img_pitch,
                                                          int w, int h, int d, int nbx, int nby, int nbz, int aligned16)
 {
@@ -165,8 +170,24 @@ __global__ __launch_bounds__(256) void k_summary_rebuild(float4* __restrict__ R,
     float lo = __builtin_inff(), hi = -__builtin_inff();
     bool nan = false, val = false;
     if (y < h && z < d) {
-        const unsigned char* row = base + (size_t)z * img_pitch + (size_t)y * pitch + (size_t)x0 * 8;
-        if (x0 + 8 <= w && aligned16) {
+        const unsigned char* row = base + (size_t)z * img_pitch + (size_t)y * pitch + (size_t)x0 * BYTES;
+        if (BYTES == 4 && x0 + 8 <= w && aligned16) {
+            uint4 c[2];
+#pragma unroll
+            for (int k = 0; k < 2; ++k) c[k] = reinterpret_cast<const uint4*>(row)[k];   // {cell, cell, cell, cell}, half {val, w} each
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const unsigned u[4] = {c[k].x, c[k].y, c[k].z, c[k].w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float a = __half2float(__ushort_as_half((unsigned short)(u[j] & 0xffffu)));
+                    nan = nan || a != a;
+                    val = val || a == a;
+                    lo = fminf(lo, a);
+                    hi = fmaxf(hi, a);
+                }
+            }
+        } else if (BYTES == 8 && x0 + 8 <= w && aligned16) {
             float4 c[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) c[k] = reinterpret_cast<const float4*>(row)[k];   // {val, w, val, w}
@@ -181,7 +202,8 @@ __global__ __launch_bounds__(256) void k_summary_rebuild(float4* __restrict__ R,
         } else {
             const int x1 = x0 + 8 < w ? x0 + 8 : w;   // this brick's eight cells (fewer in the volume's last brick)
             for (int x = x0; x < x1; ++x) {
-                const float a = *reinterpret_cast<const float*>(row + (size_t)(x - x0) * 8);
+                const float a = BYTES == 8 ? *reinterpret_cast<const float*>(row + (size_t)(x - x0) * 8)
+                                           : __half2float(__ushort_as_half(*reinterpret_cast<const unsigned short*>(row + (size_t)(x - x0) * 4)));
                 nan = nan || a != a;
                 val = val || a == a;
                 lo = fminf(lo, a);
@@ -219,13 +241,41 @@ void summary_class_layout(const kfx_sdf_summary* s, int fine_shift, ClassView& c
     cv.words = cv.coarse.first + ((class_level_words(cv.coarse, s->d) + 3) & ~3);
 }
 
-int summary_classes_prepare(kfx_sdf_summary* s, float tol, float vref, int fine_shift, hipStream_t stream)
+void summary_top_layout(const ClassView& cv, ClassLevel& l6, ClassLevel& l7, int& w6, int& w7)
 {
-    if (!s->c_dirty && s->c_tol == tol && s->c_vref == vref && s->c_shift == fine_shift) return 0;
+    int nx6, nz6, nx7, nz7;
+    class_level_up(cv.nx5, cv.coarse.ny, cv.nz5, 6, cv.words, l6, nx6, nz6, w6);
+    class_level_up(nx6, l6.ny, nz6, 7, cv.words + w6, l7, nx7, nz7, w7);
+}
+
+int summary_classes_prepare(kfx_sdf_summary* s, float tol, float vref, int fine_shift, hipStream_t stream, int global)
+{
+    if (!s->c_dirty && s->c_tol == tol && s->c_vref == vref && s->c_shift == fine_shift && s->c_global == global) return 0;
     ClassView cv;
     summary_class_layout(s, fine_shift, cv);
+    cv.nx5 = ceil_div(s->w, 32); cv.nz5 = ceil_div(s->d, 32);
+    ClassLevel l6, l7;
+    int w6, w7;
+    summary_top_layout(cv, l6, l7, w6, w7);
     const float lo_ok = vref - tol * vref, hi_ok = vref + tol * vref;
-    for (int pass = 0; pass < 2; ++pass) {
+    for (int pass = 0; pass < (global ? 4 : 2); ++pass) {
+        if (pass >= 2) {
+            // global-table mode: the 64^3- and 128^3-cell levels, each the combination of the level below it (m = 2) -- the
+            // same entries classes_level_up derives in LDS (raycast.hip)
+            const ClassLevel& L = pass == 2 ? l6 : l7;
+            const ClassLevel& S = pass == 2 ? cv.coarse : l6;
+            ClassBuild b;
+            b.R = s->R; b.C = s->C + L.first;
+            b.nbx = s->nbx; b.nby = s->nby; b.nbz = s->nbz;
+            b.shift = L.shift; b.nx = ceil_div(s->w, 1 << L.shift); b.ny = L.ny; b.nz = ceil_div(s->d, 1 << L.shift); b.rw = L.rw;
+            b.lo_ok = lo_ok; b.hi_ok = hi_ok;
+            b.src = s->C + S.first;
+            b.src_shift = S.shift; b.src_nx = ceil_div(s->w, 1 << S.shift); b.src_ny = S.ny; b.src_nz = ceil_div(s->d, 1 << S.shift); b.src_rw = S.rw;
+            const long long waves = (long long)ceil_div(b.nx, 64) * b.ny * b.nz;
+            hipLaunchKernelGGL(k_summary_classes<0>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, b, waves);
+            if (int e = check_launch("kfx_sdf_summary (classes)")) return e;
+            continue;
+        }
         const ClassLevel& L = pass ? cv.coarse : cv.fine;
         if (!pass && fine_shift >= 5) continue;
         ClassBuild b;
@@ -253,7 +303,7 @@ int summary_classes_prepare(kfx_sdf_summary* s, float tol, float vref, int fine_
         }
         if (int e = check_launch("kfx_sdf_summary (classes)")) return e;
     }
-    s->c_dirty = 0; s->c_tol = tol; s->c_vref = vref; s->c_shift = fine_shift;
+    s->c_dirty = 0; s->c_tol = tol; s->c_vref = vref; s->c_shift = fine_shift; s->c_global = global;
     return 0;
 }
 
@@ -265,9 +315,10 @@ int summary_view_offset(const kfx_sdf_summary* s, const kfx_volume* view, int* o
     if (q < s->base) return set_error(KFX_E_SHAPE, "summary: the volume is not a view of the summary's volume");
     const size_t off = (size_t)(q - s->base);
     const size_t z = off / s->img_pitch, rem = off % s->img_pitch, y = rem / s->pitch, xb = rem % s->pitch;
-    if (xb % 8 || z + view->d > (size_t)s->d || y + view->h > (size_t)s->h || xb / 8 + view->w > (size_t)s->w)
+    const size_t cb = (size_t)s->cell_bytes;
+    if (xb % cb || z + view->d > (size_t)s->d || y + view->h > (size_t)s->h || xb / cb + view->w > (size_t)s->w)
         return set_error(KFX_E_SHAPE, "summary: the volume is not a view of the summary's volume (extent)");
-    *ox = (int)(xb / 8); *oy = (int)y; *oz = (int)z;
+    *ox = (int)(xb / cb); *oy = (int)y; *oz = (int)z;
     return 0;
 }
 
@@ -275,7 +326,7 @@ int summary_view_offset(const kfx_sdf_summary* s, const kfx_volume* view, int* o
 
 using namespace kfx;
 
-extern "C" int kfx_sdf_summary_create(kfx_sdf_summary** out, const kfx_volume* vol)
+static int summary_create(kfx_sdf_summary** out, const kfx_volume* vol, int cell_bytes)
 {
     if (!out || !vol || !vol->ptr) return set_error(KFX_E_NULL, "kfx_sdf_summary_create: null argument");
     if (vol->w < 2 || vol->h < 2 || vol->d < 2 || vol->w > 65535 || vol->h > 65535 || vol->d > 65535) return set_error(KFX_E_SHAPE, "kfx_sdf_summary_create: volume dimensions");
@@ -283,17 +334,25 @@ extern "C" int kfx_sdf_summary_create(kfx_sdf_summary** out, const kfx_volume* v
     if (!s) return set_error(KFX_E_RANGE, "kfx_sdf_summary_create: out of memory");
     s->nbx = ceil_div((int)vol->w, 8); s->nby = ceil_div((int)vol->h, 8); s->nbz = ceil_div((int)vol->d, 8);
     s->w = (int)vol->w; s->h = (int)vol->h; s->d = (int)vol->d;
+    s->cell_bytes = cell_bytes;
     s->base = static_cast<const unsigned char*>(vol->ptr);
     s->pitch = vol->pitch; s->img_pitch = vol->img_pitch;
     s->R = nullptr; s->C = nullptr; s->d_count = nullptr; s->h_skippable = nullptr; s->d_skippable = nullptr;
-    s->c_dirty = 1; s->c_tol = -1.f; s->c_vref = 0.f; s->c_shift = 0; s->sweeps = 0;
+    s->c_dirty = 1; s->c_tol = -1.f; s->c_vref = 0.f; s->c_shift = 0; s->c_global = 0; s->sweeps = 0;
     s->builds = 0; s->plain_calls = 0;
     for (auto& e : s->build_done) e = nullptr;
     s->n_coarse = ceil_div(s->w, 32) * ceil_div(s->h, 32) * ceil_div(s->d, 32);
     const size_t n = (size_t)s->nbx * s->nby * s->nbz;
     ClassView cv;
-    summary_class_layout(s, 3, cv);   // the finest level is the largest table
-    bool ok = hipMalloc((void**)&s->R, n * sizeof(float4)) == hipSuccess && hipMalloc((void**)&s->C, (size_t)cv.words * sizeof(unsigned)) == hipSuccess &&
+    summary_class_layout(s, 3, cv);   // the finest level is the largest table ...
+    ClassView cg;                     // ... except for tiny volumes against the global-table mode's (16^3-cell fine level + 64^3 + 128^3)
+    summary_class_layout(s, 4, cg);
+    cg.nx5 = ceil_div(s->w, 32); cg.nz5 = ceil_div(s->d, 32);
+    ClassLevel l6, l7;
+    int w6, w7;
+    summary_top_layout(cg, l6, l7, w6, w7);
+    const int words = std::max(cv.words, cg.words + w6 + w7);
+    bool ok = hipMalloc((void**)&s->R, n * sizeof(float4)) == hipSuccess && hipMalloc((void**)&s->C, (size_t)words * sizeof(unsigned)) == hipSuccess &&
               hipMalloc((void**)&s->d_count, 2 * sizeof(int)) == hipSuccess && hipMemset(s->d_count, 0, 2 * sizeof(int)) == hipSuccess;
     // the published count lives in pinned host memory the device can write; without it the march always uses the tables
     if (ok && hipHostMalloc((void**)&s->h_skippable, KFX_SUMMARY_RING * sizeof(int), hipHostMallocMapped) == hipSuccess) {
@@ -321,6 +380,9 @@ extern "C" int kfx_sdf_summary_create(kfx_sdf_summary** out, const kfx_volume* v
     return kfx_sdf_summary_invalidate(s, nullptr); // nothing is known about the volume's contents yet
 }
 
+extern "C" int kfx_sdf_summary_create(kfx_sdf_summary** out, const kfx_volume* vol) { return summary_create(out, vol, 8); }
+extern "C" int kfx_sdf_summary_create_h(kfx_sdf_summary** out, const kfx_volume* vol) { return summary_create(out, vol, 4); }
+
 extern "C" int kfx_sdf_summary_destroy(kfx_sdf_summary* s)
 {
     if (!s) return 0;
@@ -340,8 +402,12 @@ extern "C" int kfx_sdf_summary_rebuild(kfx_sdf_summary* s, kfx_stream stream)
     if (!s) return set_error(KFX_E_NULL, "kfx_sdf_summary_rebuild: null summary");
     const long long n = (long long)s->nbx * s->nby * s->nbz;
     const int aligned16 = ((((uintptr_t)s->base) | s->pitch | s->img_pitch) & 15) == 0;
-    hipLaunchKernelGGL(k_summary_rebuild, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, s->R, s->base, s->pitch, s->img_pitch,
-                       s->w, s->h, s->d, s->nbx, s->nby, s->nbz, aligned16);
+    if (s->cell_bytes == 4)
+        hipLaunchKernelGGL(k_summary_rebuild<4>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, s->R, s->base, s->pitch, s->img_pitch,
+                           s->w, s->h, s->d, s->nbx, s->nby, s->nbz, aligned16);
+    else
+        hipLaunchKernelGGL(k_summary_rebuild<8>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, s->R, s->base, s->pitch, s->img_pitch,
+                           s->w, s->h, s->d, s->nbx, s->nby, s->nbz, aligned16);
     s->c_dirty = 1;
     return check_launch("kfx_sdf_summary_rebuild");
 }
@@ -357,19 +423,32 @@ extern "C" int kfx_sdf_summary_invalidate(kfx_sdf_summary* s, kfx_stream stream)
     return check_launch("kfx_sdf_summary_invalidate");
 }
 
-// SdfReset(vol, trunc_dist) of the WHOLE volume with the summary set to match: every cell = trunc_dist (NaN: never observed)
-extern "C" int kfx_sdf_reset_tracked(const kfx_volume* vol, kfx_sdf_summary* s, float trunc_dist, kfx_stream stream)
+// SdfReset(vol, trunc_dist) of the WHOLE volume with the summary set to match: every cell = trunc_dist (NaN: never observed;
+// half cells: trunc_dist rounded to half, the value the cells then hold)
+static int reset_tracked(const kfx_volume* vol, kfx_sdf_summary* s, float trunc_dist, kfx_stream stream, int cell_bytes, const char* name)
 {
-    if (!s) return set_error(KFX_E_NULL, "kfx_sdf_reset_tracked: null summary");
+    if (!s) return set_error(KFX_E_NULL, cell_bytes == 4 ? "kfx_sdf_reset_tracked_h: null summary" : "kfx_sdf_reset_tracked: null summary");
+    if (s->cell_bytes != cell_bytes) return set_error(KFX_E_SHAPE, "SdfReset(tracked): the summary was created for the other cell type");
     int ox, oy, oz;
     if (int e = summary_view_offset(s, vol, &ox, &oy, &oz)) return e;
     if (ox || oy || oz || (int)vol->w != s->w || (int)vol->h != s->h || (int)vol->d != s->d)
         return set_error(KFX_E_SHAPE, "kfx_sdf_reset_tracked: resets the whole volume only (use kfx_sdf_reset + kfx_sdf_summary_invalidate for views)");
-    if (int e = kfx_sdf_reset(vol, trunc_dist, stream)) return e;
+    if (int e = cell_bytes == 4 ? kfx_sdf_reset_h(vol, trunc_dist, stream) : kfx_sdf_reset(vol, trunc_dist, stream)) return e;
     const size_t n = (size_t)s->nbx * s->nby * s->nbz;
     const bool nan = trunc_dist != trunc_dist;
+    const float v = cell_bytes == 4 ? __half2float(__float2half_rn(trunc_dist)) : trunc_dist;
     hipLaunchKernelGGL(k_summary_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, s->R, n,
-                       nan ? __builtin_inff() : trunc_dist, nan ? -__builtin_inff() : trunc_dist, nan ? 1 : 0);
+                       nan ? __builtin_inff() : v, nan ? -__builtin_inff() : v, nan ? 1 : 0);
     s->c_dirty = 1;
-    return check_launch("kfx_sdf_reset_tracked");
+    return check_launch(name);
+}
+
+extern "C" int kfx_sdf_reset_tracked(const kfx_volume* vol, kfx_sdf_summary* s, float trunc_dist, kfx_stream stream)
+{
+    return reset_tracked(vol, s, trunc_dist, stream, 8, "kfx_sdf_reset_tracked");
+}
+
+extern "C" int kfx_sdf_reset_tracked_h(const kfx_volume* vol, kfx_sdf_summary* s, float trunc_dist, kfx_stream stream)
+{
+    return reset_tracked(vol, s, trunc_dist, stream, 4, "kfx_sdf_reset_tracked_h");
 }

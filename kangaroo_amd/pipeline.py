@@ -45,8 +45,11 @@ class FramePipeline:
 
     def __init__(self, ops, dims, boxmin, boxmax, w, h, K=None, near=0.4, far=8.0, bilateral=None,
                  trunc_factor=scenes.TRUNC_DIST_FACTOR, max_w=scenes.MAX_W, mincostheta=scenes.MIN_COS_THETA,
-                 contiguous_images=False, track=False, cal_first=None, cal_block=None, cal_margin=None, timing_slots=None):
-        """track: keep a brick summary of the volume (ops.SdfSummary) current in SdfFuse and let RaycastSdf step through
+                 contiguous_images=False, track=False, cal_first=None, cal_block=None, cal_margin=None, timing_slots=None, kind=None):
+        """kind: the volume's cells, "f32" (SDF_t, the default) or "f16" (SDF_h, config C5); an f16 volume runs the separate
+        operators (the one-call frame is fp32-only) and takes track=True / False, not "auto" (its host-clock calibration does not
+        synchronise the frames it times).
+        track: keep a brick summary of the volume (ops.SdfSummary) current in SdfFuse and let RaycastSdf step through
         uniformly free / never-observed space without reading the volume (same volume bits; images bit-identical in
         exact numerics, within the fast-mode tolerance in fast numerics).  True / False, or "auto": start with the summary,
         time whole frames of the stream itself with and without it and keep whichever makes the frame shorter (see CAL_*):
@@ -55,6 +58,12 @@ class FramePipeline:
         During the calibration blocks the images come from the march of the block (bit-identical in exact numerics, within
         the fast-mode tolerance otherwise); reset() re-arms the calibration for the new stream, recalibrate() at any frame."""
         self.ops = ops
+        if kind is not None or not hasattr(self, "kind"):   # (SlabPipeline sets its own before it gets here)
+            self.kind = "f32" if kind is None else kind
+        if self.kind not in ("f32", "f16"):
+            raise ValueError("FramePipeline: kind must be 'f32' or 'f16', not %r" % (self.kind,))
+        if track == "auto" and self.kind != "f32":
+            raise ValueError("FramePipeline: track='auto' needs fp32 cells (its calibration times whole frames of the one-call frame)")
         self.track_policy = "auto" if track == "auto" else ("on" if track else "off")
         self.track = bool(track) and hasattr(ops, "SdfSummary")
         if self.track_policy == "auto" and not self.track:
@@ -100,6 +109,8 @@ class FramePipeline:
 
     # -- overridable pieces ------------------------------------------------------
     def _alloc_volume(self, boxmin, boxmax):
+        if self.kind != "f32":
+            return self.ops.BoundedVolume(self.dims[0], self.dims[1], self.dims[2], boxmin, boxmax, kind=self.kind)
         return self.ops.BoundedVolume(self.dims[0], self.dims[1], self.dims[2], boxmin, boxmax)
 
     def set_track(self, on):

@@ -258,16 +258,18 @@ def get_math_mode():
 # ---- operators ------------------------------------------------------------------
 
 class SdfSummary:
-    """kfx_sdf_summary of a BoundedVolume (fp32 cells): per 8 x 8 x 8 cells the range of the stored values, kept current by
-    SdfFuse(..., summary=) / SdfReset(..., summary=) and used by RaycastSdf(..., summary=) to step through uniformly free
-    or never-observed space without reading the volume.  Views of the volume may be passed to those calls; after any
-    other write to the volume call invalidate()."""
+    """kfx_sdf_summary of a BoundedVolume (fp32 or half cells): per 8 x 8 x 8 cells the range of the stored values, kept
+    current by SdfFuse(..., summary=) / SdfReset(..., summary=) and used by RaycastSdf(..., summary=) to step through uniformly
+    free or never-observed space without reading the volume.  Views of the volume may be passed to those calls; after any
+    other write to the volume call invalidate().  kind: the volume's ("f32": kfx_sdf_summary_create, "f16": _create_h)."""
 
     def __init__(self, vol):
-        assert vol.kind == "f32"
+        assert vol.kind in ("f32", "f16")
         self.vol = vol
+        self.kind = vol.kind
         self.handle = C.c_void_p()
-        _lib.check(_lib.load().kfx_sdf_summary_create(C.byref(self.handle), vol.ref()))
+        create = _lib.load().kfx_sdf_summary_create_h if vol.kind == "f16" else _lib.load().kfx_sdf_summary_create
+        _lib.check(create(C.byref(self.handle), vol.ref()))
 
     def invalidate(self, stream=None):
         _lib.check(_lib.load().kfx_sdf_summary_invalidate(self.handle, _stream(stream)))
@@ -386,9 +388,10 @@ def SdfFuse(vol, depth, norm, T_cw, K, trunc_dist, maxw, mincostheta, full_exten
     t, _t = _fp(T_cw, 12)
     k, _k = _fp(K, 4)
     if summary is not None:
-        assert slab is None and vol.kind == "f32"
-        _lib.check(_lib.load().kfx_sdf_fuse_tracked(vol.ref(), summary.handle, depth.ref(), norm.ref(), t, k, trunc_dist, maxw, mincostheta,
-                                                    1 if full_extent else 0, _stream(stream)))
+        assert slab is None and vol.kind in ("f32", "f16")
+        fn = _lib.load().kfx_sdf_fuse_tracked_h if vol.kind == "f16" else _lib.load().kfx_sdf_fuse_tracked
+        _lib.check(fn(vol.ref(), summary.handle, depth.ref(), norm.ref(), t, k, trunc_dist, maxw, mincostheta,
+                      1 if full_extent else 0, _stream(stream)))
         return
     if slab is not None:
         sl = _lib.KfxSlab(int(slab[0]), int(slab[1]), float(slab[2]), float(slab[3]))
@@ -458,8 +461,9 @@ def RaycastSdfCount(vol, w, h, T_wc, K, near, far, trunc_dist, subpix=True, stre
     bitmap = torch.zeros((vol.w * vol.h * vol.d + 31) // 32, dtype=torch.int32, device=vol.storage.device)
     if summary is not None:
         cnt = torch.zeros(6, dtype=torch.int64, device=vol.storage.device)
-        _lib.check(_lib.load().kfx_raycast_sdf_count_tracked(vol.ref(), summary.handle, w, h, t, k, near, far, trunc_dist, 1 if subpix else 0,
-                                                             C.c_void_p(bitmap.data_ptr()), C.c_void_p(cnt.data_ptr()), _stream(stream)))
+        fn = _lib.load().kfx_raycast_sdf_count_tracked_h if vol.kind == "f16" else _lib.load().kfx_raycast_sdf_count_tracked
+        _lib.check(fn(vol.ref(), summary.handle, w, h, t, k, near, far, trunc_dist, 1 if subpix else 0,
+                      C.c_void_p(bitmap.data_ptr()), C.c_void_p(cnt.data_ptr()), _stream(stream)))
         c = cnt.tolist()
         return dict(samples=c[0], rays=c[1], hits=c[2], U=c[3], lookups=c[4], table_bytes=c[5])
     cnt = torch.zeros(4, dtype=torch.int64, device=vol.storage.device)
@@ -476,8 +480,9 @@ def RaycastSdf(depth, norm, img, vol, T_wc, K, near, far, trunc_dist, subpix=Tru
     t, _t = _fp(T_wc, 12)
     k, _k = _fp(K, 4)
     if summary is not None:
-        _lib.check(_lib.load().kfx_raycast_sdf_tracked(depth.ref(), norm.ref(), img.ref(), vol.ref(), summary.handle, t, k, near, far,
-                                                       trunc_dist, 1 if subpix else 0, _stream(stream)))
+        fn = _lib.load().kfx_raycast_sdf_tracked_h if vol.kind == "f16" else _lib.load().kfx_raycast_sdf_tracked
+        _lib.check(fn(depth.ref(), norm.ref(), img.ref(), vol.ref(), summary.handle, t, k, near, far,
+                      trunc_dist, 1 if subpix else 0, _stream(stream)))
         return
     fn = _lib.load().kfx_raycast_sdf_h if vol.kind == "f16" else _lib.load().kfx_raycast_sdf
     _lib.check(fn(depth.ref(), norm.ref(), img.ref(), vol.ref(), t, k, near, far, trunc_dist, 1 if subpix else 0,
@@ -498,8 +503,9 @@ def RaycastSdfLevels(outputs, vol, T_wc, K_levels, near, far, trunc_dist, subpix
     t, _t = _fp(T_wc, 12)
     k, _k = _fp(np.concatenate([np.asarray(K, np.float32).reshape(4) for K in K_levels]) if n else np.zeros(0, np.float32), 4 * n)
     if summary is not None:
-        _lib.check(_lib.load().kfx_raycast_sdf_levels_tracked(n, ptrs[0], ptrs[1], ptrs[2], vptrs, vol.ref(), summary.handle, t, k, near, far,
-                                                              trunc_dist, 1 if subpix else 0, _stream(stream)))
+        fn = _lib.load().kfx_raycast_sdf_levels_tracked_h if vol.kind == "f16" else _lib.load().kfx_raycast_sdf_levels_tracked
+        _lib.check(fn(n, ptrs[0], ptrs[1], ptrs[2], vptrs, vol.ref(), summary.handle, t, k, near, far,
+                      trunc_dist, 1 if subpix else 0, _stream(stream)))
         return
     fn = _lib.load().kfx_raycast_sdf_levels_h if vol.kind == "f16" else _lib.load().kfx_raycast_sdf_levels
     _lib.check(fn(n, ptrs[0], ptrs[1], ptrs[2], vptrs, vol.ref(), t, k, near, far, trunc_dist, 1 if subpix else 0, _stream(stream)))
@@ -540,7 +546,8 @@ def NormalsFromVbo(dN, dV, stream=None):
 def SdfReset(vol, trunc_dist, stream=None, summary=None):
     """roo::SdfReset(BoundedVolume<SDF_t>, float) (cu_sdffusion.h:20).  summary: the whole volume's SdfSummary, set to match."""
     if summary is not None:
-        _lib.check(_lib.load().kfx_sdf_reset_tracked(vol.ref(), summary.handle, trunc_dist, _stream(stream)))
+        fn = _lib.load().kfx_sdf_reset_tracked_h if vol.kind == "f16" else _lib.load().kfx_sdf_reset_tracked
+        _lib.check(fn(vol.ref(), summary.handle, trunc_dist, _stream(stream)))
         return
     fn = _lib.load().kfx_sdf_reset_h if vol.kind == "f16" else _lib.load().kfx_sdf_reset
     _lib.check(fn(vol.ref(), trunc_dist, _stream(stream)))

@@ -29,7 +29,8 @@ def compile_to_asm(out):
                                       os.path.join(CSRC, "raycast.hip")], check=True, stderr=subprocess.DEVNULL)
 
 
-LOAD = re.compile(r"global_load_dwordx4 v\[(\d+):(\d+)\], v(?:\[\d+:\d+\]|\d+), (?:off|s\[\d+:\d+\])")
+# dwordx4: fp32 cells (RayF32), dwordx2: half cells (RayF16)
+LOAD = re.compile(r"global_load_dwordx[24] v\[(\d+):(\d+)\], v(?:\[\d+:\d+\]|\d+), (?:off|s\[\d+:\d+\])")
 
 
 def regs_named(t):
