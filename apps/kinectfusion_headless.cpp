@@ -74,6 +74,7 @@ int main(int argc, char** argv)
     bool fast = false, track = false, device_icp = false, one_raycast = false, use_summary = false, summary_auto = false;
     int warm = 0;          // --warmup F: the first F frames run but do not count in the reported frame time (clocks, first launches)
     int drop_frame = -1;   // --drop-frame F: frame F arrives with no valid depth at all (a sensor drop-out): tracking is lost, the next frame recovers
+    const char* save_mesh = nullptr;   // --save-mesh PREFIX: roo::SaveMesh of the model after the last frame (the application's 's' key) -> PREFIX.ply
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--res") && i + 1 < argc) volres = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--frames") && i + 1 < argc) frames = atoi(argv[++i]);
@@ -87,6 +88,7 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--device-icp")) track = device_icp = true;   // the refinement loop as one device-side chain
         else if (!strcmp(argv[i], "--drop-frame") && i + 1 < argc) drop_frame = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--warmup") && i + 1 < argc) warm = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--save-mesh") && i + 1 < argc) save_mesh = argv[++i];
     }
     if (warm < 0 || warm >= frames) warm = 0;
     if (kfx_device_count() < 1) { fprintf(stderr, "no HIP device\n"); return 2; }
@@ -359,6 +361,10 @@ int main(int argc, char** argv)
            use_summary ? " (brick summary)" : "", depth_sum);
     if (track) printf("  tracking: worst position error %.2f mm over the orbit (step between poses up to %.1f mm), final rmse %.4f, %d frames lost, %d resets\n",
                       1e3 * worst_pos_err, 1e3 * 0.0105, rmse, lost, resets);
+    if (save_mesh) {
+        const size_t ntri = SaveMesh(save_mesh, vol);
+        printf("  mesh: %zu triangles written to %s.ply\n", ntri, save_mesh);
+    }
     const int expect_lost = (track && drop_frame > 0 && drop_frame < frames) ? 1 : 0;
     if (track && (lost != expect_lost || resets != (expect_lost && drop_frame + 1 < frames ? 1 : 0) || worst_pos_err > 0.02)) return 1;
     return hits > (size_t)(w * h) / 4 ? 0 : 1;

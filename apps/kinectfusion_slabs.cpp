@@ -41,6 +41,7 @@ struct Options {
     SlabVolume::RaycastMode raycast = SlabVolume::Composite;
     SlabVolume::MergeMode merge = SlabVolume::MergeDirect;
     std::string rendezvous;   // default: /tmp/kfx_slabs.<uid>.<launch id>.id (default_rendezvous)
+    std::string save_mesh;    // --save-mesh PREFIX: after the last frame every rank writes its part of the mesh as PREFIX.r<rank>.ply
 };
 
 // analytic depth of the synthetic room: same scene as kinectfusion_headless.cpp / kangaroo_amd/scenes.py
@@ -87,7 +88,8 @@ static unsigned BitSum(const void* p, size_t bytes)
     return s;
 }
 
-struct Result { double ms_per_frame = 0; unsigned chk_d = 0, chk_n = 0, chk_i = 0, chk_vol = 0, chk_hist = 0; size_t hits = 0; int rounds = 0; int status = 0; };
+struct Result { double ms_per_frame = 0; unsigned chk_d = 0, chk_n = 0, chk_i = 0, chk_vol = 0, chk_hist = 0; size_t hits = 0; int rounds = 0; int status = 0;
+                size_t mesh_tris = 0; };
 
 // the frame loop of one rank
 static void RunRank(const Options& o, kfx_comm* comm, const std::vector<std::vector<float> >& depth_mm, const std::vector<Mat<float,3,4> >& poses,
@@ -280,6 +282,8 @@ static void RunRank(const Options& o, kfx_comm* comm, const std::vector<std::vec
     GpuCheckStatus(kfx_memcpy_2d(hsum, 8, dsum, 64, 8, 1, 2, 0));
     kfx_free(dsum);
     res->chk_vol = (unsigned)hsum[0];
+    if (!o.save_mesh.empty())   // this rank's cubes; the ghost planes the normals read are current after the last fuse
+        res->mesh_tris = slab.SaveMesh(o.save_mesh + ".r" + std::to_string(comm->rank));
 }
 
 int main(int argc, char** argv)
@@ -306,6 +310,7 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--tiles") && i + 1 < argc) o.tiles = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--ghost") && i + 1 < argc) { ++i; o.ghost = !strcmp(argv[i], "auto") ? -1 : atoi(argv[i]); }
         else if (!strcmp(argv[i], "--overlap")) o.overlap = true;
+        else if (!strcmp(argv[i], "--save-mesh") && i + 1 < argc) o.save_mesh = argv[++i];
         else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
     const int ndev = kfx_device_count();
@@ -351,6 +356,7 @@ int main(int argc, char** argv)
         RunRank(o, &comms[0], depth_mm, poses, &results[0]);
         for (auto& t : threads) t.join();
         r0 = results[0];
+        for (int r = 1; r < world; ++r) r0.mesh_tris += results[r].mesh_tris;
         for (int r = 1; r < world; ++r)   // after the merge every rank must hold the same images
             if (results[r].chk_d != r0.chk_d || results[r].chk_n != r0.chk_n || results[r].chk_i != r0.chk_i || results[r].chk_hist != r0.chk_hist) r0.status = 4;
         comms[0].destroy(&comms[0]);
@@ -362,6 +368,8 @@ int main(int argc, char** argv)
                o.raycast != SlabVolume::Composite ? (" (" + std::to_string(r0.rounds) + " rounds)").c_str() : "", r0.ms_per_frame, 1e3 / r0.ms_per_frame);
         printf("checksums depth=%08x norm=%08x img=%08x volume=%08x history=%08x hits=%zu ranks_agree=%d%s\n", r0.chk_d, r0.chk_n, r0.chk_i, r0.chk_vol, r0.chk_hist,
                r0.hits, r0.status == 0 ? 1 : 0, o.pipeline ? (" pipeline=" + std::to_string(o.pipeline)).c_str() : "");
+        if (!o.save_mesh.empty())
+            printf("mesh: %zu triangles written to %s.r<rank>.ply%s\n", r0.mesh_tris, o.save_mesh.c_str(), o.rccl ? " (rank 0's part)" : "");
     }
     if (r0.status) return r0.status;
     return r0.hits > (size_t)(o.w * o.h) / 4 ? 0 : 1;

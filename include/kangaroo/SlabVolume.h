@@ -8,6 +8,7 @@
 //   roo::SdfReset(slab.local, NaN);
 //   per frame:  slab.Fuse(depth, normals, T_cw, K, trunc, max_w, mincostheta);           // + halo exchange
 //               slab.Raycast(d, n, i, T_wc, K, near, far, trunc);                        // identical images on every rank
+//   at the end: slab.SaveMesh("mesh.r" + std::to_string(rank));                         // this rank's part of the mesh
 #pragma once
 
 #include <kfx_slab.h>
@@ -15,6 +16,7 @@
 #include <kangaroo/BoundedVolume.h>
 #include <kangaroo/Image.h>
 #include <kangaroo/ImageIntrinsics.h>
+#include <kangaroo/MarchingCubes.h>
 #include <kangaroo/Mat.h>
 #include <kangaroo/Sdf.h>
 #include <kangaroo/cu_raycast.h>
@@ -119,6 +121,16 @@ public:
                 GpuCheckStatus(kfx_slab_composite(depth.abi(), norm.abi(), img.abi(), (long long*)key_, (float*)payload_, comm, 0));
             }
         }
+    }
+
+    // SaveMesh of this rank's part: the cubes whose lower plane it owns, every triangle bit-identical to the single-volume mesh's,
+    // in emission order (include/kfx_mesh.h; the ghost planes must be current: Fuse leaves them so).  Writes filename + ".ply", no
+    // colour; returns the triangle count.
+    size_t SaveMesh(std::string filename)
+    {
+        const kfx_slab s = {layout.full_d, layout.s0, layout.full_zmin, layout.full_zmax};
+        const mesh_detail::HostMesh m = mesh_detail::Extract(local.abi(), KFX_CELL_F32, &s, (int)layout.z0, (int)layout.z1, nullptr);
+        return mesh_detail::WritePly(filename + ".ply", m);
     }
 
 private:

@@ -61,7 +61,7 @@ class KfxError(RuntimeError):
 
 PI, PV, PF = C.POINTER(KfxImage), C.POINTER(KfxVolume), C.POINTER(C.c_float)
 
-# name -> (restype, argtypes); every symbol include/kfx.h declares
+# name -> (restype, argtypes); every symbol include/kfx.h declares (and kfx_summary_h.h, kfx_mesh.h)
 SIGNATURES = {
     "kfx_sdf_fuse": (C.c_int, [PV, PI, PI, PF, PF, C.c_float, C.c_float, C.c_float, C.c_uint, C.c_void_p]),
     "kfx_sdf_fuse_slab": (C.c_int, [PV, C.POINTER(KfxSlab), PI, PI, PF, PF, C.c_float, C.c_float, C.c_float, C.c_uint, C.c_void_p]),
@@ -111,6 +111,10 @@ SIGNATURES = {
     "kfx_sdf_distance": (C.c_int, [PI, PI, PV, PF, PF, C.c_float, C.c_void_p]),
     "kfx_mc_count": (C.c_int, [PV, C.c_void_p, C.c_void_p]),
     "kfx_mc_emit": (C.c_int, [PV, PV, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kfx_mesh_scratch_bytes": (C.c_size_t, [PV, C.c_int, C.POINTER(KfxSlab), C.c_int, C.c_int]),
+    "kfx_mesh_plan": (C.c_int, [PV, C.c_int, C.POINTER(KfxSlab), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_ulonglong), C.c_void_p]),
+    "kfx_mesh_emit": (C.c_int, [PV, C.c_int, C.POINTER(KfxSlab), C.c_int, C.c_int, PV, C.c_void_p, C.c_size_t, C.POINTER(C.c_ulonglong), C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kfx_icp_refine": (C.c_int, [C.POINTER(KfxIcpLevel), C.c_int, C.c_float, C.c_float, PI, PI, C.POINTER(C.c_double), PF,
                                  C.POINTER(C.c_uint), C.POINTER(C.c_int), C.c_void_p]),
     "kfx_pose_step": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), PF]),

@@ -16,10 +16,13 @@
 //               vertex / normal / colour arithmetic keeps the reference's expressions (double division in
 //               fGetOffset, multiply-by-reciprocal normalisation), so the output arrays are bit-identical to the
 //               CPU oracle's and arrive in the reference's order.
+// kfx_mc_count / kfx_mc_emit keep that two-pass form; the planned extraction of include/kfx_mesh.h (below: segments counted and
+// scanned on the device, half cells, Z-slabs) replaces the host / torch compaction in SaveMesh and ExtractMesh.
 // The case tables (mc_tables.inc) are derived by scripts/gen_mc_tables.py from the cube's topology; their boundary
 // loops and winding equal the classic tables' in all 256 cases (tests/test_mesh_cpu.py).
 #include "kfx_device.h"
 #include "sampling.h"
+#include "../../include/kfx_mesh.h"
 
 namespace kfx {
 
@@ -35,6 +38,7 @@ struct MeshParams {
     V3 inv_size;
     int fastdiv, off32;
     int cx, cy, cz;              // cubes per axis = dims - 1
+    int avail_lo, avail_hi;      // planes that may be read: [0, d) of a whole volume, the stored planes of a slab
 };
 
 // corner i of the cube at (x, y, z): offsets (0,0,0) (1,0,0) (1,1,0) (0,1,0) (0,0,1) (1,0,1) (1,1,1) (0,1,1)
@@ -42,14 +46,16 @@ __device__ __forceinline__ int corner_dx(int i) { return ((i + 1) >> 1) & 1; }
 __device__ __forceinline__ int corner_dy(int i) { return (i >> 1) & 1; }
 __device__ __forceinline__ int corner_dz(int i) { return i >> 2; }
 
-// values at the 8 corners and the case index; false if a corner is not finite (MarchingCubes.h:58-74)
+// values at the 8 corners and the case index; false if a corner is not finite (MarchingCubes.h:58-74).  Half cells are widened
+// exactly (SDF_h's operator float), so a half volume's cubes are those of the widened fp32 volume.
+template <typename CELL>
 __device__ __forceinline__ bool cube_case(const MeshParams& p, int x, int y, int z, float v[8], int& flag)
 {
     const unsigned char* r00 = rowp(p.vol, y, z);
     const unsigned char* r10 = rowp(p.vol, y + 1, z);
     const unsigned char* r01 = rowp(p.vol, y, z + 1);
     const unsigned char* r11 = rowp(p.vol, y + 1, z + 1);
-    const float2 a = RayF32::pair(r00, x), b = RayF32::pair(r10, x), c = RayF32::pair(r01, x), d = RayF32::pair(r11, x);
+    const float2 a = CELL::pair(r00, x), b = CELL::pair(r10, x), c = CELL::pair(r01, x), d = CELL::pair(r11, x);
     v[0] = a.x; v[1] = a.y; v[2] = b.y; v[3] = b.x;
     v[4] = c.x; v[5] = c.y; v[6] = d.y; v[7] = d.x;
     bool finite = true;
@@ -76,7 +82,7 @@ __global__ __launch_bounds__(256) void k_mc_count(const MeshParams p, unsigned c
         if (x < p.cx && z < p.cz) {
             float v[8];
             int flag;
-            if (cube_case(p, x, y, z, v, flag)) n = c_num_tris[flag];
+            if (cube_case<RayF32>(p, x, y, z, v, flag)) n = c_num_tris[flag];
         }
         tile[lane][zz] = n;
     }
@@ -93,7 +99,9 @@ __global__ __launch_bounds__(256) void k_mc_count(const MeshParams p, unsigned c
 }
 
 // One thread per ACTIVE cube (cube_index lists the cubes with triangles in emission order; tri_offset their first
-// triangle): dense lanes instead of the ~1 % active lanes of a thread-per-cube sweep.
+// triangle): dense lanes instead of the ~1 % active lanes of a thread-per-cube sweep.  CELL: fp32 or half cells; SLAB: p holds
+// the full volume's geometry over a slab's planes [avail_lo, avail_hi) (virtual base pointer, mesh_slab_geometry).
+template <typename CELL, bool SLAB>
 __global__ __launch_bounds__(128) void k_mc_emit(const MeshParams p, const ColorGeom cv, const int has_color,
                                                  const long long* __restrict__ cube_index, const unsigned* __restrict__ tri_offset,
                                                  const long long n_active, float* __restrict__ verts,
@@ -107,7 +115,7 @@ __global__ __launch_bounds__(128) void k_mc_emit(const MeshParams p, const Color
     const int x = (int)(ci / ((long long)p.cz * p.cy));
     float v[8];
     int flag;
-    if (!cube_case(p, x, y, z, v, flag)) return;
+    if (!cube_case<CELL>(p, x, y, z, v, flag)) return;
     const int ntri = c_num_tris[flag];
     if (ntri == 0) return;
     const unsigned mask = c_edge_mask[flag];
@@ -129,8 +137,22 @@ __global__ __launch_bounds__(128) void k_mc_emit(const MeshParams p, const Color
                     dz = (float)(corner_dz(c1) - corner_dz(c0));
         const V3 pos = v3(p0.x + (ox + off * dx) * p.voxel.x, p0.y + (oy + off * dy) * p.voxel.y, p0.z + (oz + off * dz) * p.voxel.z);
         ev[e] = pos;
-        const V3 deriv = gradient<RayF32>(p, pos);
-        V3 n = div_s(deriv, length(deriv));
+        V3 n;
+        if constexpr (SLAB) {
+            // the stencil's planes (gradient<>: base plane clamped to [1, d - 2], one plane either side) must be stored; they are
+            // for any vertex within a voxel of its cube, which float positions are unless the box lies ~2^20 voxels from the origin
+            const float pfz = (pos.z - p.vol.bmin.z) / p.size.z * p.dims1.z;
+            const int iz = (int)fmaxf(fminf(p.hi2.z, floorf(pfz)), 1.f);
+            if (iz - 1 >= p.avail_lo && iz + 1 < p.avail_hi) {
+                const V3 deriv = gradient<CELL>(p, pos);
+                n = div_s(deriv, length(deriv));
+            } else {
+                n = v3(0.f, 0.f, 0.f);
+            }
+        } else {
+            const V3 deriv = gradient<CELL>(p, pos);
+            n = div_s(deriv, length(deriv));
+        }
         if (!isfinite(n.x) || !isfinite(n.y) || !isfinite(n.z)) n = v3(0.f, 0.f, 0.f);
         en[e] = n;
         ec[e] = has_color ? trilinear<RayC32>(cv, pos) : 0.f;
@@ -166,17 +188,348 @@ static int load_tables()
     return 0;
 }
 
-static int mesh_params(MeshParams& p, const kfx_volume* vol)
+static int mesh_params(MeshParams& p, const kfx_volume* vol, size_t cell_bytes = 8)
 {
     if (!vol || !vol->ptr) return set_error(KFX_E_NULL, "SaveMesh: null volume");
     if (vol->w < 3 || vol->h < 3 || vol->d < 3 || vol->w > 65535 || vol->h > 65535 || vol->d > 65535)
         return set_error(KFX_E_SHAPE, "SaveMesh: volume dimensions");
-    if (vol->pitch < vol->w * 8 || vol->img_pitch < vol->pitch * (vol->h - 1) + vol->w * 8) return set_error(KFX_E_SHAPE, "SaveMesh: volume pitch");
-    if (((uintptr_t)vol->ptr | vol->pitch | vol->img_pitch) & 7) return set_error(KFX_E_ALIGN, "SaveMesh: alignment");
+    if (vol->pitch < vol->w * cell_bytes || vol->img_pitch < vol->pitch * (vol->h - 1) + vol->w * cell_bytes) return set_error(KFX_E_SHAPE, "SaveMesh: volume pitch");
+    if (((uintptr_t)vol->ptr | vol->pitch | vol->img_pitch) & (cell_bytes - 1)) return set_error(KFX_E_ALIGN, "SaveMesh: alignment");
     set_geometry(p, vol);
     set_voxel_size(p, vol);
     p.cx = (int)vol->w - 1; p.cy = (int)vol->h - 1; p.cz = (int)vol->d - 1;
+    p.avail_lo = 0; p.avail_hi = (int)vol->d;
     return 0;
+}
+
+// the colour volume of an emit: sampled only when it IsValid(), every dimension >= 8 (BoundedVolume.h:84-87)
+static int color_params(ColorGeom& cv, int& has_color, const kfx_volume* colorvol, const float* colors)
+{
+    cv = ColorGeom{};
+    has_color = colorvol && colorvol->ptr && colors && colorvol->w >= 8 && colorvol->h >= 8 && colorvol->d >= 8;
+    if (has_color) {
+        if (colorvol->pitch < colorvol->w * 4 || colorvol->img_pitch < colorvol->pitch * (colorvol->h - 1) + colorvol->w * 4)
+            return set_error(KFX_E_SHAPE, "SaveMesh: colour volume pitch");
+        if (((uintptr_t)colorvol->ptr | colorvol->pitch | colorvol->img_pitch) & 3) return set_error(KFX_E_ALIGN, "SaveMesh: colour volume alignment");
+        set_geometry(cv, colorvol);
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Planned extraction (include/kfx_mesh.h): the per-cube byte array and the host / torch compaction replaced by four passes
+// over SEGMENTS -- runs of up to MESH_SEG consecutive cubes along z in one (x, y) column, numbered in emission order
+// s = (x*cy + y)*nsz + k (x outer, z inner: a segment's cubes are consecutive in the reference's order):
+//   k_mesh_count     one lane per segment, lanes of a wave on x-adjacent columns (coalesced corner rows); the lane walks z and
+//                    keeps plane z+1's corner pairs as the next cube's plane z.  Writes (active cubes << 9 | triangles), 16 bits.
+//   k_mesh_reduce    sums of MESH_BLOCK consecutive segments (the scan's upsweep)
+//   k_mesh_scan_partials  one workgroup: exclusive 64-bit scan of the block sums, and the totals
+//   k_mesh_compact   the downsweep inside each block (LDS), then one lane per ACTIVE segment re-walks its cubes and writes the
+//                    active cubes' global indices (int64) and first triangles (uint32) at the scanned offsets
+//   k_mc_emit        as kfx_mc_emit
+// Kernel boundaries order the passes: no in-launch hand-off between workgroups.
+constexpr int MESH_SEG = 64;         // cubes per segment: 8 segments per column at 512^3, 32 at 2048^3
+constexpr int MESH_SEG_TILE = 32;    // segments per column and count workgroup (grid z covers the rest)
+constexpr int MESH_PER_THREAD = 2;   // segments per thread of the reduce / compact workgroups (small blocks: enough compact waves)
+constexpr int MESH_BLOCK = 256 * MESH_PER_THREAD;
+constexpr int MESH_SCAN_THREADS = 1024, MESH_SCAN_PER_THREAD = 8;
+constexpr unsigned long long MESH_MAX_TRIS = 4294967296ull / 3;   // 2^32 / 3: vertex offsets stay 32-bit
+constexpr size_t MESH_HEADER = 256;
+
+struct MeshRange {
+    int zlo, zhi;      // cube planes meshed: [zlo, zhi)
+    int nsz;           // segments per column
+    long long nseg;    // cx * cy * nsz
+    long long nblk;    // ceil(nseg / MESH_BLOCK)
+};
+
+__device__ __forceinline__ unsigned seg_pack(unsigned active, unsigned tris) { return (active << 9) | tris; }
+
+// active cubes and triangles of the cubes [za, zb) of column (x, y)
+template <typename CELL>
+__device__ __forceinline__ unsigned segment_count(const MeshParams& p, int x, int y, int za, int zb)
+{
+    float2 a = CELL::pair(rowp(p.vol, y, za), x), b = CELL::pair(rowp(p.vol, y + 1, za), x);
+    unsigned active = 0, tris = 0;
+    for (int z = za; z < zb; ++z) {
+        const float2 c = CELL::pair(rowp(p.vol, y, z + 1), x), d = CELL::pair(rowp(p.vol, y + 1, z + 1), x);
+        const float v[8] = {a.x, a.y, b.y, b.x, c.x, c.y, d.y, d.x};   // cube_case's corner order
+        bool finite = true;
+        int flag = 0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            finite = finite && isfinite(v[i]);
+            if (v[i] <= 0.0f) flag |= 1 << i;
+        }
+        const unsigned n = finite ? c_num_tris[flag] : 0u;
+        active += n != 0;
+        tris += n;
+        a = c;
+        b = d;
+    }
+    return seg_pack(active, tris);
+}
+
+// Workgroup = 64 columns along x (one per lane) x MESH_SEG_TILE segments of one y; wave w takes segments w, w + 4, ...  The
+// counts leave through an LDS tile so that each column's segments (consecutive in emission order) are stored together.
+template <typename CELL>
+__global__ __launch_bounds__(256) void k_mesh_count(const MeshParams p, const MeshRange r, unsigned short* __restrict__ seg)
+{
+    __shared__ unsigned short tile[64][MESH_SEG_TILE + 2];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int x0 = blockIdx.x * 64, y = blockIdx.y, k0 = blockIdx.z * MESH_SEG_TILE;
+    const int x = x0 + lane;
+    for (int kk = wv; kk < MESH_SEG_TILE; kk += 4) {
+        const int k = k0 + kk;
+        unsigned n = 0;
+        if (x < p.cx && k < r.nsz) {
+            const int za = r.zlo + k * MESH_SEG;
+            n = segment_count<CELL>(p, x, y, za, min(za + MESH_SEG, r.zhi));
+        }
+        tile[lane][kk] = (unsigned short)n;
+    }
+    __syncthreads();
+    // 4 threads per column, each MESH_SEG_TILE / 4 consecutive segments
+    const int xr = threadIdx.x >> 2, q = threadIdx.x & 3;
+    if (x0 + xr < p.cx) {
+        unsigned short* dst = seg + ((long long)(x0 + xr) * p.cy + y) * r.nsz;
+#pragma unroll
+        for (int b = 0; b < MESH_SEG_TILE / 4; ++b) {
+            const int kk = q * (MESH_SEG_TILE / 4) + b, k = k0 + kk;
+            if (k < r.nsz) dst[k] = tile[xr][kk];
+        }
+    }
+}
+
+// inclusive scan of one value per thread over a workgroup of 64 * NW threads; returns the exclusive prefix, *total the sum
+template <typename T, int NW>
+__device__ __forceinline__ T block_exclusive_scan(T v, T* lds, T* total)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    T inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T t = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += t;
+    }
+    if (lane == 63) lds[wv] = inc;
+    __syncthreads();
+    T base = 0, sum = 0;
+    for (int i = 0; i < NW; ++i) {
+        const T w = lds[i];
+        if (i < wv) base += w;
+        sum += w;
+    }
+    __syncthreads();
+    *total = sum;
+    return base + inc - v;
+}
+
+// sums of MESH_BLOCK consecutive segments: part[2 b] = active cubes, part[2 b + 1] = triangles
+__global__ __launch_bounds__(256) void k_mesh_reduce(const unsigned short* __restrict__ seg, const MeshRange r, unsigned* __restrict__ part)
+{
+    __shared__ unsigned lds[2][4];
+    const long long s0 = (long long)blockIdx.x * MESH_BLOCK + (long long)threadIdx.x * MESH_PER_THREAD;
+    unsigned a = 0, t = 0;
+    for (int j = 0; j < MESH_PER_THREAD; ++j) {
+        const unsigned n = s0 + j < r.nseg ? seg[s0 + j] : 0u;
+        a += n >> 9;
+        t += n & 511u;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a += __shfl_xor(a, o, 64);
+        t += __shfl_xor(t, o, 64);
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) { lds[0][wv] = a; lds[1][wv] = t; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        part[2 * (size_t)blockIdx.x] = lds[0][0] + lds[0][1] + lds[0][2] + lds[0][3];
+        part[2 * (size_t)blockIdx.x + 1] = lds[1][0] + lds[1][1] + lds[1][2] + lds[1][3];
+    }
+}
+
+// one workgroup: exclusive 64-bit offsets of the blocks (base[2 b] cubes, base[2 b + 1] triangles) and the totals
+__global__ __launch_bounds__(MESH_SCAN_THREADS) void k_mesh_scan_partials(const unsigned* __restrict__ part, const long long nblk,
+                                                                          unsigned long long* __restrict__ base, unsigned long long* __restrict__ totals)
+{
+    __shared__ unsigned long long lds[2][MESH_SCAN_THREADS / 64];
+    unsigned long long run_a = 0, run_t = 0;
+    constexpr int CHUNK = MESH_SCAN_THREADS * MESH_SCAN_PER_THREAD;
+    for (long long c0 = 0; c0 < nblk; c0 += CHUNK) {
+        const long long b0 = c0 + (long long)threadIdx.x * MESH_SCAN_PER_THREAD;
+        unsigned va[MESH_SCAN_PER_THREAD], vt[MESH_SCAN_PER_THREAD];
+        unsigned long long sa = 0, st = 0;
+#pragma unroll
+        for (int j = 0; j < MESH_SCAN_PER_THREAD; ++j) {
+            const bool in = b0 + j < nblk;
+            va[j] = in ? part[2 * (b0 + j)] : 0u;
+            vt[j] = in ? part[2 * (b0 + j) + 1] : 0u;
+            sa += va[j];
+            st += vt[j];
+        }
+        unsigned long long ta, tt;
+        unsigned long long ea = block_exclusive_scan<unsigned long long, MESH_SCAN_THREADS / 64>(sa, lds[0], &ta) + run_a;
+        unsigned long long et = block_exclusive_scan<unsigned long long, MESH_SCAN_THREADS / 64>(st, lds[1], &tt) + run_t;
+#pragma unroll
+        for (int j = 0; j < MESH_SCAN_PER_THREAD; ++j) {
+            if (b0 + j < nblk) {
+                base[2 * (b0 + j)] = ea;
+                base[2 * (b0 + j) + 1] = et;
+            }
+            ea += va[j];
+            et += vt[j];
+        }
+        run_a += ta;
+        run_t += tt;
+    }
+    if (threadIdx.x == 0) {
+        totals[0] = run_a;
+        totals[1] = run_t;
+    }
+}
+
+// One workgroup per block of MESH_BLOCK segments: the block's exclusive offsets in LDS (thread t scans its MESH_PER_THREAD
+// consecutive segments, the workgroup scans the threads' sums), then lane t walks segments t, t + 256, ... that have active
+// cubes and writes each active cube's global index and first triangle.  Writes stop at the caller's capacities.
+template <typename CELL>
+__global__ __launch_bounds__(256) void k_mesh_compact(const MeshParams p, const MeshRange r, const unsigned short* __restrict__ seg,
+                                                      const unsigned long long* __restrict__ base, long long* __restrict__ cube_index,
+                                                      unsigned* __restrict__ tri_offset, const unsigned long long cap_active,
+                                                      const unsigned long long cap_tris)
+{
+    __shared__ unsigned off_a[MESH_BLOCK], off_t[MESH_BLOCK];
+    __shared__ unsigned short cnt[MESH_BLOCK];
+    __shared__ unsigned lds[2][4];
+    const long long blk0 = (long long)blockIdx.x * MESH_BLOCK;
+    const int j0 = threadIdx.x * MESH_PER_THREAD;
+    unsigned sa = 0, st = 0;
+    for (int j = 0; j < MESH_PER_THREAD; ++j) {
+        const unsigned short n = blk0 + j0 + j < r.nseg ? seg[blk0 + j0 + j] : (unsigned short)0;
+        cnt[j0 + j] = n;
+        sa += n >> 9;
+        st += n & 511u;
+    }
+    unsigned ta, tt;
+    unsigned ea = block_exclusive_scan<unsigned, 4>(sa, lds[0], &ta);
+    unsigned et = block_exclusive_scan<unsigned, 4>(st, lds[1], &tt);
+    for (int j = 0; j < MESH_PER_THREAD; ++j) {
+        off_a[j0 + j] = ea;
+        off_t[j0 + j] = et;
+        ea += cnt[j0 + j] >> 9;
+        et += cnt[j0 + j] & 511u;
+    }
+    __syncthreads();
+    const unsigned long long ba = base[2 * (size_t)blockIdx.x], bt = base[2 * (size_t)blockIdx.x + 1];
+    for (int j = threadIdx.x; j < MESH_BLOCK; j += 256) {
+        if (cnt[j] == 0) continue;
+        const long long s = blk0 + j;
+        const long long col = s / r.nsz;
+        const int k = (int)(s - col * r.nsz);
+        const int x = (int)(col / p.cy), y = (int)(col - (long long)x * p.cy);
+        const int za = r.zlo + k * MESH_SEG, zb = min(za + MESH_SEG, r.zhi);
+        unsigned long long ia = ba + off_a[j], it = bt + off_t[j];
+        float2 a = CELL::pair(rowp(p.vol, y, za), x), b = CELL::pair(rowp(p.vol, y + 1, za), x);
+        const long long ci0 = col * p.cz;
+        for (int z = za; z < zb; ++z) {
+            const float2 c = CELL::pair(rowp(p.vol, y, z + 1), x), d = CELL::pair(rowp(p.vol, y + 1, z + 1), x);
+            const float v[8] = {a.x, a.y, b.y, b.x, c.x, c.y, d.y, d.x};
+            bool finite = true;
+            int flag = 0;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                finite = finite && isfinite(v[i]);
+                if (v[i] <= 0.0f) flag |= 1 << i;
+            }
+            const unsigned n = finite ? c_num_tris[flag] : 0u;
+            if (n) {
+                if (ia < cap_active && it + n <= cap_tris) {
+                    cube_index[ia] = ci0 + z;
+                    tri_offset[ia] = (unsigned)it;
+                }
+                ++ia;
+                it += n;
+            }
+            a = c;
+            b = d;
+        }
+    }
+}
+
+// The meshed cube planes and the geometry: the whole volume, or a slab view through the full volume's geometry -- the recipe of
+// raycast_slab_launch (raycast.hip): base pointer moved back by z_offset planes (dereferenced only inside the stored planes),
+// full_d / full_zmin / full_zmax in z, set_shortcuts on the full geometry.
+static int mesh_setup(MeshParams& p, MeshRange& r, const kfx_volume* vol, int cell, const kfx_slab* slab, int own_lo, int own_hi)
+{
+    if (!vol || !vol->ptr) return set_error(KFX_E_NULL, "kfx_mesh: null volume");
+    if (cell != KFX_CELL_F32 && cell != KFX_CELL_F16) return set_error(KFX_E_RANGE, "kfx_mesh: unknown cell kind");
+    const size_t cb = cell == KFX_CELL_F32 ? 8 : 4;
+    if (!slab) {
+        if (int e = mesh_params(p, vol, cb)) return e;
+        r.zlo = 0;
+        r.zhi = p.cz;
+    } else {
+        if (vol->w < 3 || vol->h < 3 || vol->d < 1 || vol->w > 65535 || vol->h > 65535 || slab->full_d < 3 || slab->full_d > 65535 ||
+            slab->z_offset + vol->d > slab->full_d)
+            return set_error(KFX_E_SHAPE, "kfx_mesh: slab outside the full volume");
+        if (vol->pitch < vol->w * cb || vol->img_pitch < vol->pitch * (vol->h - 1) + vol->w * cb) return set_error(KFX_E_SHAPE, "kfx_mesh: volume pitch");
+        if (((uintptr_t)vol->ptr | vol->pitch | vol->img_pitch) & (cb - 1)) return set_error(KFX_E_ALIGN, "kfx_mesh: alignment");
+        const int full_d = (int)slab->full_d;
+        const int zlo = own_lo < 0 ? 0 : own_lo, zhi = own_hi < full_d - 1 ? own_hi : full_d - 1;
+        r.zlo = zlo;
+        r.zhi = zhi > zlo ? zhi : zlo;
+        if (r.zhi > r.zlo) {
+            // corners: planes z, z + 1; normals: gradient<>'s base plane clamp(floor(vertex z), 1, d - 2), with the vertex in
+            // [z, z + 1], and its planes either side -> [zlo - 2, zhi + 2) within the volume
+            const long long need_lo = r.zlo - 2 > 0 ? r.zlo - 2 : 0, need_hi = r.zhi + 2 < full_d ? r.zhi + 2 : full_d;
+            if (need_lo < (long long)slab->z_offset || need_hi > (long long)(slab->z_offset + vol->d))
+                return set_error(KFX_E_RANGE, "kfx_mesh: the stored planes do not cover the slab's cubes and their normals' stencil");
+        }
+        p.vol.ptr = (unsigned char*)vol->ptr - (ptrdiff_t)slab->z_offset * (ptrdiff_t)vol->img_pitch;
+        p.vol.pitch = vol->pitch;
+        p.vol.img_pitch = vol->img_pitch;
+        p.vol.w = (int)vol->w;
+        p.vol.h = (int)vol->h;
+        p.vol.d = full_d;
+        p.vol.bmin = V3{vol->boxmin[0], vol->boxmin[1], slab->full_zmin};
+        p.vol.bmax = V3{vol->boxmax[0], vol->boxmax[1], slab->full_zmax};
+        p.size = V3{vol->boxmax[0] - vol->boxmin[0], vol->boxmax[1] - vol->boxmin[1], slab->full_zmax - slab->full_zmin};
+        p.dims1 = V3{(float)vol->w - 1.f, (float)vol->h - 1.f, (float)full_d - 1.f};
+        p.hi2 = V3{(float)(vol->w - 2), (float)(vol->h - 2), (float)(full_d - 2)};
+        p.voxel = V3{p.size.x / (float)(vol->w - 1), p.size.y / (float)(vol->h - 1), p.size.z / (float)(full_d - 1)};
+        set_shortcuts(p);
+        p.cx = (int)vol->w - 1; p.cy = (int)vol->h - 1; p.cz = full_d - 1;
+        p.avail_lo = (int)slab->z_offset;
+        p.avail_hi = (int)(slab->z_offset + vol->d);
+    }
+    r.nsz = (r.zhi - r.zlo + MESH_SEG - 1) / MESH_SEG;
+    r.nseg = (long long)p.cx * p.cy * r.nsz;
+    r.nblk = (r.nseg + MESH_BLOCK - 1) / MESH_BLOCK;
+    return 0;
+}
+
+static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// scratch: [header: totals][segment counts, 2 B, nblk * MESH_BLOCK][block sums, 8 B per block][block offsets, 16 B per block]
+struct MeshScratch {
+    unsigned long long* totals;
+    unsigned short* seg;
+    unsigned* part;
+    unsigned long long* base;
+    size_t bytes;
+};
+static MeshScratch mesh_scratch(const MeshRange& r, void* scratch)
+{
+    MeshScratch s;
+    unsigned char* b = (unsigned char*)scratch;
+    size_t o = 0;
+    s.totals = (unsigned long long*)(b + o); o += MESH_HEADER;
+    s.seg = (unsigned short*)(b + o); o += align256((size_t)r.nblk * MESH_BLOCK * 2);
+    s.part = (unsigned*)(b + o); o += align256((size_t)r.nblk * 8);
+    s.base = (unsigned long long*)(b + o); o += align256((size_t)r.nblk * 16);
+    s.bytes = o;
+    return s;
 }
 
 } // namespace kfx
@@ -202,17 +555,107 @@ extern "C" int kfx_mc_emit(const kfx_volume* vol, const kfx_volume* colorvol, co
     if (n_active <= 0) return 0;
     if (!cube_index || !tri_offset || !verts || !norms) return set_error(KFX_E_NULL, "SaveMesh: null output");
     if (int e = load_tables()) return e;
-    ColorGeom cv{};
-    // the reference samples the colour volume only when it IsValid(): every dimension >= 8 (BoundedVolume.h:84-87)
-    const int has_color = colorvol && colorvol->ptr && colors && colorvol->w >= 8 && colorvol->h >= 8 && colorvol->d >= 8;
-    if (has_color) {
-        if (colorvol->pitch < colorvol->w * 4 || colorvol->img_pitch < colorvol->pitch * (colorvol->h - 1) + colorvol->w * 4)
-            return set_error(KFX_E_SHAPE, "SaveMesh: colour volume pitch");
-        if (((uintptr_t)colorvol->ptr | colorvol->pitch | colorvol->img_pitch) & 3) return set_error(KFX_E_ALIGN, "SaveMesh: colour volume alignment");
-        set_geometry(cv, colorvol);
-    }
+    ColorGeom cv;
+    int has_color = 0;
+    if (int e = color_params(cv, has_color, colorvol, colors)) return e;
     if (n_active > 0x7fffffffLL * 128) return set_error(KFX_E_RANGE, "SaveMesh: too many active cubes");
-    hipLaunchKernelGGL(k_mc_emit, dim3((unsigned)((n_active + 127) / 128)), dim3(128), 0, (hipStream_t)stream, p, cv, has_color,
+    hipLaunchKernelGGL((k_mc_emit<RayF32, false>), dim3((unsigned)((n_active + 127) / 128)), dim3(128), 0, (hipStream_t)stream, p, cv, has_color,
                        cube_index, tri_offset, n_active, verts, norms, colors);
     return check_launch("kfx_mc_emit");
+}
+
+extern "C" size_t kfx_mesh_scratch_bytes(const kfx_volume* vol, int cell, const kfx_slab* slab, int own_lo, int own_hi)
+{
+    MeshParams p;
+    MeshRange r;
+    if (mesh_setup(p, r, vol, cell, slab, own_lo, own_hi)) return 0;
+    return mesh_scratch(r, nullptr).bytes;
+}
+
+template <typename CELL>
+static void mesh_plan_launch(const MeshParams& p, const MeshRange& r, const MeshScratch& s, hipStream_t st)
+{
+    dim3 grid(ceil_div(p.cx, 64), p.cy, ceil_div(r.nsz, MESH_SEG_TILE));
+    hipLaunchKernelGGL(k_mesh_count<CELL>, grid, dim3(256), 0, st, p, r, s.seg);
+    hipLaunchKernelGGL(k_mesh_reduce, dim3((unsigned)r.nblk), dim3(256), 0, st, s.seg, r, s.part);
+    hipLaunchKernelGGL(k_mesh_scan_partials, dim3(1), dim3(MESH_SCAN_THREADS), 0, st, s.part, r.nblk, s.base, s.totals);
+}
+
+extern "C" int kfx_mesh_plan(const kfx_volume* vol, int cell, const kfx_slab* slab, int own_lo, int own_hi, void* scratch,
+                             size_t scratch_bytes, unsigned long long totals[2], kfx_stream stream)
+{
+    MeshParams p;
+    MeshRange r;
+    if (int e = mesh_setup(p, r, vol, cell, slab, own_lo, own_hi)) return e;
+    if (!scratch || !totals) return set_error(KFX_E_NULL, "kfx_mesh_plan: null scratch or totals");
+    if ((uintptr_t)scratch & 255) return set_error(KFX_E_ALIGN, "kfx_mesh_plan: scratch not 256-byte aligned");
+    const MeshScratch s = mesh_scratch(r, scratch);
+    if (scratch_bytes < s.bytes) return set_error(KFX_E_SHAPE, "kfx_mesh_plan: scratch smaller than kfx_mesh_scratch_bytes");
+    if (r.nblk > 0x7fffffffLL) return set_error(KFX_E_RANGE, "kfx_mesh_plan: volume too large");
+    totals[0] = totals[1] = 0;
+    if (r.nseg == 0) return 0;
+    if (int e = load_tables()) return e;
+    const hipStream_t st = (hipStream_t)stream;
+    if (cell == KFX_CELL_F32) mesh_plan_launch<RayF32>(p, r, s, st);
+    else mesh_plan_launch<RayF16>(p, r, s, st);
+    if (int e = check_launch("kfx_mesh_plan")) return e;
+    unsigned long long host[2];
+    hipError_t e = hipMemcpyAsync(host, s.totals, sizeof(host), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return set_error((int)e, hipGetErrorString(e));
+    totals[0] = host[0];
+    totals[1] = host[1];
+    if (host[1] >= MESH_MAX_TRIS) return set_error(KFX_E_RANGE, "kfx_mesh_plan: 2^32/3 triangles or more (32-bit vertex offsets)");
+    return 0;
+}
+
+template <typename CELL, bool SLAB>
+static void mesh_emit_launch(const MeshParams& p, const MeshRange& r, const MeshScratch& s, const ColorGeom& cv, int has_color,
+                             const unsigned long long totals[2], long long* cube_index, unsigned* tri_offset, float* verts,
+                             float* norms, float* colors, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_mesh_compact<CELL>, dim3((unsigned)r.nblk), dim3(256), 0, st, p, r, s.seg, s.base, cube_index, tri_offset,
+                       totals[0], totals[1]);
+    const long long n_active = (long long)totals[0];
+    hipLaunchKernelGGL((k_mc_emit<CELL, SLAB>), dim3((unsigned)((n_active + 127) / 128)), dim3(128), 0, st, p, cv, has_color,
+                       cube_index, tri_offset, n_active, verts, norms, colors);
+}
+
+extern "C" int kfx_mesh_emit(const kfx_volume* vol, int cell, const kfx_slab* slab, int own_lo, int own_hi, const kfx_volume* colorvol,
+                             const void* scratch, size_t scratch_bytes, const unsigned long long totals[2], long long* cube_index,
+                             unsigned* tri_offset, float* verts, float* norms, float* colors, kfx_stream stream)
+{
+    MeshParams p;
+    MeshRange r;
+    if (int e = mesh_setup(p, r, vol, cell, slab, own_lo, own_hi)) return e;
+    if (!scratch || !totals) return set_error(KFX_E_NULL, "kfx_mesh_emit: null scratch or totals");
+    if ((uintptr_t)scratch & 255) return set_error(KFX_E_ALIGN, "kfx_mesh_emit: scratch not 256-byte aligned");
+    const MeshScratch s = mesh_scratch(r, (void*)scratch);
+    if (scratch_bytes < s.bytes) return set_error(KFX_E_SHAPE, "kfx_mesh_emit: scratch smaller than kfx_mesh_scratch_bytes");
+    if (totals[1] >= MESH_MAX_TRIS || totals[0] > totals[1]) return set_error(KFX_E_RANGE, "kfx_mesh_emit: totals out of range");
+    if (totals[0] == 0) return 0;
+    if (!cube_index || !tri_offset || !verts || !norms) return set_error(KFX_E_NULL, "kfx_mesh_emit: null output");
+    if ((((uintptr_t)cube_index) & 7) || (((uintptr_t)tri_offset | (uintptr_t)verts | (uintptr_t)norms | (uintptr_t)colors) & 3))
+        return set_error(KFX_E_ALIGN, "kfx_mesh_emit: output alignment");
+    ColorGeom cv;
+    int has_color = 0;
+    if (!slab)
+        if (int e = color_params(cv, has_color, colorvol, colors)) return e;
+    if (!has_color) cv = ColorGeom{};
+    if (int e = load_tables()) return e;
+    const hipStream_t st = (hipStream_t)stream;
+    // the totals must be this scratch's plan's: the emit kernel trusts the compacted lists to fit the caller's buffers
+    unsigned long long planned[2];
+    hipError_t he = hipMemcpyAsync(planned, s.totals, sizeof(planned), hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess) he = hipStreamSynchronize(st);
+    if (he != hipSuccess) return set_error((int)he, hipGetErrorString(he));
+    if (planned[0] != totals[0] || planned[1] != totals[1]) return set_error(KFX_E_RANGE, "kfx_mesh_emit: totals are not the plan's");
+    if (cell == KFX_CELL_F32) {
+        if (slab) mesh_emit_launch<RayF32, true>(p, r, s, cv, 0, totals, cube_index, tri_offset, verts, norms, nullptr, st);
+        else mesh_emit_launch<RayF32, false>(p, r, s, cv, has_color, totals, cube_index, tri_offset, verts, norms, colors, st);
+    } else {
+        if (slab) mesh_emit_launch<RayF16, true>(p, r, s, cv, 0, totals, cube_index, tri_offset, verts, norms, nullptr, st);
+        else mesh_emit_launch<RayF16, false>(p, r, s, cv, has_color, totals, cube_index, tri_offset, verts, norms, colors, st);
+    }
+    return check_launch("kfx_mesh_emit");
 }

@@ -1,11 +1,12 @@
 """Mesh extraction: roo::SaveMesh (reference include/kangaroo/MarchingCubes.h:205-262) with the volume left in HBM.
 
 The reference copies the volume to the host, marches the (w-1)(h-1)(d-1) cubes one by one and hands the lists to
-Assimp's PLY exporter.  Here: kfx_mc_count (triangles per cube, in the reference's emission order) -> exclusive
-compaction of the active cubes and prefix sum over them (torch.nonzero / torch.cumsum on the device) -> kfx_mc_emit (one
-thread per active cube: vertices, normals, grey colours into their slots).  The
-arrays equal the host algorithm's element for element (tests compare with the oracle); only the finished arrays
-cross PCIe.
+Assimp's PLY exporter.  Here (include/kfx_mesh.h): kfx_mesh_plan counts active cubes and triangles per z-segment of a column
+and scans them in the reference's emission order on the device (one 16-byte read-back: the totals) -> kfx_mesh_emit compacts
+the active cubes at their scanned offsets and emits them (one thread per active cube: vertices, normals, grey colours into
+their slots).  fp32 (SDF_t) and half (SDF_h, meshed as the exactly widened volume) cells; the whole volume or one Z-slab of a
+partitioned one.  The arrays equal the host algorithm's element for element (tests compare with the oracle); only the
+finished arrays cross PCIe.
 
 Case tables: kangaroo_amd/csrc/mc_tables.inc, derived by scripts/gen_mc_tables.py.  Their boundary loops and
 winding agree with the classic tables the reference uses in all 256 cases; 158 cases split a polygon along a
@@ -25,28 +26,48 @@ from . import _lib
 from .roo import _stream
 
 
-def ExtractMesh(vol, colorVol=None, stream=None):
-    """Returns (verts, norms, colors): float32 device tensors of shape (3T, 3), (3T, 3) and (3T, 4) or None."""
+CELL = {"f32": 0, "f16": 1}   # KFX_CELL_F32 / KFX_CELL_F16
+
+
+def ExtractMesh(vol, colorVol=None, stream=None, slab=None, with_index=False):
+    """Returns (verts, norms, colors): float32 device tensors of shape (3T, 3), (3T, 3) and (3T, 4) or None.
+
+    vol.kind "f32" or "f16".  slab = (full_d, z_offset, full_zmin, full_zmax, own_lo, own_hi): `vol` holds planes
+    [z_offset, z_offset + vol.d) of that volume and the cubes with lower plane in [own_lo, min(own_hi, full_d - 1)) are meshed,
+    each triangle bit-identical to the single-volume mesh's (no colour).  with_index: also return cube_index (int64, global) and
+    tri_offset (int32: the first triangle of each active cube, uint32 bits)."""
     L = _lib.load()
-    cx, cy, cz = vol.w - 1, vol.h - 1, vol.d - 1
-    dev = vol.storage.device
-    counts = torch.empty(cx * cy * cz, dtype=torch.uint8, device=dev)
-    _lib.check(L.kfx_mc_count(vol.ref(), C.c_void_p(counts.data_ptr()), _stream(stream)))
-    active = torch.nonzero(counts).reshape(-1)                        # cubes with triangles, ascending = emission order
-    ca = counts[active].to(torch.int64)                               # the scan only needs them: empty cubes add nothing
-    incl = torch.cumsum(ca, 0)
-    ntri = int(incl[-1].item()) if incl.numel() else 0
-    if ntri >= 2 ** 32 // 3:
+    if vol.kind not in CELL:
+        raise ValueError("ExtractMesh: volume kind %r (fp32 or half SDF cells)" % vol.kind)
+    cell, dev = CELL[vol.kind], vol.storage.device
+    sl, lo, hi = None, 0, 0
+    if slab is not None:
+        full_d, z_offset, zmin, zmax, lo, hi = slab
+        sl = C.byref(_lib.KfxSlab(int(full_d), int(z_offset), float(zmin), float(zmax)))
+        colorVol = None
+    nbytes = L.kfx_mesh_scratch_bytes(vol.ref(), cell, sl, int(lo), int(hi))
+    if nbytes == 0:
+        _lib.check(L.kfx_mesh_plan(vol.ref(), cell, sl, int(lo), int(hi), None, 0, None, None))   # the reason
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    totals = (C.c_ulonglong * 2)()
+    st = _stream(stream)
+    code = L.kfx_mesh_plan(vol.ref(), cell, sl, int(lo), int(hi), C.c_void_p(scratch.data_ptr()), nbytes, totals, st)
+    if code == -4 and totals[1] >= 2 ** 32 // 3:   # KFX_E_RANGE
         raise ValueError("mesh too large for 32-bit vertex offsets")
-    tri_offset = (incl - ca).to(torch.int32)                          # exclusive prefix sum at those cubes
+    _lib.check(code)
+    na, ntri = int(totals[0]), int(totals[1])
+    cube_index = torch.empty(na, dtype=torch.int64, device=dev)
+    tri_offset = torch.empty(na, dtype=torch.int32, device=dev)
     verts = torch.empty((3 * ntri, 3), dtype=torch.float32, device=dev)
     norms = torch.empty((3 * ntri, 3), dtype=torch.float32, device=dev)
     has_color = colorVol is not None and min(colorVol.w, colorVol.h, colorVol.d) >= 8
     colors = torch.empty((3 * ntri, 4), dtype=torch.float32, device=dev) if has_color else None
-    if ntri:
-        _lib.check(L.kfx_mc_emit(vol.ref(), colorVol.ref() if has_color else None, C.c_void_p(active.data_ptr()),
-                                 C.c_void_p(tri_offset.data_ptr()), int(active.numel()), C.c_void_p(verts.data_ptr()),
-                                 C.c_void_p(norms.data_ptr()), C.c_void_p(colors.data_ptr()) if has_color else None, _stream(stream)))
+    if na:
+        _lib.check(L.kfx_mesh_emit(vol.ref(), cell, sl, int(lo), int(hi), colorVol.ref() if has_color else None, C.c_void_p(scratch.data_ptr()),
+                                   nbytes, totals, C.c_void_p(cube_index.data_ptr()), C.c_void_p(tri_offset.data_ptr()), C.c_void_p(verts.data_ptr()),
+                                   C.c_void_p(norms.data_ptr()), C.c_void_p(colors.data_ptr()) if has_color else None, st))
+    if with_index:
+        return verts, norms, colors, cube_index, tri_offset
     return verts, norms, colors
 
 
@@ -75,9 +96,10 @@ def write_ply(path, verts, norms, colors=None, binary=True):
                 f.write(("3 %d %d %d\n" % (i, i + 1, i + 2)).encode())
 
 
-def SaveMesh(filename, vol, colorVol=None, binary=True):
-    """SaveMesh(filename, vol[, volColor]) (MarchingCubes.h:246-262): writes filename + ".ply"; returns the triangle count."""
-    verts, norms, colors = ExtractMesh(vol, colorVol)
+def SaveMesh(filename, vol, colorVol=None, binary=True, slab=None):
+    """SaveMesh(filename, vol[, volColor]) (MarchingCubes.h:246-262): writes filename + ".ply"; returns the triangle count.
+    fp32 or half volumes; slab: ExtractMesh's."""
+    verts, norms, colors = ExtractMesh(vol, colorVol, slab=slab)
     torch.cuda.synchronize() if verts.is_cuda else None
     write_ply(filename + ".ply", verts.cpu().numpy(), norms.cpu().numpy(), None if colors is None else colors.cpu().numpy(), binary)
     return len(verts) // 3

@@ -635,6 +635,27 @@ class SlabPipeline(FramePipeline):
             ops.append(dist.P2POp(dist.irecv, self.vol.planes(own1, own1 + hi_ghost), self.rank + 1))
         self._p2p(ops)
 
+    def ExtractMesh(self):
+        """This rank's part of the model's mesh (include/kfx_mesh.h): the cubes whose lower plane it owns, [z0, min(z1, D - 1)),
+        every triangle bit-identical to the single-volume mesh's, in emission order; (verts, norms) device tensors.  No colour.
+        With halo = "exchange" the ghost planes the normals read are refreshed first (a collective step: every rank calls)."""
+        from . import mesh
+        if self.sframe is not None:
+            self.wait_composite()
+        elif self.halo == "exchange" and self.world > 1:
+            self.exchange_halos()     # (the C driver's fuse step leaves them current itself)
+        D = self.dims[2]
+        slab = (D, self.s0, float(self.full_boxmin[2]), float(self.full_boxmax[2]), self.z0, self.z1)
+        verts, norms, _ = mesh.ExtractMesh(self.vol, slab=slab)
+        return verts, norms
+
+    def SaveMesh(self, prefix, binary=True):
+        """Writes this rank's part as prefix.r<rank>.ply; returns its triangle count."""
+        from . import mesh
+        verts, norms = self.ExtractMesh()
+        mesh.write_ply("%s.r%d.ply" % (prefix, self.rank), verts.cpu().numpy(), norms.cpu().numpy(), None, binary)
+        return len(verts) // 3
+
     def raycast(self, T_wc):
         """raycast = "composite": every rank marches its own slab from the slab's entry point and the nearest
         hit wins (one MIN + one SUM all-reduce; rays re-enter each slab with a fresh step, so depths can differ
