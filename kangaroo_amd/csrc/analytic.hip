@@ -195,10 +195,8 @@ extern "C" int kfx_sdf_distance(const kfx_image* dist, const kfx_image* depth, c
     if (depth->w == 0 || depth->h == 0) return 0;
     if (dist->w < depth->w || dist->h < depth->h || dist->pitch < depth->w * 4 || depth->pitch < depth->w * 4)
         return set_error(KFX_E_SHAPE, "SdfDistance: image sizes");
-    if (vol->w < 2 || vol->h < 2 || vol->d < 2 || vol->pitch < vol->w * 8 || vol->img_pitch < vol->pitch * (vol->h - 1) + vol->w * 8)
-        return set_error(KFX_E_SHAPE, "SdfDistance: volume");
-    if ((((uintptr_t)dist->ptr | dist->pitch | (uintptr_t)depth->ptr | depth->pitch) & 3) || (((uintptr_t)vol->ptr | vol->pitch | vol->img_pitch) & 7))
-        return set_error(KFX_E_ALIGN, "SdfDistance: alignment");
+    if (int e = check_volume(vol, 8, 2, VOLUME_ANY_DIM, "SdfDistance")) return e;
+    if (((uintptr_t)dist->ptr | dist->pitch | (uintptr_t)depth->ptr | depth->pitch) & 3) return set_error(KFX_E_ALIGN, "SdfDistance: image alignment");
     DistParams p;
     set_geometry(p, vol);
     p.optr = (unsigned char*)dist->ptr; p.opitch = dist->pitch;

@@ -21,7 +21,6 @@
 // Packed v_pk_*_f32 arithmetic was tried for the exact mode and dropped: on gfx950 a packed
 // op issues in 4 cycles, twice a scalar op, so it only saves issue slots (0.755 -> 0.726 ms).
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 
 #include <sys/syscall.h>
@@ -32,6 +31,7 @@
 #include <type_traits>
 
 #include "kfx_device.h"
+#include "host_args.h"
 
 // The tiled kernels stage their pixel rectangle by LDS-DMA from a packed texel image (round 6: k_pack_texels / the fused preprocess of
 // kfx_frame_step write it; C3 / S_room SdfFuse 0.400 -> 0.361 ms, S_room 0.2737 -> 0.2645, S_full 0.3490 -> 0.3452, same bits:
@@ -1656,17 +1656,6 @@ static void* tex_scratch(size_t bytes, hipStream_t stream)
     return pool.get(bytes, stream);
 }
 
-static int check_volume(const kfx_volume* vol, size_t cell = 8)
-{
-    if (!vol || !vol->ptr) return set_error(KFX_E_NULL, "volume is null");
-    if (vol->w == 0 || vol->h == 0 || vol->d == 0 || vol->w > 65535 || vol->h > 65535 || vol->d > 65535)
-        return set_error(KFX_E_SHAPE, "volume dimensions");
-    if (vol->pitch < vol->w * cell || vol->img_pitch < vol->pitch * (vol->h - 1) + vol->w * cell)
-        return set_error(KFX_E_SHAPE, "volume pitch smaller than a row / slice");
-    if (((uintptr_t)vol->ptr | vol->pitch | vol->img_pitch) & (cell - 1)) return set_error(KFX_E_ALIGN, "volume not aligned to its cell size");
-    return 0;
-}
-
 static VolView vol_view(const kfx_volume* vol)
 {
     VolView v;
@@ -1704,9 +1693,9 @@ static bool pos_div_verified(int axis, float size, int dim)
 
 static int fuse_params(FuseParams& p, bool* small_images, const kfx_volume* vol, const kfx_image* depth,
                        const kfx_image* norm, const float T_cw[12], const float K[4], float trunc_dist, float max_w,
-                       float mincostheta, unsigned flags, size_t cell = 8, const kfx_slab* slab = nullptr)
+                       float mincostheta, unsigned flags, size_t cell, const kfx_slab* slab)
 {
-    if (int e = check_volume(vol, cell)) return e;
+    if (int e = check_volume(vol, cell, 1, VOLUME_MAX_DIM, "SdfFuse")) return e;
     if (!depth || !norm || !depth->ptr || !norm->ptr || !T_cw || !K) return set_error(KFX_E_NULL, "SdfFuse: null argument");
     if (depth->w < 4 || depth->h < 4 || norm->w < depth->w || norm->h < depth->h)
         return set_error(KFX_E_SHAPE, "SdfFuse: depth/normal image dimensions");
@@ -1766,15 +1755,15 @@ static int fuse_params(FuseParams& p, bool* small_images, const kfx_volume* vol,
     // a volume's extents do not change between frames), so the positions are the reference's by construction
     p.inv_w1 = 1.0f / p.w1;
     p.inv_h1 = 1.0f / p.h1;
-    static const int pos_div_env = [] { const char* e = getenv("KFX_FUSE_POS_DIV"); return e ? atoi(e) : 1; }();
+    static const int pos_div_env = env_int("KFX_FUSE_POS_DIV", 1);
     p.pos_div = (pos_div_env && vol->w >= 2 && vol->h >= 2 && pos_div_verified(0, p.size.x, (int)vol->w) && pos_div_verified(1, p.size.y, (int)vol->h)) ? 1 : 0;
-    static const int swizzle_env = [] { const char* e = getenv("KFX_FUSE_XCD_SWIZZLE"); const int v = e ? atoi(e) : 1; return v < 0 ? 0 : (v > 8 ? 8 : v); }();
+    static const int swizzle_env = env_int("KFX_FUSE_XCD_SWIZZLE", 1, 0, 8);
     p.xcd_swizzle = swizzle_env;
-    static const int cull_env = [] { const char* e = getenv("KFX_FUSE_CULL"); return e ? atoi(e) : 1; }();
+    static const int cull_env = env_int("KFX_FUSE_CULL", 1);
     p.fuse_cull = cull_env;
     // launch-wide half of the operand-range test of the exact kernel's shared-reciprocal arithmetic (finish_shared);
     // KFX_FUSE_EXACT_SHARED=0 keeps hipcc's own division / square-root expansions (A/B, and the parity suite runs both)
-    static const int shared_env = [] { const char* e = getenv("KFX_FUSE_EXACT_SHARED"); return e ? atoi(e) : 1; }();
+    static const int shared_env = env_int("KFX_FUSE_EXACT_SHARED", 1);
     const float afu = fabsf(p.K.fu), afv = fabsf(p.K.fv);
     p.z_rev = 0; p.keep_z0 = 0; p.keep_z1 = 0;
     p.exact_shared = shared_env && afu >= 0x1p-20f && afu <= 0x1p20f && afv >= 0x1p-20f && afv <= 0x1p20f &&
@@ -1804,7 +1793,7 @@ static int tile_cap(const FuseParams& p, const Pose& T, const Intr& K, int z0, i
     // 2.6 m) 0.286 -> 0.283 ms; with 1216 texels everywhere S_room loses (0.291 ms: the near bricks gather from global
     // memory).  The bit-exact kernel holds 78 VGPRs = 6 waves per SIMD whatever the tile and only pays for the extra launch
     // boundary (S_room 0.391 -> 0.405 ms), so it keeps 1536.
-    static const float r_small = [] { const char* e = getenv("KFX_FUSE_R_SMALL"); return e ? (float)atof(e) : 0.85f; }();
+    static const float r_small = env_float("KFX_FUSE_R_SMALL", 0.85f);
     if (small_ok && !(r > r_small)) return 1216;
     if (!(r > 1.3f)) return 1536;
     const float want = 1536.f * (r / 1.05f) * (r / 1.05f);
@@ -1823,11 +1812,12 @@ static int tile_cap(const FuseParams& p, const Pose& T, const Intr& K, int z0, i
 // rectangle -- about (73 r + 5) x (14.7 r + 5) texels -- fits 768 texels, the 24 KiB that keep six workgroups on a CU
 // (r <= 0.64; KFX_FUSE_DXT=0 switches it off, a positive value sets the limit in hundredths).
 struct TilePlan { int small_brick, cap, dxt; };
+static bool operator==(const TilePlan& a, const TilePlan& b) { return a.cap == b.cap && a.small_brick == b.small_brick && a.dxt == b.dxt; }
 static TilePlan tile_plan(const FuseParams& p, const Pose& T, const Intr& K, int z0, int z1, int brick_env, bool fast)
 {
     const float r = px_per_voxel(p, T, K, z0, z1);
     const int small_brick = brick_env < 0 ? (r > 1.3f ? 1 : 0) : (brick_env != 0);
-    static const float r_dxt = [] { const char* e = getenv("KFX_FUSE_DXT"); return e ? 0.01f * (float)atoi(e) : 0.64f; }();
+    static const float r_dxt = 0.01f * (float)env_int("KFX_FUSE_DXT", 64);   // (0.01f * 64 is 0.64f exactly)
     if (!small_brick && !fast && r_dxt > 0.f && r > 0.f && !(r > r_dxt)) return TilePlan{0, 768, 1};
     if (!small_brick) return TilePlan{0, tile_cap(p, T, K, z0, z1, fast), 0};
     // three quarters of the worst-case rectangle: most bricks are nearer the optical axis than the image corner, and a
@@ -1838,6 +1828,29 @@ static TilePlan tile_plan(const FuseParams& p, const Pose& T, const Intr& K, int
     for (int c : caps)
         if (want <= (float)c) return TilePlan{small_brick, c, 0};
     return TilePlan{small_brick, 3328, 0};
+}
+
+// KFX_FUSE_TILED=0 forces the global-gather kernels (SdfFuse and its colour form)
+static int fuse_tiled_env()
+{
+    static const int tiled = env_int("KFX_FUSE_TILED", 1);
+    return tiled;
+}
+
+// The planes of a view are launched in z-ranges of whole steps of FUSE_ZSTEP planes that want the same plan (brick, LDS
+// capacities: plan_of(za, zb), evaluated per step).  Returns the end of the range that starts at z0, its plan in `plan`.
+constexpr int FUSE_ZSTEP = 64;
+template <typename PLAN, typename F>
+static int merged_range_end(int z0, int Z, PLAN& plan, F plan_of)
+{
+    int z1 = z0 + FUSE_ZSTEP < Z ? z0 + FUSE_ZSTEP : Z;
+    plan = plan_of(z0, z1);
+    while (z1 < Z) { // extend over following steps that want the same plan
+        const int z2 = z1 + FUSE_ZSTEP < Z ? z1 + FUSE_ZSTEP : Z;
+        if (!(plan_of(z1, z2) == plan)) break;
+        z1 = z2;
+    }
+    return z1;
 }
 
 template <typename CELL>
@@ -1867,10 +1880,9 @@ static int fuse_launch(const kfx_volume* vol, const kfx_image* depth, const kfx_
     const bool vec2 = (p.X % 2 == 0) && ((((uintptr_t)vol->ptr | vol->pitch | vol->img_pitch) & (2 * CELL::BYTES - 1)) == 0);
     const bool fast = math_mode() == KFX_MATH_FAST;
     hipStream_t s = (hipStream_t)stream;
-    // tuning / A-B knobs (read once): KFX_FUSE_TILED=0 forces the global-gather kernel,
-    // KFX_FUSE_CAP sets the LDS tile capacity in texels (16 B each, at most 3968)
-    static const int tiled = [] { const char* e = getenv("KFX_FUSE_TILED"); return e ? atoi(e) : 1; }();
-    static const int cap_env = [] { const char* e = getenv("KFX_FUSE_CAP"); const int v = e ? atoi(e) : 0; return v <= 0 ? 0 : (v < 64 ? 64 : (v > 3968 ? 3968 : v)); }();  // <= 62 KiB: dynamic + static LDS stay below the 64 KiB launch limit
+    // tuning / A-B knobs (read once): KFX_FUSE_CAP sets the LDS tile capacity in texels (16 B each, at most 3968)
+    const int tiled = fuse_tiled_env();
+    static const int cap_env = [] { const int v = env_int("KFX_FUSE_CAP", 0); return v <= 0 ? 0 : (v < 64 ? 64 : (v > 3968 ? 3968 : v)); }();  // <= 62 KiB: dynamic + static LDS stay below the 64 KiB launch limit
     if (summary && !(track && tiled && vec2 && small_images)) {
         // this launch cannot keep the summary current (unaligned view, untiled kernel): nothing is known afterwards
         if (int e = kfx_sdf_summary_invalidate(summary, stream)) return e;
@@ -1881,7 +1893,7 @@ static int fuse_launch(const kfx_volume* vol, const kfx_image* depth, const kfx_
         // slices per iteration: 2 in fast mode (memory-bound: more reads in flight), 4 where the large LDS tile leaves
         // only 3 workgroups per CU (1280x960 at 512^3: 0.568 -> 0.538 ms; at 6 workgroups per CU 4 is slower), 1 in exact
         // mode (VALU-bound)
-        static const int zu_env = [] { const char* e = getenv("KFX_FUSE_ZU"); return e ? atoi(e) : 0; }();
+        static const int zu_env = env_int("KFX_FUSE_ZU", 0);
         // LDS tile capacity per z-range.  A brick's pixel rectangle grows with the pixels-per-voxel ratio
         // r = f * voxel / Z: 1536 texels (24 KiB, 6 workgroups per CU) hold it up to r ~ 1.3; beyond that more
         // bricks would fall back to global gathers, so the capacity grows with r^2 up to 3072 texels (48 KiB,
@@ -1891,7 +1903,7 @@ static int fuse_launch(const kfx_volume* vol, const kfx_image* depth, const kfx_
         // Beyond r = 1.3 the brick narrows to 32 x 8 x 16 voxels instead (tile_plan; KFX_FUSE_BRICK=0 / 1 forces the wide /
         // narrow brick): its rectangle fits 25-52 KiB up to r ~ 2.2, where the wide brick needs the full 48 KiB from
         // r ~ 1.5 on and above r ~ 1.9 does not fit at all (those bricks gathered from global memory).
-        static const int brick_env = [] { const char* e = getenv("KFX_FUSE_BRICK"); return e ? atoi(e) : -1; }();
+        static const int brick_env = env_int("KFX_FUSE_BRICK", -1);
         auto plan_for = [&](int z0, int z1) -> TilePlan {
             TilePlan t = tile_plan(p, p.T, p.K, z0, z1, brick_env, fast);
             if (track || CELL::BYTES != 8) { // the difference tile exists for the untracked fp32-cell kernel only
@@ -1900,11 +1912,10 @@ static int fuse_launch(const kfx_volume* vol, const kfx_image* depth, const kfx_
             if (cap_env) { t.cap = cap_env; t.dxt = 0; }
             return t;
         };
-        const int zstep = 64;
         // the difference tile only where it costs no extra launch: every range of the view must want it (S_room at 512^3,
         // whose far third qualifies, lost 4 % to the third launch boundary; S_full gains 3 %)
         bool all_dxt = true;
-        for (int z = 0; z < p.Z; z += zstep) all_dxt = all_dxt && plan_for(z, z + zstep < p.Z ? z + zstep : p.Z).dxt != 0;
+        for (int z = 0; z < p.Z; z += FUSE_ZSTEP) all_dxt = all_dxt && plan_for(z, z + FUSE_ZSTEP < p.Z ? z + FUSE_ZSTEP : p.Z).dxt != 0;
         auto plan_of = [&](int za, int zb) -> TilePlan {
             TilePlan t = plan_for(za, zb);
             if (t.dxt && !all_dxt) { t = TilePlan{0, tile_cap(p, p.T, p.K, za, zb, fast), 0}; if (cap_env) t.cap = cap_env; }
@@ -1914,7 +1925,7 @@ static int fuse_launch(const kfx_volume* vol, const kfx_image* depth, const kfx_
         // KFX_FUSE_KEEP_MB (default 256) of a sweep with ordinary loads: those planes stay in the 256 MiB memory-side cache
         // and the next sweep starts on them.  (The volume is otherwise streamed nontemporally, which leaves nothing behind;
         // untracked launches belong to loops whose plain march reads ~500 MB of the volume in between and evicts the tail.)
-        static const int keep_mb = [] { const char* e = getenv("KFX_FUSE_KEEP_MB"); return e ? atoi(e) : 256; }();
+        static const int keep_mb = env_int("KFX_FUSE_KEEP_MB", 256);
         const int rev = (track && keep_mb > 0) ? (int)(summary->sweeps++ & 1u) : 0;
         int keep_lo = 0, keep_hi = 0;   // planes read with ordinary loads (this view's local coordinates)
         if (track && keep_mb > 0) {
@@ -1928,14 +1939,8 @@ static int fuse_launch(const kfx_volume* vol, const kfx_image* depth, const kfx_
         Range ranges[64];
         int n_ranges = 0;
         for (int z0 = 0; z0 < p.Z;) {
-            int z1 = z0 + zstep < p.Z ? z0 + zstep : p.Z;
-            const TilePlan plan = plan_of(z0, z1);
-            while (z1 < p.Z) { // extend over following ranges that want the same brick and capacity
-                const int z2 = z1 + zstep < p.Z ? z1 + zstep : p.Z;
-                const TilePlan nxt = plan_of(z1, z2);
-                if (nxt.cap != plan.cap || nxt.small_brick != plan.small_brick || nxt.dxt != plan.dxt) break;
-                z1 = z2;
-            }
+            TilePlan plan;
+            const int z1 = merged_range_end(z0, p.Z, plan, plan_of);
             if (n_ranges == 64) { ranges[63].z1 = p.Z; break; } // (never: a range is at least 64 planes and plans change a few times at most)
             ranges[n_ranges++] = Range{z0, z1, plan};
             z0 = z1;
@@ -1990,7 +1995,7 @@ static int fuse_launch(const kfx_volume* vol, const kfx_image* depth, const kfx_
                 // twice the waves behind one staged rectangle; C3 / S_room 0.4182 -> 0.4237 of peak, interleaved A/B; below that
                 // size the shorter waves' prologues cost more than the residency buys (-1 %).  KFX_FUSE_NW8=<texels> moves the
                 // threshold (0: never).  Same bits.
-                static const int nw8_from = [] { const char* e = getenv("KFX_FUSE_NW8"); return e ? atoi(e) : 2048; }();
+                static const int nw8_from = env_int("KFX_FUSE_NW8", 2048);
                 if (fast && nw8_from > 0 && cap_px > nw8_from) {
                     hipLaunchKernelGGL((k_sdf_fuse_tiled<true, 2, CELL, 16, 2, 16, false, false, 8>), grid, dim3(512), lds, s, q, cap_px);
                     continue;
@@ -2094,7 +2099,7 @@ extern "C" int kfx_sdf_fuse_count(const kfx_volume* vol, const kfx_image* depth,
     if (!d_count) return set_error(KFX_E_NULL, "kfx_sdf_fuse_count: null counter");
     FuseParams p;
     bool small_images = false;
-    if (int e = fuse_params(p, &small_images, vol, depth, norm, T_cw, K, trunc_dist, 0.f, mincostheta, flags)) return e;
+    if (int e = fuse_params(p, &small_images, vol, depth, norm, T_cw, K, trunc_dist, 0.f, mincostheta, flags, 8, nullptr)) return e;
     if (p.X == 0 || p.Y == 0 || p.Z == 0) return 0;
     const int bx = ceil_div(p.X, 64), by = ceil_div(p.Y, FUSE_ROWS), bz = ceil_div(p.Z, FUSE_ZC);
     const long long total = (long long)bx * by * bz;
@@ -2107,7 +2112,7 @@ extern "C" int kfx_sdf_fuse_count(const kfx_volume* vol, const kfx_image* depth,
 
 extern "C" int kfx_sdf_reset(const kfx_volume* vol, float trunc_dist, kfx_stream stream)
 {
-    if (int e = check_volume(vol)) return e;
+    if (int e = check_volume(vol, 8, 1, VOLUME_MAX_DIM, "SdfReset")) return e;
     const size_t span_bytes = (vol->d - 1) * vol->img_pitch + (vol->h - 1) * vol->pitch + vol->w * 8;
     const size_t n = span_bytes / 8;
     const int blocks = (int)std::min<size_t>((n / 2 + 255) / 256 + 1, 256 * 32);
@@ -2121,7 +2126,7 @@ extern "C" int kfx_sdf_reset(const kfx_volume* vol, float trunc_dist, kfx_stream
 
 extern "C" int kfx_sdf_sphere(const kfx_volume* vol, const float center[3], float r, kfx_stream stream)
 {
-    if (int e = check_volume(vol)) return e;
+    if (int e = check_volume(vol, 8, 1, VOLUME_MAX_DIM, "SdfSphere")) return e;
     if (!center) return set_error(KFX_E_NULL, "SdfSphere: null center");
     const int X = (int)(vol->w / 8) * 8, Y = (int)(vol->h / 8) * 8, Z = (int)(vol->d / 8) * 8;
     if (X == 0 || Y == 0 || Z == 0) return 0;
@@ -2133,7 +2138,7 @@ extern "C" int kfx_sdf_sphere(const kfx_volume* vol, const float center[3], floa
 
 extern "C" int kfx_sdf_reset_h(const kfx_volume* vol, float trunc_dist, kfx_stream stream)
 {
-    if (int e = check_volume(vol, 4)) return e;
+    if (int e = check_volume(vol, 4, 1, VOLUME_MAX_DIM, "SdfReset")) return e;
     const size_t span_bytes = (vol->d - 1) * vol->img_pitch + (vol->h - 1) * vol->pitch + vol->w * 4;
     const size_t n = span_bytes / 4;
     const unsigned pattern = (unsigned)__half_as_ushort(__float2half_rn(trunc_dist)); // {val = trunc, w = 0}
@@ -2144,7 +2149,7 @@ extern "C" int kfx_sdf_reset_h(const kfx_volume* vol, float trunc_dist, kfx_stre
 
 extern "C" int kfx_sdf_sphere_h(const kfx_volume* vol, const float center[3], float r, kfx_stream stream)
 {
-    if (int e = check_volume(vol, 4)) return e;
+    if (int e = check_volume(vol, 4, 1, VOLUME_MAX_DIM, "SdfSphere")) return e;
     if (!center) return set_error(KFX_E_NULL, "SdfSphere: null center");
     const int X = (int)(vol->w / 8) * 8, Y = (int)(vol->h / 8) * 8, Z = (int)(vol->d / 8) * 8;
     if (X == 0 || Y == 0 || Z == 0) return 0;
@@ -2161,8 +2166,8 @@ extern "C" int kfx_sdf_fuse_color(const kfx_volume* vol, const kfx_volume* color
 {
     FuseParams p;
     bool small_images = false;
-    if (int e = fuse_params(p, &small_images, vol, depth, norm, T_cw, K, trunc_dist, max_w, mincostheta, flags | KFX_FUSE_FULL_EXTENT)) return e;
-    if (int e = check_volume(colorvol, 4)) return e;
+    if (int e = fuse_params(p, &small_images, vol, depth, norm, T_cw, K, trunc_dist, max_w, mincostheta, flags | KFX_FUSE_FULL_EXTENT, 8, nullptr)) return e;
+    if (int e = check_volume(colorvol, 4, 1, VOLUME_MAX_DIM, "SdfFuse(colour)")) return e;
     if (!img || !img->ptr || !T_iw || !Kimg) return set_error(KFX_E_NULL, "SdfFuse(colour): null argument");
     if (colorvol->w < vol->w || colorvol->h < vol->h || colorvol->d < vol->d) return set_error(KFX_E_SHAPE, "SdfFuse(colour): colour volume smaller than the SDF volume");
     if (img->w < 4 || img->h < 4 || img->pitch < img->w * 3) return set_error(KFX_E_SHAPE, "SdfFuse(colour): rgb image dimensions");
@@ -2182,24 +2187,18 @@ extern "C" int kfx_sdf_fuse_color(const kfx_volume* vol, const kfx_volume* color
     q.ihb = (float)img->h - 2.0f;
     const bool fast = math_mode() == KFX_MATH_FAST;
     hipStream_t s = (hipStream_t)stream;
-    static const int tiled = [] { const char* e = getenv("KFX_FUSE_TILED"); return e ? atoi(e) : 1; }();
     // two voxels per lane: even extent, 16-byte aligned SDF rows, 8-byte aligned colour rows
     const bool vec2 = (p.X % 2 == 0) && ((((uintptr_t)vol->ptr | vol->pitch | vol->img_pitch) & 15) == 0) &&
                       ((((uintptr_t)colorvol->ptr | colorvol->pitch | colorvol->img_pitch) & 7) == 0);
-    if (tiled && vec2) {
+    if (fuse_tiled_env() && vec2) {
         // per z-range LDS capacities as in fuse_launch: the depth / normal tile (16 B texels) by the depth camera's
         // pixels-per-voxel ratio, the RGB tile (4 B texels, a third more room) by the colour camera's
         auto rgb_cap = [&](int a, int b) { const int c = tile_cap(p, q.Ti, q.Ki, a, b) * 4 / 3; return c > 3584 ? 3584 : c; }; // 48 + 14 KiB + statics < 64 KiB
-        const int zstep = 64;
         int z0 = 0;
         while (z0 < p.Z) {
-            int z1 = z0 + zstep < p.Z ? z0 + zstep : p.Z;
-            const int cap_px = tile_cap(p, p.T, p.K, z0, z1), cap_cpx = rgb_cap(z0, z1);
-            while (z1 < p.Z) {
-                const int z2 = z1 + zstep < p.Z ? z1 + zstep : p.Z;
-                if (tile_cap(p, p.T, p.K, z1, z2) != cap_px || rgb_cap(z1, z2) != cap_cpx) break;
-                z1 = z2;
-            }
+            std::pair<int, int> caps;   // {depth / normal tile, RGB tile}
+            const int z1 = merged_range_end(z0, p.Z, caps, [&](int a, int b) { return std::make_pair(tile_cap(p, p.T, p.K, a, b), rgb_cap(a, b)); });
+            const int cap_px = caps.first, cap_cpx = caps.second;
             FuseParams pp = p;
             ColorParams qq = q;
             pp.vptr = p.vptr + (size_t)z0 * p.vimg_pitch;
@@ -2223,7 +2222,7 @@ extern "C" int kfx_sdf_fuse_color(const kfx_volume* vol, const kfx_volume* color
 // SdfReset(BoundedVolume<float>) (cu_sdffusion.cu:166-169): every cell of the span, padding included, = 0.5
 extern "C" int kfx_color_reset(const kfx_volume* colorvol, kfx_stream stream)
 {
-    if (int e = check_volume(colorvol, 4)) return e;
+    if (int e = check_volume(colorvol, 4, 1, VOLUME_MAX_DIM, "SdfReset(colour)")) return e;
     const size_t n = ((colorvol->d - 1) * colorvol->img_pitch + (colorvol->h - 1) * colorvol->pitch + colorvol->w * 4) / 4;
     const int blocks = (int)std::min<size_t>((n + 255) / 256, 256 * 16);
     hipLaunchKernelGGL(k_fill_f32, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (float*)colorvol->ptr, n, 0.5f);

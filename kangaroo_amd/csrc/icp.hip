@@ -11,10 +11,10 @@
 // k*S + l), the levels S < 64 are wave64 lane shifts -- so a block's sum is bit-identical to the
 // reference's.  The sum over blocks (thrust::reduce: order unspecified in the reference) is a fixed order
 // here: thread t of one 256-thread group adds blocks t, t+256, ... in turn, then the same tree.
-#include <cstdlib>
 #include <string.h>
 
 #include "kfx_device.h"
+#include "host_args.h"
 
 namespace kfx {
 
@@ -696,6 +696,13 @@ __global__ __launch_bounds__(256) void k_icp_refine_persistent(const IcpPersiste
 
 static unsigned gcd_u(unsigned a, unsigned b) { return b == 0 ? a : gcd_u(b, a % b); }
 
+// KFX_ICP_MAILBOX=0: no mapped mailbox, the results are copied to the host (kfx_icp_point_plane, kfx_icp_refine)
+static bool icp_mailbox_env()
+{
+    static const bool on = env_int("KFX_ICP_MAILBOX", 1) != 0;
+    return on;
+}
+
 } // namespace kfx
 
 using namespace kfx;
@@ -745,7 +752,7 @@ extern "C" int kfx_icp_point_plane(const kfx_image* Pl, const kfx_image* Pr, con
     // mapped memory: the round-5 path (a copy into a pinned staging word + hipStreamSynchronize).
     struct Mailbox { float* host; float* dev; unsigned seq; };
     thread_local Mailbox mb = {nullptr, nullptr, 0u};
-    static const bool mailbox_env = [] { const char* e = getenv("KFX_ICP_MAILBOX"); return !e || atoi(e) != 0; }();
+    const bool mailbox_env = icp_mailbox_env();
     if (mailbox_env && !mb.host) {
         void* h = nullptr;
         void* d = nullptr;
@@ -832,7 +839,7 @@ static int icp_refine_impl(const kfx_icp_level* levels, int n_levels, float c, f
     // below, which stays the default: measured on MI355X (512^3 tracked frame, C++ loop) the chain takes 0.655 ms per frame, the
     // persistent launch 0.754 (128 workgroups) - 0.844 ms (512) -- a grid-wide barrier across the eight XCDs and a 6 x 6 float64
     // step in every workgroup cost more than the launch boundaries they replace (EXPERIMENTS.md 7.3).
-    static const int persistent_env = [] { const char* e = getenv("KFX_ICP_PERSISTENT"); return e ? atoi(e) : 0; }();
+    static const int persistent_env = env_int("KFX_ICP_PERSISTENT", 0);
     const size_t sums2_off = (state_off + sizeof(RefineState) + 255) / 256 * 256, bar_off = sums2_off + state_off;
     bool fits = persistent_env != 0 && n_levels <= 4 && bar_off + 256 <= workspace->pitch * workspace->h;
     for (int l = 0; l < n_levels && fits; ++l) {
@@ -879,7 +886,7 @@ static int icp_refine_impl(const kfx_icp_level* levels, int n_levels, float c, f
             q.sums[1] = (float*)((unsigned char*)workspace->ptr + sums2_off);
             q.st = st;
             q.bar = (unsigned*)((unsigned char*)workspace->ptr + bar_off);
-            static const int grid_env = [] { const char* e = getenv("KFX_ICP_GRID"); return e ? atoi(e) : 0; }();   // (A/B: cap on the resident workgroups)
+            static const int grid_env = env_int("KFX_ICP_GRID", 0);   // (A/B: cap on the resident workgroups)
             size_t want = (size_t)capacity < most ? (size_t)capacity : most;
             if (grid_env > 0 && (size_t)grid_env < want) want = (size_t)grid_env;
             const unsigned grid = (unsigned)want;
@@ -921,7 +928,7 @@ static int icp_refine_impl(const kfx_icp_level* levels, int n_levels, float c, f
     // (4 us of the stream per frame), no wait for an event (as kfx_icp_point_plane's mailbox; KFX_ICP_MAILBOX=0: the copy below)
     struct Mailbox { double* host; double* dev; unsigned seq; };
     thread_local Mailbox mb = {nullptr, nullptr, 0u};
-    static const bool mailbox_env = [] { const char* e = getenv("KFX_ICP_MAILBOX"); return !e || atoi(e) != 0; }();
+    const bool mailbox_env = icp_mailbox_env();
     if (mailbox_env && !mb.host) {
         void* h = nullptr;
         void* d = nullptr;

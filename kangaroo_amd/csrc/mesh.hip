@@ -46,7 +46,21 @@ __device__ __forceinline__ int corner_dx(int i) { return ((i + 1) >> 1) & 1; }
 __device__ __forceinline__ int corner_dy(int i) { return (i >> 1) & 1; }
 __device__ __forceinline__ int corner_dz(int i) { return i >> 2; }
 
-// values at the 8 corners and the case index; false if a corner is not finite (MarchingCubes.h:58-74).  Half cells are widened
+// the case index of 8 corner values; false if a corner is not finite (MarchingCubes.h:58-74)
+__device__ __forceinline__ bool corner_case(const float v[8], int& flag)
+{
+    bool finite = true;
+    int bits = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        finite = finite && isfinite(v[i]);
+        if (v[i] <= 0.0f) bits |= 1 << i;
+    }
+    flag = bits;
+    return finite;
+}
+
+// values at the 8 corners and their corner_case.  Half cells are widened
 // exactly (SDF_h's operator float), so a half volume's cubes are those of the widened fp32 volume.
 template <typename CELL>
 __device__ __forceinline__ bool cube_case(const MeshParams& p, int x, int y, int z, float v[8], int& flag)
@@ -58,14 +72,7 @@ __device__ __forceinline__ bool cube_case(const MeshParams& p, int x, int y, int
     const float2 a = CELL::pair(r00, x), b = CELL::pair(r10, x), c = CELL::pair(r01, x), d = CELL::pair(r11, x);
     v[0] = a.x; v[1] = a.y; v[2] = b.y; v[3] = b.x;
     v[4] = c.x; v[5] = c.y; v[6] = d.y; v[7] = d.x;
-    bool finite = true;
-    flag = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        finite = finite && isfinite(v[i]);
-        if (v[i] <= 0.0f) flag |= 1 << i;
-    }
-    return finite;
+    return corner_case(v, flag);
 }
 
 // Workgroup = 64 cubes along x, 16 along z, one y.  Corner rows are read x-fastest (coalesced); the counts go
@@ -100,7 +107,7 @@ __global__ __launch_bounds__(256) void k_mc_count(const MeshParams p, unsigned c
 
 // One thread per ACTIVE cube (cube_index lists the cubes with triangles in emission order; tri_offset their first
 // triangle): dense lanes instead of the ~1 % active lanes of a thread-per-cube sweep.  CELL: fp32 or half cells; SLAB: p holds
-// the full volume's geometry over a slab's planes [avail_lo, avail_hi) (virtual base pointer, mesh_slab_geometry).
+// the full volume's geometry over a slab's planes [avail_lo, avail_hi) (virtual base pointer, slab_full_volume).
 template <typename CELL, bool SLAB>
 __global__ __launch_bounds__(128) void k_mc_emit(const MeshParams p, const ColorGeom cv, const int has_color,
                                                  const long long* __restrict__ cube_index, const unsigned* __restrict__ tri_offset,
@@ -188,29 +195,13 @@ static int load_tables()
     return 0;
 }
 
-static int mesh_params(MeshParams& p, const kfx_volume* vol, size_t cell_bytes = 8)
-{
-    if (!vol || !vol->ptr) return set_error(KFX_E_NULL, "SaveMesh: null volume");
-    if (vol->w < 3 || vol->h < 3 || vol->d < 3 || vol->w > 65535 || vol->h > 65535 || vol->d > 65535)
-        return set_error(KFX_E_SHAPE, "SaveMesh: volume dimensions");
-    if (vol->pitch < vol->w * cell_bytes || vol->img_pitch < vol->pitch * (vol->h - 1) + vol->w * cell_bytes) return set_error(KFX_E_SHAPE, "SaveMesh: volume pitch");
-    if (((uintptr_t)vol->ptr | vol->pitch | vol->img_pitch) & (cell_bytes - 1)) return set_error(KFX_E_ALIGN, "SaveMesh: alignment");
-    set_geometry(p, vol);
-    set_voxel_size(p, vol);
-    p.cx = (int)vol->w - 1; p.cy = (int)vol->h - 1; p.cz = (int)vol->d - 1;
-    p.avail_lo = 0; p.avail_hi = (int)vol->d;
-    return 0;
-}
-
 // the colour volume of an emit: sampled only when it IsValid(), every dimension >= 8 (BoundedVolume.h:84-87)
 static int color_params(ColorGeom& cv, int& has_color, const kfx_volume* colorvol, const float* colors)
 {
     cv = ColorGeom{};
     has_color = colorvol && colorvol->ptr && colors && colorvol->w >= 8 && colorvol->h >= 8 && colorvol->d >= 8;
     if (has_color) {
-        if (colorvol->pitch < colorvol->w * 4 || colorvol->img_pitch < colorvol->pitch * (colorvol->h - 1) + colorvol->w * 4)
-            return set_error(KFX_E_SHAPE, "SaveMesh: colour volume pitch");
-        if (((uintptr_t)colorvol->ptr | colorvol->pitch | colorvol->img_pitch) & 3) return set_error(KFX_E_ALIGN, "SaveMesh: colour volume alignment");
+        if (int e = check_volume(colorvol, 4, 8, VOLUME_ANY_DIM, "SaveMesh(colour)")) return e;
         set_geometry(cv, colorvol);
     }
     return 0;
@@ -245,28 +236,31 @@ struct MeshRange {
 
 __device__ __forceinline__ unsigned seg_pack(unsigned active, unsigned tris) { return (active << 9) | tris; }
 
+// The cubes [za, zb) of column (x, y) from the bottom up, plane z + 1's corner pairs kept as the next cube's plane z: each(z, n)
+// gets every cube's plane and triangle count.  Plan and emit both walk with this, so they agree on which cubes are active.
+template <typename CELL, typename F>
+__device__ __forceinline__ void walk_segment(const MeshParams& p, int x, int y, int za, int zb, F each)
+{
+    float2 a = CELL::pair(rowp(p.vol, y, za), x), b = CELL::pair(rowp(p.vol, y + 1, za), x);
+    for (int z = za; z < zb; ++z) {
+        const float2 c = CELL::pair(rowp(p.vol, y, z + 1), x), d = CELL::pair(rowp(p.vol, y + 1, z + 1), x);
+        const float v[8] = {a.x, a.y, b.y, b.x, c.x, c.y, d.y, d.x};   // cube_case's corner order
+        int flag;
+        each(z, corner_case(v, flag) ? c_num_tris[flag] : 0u);
+        a = c;
+        b = d;
+    }
+}
+
 // active cubes and triangles of the cubes [za, zb) of column (x, y)
 template <typename CELL>
 __device__ __forceinline__ unsigned segment_count(const MeshParams& p, int x, int y, int za, int zb)
 {
-    float2 a = CELL::pair(rowp(p.vol, y, za), x), b = CELL::pair(rowp(p.vol, y + 1, za), x);
     unsigned active = 0, tris = 0;
-    for (int z = za; z < zb; ++z) {
-        const float2 c = CELL::pair(rowp(p.vol, y, z + 1), x), d = CELL::pair(rowp(p.vol, y + 1, z + 1), x);
-        const float v[8] = {a.x, a.y, b.y, b.x, c.x, c.y, d.y, d.x};   // cube_case's corner order
-        bool finite = true;
-        int flag = 0;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            finite = finite && isfinite(v[i]);
-            if (v[i] <= 0.0f) flag |= 1 << i;
-        }
-        const unsigned n = finite ? c_num_tris[flag] : 0u;
+    walk_segment<CELL>(p, x, y, za, zb, [&](int, unsigned n) {
         active += n != 0;
         tris += n;
-        a = c;
-        b = d;
-    }
+    });
     return seg_pack(active, tris);
 }
 
@@ -430,51 +424,36 @@ __global__ __launch_bounds__(256) void k_mesh_compact(const MeshParams p, const 
         const int x = (int)(col / p.cy), y = (int)(col - (long long)x * p.cy);
         const int za = r.zlo + k * MESH_SEG, zb = min(za + MESH_SEG, r.zhi);
         unsigned long long ia = ba + off_a[j], it = bt + off_t[j];
-        float2 a = CELL::pair(rowp(p.vol, y, za), x), b = CELL::pair(rowp(p.vol, y + 1, za), x);
         const long long ci0 = col * p.cz;
-        for (int z = za; z < zb; ++z) {
-            const float2 c = CELL::pair(rowp(p.vol, y, z + 1), x), d = CELL::pair(rowp(p.vol, y + 1, z + 1), x);
-            const float v[8] = {a.x, a.y, b.y, b.x, c.x, c.y, d.y, d.x};
-            bool finite = true;
-            int flag = 0;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                finite = finite && isfinite(v[i]);
-                if (v[i] <= 0.0f) flag |= 1 << i;
+        walk_segment<CELL>(p, x, y, za, zb, [&](int z, unsigned n) {
+            if (!n) return;
+            if (ia < cap_active && it + n <= cap_tris) {
+                cube_index[ia] = ci0 + z;
+                tri_offset[ia] = (unsigned)it;
             }
-            const unsigned n = finite ? c_num_tris[flag] : 0u;
-            if (n) {
-                if (ia < cap_active && it + n <= cap_tris) {
-                    cube_index[ia] = ci0 + z;
-                    tri_offset[ia] = (unsigned)it;
-                }
-                ++ia;
-                it += n;
-            }
-            a = c;
-            b = d;
-        }
+            ++ia;
+            it += n;
+        });
     }
 }
 
-// The meshed cube planes and the geometry: the whole volume, or a slab view through the full volume's geometry -- the recipe of
-// raycast_slab_launch (raycast.hip): base pointer moved back by z_offset planes (dereferenced only inside the stored planes),
-// full_d / full_zmin / full_zmax in z, set_shortcuts on the full geometry.
+// The meshed cube planes and the geometry: the whole volume, or a slab view through the full volume's geometry
+// (slab_full_volume: the virtual base pointer is dereferenced only inside the stored planes).
 static int mesh_setup(MeshParams& p, MeshRange& r, const kfx_volume* vol, int cell, const kfx_slab* slab, int own_lo, int own_hi)
 {
     if (!vol || !vol->ptr) return set_error(KFX_E_NULL, "kfx_mesh: null volume");
     if (cell != KFX_CELL_F32 && cell != KFX_CELL_F16) return set_error(KFX_E_RANGE, "kfx_mesh: unknown cell kind");
     const size_t cb = cell == KFX_CELL_F32 ? 8 : 4;
+    kfx_volume full = *vol;   // the volume the cubes are numbered in
     if (!slab) {
-        if (int e = mesh_params(p, vol, cb)) return e;
+        if (int e = check_volume(vol, cb, 3, VOLUME_MAX_DIM, "SaveMesh")) return e;
         r.zlo = 0;
-        r.zhi = p.cz;
+        r.zhi = (int)vol->d - 1;
     } else {
-        if (vol->w < 3 || vol->h < 3 || vol->d < 1 || vol->w > 65535 || vol->h > 65535 || slab->full_d < 3 || slab->full_d > 65535 ||
-            slab->z_offset + vol->d > slab->full_d)
+        // (a slab may store a single plane; w and h as for a whole volume)
+        if (vol->w < 3 || vol->h < 3 || slab->full_d < 3 || slab->full_d > 65535 || slab->z_offset + vol->d > slab->full_d)
             return set_error(KFX_E_SHAPE, "kfx_mesh: slab outside the full volume");
-        if (vol->pitch < vol->w * cb || vol->img_pitch < vol->pitch * (vol->h - 1) + vol->w * cb) return set_error(KFX_E_SHAPE, "kfx_mesh: volume pitch");
-        if (((uintptr_t)vol->ptr | vol->pitch | vol->img_pitch) & (cb - 1)) return set_error(KFX_E_ALIGN, "kfx_mesh: alignment");
+        if (int e = check_volume(vol, cb, 1, VOLUME_MAX_DIM, "kfx_mesh(slab)")) return e;
         const int full_d = (int)slab->full_d;
         const int zlo = own_lo < 0 ? 0 : own_lo, zhi = own_hi < full_d - 1 ? own_hi : full_d - 1;
         r.zlo = zlo;
@@ -486,23 +465,13 @@ static int mesh_setup(MeshParams& p, MeshRange& r, const kfx_volume* vol, int ce
             if (need_lo < (long long)slab->z_offset || need_hi > (long long)(slab->z_offset + vol->d))
                 return set_error(KFX_E_RANGE, "kfx_mesh: the stored planes do not cover the slab's cubes and their normals' stencil");
         }
-        p.vol.ptr = (unsigned char*)vol->ptr - (ptrdiff_t)slab->z_offset * (ptrdiff_t)vol->img_pitch;
-        p.vol.pitch = vol->pitch;
-        p.vol.img_pitch = vol->img_pitch;
-        p.vol.w = (int)vol->w;
-        p.vol.h = (int)vol->h;
-        p.vol.d = full_d;
-        p.vol.bmin = V3{vol->boxmin[0], vol->boxmin[1], slab->full_zmin};
-        p.vol.bmax = V3{vol->boxmax[0], vol->boxmax[1], slab->full_zmax};
-        p.size = V3{vol->boxmax[0] - vol->boxmin[0], vol->boxmax[1] - vol->boxmin[1], slab->full_zmax - slab->full_zmin};
-        p.dims1 = V3{(float)vol->w - 1.f, (float)vol->h - 1.f, (float)full_d - 1.f};
-        p.hi2 = V3{(float)(vol->w - 2), (float)(vol->h - 2), (float)(full_d - 2)};
-        p.voxel = V3{p.size.x / (float)(vol->w - 1), p.size.y / (float)(vol->h - 1), p.size.z / (float)(full_d - 1)};
-        set_shortcuts(p);
-        p.cx = (int)vol->w - 1; p.cy = (int)vol->h - 1; p.cz = full_d - 1;
-        p.avail_lo = (int)slab->z_offset;
-        p.avail_hi = (int)(slab->z_offset + vol->d);
+        full = slab_full_volume(vol, slab);
     }
+    set_geometry(p, &full);
+    set_voxel_size(p, &full);
+    p.cx = (int)full.w - 1; p.cy = (int)full.h - 1; p.cz = (int)full.d - 1;
+    p.avail_lo = slab ? (int)slab->z_offset : 0;
+    p.avail_hi = p.avail_lo + (int)vol->d;
     r.nsz = (r.zhi - r.zlo + MESH_SEG - 1) / MESH_SEG;
     r.nseg = (long long)p.cx * p.cy * r.nsz;
     r.nblk = (r.nseg + MESH_BLOCK - 1) / MESH_BLOCK;
@@ -539,7 +508,8 @@ using namespace kfx;
 extern "C" int kfx_mc_count(const kfx_volume* vol, unsigned char* counts, kfx_stream stream)
 {
     MeshParams p;
-    if (int e = mesh_params(p, vol)) return e;
+    MeshRange r;
+    if (int e = mesh_setup(p, r, vol, KFX_CELL_F32, nullptr, 0, 0)) return e;
     if (!counts) return set_error(KFX_E_NULL, "SaveMesh: null counts");
     if (int e = load_tables()) return e;
     dim3 grid(ceil_div(p.cx, 64), p.cy, ceil_div(p.cz, 16));
@@ -551,7 +521,8 @@ extern "C" int kfx_mc_emit(const kfx_volume* vol, const kfx_volume* colorvol, co
                            long long n_active, float* verts, float* norms, float* colors, kfx_stream stream)
 {
     MeshParams p;
-    if (int e = mesh_params(p, vol)) return e;
+    MeshRange r;
+    if (int e = mesh_setup(p, r, vol, KFX_CELL_F32, nullptr, 0, 0)) return e;
     if (n_active <= 0) return 0;
     if (!cube_index || !tri_offset || !verts || !norms) return set_error(KFX_E_NULL, "SaveMesh: null output");
     if (int e = load_tables()) return e;

@@ -6,9 +6,9 @@
 // tile (workgroup tile + apron, loaded once with clamped coordinates, which is exactly
 // Image::GetWithClampedRange) and the (2r+1)^2 spatial weights are evaluated once per
 // workgroup into LDS instead of once per tap per pixel.
-#include <cstdlib>
 
 #include "kfx_device.h"
+#include "host_args.h"
 
 namespace kfx {
 
@@ -536,7 +536,7 @@ static int bilateral_launch(const kfx_image* out, const kfx_image* in, float gs,
     } else if (p.R <= BIL_MAX_R) {
         const int D = 2 * p.R + 1;
         // tile shape (config C3 sweep, scripts/config_sweep.py): KFX_BILATERAL_TILE = 0..5
-        static const int shape = [] { const char* e = getenv("KFX_BILATERAL_TILE"); return e ? atoi(e) : 2; }();
+        static const int shape = env_int("KFX_BILATERAL_TILE", 2);
 #define KFX_BIL(TX_, TY_, PY_)                                                                                   \
     do {                                                                                                        \
         const size_t lds = (size_t)((TX_ + 2 * p.R) * (TY_ * PY_ + 2 * p.R) + D * D) * sizeof(float);           \

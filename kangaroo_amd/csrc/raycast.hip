@@ -9,7 +9,6 @@
 // the gradient stencil is 20 distinct cells instead of 32 loads; missed rays skip the
 // (discarded) normal evaluation of the reference.
 #include <cmath>
-#include <cstdlib>
 
 #include <hip/hip_fp16.h>
 
@@ -877,14 +876,10 @@ static int ray_params(RayParams& p, const kfx_image* depth, const kfx_image* nor
         return set_error(KFX_E_SHAPE, "RaycastSdf: output images smaller than img");
     if (depth->pitch < img->w * 4 || img->pitch < img->w * 4 || norm->pitch < img->w * 16)
         return set_error(KFX_E_SHAPE, "RaycastSdf: image pitch");
-    if ((((uintptr_t)depth->ptr | depth->pitch | (uintptr_t)img->ptr | img->pitch) & 3) ||
-        (((uintptr_t)norm->ptr | norm->pitch) & 15) || (((uintptr_t)vol->ptr | vol->pitch | vol->img_pitch) & (CELL::BYTES - 1)))
-        return set_error(KFX_E_ALIGN, "RaycastSdf: alignment");
+    if ((((uintptr_t)depth->ptr | depth->pitch | (uintptr_t)img->ptr | img->pitch) & 3) || (((uintptr_t)norm->ptr | norm->pitch) & 15))
+        return set_error(KFX_E_ALIGN, "RaycastSdf: image alignment");
     // the gradient stencil reads cells [1-1, (dim-2)+1] (Volume.h:271-273)
-    if (vol->w < 3 || vol->h < 3 || vol->d < 3 || vol->w > 65535 || vol->h > 65535 || vol->d > 65535)
-        return set_error(KFX_E_SHAPE, "RaycastSdf: volume dimensions");
-    if (vol->pitch < vol->w * CELL::BYTES || vol->img_pitch < vol->pitch * (vol->h - 1) + vol->w * CELL::BYTES)
-        return set_error(KFX_E_SHAPE, "RaycastSdf: volume pitch");
+    if (int e = check_volume(vol, CELL::BYTES, 3, VOLUME_MAX_DIM, "RaycastSdf")) return e;
     set_geometry(p, vol);
     set_voxel_size(p, vol);
     for (int i = 0; i < 12; ++i) p.T.m[i] = T_wc[i];
@@ -924,9 +919,9 @@ static int class_view(ClassView& cl, size_t* lds_bytes, int* usable, kfx_sdf_sum
     *usable = 0;
     if (int e = summary_view_offset(summary, vol, &cl.ox, &cl.oy, &cl.oz)) return e;
     if (!(p.trunc > 0.f) || !(p.trunc < __builtin_inff())) return 0;
-    static const int kb_env = [] { const char* e = getenv("KFX_RAYCAST_CLASS_KB"); const int v = e ? atoi(e) : 16; return v < 1 ? 1 : (v > 60 ? 60 : v); }();
-    static const int gt_env = [] { const char* e = getenv("KFX_RAYCAST_GLOBAL_TABLES"); return e ? atoi(e) : 0; }();
-    static const int top_env = [] { const char* e = getenv("KFX_RAYCAST_TOP_LEVELS"); const int v = e ? atoi(e) : 2; return v < 0 ? 0 : (v > 2 ? 2 : v); }();
+    static const int kb_env = env_int("KFX_RAYCAST_CLASS_KB", 16, 1, 60);
+    static const int gt_env = env_int("KFX_RAYCAST_GLOBAL_TABLES", 0);
+    static const int top_env = env_int("KFX_RAYCAST_TOP_LEVELS", 2, 0, 2);
     int fine = 3;
     for (; fine < 5; ++fine) {
         summary_class_layout(summary, fine, cl);
@@ -976,7 +971,7 @@ static int class_view(ClassView& cl, size_t* lds_bytes, int* usable, kfx_sdf_sum
     // function of the sequence of calls, not of how far the GPU happens to have got (round-3 advice).  Exact numerics on a
     // running stream, where only never-observed space qualifies, fall back to the plain march this way; while the choice is
     // "plain" the tables are rebuilt on every 8th call only.  KFX_RAYCAST_SUMMARY=1 always uses the tables, -1 never.
-    static const int force_env = [] { const char* e = getenv("KFX_RAYCAST_SUMMARY"); return e ? atoi(e) : 0; }();
+    static const int force_env = env_int("KFX_RAYCAST_SUMMARY", 0);
     if (force_env < 0) return 0;
     const bool steer = force_env == 0 && summary->h_skippable;
     if (steer && summary->plain_calls && (summary->plain_calls++ % 8u) != 0u) return 0;   // still plain: no build, no look
@@ -1053,7 +1048,7 @@ static int raycast_levels_launch(int n_levels, const kfx_image* const* depth, co
             lv.vpitch = vb->pitch;
         }
         lv.first_block = blocks;
-        static const int sparse_env = [] { const char* e = getenv("KFX_RAYCAST_SPARSE"); const int v = e ? atoi(e) : 16; return (v == 8 || v == 16 || v == 32) ? v : 0; }();
+        static const int sparse_env = [] { const int v = env_int("KFX_RAYCAST_SPARSE", 16); return (v == 8 || v == 16 || v == 32) ? v : 0; }();
         lv.sparse = (long long)p.w * p.h <= 160 * 120 ? sparse_env : 0; // coarse levels only: at full resolution dense waves are faster
         lv.blocks_x = lv.sparse ? ceil_div(p.w, 2 * lv.sparse) : ceil_div(p.w, 64);
         blocks += lv.blocks_x * (lv.sparse ? ceil_div(p.h, 2) : ceil_div(p.h, 4));
@@ -1088,12 +1083,12 @@ static int raycast_launch(const kfx_image* depth, const kfx_image* norm, const k
         return set_error(KFX_E_SHAPE, "RaycastSdf(tracked): the summary was created for the other cell type (kfx_sdf_summary_create / _create_h)");
     if (p.w == 0 || p.h == 0) return 0;
 
-    static const int tile_env = [] { const char* e = getenv("KFX_RAYCAST_TILE"); const int v = e ? atoi(e) : 5; return v < 0 ? 0 : (v > 6 ? 6 : v); }();
-    static const int wg_env = [] { const char* e = getenv("KFX_RAYCAST_WG"); const int v = e ? atoi(e) : 1; return v < 0 ? 0 : (v > 2 ? 2 : v); }();
+    static const int tile_env = env_int("KFX_RAYCAST_TILE", 5, 0, 6);
+    static const int wg_env = env_int("KFX_RAYCAST_WG", 1, 0, 2);
     p.tile_log2w = tile_env;
     p.wg_log2x = wg_env;
     dim3 grid(ceil_div(p.w, (1 << p.wg_log2x) << p.tile_log2w), ceil_div(p.h, (4 >> p.wg_log2x) * (64 >> p.tile_log2w)));
-    static const int lanes_env = [] { const char* e = getenv("KFX_RAYCAST_LANES"); const int v = e ? atoi(e) : 0; return (v == 8 || v == 16 || v == 32) ? v : (v < 0 ? -1 : 0); }();
+    static const int lanes_env = [] { const int v = env_int("KFX_RAYCAST_LANES", 0); return (v == 8 || v == 16 || v == 32) ? v : (v < 0 ? -1 : 0); }();
     // small images (pyramid levels): rays of a wave are many voxels apart, 16 rays per wave wait for fewer misses per step
     const int lanes = lanes_env ? lanes_env : ((long long)p.w * p.h <= 160 * 120 ? 16 : 0);
     if (lanes && lanes_env >= 0) {
@@ -1102,11 +1097,7 @@ static int raycast_launch(const kfx_image* depth, const kfx_image* norm, const k
     }
     ColorGeom cv{};
     if (colorvol) {
-        if (!colorvol->ptr) return set_error(KFX_E_NULL, "RaycastSdf(colour): null colour volume");
-        if (colorvol->w < 2 || colorvol->h < 2 || colorvol->d < 2 || colorvol->pitch < colorvol->w * 4 ||
-            colorvol->img_pitch < colorvol->pitch * (colorvol->h - 1) + colorvol->w * 4)
-            return set_error(KFX_E_SHAPE, "RaycastSdf(colour): colour volume dimensions / pitch");
-        if (((uintptr_t)colorvol->ptr | colorvol->pitch | colorvol->img_pitch) & 3) return set_error(KFX_E_ALIGN, "RaycastSdf(colour): alignment");
+        if (int e = check_volume(colorvol, 4, 2, VOLUME_ANY_DIM, "RaycastSdf(colour)")) return e;
         set_geometry(cv, colorvol);
         hipLaunchKernelGGL((k_raycast_sdf<CELL, true>), grid, dim3(256), 0, (hipStream_t)stream, p, cv);
     } else if (summary) {
@@ -1198,7 +1189,6 @@ extern "C" int kfx_raycast_sdf_count_tracked_h(const kfx_volume* vol, kfx_sdf_su
                                                float near, float far, float trunc_dist, int subpix, unsigned* d_bitmap, unsigned long long* d_counters,
                                                kfx_stream stream)
 {
-    if (!d_bitmap || !d_counters || !summary) return set_error(KFX_E_NULL, "kfx_raycast_sdf_count_tracked_h: null argument");
     return raycast_count_tracked_launch<RayF16>(vol, summary, w, h, T_wc, K, near, far, trunc_dist, subpix, d_bitmap, d_counters, stream);
 }
 
@@ -1281,19 +1271,9 @@ static int raycast_slab_launch(const SlabRay& geom, const kfx_volume* vol, const
         return set_error(KFX_E_ALIGN, "RaycastSdf(slab): alignment");
     RayParams p;
     // full-volume geometry, virtual base pointer (never dereferenced outside [avail_lo, avail_hi))
-    p.vol.ptr = (unsigned char*)vol->ptr - (ptrdiff_t)slab->z_offset * (ptrdiff_t)vol->img_pitch;
-    p.vol.pitch = vol->pitch;
-    p.vol.img_pitch = vol->img_pitch;
-    p.vol.w = (int)vol->w;
-    p.vol.h = (int)vol->h;
-    p.vol.d = (int)slab->full_d;
-    p.vol.bmin = V3{vol->boxmin[0], vol->boxmin[1], slab->full_zmin};
-    p.vol.bmax = V3{vol->boxmax[0], vol->boxmax[1], slab->full_zmax};
-    p.size = V3{vol->boxmax[0] - vol->boxmin[0], vol->boxmax[1] - vol->boxmin[1], slab->full_zmax - slab->full_zmin};
-    p.dims1 = V3{(float)vol->w - 1.f, (float)vol->h - 1.f, (float)slab->full_d - 1.f};
-    p.hi2 = V3{(float)(vol->w - 2), (float)(vol->h - 2), (float)(slab->full_d - 2)};
-    p.voxel = V3{p.size.x / (float)(vol->w - 1), p.size.y / (float)(vol->h - 1), p.size.z / (float)(slab->full_d - 1)};
-    set_shortcuts(p);
+    const kfx_volume full = slab_full_volume(vol, slab);
+    set_geometry(p, &full);
+    set_voxel_size(p, &full);
     for (int i = 0; i < 12; ++i) p.T.m[i] = T_wc[i];
     p.K = Intr{K[0], K[1], K[2], K[3]};
     p.dptr = p.nptr = p.iptr = nullptr;

@@ -7,11 +7,10 @@
 // global_load: no 64-bit address arithmetic per lane).
 #pragma once
 
-#include <cstdlib>
-
 #include <hip/hip_fp16.h>
 
 #include "kfx_device.h"
+#include "host_args.h"
 
 namespace kfx {
 
@@ -329,7 +328,7 @@ __device__ __forceinline__ V3 gradient(const GEOM& p, const V3 pos_w)
 }
 
 // Host side: the arithmetic / addressing shortcuts of a geometry block whose vol / size members are set (g.vol.d planes
-// addressed from g.vol.ptr, which may be a virtual base: raycast_slab_launch)
+// addressed from g.vol.ptr, which may be a virtual base: slab_full_volume)
 template <typename GEOM>
 inline void set_shortcuts(GEOM& g)
 {
@@ -339,7 +338,7 @@ inline void set_shortcuts(GEOM& g)
     const double span = (double)(g.vol.d - 1) * (double)g.vol.img_pitch + (double)(g.vol.h - 1) * (double)g.vol.pitch + (double)g.vol.w * 16.0;
     // KFX_SAMPLER_SHORTCUTS=0 switches both shortcuts off (hardware division, 64-bit addresses: the paths volumes above
     // 4 GiB and out-of-range boxes take), so that the parity tests can run through them at small sizes
-    static const int enabled = [] { const char* e = getenv("KFX_SAMPLER_SHORTCUTS"); return e ? atoi(e) : 1; }();
+    static const int enabled = env_int("KFX_SAMPLER_SHORTCUTS", 1);
     g.off32 = enabled && span < 4294967296.0;
     g.fastdiv = enabled && g.fastdiv;
 }

@@ -11,6 +11,7 @@
 #include <new>
 
 #include "kfx_device.h"
+#include "host_args.h"
 #include "../../include/kfx_slab.h"
 #include "slab_internal.h"
 
@@ -901,8 +902,7 @@ bool normals_stage_forced()
 {
     int v = g_normals_stage.load(std::memory_order_relaxed);
     if (v < 0) {
-        const char* e = getenv("KFX_SLAB_NORMALS_STAGE");
-        v = (e && atoi(e) != 0) ? 1 : 0;
+        v = env_int("KFX_SLAB_NORMALS_STAGE", 0) != 0 ? 1 : 0;
         g_normals_stage.store(v, std::memory_order_relaxed);
     }
     return v != 0;

@@ -133,6 +133,57 @@ def test_argument_errors_are_reported_not_fatal():
     assert L.kfx_alloc_pitched(C.byref(p), C.byref(pitch), 0, 4) == -2
     assert L.kfx_free(None) == 0
 
+    # One argument per broken rule of a volume, for every family of entry points: the exact code, before any launch (the pointers
+    # are fake).  Where a family has no such rule (an upper bound on the dimensions, a pitch test), the argument also breaks the
+    # alignment rule, which every family tests last: KFX_E_ALIGN then shows that the call got past the dimension / pitch tests.
+    E_NULL, E_SHAPE, E_ALIGN = -1, -2, -3
+    FAKE = 1 << 20
+
+    def volume(cell, w=16, h=16, d=16, pitch=None, img_pitch=None, ptr=FAKE):
+        pitch = w * cell if pitch is None else pitch
+        return _lib.KfxVolume(pitch, ptr, w, h, pitch * h if img_pitch is None else img_pitch, d)
+
+    def broken(cell, min_dim, bounded=True):
+        """(what, volume, code): a volume of `cell`-byte cells that breaks exactly one rule of a family whose dimensions start at min_dim"""
+        cases = [("null", volume(cell, ptr=None), E_NULL),
+                 ("short pitch", volume(cell, pitch=16 * cell - cell, img_pitch=16 * cell * 16), E_SHAPE),
+                 ("short img_pitch", volume(cell, img_pitch=16 * cell * 16 - cell), E_SHAPE),
+                 ("misaligned", volume(cell, ptr=FAKE + cell // 2), E_ALIGN)]
+        for axis in "whd":
+            cases.append(("%s below the minimum" % axis, volume(cell, **{axis: min_dim - 1}), E_SHAPE))
+            if bounded:
+                cases.append(("%s above 65535" % axis, volume(cell, **{axis: 65536}), E_SHAPE))
+        return cases
+    d4, n4 = _lib.KfxImage(8 * 4, FAKE, 8, 8), _lib.KfxImage(8 * 16, FAKE, 8, 8)
+    good = volume(8)
+    for cell, fuse, reset, ray in ((8, L.kfx_sdf_fuse, L.kfx_sdf_reset, L.kfx_raycast_sdf), (4, L.kfx_sdf_fuse_h, L.kfx_sdf_reset_h, L.kfx_raycast_sdf_h)):
+        for what, v, code in broken(cell, 1):
+            assert fuse(C.byref(v), C.byref(d4), C.byref(n4), Tm, K, 0.1, 100.0, 0.1, 0, None) == code, ("SdfFuse", cell, what)
+            assert reset(C.byref(v), 0.1, None) == code, ("SdfReset", cell, what)
+        for what, v, code in broken(cell, 3):
+            assert ray(C.byref(d4), C.byref(n4), C.byref(d4), C.byref(v), Tm, K, 0.1, 1.0, 0.1, 1, None) == code, ("RaycastSdf", cell, what)
+        # SdfFuse takes dimensions from 1: a 1 x 1 x 1 volume gets as far as the image checks
+        odd = _lib.KfxImage(8 * 4, FAKE + 2, 8, 8)
+        assert fuse(C.byref(volume(cell, 1, 1, 1)), C.byref(odd), C.byref(n4), Tm, K, 0.1, 100.0, 0.1, 0, None) == E_ALIGN
+    assert L.kfx_color_reset(C.byref(volume(4, w=0)), None) == E_SHAPE and L.kfx_color_reset(C.byref(volume(4, ptr=FAKE + 2)), None) == E_ALIGN
+    # RaycastSdf's colour volume and SdfDistance: dimensions from 2, no upper bound
+    for what, v, code in broken(4, 2, bounded=False) + [("above 65535 and misaligned", volume(4, w=70000, ptr=FAKE + 2), E_ALIGN)]:
+        assert L.kfx_raycast_sdf_color(C.byref(d4), C.byref(n4), C.byref(d4), C.byref(good), C.byref(v), Tm, K, 0.1, 1.0, 0.1, 1, None) == code, ("RaycastSdf colour", what)
+    for what, v, code in broken(8, 2, bounded=False):
+        assert L.kfx_sdf_distance(C.byref(d4), C.byref(d4), C.byref(v), Tm, K, 0.1, None) == code, ("SdfDistance", what)
+    assert L.kfx_sdf_distance(C.byref(_lib.KfxImage(8 * 4, FAKE + 2, 8, 8)), C.byref(d4), C.byref(volume(8, d=70000)), Tm, K, 0.1, None) == E_ALIGN
+    # RaycastSdf on a slab: w and h from 3, the slab inside a full volume of 3 planes or more; no pitch test, no upper bound
+    for cell, ray in ((8, L.kfx_raycast_sdf_slab), (4, L.kfx_raycast_sdf_slab_h)):
+        def slab_ray(v, full_d=64, z_offset=8):
+            return ray(FAKE, 1, C.byref(v), C.byref(_lib.KfxSlab(full_d, z_offset, -1.0, 1.0)), 8, 24, 8, 8, Tm, K, 0.1, 1.0, 0.1, 1, None)
+        odd = FAKE + cell // 2
+        assert slab_ray(volume(cell, ptr=None)) == E_NULL and slab_ray(volume(cell, ptr=odd)) == E_ALIGN
+        assert slab_ray(volume(cell, w=2)) == E_SHAPE and slab_ray(volume(cell, h=2)) == E_SHAPE
+        assert slab_ray(volume(cell), full_d=2, z_offset=0) == E_SHAPE and slab_ray(volume(cell), z_offset=49) == E_SHAPE
+        assert slab_ray(volume(cell, w=70000, ptr=odd)) == E_ALIGN
+        assert slab_ray(volume(cell, pitch=16 * cell - cell, img_pitch=16 * cell * 16, ptr=odd)) == E_ALIGN
+        assert slab_ray(volume(cell, img_pitch=16 * cell * 16 - cell, ptr=odd)) == E_ALIGN
+
 
 def test_every_compute_entry_point_rejects_null_arguments():
     """Every entry point that takes container pointers validates them before any HIP call: all-NULL arguments

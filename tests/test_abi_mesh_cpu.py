@@ -8,7 +8,7 @@ import re
 import kfx_testlib as T
 from kangaroo_amd import _lib
 
-E_NULL, E_SHAPE, E_RANGE = -1, -2, -4
+E_NULL, E_SHAPE, E_ALIGN, E_RANGE = -1, -2, -3, -4
 FAKE = 1 << 20   # an aligned address that nothing may touch
 
 
@@ -98,3 +98,29 @@ def test_mesh_entry_points_refuse_before_any_hip_call():
         # a slab that leaves the full volume
         slab = _lib.KfxSlab(D, 50, -1.0, 1.0)
         assert plan(L, volume(40, 30, 20, cb), cell, slab, 50, 60, FAKE, 1 << 30, tot) == E_SHAPE
+        # one argument per broken rule of the volume, whole and as a slab (stored planes [10, 30) of 60): the exact code
+        slab = _lib.KfxSlab(D, 10, -1.0, 1.0)
+        for sl, lo, hi, min_d in ((None, 0, 0, 3), (slab, 12, 28, 1)):
+            def broken(**kw):
+                v = volume(40, 30, 20, cb)
+                for k, val in kw.items():
+                    setattr(v, k, val)
+                return plan(L, v, cell, sl, lo, hi, FAKE, 1 << 30, tot)
+            assert broken(ptr=None) == E_NULL and broken(ptr=FAKE + cb // 2) == E_ALIGN
+            assert broken(w=2) == E_SHAPE and broken(h=2) == E_SHAPE and broken(d=min_d - 1) == E_SHAPE
+            assert broken(w=65536, pitch=65536 * cb, img_pitch=65536 * cb * 30) == E_SHAPE and broken(h=65536, img_pitch=40 * cb * 65536) == E_SHAPE
+            assert broken(d=65536) == E_SHAPE
+            assert broken(pitch=39 * cb) == E_SHAPE and broken(img_pitch=40 * cb * 30 - cb) == E_SHAPE
+        # a slab may store a single plane: with no cubes of its own to mesh it gets past the volume's checks, to the scratch pointer
+        assert plan(L, volume(40, 30, 1, cb), cell, slab, 10, 10, None, 1 << 30, tot) == E_NULL
+        assert L.kfx_mesh_scratch_bytes(C.byref(volume(40, 30, 1, cb)), cell, C.byref(slab), 10, 10) > 0
+    # kfx_mc_count (fp32 cells): the same rules, dimensions from 3
+    def count(**kw):
+        v = volume(40, 30, 20, 8)
+        for k, val in kw.items():
+            setattr(v, k, val)
+        return L.kfx_mc_count(C.byref(v), FAKE, None)
+    assert count(ptr=None) == E_NULL and count(ptr=FAKE + 4) == E_ALIGN
+    assert count(w=2) == E_SHAPE and count(h=2) == E_SHAPE and count(d=2) == E_SHAPE
+    assert count(w=65536, pitch=65536 * 8, img_pitch=65536 * 8 * 30) == E_SHAPE and count(h=65536, img_pitch=40 * 8 * 65536) == E_SHAPE and count(d=65536) == E_SHAPE
+    assert count(pitch=39 * 8) == E_SHAPE and count(img_pitch=40 * 8 * 30 - 8) == E_SHAPE
