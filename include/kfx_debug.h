@@ -43,6 +43,10 @@ int kfx_debug_wave_xor_check(unsigned seed, unsigned long long* d_out, kfx_strea
 int kfx_debug_summary_export(kfx_sdf_summary* s, float tol, float vref, int fine_shift, void* R_out, void* C_out, int dims_out[12],
                              kfx_stream stream);
 
+/* The class tables are rebuilt only when a brick changed its class since the last build: a build that follows nothing but
+ * tracked SdfFuse launches is "conditional" and returns early unless one of them reported such a change.  out[0] = conditional
+ * builds that built, out[1] = conditional builds that returned early, both since the summary was created (waits for `stream`). */
+int kfx_debug_summary_conditional_builds(kfx_sdf_summary* s, int out[2], kfx_stream stream);
 
 #ifdef __cplusplus
 }

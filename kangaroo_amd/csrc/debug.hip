@@ -291,3 +291,12 @@ extern "C" int kfx_debug_summary_export(kfx_sdf_summary* s, float tol, float vre
     }
     return 0;
 }
+
+extern "C" int kfx_debug_summary_conditional_builds(kfx_sdf_summary* s, int out[2], kfx_stream stream)
+{
+    if (!s || !out) return set_error(KFX_E_NULL, "kfx_debug_summary_conditional_builds: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemcpyAsync(out, s->d_count + 3, 2 * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return set_error(KFX_E_RANGE, "kfx_debug_summary_conditional_builds: copy");
+    return 0;
+}

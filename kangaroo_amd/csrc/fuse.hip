@@ -71,6 +71,10 @@ struct FuseParams {
     int sum_nbx, sum_nby;
     int sum_bx0, sum_by0, sum_bz0;
     int sum_w, sum_h, sum_d; // parent volume dimensions in cells
+    // the band the class tables were last built with and the word that tells their next build that a brick's class mask
+    // (brick_class_mask, kfx_device.h) changed under this launch
+    float sum_lo_ok, sum_hi_ok;
+    int* sum_dirty;
     int zoff_local;          // first plane of this launch within the view (fuse_launch splits the view into z-ranges)
     int xcd_swizzle;         // tiled kernels: n > 0 rotates the x-brick of a workgroup by (z-brick >> (n - 1)) (see k_sdf_fuse_tiled)
     int fuse_cull;           // fast tiled kernels: the brick cull by the tile's own costheta bound (KFX_FUSE_CULL=0 switches it off)
@@ -1113,14 +1117,17 @@ __global__ __launch_bounds__(64 * NW, (FAST && ZU == 2) ? 8 : (!FAST ? 6 : 1)) v
                 // state 0: every cell has a value in [lo, hi]; 1: every cell NaN; 2: mixed / unknown
                 // `full`: all 8 x 8 x 8 cells were updated (a brick cut by the volume's or the launch's extents never is: it
                 // takes the merge below, which is always valid)
-                if (full) { // every cell rewritten: the frame's range, no need to know the old one
-                    *r = make_float4(mn, mx, __int_as_float(0), 0.f);
-                } else {
-                    float4 old = *r;
-                    if (__float_as_int(old.z) == 1) old = make_float4(mn, mx, __int_as_float(2), 0.f);
-                    else old = make_float4(fminf(old.x, mn), fmaxf(old.y, mx), old.z, 0.f);
-                    *r = old;
-                }
+                const float4 old = *r;   // (the full branch needs it only to tell whether the brick's class mask changes)
+                float4 now;
+                if (full) now = make_float4(mn, mx, __int_as_float(0), 0.f); // every cell rewritten: the frame's range
+                else if (__float_as_int(old.z) == 1) now = make_float4(mn, mx, __int_as_float(2), 0.f);
+                else now = make_float4(fminf(old.x, mn), fmaxf(old.y, mx), old.z, 0.f);
+                *r = now;
+                // the class tables depend on the brick through its mask only: tell their next build if it changed (every
+                // writer stores the same value, and the kernel boundary orders it before the build)
+                if (brick_class_mask(old.x, old.y, __float_as_int(old.z), p.sum_lo_ok, p.sum_hi_ok) !=
+                    brick_class_mask(now.x, now.y, __float_as_int(now.z), p.sum_lo_ok, p.sum_hi_ok))
+                    *p.sum_dirty = 1;
             }
         }
     }
@@ -1746,6 +1753,8 @@ static int fuse_params(FuseParams& p, bool* small_images, const kfx_volume* vol,
     p.dpitch = *small_images ? (unsigned)depth->pitch : 0u;
     p.npitch = *small_images ? (unsigned)norm->pitch : 0u;
     p.sum_R = nullptr;
+    p.sum_dirty = nullptr;
+    p.sum_lo_ok = p.sum_hi_ok = 0.f;
     p.sum_nbx = p.sum_nby = p.sum_bx0 = p.sum_by0 = p.sum_bz0 = p.sum_w = p.sum_h = p.sum_d = p.zoff_local = 0;
     p.tex = nullptr;
     p.tpitch = 0;
@@ -1874,6 +1883,8 @@ static int fuse_launch(const kfx_volume* vol, const kfx_image* depth, const kfx_
         p.sum_nbx = summary->nbx; p.sum_nby = summary->nby;
         p.sum_bx0 = ox / 8; p.sum_by0 = oy / 8; p.sum_bz0 = oz / 8;
         p.sum_w = summary->w; p.sum_h = summary->h; p.sum_d = summary->d;
+        p.sum_lo_ok = summary->c_lo_ok; p.sum_hi_ok = summary->c_hi_ok;
+        p.sum_dirty = summary->d_dirty;
     }
     if (p.X == 0 || p.Y == 0 || p.Z == 0) return 0; // reference launches an empty grid
     // two cells per lane need an even extent and a pointer / pitches aligned to the cell pair
@@ -1888,7 +1899,7 @@ static int fuse_launch(const kfx_volume* vol, const kfx_image* depth, const kfx_
         if (int e = kfx_sdf_summary_invalidate(summary, stream)) return e;
         track = false;
     }
-    if (summary) summary->c_dirty = 1;
+    if (summary && !summary->c_dirty) summary->c_dirty = 1;   // (a tracked launch: whether the tables change is for d_dirty to say)
     if (tiled && vec2 && small_images) {
         // slices per iteration: 2 in fast mode (memory-bound: more reads in flight), 4 where the large LDS tile leaves
         // only 3 workgroups per CU (1280x960 at 512^3: 0.568 -> 0.538 ms; at 6 workgroups per CU 4 is slower), 1 in exact

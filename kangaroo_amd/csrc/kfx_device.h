@@ -200,12 +200,18 @@ struct kfx_sdf_summary {
     size_t pitch, img_pitch;
     // class tables of the march (ClassView below): two bit planes per entry, fine level (8^3 or 16^3 cells) then 32^3 cells
     unsigned* C;                 // device, sized for the finest level
-    int c_dirty;                 // R changed since C was built
+    int c_dirty;                 // R changed since C was built: 0 no; 1 maybe (a tracked SdfFuse ran: the device word d_dirty knows); 2 yes
+    float c_lo_ok, c_hi_ok;      // the band of (c_tol, c_vref): what the tracked SdfFuse compares brick masks with (brick_class_mask)
     float c_tol, c_vref;         // what C was built with
     int c_shift;                 // fine level C was built for (log2 of its cells per entry)
     int c_global;                // C also holds the 64^3- and 128^3-cell levels (the global-table mode, raycast.hip class_view)
     int n_coarse;                // 32^3-cell entries
-    int* d_count;                // device: {running count of 32^3-cell entries of class != 0, workgroups that have added theirs}
+    // device: {running count of 32^3-cell entries of class != 0, workgroups that have added theirs, the count of the last real
+    // build, conditional builds that built, conditional builds that returned early}
+    int* d_count;
+    // device word: some brick's class mask (brick_class_mask) changed since C was built.  Set by the tracked SdfFuse kernels,
+    // read by the conditional table builds (summary.hip), cleared by the last workgroup of a build.
+    int* d_dirty;
     // The table builds publish their count of 32^3-cell entries of class != 0 in a host-visible ring (pinned, mapped): build b
     // writes slot b % KFX_SUMMARY_RING and records build_done[b % KFX_SUMMARY_RING] behind it.  The tracked raycast chooses its
     // kernel from the count of build b - 2 (raycast.hip, class_view): old enough to have finished without anybody waiting,
@@ -239,23 +245,72 @@ struct ClassView {
     int amb_ok;          // class 3 may be skipped (trunc >= min_delta)
     int ox, oy, oz;      // cell offset of the view inside the parent volume
     float eps;           // margin (cells) that covers the error of the affine cell estimate
-    // Coarser levels (64^3 and 128^3 cells) are not built in global memory: every raycast workgroup derives them in LDS from
-    // the 32^3-cell level it has just staged (an entry = the combination of its 2 x 2 x 2 children, which include their +1
-    // cells), behind the staged words.  nx5 / nz5: entries of the 32^3-cell level along x / z (ny5 = coarse.ny); top_n: how
-    // many coarser levels there are (0-2); lds_words: staged words + the derived levels.
+    // Coarser levels (64^3 and 128^3 cells; an entry = the combination of its 2 x 2 x 2 children, which include their +1 cells):
+    // the last workgroup of a table build derives them from the 32^3-cell level into the words behind it (classes_level_up), and
+    // the raycast workgroups stage them with the rest.  nx5 / nz5: entries of the 32^3-cell level along x / z (ny5 = coarse.ny);
+    // top_n: how many coarser levels the march consults (0-2); lds_words: the words a workgroup stages.
     int nx5, nz5, top_n, lds_words;
     // Global-table mode (class tables larger than the LDS budget, or KFX_RAYCAST_GLOBAL_TABLES=1): the table build also writes the
     // 64^3- and 128^3-cell levels to global memory behind the 32^3-cell level (top_first); a workgroup stages only those two
-    // (stage_words from word top_first) and looks the fine and 32^3-cell levels up in global memory, coarse level first.
+    // (lds_words from word top_first) and looks the fine and 32^3-cell levels up in global memory, coarse level first.
     // LDS mode: the staged words are [0, words).
-    int global, top_first, stage_words;
+    int global, top_first;
 };
+// What the class of an entry depends on a brick through: bit 0 every cell NaN, bit 1 every cell holds vref (within the band),
+// bit 2 every cell is NaN or holds vref.  The table builds (class_row, summary.hip) combine these, and the tracked SdfFuse
+// compares a brick's mask before and after its update: while no mask changes, the tables stay what they are.
+__device__ __forceinline__ unsigned brick_class_mask(const float lo, const float hi, const int state, const float lo_ok, const float hi_ok)
+{
+    const bool in_band = lo >= lo_ok && hi <= hi_ok;   // every valued cell of the brick holds vref (false for the unknown state's infinite range)
+    return (state == 1 ? 1u : 0u) | ((state == 0 && in_band) ? 2u : 0u) | ((state == 1 || in_band) ? 4u : 0u);
+}
 // geometry of a level derived from a finer one with nx x ny x nz entries, placed at word `first`
 inline __host__ __device__ void class_level_up(const int nx, const int ny, const int nz, const int shift, const int first, ClassLevel& L, int& ux, int& uz, int& words)
 {
     ux = (nx + 1) >> 1; uz = (nz + 1) >> 1;
     L.shift = shift; L.ny = (ny + 1) >> 1; L.rw = 2 * ((ux + 31) >> 5); L.first = first;
     words = (L.rw * L.ny * uz + 3) & ~3;
+}
+// one derived level: entry (bx, by, bz) = combination of the 2 x 2 x 2 entries of `src` below it (edge entries repeat a
+// neighbour: same verdict).  One entry per thread and round: rows are padded to a power of two (or to whole waves when they are
+// longer than a wave), so a wave's 64 lanes hold whole rows side by side, the two bit planes are its ballots, and the first
+// lane of each row writes the row's share of them.
+__device__ __forceinline__ void classes_level_up(unsigned* tab, const ClassLevel& src, int snx, int snz, const ClassLevel& dst, int dnx, int dnz)
+{
+    const int lane = threadIdx.x & 63;
+    int lg = 0;                                      // log2 of the padded row length, at most 6 ...
+    while ((1 << lg) < dnx && lg < 6) ++lg;
+    const int chunks = (dnx + 63) >> 6;              // ... rows longer than a wave take `chunks` waves
+    const int px = chunks > 1 ? chunks << 6 : 1 << lg;
+    const int total = px * dst.ny * dnz;
+    for (int e0 = 0; e0 < total; e0 += 256) {        // uniform: every wave runs the same number of rounds (ballots below)
+        const int e = e0 + (int)threadIdx.x;
+        const int bx = chunks > 1 ? e % px : e & (px - 1), r = chunks > 1 ? e / px : e >> lg;
+        const int by = r % dst.ny, bz = r / dst.ny;
+        int cls = 0;
+        if (e < total && bx < dnx) {
+            bool all_free = true, all_nan = true, all_either = true;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int x = min(2 * bx + (k & 1), snx - 1), y = min(2 * by + ((k >> 1) & 1), src.ny - 1), z = min(2 * bz + (k >> 2), snz - 1);
+                const uint2 w = *reinterpret_cast<const uint2*>(tab + src.first + (z * src.ny + y) * src.rw + ((x >> 5) << 1));
+                const int c = (int)((w.x >> (x & 31)) & 1u) | (int)(((w.y >> (x & 31)) & 1u) << 1);
+                all_free = all_free && c == 1;
+                all_nan = all_nan && c == 2;
+                all_either = all_either && c != 0;
+            }
+            cls = all_free ? 1 : (all_nan ? 2 : (all_either ? 3 : 0));
+        }
+        const unsigned long long p0 = __ballot(cls & 1), p1 = __ballot(cls & 2);
+        if (e < total && (bx & 63) == 0 && (chunks > 1 || bx == 0)) {   // first lane of a row (or of a row's 64-entry chunk)
+            const int sh = chunks > 1 ? 0 : lane;                        // where the row's bits start in the ballots
+            const unsigned long long m = (chunks > 1 || lg == 6) ? ~0ull : ((1ull << (1 << lg)) - 1ull);
+            const unsigned long long r0 = (p0 >> sh) & m, r1 = (p1 >> sh) & m;
+            unsigned* out = tab + dst.first + (bz * dst.ny + by) * dst.rw + (bx >> 6) * 4;
+            out[0] = (unsigned)r0; out[1] = (unsigned)r1;
+            if ((bx >> 6) * 4 + 2 < dst.rw) { out[2] = (unsigned)(r0 >> 32); out[3] = (unsigned)(r1 >> 32); }
+        }
+    }
 }
 // global = 1: also build the 64^3- and 128^3-cell levels in global memory (at word summary_top_first)
 int summary_classes_prepare(kfx_sdf_summary* s, float tol, float vref, int fine_shift, hipStream_t stream, int global = 0);

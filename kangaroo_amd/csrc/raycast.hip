@@ -141,7 +141,7 @@ __device__ __forceinline__ float raycast_pixel(const RayParams& p, const ColorGe
 // exact-numerics tables (tol = 0: cells bit-equal to trunc, or NaN) depth, normals and shade stay bit-identical to the
 // plain march.
 // ---------------------------------------------------------------------------------------
-// The coarser levels of the workgroup (ClassView::top_n of them: 64^3 and 128^3 cells, derived in LDS by classes_stage), described
+// The coarser levels of the workgroup (ClassView::top_n of them: 64^3 and 128^3 cells, staged behind the others by classes_stage), described
 // where the march can read them without holding them in registers across its loop.
 struct TopLevels { ClassLevel lv[2]; int n; };
 
@@ -159,24 +159,50 @@ __device__ __forceinline__ unsigned touch(unsigned* bitmap, const VolView& v, in
 // 128^3 levels from LDS, and the levels are consulted coarse-first: a coarse entry of class != 0 implies that every entry below
 // it is != 0, so the coarsest level with class != 0 is the one the fine-first order of the LDS mode arrives at -- the same
 // runs, the same images -- and a ray in wide free space does not touch the global tables.
-template <typename CELL, bool COLOR, bool COUNT = false, bool GT = false>
-__device__ __forceinline__ float raycast_pixel_classes(const RayParams& p, const RayParams& q, const ColorGeom& cv, const int u, const int v, const ClassView& cl, const unsigned* tab,
-                                                       const TopLevels& top, unsigned* bitmap = nullptr, unsigned* cnt = nullptr)
+// The ray of pixel (u, v) and the slab test against the volume's box (cu_raycast.cu:40-51): the one definition the march and
+// the workgroups' vote before their prologue (k_raycast_sdf_classes) share.
+struct RayBox { V3 c_w, ray_c, ray_w; float max_tmin, min_tmax; };
+__device__ __forceinline__ RayBox ray_box(const RayParams& p, const int u, const int v)
 {
-    // p: the launch parameters as kernel arguments (scalar registers); q: the workgroup's copy of them in LDS, read by the
-    // epilogue -- pose, intrinsics, output images and the gradient's geometry are then not held in scalar registers across the
-    // march (the loop's own uniforms fill the register file: 22 spilled SGPRs, each a v_readlane in the loop, without this)
-    if (u >= p.w || v >= p.h) return 0.f;
-
-    const V3 c_w = v3(p.T.m[3], p.T.m[7], p.T.m[11]);
-    const V3 ray_c = v3(((float)u - p.K.u0) / p.K.fu, ((float)v - p.K.v0) / p.K.fv, 1.0f);
-    const V3 ray_w = so3_mul(p.T, ray_c);
-    const V3 ta = div_cw(p.vol.bmin - c_w, ray_w);
-    const V3 tb = div_cw(p.vol.bmax - c_w, ray_w);
+    RayBox b;
+    b.c_w = v3(p.T.m[3], p.T.m[7], p.T.m[11]);
+    b.ray_c = v3(((float)u - p.K.u0) / p.K.fu, ((float)v - p.K.v0) / p.K.fv, 1.0f);
+    b.ray_w = so3_mul(p.T, b.ray_c);
+    const V3 ta = div_cw(p.vol.bmin - b.c_w, b.ray_w);
+    const V3 tb = div_cw(p.vol.bmax - b.c_w, b.ray_w);
     const V3 tmin = v3(fminf(ta.x, tb.x), fminf(ta.y, tb.y), fminf(ta.z, tb.z));
     const V3 tmax = v3(fmaxf(ta.x, tb.x), fmaxf(ta.y, tb.y), fmaxf(ta.z, tb.z));
-    const float max_tmin = fmaxf(fmaxf(fmaxf(tmin.x, tmin.y), tmin.z), p.near);
-    const float min_tmax = fminf(fminf(fminf(tmax.x, tmax.y), tmax.z), p.far);
+    b.max_tmin = fmaxf(fmaxf(fmaxf(tmin.x, tmin.y), tmin.z), p.near);
+    b.min_tmax = fminf(fminf(fminf(tmax.x, tmax.y), tmax.z), p.far);
+    return b;
+}
+__device__ __forceinline__ bool enters(const RayBox& b) { return b.max_tmin < b.min_tmax; }
+
+template <typename CELL, bool COLOR, bool COUNT = false, bool GT = false>
+__device__ __forceinline__ float raycast_pixel_classes(const RayParams& p, const RayParams& q, const ColorGeom& cv, const int u, const int v, const ClassView& cl_arg, const unsigned* tab,
+                                                       const TopLevels& top, unsigned* bitmap = nullptr, unsigned* cnt = nullptr)
+{
+    // The loop's uniforms fill the scalar register file, and what does not fit comes back with a v_readlane on the march's chain
+    // of dependent instructions.  So: p are the launch parameters as kernel arguments (scalar registers), q the workgroup's copy of
+    // them in LDS, which the epilogue reads -- pose, intrinsics, output images and the gradient's geometry are not held across the
+    // march; and (LDS mode) the table descriptors and the view's offsets and margins are parked in vector registers (in_vgpr,
+    // kfx_device.h; VGPRs are not this kernel's limit) -- the same values in the same expressions.
+    constexpr bool PARK = !GT && !COUNT;
+    ClassView parked;
+    if constexpr (PARK) parked = cl_arg;
+    ClassView& clp = parked;
+    if constexpr (PARK) {
+        clp.fine.shift = in_vgpr(clp.fine.shift); clp.fine.ny = in_vgpr(clp.fine.ny); clp.fine.rw = in_vgpr(clp.fine.rw); clp.fine.first = in_vgpr(clp.fine.first);
+        clp.coarse.ny = in_vgpr(clp.coarse.ny); clp.coarse.rw = in_vgpr(clp.coarse.rw); clp.coarse.first = in_vgpr(clp.coarse.first);
+        clp.ox = in_vgpr(clp.ox); clp.oy = in_vgpr(clp.oy); clp.oz = in_vgpr(clp.oz);
+        clp.eps = in_vgpr(clp.eps); clp.vref = in_vgpr(clp.vref);
+    }
+    const ClassView& cl = PARK ? parked : cl_arg;
+    if (u >= p.w || v >= p.h) return 0.f;
+
+    const RayBox box = ray_box(p, u, v);
+    const V3 c_w = box.c_w, ray_w = box.ray_w;
+    const float max_tmin = box.max_tmin, min_tmax = box.min_tmax;
 
     float depth = 0.0f;
     if (max_tmin < min_tmax) {
@@ -259,7 +285,7 @@ __device__ __forceinline__ float raycast_pixel_classes(const RayParams& p, const
                         if (c5 == 3 && !cl.amb_ok) c5 = 0;
                         if (c5 != 0) { cls = c5; shift = 5; }
                     }
-                    // ... and a run through 32^3 cells may be one through 64^3 or 128^3 (the levels the workgroup derived in LDS):
+                    // ... and a run through 32^3 cells may be one through 64^3 or 128^3 (the levels the table build derived from it):
                     // wide free or never-observed space is crossed in a third of the look-ups
                     if (shift == 5 && cl.top_n > 0) {
                         int c6 = class_lookup(tab, top.lv[0], gx, gy, gz);
@@ -382,57 +408,16 @@ __device__ __forceinline__ float raycast_pixel_classes(const RayParams& p, const
     return depth > 0 ? depth : __builtin_nanf("");
 }
 
-// one derived level: entry (bx, by, bz) = combination of the 2 x 2 x 2 entries of `src` below it (edge entries repeat a
-// neighbour: same verdict).  One entry per thread and round: rows are padded to a power of two (or to whole waves when they are
-// longer than a wave), so a wave's 64 lanes hold whole rows side by side, the two bit planes are its ballots, and the first
-// lane of each row writes the row's share of them.
-__device__ __forceinline__ void classes_level_up(unsigned* tab, const ClassLevel& src, int snx, int snz, const ClassLevel& dst, int dnx, int dnz)
-{
-    const int lane = threadIdx.x & 63;
-    int lg = 0;                                      // log2 of the padded row length, at most 6 ...
-    while ((1 << lg) < dnx && lg < 6) ++lg;
-    const int chunks = (dnx + 63) >> 6;              // ... rows longer than a wave take `chunks` waves
-    const int px = chunks > 1 ? chunks << 6 : 1 << lg;
-    const int total = px * dst.ny * dnz;
-    for (int e0 = 0; e0 < total; e0 += 256) {        // uniform: every wave runs the same number of rounds (ballots below)
-        const int e = e0 + (int)threadIdx.x;
-        const int bx = chunks > 1 ? e % px : e & (px - 1), r = chunks > 1 ? e / px : e >> lg;
-        const int by = r % dst.ny, bz = r / dst.ny;
-        int cls = 0;
-        if (e < total && bx < dnx) {
-            bool all_free = true, all_nan = true, all_either = true;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int x = min(2 * bx + (k & 1), snx - 1), y = min(2 * by + ((k >> 1) & 1), src.ny - 1), z = min(2 * bz + (k >> 2), snz - 1);
-                const uint2 w = *reinterpret_cast<const uint2*>(tab + src.first + (z * src.ny + y) * src.rw + ((x >> 5) << 1));
-                const int c = (int)((w.x >> (x & 31)) & 1u) | (int)(((w.y >> (x & 31)) & 1u) << 1);
-                all_free = all_free && c == 1;
-                all_nan = all_nan && c == 2;
-                all_either = all_either && c != 0;
-            }
-            cls = all_free ? 1 : (all_nan ? 2 : (all_either ? 3 : 0));
-        }
-        const unsigned long long p0 = __ballot(cls & 1), p1 = __ballot(cls & 2);
-        if (e < total && (bx & 63) == 0 && (chunks > 1 || bx == 0)) {   // first lane of a row (or of a row's 64-entry chunk)
-            const int sh = chunks > 1 ? 0 : lane;                        // where the row's bits start in the ballots
-            const unsigned long long m = (chunks > 1 || lg == 6) ? ~0ull : ((1ull << (1 << lg)) - 1ull);
-            const unsigned long long r0 = (p0 >> sh) & m, r1 = (p1 >> sh) & m;
-            unsigned* out = tab + dst.first + (bz * dst.ny + by) * dst.rw + (bx >> 6) * 4;
-            out[0] = (unsigned)r0; out[1] = (unsigned)r1;
-            if ((bx >> 6) * 4 + 2 < dst.rw) { out[2] = (unsigned)(r0 >> 32); out[3] = (unsigned)(r1 >> 32); }
-        }
-    }
-}
-
-// workgroup prologue of the class-table kernels: the tables into LDS (16-byte loads, all in flight together), then the
-// coarser levels derived from the 32^3-cell level
-// (GT: only the 64^3- and 128^3-cell levels, which the table build wrote to global memory, staged at word 0)
+// workgroup prologue of the class-table kernels: the tables into LDS (16-byte loads, all in flight together) -- the fine and the
+// 32^3-cell level and, behind them, as many of the 64^3- and 128^3-cell levels as the march consults (cl.top_n): the table
+// build derived those once (k_summary_classes_coarse, summary.hip), nothing is derived here
+// (GT: only the 64^3- and 128^3-cell levels, staged at word 0)
 template <bool GT = false>
 __device__ __forceinline__ void classes_stage(const ClassView& cl, unsigned* tab, TopLevels& top)
 {
     const uint4* src = reinterpret_cast<const uint4*>(cl.C + (GT ? cl.top_first : 0));
     uint4* dst = reinterpret_cast<uint4*>(tab);
-    for (int i = threadIdx.x; i < (cl.stage_words >> 2); i += blockDim.x) dst[i] = src[i];
+    for (int i = threadIdx.x; i < (cl.lds_words >> 2); i += blockDim.x) dst[i] = src[i];
     ClassLevel l6, l7;
     int nx6, nz6, nx7, nz7, w6, w7;
     const int at = GT ? 0 : cl.words;
@@ -440,14 +425,23 @@ __device__ __forceinline__ void classes_stage(const ClassView& cl, unsigned* tab
     class_level_up(nx6, l6.ny, nz6, 7, at + w6, l7, nx7, nz7, w7);
     if (threadIdx.x == 0) { top.lv[0] = l6; top.lv[1] = l7; top.n = cl.top_n; }
     __syncthreads();
-    if (!GT && cl.top_n > 0) {   // launch-uniform
-        classes_level_up(tab, cl.coarse, cl.nx5, cl.nz5, l6, nx6, nz6);
-        __syncthreads();
-        if (cl.top_n > 1) {
-            classes_level_up(tab, l6, nx6, nz6, l7, nx7, nz7);
-            __syncthreads();
-        }
-    }
+}
+
+// does any thread of the workgroup say yes?  One barrier: a ballot per wave, the verdicts of the four waves of a 256-thread
+// workgroup (every kernel that calls this has __launch_bounds__(256) and is launched with dim3(256)) through LDS.
+__device__ __forceinline__ bool workgroup_any(const bool yes, int* s_any)
+{
+    const bool wave_any = __ballot(yes) != 0ull;
+    if ((threadIdx.x & 63) == 0) s_any[threadIdx.x >> 6] = wave_any ? 1 : 0;
+    __syncthreads();
+    return (s_any[0] | s_any[1] | s_any[2] | s_any[3]) != 0;
+}
+// what a ray that hits nothing writes (cu_raycast.cu:104-108)
+__device__ __forceinline__ void write_no_hit(const RayParams& p, const int u, const int v)
+{
+    *(reinterpret_cast<float*>(p.dptr + (size_t)v * p.dpitch) + u) = __builtin_nanf("");
+    *(reinterpret_cast<float*>(p.iptr + (size_t)v * p.ipitch) + u) = 0.f;
+    *(reinterpret_cast<float4*>(p.nptr + (size_t)v * p.npitch) + u) = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
 template <typename CELL, bool GT = false>
@@ -456,17 +450,29 @@ __global__ __launch_bounds__(256) void k_raycast_sdf_classes(const RayParams p, 
     extern __shared__ unsigned s_tab[];
     __shared__ RayParams s_p;
     __shared__ TopLevels s_top;
+    __shared__ int s_any[4];   // (workgroup_any: one word per wave of the 256-thread workgroup)
     if (threadIdx.x == 0) s_p = p;
-    classes_stage<GT>(cl, s_tab, s_top);   // (barriers inside)
     int u, v;
+    bool carries = true;   // sparse lanes: only the first sparse_lanes lanes of a wave carry rays
     if (p.sparse_lanes) {
         const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-        if (lane >= p.sparse_lanes) return;
+        carries = lane < p.sparse_lanes;
         u = (blockIdx.x * 2 + (wv & 1)) * p.sparse_lanes + lane;
         v = blockIdx.y * 2 + (wv >> 1);
     } else {
         ray_pixel_of(p, blockIdx.x, blockIdx.y, threadIdx.x, u, v);
     }
+    // a workgroup without a ray in the box (S_full at 640 x 480: seven in ten) writes "no hit" and leaves before the prologue
+    const bool pixel = carries && u < p.w && v < p.h;
+    // (LDS mode; the global-table kernel's register allocation does not take the extra live ranges)
+    if constexpr (!GT) {
+        if (!workgroup_any(pixel && enters(ray_box(p, u, v)), s_any)) {   // (every thread arrives: idle lanes leave after it)
+            if (pixel) write_no_hit(p, u, v);
+            return;
+        }
+    }
+    classes_stage<GT>(cl, s_tab, s_top);   // (barrier inside)
+    if (!carries) return;
     raycast_pixel_classes<CELL, false, false, GT>(p, s_p, ColorGeom{}, u, v, cl, s_tab, s_top);
 }
 
@@ -595,7 +601,7 @@ __global__ __launch_bounds__(256) void k_raycast_sdf_classes_count(const RayPara
         if (cnt[3]) atomicAdd(&counters[3], (unsigned long long)cnt[3]);
         if (cnt[1]) atomicAdd(&counters[4], (unsigned long long)cnt[1]);
     }
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(&counters[5], (unsigned long long)cl.stage_words * 4ull);
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(&counters[5], (unsigned long long)cl.lds_words * 4ull);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -667,19 +673,30 @@ __global__ __launch_bounds__(256) void k_raycast_sdf_levels_classes(const RayPar
     p.w = lv.w; p.h = lv.h;
     p.K = lv.K;
     __shared__ TopLevels s_top;
+    __shared__ int s_any[4];   // (workgroup_any: one word per wave of the 256-thread workgroup)
     if (threadIdx.x == 0) s_p = p;
-    classes_stage(cl, s_tab, s_top);   // before any lane leaves (barriers inside)
     const int b = (int)blockIdx.x - lv.first_block;
     int u, v;
+    bool carries = true;
     if (lv.sparse) {
         const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-        if (lane >= lv.sparse) return;
+        carries = lane < lv.sparse;
         u = ((b % lv.blocks_x) * 2 + (wv & 1)) * lv.sparse + lane;
         v = (b / lv.blocks_x) * 2 + (wv >> 1);
     } else {
         ray_pixel_of(p, b % lv.blocks_x, b / lv.blocks_x, threadIdx.x, u, v);
     }
-    const float kz = raycast_pixel_classes<CELL, false>(p, s_p, ColorGeom{}, u, v, cl, s_tab, s_top);
+    // as k_raycast_sdf_classes: a workgroup without a ray in the box leaves before the prologue (every thread reaches the barrier)
+    const bool pixel = carries && u < p.w && v < p.h;
+    float kz = __builtin_nanf("");   // what raycast_pixel_classes returns for a ray that hits nothing
+    if (!workgroup_any(pixel && enters(ray_box(p, u, v)), s_any)) {
+        if (!pixel) return;
+        write_no_hit(p, u, v);
+    } else {
+        classes_stage(cl, s_tab, s_top);   // before any lane leaves (barrier inside)
+        if (!carries) return;
+        kz = raycast_pixel_classes<CELL, false>(p, s_p, ColorGeom{}, u, v, cl, s_tab, s_top);
+    }
     if (lv.vptr && u < p.w && v < p.h)
         reinterpret_cast<float4*>(lv.vptr + (size_t)v * lv.vpitch)[u] =
             make_float4(kz * ((float)u - p.K.u0) / p.K.fu, kz * ((float)v - p.K.v0) / p.K.fv, kz, 1.0f);
@@ -928,7 +945,8 @@ static int class_view(ClassView& cl, size_t* lds_bytes, int* usable, kfx_sdf_sum
         if ((size_t)cl.words * 4 <= (size_t)kb_env * 1024) break;
     }
     // the coarser levels (64^3 cells where the 32^3-cell level has more than one entry along some axis, 128^3 cells likewise on
-    // top of that): derived in LDS by every workgroup (classes_stage), or -- global-table mode -- built in global memory
+    // top of that): built in global memory behind the 32^3-cell level (by the table build's last workgroup, or -- global-table
+    // mode -- by launches of their own) and staged with the rest
     auto top_levels = [&](int& w6, int& w7) {
         summary_class_layout(summary, fine, cl);
         cl.nx5 = ceil_div(summary->w, 32); cl.nz5 = ceil_div(summary->d, 32);
@@ -951,12 +969,10 @@ static int class_view(ClassView& cl, size_t* lds_bytes, int* usable, kfx_sdf_sum
         fine = 4;
         top_levels(w6, w7);
         cl.top_first = cl.words;
-        cl.stage_words = (cl.top_n > 0 ? w6 : 0) + (cl.top_n > 1 ? w7 : 0);
-        cl.lds_words = cl.stage_words;
+        cl.lds_words = (cl.top_n > 0 ? w6 : 0) + (cl.top_n > 1 ? w7 : 0);
         if ((size_t)cl.lds_words * 4 + lds_static > 64 * 1024) return 0;
     } else {
         cl.top_first = 0;
-        cl.stage_words = cl.words;
         cl.lds_words = cl.words + derived;
     }
     if (cl.global && !allow_global) return 0;

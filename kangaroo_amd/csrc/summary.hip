@@ -36,6 +36,14 @@ struct ClassBuild {
     const unsigned* src;   // M == 0: the fine level's words
     int src_shift, src_nx, src_ny, src_nz, src_rw;
 };
+// The 64^3- and 128^3-cell levels (LDS mode; the global-table mode builds them with launches of their own): derived from the
+// 32^3-cell level by the last workgroup of its build, into the words summary_top_layout assigns behind it.  tab: the tables' first word.
+struct TopBuild {
+    int on;
+    unsigned* tab;
+    ClassLevel l5, l6, l7;
+    int nx5, nz5, nx6, nz6, nx7, nz7;
+};
 // one wave = 64 consecutive entries of a row; returns (lane 0) the number of them with class != 0
 template <int M>   // summary bricks per fine entry and axis (1: 8^3 cells, 2: 16^3, 4: 32^3 straight from R); 0: combine `src`
 __device__ __forceinline__ int class_row(const ClassBuild& b, const long long wave)
@@ -82,11 +90,10 @@ __device__ __forceinline__ int class_row(const ClassBuild& b, const long long wa
                 for (int y = by * M; y <= by * M + M; ++y)
                     for (int x = bx * M; x <= bx * M + M; ++x) {
                         const float4 r = R[((size_t)min(z, nbz - 1) * nby + min(y, nby - 1)) * nbx + min(x, nbx - 1)];
-                        const int st = __float_as_int(r.z);
-                        const bool in_band = r.x >= lo_ok && r.y <= hi_ok;
-                        all_nan = all_nan && st == 1;
-                        all_free = all_free && st == 0 && in_band;
-                        all_either = all_either && (st == 1 || in_band);
+                        const unsigned m = brick_class_mask(r.x, r.y, __float_as_int(r.z), lo_ok, hi_ok);
+                        all_nan = all_nan && (m & 1u);
+                        all_free = all_free && (m & 2u);
+                        all_either = all_either && (m & 4u);
                     }
         } else {
             // (M + 1)^3 brick ranges, all requested before the first is looked at (fully unrolled: the loop form waited for
@@ -102,11 +109,10 @@ __device__ __forceinline__ int class_row(const ClassBuild& b, const long long wa
                             R[((size_t)min(bz * M + dz, nbz - 1) * nby + min(by * M + dy, nby - 1)) * nbx + min(bx * M + dx, nbx - 1)];
 #pragma unroll
             for (int k = 0; k < (M + 1) * (M + 1) * (M + 1); ++k) {
-                const int st = __float_as_int(r[k].z);
-                const bool in_band = r[k].x >= lo_ok && r[k].y <= hi_ok;   // every valued cell of the brick holds vref (false for the unknown state's infinite range)
-                all_nan = all_nan && st == 1;
-                all_free = all_free && st == 0 && in_band;
-                all_either = all_either && (st == 1 || in_band);
+                const unsigned m = brick_class_mask(r[k].x, r[k].y, __float_as_int(r[k].z), lo_ok, hi_ok);
+                all_nan = all_nan && (m & 1u);
+                all_free = all_free && (m & 2u);
+                all_either = all_either && (m & 4u);
             }
         }
         cls = all_free ? 1 : (all_nan ? 2 : (all_either ? 3 : 0));
@@ -120,35 +126,66 @@ __device__ __forceinline__ int class_row(const ClassBuild& b, const long long wa
     return __popcll(p0 | p1);
 }
 
-// the fine level: one wave per row of 64 entries
+// the fine level: one wave per row of 64 entries.  dirty != nullptr (a conditional build: the host knows of nothing but tracked
+// SdfFuse launches since the last build): the tables are rebuilt only if one of those launches saw a brick change its class
+// mask (*dirty, kfx_sdf_summary::d_dirty); otherwise they are the bits this launch would write.
 template <int M>
-__global__ __launch_bounds__(256) void k_summary_classes(const ClassBuild b, const long long n_waves)
+__global__ __launch_bounds__(256) void k_summary_classes(const ClassBuild b, const long long n_waves, const int* __restrict__ dirty)
 {
+    if (dirty && *dirty == 0) return;   // (uniform)
     const long long wave = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (wave < n_waves) class_row<M>(b, wave);
 }
 
 // the 32^3-cell level: the workgroups add up their entries of class != 0 (LDS), take a ticket, and the last one publishes the
 // total in host-visible memory and clears the counters for the next build -- the host reads that word without synchronising
-// (raycast.hip, class_view).  count = {running total, tickets taken}.
+// (raycast.hip, class_view).  count = {running total, tickets taken, the total of the last real build, conditional builds that
+// built, conditional builds that returned early}.  conditional: as k_summary_classes -- with *dirty == 0 nothing is built and
+// one thread publishes the retained total, so the host sees what it would have seen.  The last workgroup of a real build
+// retains the total and clears *dirty: every workgroup of both launches has read it by then.  It also derives the two coarser
+// levels (TopBuild) from rows that other workgroups -- on other XCDs, whose L2s are not coherent with this one's -- wrote: the
+// writers' agent-scope fence before the ticket and this workgroup's agent-scope fence after it order those rows before the reads.
 template <int M>
-__global__ __launch_bounds__(256) void k_summary_classes_coarse(const ClassBuild b, const long long n_waves, int* __restrict__ count, int* __restrict__ publish)
+__global__ __launch_bounds__(256) void k_summary_classes_coarse(const ClassBuild b, const long long n_waves, int* __restrict__ count, int* __restrict__ publish,
+                                                                int* __restrict__ dirty, const int conditional, const TopBuild t)
 {
     __shared__ int s_count[4];
+    __shared__ int s_last;
+    if (conditional && *dirty == 0) {   // (uniform)
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            __hip_atomic_store(publish, count[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            count[4] += 1;
+        }
+        return;
+    }
     const int wv = threadIdx.x >> 6;
     const long long wave = (long long)blockIdx.x * 4 + wv;
     const int n = wave < n_waves ? class_row<M>(b, wave) : 0;
     if ((threadIdx.x & 63) == 0) s_count[wv] = n;
+    __threadfence();   // (release, agent scope: this thread's rows, for the workgroup that derives the coarser levels)
     __syncthreads();
     if (threadIdx.x == 0) {
+        s_last = 0;
         atomicAdd(&count[0], s_count[0] + s_count[1] + s_count[2] + s_count[3]);
         __threadfence();
         if (atomicAdd(&count[1], 1) == (int)gridDim.x - 1) {   // every workgroup's contribution is in
             __threadfence();
+            s_last = 1;
             const int total = atomicExch(&count[0], 0);
             count[1] = 0;
+            count[2] = total;
+            if (conditional) count[3] += 1;
+            *dirty = 0;
             __hip_atomic_store(publish, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
+    }
+    __syncthreads();
+    if (t.on && s_last) {   // (uniform) the last workgroup: every row of the 32^3-cell level has been written and released
+        __threadfence();    // (acquire, agent scope, by every thread that is about to read them)
+        classes_level_up(t.tab, t.l5, t.nx5, t.nz5, t.l6, t.nx6, t.nz6);
+        __threadfence();
+        __syncthreads();
+        classes_level_up(t.tab, t.l6, t.nx6, t.nz6, t.l7, t.nx7, t.nz7);
     }
 }
 
@@ -250,18 +287,31 @@ void summary_top_layout(const ClassView& cv, ClassLevel& l6, ClassLevel& l7, int
 
 int summary_classes_prepare(kfx_sdf_summary* s, float tol, float vref, int fine_shift, hipStream_t stream, int global)
 {
-    if (!s->c_dirty && s->c_tol == tol && s->c_vref == vref && s->c_shift == fine_shift && s->c_global == global) return 0;
+    const bool same = s->c_tol == tol && s->c_vref == vref && s->c_shift == fine_shift && s->c_global == global;
+    if (!s->c_dirty && same) return 0;
+    // Only tracked SdfFuse launches since the tables were built for these parameters: the same launches, which return at once
+    // unless one of those saw a brick change its class mask (d_dirty).  Everything else -- and the global-table mode, whose two
+    // further levels are built by launches of their own and which the headline does not run -- builds unconditionally.
+    const int conditional = (s->c_dirty == 1 && same && !global) ? 1 : 0;
+    const int* fine_dirty = conditional ? s->d_dirty : nullptr;
     ClassView cv;
     summary_class_layout(s, fine_shift, cv);
     cv.nx5 = ceil_div(s->w, 32); cv.nz5 = ceil_div(s->d, 32);
     ClassLevel l6, l7;
     int w6, w7;
     summary_top_layout(cv, l6, l7, w6, w7);
+    TopBuild top{};
+    top.on = global ? 0 : 1;
+    top.tab = s->C;
+    top.l5 = cv.coarse; top.l6 = l6; top.l7 = l7;
+    top.nx5 = cv.nx5; top.nz5 = cv.nz5;
+    top.nx6 = (top.nx5 + 1) >> 1; top.nz6 = (top.nz5 + 1) >> 1;
+    top.nx7 = (top.nx6 + 1) >> 1; top.nz7 = (top.nz6 + 1) >> 1;
     const float lo_ok = vref - tol * vref, hi_ok = vref + tol * vref;
     for (int pass = 0; pass < (global ? 4 : 2); ++pass) {
         if (pass >= 2) {
             // global-table mode: the 64^3- and 128^3-cell levels, each the combination of the level below it (m = 2) -- the
-            // same entries classes_level_up derives in LDS (raycast.hip)
+            // same entries classes_level_up derives in the LDS mode's build
             const ClassLevel& L = pass == 2 ? l6 : l7;
             const ClassLevel& S = pass == 2 ? cv.coarse : l6;
             ClassBuild b;
@@ -272,7 +322,7 @@ int summary_classes_prepare(kfx_sdf_summary* s, float tol, float vref, int fine_
             b.src = s->C + S.first;
             b.src_shift = S.shift; b.src_nx = ceil_div(s->w, 1 << S.shift); b.src_ny = S.ny; b.src_nz = ceil_div(s->d, 1 << S.shift); b.src_rw = S.rw;
             const long long waves = (long long)ceil_div(b.nx, 64) * b.ny * b.nz;
-            hipLaunchKernelGGL(k_summary_classes<0>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, b, waves);
+            hipLaunchKernelGGL(k_summary_classes<0>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, b, waves, (const int*)nullptr);
             if (int e = check_launch("kfx_sdf_summary (classes)")) return e;
             continue;
         }
@@ -292,18 +342,19 @@ int summary_classes_prepare(kfx_sdf_summary* s, float tol, float vref, int fine_
             const dim3 grid((unsigned)((waves + 3) / 4));
             const unsigned slot = s->builds % KFX_SUMMARY_RING;
             int* publish = s->d_skippable + (s->h_skippable ? slot : 0);
-            if (from_fine) hipLaunchKernelGGL(k_summary_classes_coarse<0>, grid, dim3(256), 0, stream, b, waves, s->d_count, publish);
-            else hipLaunchKernelGGL(k_summary_classes_coarse<4>, grid, dim3(256), 0, stream, b, waves, s->d_count, publish);
+            if (from_fine) hipLaunchKernelGGL(k_summary_classes_coarse<0>, grid, dim3(256), 0, stream, b, waves, s->d_count, publish, s->d_dirty, conditional, top);
+            else hipLaunchKernelGGL(k_summary_classes_coarse<4>, grid, dim3(256), 0, stream, b, waves, s->d_count, publish, s->d_dirty, conditional, top);
             if (s->h_skippable) (void)hipEventRecord(s->build_done[slot], stream);
             s->builds += 1;
         } else if (L.shift == 3) {
-            hipLaunchKernelGGL(k_summary_classes<1>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, b, waves);
+            hipLaunchKernelGGL(k_summary_classes<1>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, b, waves, fine_dirty);
         } else {
-            hipLaunchKernelGGL(k_summary_classes<2>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, b, waves);
+            hipLaunchKernelGGL(k_summary_classes<2>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, b, waves, fine_dirty);
         }
         if (int e = check_launch("kfx_sdf_summary (classes)")) return e;
     }
     s->c_dirty = 0; s->c_tol = tol; s->c_vref = vref; s->c_shift = fine_shift; s->c_global = global;
+    s->c_lo_ok = lo_ok; s->c_hi_ok = hi_ok;
     return 0;
 }
 
@@ -338,22 +389,22 @@ static int summary_create(kfx_sdf_summary** out, const kfx_volume* vol, int cell
     s->base = static_cast<const unsigned char*>(vol->ptr);
     s->pitch = vol->pitch; s->img_pitch = vol->img_pitch;
     s->R = nullptr; s->C = nullptr; s->d_count = nullptr; s->h_skippable = nullptr; s->d_skippable = nullptr;
-    s->c_dirty = 1; s->c_tol = -1.f; s->c_vref = 0.f; s->c_shift = 0; s->c_global = 0; s->sweeps = 0;
+    s->c_dirty = 2; s->c_tol = -1.f; s->c_vref = 0.f; s->c_shift = 0; s->c_global = 0; s->sweeps = 0;
+    s->c_lo_ok = 0.f; s->c_hi_ok = 0.f; s->d_dirty = nullptr;
     s->builds = 0; s->plain_calls = 0;
     for (auto& e : s->build_done) e = nullptr;
     s->n_coarse = ceil_div(s->w, 32) * ceil_div(s->h, 32) * ceil_div(s->d, 32);
     const size_t n = (size_t)s->nbx * s->nby * s->nbz;
     ClassView cv;
-    summary_class_layout(s, 3, cv);   // the finest level is the largest table ...
-    ClassView cg;                     // ... except for tiny volumes against the global-table mode's (16^3-cell fine level + 64^3 + 128^3)
-    summary_class_layout(s, 4, cg);
-    cg.nx5 = ceil_div(s->w, 32); cg.nz5 = ceil_div(s->d, 32);
+    summary_class_layout(s, 3, cv);   // the finest level is the largest table; behind it, the 64^3- and 128^3-cell levels
+    cv.nx5 = ceil_div(s->w, 32); cv.nz5 = ceil_div(s->d, 32);
     ClassLevel l6, l7;
     int w6, w7;
-    summary_top_layout(cg, l6, l7, w6, w7);
-    const int words = std::max(cv.words, cg.words + w6 + w7);
+    summary_top_layout(cv, l6, l7, w6, w7);   // (the two levels' sizes do not depend on the fine level)
+    const int words = cv.words + w6 + w7;
     bool ok = hipMalloc((void**)&s->R, n * sizeof(float4)) == hipSuccess && hipMalloc((void**)&s->C, (size_t)words * sizeof(unsigned)) == hipSuccess &&
-              hipMalloc((void**)&s->d_count, 2 * sizeof(int)) == hipSuccess && hipMemset(s->d_count, 0, 2 * sizeof(int)) == hipSuccess;
+              hipMalloc((void**)&s->d_count, 64 * sizeof(int)) == hipSuccess && hipMemset(s->d_count, 0, 64 * sizeof(int)) == hipSuccess;
+    if (ok) s->d_dirty = s->d_count + 32;   // (a cache line of its own: the kernels that set it store plainly, the counters are atomics)
     // the published count lives in pinned host memory the device can write; without it the march always uses the tables
     if (ok && hipHostMalloc((void**)&s->h_skippable, KFX_SUMMARY_RING * sizeof(int), hipHostMallocMapped) == hipSuccess) {
         for (int i = 0; i < KFX_SUMMARY_RING; ++i) s->h_skippable[i] = -1;
@@ -408,7 +459,7 @@ extern "C" int kfx_sdf_summary_rebuild(kfx_sdf_summary* s, kfx_stream stream)
     else
         hipLaunchKernelGGL(k_summary_rebuild<8>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, s->R, s->base, s->pitch, s->img_pitch,
                            s->w, s->h, s->d, s->nbx, s->nby, s->nbz, aligned16);
-    s->c_dirty = 1;
+    s->c_dirty = 2;
     return check_launch("kfx_sdf_summary_rebuild");
 }
 
@@ -419,7 +470,7 @@ extern "C" int kfx_sdf_summary_invalidate(kfx_sdf_summary* s, kfx_stream stream)
     if (!s) return set_error(KFX_E_NULL, "kfx_sdf_summary_invalidate: null summary");
     const size_t n = (size_t)s->nbx * s->nby * s->nbz;
     hipLaunchKernelGGL(k_summary_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, s->R, n, -__builtin_inff(), __builtin_inff(), 2);
-    s->c_dirty = 1;
+    s->c_dirty = 2;
     return check_launch("kfx_sdf_summary_invalidate");
 }
 
@@ -439,7 +490,7 @@ static int reset_tracked(const kfx_volume* vol, kfx_sdf_summary* s, float trunc_
     const float v = cell_bytes == 4 ? __half2float(__float2half_rn(trunc_dist)) : trunc_dist;
     hipLaunchKernelGGL(k_summary_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, s->R, n,
                        nan ? __builtin_inff() : v, nan ? -__builtin_inff() : v, nan ? 1 : 0);
-    s->c_dirty = 1;
+    s->c_dirty = 2;
     return check_launch(name);
 }
 
