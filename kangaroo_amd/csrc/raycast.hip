@@ -62,23 +62,140 @@ __device__ __forceinline__ void ray_pixel_of(const RayParams& p, int bx, int by,
     v = (by * wgy + (wv >> p.wg_log2x)) * th + (lane >> p.tile_log2w);
 }
 
-// one ray: KernRaycastSdf (cu_raycast.cu:34-113) for pixel (u, v).
+// The same for a launch with sparse lanes (sparse != 0: small images and coarse pyramid levels).  Only the first `sparse` lanes
+// of a wave carry rays, a strip of one pixel row, and a workgroup is 2 x 2 strips: neighbouring rays are many voxels apart
+// there, so every lane of a load fetches its own line and a wave-step waits for the slowest of its misses -- of `sparse`
+// instead of 64.  Returns whether the lane carries a ray.
+__device__ __forceinline__ bool ray_lane_pixel(const RayParams& p, int sparse, int bx, int by, int& u, int& v)
+{
+    if (!sparse) {
+        ray_pixel_of(p, bx, by, threadIdx.x, u, v);
+        return true;
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    u = (bx * 2 + (wv & 1)) * sparse + lane;
+    v = by * 2 + (wv >> 1);
+    return lane < sparse;
+}
+
+// The ray of pixel (u, v) and the slab test against the volume's box (cu_raycast.cu:40-51): the one definition the marches, the
+// workgroups' vote before their prologue (k_raycast_sdf_classes) and the epilogue (write_ray: the ray alone) share.
+struct RayBox { V3 c_w, ray_c, ray_w; float max_tmin, min_tmax; };
+__device__ __forceinline__ RayBox ray_box(const RayParams& p, const int u, const int v)
+{
+    RayBox b;
+    b.c_w = v3(p.T.m[3], p.T.m[7], p.T.m[11]);                                        // SE3Translation
+    b.ray_c = v3(((float)u - p.K.u0) / p.K.fu, ((float)v - p.K.v0) / p.K.fv, 1.0f);   // Unproject
+    b.ray_w = so3_mul(p.T, b.ray_c);
+    const V3 ta = div_cw(p.vol.bmin - b.c_w, b.ray_w);
+    const V3 tb = div_cw(p.vol.bmax - b.c_w, b.ray_w);
+    const V3 tmin = v3(fminf(ta.x, tb.x), fminf(ta.y, tb.y), fminf(ta.z, tb.z));
+    const V3 tmax = v3(fmaxf(ta.x, tb.x), fmaxf(ta.y, tb.y), fmaxf(ta.z, tb.z));
+    b.max_tmin = fmaxf(fmaxf(fmaxf(tmin.x, tmin.y), tmin.z), p.near);
+    b.min_tmax = fminf(fminf(fminf(tmax.x, tmax.y), tmax.z), p.far);
+    return b;
+}
+__device__ __forceinline__ bool enters(const RayBox& b) { return b.max_tmin < b.min_tmax; }
+
+// the surface normal at pos_w in the camera frame (cu_raycast.cu:92-97): the normalised gradient, (0, 0, 1) where it vanishes
+template <typename CELL>
+__device__ __forceinline__ V3 normal_c(const RayParams& p, const V3 pos_w)
+{
+    const V3 g = gradient<CELL>(p, pos_w);
+    const float len = length(g);
+    const V3 n_w = len > 0 ? div_s(g, len) : v3(0.f, 0.f, 1.f);
+    return so3_mul_inv(p.T, n_w);
+}
+
+// where pixel (u, v) of the three output images lies
+struct RayOut { float* depth; float* shade; float4* normal; };
+__device__ __forceinline__ RayOut ray_out(const RayParams& p, const int u, const int v)
+{
+    return RayOut{reinterpret_cast<float*>(p.dptr + (size_t)v * p.dpitch) + u, reinterpret_cast<float*>(p.iptr + (size_t)v * p.ipitch) + u,
+                  reinterpret_cast<float4*>(p.nptr + (size_t)v * p.npitch) + u};
+}
+// what a ray that hits nothing writes (cu_raycast.cu:104-108)
+__device__ __forceinline__ void write_no_hit(const RayOut& o)
+{
+    *o.depth = __builtin_nanf("");
+    *o.shade = 0.f;
+    *o.normal = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+// What a ray writes (cu_raycast.cu:90-108): depth, normal and shade of a hit at `depth` along the ray (depth > 0), else "no
+// hit".  q is the parameter block to read from: the kernel's arguments, or the class kernels' copy of them in LDS -- the ray
+// again, the same expressions on the same values.
 template <typename CELL, bool COLOR>
-__device__ __forceinline__ float raycast_pixel(const RayParams& p, const ColorGeom& cv, const int u, const int v)
+__device__ __forceinline__ void write_ray(const RayParams& q, const ColorGeom& cv, const int u, const int v, const float depth)
+{
+    const RayOut o = ray_out(q, u, v);
+    if (depth > 0) {
+        const RayBox r = ray_box(q, u, v);
+        const V3 n_c = normal_c<CELL>(q, r.c_w + r.ray_w * depth);
+        *o.depth = depth;
+        // colour variant: img = colorVol.GetUnitsTrilinearClamped(pos_w) instead of the Phong shade (cu_raycast.cu:172,179)
+        if constexpr (COLOR) *o.shade = trilinear<RayC32>(cv, r.c_w + r.ray_w * depth);
+        else *o.shade = phong(r.ray_c * depth, n_c);
+        *o.normal = make_float4(n_c.x, n_c.y, n_c.z, 1.0f);
+    } else {
+        write_no_hit(o);
+    }
+}
+
+// COUNT mode of the marches (kfx_raycast_sdf_count[_tracked]): every cell a sample or a hit's gradient stencil reads is marked
+// in a bitmap (one bit per voxel, dense x-fastest index) and counted in cnt[] = {samples, table look-ups, hits, newly marked
+// cells}; no image is written.  U = distinct voxels touched is the figure SURVEY.md 8(d) prices RaycastSdf's algorithmic bytes
+// with (8 B x U + 24 B x w h).
+__device__ __forceinline__ unsigned touch(unsigned* bitmap, const VolView& v, int x, int y, int z)
+{
+    const size_t i = ((size_t)z * v.h + y) * v.w + x;
+    const unsigned bit = 1u << (i & 31);
+    unsigned* word = bitmap + (i >> 5);
+    if (*reinterpret_cast<volatile unsigned*>(word) & bit) return 0u;
+    return (atomicOr(word, bit) & bit) ? 0u : 1u;
+}
+// one sample: its 8 cells (c by value: behind a reference touch()'s atomics make the compiler reload it, at the price of SGPR spills)
+__device__ __forceinline__ void touch_sample(unsigned* bitmap, const VolView& vol, const CellPos c, unsigned* cnt)
+{
+    cnt[0] += 1;
+    for (int k = 0; k < 8; ++k) cnt[3] += touch(bitmap, vol, c.ix + (k & 1), c.iy + ((k >> 1) & 1), c.iz + (k >> 2));
+}
+// one hit: the gradient's 20 cells, {-1, 0, 1}^3 around its base cell with at most one coordinate at -1 (sampling.h)
+__device__ __forceinline__ void touch_gradient(unsigned* bitmap, const RayParams& p, const V3 pos_w, unsigned* cnt)
+{
+    cnt[2] += 1;
+    const V3 pos_v = div_cw(pos_w - p.vol.bmin, p.size);
+    const int ix = (int)fmaxf(fminf(p.hi2.x, floorf(pos_v.x * p.dims1.x)), 1.f), iy = (int)fmaxf(fminf(p.hi2.y, floorf(pos_v.y * p.dims1.y)), 1.f),
+              iz = (int)fmaxf(fminf(p.hi2.z, floorf(pos_v.z * p.dims1.z)), 1.f);
+    for (int dz = -1; dz < 2; ++dz)
+        for (int dy = -1; dy < 2; ++dy)
+            for (int dx = -1; dx < 2; ++dx)
+                if ((dx < 0) + (dy < 0) + (dz < 0) <= 1) cnt[3] += touch(bitmap, p.vol, ix + dx, iy + dy, iz + dz);
+}
+// a wave's counts into counters[] = {samples, rays that enter the box, hits, U, table look-ups} (include/kfx_debug.h)
+__device__ __forceinline__ void publish_counts(const unsigned* cnt, const unsigned entered, unsigned long long* counters)
+{
+    unsigned c[5] = {cnt[0], entered, cnt[2], cnt[3], cnt[1]};
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+        for (int k = 0; k < 5; ++k) c[k] += __shfl_xor(c[k], off, 64);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k)
+            if (c[k]) atomicAdd(&counters[k], (unsigned long long)c[k]);
+    }
+}
+
+// one ray: KernRaycastSdf (cu_raycast.cu:34-113) for pixel (u, v).  Returns the value written to the depth image.
+template <typename CELL, bool COLOR, bool COUNT = false>
+__device__ __forceinline__ float raycast_pixel(const RayParams& p, const ColorGeom& cv, const int u, const int v, unsigned* bitmap = nullptr,
+                                               unsigned* cnt = nullptr)
 {
     if (u >= p.w || v >= p.h) return 0.f;
 
-    const V3 c_w = v3(p.T.m[3], p.T.m[7], p.T.m[11]);                              // SE3Translation
-    const V3 ray_c = v3(((float)u - p.K.u0) / p.K.fu, ((float)v - p.K.v0) / p.K.fv, 1.0f); // Unproject
-    const V3 ray_w = so3_mul(p.T, ray_c);
-
-    // slab test against the volume's box (cu_raycast.cu:46-51)
-    const V3 ta = div_cw(p.vol.bmin - c_w, ray_w);
-    const V3 tb = div_cw(p.vol.bmax - c_w, ray_w);
-    const V3 tmin = v3(fminf(ta.x, tb.x), fminf(ta.y, tb.y), fminf(ta.z, tb.z));
-    const V3 tmax = v3(fmaxf(ta.x, tb.x), fmaxf(ta.y, tb.y), fmaxf(ta.z, tb.z));
-    const float max_tmin = fmaxf(fmaxf(fmaxf(tmin.x, tmin.y), tmin.z), p.near);
-    const float min_tmax = fminf(fminf(fminf(tmax.x, tmax.y), tmax.z), p.far);
+    const RayBox box = ray_box(p, u, v);
+    const V3 c_w = box.c_w, ray_w = box.ray_w;
+    const float max_tmin = box.max_tmin, min_tmax = box.min_tmax;
 
     float depth = 0.0f;
     if (max_tmin < min_tmax) {
@@ -87,7 +204,9 @@ __device__ __forceinline__ float raycast_pixel(const RayParams& p, const ColorGe
         const float min_delta = p.voxel.x;
         float delta = 0.f;
         while (lambda < min_tmax) {
-            const float sdf = trilinear<CELL>(p, c_w + ray_w * lambda);
+            const V3 pos_w = c_w + ray_w * lambda;
+            if constexpr (COUNT) touch_sample(bitmap, p.vol, cell_of(p, pos_w), cnt);
+            const float sdf = trilinear<CELL>(p, pos_w);
             if (sdf <= 0) {
                 if (last_sdf > 0) {
                     if (p.subpix) lambda = lambda + delta * sdf / (last_sdf - sdf);
@@ -101,28 +220,13 @@ __device__ __forceinline__ float raycast_pixel(const RayParams& p, const ColorGe
         }
     }
 
-    float* pd = reinterpret_cast<float*>(p.dptr + (size_t)v * p.dpitch) + u;
-    float* pi = reinterpret_cast<float*>(p.iptr + (size_t)v * p.ipitch) + u;
-    float4* pn = reinterpret_cast<float4*>(p.nptr + (size_t)v * p.npitch) + u;
-    if (depth > 0) {
-        const V3 g = gradient<CELL>(p, c_w + ray_w * depth);
-        const float len = length(g);
-        const V3 n_w = len > 0 ? div_s(g, len) : v3(0.f, 0.f, 1.f);
-        const V3 n_c = so3_mul_inv(p.T, n_w);
-        const V3 p_c = ray_c * depth;
-        *pd = depth;
-        // colour variant: img = colorVol.GetUnitsTrilinearClamped(pos_w) instead of the Phong shade (cu_raycast.cu:172,179)
-        if constexpr (COLOR) *pi = trilinear<RayC32>(cv, c_w + ray_w * depth);
-        else *pi = phong(p_c, n_c);
-        *pn = make_float4(n_c.x, n_c.y, n_c.z, 1.0f);
+    if constexpr (COUNT) {
+        if (depth > 0) touch_gradient(bitmap, p, c_w + ray_w * depth, cnt);
     } else {
-        *pd = __builtin_nanf("");
-        *pi = 0.f;
-        *pn = make_float4(0.f, 0.f, 0.f, 0.f);
+        write_ray<CELL, COLOR>(p, cv, u, v, depth);
     }
-    return depth > 0 ? depth : __builtin_nanf(""); // the value written to the depth image
+    return depth > 0 ? depth : __builtin_nanf("");
 }
-
 
 // ---------------------------------------------------------------------------------------
 // The march through the class tables (ClassView, kfx_device.h).  Every workgroup stages the tables -- a
@@ -152,32 +256,11 @@ __device__ __forceinline__ int class_lookup(const unsigned* tab, const ClassLeve
     return (int)((w.x >> (bx & 31)) & 1u) | (int)(((w.y >> (bx & 31)) & 1u) << 1);
 }
 
-// COUNT (kfx_raycast_sdf_count_tracked): the same march with every cell it reads marked in a bitmap and its samples, table
-// look-ups and hits counted in cnt[] = {samples, look-ups, hit, newly marked cells}; writes no image.
-__device__ __forceinline__ unsigned touch(unsigned* bitmap, const VolView& v, int x, int y, int z);
 // GT (global-table mode, ClassView::global): the fine and 32^3-cell levels are read from global memory (cl.C), the 64^3 and
 // 128^3 levels from LDS, and the levels are consulted coarse-first: a coarse entry of class != 0 implies that every entry below
 // it is != 0, so the coarsest level with class != 0 is the one the fine-first order of the LDS mode arrives at -- the same
 // runs, the same images -- and a ray in wide free space does not touch the global tables.
-// The ray of pixel (u, v) and the slab test against the volume's box (cu_raycast.cu:40-51): the one definition the march and
-// the workgroups' vote before their prologue (k_raycast_sdf_classes) share.
-struct RayBox { V3 c_w, ray_c, ray_w; float max_tmin, min_tmax; };
-__device__ __forceinline__ RayBox ray_box(const RayParams& p, const int u, const int v)
-{
-    RayBox b;
-    b.c_w = v3(p.T.m[3], p.T.m[7], p.T.m[11]);
-    b.ray_c = v3(((float)u - p.K.u0) / p.K.fu, ((float)v - p.K.v0) / p.K.fv, 1.0f);
-    b.ray_w = so3_mul(p.T, b.ray_c);
-    const V3 ta = div_cw(p.vol.bmin - b.c_w, b.ray_w);
-    const V3 tb = div_cw(p.vol.bmax - b.c_w, b.ray_w);
-    const V3 tmin = v3(fminf(ta.x, tb.x), fminf(ta.y, tb.y), fminf(ta.z, tb.z));
-    const V3 tmax = v3(fmaxf(ta.x, tb.x), fmaxf(ta.y, tb.y), fmaxf(ta.z, tb.z));
-    b.max_tmin = fmaxf(fmaxf(fmaxf(tmin.x, tmin.y), tmin.z), p.near);
-    b.min_tmax = fminf(fminf(fminf(tmax.x, tmax.y), tmax.z), p.far);
-    return b;
-}
-__device__ __forceinline__ bool enters(const RayBox& b) { return b.max_tmin < b.min_tmax; }
-
+// COUNT: as raycast_pixel's.
 template <typename CELL, bool COLOR, bool COUNT = false, bool GT = false>
 __device__ __forceinline__ float raycast_pixel_classes(const RayParams& p, const RayParams& q, const ColorGeom& cv, const int u, const int v, const ClassView& cl_arg, const unsigned* tab,
                                                        const TopLevels& top, unsigned* bitmap = nullptr, unsigned* cnt = nullptr)
@@ -237,10 +320,7 @@ __device__ __forceinline__ float raycast_pixel_classes(const RayParams& p, const
             if (!look) {
                 c = cell_of(p, c_w + ray_w * lambda);
                 trilinear_issue<CELL>(fl, p, c);
-                if constexpr (COUNT) {
-                    cnt[0] += 1;
-                    for (int k = 0; k < 8; ++k) cnt[3] += touch(bitmap, p.vol, c.ix + (k & 1), c.iy + ((k >> 1) & 1), c.iz + (k >> 2));
-                }
+                if constexpr (COUNT) touch_sample(bitmap, p.vol, c, cnt);
             }
             if (look) {
                 if constexpr (COUNT) cnt[1] += 1;
@@ -349,11 +429,7 @@ __device__ __forceinline__ float raycast_pixel_classes(const RayParams& p, const
                     // a crossing needs the previous sample's value: the one thing a class-3 step left open
                     if (pending) {
                         last_sdf = trilinear<CELL>(p, c_w + ray_w * lambda_prev);
-                        if constexpr (COUNT) {
-                            const CellPos cp = cell_of(p, c_w + ray_w * lambda_prev);
-                            cnt[0] += 1;
-                            for (int k = 0; k < 8; ++k) cnt[3] += touch(bitmap, p.vol, cp.ix + (k & 1), cp.iy + ((k >> 1) & 1), cp.iz + (k >> 2));
-                        }
+                        if constexpr (COUNT) touch_sample(bitmap, p.vol, cell_of(p, c_w + ray_w * lambda_prev), cnt);
                     }
                     if (last_sdf > 0) {
                         if (p.subpix) lambda = lambda + delta * sdf / (last_sdf - sdf);
@@ -370,40 +446,10 @@ __device__ __forceinline__ float raycast_pixel_classes(const RayParams& p, const
         }
     }
 
-    if constexpr (COUNT) {   // the gradient's cells of a hit (the 20 of {-1, 0, 1}^3 with at most one coordinate at -1: sampling.h)
-        if (depth > 0) {
-            cnt[2] += 1;
-            const V3 pos_v = div_cw(c_w + ray_w * depth - p.vol.bmin, p.size);
-            const int ix = (int)fmaxf(fminf(p.hi2.x, floorf(pos_v.x * p.dims1.x)), 1.f), iy = (int)fmaxf(fminf(p.hi2.y, floorf(pos_v.y * p.dims1.y)), 1.f),
-                      iz = (int)fmaxf(fminf(p.hi2.z, floorf(pos_v.z * p.dims1.z)), 1.f);
-            for (int dz = -1; dz < 2; ++dz)
-                for (int dy = -1; dy < 2; ++dy)
-                    for (int dx = -1; dx < 2; ++dx)
-                        if ((dx < 0) + (dy < 0) + (dz < 0) <= 1) cnt[3] += touch(bitmap, p.vol, ix + dx, iy + dy, iz + dz);
-        }
-        return depth > 0 ? depth : __builtin_nanf("");
-    }
-    float* pd = reinterpret_cast<float*>(q.dptr + (size_t)v * q.dpitch) + u;
-    float* pi = reinterpret_cast<float*>(q.iptr + (size_t)v * q.ipitch) + u;
-    float4* pn = reinterpret_cast<float4*>(q.nptr + (size_t)v * q.npitch) + u;
-    if (depth > 0) {
-        // the ray again, from the LDS copy: the same expressions on the same values
-        const V3 cq = v3(q.T.m[3], q.T.m[7], q.T.m[11]);
-        const V3 rcq = v3(((float)u - q.K.u0) / q.K.fu, ((float)v - q.K.v0) / q.K.fv, 1.0f);
-        const V3 rq = so3_mul(q.T, rcq);
-        const V3 g = gradient<CELL>(q, cq + rq * depth);
-        const float len = length(g);
-        const V3 n_w = len > 0 ? div_s(g, len) : v3(0.f, 0.f, 1.f);
-        const V3 n_c = so3_mul_inv(q.T, n_w);
-        const V3 p_c = rcq * depth;
-        *pd = depth;
-        if constexpr (COLOR) *pi = trilinear<RayC32>(cv, cq + rq * depth);
-        else *pi = phong(p_c, n_c);
-        *pn = make_float4(n_c.x, n_c.y, n_c.z, 1.0f);
+    if constexpr (COUNT) {
+        if (depth > 0) touch_gradient(bitmap, p, c_w + ray_w * depth, cnt);
     } else {
-        *pd = __builtin_nanf("");
-        *pi = 0.f;
-        *pn = make_float4(0.f, 0.f, 0.f, 0.f);
+        write_ray<CELL, COLOR>(q, cv, u, v, depth);
     }
     return depth > 0 ? depth : __builtin_nanf("");
 }
@@ -436,13 +482,6 @@ __device__ __forceinline__ bool workgroup_any(const bool yes, int* s_any)
     __syncthreads();
     return (s_any[0] | s_any[1] | s_any[2] | s_any[3]) != 0;
 }
-// what a ray that hits nothing writes (cu_raycast.cu:104-108)
-__device__ __forceinline__ void write_no_hit(const RayParams& p, const int u, const int v)
-{
-    *(reinterpret_cast<float*>(p.dptr + (size_t)v * p.dpitch) + u) = __builtin_nanf("");
-    *(reinterpret_cast<float*>(p.iptr + (size_t)v * p.ipitch) + u) = 0.f;
-    *(reinterpret_cast<float4*>(p.nptr + (size_t)v * p.npitch) + u) = make_float4(0.f, 0.f, 0.f, 0.f);
-}
 
 template <typename CELL, bool GT = false>
 __global__ __launch_bounds__(256) void k_raycast_sdf_classes(const RayParams p, const ClassView cl)
@@ -453,21 +492,13 @@ __global__ __launch_bounds__(256) void k_raycast_sdf_classes(const RayParams p, 
     __shared__ int s_any[4];   // (workgroup_any: one word per wave of the 256-thread workgroup)
     if (threadIdx.x == 0) s_p = p;
     int u, v;
-    bool carries = true;   // sparse lanes: only the first sparse_lanes lanes of a wave carry rays
-    if (p.sparse_lanes) {
-        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-        carries = lane < p.sparse_lanes;
-        u = (blockIdx.x * 2 + (wv & 1)) * p.sparse_lanes + lane;
-        v = blockIdx.y * 2 + (wv >> 1);
-    } else {
-        ray_pixel_of(p, blockIdx.x, blockIdx.y, threadIdx.x, u, v);
-    }
+    const bool carries = ray_lane_pixel(p, p.sparse_lanes, blockIdx.x, blockIdx.y, u, v);
     // a workgroup without a ray in the box (S_full at 640 x 480: seven in ten) writes "no hit" and leaves before the prologue
     const bool pixel = carries && u < p.w && v < p.h;
     // (LDS mode; the global-table kernel's register allocation does not take the extra live ranges)
     if constexpr (!GT) {
         if (!workgroup_any(pixel && enters(ray_box(p, u, v)), s_any)) {   // (every thread arrives: idle lanes leave after it)
-            if (pixel) write_no_hit(p, u, v);
+            if (pixel) write_no_hit(ray_out(p, u, v));
             return;
         }
     }
@@ -480,88 +511,22 @@ template <typename CELL, bool COLOR>
 __global__ __launch_bounds__(256) void k_raycast_sdf(const RayParams p, const ColorGeom cv)
 {
     int u, v;
-    if (p.sparse_lanes) { // only the first sparse_lanes lanes of a wave carry rays (a strip of one pixel row): small images
-        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-        if (lane >= p.sparse_lanes) return;
-        u = (blockIdx.x * 2 + (wv & 1)) * p.sparse_lanes + lane;
-        v = blockIdx.y * 2 + (wv >> 1);
-    } else {
-        ray_pixel_of(p, blockIdx.x, blockIdx.y, threadIdx.x, u, v);
-    }
+    if (!ray_lane_pixel(p, p.sparse_lanes, blockIdx.x, blockIdx.y, u, v)) return;
     raycast_pixel<CELL, COLOR>(p, cv, u, v);
 }
 
-// Diagnostics (kfx_raycast_sdf_count): the march of k_raycast_sdf with every cell a sample or a hit's gradient stencil reads
-// marked in a bitmap (one bit per voxel, dense x-fastest index): U = distinct voxels touched is the figure SURVEY.md 8(d)
-// prices RaycastSdf's algorithmic bytes with (8 B x U + 24 B x w h).  counters: {samples, rays that enter the box, hits, U}.
-__device__ __forceinline__ unsigned touch(unsigned* bitmap, const VolView& v, int x, int y, int z)
-{
-    const size_t i = ((size_t)z * v.h + y) * v.w + x;
-    const unsigned bit = 1u << (i & 31);
-    unsigned* word = bitmap + (i >> 5);
-    if (*reinterpret_cast<volatile unsigned*>(word) & bit) return 0u;
-    return (atomicOr(word, bit) & bit) ? 0u : 1u;
-}
+// Diagnostics (kfx_raycast_sdf_count): the march of k_raycast_sdf in COUNT mode.  counters: {samples, rays that enter the box, hits, U}.
 template <typename CELL>
 __global__ __launch_bounds__(256) void k_raycast_sdf_count(const RayParams p, unsigned* __restrict__ bitmap, unsigned long long* __restrict__ counters)
 {
     int u, v;
     ray_pixel_of(p, blockIdx.x, blockIdx.y, threadIdx.x, u, v);
-    unsigned n_samples = 0, n_new = 0, entered = 0, hit = 0;
+    unsigned cnt[4] = {0u, 0u, 0u, 0u}, entered = 0;
     if (u < p.w && v < p.h) {
-        const V3 c_w = v3(p.T.m[3], p.T.m[7], p.T.m[11]);
-        const V3 ray_c = v3(((float)u - p.K.u0) / p.K.fu, ((float)v - p.K.v0) / p.K.fv, 1.0f);
-        const V3 ray_w = so3_mul(p.T, ray_c);
-        const V3 ta = div_cw(p.vol.bmin - c_w, ray_w);
-        const V3 tb = div_cw(p.vol.bmax - c_w, ray_w);
-        const V3 tmin = v3(fminf(ta.x, tb.x), fminf(ta.y, tb.y), fminf(ta.z, tb.z));
-        const V3 tmax = v3(fmaxf(ta.x, tb.x), fmaxf(ta.y, tb.y), fmaxf(ta.z, tb.z));
-        const float max_tmin = fmaxf(fmaxf(fmaxf(tmin.x, tmin.y), tmin.z), p.near);
-        const float min_tmax = fminf(fminf(fminf(tmax.x, tmax.y), tmax.z), p.far);
-        float depth = 0.0f;
-        if (max_tmin < min_tmax) {
-            entered = 1;
-            float lambda = max_tmin, last_sdf = __builtin_nanf(""), delta = 0.f;
-            const float min_delta = p.voxel.x;
-            while (lambda < min_tmax) {
-                const CellPos c = cell_of(p, c_w + ray_w * lambda);
-                for (int k = 0; k < 8; ++k) n_new += touch(bitmap, p.vol, c.ix + (k & 1), c.iy + ((k >> 1) & 1), c.iz + (k >> 2));
-                n_samples += 1;
-                const float sdf = trilinear_at<CELL>(p, c);
-                if (sdf <= 0) {
-                    if (last_sdf > 0) {
-                        if (p.subpix) lambda = lambda + delta * sdf / (last_sdf - sdf);
-                        depth = lambda;
-                    }
-                    break;
-                }
-                delta = march_step(sdf, min_delta, p.trunc);
-                lambda += delta;
-                last_sdf = sdf;
-            }
-        }
-        if (depth > 0) { // the gradient's cells: {-1, 0, 1}^3 around its base cell with at most one coordinate at -1 (sampling.h)
-            hit = 1;
-            const V3 pos_v = div_cw(c_w + ray_w * depth - p.vol.bmin, p.size);
-            const int ix = (int)fmaxf(fminf(p.hi2.x, floorf(pos_v.x * p.dims1.x)), 1.f), iy = (int)fmaxf(fminf(p.hi2.y, floorf(pos_v.y * p.dims1.y)), 1.f),
-                      iz = (int)fmaxf(fminf(p.hi2.z, floorf(pos_v.z * p.dims1.z)), 1.f);
-            for (int dz = -1; dz < 2; ++dz)
-                for (int dy = -1; dy < 2; ++dy)
-                    for (int dx = -1; dx < 2; ++dx)
-                        if ((dx < 0) + (dy < 0) + (dz < 0) <= 1) n_new += touch(bitmap, p.vol, ix + dx, iy + dy, iz + dz);
-        }
+        entered = enters(ray_box(p, u, v)) ? 1u : 0u;
+        raycast_pixel<CELL, false, true>(p, ColorGeom{}, u, v, bitmap, cnt);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        n_samples += __shfl_xor(n_samples, off, 64); n_new += __shfl_xor(n_new, off, 64);
-        entered += __shfl_xor(entered, off, 64); hit += __shfl_xor(hit, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        if (n_samples) atomicAdd(&counters[0], (unsigned long long)n_samples);
-        if (entered) atomicAdd(&counters[1], (unsigned long long)entered);
-        if (hit) atomicAdd(&counters[2], (unsigned long long)hit);
-        if (n_new) atomicAdd(&counters[3], (unsigned long long)n_new);
-    }
+    publish_counts(cnt, entered, counters);
 }
 
 // the same for the march through the class tables: counters = {samples, rays that enter the box, hits, U, table look-ups, table bytes}
@@ -578,29 +543,10 @@ __global__ __launch_bounds__(256) void k_raycast_sdf_classes_count(const RayPara
     ray_pixel_of(p, blockIdx.x, blockIdx.y, threadIdx.x, u, v);
     unsigned cnt[4] = {0u, 0u, 0u, 0u}, entered = 0;
     if (u < p.w && v < p.h) {
-        const V3 c_w = v3(p.T.m[3], p.T.m[7], p.T.m[11]);
-        const V3 ray_c = v3(((float)u - p.K.u0) / p.K.fu, ((float)v - p.K.v0) / p.K.fv, 1.0f);
-        const V3 ray_w = so3_mul(p.T, ray_c);
-        const V3 ta = div_cw(p.vol.bmin - c_w, ray_w);
-        const V3 tb = div_cw(p.vol.bmax - c_w, ray_w);
-        const V3 tmin = v3(fminf(ta.x, tb.x), fminf(ta.y, tb.y), fminf(ta.z, tb.z));
-        const V3 tmax = v3(fmaxf(ta.x, tb.x), fmaxf(ta.y, tb.y), fmaxf(ta.z, tb.z));
-        entered = fmaxf(fmaxf(fmaxf(tmin.x, tmin.y), tmin.z), p.near) < fminf(fminf(fminf(tmax.x, tmax.y), tmax.z), p.far) ? 1u : 0u;
+        entered = enters(ray_box(p, u, v)) ? 1u : 0u;
         raycast_pixel_classes<CELL, false, true, GT>(p, s_p, ColorGeom{}, u, v, cl, s_tab, s_top, bitmap, cnt);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        cnt[0] += __shfl_xor(cnt[0], off, 64); cnt[1] += __shfl_xor(cnt[1], off, 64);
-        cnt[2] += __shfl_xor(cnt[2], off, 64); cnt[3] += __shfl_xor(cnt[3], off, 64);
-        entered += __shfl_xor(entered, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        if (cnt[0]) atomicAdd(&counters[0], (unsigned long long)cnt[0]);
-        if (entered) atomicAdd(&counters[1], (unsigned long long)entered);
-        if (cnt[2]) atomicAdd(&counters[2], (unsigned long long)cnt[2]);
-        if (cnt[3]) atomicAdd(&counters[3], (unsigned long long)cnt[3]);
-        if (cnt[1]) atomicAdd(&counters[4], (unsigned long long)cnt[1]);
-    }
+    publish_counts(cnt, entered, counters);
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(&counters[5], (unsigned long long)cl.lds_words * 4ull);
 }
 
@@ -628,34 +574,41 @@ struct RayLevels {
     int n;
 };
 
-template <typename CELL>
-__global__ __launch_bounds__(256) void k_raycast_sdf_levels(const RayParams base, const RayLevels L)
+// the level of workgroup `block` of the launch (uniform)
+__device__ __forceinline__ const RayLevel& level_of(const RayLevels& L, const int block)
 {
     int l = 0;
     for (int k = 1; k < L.n; ++k)
-        if ((int)blockIdx.x >= L.lv[k].first_block) l = k; // uniform
-    const RayLevel& lv = L.lv[l];
+        if (block >= L.lv[k].first_block) l = k;
+    return L.lv[l];
+}
+// the launch's parameters with a level's images and intrinsics
+__device__ __forceinline__ RayParams level_params(const RayParams& base, const RayLevel& lv)
+{
     RayParams p = base;
     p.dptr = lv.dptr; p.nptr = lv.nptr; p.iptr = lv.iptr;
     p.dpitch = lv.dpitch; p.npitch = lv.npitch; p.ipitch = lv.ipitch;
     p.w = lv.w; p.h = lv.h;
     p.K = lv.K;
-    const int b = (int)blockIdx.x - lv.first_block;
-    int u, v;
-    if (lv.sparse) {
-        // coarse levels: neighbouring rays are many voxels apart, so every lane of a load fetches its own line and a
-        // wave-step waits for the slowest of 64 misses; with `sparse` rays per wave it waits for the slowest of those
-        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-        if (lane >= lv.sparse) return;
-        u = ((b % lv.blocks_x) * 2 + (wv & 1)) * lv.sparse + lane;
-        v = (b / lv.blocks_x) * 2 + (wv >> 1);
-    } else {
-        ray_pixel_of(p, b % lv.blocks_x, b / lv.blocks_x, threadIdx.x, u, v);
-    }
-    const float kz = raycast_pixel<CELL, false>(p, ColorGeom{}, u, v);
-    if (lv.vptr && u < p.w && v < p.h) // the application's DepthToVbo(ray_v[l], ray_d[l], K[l]) (main.cpp:286), same expression
+    return p;
+}
+// the application's DepthToVbo(ray_v[l], ray_d[l], K[l]) (main.cpp:286), same expression, for a pixel whose depth image holds kz
+__device__ __forceinline__ void write_vertex(const RayLevel& lv, const RayParams& p, const int u, const int v, const float kz)
+{
+    if (lv.vptr && u < p.w && v < p.h)
         reinterpret_cast<float4*>(lv.vptr + (size_t)v * lv.vpitch)[u] =
             make_float4(kz * ((float)u - p.K.u0) / p.K.fu, kz * ((float)v - p.K.v0) / p.K.fv, kz, 1.0f);
+}
+
+template <typename CELL>
+__global__ __launch_bounds__(256) void k_raycast_sdf_levels(const RayParams base, const RayLevels L)
+{
+    const RayLevel& lv = level_of(L, (int)blockIdx.x);
+    const RayParams p = level_params(base, lv);
+    const int b = (int)blockIdx.x - lv.first_block;
+    int u, v;
+    if (!ray_lane_pixel(p, lv.sparse, b % lv.blocks_x, b / lv.blocks_x, u, v)) return;
+    write_vertex(lv, p, u, v, raycast_pixel<CELL, false>(p, ColorGeom{}, u, v));
 }
 
 template <typename CELL>
@@ -663,43 +616,26 @@ __global__ __launch_bounds__(256) void k_raycast_sdf_levels_classes(const RayPar
 {
     extern __shared__ unsigned s_tab[];
     __shared__ RayParams s_p;
-    int l = 0;
-    for (int k = 1; k < L.n; ++k)
-        if ((int)blockIdx.x >= L.lv[k].first_block) l = k; // uniform
-    const RayLevel& lv = L.lv[l];
-    RayParams p = base;
-    p.dptr = lv.dptr; p.nptr = lv.nptr; p.iptr = lv.iptr;
-    p.dpitch = lv.dpitch; p.npitch = lv.npitch; p.ipitch = lv.ipitch;
-    p.w = lv.w; p.h = lv.h;
-    p.K = lv.K;
     __shared__ TopLevels s_top;
     __shared__ int s_any[4];   // (workgroup_any: one word per wave of the 256-thread workgroup)
+    const RayLevel& lv = level_of(L, (int)blockIdx.x);
+    const RayParams p = level_params(base, lv);
     if (threadIdx.x == 0) s_p = p;
     const int b = (int)blockIdx.x - lv.first_block;
     int u, v;
-    bool carries = true;
-    if (lv.sparse) {
-        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-        carries = lane < lv.sparse;
-        u = ((b % lv.blocks_x) * 2 + (wv & 1)) * lv.sparse + lane;
-        v = (b / lv.blocks_x) * 2 + (wv >> 1);
-    } else {
-        ray_pixel_of(p, b % lv.blocks_x, b / lv.blocks_x, threadIdx.x, u, v);
-    }
+    const bool carries = ray_lane_pixel(p, lv.sparse, b % lv.blocks_x, b / lv.blocks_x, u, v);
     // as k_raycast_sdf_classes: a workgroup without a ray in the box leaves before the prologue (every thread reaches the barrier)
     const bool pixel = carries && u < p.w && v < p.h;
     float kz = __builtin_nanf("");   // what raycast_pixel_classes returns for a ray that hits nothing
     if (!workgroup_any(pixel && enters(ray_box(p, u, v)), s_any)) {
         if (!pixel) return;
-        write_no_hit(p, u, v);
+        write_no_hit(ray_out(p, u, v));
     } else {
         classes_stage(cl, s_tab, s_top);   // before any lane leaves (barrier inside)
         if (!carries) return;
         kz = raycast_pixel_classes<CELL, false>(p, s_p, ColorGeom{}, u, v, cl, s_tab, s_top);
     }
-    if (lv.vptr && u < p.w && v < p.h)
-        reinterpret_cast<float4*>(lv.vptr + (size_t)v * lv.vpitch)[u] =
-            make_float4(kz * ((float)u - p.K.u0) / p.K.fu, kz * ((float)v - p.K.v0) / p.K.fv, kz, 1.0f);
+    write_vertex(lv, p, u, v, kz);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -778,15 +714,9 @@ __global__ __launch_bounds__(256) void k_raycast_sdf_slab(const RayParams p, con
     float* st = sl.state + (size_t)tile * NP * plane + q;   // plane k at st[k * plane]
     float* rs = sl.result + (size_t)tile * 4 * plane + q;  // normal x / y / z, shade
 
-    const V3 c_w = v3(p.T.m[3], p.T.m[7], p.T.m[11]);
-    const V3 ray_c = v3(((float)u - p.K.u0) / p.K.fu, ((float)v - p.K.v0) / p.K.fv, 1.0f);
-    const V3 ray_w = so3_mul(p.T, ray_c);
-    const V3 ta = div_cw(p.vol.bmin - c_w, ray_w);
-    const V3 tb = div_cw(p.vol.bmax - c_w, ray_w);
-    const V3 tmin = v3(fminf(ta.x, tb.x), fminf(ta.y, tb.y), fminf(ta.z, tb.z));
-    const V3 tmax = v3(fmaxf(ta.x, tb.x), fmaxf(ta.y, tb.y), fmaxf(ta.z, tb.z));
-    const float max_tmin = fmaxf(fmaxf(fmaxf(tmin.x, tmin.y), tmin.z), p.near);
-    const float min_tmax = fminf(fminf(fminf(tmax.x, tmax.y), tmax.z), p.far);
+    const RayBox box = ray_box(p, u, v);
+    const V3 c_w = box.c_w, ray_c = box.ray_c, ray_w = box.ray_w;
+    const float max_tmin = box.max_tmin, min_tmax = box.min_tmax;
 
     float lambda, last_sdf, delta, status;
     if (sl.init) {
@@ -845,10 +775,7 @@ __global__ __launch_bounds__(256) void k_raycast_sdf_slab(const RayParams p, con
         const V3 pos = c_w + ray_w * lambda;
         const int gz = grad_cell_z(p, pos);
         if ((sl.normals_here || (gz >= sl.own_lo && gz < sl.own_hi)) && gz - 1 >= sl.avail_lo && gz + 1 < sl.avail_hi) {
-            const V3 g = gradient<CELL>(p, pos);
-            const float len = length(g);
-            const V3 n_w = len > 0 ? div_s(g, len) : v3(0.f, 0.f, 1.f);
-            const V3 n_c = so3_mul_inv(p.T, n_w);
+            const V3 n_c = normal_c<CELL>(p, pos);
             rs[0] = n_c.x; rs[plane] = n_c.y; rs[2 * plane] = n_c.z;
             rs[3 * plane] = phong(ray_c * lambda, n_c);
             status = 1.f;
@@ -871,10 +798,14 @@ __global__ __launch_bounds__(256) void k_raycast_state_to_images(const RayParams
     const float* st = state + (size_t)v * p.w + u;
     const float depth = st[0];
     const bool hit = st[3 * plane] == 1.f && depth > 0.f;
-    *(reinterpret_cast<float*>(p.dptr + (size_t)v * p.dpitch) + u) = hit ? depth : __builtin_nanf("");
-    *(reinterpret_cast<float*>(p.iptr + (size_t)v * p.ipitch) + u) = hit ? st[8 * plane] : 0.f;
-    *(reinterpret_cast<float4*>(p.nptr + (size_t)v * p.npitch) + u) =
-        hit ? make_float4(st[5 * plane], st[6 * plane], st[7 * plane], 1.0f) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const RayOut o = ray_out(p, u, v);
+    if (hit) {
+        *o.depth = depth;
+        *o.shade = st[8 * plane];
+        *o.normal = make_float4(st[5 * plane], st[6 * plane], st[7 * plane], 1.0f);
+    } else {
+        write_no_hit(o);
+    }
 }
 
 } // namespace kfx
@@ -1034,6 +965,17 @@ static int class_view(ClassView& cl, size_t* lds_bytes, int* usable, kfx_sdf_sum
     return 0;
 }
 
+// The march a class_view() result selects, launched on `grid`: through the tables (`global`: the global-table kernel, `lds`: the
+// one with all levels in LDS; a... are their arguments after (p, cl)), or, where the tables are not usable, plain().
+template <typename PLAIN, typename... A>
+static int launch_march(const char* what, int usable, const ClassView& cl, size_t cl_bytes, dim3 grid, kfx_stream stream, const RayParams& p,
+                        void (*global)(RayParams, ClassView, A...), void (*lds)(RayParams, ClassView, A...), PLAIN plain, A... a)
+{
+    if (usable) hipLaunchKernelGGL(cl.global ? global : lds, grid, dim3(256), cl_bytes, (hipStream_t)stream, p, cl, a...);
+    else plain();
+    return check_launch(what);
+}
+
 template <typename CELL>
 static int raycast_levels_launch(int n_levels, const kfx_image* const* depth, const kfx_image* const* norm, const kfx_image* const* img,
                                  const kfx_image* const* vbo, const kfx_volume* vol, const float T_wc[12], const float* K, float near, float far,
@@ -1121,10 +1063,8 @@ static int raycast_launch(const kfx_image* depth, const kfx_image* norm, const k
         size_t cl_bytes = 0;
         int usable = 0;
         if (int e = class_view<CELL>(cl, &cl_bytes, &usable, summary, vol, p, stream)) return e;
-        if (usable && cl.global) hipLaunchKernelGGL((k_raycast_sdf_classes<CELL, true>), grid, dim3(256), cl_bytes, (hipStream_t)stream, p, cl);
-        else if (usable) hipLaunchKernelGGL((k_raycast_sdf_classes<CELL>), grid, dim3(256), cl_bytes, (hipStream_t)stream, p, cl);
-        else hipLaunchKernelGGL((k_raycast_sdf<CELL, false>), grid, dim3(256), 0, (hipStream_t)stream, p, cv);
-        return check_launch("kfx_raycast_sdf_tracked");
+        return launch_march("kfx_raycast_sdf_tracked", usable, cl, cl_bytes, grid, stream, p, k_raycast_sdf_classes<CELL, true>, k_raycast_sdf_classes<CELL, false>,
+                            [&] { hipLaunchKernelGGL((k_raycast_sdf<CELL, false>), grid, dim3(256), 0, (hipStream_t)stream, p, cv); });
     } else {
         hipLaunchKernelGGL((k_raycast_sdf<CELL, false>), grid, dim3(256), 0, (hipStream_t)stream, p, cv);
     }
@@ -1138,18 +1078,28 @@ extern "C" int kfx_raycast_sdf(const kfx_image* depth, const kfx_image* norm, co
     return raycast_launch<RayF32>(depth, norm, img, vol, T_wc, K, near, far, trunc_dist, subpix, stream);
 }
 
+// Parameters and grid of a count launch.  The image arguments of ray_params() only give the launch its size: nothing is written to them.
+template <typename CELL>
+static int count_params(RayParams& p, dim3& grid, const kfx_volume* vol, unsigned w, unsigned h, const float T_wc[12], const float K[4], float near, float far,
+                        float trunc_dist, int subpix)
+{
+    kfx_image dummy = {(size_t)w * 16, (void*)(uintptr_t)16, w, h};
+    if (int e = ray_params<CELL>(p, &dummy, &dummy, &dummy, vol, T_wc, K, near, far, trunc_dist, subpix)) return e;
+    p.dptr = p.nptr = p.iptr = nullptr;
+    grid = dim3(ceil_div(p.w, 64), ceil_div(p.h, 4));
+    return 0;
+}
+
 template <typename CELL>
 static int raycast_count_launch(const kfx_volume* vol, unsigned w, unsigned h, const float T_wc[12], const float K[4], float near, float far,
                                 float trunc_dist, int subpix, unsigned* d_bitmap, unsigned long long* d_counters, kfx_stream stream)
 {
     if (!d_bitmap || !d_counters) return set_error(KFX_E_NULL, "kfx_raycast_sdf_count: null argument");
-    // the image arguments of ray_params() only give the launch its size: nothing is written to them
-    kfx_image dummy = {(size_t)w * 16, (void*)(uintptr_t)16, w, h};
     RayParams p;
-    if (int e = ray_params<CELL>(p, &dummy, &dummy, &dummy, vol, T_wc, K, near, far, trunc_dist, subpix)) return e;
+    dim3 grid;
+    if (int e = count_params<CELL>(p, grid, vol, w, h, T_wc, K, near, far, trunc_dist, subpix)) return e;
     if (p.w == 0 || p.h == 0) return 0;
-    p.dptr = p.nptr = p.iptr = nullptr;
-    hipLaunchKernelGGL(k_raycast_sdf_count<CELL>, dim3(ceil_div(p.w, 64), ceil_div(p.h, 4)), dim3(256), 0, (hipStream_t)stream, p, d_bitmap, d_counters);
+    hipLaunchKernelGGL(k_raycast_sdf_count<CELL>, grid, dim3(256), 0, (hipStream_t)stream, p, d_bitmap, d_counters);
     return check_launch("kfx_raycast_sdf_count");
 }
 
@@ -1171,13 +1121,12 @@ static int raycast_count_tracked_launch(const kfx_volume* vol, kfx_sdf_summary* 
                                         kfx_stream stream)
 {
     if (!d_bitmap || !d_counters || !summary) return set_error(KFX_E_NULL, "kfx_raycast_sdf_count_tracked: null argument");
-    kfx_image dummy = {(size_t)w * 16, (void*)(uintptr_t)16, w, h};
     RayParams p;
-    if (int e = ray_params<CELL>(p, &dummy, &dummy, &dummy, vol, T_wc, K, near, far, trunc_dist, subpix)) return e;
+    dim3 grid;
+    if (int e = count_params<CELL>(p, grid, vol, w, h, T_wc, K, near, far, trunc_dist, subpix)) return e;
     if (summary->cell_bytes != CELL::BYTES)
         return set_error(KFX_E_SHAPE, "kfx_raycast_sdf_count_tracked: the summary was created for the other cell type (kfx_sdf_summary_create / _create_h)");
     if (p.w == 0 || p.h == 0) return 0;
-    p.dptr = p.nptr = p.iptr = nullptr;
     ClassView cl;
     size_t cl_bytes = 0;
     int usable = 0;
@@ -1187,11 +1136,9 @@ static int raycast_count_tracked_launch(const kfx_volume* vol, kfx_sdf_summary* 
     const int ce = class_view<CELL>(cl, &cl_bytes, &usable, summary, vol, p, stream);
     summary->plain_calls = plain_calls;
     if (ce) return ce;
-    const dim3 grid(ceil_div(p.w, 64), ceil_div(p.h, 4));
-    if (usable && cl.global) hipLaunchKernelGGL((k_raycast_sdf_classes_count<CELL, true>), grid, dim3(256), cl_bytes, (hipStream_t)stream, p, cl, d_bitmap, d_counters);
-    else if (usable) hipLaunchKernelGGL((k_raycast_sdf_classes_count<CELL>), grid, dim3(256), cl_bytes, (hipStream_t)stream, p, cl, d_bitmap, d_counters);
-    else hipLaunchKernelGGL(k_raycast_sdf_count<CELL>, grid, dim3(256), 0, (hipStream_t)stream, p, d_bitmap, d_counters);   // what the tracked call would launch
-    return check_launch("kfx_raycast_sdf_count_tracked");
+    return launch_march("kfx_raycast_sdf_count_tracked", usable, cl, cl_bytes, grid, stream, p, k_raycast_sdf_classes_count<CELL, true>,
+                        k_raycast_sdf_classes_count<CELL, false>,   // (plain: what the tracked call would launch)
+                        [&] { hipLaunchKernelGGL(k_raycast_sdf_count<CELL>, grid, dim3(256), 0, (hipStream_t)stream, p, d_bitmap, d_counters); }, d_bitmap, d_counters);
 }
 
 extern "C" int kfx_raycast_sdf_count_tracked(const kfx_volume* vol, kfx_sdf_summary* summary, unsigned w, unsigned h, const float T_wc[12], const float K[4],

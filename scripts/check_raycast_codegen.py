@@ -17,15 +17,12 @@ import subprocess
 import sys
 import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "kangaroo_amd", "csrc")
-FLAGS = ["-std=c++17", "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math",
-         "-fhip-fp32-correctly-rounded-divide-sqrt", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]   # raycast.o in csrc/Makefile
+from check_raycast_spills import CSRC, ROOT, makefile_flags   # raycast.o's flags, read from csrc/Makefile
 
 
 def compile_to_asm(out):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    subprocess.run([hipcc] + FLAGS + ["-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-S", "--cuda-device-only", "-o", out,
+    subprocess.run([hipcc] + makefile_flags() + ["-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-S", "--cuda-device-only", "-o", out,
                                       os.path.join(CSRC, "raycast.hip")], check=True, stderr=subprocess.DEVNULL)
 
 
