@@ -99,6 +99,53 @@ __device__ __forceinline__ float voxel_pos(float bmin, float size, int i, float 
     return bmin + (pos_div ? div_uniform(a, n1, inv_n1) : a / n1);
 }
 
+// VoxelPositionInUnits z of local plane z (BoundedVolume.h:115-125)
+__device__ __forceinline__ float slice_z(const FuseParams& p, int z) { return p.bmin.z + p.size.z * (float)(z + p.zoff) / p.d1; }
+
+// Workgroups go to the 8 XCDs round-robin by linear id, and the grid is 8 bricks wide at 512 voxels: blockIdx.x alone
+// would pin an x-slab of the volume to an XCD, and a scene that leaves the outer slabs half empty (the walls of
+// S_room) leaves two XCDs idle while six finish.  Rotating the x-brick by the z-brick gives every XCD every x-slab;
+// an XCD still works on one x-slab at a time (all y-bricks of a layer), so the image columns its bricks stage stay
+// in its L2 (rotating by the y-brick as well made S_full 12 % slower: every XCD then cycles through the whole image).
+// Measured, interleaved on one box (scripts/ab_xcd_swizzle.sh): S_room fast 0.438 -> 0.410 ms, S_full unchanged.
+__device__ __forceinline__ int xcd_rotated_brick(const FuseParams& p, int bzi)
+{
+    return p.xcd_swizzle ? (int)((blockIdx.x + (bzi >> (p.xcd_swizzle - 1))) % gridDim.x) : (int)blockIdx.x;
+}
+
+// The pixel rectangle a brick stages: the bilinear cells (ix, ix+1) x (iy, iy+1) of every sample between the projected bounds,
+// one texel of slack per side, cut to the image.
+struct TileRect {
+    int x0, y0, w, h;
+    __device__ __forceinline__ bool fits(int cap) const { return w > 1 && h > 1 && w * h <= cap; }
+};
+__device__ __forceinline__ TileRect tile_rect(float lo_u, float hi_u, float lo_v, float hi_v, int img_w, int img_h)
+{
+    const float fx0 = fmaxf(floorf(lo_u) - 1.f, 0.f), fx1 = fminf(floorf(hi_u) + 2.f, (float)(img_w - 1));
+    const float fy0 = fmaxf(floorf(lo_v) - 1.f, 0.f), fy1 = fminf(floorf(hi_v) + 2.f, (float)(img_h - 1));
+    TileRect r;
+    r.x0 = (int)fx0; r.y0 = (int)fy0;
+    r.w = (int)fx1 - r.x0 + 1; r.h = (int)fy1 - r.y0 + 1;
+    return r;
+}
+// every sample needs 2 <= u < wb and 2 <= v < hb (InBounds with border 2): projected bounds that miss that band mean no voxel
+// of the brick can pass it
+__device__ __forceinline__ bool misses_band(float lo_u, float hi_u, float lo_v, float hi_v, float wb, float hb)
+{
+    return hi_u < 2.0f || !(lo_u < wb) || hi_v < 2.0f || !(lo_v < hb);
+}
+
+// Occlusion culling of a whole brick.  An update needs costheta > mincos and
+// costheta * (md - Z) > -trunc, hence md - Z > -trunc / mincos; md is a convex combination of
+// texels of the staged rectangle, so md <= dmax, and Z >= zmin.  If even dmax - zmin lies below
+// that bound (with a relative margin far above the rounding of the per-voxel expression), no voxel
+// of the brick can change.  (Also when every texel is NaN: dmax = -inf.)
+__device__ __forceinline__ float far_depth(float dmax) { return dmax + fabsf(dmax) * 1e-5f; }
+__device__ __forceinline__ bool brick_occluded(float dmax, float zmin, const FuseParams& p)
+{
+    return far_depth(dmax) - zmin < -(p.trunc / p.mincos) * 1.001f;
+}
+
 struct Obs {
     float val, w;
     bool ok;
@@ -106,6 +153,19 @@ struct Obs {
 
 // {nx, ny, nz, depth} at the four corners of a bilinear cell: (ix,iy) (ix+1,iy) (ix,iy+1) (ix+1,iy+1)
 struct Corners { float4 c00, c01, c10, c11; };
+// ... read from a staged tile with rows of tw texels, `t` at (ix, iy)
+__device__ __forceinline__ Corners tile_corners(const float4* t, int tw)
+{
+    Corners c;
+    c.c00 = t[0]; c.c01 = t[1]; c.c10 = t[tw]; c.c11 = t[tw + 1];
+    return c;
+}
+// ... and from the {texel, x-difference} tile of the DXT kernels: the two left corners and their differences d0 = c01 - c00, d1 = c11 - c10
+struct CornersDx { float4 c00, d0, c10, d1; };
+__device__ __forceinline__ CornersDx tile_corners_dx(const float4* t, int tw)
+{
+    return CornersDx{t[0], t[1], t[2 * tw], t[2 * tw + 1]};
+}
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 
@@ -268,15 +328,14 @@ __device__ __forceinline__ Obs finish_shared(const FuseParams& p, const V3 Pc, f
 // are the same single roundings whoever computes them, and every voxel that samples the cell uses them, so they are formed
 // once per texel while staging; lerp(a, b, fx) = a + fx * (b - a) becomes a + fx * d: two operations instead of three,
 // eight fewer per voxel, same bits.
-__device__ __forceinline__ Obs finish_shared_dx(const FuseParams& p, const V3 Pc, float yz, float fx, float fy, const float4 c00, const float4 d0,
-                                                const float4 c10, const float4 d1)
+__device__ __forceinline__ Obs finish_shared(const FuseParams& p, const V3 Pc, float yz, float fx, float fy, const CornersDx& c)
 {
     Obs o;
-    const float md = lerp(c00.w + fx * d0.w, c10.w + fx * d1.w, fy);
+    const float md = lerp(c.c00.w + fx * c.d0.w, c.c10.w + fx * c.d1.w, fy);
     V3 mdn;
-    mdn.x = lerp(c00.x + fx * d0.x, c10.x + fx * d1.x, fy);
-    mdn.y = lerp(c00.y + fx * d0.y, c10.y + fx * d1.y, fy);
-    mdn.z = lerp(c00.z + fx * d0.z, c10.z + fx * d1.z, fy);
+    mdn.x = lerp(c.c00.x + fx * c.d0.x, c.c10.x + fx * c.d1.x, fy);
+    mdn.y = lerp(c.c00.y + fx * c.d0.y, c.c10.y + fx * c.d1.y, fy);
+    mdn.z = lerp(c.c00.z + fx * c.d0.z, c.c10.z + fx * c.d1.z, fy);
     const float nlen = -sqrt_core(dot(Pc, Pc));
     const float costheta = div_core(dot(mdn, Pc), nlen, rcp_nr(nlen));
     const float w = div_core(costheta, Pc.z, yz); // costheta * 1.0f / Pc.z
@@ -292,6 +351,19 @@ __device__ __forceinline__ int med3_i32(int x, int lo, int hi) // clamp for lo <
     int r;
     asm("v_med3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(lo), "v"(hi));
     return r;
+}
+
+// The bilinear cell (rx, ry) of a sample, relative to a staged rectangle whose last cell of a row / column is cxmax / cymax
+// (tw - 2 / th - 2): whether it lies inside, and its index in texels clamped into the rectangle (always a valid LDS address;
+// one v_med3_i32 per axis).
+__device__ __forceinline__ bool cell_inside(int rx, int ry, int cxmax, int cymax) { return (unsigned)rx <= (unsigned)cxmax && (unsigned)ry <= (unsigned)cymax; }
+__device__ __forceinline__ int cell_clamped(int rx, int ry, int cxmax, int cymax, int tw) { return med3_i32(ry, 0, cymax) * tw + med3_i32(rx, 0, cxmax); }
+// ... and what a checked sample may do: `inb` = the lane takes part and the sample passed InBounds.  In bounds but outside the
+// rectangle is a stray (returned): the wave then goes through the global-gather path for that iteration.
+__device__ __forceinline__ bool gate_sample(Obs& o, bool inb, bool inside)
+{
+    o.ok = ((int)o.ok & (int)inb & (int)inside) != 0;
+    return ((int)inb & (int)!inside) != 0;
 }
 
 // ---- cell storage policies ----------------------------------------------------------------
@@ -375,6 +447,14 @@ __device__ __forceinline__ void accumulate(const Obs& o, float max_w, float& ova
     ow = CELL::q(fminf(w, max_w));
 }
 
+// the two cells of a lane, (val0, w0, val1, w1), each updated where its sample passed
+template <bool FAST, typename CELL>
+__device__ __forceinline__ void accumulate_pair(const Obs& o0, const Obs& o1, float max_w, float4& c)
+{
+    if (o0.ok) accumulate<FAST, CELL>(o0, max_w, c.x, c.y);
+    if (o1.ok) accumulate<FAST, CELL>(o1, max_w, c.z, c.w);
+}
+
 // the four corners from the packed texel image (k_pack_texels: copies of the same normals and depths), one 16-byte load each
 __device__ __forceinline__ Corners fetch_texels(const FuseParams& p, int ix, int iy)
 {
@@ -418,7 +498,7 @@ __global__ __launch_bounds__(256) void k_sdf_fuse(const FuseParams p)
     const int zbeg = blockIdx.z * FUSE_ZC;
     const int zend = min(zbeg + FUSE_ZC, p.Z);
     if (threadIdx.x < FUSE_ZC) // VoxelPositionInUnits z, once per slice
-        s_pz[threadIdx.x] = p.bmin.z + p.size.z * (float)(zbeg + (int)threadIdx.x + p.zoff) / p.d1;
+        s_pz[threadIdx.x] = slice_z(p, zbeg + (int)threadIdx.x);
     __syncthreads();
     if (x0 >= p.X || y >= p.Y) return;
 
@@ -436,8 +516,7 @@ __global__ __launch_bounds__(256) void k_sdf_fuse(const FuseParams p)
         if constexpr (VEC == 2) {
             if (o[0].ok || o[1].ok) {
                 float4 c = CELL::ld2(cell);
-                if (o[0].ok) accumulate<FAST, CELL>(o[0], p.max_w, c.x, c.y);
-                if (o[1].ok) accumulate<FAST, CELL>(o[1], p.max_w, c.z, c.w);
+                accumulate_pair<FAST, CELL>(o[0], o[1], p.max_w, c);
                 CELL::st2(cell, c);
             }
         } else {
@@ -478,7 +557,7 @@ __global__ __launch_bounds__(256) void k_sdf_fuse(const FuseParams p)
 // wave less costs 6 % (measured when an edit took the untracked kernel from 78 to 81; the tracked one took 86 unbounded and
 // fits 77 without scratch).  scripts/check_fuse_codegen.py checks both.
 // DXT (bit-exact kernels): a texel is staged as {texel, difference to its right neighbour} -- 32 bytes, so `cap_px` texels take
-// twice the LDS; chosen by the host for ranges whose rectangles fit half the tile (finish_shared_dx).
+// twice the LDS; chosen by the host for ranges whose rectangles fit half the tile (finish_shared on CornersDx).
 // NW: waves per workgroup (4; 8 for the narrow brick at large tiles -- twice the waves behind one staged rectangle where LDS,
 // not registers, limits how many workgroups a CU holds: k_sdf_fuse_tiled<true, 2, CELL, 16, 2, 16, false, false, 8>).
 template <bool FAST, int ZU, typename CELL, int LX = 32, int WY = 4, int ZC = FUSE_ZC, bool TRACK = false, bool DXT = false, int NW = 4>
@@ -509,14 +588,8 @@ __global__ __launch_bounds__(64 * NW, (FAST && ZU == 2) ? 8 : (!FAST ? 6 : 1)) v
     // (the wave index through readfirstlane: the compiler cannot tell that tid >> 6 is wave-uniform, and without it the slice
     // loop's bounds, the loop branch and everything derived from them are computed per lane)
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // Workgroups go to the 8 XCDs round-robin by linear id, and the grid is 8 bricks wide at 512 voxels: blockIdx.x alone
-    // would pin an x-slab of the volume to an XCD, and a scene that leaves the outer slabs half empty (the walls of
-    // S_room) leaves two XCDs idle while six finish.  Rotating the x-brick by the z-brick gives every XCD every x-slab;
-    // an XCD still works on one x-slab at a time (all y-bricks of a layer), so the image columns its bricks stage stay
-    // in its L2 (rotating by the y-brick as well made S_full 12 % slower: every XCD then cycles through the whole image).
-    // Measured, interleaved on one box (scripts/ab_xcd_swizzle.sh): S_room fast 0.438 -> 0.410 ms, S_full unchanged.
     const int bzi = (TRACK && p.z_rev) ? (int)(gridDim.z - 1 - blockIdx.z) : (int)blockIdx.z;
-    const int bxi = p.xcd_swizzle ? (int)((blockIdx.x + (bzi >> (p.xcd_swizzle - 1))) % gridDim.x) : (int)blockIdx.x;
+    const int bxi = xcd_rotated_brick(p, bzi);
     const int x0 = (bxi * LX + (lane & (LX - 1))) * 2;
     const int y = blockIdx.y * BY + (wv % WY) * RW + lane / LX;
     const int zbeg = bzi * ZC;
@@ -525,7 +598,7 @@ __global__ __launch_bounds__(64 * NW, (FAST && ZU == 2) ? 8 : (!FAST ? 6 : 1)) v
     const int wz0 = zbeg + (wv / WY) * ZW, wz1 = min(wz0 + ZW, zend); // this wave's slices
     const bool live = x0 < p.X && y < p.Y;
     if (tid < ZC) {
-        const float pz = p.bmin.z + p.size.z * (float)(zbeg + tid + p.zoff) / p.d1;
+        const float pz = slice_z(p, zbeg + tid);
         s_pz[tid] = pz;
         if constexpr (!FAST) s_tz[tid] = make_float4(pz, p.T.m[2] * pz, p.T.m[6] * pz, p.T.m[10] * pz);
     }
@@ -558,8 +631,8 @@ __global__ __launch_bounds__(64 * NW, (FAST && ZU == 2) ? 8 : (!FAST ? 6 : 1)) v
         float pu, pv, iz;
         project<FAST>(p, Pc, pu, pv, iz);
         const bool bad = !(Pc.z > 0.f) || !(fabsf(pu) < 1e9f) || !(fabsf(pv) < 1e9f);
-        const auto fmin2 = [](float a, float b) { return fminf(a, b); };
-        const auto fmax2 = [](float a, float b) { return fmaxf(a, b); };
+        const FMin fmin2;
+        const FMax fmax2;
         // (every lane holds the same values now; readfirstlane tells the compiler so -- what is derived from them below, the tile's
         //  origin and width in the voxel loop's addresses included, belongs in scalar registers)
         const auto uni = [](float x) { return __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(x))); };
@@ -571,21 +644,16 @@ __global__ __launch_bounds__(64 * NW, (FAST && ZU == 2) ? 8 : (!FAST ? 6 : 1)) v
     }
 
     bool use_tile = false;
-    int tx0 = 0, ty0 = 0, tw = 0, th = 0;
+    TileRect tile = {0, 0, 0, 0};
     if (!any_bad) {
-        // every sample needs 2 <= pu < w-2 and 2 <= pv < h-2: a rectangle that misses that band
-        // means no voxel of the brick can pass InBounds (workgroup-uniform exit)
-        if (umax < 2.0f || !(umin < p.dwb) || vmax < 2.0f || !(vmin < p.dhb)) return;
-        // bilinear cells (ix, ix+1) x (iy, iy+1) of every sample, one texel of slack per side
-        const float fx0 = fmaxf(floorf(umin) - 1.f, 0.f), fx1 = fminf(floorf(umax) + 2.f, (float)(p.depth.w - 1));
-        const float fy0 = fmaxf(floorf(vmin) - 1.f, 0.f), fy1 = fminf(floorf(vmax) + 2.f, (float)(p.depth.h - 1));
-        tx0 = (int)fx0; ty0 = (int)fy0;
-        tw = (int)fx1 - tx0 + 1; th = (int)fy1 - ty0 + 1;
-        use_tile = tw > 1 && th > 1 && tw * th <= cap_px;
+        if (misses_band(umin, umax, vmin, vmax, p.dwb, p.dhb)) return;   // (workgroup-uniform exit)
+        tile = tile_rect(umin, umax, vmin, vmax, p.depth.w, p.depth.h);
+        use_tile = tile.fits(cap_px);
         // DXT: only the shared-reciprocal loop reads the {texel, difference} layout; a brick that fails its operand-range test
         // (or KFX_FUSE_EXACT_SHARED=0) gathers from global memory
         if constexpr (DXT) use_tile = use_tile && p.exact_shared && zmin >= 0x1p-20f && cmax <= 0x1p20f;
     }
+    const int tx0 = tile.x0, ty0 = tile.y0, tw = tile.w, th = tile.h;
     // Interior bricks: the rectangle of projections lies inside the band 2 <= pu < w - 2, 2 <= pv < h - 2 by a margin far
     // above the rounding of a projection (a voxel of an inner slice projects between the projections of its column's two
     // ends), so every sample passes InBounds and falls inside the staged rectangle with its one-texel slack: the voxel loop
@@ -646,9 +714,7 @@ __global__ __launch_bounds__(64 * NW, (FAST && ZU == 2) ? 8 : (!FAST ? 6 : 1)) v
                     const int br = (int)(((float)i + 0.5f) * inv_nbx);   // i / nbx (i < 4096)
                     dmax = fmaxf(dmax, p.bmax[(size_t)(by0 + br) * p.bw8 + (size_t)(bx0 + i - br * nbx)]);
                 }
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) dmax = fmaxf(dmax, __shfl_xor(dmax, off, 64));
-                if (lane == 0) s_dmax[wv] = dmax;
+                block_put(s_dmax, wv, dmax, FMax{});
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMAs have landed; the barrier below covers the other waves'
         }
@@ -701,27 +767,14 @@ __global__ __launch_bounds__(64 * NW, (FAST && ZU == 2) ? 8 : (!FAST ? 6 : 1)) v
                 }
             }
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) dmax = fmaxf(dmax, __shfl_xor(dmax, off, 64));
-        if (lane == 0) s_dmax[wv] = dmax;
+        block_put(s_dmax, wv, dmax, FMax{});
     }
     __syncthreads();
-    // Occlusion culling of the whole brick.  An update needs costheta > mincos and
-    // costheta * (md - Z) > -trunc, hence md - Z > -trunc / mincos; md is a convex combination of
-    // texels of the staged rectangle, so md <= dmax, and Z >= zmin.  If even dmax - zmin lies below
-    // that bound (with a relative margin far above the rounding of the per-voxel expression), no voxel
-    // of the brick can change: skip it before any volume traffic or per-voxel arithmetic.
+    // skip an occluded brick before any volume traffic or per-voxel arithmetic
     if (use_tile && p.mincos > 0.f && p.trunc > 0.f) {
-        if constexpr (NW == 4) {
-            dmax = fmaxf(fmaxf(s_dmax[0], s_dmax[1]), fmaxf(s_dmax[2], s_dmax[3]));
-        } else {
-            dmax = s_dmax[0];
-#pragma unroll
-            for (int k = 1; k < NW; ++k) dmax = fmaxf(dmax, s_dmax[k]);
-        }
-        const float bound = -(p.trunc / p.mincos) * 1.001f;
-        const float dfar = dmax + fabsf(dmax) * 1e-5f;
-        if (dfar - zmin < bound) return; // also when every texel is NaN (dmax = -inf)
+        dmax = block_get<NW>(s_dmax, FMax{});
+        if (brick_occluded(dmax, zmin, p)) return;
+        const float dfar = far_depth(dmax);
         // Fast kernels, beyond that.  A voxel that lies D = Z - md behind the surface it sees is updated only if mincos < costheta AND
         // costheta D < trunc, and costheta -- the interpolated normal against the voxel's own viewing direction -- is at least
         // c_min = the smallest value any texel of the rectangle gives with ITS viewing direction, less what one pixel of direction
@@ -750,17 +803,9 @@ __global__ __launch_bounds__(64 * NW, (FAST && ZU == 2) ? 8 : (!FAST ? 6 : 1)) v
                     const float ct = -dotn * rs - (fabsf(q.x) + fabsf(q.y) + fabsf(q.z)) * slack - 1e-4f;
                     if (isfinite(ct) && isfinite(q.w)) c = fminf(c, ct);
                 }
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) c = fminf(c, __shfl_xor(c, off, 64));
-                if (lane == 0) s_cmin[wv] = c;
+                block_put(s_cmin, wv, c, FMin{});
                 __syncthreads();
-                if constexpr (NW == 4) {
-                    c = fminf(fminf(s_cmin[0], s_cmin[1]), fminf(s_cmin[2], s_cmin[3]));
-                } else {
-                    c = s_cmin[0];
-#pragma unroll
-                    for (int k = 1; k < NW; ++k) c = fminf(c, s_cmin[k]);
-                }
+                c = block_get<NW>(s_cmin, FMin{});
                 if ((zmin - dfar) * fmaxf(p.mincos, c) >= band) return;   // (c = +inf: no finite texel at all -- the test above has returned)
             }
         }
@@ -807,8 +852,8 @@ __global__ __launch_bounds__(64 * NW, (FAST && ZU == 2) ? 8 : (!FAST ? 6 : 1)) v
         };
         auto emit_group = [&](int g, float mn, float mx, unsigned long long all) {
             if constexpr (TRACK) {
-                const auto fmin2 = [](float a, float b) { return fminf(a, b); };
-                const auto fmax2 = [](float a, float b) { return fmaxf(a, b); };
+                const FMin fmin2;
+                const FMax fmax2;
                 mn = wave_xor_combine<1>(mn, fmin2); mx = wave_xor_combine<1>(mx, fmax2);
                 mn = wave_xor_combine<2>(mn, fmin2); mx = wave_xor_combine<2>(mx, fmax2);
                 if constexpr (LX == 16) { mn = wave_xor_combine<16>(mn, fmin2); mx = wave_xor_combine<16>(mx, fmax2); }
@@ -881,8 +926,7 @@ __global__ __launch_bounds__(64 * NW, (FAST && ZU == 2) ? 8 : (!FAST ? 6 : 1)) v
                 const unsigned rx = (unsigned)(ix - tx0), ry = (unsigned)(iy - ty0);
                 Corners c;
                 if (use_tile && rx < (unsigned)(tw - 1) && ry < (unsigned)(th - 1)) {
-                    const float4* t = s_tile + (ry * (unsigned)tw + rx);
-                    c.c00 = t[0]; c.c01 = t[1]; c.c10 = t[tw]; c.c11 = t[tw + 1];
+                    c = tile_corners(s_tile + (ry * (unsigned)tw + rx), tw);
                 } else {
                     c = DMA ? fetch_texels(p, ix, iy) : fetch_global32(p, ix, iy);
                 }
@@ -920,30 +964,16 @@ __global__ __launch_bounds__(64 * NW, (FAST && ZU == 2) ? 8 : (!FAST ? 6 : 1)) v
                         const float pv = p.K.v0 + div_core(p.K.fv * Pc.y, Pc.z, yz);
                         const float fix = floorf(pu), fiy = floorf(pv);
                         const int rx = (int)fix - tx0v, ry = (int)fiy - ty0v;
+                        const auto sample = [&](int at) {
+                            if constexpr (DXT) return finish_shared(p, Pc, yz, pu - fix, pv - fiy, tile_corners_dx(s_tile + 2 * at, tw));
+                            else return finish_shared(p, Pc, yz, pu - fix, pv - fiy, tile_corners(s_tile + at, tw));
+                        };
                         if constexpr (INTERIOR) { // every lane samples inside the image band and the rectangle
-                            if constexpr (DXT) {
-                                const float4* t = s_tile + 2 * (ry * tw + rx);
-                                o[v] = finish_shared_dx(p, Pc, yz, pu - fix, pv - fiy, t[0], t[1], t[2 * tw], t[2 * tw + 1]);
-                            } else {
-                                const float4* t = s_tile + (ry * tw + rx);
-                                Corners c;
-                                c.c00 = t[0]; c.c01 = t[1]; c.c10 = t[tw]; c.c11 = t[tw + 1];
-                                o[v] = finish_shared(p, Pc, yz, pu - fix, pv - fiy, c);
-                            }
+                            o[v] = sample(ry * tw + rx);
                         } else {
-                            const bool inb = INTERIOR ? upd : (upd && in_bounds(p, pu, pv));
-                            const bool inside = INTERIOR || ((unsigned)rx <= (unsigned)cxmax && (unsigned)ry <= (unsigned)cymax);
-                            if constexpr (DXT) {
-                                const float4* t = s_tile + 2 * (med3_i32(ry, 0, cymax) * tw + med3_i32(rx, 0, cxmax));
-                                o[v] = finish_shared_dx(p, Pc, yz, pu - fix, pv - fiy, t[0], t[1], t[2 * tw], t[2 * tw + 1]);
-                            } else {
-                            const float4* t = s_tile + (med3_i32(ry, 0, cymax) * tw + med3_i32(rx, 0, cxmax));
-                            Corners c;
-                            c.c00 = t[0]; c.c01 = t[1]; c.c10 = t[tw]; c.c11 = t[tw + 1];
-                            o[v] = finish_shared(p, Pc, yz, pu - fix, pv - fiy, c);
-                            }
-                            o[v].ok = ((int)o[v].ok & (int)inb & (int)inside) != 0;
-                            stray |= ((int)inb & (int)!inside) != 0;
+                            const bool inb = upd && in_bounds(p, pu, pv), inside = cell_inside(rx, ry, cxmax, cymax);
+                            o[v] = sample(cell_clamped(rx, ry, cxmax, cymax, tw));
+                            stray |= gate_sample(o[v], inb, inside);
                         }
                     }
                     if constexpr (!INTERIOR) {
@@ -976,8 +1006,7 @@ __global__ __launch_bounds__(64 * NW, (FAST && ZU == 2) ? 8 : (!FAST ? 6 : 1)) v
     #pragma unroll
                     for (int k = 0; k < ZU; ++k)
                         if (any[k]) {
-                            if (o[k][0].ok) accumulate<false, CELL>(o[k][0], p.max_w, c[k].x, c[k].y);
-                            if (o[k][1].ok) accumulate<false, CELL>(o[k][1], p.max_w, c[k].z, c[k].w);
+                            accumulate_pair<false, CELL>(o[k][0], o[k][1], p.max_w, c[k]);
                             CELL::st2(cell + (size_t)k * p.vimg_pitch, c[k]);
                             note_vals(c[k]);
                         }
@@ -1012,19 +1041,11 @@ __global__ __launch_bounds__(64 * NW, (FAST && ZU == 2) ? 8 : (!FAST ? 6 : 1)) v
                             const float fix = floorf(pu), fiy = floorf(pv);
                             const int rx = (int)fix - tx0v, ry = (int)fiy - ty0v;
                             if constexpr (INTERIOR) { // every lane samples inside the image band and the rectangle
-                                const float4* t = s_tile + (ry * tw + rx);
-                                Corners c;
-                                c.c00 = t[0]; c.c01 = t[1]; c.c10 = t[tw]; c.c11 = t[tw + 1];
-                                o[k][v] = finish<FAST>(p, Pc, iz, pu - fix, pv - fiy, c);
+                                o[k][v] = finish<FAST>(p, Pc, iz, pu - fix, pv - fiy, tile_corners(s_tile + (ry * tw + rx), tw));
                             } else {
-                                const bool inb = INTERIOR ? upd : (upd && in_bounds(p, pu, pv));
-                                const bool inside = INTERIOR || ((unsigned)rx <= (unsigned)cxmax && (unsigned)ry <= (unsigned)cymax);
-                                const float4* t = s_tile + (med3_i32(ry, 0, cymax) * tw + med3_i32(rx, 0, cxmax)); // clamps: one v_med3_i32 each
-                                Corners c;
-                                c.c00 = t[0]; c.c01 = t[1]; c.c10 = t[tw]; c.c11 = t[tw + 1];
-                                o[k][v] = finish<FAST>(p, Pc, iz, pu - fix, pv - fiy, c);
-                                o[k][v].ok = ((int)o[k][v].ok & (int)inb & (int)inside) != 0;
-                                stray |= ((int)inb & (int)!inside) != 0;
+                                const bool inb = upd && in_bounds(p, pu, pv), inside = cell_inside(rx, ry, cxmax, cymax);
+                                o[k][v] = finish<FAST>(p, Pc, iz, pu - fix, pv - fiy, tile_corners(s_tile + cell_clamped(rx, ry, cxmax, cymax, tw), tw));
+                                stray |= gate_sample(o[k][v], inb, inside);
                             }
                         }
                         any[k] = ((int)o[k][0].ok | (int)o[k][1].ok) != 0;
@@ -1051,6 +1072,8 @@ __global__ __launch_bounds__(64 * NW, (FAST && ZU == 2) ? 8 : (!FAST ? 6 : 1)) v
     #pragma unroll
                 for (int k = 0; k < ZU; ++k)
                     if (any[k]) {
+                        // (not accumulate_pair, here and in the gather loop below: with it hipcc gives the fast tracked fp32 kernels a 64th
+                        // VGPR, moves their scratch and changes the vector instructions of their slice loops)
                         if (o[k][0].ok) accumulate<FAST, CELL>(o[k][0], p.max_w, c[k].x, c[k].y);
                         if (o[k][1].ok) accumulate<FAST, CELL>(o[k][1], p.max_w, c[k].z, c[k].w);
                         CELL::st2(cell + (size_t)k * p.vimg_pitch, c[k]);
@@ -1151,12 +1174,11 @@ __global__ __launch_bounds__(256) void k_sdf_fuse_count(const FuseParams p, cons
         CamXY<FAST> cam;
         cam.init(p, p.bmin.x + p.size.x * (float)x / p.w1, p.bmin.y + p.size.y * (float)y / p.h1);
         for (int z = zbeg; z < zend; ++z) {
-            const float pz = p.bmin.z + p.size.z * (float)(z + p.zoff) / p.d1;
+            const float pz = slice_z(p, z);
             n += observe<FAST, false>(p, cam.at(p, pz)).ok ? 1u : 0u;
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64); // wave64 butterfly sum
+    n = wave_combine(n, [](unsigned a, unsigned b) { return a + b; });
     if (lane == 0 && n) atomicAdd(count, (unsigned long long)n);
 }
 
@@ -1340,7 +1362,7 @@ __global__ __launch_bounds__(256) void k_sdf_fuse_color(const FuseParams p, cons
     const int y = blockIdx.y * FUSE_ROWS + wv;
     const int zbeg = blockIdx.z * FUSE_ZC;
     const int zend = min(zbeg + FUSE_ZC, p.Z);
-    if (threadIdx.x < FUSE_ZC) s_pz[threadIdx.x] = p.bmin.z + p.size.z * (float)(zbeg + (int)threadIdx.x) / p.d1;
+    if (threadIdx.x < FUSE_ZC) s_pz[threadIdx.x] = slice_z(p, zbeg + (int)threadIdx.x);   // (p.zoff = 0: kfx_sdf_fuse_color takes no slab)
     __syncthreads();
     if (x >= p.X || y >= p.Y) return;
 
@@ -1383,18 +1405,16 @@ __global__ __launch_bounds__(256) void k_sdf_fuse_color_tiled(const FuseParams p
     extern __shared__ __attribute__((aligned(16))) float4 s_tile[];
     unsigned* const s_rgb = reinterpret_cast<unsigned*>(s_tile + cap_px);
     __shared__ float s_pz[FUSE_ZC];
-    __shared__ float s_box[4][9];
+    __shared__ float s_box[9][4];   // the waves' values of umin, vmin, qumin, qvmin, zmin, umax, vmax, qumax, qvmax
     __shared__ float s_dmax[4];
-    __shared__ int s_bad[4];
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // XCD-aware brick order, as k_sdf_fuse_tiled: the x-brick rotated by the z-brick
-    const int bxi = p.xcd_swizzle ? (int)((blockIdx.x + (blockIdx.z >> (p.xcd_swizzle - 1))) % gridDim.x) : (int)blockIdx.x;
+    const int bxi = xcd_rotated_brick(p, (int)blockIdx.z);
     const int x0 = (bxi * 32 + (lane & 31)) * 2;
     const int y = blockIdx.y * TB_Y + wv * 2 + (lane >> 5);
     const int zbeg = blockIdx.z * FUSE_ZC;
     const int zend = min(zbeg + FUSE_ZC, p.Z);
     const bool live = x0 < p.X && y < p.Y;
-    if (tid < FUSE_ZC) s_pz[tid] = p.bmin.z + p.size.z * (float)(zbeg + tid + p.zoff) / p.d1;
+    if (tid < FUSE_ZC) s_pz[tid] = slice_z(p, zbeg + tid);
     __syncthreads();
 
     const float py = p.bmin.y + p.size.y * (float)y / p.h1;
@@ -1432,45 +1452,26 @@ __global__ __launch_bounds__(256) void k_sdf_fuse_color_tiled(const FuseParams p
         }
     }
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { // wave64 butterfly
+    for (int k = 0; k < 5; ++k) block_put(s_box[k], wv, lo[k], FMin{});
 #pragma unroll
-        for (int k = 0; k < 5; ++k) lo[k] = fminf(lo[k], __shfl_xor(lo[k], off, 64));
+    for (int k = 0; k < 4; ++k) block_put(s_box[5 + k], wv, hi[k], FMax{});
+    const bool any_bad = __syncthreads_or(bad) != 0;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], off, 64));
-    }
-    const bool wave_bad = __ballot(bad) != 0ull;
-    if (lane == 0) {
+    for (int k = 0; k < 5; ++k) lo[k] = block_get<4>(s_box[k], FMin{});
 #pragma unroll
-        for (int k = 0; k < 5; ++k) s_box[wv][k] = lo[k];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) s_box[wv][5 + k] = hi[k];
-        s_bad[wv] = wave_bad ? 1 : 0;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 5; ++k) lo[k] = fminf(fminf(s_box[0][k], s_box[1][k]), fminf(s_box[2][k], s_box[3][k]));
-#pragma unroll
-    for (int k = 0; k < 4; ++k) hi[k] = fmaxf(fmaxf(s_box[0][5 + k], s_box[1][5 + k]), fmaxf(s_box[2][5 + k], s_box[3][5 + k]));
-    const bool any_bad = (s_bad[0] | s_bad[1] | s_bad[2] | s_bad[3]) != 0;
+    for (int k = 0; k < 4; ++k) hi[k] = block_get<4>(s_box[5 + k], FMax{});
     const float zmin = lo[4];
 
     bool use_tile = false;
-    int tx0 = 0, ty0 = 0, tw = 0, th = 0, cx0 = 0, cy0 = 0, cw = 0, chh = 0;
+    TileRect td = {0, 0, 0, 0}, tc = {0, 0, 0, 0};   // in the depth / normal image, in the RGB image
     if (!any_bad) {
-        // an update needs both samples inside their image's border band: a rectangle that misses it means no voxel
-        // of the brick can change (workgroup-uniform exit)
-        if (hi[0] < 2.0f || !(lo[0] < p.dwb) || hi[1] < 2.0f || !(lo[1] < p.dhb)) return;
-        if (hi[2] < 2.0f || !(lo[2] < q.iwb) || hi[3] < 2.0f || !(lo[3] < q.ihb)) return;
-        const float fx0 = fmaxf(floorf(lo[0]) - 1.f, 0.f), fx1 = fminf(floorf(hi[0]) + 2.f, (float)(p.depth.w - 1));
-        const float fy0 = fmaxf(floorf(lo[1]) - 1.f, 0.f), fy1 = fminf(floorf(hi[1]) + 2.f, (float)(p.depth.h - 1));
-        tx0 = (int)fx0; ty0 = (int)fy0;
-        tw = (int)fx1 - tx0 + 1; th = (int)fy1 - ty0 + 1;
-        const float gx0 = fmaxf(floorf(lo[2]) - 1.f, 0.f), gx1 = fminf(floorf(hi[2]) + 2.f, (float)(q.img.w - 1));
-        const float gy0 = fmaxf(floorf(lo[3]) - 1.f, 0.f), gy1 = fminf(floorf(hi[3]) + 2.f, (float)(q.img.h - 1));
-        cx0 = (int)gx0; cy0 = (int)gy0;
-        cw = (int)gx1 - cx0 + 1; chh = (int)gy1 - cy0 + 1;
-        use_tile = tw > 1 && th > 1 && tw * th <= cap_px && cw > 1 && chh > 1 && cw * chh <= cap_cpx;
+        // an update needs both samples inside their image's border band (workgroup-uniform exit)
+        if (misses_band(lo[0], hi[0], lo[1], hi[1], p.dwb, p.dhb) || misses_band(lo[2], hi[2], lo[3], hi[3], q.iwb, q.ihb)) return;
+        td = tile_rect(lo[0], hi[0], lo[1], hi[1], p.depth.w, p.depth.h);
+        tc = tile_rect(lo[2], hi[2], lo[3], hi[3], q.img.w, q.img.h);
+        use_tile = td.fits(cap_px) && tc.fits(cap_cpx);
     }
+    const int tx0 = td.x0, ty0 = td.y0, tw = td.w, th = td.h, cx0 = tc.x0, cy0 = tc.y0, cw = tc.w, chh = tc.h;
     float dmax = -inf;
     if (use_tile) { // cooperative, row-coalesced staging of both rectangles
         for (int r = wv; r < th; r += 4) {
@@ -1487,17 +1488,10 @@ __global__ __launch_bounds__(256) void k_sdf_fuse_color_tiled(const FuseParams p
             const U3* irow = reinterpret_cast<const U3*>(q.img.ptr + (size_t)(cy0 + r) * q.img.pitch) + cx0;
             for (int c = lane; c < cw; c += 64) s_rgb[r * cw + c] = pack_rgb(irow[c]);
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) dmax = fmaxf(dmax, __shfl_xor(dmax, off, 64));
-        if (lane == 0) s_dmax[wv] = dmax;
+        block_put(s_dmax, wv, dmax, FMax{});
     }
     __syncthreads();
-    // occlusion culling of the whole brick: see k_sdf_fuse_tiled
-    if (use_tile && p.mincos > 0.f && p.trunc > 0.f) {
-        dmax = fmaxf(fmaxf(s_dmax[0], s_dmax[1]), fmaxf(s_dmax[2], s_dmax[3]));
-        const float bound = -(p.trunc / p.mincos) * 1.001f;
-        if (dmax + fabsf(dmax) * 1e-5f - zmin < bound) return;
-    }
+    if (use_tile && p.mincos > 0.f && p.trunc > 0.f && brick_occluded(block_get<4>(s_dmax, FMax{}), zmin, p)) return;
     if (!live) return;
 
     unsigned char* cell = p.vptr + (size_t)zbeg * p.vimg_pitch + (size_t)y * p.vpitch + (size_t)x0 * 8;
@@ -1518,14 +1512,10 @@ __global__ __launch_bounds__(256) void k_sdf_fuse_color_tiled(const FuseParams p
                 const bool inb = in_bounds(p, pu, pv) && in_bounds_color(q, qu, qv);
                 const float fix = floorf(pu), fiy = floorf(pv), gix = floorf(qu), giy = floorf(qv);
                 const int rx = (int)fix - tx0, ry = (int)fiy - ty0, gx = (int)gix - cx0, gy = (int)giy - cy0;
-                const bool inside = (unsigned)rx <= (unsigned)cxmax && (unsigned)ry <= (unsigned)cymax &&
-                                    (unsigned)gx <= (unsigned)gxmax && (unsigned)gy <= (unsigned)gymax;
-                const float4* t = s_tile + (min(max(ry, 0), cymax) * tw + min(max(rx, 0), cxmax));
-                Corners c;
-                c.c00 = t[0]; c.c01 = t[1]; c.c10 = t[tw]; c.c11 = t[tw + 1];
-                o[v] = finish<FAST>(p, Pc, iz, pu - fix, pv - fiy, c);
-                o[v].ok = ((int)o[v].ok & (int)inb & (int)inside) != 0;
-                const unsigned* g = s_rgb + (min(max(gy, 0), gymax) * cw + min(max(gx, 0), gxmax));
+                const bool inside = cell_inside(rx, ry, cxmax, cymax) && cell_inside(gx, gy, gxmax, gymax);
+                o[v] = finish<FAST>(p, Pc, iz, pu - fix, pv - fiy, tile_corners(s_tile + cell_clamped(rx, ry, cxmax, cymax, tw), tw));
+                stray |= gate_sample(o[v], inb, inside);
+                const unsigned* g = s_rgb + cell_clamped(gx, gy, gxmax, gymax, cw);
                 const Rgb4 texels{g[0], g[1], g[cw], g[cw + 1]};
                 if constexpr (FAST) {
                     grey[v] = grey_bilinear<true>(texels, qu - gix, qv - giy);
@@ -1533,7 +1523,6 @@ __global__ __launch_bounds__(256) void k_sdf_fuse_color_tiled(const FuseParams p
                     grey[v] = 0.f;
                     if (o[v].ok) grey[v] = grey_bilinear<false>(texels, qu - gix, qv - giy);
                 }
-                stray |= ((int)inb & (int)!inside) != 0;
             }
         }
         if (__builtin_expect(__ballot(stray) != 0ull, 0)) {
@@ -1544,14 +1533,9 @@ __global__ __launch_bounds__(256) void k_sdf_fuse_color_tiled(const FuseParams p
             float4 c = CellF32::ld2(cell);
             const v2f k = __builtin_nontemporal_load(reinterpret_cast<const v2f*>(ccell));
             float k0 = k.x, k1 = k.y;
-            if (o[0].ok) {
-                k0 = color_mean<FAST>(o[0].w, grey[0], k0, c.y);
-                accumulate<FAST, CellF32>(o[0], p.max_w, c.x, c.y);
-            }
-            if (o[1].ok) {
-                k1 = color_mean<FAST>(o[1].w, grey[1], k1, c.w);
-                accumulate<FAST, CellF32>(o[1], p.max_w, c.z, c.w);
-            }
+            if (o[0].ok) k0 = color_mean<FAST>(o[0].w, grey[0], k0, c.y);   // (with the weights stored before the update)
+            if (o[1].ok) k1 = color_mean<FAST>(o[1].w, grey[1], k1, c.w);
+            accumulate_pair<FAST, CellF32>(o[0], o[1], p.max_w, c);
             CellF32::st2(cell, c);
             v2f kk;
             kk.x = k0; kk.y = k1;
@@ -1578,7 +1562,7 @@ using namespace kfx;
 __global__ __launch_bounds__(256) void k_pack_texels(const ImgView depth, const ImgView norm, unsigned char* __restrict__ tex, const size_t tpitch,
                                                      float* __restrict__ bmax, const unsigned bw8)
 {
-    __shared__ float s_max[4][8];
+    __shared__ float s_max[8][4];   // per 8-pixel block of the row of tiles: the four image rows' maxima
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int u = blockIdx.x * 64 + lane, v = blockIdx.y * 4 + wv;
     float d = -__builtin_inff();
@@ -1588,12 +1572,12 @@ __global__ __launch_bounds__(256) void k_pack_texels(const ImgView depth, const 
         reinterpret_cast<float4*>(tex + (size_t)v * tpitch)[u] = make_float4(n.x, n.y, n.z, dd);
         d = dd;
     }
-    d = wave8_combine(fmaxf(d, -__builtin_inff()), [](float a, float b) { return fmaxf(a, b); });   // (fmaxf drops NaN)
-    if ((lane & 7) == 0) s_max[wv][lane >> 3] = d;
+    d = wave8_combine(fmaxf(d, -__builtin_inff()), FMax{});   // (fmaxf drops NaN)
+    if ((lane & 7) == 0) s_max[lane >> 3][wv] = d;
     __syncthreads();
     if (threadIdx.x < 8)
         bmax[(size_t)blockIdx.y * bw8 + blockIdx.x * 8 + threadIdx.x] =
-            fmaxf(fmaxf(s_max[0][threadIdx.x], s_max[1][threadIdx.x]), fmaxf(s_max[2][threadIdx.x], s_max[3][threadIdx.x]));
+            block_get<4>(s_max[threadIdx.x], FMax{});
 }
 
 // the packed image's geometry for a w x h depth image: texel rows of tpitch bytes, then the block maxima
@@ -1709,6 +1693,7 @@ static int fuse_params(FuseParams& p, bool* small_images, const kfx_volume* vol,
     if (depth->pitch < depth->w * 4 || norm->pitch < depth->w * 16) return set_error(KFX_E_SHAPE, "SdfFuse: image pitch");
     if ((((uintptr_t)depth->ptr | depth->pitch) & 3) || (((uintptr_t)norm->ptr | norm->pitch) & 15))
         return set_error(KFX_E_ALIGN, "SdfFuse: image alignment");
+    p = FuseParams{};   // no slab offset, no summary, no packed texels, no serpentine sweep: fuse_launch fills in what a launch has
     p.vptr = (unsigned char*)vol->ptr;
     p.vpitch = vol->pitch;
     p.vimg_pitch = vol->img_pitch;
@@ -1725,7 +1710,6 @@ static int fuse_params(FuseParams& p, bool* small_images, const kfx_volume* vol,
     p.w1 = (float)(vol->w - 1);
     p.h1 = (float)(vol->h - 1);
     p.d1 = (float)(vol->d - 1);
-    p.zoff = 0;
     p.bmin = V3{vol->boxmin[0], vol->boxmin[1], vol->boxmin[2]};
     p.size = V3{vol->boxmax[0] - vol->boxmin[0], vol->boxmax[1] - vol->boxmin[1], vol->boxmax[2] - vol->boxmin[2]};
     if (slab) {
@@ -1752,14 +1736,6 @@ static int fuse_params(FuseParams& p, bool* small_images, const kfx_volume* vol,
                     depth->pitch < (1u << 24) && norm->pitch < (1u << 24) && depth->h < (1u << 24);
     p.dpitch = *small_images ? (unsigned)depth->pitch : 0u;
     p.npitch = *small_images ? (unsigned)norm->pitch : 0u;
-    p.sum_R = nullptr;
-    p.sum_dirty = nullptr;
-    p.sum_lo_ok = p.sum_hi_ok = 0.f;
-    p.sum_nbx = p.sum_nby = p.sum_bx0 = p.sum_by0 = p.sum_bz0 = p.sum_w = p.sum_h = p.sum_d = p.zoff_local = 0;
-    p.tex = nullptr;
-    p.tpitch = 0;
-    p.bmax = nullptr;
-    p.bw8 = 0;
     // div_uniform is taken only where the host has compared it with the IEEE division for EVERY index of the axis (cached per axis:
     // a volume's extents do not change between frames), so the positions are the reference's by construction
     p.inv_w1 = 1.0f / p.w1;
@@ -1774,7 +1750,6 @@ static int fuse_params(FuseParams& p, bool* small_images, const kfx_volume* vol,
     // KFX_FUSE_EXACT_SHARED=0 keeps hipcc's own division / square-root expansions (A/B, and the parity suite runs both)
     static const int shared_env = env_int("KFX_FUSE_EXACT_SHARED", 1);
     const float afu = fabsf(p.K.fu), afv = fabsf(p.K.fv);
-    p.z_rev = 0; p.keep_z0 = 0; p.keep_z1 = 0;
     p.exact_shared = shared_env && afu >= 0x1p-20f && afu <= 0x1p20f && afv >= 0x1p-20f && afv <= 0x1p20f &&
                      mincostheta >= 0x1p-20f && mincostheta < __builtin_inff() && trunc_dist > 0.f && trunc_dist < __builtin_inff();
     return 0;
@@ -1817,7 +1792,7 @@ static int tile_cap(const FuseParams& p, const Pose& T, const Intr& K, int z0, i
 // 512^3, 1280x960, 2-4 m (r = 2.2 ... 1.1; scripts/c3_brick_ab.py, fast / exact): 64 x 8 x 16 everywhere 0.591 / 0.799 ms,
 // 32 x 8 x 16 everywhere 0.537 / 0.732 ms, 32 x 8 x 8 0.586 / 0.749 ms (its staging and rectangle prologue are amortised
 // over half the slices); at 640x480 (r <= 1.05) the narrow brick costs 0-3 %.
-// dxt: the bit-exact kernel with {texel, x-difference} tiles (finish_shared_dx): 32 bytes per texel, so it is used where the
+// dxt: the bit-exact kernel with {texel, x-difference} tiles (finish_shared on CornersDx): 32 bytes per texel, so it is used where the
 // rectangle -- about (73 r + 5) x (14.7 r + 5) texels -- fits 768 texels, the 24 KiB that keep six workgroups on a CU
 // (r <= 0.64; KFX_FUSE_DXT=0 switches it off, a positive value sets the limit in hundredths).
 struct TilePlan { int small_brick, cap, dxt; };
@@ -1862,6 +1837,63 @@ static int merged_range_end(int z0, int Z, PLAN& plan, F plan_of)
     return z1;
 }
 
+// the planes [z0, z1) of a view as a launch of their own
+static FuseParams z_range(const FuseParams& p, int z0, int z1)
+{
+    FuseParams q = p;
+    q.vptr = p.vptr + (size_t)z0 * p.vimg_pitch;
+    q.zoff = p.zoff + z0;
+    q.zoff_local = z0;
+    q.Z = z1 - z0;
+    return q;
+}
+
+// A k_sdf_fuse_tiled instantiation with the brick it was instantiated for: what its grid and its block size follow from
+struct TiledKernel {
+    void (*fn)(FuseParams, int);
+    int bx, by, bz, threads;   // voxels of a brick, threads of a workgroup
+    dim3 grid(const FuseParams& q) const { return dim3(ceil_div(q.X, bx), ceil_div(q.Y, by), ceil_div(q.Z, bz)); }
+};
+template <bool FAST, int ZU, typename CELL, int LX, int WY, bool TRACK = false, bool DXT = false, int NW = 4>
+static TiledKernel tiled_kernel()
+{
+    return TiledKernel{k_sdf_fuse_tiled<FAST, ZU, CELL, LX, WY, FUSE_ZC, TRACK, DXT, NW>, LX * 2, 64 / LX * WY, FUSE_ZC, 64 * NW};
+}
+// The instantiation for a z-range.  The tracked kernels (summary epilogue) exist with ZU = 2 fast, 1 exact; the eight-wave and the
+// four-slice kernels are fast ones, the former for the narrow brick only; the two-slice exact kernel and the difference tile
+// belong to the wide brick.
+template <typename CELL, int LX, int WY>
+static TiledKernel tiled_kernel_for(bool fast, int zu, bool track, bool dxt, bool nw8)
+{
+    if (track) return fast ? tiled_kernel<true, 2, CELL, LX, WY, true>() : tiled_kernel<false, 1, CELL, LX, WY, true>();
+    if constexpr (LX == 16) {
+        if (nw8) return tiled_kernel<true, 2, CELL, LX, WY, false, false, 8>();
+    }
+    if (fast) return zu == 4 ? tiled_kernel<true, 4, CELL, LX, WY>() : zu == 2 ? tiled_kernel<true, 2, CELL, LX, WY>() : tiled_kernel<true, 1, CELL, LX, WY>();
+    if constexpr (LX == 32) {
+        if (zu == 2) return tiled_kernel<false, 2, CELL, LX, WY>();
+        if (dxt) return tiled_kernel<false, 1, CELL, LX, WY, false, true>();
+    }
+    return tiled_kernel<false, 1, CELL, LX, WY>();
+}
+template <typename CELL>
+static TiledKernel tiled_kernel_for(bool fast, int zu, bool small_brick, bool track, bool dxt, bool nw8)
+{
+    // <LX, WY>: 32 x 8 x 16 voxels, or the default 64 x 8 x 16 (brick geometry, k_sdf_fuse_tiled)
+    return small_brick ? tiled_kernel_for<CELL, 16, 2>(fast, zu, track, dxt, nw8) : tiled_kernel_for<CELL, 32, 4>(fast, zu, track, dxt, false);
+}
+
+// the global-gather kernel: VEC cells per lane, 32-bit image offsets where the images allow them
+template <int VEC, typename CELL>
+static void launch_generic(const FuseParams& p, bool fast, bool small_images, hipStream_t s)
+{
+    const dim3 grid(ceil_div(p.X, 64 * VEC), ceil_div(p.Y, FUSE_ROWS), ceil_div(p.Z, FUSE_ZC));
+    if (fast && small_images) hipLaunchKernelGGL((k_sdf_fuse<VEC, true, true, CELL>), grid, dim3(256), 0, s, p);
+    else if (fast) hipLaunchKernelGGL((k_sdf_fuse<VEC, true, false, CELL>), grid, dim3(256), 0, s, p);
+    else if (small_images) hipLaunchKernelGGL((k_sdf_fuse<VEC, false, true, CELL>), grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((k_sdf_fuse<VEC, false, false, CELL>), grid, dim3(256), 0, s, p);
+}
+
 template <typename CELL>
 static int fuse_launch(const kfx_volume* vol, const kfx_image* depth, const kfx_image* norm, const float T_cw[12],
                        const float K[4], float trunc_dist, float max_w, float mincostheta, unsigned flags, kfx_stream stream,
@@ -1872,8 +1904,6 @@ static int fuse_launch(const kfx_volume* vol, const kfx_image* depth, const kfx_
     if (int e = fuse_params(p, &small_images, vol, depth, norm, T_cw, K, trunc_dist, max_w, mincostheta, flags, CELL::BYTES, slab)) return e;
     if (summary && summary->cell_bytes != CELL::BYTES)
         return set_error(KFX_E_SHAPE, "SdfFuse(tracked): the summary was created for the other cell type (kfx_sdf_summary_create / _create_h)");
-    p.sum_R = nullptr;
-    p.zoff_local = 0;
     bool track = false;
     if (summary) {
         int ox, oy, oz;
@@ -1978,66 +2008,28 @@ static int fuse_launch(const kfx_volume* vol, const kfx_image* depth, const kfx_
             p.bmax = reinterpret_cast<const float*>(p.tex + tl.bmax_off);
             p.bw8 = tl.bw8;
         }
+        // Narrow-brick tiles above 2048 texels (32 KiB: at most four workgroups on a CU) get eight waves per workgroup instead of four --
+        // twice the waves behind one staged rectangle; C3 / S_room 0.4182 -> 0.4237 of peak, interleaved A/B; below that
+        // size the shorter waves' prologues cost more than the residency buys (-1 %).  KFX_FUSE_NW8=<texels> moves the
+        // threshold (0: never).  Same bits.
+        static const int nw8_from = env_int("KFX_FUSE_NW8", 2048);
         for (int ri = 0; ri < n_ranges; ++ri) {
             const Range& rg = ranges[rev ? n_ranges - 1 - ri : ri];
-            const int z0 = rg.z0, z1 = rg.z1;
             const TilePlan plan = rg.plan;
             const int cap_px = plan.cap;
-            FuseParams q = p;
+            FuseParams q = z_range(p, rg.z0, rg.z1);
             q.z_rev = rev;
-            q.keep_z0 = keep_lo - z0; q.keep_z1 = keep_hi - z0;
-            q.vptr = p.vptr + (size_t)z0 * p.vimg_pitch;
-            q.zoff = p.zoff + z0;
-            q.zoff_local = z0;
-            q.Z = z1 - z0;
+            q.keep_z0 = keep_lo - rg.z0; q.keep_z1 = keep_hi - rg.z0;
             const size_t lds = (size_t)cap_px * sizeof(float4) * (plan.dxt ? 2 : 1);
-            if (track) { // the same kernels with the summary epilogue (ZU = 2 fast, 1 exact), fp32 and half cells
-                const dim3 gw(ceil_div(q.X, TB_X), ceil_div(q.Y, TB_Y), ceil_div(q.Z, FUSE_ZC)), gn(ceil_div(q.X, 32), ceil_div(q.Y, 8), ceil_div(q.Z, 16));
-                if (plan.small_brick && fast) hipLaunchKernelGGL((k_sdf_fuse_tiled<true, 2, CELL, 16, 2, 16, true>), gn, dim3(256), lds, s, q, cap_px);
-                else if (plan.small_brick) hipLaunchKernelGGL((k_sdf_fuse_tiled<false, 1, CELL, 16, 2, 16, true>), gn, dim3(256), lds, s, q, cap_px);
-                else if (fast) hipLaunchKernelGGL((k_sdf_fuse_tiled<true, 2, CELL, 32, 4, FUSE_ZC, true>), gw, dim3(256), lds, s, q, cap_px);
-                else hipLaunchKernelGGL((k_sdf_fuse_tiled<false, 1, CELL, 32, 4, FUSE_ZC, true>), gw, dim3(256), lds, s, q, cap_px);
-                continue;
-            }
-            if (plan.small_brick) {
-                dim3 grid(ceil_div(q.X, 32), ceil_div(q.Y, 8), ceil_div(q.Z, 16));
-                const int zu = zu_env ? zu_env : (fast ? (cap_px > 2560 ? 4 : 2) : 1);
-                // Tiles above 2048 texels (32 KiB: at most four workgroups on a CU) get eight waves per workgroup instead of four --
-                // twice the waves behind one staged rectangle; C3 / S_room 0.4182 -> 0.4237 of peak, interleaved A/B; below that
-                // size the shorter waves' prologues cost more than the residency buys (-1 %).  KFX_FUSE_NW8=<texels> moves the
-                // threshold (0: never).  Same bits.
-                static const int nw8_from = env_int("KFX_FUSE_NW8", 2048);
-                if (fast && nw8_from > 0 && cap_px > nw8_from) {
-                    hipLaunchKernelGGL((k_sdf_fuse_tiled<true, 2, CELL, 16, 2, 16, false, false, 8>), grid, dim3(512), lds, s, q, cap_px);
-                    continue;
-                }
-                if (fast && zu == 4) hipLaunchKernelGGL((k_sdf_fuse_tiled<true, 4, CELL, 16, 2, 16>), grid, dim3(256), lds, s, q, cap_px);
-                else if (fast && zu == 2) hipLaunchKernelGGL((k_sdf_fuse_tiled<true, 2, CELL, 16, 2, 16>), grid, dim3(256), lds, s, q, cap_px);
-                else if (fast) hipLaunchKernelGGL((k_sdf_fuse_tiled<true, 1, CELL, 16, 2, 16>), grid, dim3(256), lds, s, q, cap_px);
-                else hipLaunchKernelGGL((k_sdf_fuse_tiled<false, 1, CELL, 16, 2, 16>), grid, dim3(256), lds, s, q, cap_px);
-            } else {
-                dim3 grid(ceil_div(q.X, TB_X), ceil_div(q.Y, TB_Y), ceil_div(q.Z, FUSE_ZC));
-                const int zu = zu_env ? zu_env : (fast ? (cap_px > 2560 ? 4 : 2) : 1);
-                if (fast && zu == 4) hipLaunchKernelGGL((k_sdf_fuse_tiled<true, 4, CELL>), grid, dim3(256), lds, s, q, cap_px);
-                else if (fast && zu == 2) hipLaunchKernelGGL((k_sdf_fuse_tiled<true, 2, CELL>), grid, dim3(256), lds, s, q, cap_px);
-                else if (fast) hipLaunchKernelGGL((k_sdf_fuse_tiled<true, 1, CELL>), grid, dim3(256), lds, s, q, cap_px);
-                else if (zu == 2) hipLaunchKernelGGL((k_sdf_fuse_tiled<false, 2, CELL>), grid, dim3(256), lds, s, q, cap_px);
-                else if (plan.dxt) hipLaunchKernelGGL((k_sdf_fuse_tiled<false, 1, CELL, 32, 4, FUSE_ZC, false, true>), grid, dim3(256), lds, s, q, cap_px);
-                else hipLaunchKernelGGL((k_sdf_fuse_tiled<false, 1, CELL>), grid, dim3(256), lds, s, q, cap_px);
-            }
+            const int zu = zu_env ? zu_env : (fast ? (cap_px > 2560 ? 4 : 2) : 1);
+            const bool nw8 = fast && nw8_from > 0 && cap_px > nw8_from;
+            const TiledKernel k = tiled_kernel_for<CELL>(fast, zu, plan.small_brick != 0, track, plan.dxt != 0, nw8);
+            hipLaunchKernelGGL(k.fn, k.grid(q), dim3(k.threads), lds, s, q, cap_px);
         }
     } else if (vec2) {
-        dim3 grid(ceil_div(p.X, 128), ceil_div(p.Y, FUSE_ROWS), ceil_div(p.Z, FUSE_ZC));
-        if (fast && small_images) hipLaunchKernelGGL((k_sdf_fuse<2, true, true, CELL>), grid, dim3(256), 0, s, p);
-        else if (fast) hipLaunchKernelGGL((k_sdf_fuse<2, true, false, CELL>), grid, dim3(256), 0, s, p);
-        else if (small_images) hipLaunchKernelGGL((k_sdf_fuse<2, false, true, CELL>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((k_sdf_fuse<2, false, false, CELL>), grid, dim3(256), 0, s, p);
+        launch_generic<2, CELL>(p, fast, small_images, s);
     } else {
-        dim3 grid(ceil_div(p.X, 64), ceil_div(p.Y, FUSE_ROWS), ceil_div(p.Z, FUSE_ZC));
-        if (fast && small_images) hipLaunchKernelGGL((k_sdf_fuse<1, true, true, CELL>), grid, dim3(256), 0, s, p);
-        else if (fast) hipLaunchKernelGGL((k_sdf_fuse<1, true, false, CELL>), grid, dim3(256), 0, s, p);
-        else if (small_images) hipLaunchKernelGGL((k_sdf_fuse<1, false, true, CELL>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((k_sdf_fuse<1, false, false, CELL>), grid, dim3(256), 0, s, p);
+        launch_generic<1, CELL>(p, fast, small_images, s);
     }
     return check_launch("kfx_sdf_fuse");
 }
@@ -2135,16 +2127,22 @@ extern "C" int kfx_sdf_reset(const kfx_volume* vol, float trunc_dist, kfx_stream
     return check_launch("kfx_sdf_reset");
 }
 
-extern "C" int kfx_sdf_sphere(const kfx_volume* vol, const float center[3], float r, kfx_stream stream)
+template <typename CELL>
+static int sphere_launch(const kfx_volume* vol, const float center[3], float r, kfx_stream stream, const char* what)
 {
-    if (int e = check_volume(vol, 8, 1, VOLUME_MAX_DIM, "SdfSphere")) return e;
+    if (int e = check_volume(vol, CELL::BYTES, 1, VOLUME_MAX_DIM, "SdfSphere")) return e;
     if (!center) return set_error(KFX_E_NULL, "SdfSphere: null center");
     const int X = (int)(vol->w / 8) * 8, Y = (int)(vol->h / 8) * 8, Z = (int)(vol->d / 8) * 8;
     if (X == 0 || Y == 0 || Z == 0) return 0;
     dim3 grid(ceil_div(X, 64), ceil_div(Y, 4), Z);
-    hipLaunchKernelGGL(k_sdf_sphere<CellF32>, grid, dim3(256), 0, (hipStream_t)stream, vol_view(vol), X, Y, Z,
+    hipLaunchKernelGGL(k_sdf_sphere<CELL>, grid, dim3(256), 0, (hipStream_t)stream, vol_view(vol), X, Y, Z,
                        V3{center[0], center[1], center[2]}, r);
-    return check_launch("kfx_sdf_sphere");
+    return check_launch(what);
+}
+
+extern "C" int kfx_sdf_sphere(const kfx_volume* vol, const float center[3], float r, kfx_stream stream)
+{
+    return sphere_launch<CellF32>(vol, center, r, stream, "kfx_sdf_sphere");
 }
 
 extern "C" int kfx_sdf_reset_h(const kfx_volume* vol, float trunc_dist, kfx_stream stream)
@@ -2160,14 +2158,7 @@ extern "C" int kfx_sdf_reset_h(const kfx_volume* vol, float trunc_dist, kfx_stre
 
 extern "C" int kfx_sdf_sphere_h(const kfx_volume* vol, const float center[3], float r, kfx_stream stream)
 {
-    if (int e = check_volume(vol, 4, 1, VOLUME_MAX_DIM, "SdfSphere")) return e;
-    if (!center) return set_error(KFX_E_NULL, "SdfSphere: null center");
-    const int X = (int)(vol->w / 8) * 8, Y = (int)(vol->h / 8) * 8, Z = (int)(vol->d / 8) * 8;
-    if (X == 0 || Y == 0 || Z == 0) return 0;
-    dim3 grid(ceil_div(X, 64), ceil_div(Y, 4), Z);
-    hipLaunchKernelGGL(k_sdf_sphere<CellF16>, grid, dim3(256), 0, (hipStream_t)stream, vol_view(vol), X, Y, Z,
-                       V3{center[0], center[1], center[2]}, r);
-    return check_launch("kfx_sdf_sphere_h");
+    return sphere_launch<CellF16>(vol, center, r, stream, "kfx_sdf_sphere_h");
 }
 
 // SdfFuse(vol, colorVol, depth, norm, T_cw, K, img, T_iw, Kimg, trunc_dist, max_w, mincostheta) (cu_sdffusion.cu:120-138)
@@ -2210,12 +2201,9 @@ extern "C" int kfx_sdf_fuse_color(const kfx_volume* vol, const kfx_volume* color
             std::pair<int, int> caps;   // {depth / normal tile, RGB tile}
             const int z1 = merged_range_end(z0, p.Z, caps, [&](int a, int b) { return std::make_pair(tile_cap(p, p.T, p.K, a, b), rgb_cap(a, b)); });
             const int cap_px = caps.first, cap_cpx = caps.second;
-            FuseParams pp = p;
+            const FuseParams pp = z_range(p, z0, z1);
             ColorParams qq = q;
-            pp.vptr = p.vptr + (size_t)z0 * p.vimg_pitch;
             qq.cptr = q.cptr + (size_t)z0 * q.cimg_pitch;
-            pp.zoff = z0;
-            pp.Z = z1 - z0;
             dim3 grid(ceil_div(pp.X, TB_X), ceil_div(pp.Y, TB_Y), ceil_div(pp.Z, FUSE_ZC));
             const size_t lds = (size_t)cap_px * sizeof(float4) + (size_t)cap_cpx * sizeof(unsigned);
             if (fast) hipLaunchKernelGGL(k_sdf_fuse_color_tiled<true>, grid, dim3(256), lds, s, pp, qq, cap_px, cap_cpx);

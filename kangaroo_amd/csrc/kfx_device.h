@@ -135,6 +135,39 @@ __device__ __forceinline__ float wave8_combine(float x, F op)
     return op(x, __uint_as_float((unsigned)o));
 }
 
+// op over the 64 lanes of a wave, result in all of them: the __shfl_xor butterfly (ds_bpermute), for values of any 32-bit type
+template <typename T, typename F>
+__device__ __forceinline__ T wave_combine(T x, F op)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x = op(x, __shfl_xor(x, off, 64));
+    return x;
+}
+
+// op over the NW waves of a workgroup, in two halves with the caller's barrier between them: block_put leaves the wave's value
+// in s[wv] (its lanes combined first), block_get combines s[0 .. NW) (adjacent pairs first).
+template <typename F>
+__device__ __forceinline__ void block_put(float* s, int wv, float x, F op)
+{
+    x = wave_combine(x, op);
+    if ((threadIdx.x & 63) == 0) s[wv] = x;
+}
+template <int NW, typename F>
+__device__ __forceinline__ float block_get(const float* s, F op)
+{
+    static_assert(NW >= 2 && (NW & (NW - 1)) == 0, "a power of two waves");
+    float v[NW];
+#pragma unroll
+    for (int k = 0; k < NW; ++k) v[k] = s[k];
+#pragma unroll
+    for (int n = NW / 2; n > 0; n >>= 1)
+#pragma unroll
+        for (int k = 0; k < n; ++k) v[k] = op(v[2 * k], v[2 * k + 1]);
+    return v[0];
+}
+struct FMin { __device__ __forceinline__ float operator()(float a, float b) const { return fminf(a, b); } };
+struct FMax { __device__ __forceinline__ float operator()(float a, float b) const { return fmaxf(a, b); } };
+
 // Row-major 3x4 pose, roo::Mat<float,3,4> (Mat.h:33-163)
 struct Pose { float m[12]; };
 // ImageIntrinsics {fu, fv, u0, v0} (ImageIntrinsics.h:51-200)

@@ -7,22 +7,22 @@ constants read from LDS; the hazard is resolved with `s_waitcnt vmcnt(0)` at the
 store (and exposes its full latency) before any arithmetic starts: the bit-exact kernel went from 0.438 to 0.486 ms with
 an identical instruction sequence otherwise (round 2, found by diffing the two builds).  This script compiles fuse.hip to
 assembly with the Makefile's flags and fails if any block with >= 8 ds_read_b128 (an observation of a voxel pair) waits
-for vector memory before it has issued a load of its own (i.e. for the previous iteration's traffic), or touches scratch.  Usage: python scripts/check_fuse_codegen.py [path/to/fuse.s]"""
+for vector memory before it has issued a load of its own (i.e. for the previous iteration's traffic), or touches scratch.
+It prints one line per k_sdf_fuse_tiled instantiation first (registers, scratch, LDS, occupancy, code bytes, instruction counts
+by class): the tables of two builds are compared with diff.  Usage: python scripts/check_fuse_codegen.py [path/to/fuse.s]"""
 import os
 import re
 import subprocess
 import sys
 import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "kangaroo_amd", "csrc")
-FLAGS = ["-std=c++17", "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math",
-         "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from check_raycast_spills import CSRC, ROOT, makefile_flags   # fuse.o's flags, read from csrc/Makefile
 
 
 def compile_to_asm(out):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    subprocess.run([hipcc] + FLAGS + ["-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-S", "--cuda-device-only", "-o", out,
+    subprocess.run([hipcc] + makefile_flags("fuse.o") + ["-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-S", "--cuda-device-only", "-o", out,
                                       os.path.join(CSRC, "fuse.hip")], check=True, stderr=subprocess.DEVNULL)
 
 
@@ -130,12 +130,52 @@ def keep_load_hazards(asm_path):
     return seen, bad
 
 
+def short_name(mangled):
+    """_ZN3kfx16k_sdf_fuse_tiledILb1ELi2ENS_7CellF32ELi32ELi4ELi16ELb0ELb0ELi4EEEv... -> <1,2,CellF32,32,4,16,0,0,4>"""
+    targs = re.match(r"_ZN3kfx16k_sdf_fuse_tiledI(.*?)EEv", mangled)
+    args = re.findall(r"Lb([01])E|Li(\d+)E|NS_\d+(Cell\w\d\d)E", targs.group(1)) if targs else []
+    return "<%s>" % ",".join(a or b or c for a, b, c in args) if args else mangled
+
+
+def instantiation_table(asm_path):
+    """One line per k_sdf_fuse_tiled instantiation <FAST,ZU,CELL,LX,WY,ZC,TRACK,DXT,NW>, sorted by name: resources as hipcc reports
+    them and the kernel's instruction counts by class (hand-written blocks included).  Two builds are compared with diff."""
+    rows, cur, n = {}, None, None
+    for line in open(asm_path):
+        m = re.match(r"^(_ZN3kfx16k_sdf_fuse_tiled\w+):", line)
+        if m:
+            cur, n = short_name(m.group(1)), {"vector": 0, "scalar": 0, "lds": 0, "memory": 0}
+            rows[cur] = {"n": n}
+        elif cur is None:
+            continue
+        elif line.startswith("\t") and not line.startswith("\t.") and not line.startswith("\t;"):
+            op = line.split()[0]
+            kind = "lds" if op.startswith("ds_") else "memory" if op.startswith(("global_", "buffer_", "scratch_", "flat_")) else \
+                   "scalar" if op.startswith("s_") else "vector" if op.startswith("v_") else None
+            if kind:
+                n[kind] += 1
+        else:
+            m = re.match(r"^; (NumVgprs|ScratchSize|LDSByteSize|Occupancy|codeLenInByte)\s*[:=] (\d+)", line)
+            if m:
+                rows[cur][m.group(1)] = int(m.group(2))
+            if line.startswith("; Occupancy"):   # the last of a kernel's resource lines that the table reads
+                cur = None
+    out = []
+    for k in sorted(rows):
+        r = rows[k]
+        out.append("  %-34s VGPRs %3d  scratch %3d  LDS %5d  occupancy %d  code %6d B  vector %4d  scalar %4d  lds %3d  memory %3d" % (
+            k, r.get("NumVgprs", -1), r.get("ScratchSize", -1), r.get("LDSByteSize", -1), r.get("Occupancy", -1), r.get("codeLenInByte", -1),
+            r["n"]["vector"], r["n"]["scalar"], r["n"]["lds"], r["n"]["memory"]))
+    return out
+
+
 def main():
     if len(sys.argv) > 1:
         path = sys.argv[1]
         kernels, found = hot_block_waits(path)
         budget = register_budget(path)
         keep_seen, keep_bad = keep_load_hazards(path)
+        table = instantiation_table(path)
     else:
         with tempfile.TemporaryDirectory() as d:
             path = os.path.join(d, "fuse.s")
@@ -143,6 +183,8 @@ def main():
             kernels, found = hot_block_waits(path)
             budget = register_budget(path)
             keep_seen, keep_bad = keep_load_hazards(path)
+            table = instantiation_table(path)
+    print("\n".join(table))
     print("%d k_sdf_fuse_tiled instantiations, %d vector-memory waits inside observation blocks" % (kernels, len(found)))
     for f in found:
         print("  %s %s [%d] %s" % f)

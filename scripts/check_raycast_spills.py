@@ -20,11 +20,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "kangaroo_amd", "csrc")
 
 
-def makefile_flags():
-    """CXXFLAGS of csrc/Makefile plus what it adds for raycast.o (EXTRA, the A/B hook, left out)"""
+def makefile_flags(obj="raycast.o"):
+    """CXXFLAGS of csrc/Makefile plus what it adds for `obj` (EXTRA, the A/B hook, left out)"""
     text = open(os.path.join(CSRC, "Makefile")).read().replace("\\\n", " ")
-    found = [re.search(rx, text, re.M) for rx in (r"^CXXFLAGS\s*:=\s*(.*)$", r"^raycast\.o:\s*CXXFLAGS\s*\+=\s*(.*)$", r"^ARCH\s*\?=\s*(\S+)")]
-    assert all(found), "csrc/Makefile: 'CXXFLAGS :=', 'raycast.o: CXXFLAGS +=' or 'ARCH ?=' not found -- makefile_flags() reads those three lines"
+    found = [re.search(rx, text, re.M) for rx in (r"^CXXFLAGS\s*:=\s*(.*)$", r"^%s:\s*CXXFLAGS\s*\+=\s*(.*)$" % re.escape(obj), r"^ARCH\s*\?=\s*(\S+)")]
+    assert all(found), "csrc/Makefile: 'CXXFLAGS :=', '%s: CXXFLAGS +=' or 'ARCH ?=' not found -- makefile_flags() reads those three lines" % obj
     base, extra, arch = (m.group(1) for m in found)
     flags = (base + " " + extra).replace("$(ARCH)", arch).replace("$(EXTRA)", "").split()
     return [f for f in flags if f not in ("-fPIC", "-Wall", "-Wno-unused-function")]
