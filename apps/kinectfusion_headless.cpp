@@ -12,9 +12,12 @@
 //   [--track] for l = MaxLevels-1 .. 0, its[l] times: lss = PoseRefinementProjectiveIcpPointPlane(kin_v[l],
 //             ray_v[l], ray_n[l], K[l]*T_lp, T_lp^-1, icp_c, dScratch, dDebug); solve; T_lp *= exp(x)  (:301-337)
 //   SdfFuse(work_vol, kin_d, kin_n, T_wl^-1, K, trunc_dist, max_w, mincostheta)            (:345-356)
+// --color: the application's fuse_color branch -- SdfReset(colorVol) (:233), SdfFuse(vol, colorVol, ..., drgb, T_cd * T_wl^-1,
+//   Kimg, ...) (:238, :353) and RaycastSdf(..., work_vol, colorVol, ...) on every level (:284); the RGB camera sits a few
+//   centimetres beside the depth camera and sees a fixed, view-independent albedo on the room's surfaces.
 //
 // Host code only; all device work happens in libkfx behind the roo:: wrappers.
-// Usage: kinectfusion_headless [--res N] [--frames F] [--warmup F] [--width W] [--height H] [--fast] [--track | --device-icp] [--fused-launches] [--summary | --summary-auto]
+// Usage: kinectfusion_headless [--res N] [--frames F] [--warmup F] [--width W] [--height H] [--fast] [--track | --device-icp] [--fused-launches] [--summary | --summary-auto] [--color]
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -56,6 +59,29 @@ static void RenderRoom(std::vector<float>& out, int w, int h, const Mat<float,3,
         }
 }
 
+// the colour camera's view of the same room: the albedo of kangaroo_amd/scenes.py render_rgb at the hit point P (metres),
+// r, g, b = round(127.5 + 100 sin(5 P + phi)) with P's x, y, z and phi = 1, 2, 3; (0, 0, 0) where the ray sees nothing
+static void RenderRoomRgb(std::vector<uchar3>& out, int w, int h, const Mat<float,3,4>& T_wi, const ImageIntrinsics& Kimg)
+{
+    std::vector<float> depth;
+    RenderRoom(depth, w, h, T_wi, Kimg);
+    out.resize((size_t)w * h);
+    const float3 c = SE3Translation(T_wi);
+    for (int v = 0; v < h; ++v)
+        for (int u = 0; u < w; ++u) {
+            const float d = depth[(size_t)v * w + u];
+            uchar3 px = make_uchar3(0, 0, 0);
+            if (std::isfinite(d)) {
+                const float3 r = mulSO3(T_wi, Kimg.Unproject((float)u, (float)v));
+                const double P[3] = {(double)c.x + (double)r.x * d, (double)c.y + (double)r.y * d, (double)c.z + (double)r.z * d};
+                px.x = (unsigned char)std::lrint(127.5 + 100.0 * std::sin(5.0 * P[0] + 1.0));
+                px.y = (unsigned char)std::lrint(127.5 + 100.0 * std::sin(5.0 * P[1] + 2.0));
+                px.z = (unsigned char)std::lrint(127.5 + 100.0 * std::sin(5.0 * P[2] + 3.0));
+            }
+            out[(size_t)v * w + u] = px;
+        }
+}
+
 static Mat<float,3,4> OrbitPose(int i, int n)
 {
     const float ph = 2.0f * (float)M_PI * i / n;
@@ -71,7 +97,7 @@ static Mat<float,3,4> OrbitPose(int i, int n)
 int main(int argc, char** argv)
 {
     int volres = 256, frames = 30, w = 640, h = 480;   // the application's defaults (main.cpp:90-91)
-    bool fast = false, track = false, device_icp = false, one_raycast = false, use_summary = false, summary_auto = false;
+    bool fast = false, track = false, device_icp = false, one_raycast = false, use_summary = false, summary_auto = false, use_colour = false;
     int warm = 0;          // --warmup F: the first F frames run but do not count in the reported frame time (clocks, first launches)
     int drop_frame = -1;   // --drop-frame F: frame F arrives with no valid depth at all (a sensor drop-out): tracking is lost, the next frame recovers
     const char* save_mesh = nullptr;   // --save-mesh PREFIX: roo::SaveMesh of the model after the last frame (the application's 's' key) -> PREFIX.ply
@@ -81,6 +107,7 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--width") && i + 1 < argc) w = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--height") && i + 1 < argc) h = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--fast")) fast = true;
+        else if (!strcmp(argv[i], "--color") || !strcmp(argv[i], "--colour")) use_colour = true;   // the application's fuse_color mode
         else if (!strcmp(argv[i], "--track")) track = true;
         else if (!strcmp(argv[i], "--summary")) use_summary = true;   // roo::SdfSummary: SdfFuse keeps it current, RaycastSdf marches through its class tables
         else if (!strcmp(argv[i], "--summary-auto")) use_summary = summary_auto = true;   // ... and the application keeps it only if it pays (whole frames timed with and without it)
@@ -118,6 +145,16 @@ int main(int argc, char** argv)
     Pyramid<float, MaxLevels, TargetDevice, Manage> ray_i(w, h), ray_d(w, h);
     Pyramid<float4, MaxLevels, TargetDevice, Manage> ray_n(w, h), ray_v(w, h);
     BoundedVolume<SDF_t, TargetDevice, Manage> vol(volres, volres, volres, reset_bb);
+    // --color: the grey-level colour volume (main.cpp:119), the RGB frame (:105) and the colour camera: the depth camera's
+    // intrinsics, 25 mm beside it (T_cd: colour <- depth)
+    const int cres = use_colour ? volres : 8;
+    BoundedVolume<float, TargetDevice, Manage> colorVol(cres, cres, cres, reset_bb);
+    Image<uchar3, TargetDevice, Manage> drgb(w, h);
+    const ImageIntrinsics Kimg = K;
+    Mat<float,3,4> T_cd = SE3Identity();
+    T_cd(0,3) = 0.025f; T_cd(1,3) = -0.003f; T_cd(2,3) = 0.002f;
+    // T_cd * T_cw (main.cpp:238: (T_cd * T_wl.inverse()).matrix3x4()); T_cd is a translation
+    const auto color_pose = [&](const Mat<float,3,4>& T_cw) { Mat<float,3,4> T = T_cw; for (int i = 0; i < 3; ++i) T(i,3) = T_cw(i,3) + T_cd(i,3); return T; };
     Image<float4, TargetDevice, Manage> dDebug(w, h);                                             // main.cpp:110
     Image<unsigned char, TargetDevice, Manage> dScratch(w * sizeof(LeastSquaresSystem<float,12>), h);  // main.cpp:111
     const float icp_c = 0.1f, max_rmse = 0.10f;                                                   // main.cpp:154,162
@@ -142,6 +179,14 @@ int main(int argc, char** argv)
         for (float& d : depth_frames[f]) d *= 1000.0f;   // the sensor delivers millimetres (main.cpp:208)
         if (f == drop_frame) for (float& d : depth_frames[f]) d = std::numeric_limits<float>::quiet_NaN();
     }
+    // the RGB frames, as seen from the colour camera of the known poses, resident in device memory like the depth frames
+    std::vector<std::unique_ptr<Image<uchar3, TargetDevice, Manage> > > dRgb(use_colour ? frames : 0);
+    for (int f = 0; f < (int)dRgb.size(); ++f) {
+        std::vector<uchar3> rgb;
+        RenderRoomRgb(rgb, w, h, SE3inv(color_pose(SE3inv(poses[f]))), Kimg);
+        dRgb[f].reset(new Image<uchar3, TargetDevice, Manage>(w, h));
+        dRgb[f]->MemcpyFromHost(rgb.data());
+    }
 
     // the sensor's frames (millimetres), resident in device memory before the loop starts: the timed region begins with its inputs in
     // HBM (the application's per-frame host -> device copy, main.cpp:203, is not part of the path measured here)
@@ -155,7 +200,7 @@ int main(int argc, char** argv)
     std::chrono::steady_clock::time_point t_timed = std::chrono::steady_clock::now();   // start of the timed region (frame `warm`)
     double total_ms = 0, worst_pos_err = 0, rmse = 0;
     size_t hits = 0;
-    unsigned long long depth_sum = 1469598103934665603ull;
+    unsigned long long depth_sum = 1469598103934665603ull, image_sum = 1469598103934665603ull;
     int lost = 0, resets = 0;
     posesolve::SE3d T_anchor;   // the world frame of the estimate in the frame of the known poses (identity until tracking is lost and the model is reset)
     posesolve::SE3d T_wl_est;   // tracked pose (double, as Sophus::SE3d in the application)
@@ -206,12 +251,17 @@ int main(int argc, char** argv)
             rmse = 0;
             ++resets;
         }
+        if (use_colour) drgb.CopyFrom(*dRgb[f]);   // main.cpp:205
         if (f == 0 || recover) {
-            if (use_summary) {
-                SdfReset(vol, std::numeric_limits<float>::quiet_NaN(), *summary);
+            if (use_summary) SdfReset(vol, std::numeric_limits<float>::quiet_NaN(), *summary);
+            else SdfReset(vol, std::numeric_limits<float>::quiet_NaN());
+            if (use_colour) {
+                SdfReset(colorVol);   // main.cpp:233
+                if (use_summary) SdfFuse(vol, colorVol, *summary, kin_d[0], kin_n[0], SE3inv(T_wl), K, drgb, color_pose(SE3inv(T_wl)), Kimg, trunc_dist, max_w, mincostheta);
+                else SdfFuse(vol, colorVol, kin_d[0], kin_n[0], SE3inv(T_wl), K, drgb, color_pose(SE3inv(T_wl)), Kimg, trunc_dist, max_w, mincostheta);   // main.cpp:238
+            } else if (use_summary) {
                 SdfFuse(vol, *summary, kin_d[0], kin_n[0], SE3inv(T_wl), K, trunc_dist, max_w, mincostheta);
             } else {
-                SdfReset(vol, std::numeric_limits<float>::quiet_NaN());
                 SdfFuse(vol, kin_d[0], kin_n[0], SE3inv(T_wl), K, trunc_dist, max_w, mincostheta);
             }
         }
@@ -226,13 +276,17 @@ int main(int argc, char** argv)
                 unsigned n = 0;
                 for (int l = 0; l < MaxLevels; ++l)
                     if (its[l] > 0) { rd[n] = ray_d[l]; rn[n] = ray_n[l]; ri[n] = ray_i[l]; rv[n] = ray_v[l]; Kl[n] = K[l]; ++n; }
-                if (use_summary) RaycastSdfLevels(rd, rn, ri, n, work_vol, *summary, T_wl, Kl, knear, kfar, trunc_dist, true, rv);
+                if (use_colour && use_summary) RaycastSdfLevels(rd, rn, ri, n, work_vol, colorVol, *summary, T_wl, Kl, knear, kfar, trunc_dist, true, rv);
+                else if (use_colour) RaycastSdfLevels(rd, rn, ri, n, work_vol, colorVol, T_wl, Kl, knear, kfar, trunc_dist, true, rv);
+                else if (use_summary) RaycastSdfLevels(rd, rn, ri, n, work_vol, *summary, T_wl, Kl, knear, kfar, trunc_dist, true, rv);
                 else RaycastSdfLevels(rd, rn, ri, n, work_vol, T_wl, Kl, knear, kfar, trunc_dist, true, rv);   // rv[l] = DepthToVbo(rd[l], K[l])
             } else {
                 for (int l = 0; l < MaxLevels; ++l) {
                     if (its[l] > 0) {
                         const ImageIntrinsics Kl = K[l];
-                        if (use_summary) RaycastSdf(ray_d[l], ray_n[l], ray_i[l], work_vol, *summary, T_wl, Kl, knear, kfar, trunc_dist, true);
+                        if (use_colour && use_summary) RaycastSdf(ray_d[l], ray_n[l], ray_i[l], work_vol, colorVol, *summary, T_wl, Kl, knear, kfar, trunc_dist, true);
+                        else if (use_colour) RaycastSdf(ray_d[l], ray_n[l], ray_i[l], work_vol, colorVol, T_wl, Kl, knear, kfar, trunc_dist, true);   // main.cpp:284
+                        else if (use_summary) RaycastSdf(ray_d[l], ray_n[l], ray_i[l], work_vol, *summary, T_wl, Kl, knear, kfar, trunc_dist, true);
                         else RaycastSdf(ray_d[l], ray_n[l], ray_i[l], work_vol, T_wl, Kl, knear, kfar, trunc_dist, true);
                         DepthToVbo<float>(ray_v[l], ray_d[l], Kl);
                     }
@@ -316,7 +370,11 @@ int main(int argc, char** argv)
                 for (int i = 0; i < 3; ++i) e += (T_abs.t[i] - poses[f](i, 3)) * (T_abs.t[i] - poses[f](i, 3));
                 if (f != drop_frame) worst_pos_err = std::fmax(worst_pos_err, std::sqrt(e));   // (a frame without depth has no estimate)
             }
-            if (f > 0 && tracking_good) {
+            if (f > 0 && tracking_good && use_colour) {
+                BoundedVolume<float> work_colorVol = colorVol.SubBoundingVolume(roi);   // main.cpp:349
+                if (use_summary) SdfFuse(work_vol, work_colorVol, *summary, kin_d[0], kin_n[0], SE3inv(T_wl), K, drgb, color_pose(SE3inv(T_wl)), Kimg, trunc_dist, max_w, mincostheta);
+                else SdfFuse(work_vol, work_colorVol, kin_d[0], kin_n[0], SE3inv(T_wl), K, drgb, color_pose(SE3inv(T_wl)), Kimg, trunc_dist, max_w, mincostheta);   // main.cpp:353
+            } else if (f > 0 && tracking_good) {
                 if (use_summary) SdfFuse(work_vol, *summary, kin_d[0], kin_n[0], SE3inv(T_wl), K, trunc_dist, max_w, mincostheta);
                 else SdfFuse(work_vol, kin_d[0], kin_n[0], SE3inv(T_wl), K, trunc_dist, max_w, mincostheta);
             }
@@ -354,15 +412,21 @@ int main(int argc, char** argv)
                 memcpy(&u, &d, 4);
                 depth_sum = (depth_sum ^ u) * 1099511628211ull;
             }
+            ray_i[0].MemcpyToHost(hdepth.data());
+            for (float d : hdepth) {   // ... and of the last shade / colour image
+                unsigned u;
+                memcpy(&u, &d, 4);
+                image_sum = (image_sum ^ u) * 1099511628211ull;
+            }
         }
     }
-    printf("kinectfusion_headless: %d^3 volume, %dx%d, %d frames, %s math, %s poses: %.3f ms/frame (%.1f fps), last raycast hits %zu/%d%s, depth checksum %016llx\n",
+    printf("kinectfusion_headless: %d^3 volume, %dx%d, %d frames, %s math, %s poses: %.3f ms/frame (%.1f fps), last raycast hits %zu/%d%s, depth checksum %016llx, %s checksum %016llx\n",
            volres, w, h, frames, fast ? "fast" : "exact", device_icp ? "ICP-tracked (device loop)" : (track ? "ICP-tracked" : "known"), total_ms / (frames - warm), 1e3 * (frames - warm) / total_ms, hits, w * h,
-           use_summary ? " (brick summary)" : "", depth_sum);
+           use_summary ? " (brick summary)" : "", depth_sum, use_colour ? "colour" : "shade", image_sum);
     if (track) printf("  tracking: worst position error %.2f mm over the orbit (step between poses up to %.1f mm), final rmse %.4f, %d frames lost, %d resets\n",
                       1e3 * worst_pos_err, 1e3 * 0.0105, rmse, lost, resets);
     if (save_mesh) {
-        const size_t ntri = SaveMesh(save_mesh, vol);
+        const size_t ntri = use_colour ? SaveMesh(save_mesh, vol, colorVol) : SaveMesh(save_mesh, vol);   // main.cpp:187
         printf("  mesh: %zu triangles written to %s.ply\n", ntri, save_mesh);
     }
     const int expect_lost = (track && drop_frame > 0 && drop_frame < frames) ? 1 : 0;

@@ -406,8 +406,9 @@ int kfx_raycast_state_to_images(const kfx_image* depth, const kfx_image* norm, c
  * Where less than a quarter of the volume qualifies (the count the last table build published; KFX_RAYCAST_SUMMARY=1 / -1
  * overrides) the tracked call runs the plain march: same images.
  * The summary describes the volume it was created for; views of that volume (SubBoundingVolume) may be passed to the
- * tracked calls.  Anything else that writes the volume (copies, kfx_sdf_sphere, untracked kfx_sdf_fuse) must be followed
- * by kfx_sdf_summary_invalidate.  A tracked SdfFuse whose view does not start on multiples of 8 cells, or that takes the
+ * tracked calls.  Anything else that writes the volume (copies, kfx_sdf_sphere, untracked kfx_sdf_fuse, kfx_sdf_fuse_color)
+ * must be followed by kfx_sdf_summary_invalidate; the colour fusion that keeps the summary is kfx_sdf_fuse_color_tracked
+ * (include/kfx_color.h).  A tracked SdfFuse whose view does not start on multiples of 8 cells, or that takes the
  * untiled kernel, invalidates the summary itself (correct, no skipping until the next reset). */
 typedef struct kfx_sdf_summary kfx_sdf_summary;
 int kfx_sdf_summary_create(kfx_sdf_summary** out, const kfx_volume* vol);

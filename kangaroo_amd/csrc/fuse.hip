@@ -1399,10 +1399,99 @@ __global__ __launch_bounds__(256) void k_sdf_fuse_color(const FuseParams p, cons
 // ---------------------------------------------------------------------------------------
 typedef float v2f __attribute__((ext_vector_type(2)));
 
-template <bool FAST>
+// TRACK bookkeeping of the colour kernel: a copy of k_sdf_fuse_tiled's -- its note_pair / note_vals / emit_group / flush /
+// next_group lambdas and its summary epilogue, which stay where they are: that kernel's code is pinned by
+// scripts/check_fuse_codegen.py -- for the one brick the colour kernel has, 64 x 8 x 16 voxels (<LX, WY, NG> = <32, 4, 2>: a
+// wave holds two rows of 64 voxels over all 16 slices, i.e. two 8-slice groups of eight summary bricks side by side in x).
+// Per group: the range of the cell values the wave stored and the lanes that updated both of their cells in every slice.
+struct ColorTrack {
+    float mn, mx;
+    unsigned long long all;
+    int g;
+    __device__ __forceinline__ void reset(int group) { mn = __builtin_inff(); mx = -__builtin_inff(); all = ~0ull; g = group; }
+    // every cell pair of every slice, in wave-uniform control flow (`ok` = the cell is updated)
+    __device__ __forceinline__ void note_pair(bool ok0, bool ok1) { all &= __ballot(ok0) & __ballot(ok1); }
+    // a pair that was loaded, updated (one or both cells) and stored: both cells enter the range (a cell that was not updated
+    // keeps a value that belongs to the brick anyway; NaN is ignored by min / max)
+    __device__ __forceinline__ void note_vals(const float4& c)
+    {
+        mn = __builtin_fminf(__builtin_fminf(mn, c.x), c.z);
+        mx = __builtin_fmaxf(__builtin_fmaxf(mx, c.x), c.z);
+    }
+    // a complete group: reduce over the lanes of each summary brick (4 neighbours in x = 8 cells, both rows of the wave) and
+    // leave {lo, hi, every cell rewritten} per brick in s_part.  `slices`: the slices of the workgroup that lie in the launch.
+    __device__ static __forceinline__ void emit(float* s_part, int wv, int lane, int slices, int group, float lo, float hi, unsigned long long every)
+    {
+        const FMin fmin2;
+        const FMax fmax2;
+        lo = wave_xor_combine<1>(lo, fmin2); hi = wave_xor_combine<1>(hi, fmax2);
+        lo = wave_xor_combine<2>(lo, fmin2); hi = wave_xor_combine<2>(hi, fmax2);
+        lo = wave_xor_combine<32>(lo, fmin2); hi = wave_xor_combine<32>(hi, fmax2);
+        if ((lane & 3) == 0 && lane < 32) {
+            const unsigned long long brick = 0x0000000F0000000Full << (lane & 31 & ~3);
+            const int full = (slices >= 8 * (group + 1) && (every & brick) == brick) ? 1 : 0;
+            float* q = s_part + ((wv * 2 + group) * 8 + (lane >> 2)) * 3;
+            q[0] = lo; q[1] = hi; q[2] = __int_as_float(full);
+        }
+    }
+    __device__ __forceinline__ void next_group(float* s_part, int wv, int lane, int slices, int zrel)
+    {
+        if (zrel == 8) { // uniform
+            emit(s_part, wv, lane, slices, 0, mn, mx, all);
+            reset(1);
+        }
+    }
+    // before leaving: the current group, and an empty second group if the wave never reached it
+    __device__ __forceinline__ void flush(float* s_part, int wv, int lane, int slices) const
+    {
+        emit(s_part, wv, lane, slices, g, mn, mx, all);
+        if (g == 0) emit(s_part, wv, lane, slices, 1, __builtin_inff(), -__builtin_inff(), 0ull);
+    }
+};
+
+// ... and the workgroup's epilogue (k_sdf_fuse_tiled's, for NXB = 8, NZB = 2 and four waves stacked in y): threads 0 .. 15 fold
+// the four waves' parts of one summary brick each into its stored range.  Every thread of the workgroup has passed a barrier
+// after the last emit.
+__device__ __forceinline__ void color_track_epilogue(const FuseParams& p, const float* s_part, int tid, int bxi, int zbeg)
+{
+    if (tid < 16) {
+        const int xb = tid % 8, zb = tid / 8;
+        float mn = __builtin_inff(), mx = -__builtin_inff();
+        int full = 1;
+#pragma unroll
+        for (int w4 = 0; w4 < 4; ++w4) {
+            const float* q = s_part + ((w4 * 2 + zb) * 8 + xb) * 3;
+            mn = fminf(mn, q[0]); mx = fmaxf(mx, q[1]); full &= __float_as_int(q[2]);
+        }
+        const bool some = mx > -__builtin_inff(); // an updated cell holds a number, and it entered the range
+        const int bx = p.sum_bx0 + bxi * 8 + xb, by = p.sum_by0 + blockIdx.y, bz = p.sum_bz0 + (zbeg + p.zoff_local) / 8 + zb;
+        if (some && bx * 8 < p.sum_w && by * 8 < p.sum_h && bz * 8 < p.sum_d) {
+            float4* r = p.sum_R + ((size_t)bz * p.sum_nby + by) * p.sum_nbx + bx;
+            // state 0: every cell has a value in [lo, hi]; 1: every cell NaN; 2: mixed / unknown.  `full`: all 8 x 8 x 8 cells
+            // were updated (a brick cut by the extents never is: it takes the merge, which is always valid)
+            const float4 old = *r;
+            float4 now;
+            if (full) now = make_float4(mn, mx, __int_as_float(0), 0.f);
+            else if (__float_as_int(old.z) == 1) now = make_float4(mn, mx, __int_as_float(2), 0.f);
+            else now = make_float4(fminf(old.x, mn), fmaxf(old.y, mx), old.z, 0.f);
+            *r = now;
+            // the class tables depend on the brick through its mask only: tell their next build if it changed
+            if (brick_class_mask(old.x, old.y, __float_as_int(old.z), p.sum_lo_ok, p.sum_hi_ok) !=
+                brick_class_mask(now.x, now.y, __float_as_int(now.z), p.sum_lo_ok, p.sum_hi_ok))
+                *p.sum_dirty = 1;
+        }
+    }
+}
+
+// TRACK: besides the update the kernel keeps the brick summary current, as k_sdf_fuse_tiled<.., TRACK = true> does: every lane
+// stays in the march (`live` only gates the updates), so the ballots and DPP reductions run in wave-uniform control flow; the
+// workgroup-uniform early exits leave the summary as it is (nothing was written).  No serpentine sweep, no "keep" planes.
+template <bool FAST, bool TRACK = false>
 __global__ __launch_bounds__(256) void k_sdf_fuse_color_tiled(const FuseParams p, const ColorParams q, const int cap_px, const int cap_cpx)
 {
+    static_assert(TB_X == 64 && TB_Y == 8 && FUSE_ZC == 16, "ColorTrack is written for the 64 x 8 x 16 brick");
     extern __shared__ __attribute__((aligned(16))) float4 s_tile[];
+    __shared__ float s_part[TRACK ? 4 * 2 * 8 * 3 : 1];
     unsigned* const s_rgb = reinterpret_cast<unsigned*>(s_tile + cap_px);
     __shared__ float s_pz[FUSE_ZC];
     __shared__ float s_box[9][4];   // the waves' values of umin, vmin, qumin, qvmin, zmin, umax, vmax, qumax, qvmax
@@ -1492,12 +1581,18 @@ __global__ __launch_bounds__(256) void k_sdf_fuse_color_tiled(const FuseParams p
     }
     __syncthreads();
     if (use_tile && p.mincos > 0.f && p.trunc > 0.f && brick_occluded(block_get<4>(s_dmax, FMax{}), zmin, p)) return;
-    if (!live) return;
+    if constexpr (!TRACK) {
+        if (!live) return;
+    }
+    const bool upd = !TRACK || live;   // TRACK: a lane outside the extents observes like the others and updates nothing
+    ColorTrack trk;
+    trk.reset(0);
 
     unsigned char* cell = p.vptr + (size_t)zbeg * p.vimg_pitch + (size_t)y * p.vpitch + (size_t)x0 * 8;
     unsigned char* ccell = q.cptr + (size_t)zbeg * q.cimg_pitch + (size_t)y * q.cpitch + (size_t)x0 * 4;
     const int cxmax = tw - 2, cymax = th - 2, gxmax = cw - 2, gymax = chh - 2;
     for (int z = zbeg; z < zend; ++z, cell += p.vimg_pitch, ccell += q.cimg_pitch) {
+        if constexpr (TRACK) trk.next_group(s_part, wv, lane, zend - zbeg, z - zbeg);
         const float pz = s_pz[z - zbeg];
         Obs o[2];
         float grey[2];
@@ -1509,7 +1604,7 @@ __global__ __launch_bounds__(256) void k_sdf_fuse_color_tiled(const FuseParams p
                 float pu, pv, iz, qu, qv;
                 project<FAST>(p, Pc, pu, pv, iz);
                 project_color<FAST>(q, Pi, qu, qv);
-                const bool inb = in_bounds(p, pu, pv) && in_bounds_color(q, qu, qv);
+                const bool inb = upd && in_bounds(p, pu, pv) && in_bounds_color(q, qu, qv);
                 const float fix = floorf(pu), fiy = floorf(pv), gix = floorf(qu), giy = floorf(qv);
                 const int rx = (int)fix - tx0, ry = (int)fiy - ty0, gx = (int)gix - cx0, gy = (int)giy - cy0;
                 const bool inside = cell_inside(rx, ry, cxmax, cymax) && cell_inside(gx, gy, gxmax, gymax);
@@ -1527,8 +1622,12 @@ __global__ __launch_bounds__(256) void k_sdf_fuse_color_tiled(const FuseParams p
         }
         if (__builtin_expect(__ballot(stray) != 0ull, 0)) {
 #pragma unroll
-            for (int v = 0; v < 2; ++v) o[v] = observe_color_global<FAST>(p, q, cam[v].at(p, pz), ccam[v].at(q, pz), grey[v]);
+            for (int v = 0; v < 2; ++v) {
+                o[v] = observe_color_global<FAST>(p, q, cam[v].at(p, pz), ccam[v].at(q, pz), grey[v]);
+                o[v].ok = o[v].ok && upd;
+            }
         }
+        if constexpr (TRACK) trk.note_pair(o[0].ok, o[1].ok);
         if (o[0].ok || o[1].ok) {
             float4 c = CellF32::ld2(cell);
             const v2f k = __builtin_nontemporal_load(reinterpret_cast<const v2f*>(ccell));
@@ -1540,7 +1639,13 @@ __global__ __launch_bounds__(256) void k_sdf_fuse_color_tiled(const FuseParams p
             v2f kk;
             kk.x = k0; kk.y = k1;
             __builtin_nontemporal_store(kk, reinterpret_cast<v2f*>(ccell));
+            if constexpr (TRACK) trk.note_vals(c);
         }
+    }
+    if constexpr (TRACK) {
+        trk.flush(s_part, wv, lane, zend - zbeg);
+        __syncthreads();   // every thread of the workgroup arrives here (the early exits above are workgroup-uniform)
+        color_track_epilogue(p, s_part, tid, bxi, zbeg);
     }
 }
 
@@ -1894,6 +1999,32 @@ static void launch_generic(const FuseParams& p, bool fast, bool small_images, hi
     else hipLaunchKernelGGL((k_sdf_fuse<VEC, false, false, CELL>), grid, dim3(256), 0, s, p);
 }
 
+// The summary hook-up of a tracked launch on the view `vol` (SdfFuse and its colour form): where the view lies in the summary's
+// volume goes into p; *track = the launch keeps the summary current.  `can_track`: the launch runs a kernel with a TRACK
+// instantiation; a launch that cannot keep the summary -- that, or a view that does not start on multiples of 8 cells --
+// invalidates it: nothing is known afterwards.  An empty launch (the reference launches an empty grid) leaves it as it is.
+static int summary_hookup(FuseParams& p, bool* track, kfx_sdf_summary* summary, const kfx_volume* vol, bool empty, bool can_track, kfx_stream stream)
+{
+    *track = false;
+    if (!summary) return 0;
+    int ox, oy, oz;
+    if (int e = summary_view_offset(summary, vol, &ox, &oy, &oz)) return e;
+    *track = (ox % 8 == 0) && (oy % 8 == 0) && (oz % 8 == 0);
+    p.sum_R = summary->R;
+    p.sum_nbx = summary->nbx; p.sum_nby = summary->nby;
+    p.sum_bx0 = ox / 8; p.sum_by0 = oy / 8; p.sum_bz0 = oz / 8;
+    p.sum_w = summary->w; p.sum_h = summary->h; p.sum_d = summary->d;
+    p.sum_lo_ok = summary->c_lo_ok; p.sum_hi_ok = summary->c_hi_ok;
+    p.sum_dirty = summary->d_dirty;
+    if (empty) return 0;
+    if (!(*track && can_track)) {
+        if (int e = kfx_sdf_summary_invalidate(summary, stream)) return e;
+        *track = false;
+    }
+    if (!summary->c_dirty) summary->c_dirty = 1;   // (a tracked launch: whether the tables change is for d_dirty to say)
+    return 0;
+}
+
 template <typename CELL>
 static int fuse_launch(const kfx_volume* vol, const kfx_image* depth, const kfx_image* norm, const float T_cw[12],
                        const float K[4], float trunc_dist, float max_w, float mincostheta, unsigned flags, kfx_stream stream,
@@ -1904,32 +2035,18 @@ static int fuse_launch(const kfx_volume* vol, const kfx_image* depth, const kfx_
     if (int e = fuse_params(p, &small_images, vol, depth, norm, T_cw, K, trunc_dist, max_w, mincostheta, flags, CELL::BYTES, slab)) return e;
     if (summary && summary->cell_bytes != CELL::BYTES)
         return set_error(KFX_E_SHAPE, "SdfFuse(tracked): the summary was created for the other cell type (kfx_sdf_summary_create / _create_h)");
-    bool track = false;
-    if (summary) {
-        int ox, oy, oz;
-        if (int e = summary_view_offset(summary, vol, &ox, &oy, &oz)) return e;
-        track = (ox % 8 == 0) && (oy % 8 == 0) && (oz % 8 == 0);
-        p.sum_R = summary->R;
-        p.sum_nbx = summary->nbx; p.sum_nby = summary->nby;
-        p.sum_bx0 = ox / 8; p.sum_by0 = oy / 8; p.sum_bz0 = oz / 8;
-        p.sum_w = summary->w; p.sum_h = summary->h; p.sum_d = summary->d;
-        p.sum_lo_ok = summary->c_lo_ok; p.sum_hi_ok = summary->c_hi_ok;
-        p.sum_dirty = summary->d_dirty;
-    }
-    if (p.X == 0 || p.Y == 0 || p.Z == 0) return 0; // reference launches an empty grid
+    const bool empty = p.X == 0 || p.Y == 0 || p.Z == 0;
     // two cells per lane need an even extent and a pointer / pitches aligned to the cell pair
     const bool vec2 = (p.X % 2 == 0) && ((((uintptr_t)vol->ptr | vol->pitch | vol->img_pitch) & (2 * CELL::BYTES - 1)) == 0);
+    const int tiled = fuse_tiled_env();
+    bool track = false;
+    // (an untiled launch, or an unaligned view, cannot keep the summary current: the hook-up invalidates it)
+    if (int e = summary_hookup(p, &track, summary, vol, empty, tiled && vec2 && small_images, stream)) return e;
+    if (empty) return 0; // reference launches an empty grid
     const bool fast = math_mode() == KFX_MATH_FAST;
     hipStream_t s = (hipStream_t)stream;
     // tuning / A-B knobs (read once): KFX_FUSE_CAP sets the LDS tile capacity in texels (16 B each, at most 3968)
-    const int tiled = fuse_tiled_env();
     static const int cap_env = [] { const int v = env_int("KFX_FUSE_CAP", 0); return v <= 0 ? 0 : (v < 64 ? 64 : (v > 3968 ? 3968 : v)); }();  // <= 62 KiB: dynamic + static LDS stay below the 64 KiB launch limit
-    if (summary && !(track && tiled && vec2 && small_images)) {
-        // this launch cannot keep the summary current (unaligned view, untiled kernel): nothing is known afterwards
-        if (int e = kfx_sdf_summary_invalidate(summary, stream)) return e;
-        track = false;
-    }
-    if (summary && !summary->c_dirty) summary->c_dirty = 1;   // (a tracked launch: whether the tables change is for d_dirty to say)
     if (tiled && vec2 && small_images) {
         // slices per iteration: 2 in fast mode (memory-bound: more reads in flight), 4 where the large LDS tile leaves
         // only 3 workgroups per CU (1280x960 at 512^3: 0.568 -> 0.538 ms; at 6 workgroups per CU 4 is slower), 1 in exact
@@ -2162,9 +2279,9 @@ extern "C" int kfx_sdf_sphere_h(const kfx_volume* vol, const float center[3], fl
 }
 
 // SdfFuse(vol, colorVol, depth, norm, T_cw, K, img, T_iw, Kimg, trunc_dist, max_w, mincostheta) (cu_sdffusion.cu:120-138)
-extern "C" int kfx_sdf_fuse_color(const kfx_volume* vol, const kfx_volume* colorvol, const kfx_image* depth, const kfx_image* norm,
-                                  const float T_cw[12], const float K[4], const kfx_image* img, const float T_iw[12], const float Kimg[4],
-                                  float trunc_dist, float max_w, float mincostheta, unsigned flags, kfx_stream stream)
+static int fuse_color_launch(const kfx_volume* vol, const kfx_volume* colorvol, const kfx_image* depth, const kfx_image* norm,
+                             const float T_cw[12], const float K[4], const kfx_image* img, const float T_iw[12], const float Kimg[4],
+                             float trunc_dist, float max_w, float mincostheta, unsigned flags, kfx_stream stream, kfx_sdf_summary* summary = nullptr)
 {
     FuseParams p;
     bool small_images = false;
@@ -2177,7 +2294,15 @@ extern "C" int kfx_sdf_fuse_color(const kfx_volume* vol, const kfx_volume* color
         p.X = (int)(vol->w / 16) * 16;
         p.Y = (int)(vol->h / 16) * 16;
     }
-    if (p.X == 0 || p.Y == 0 || p.Z == 0) return 0;
+    if (summary && summary->cell_bytes != 8)
+        return set_error(KFX_E_SHAPE, "SdfFuse(colour, tracked): the summary was created for the other cell type (kfx_sdf_summary_create / _create_h)");
+    const bool empty = p.X == 0 || p.Y == 0 || p.Z == 0;
+    // two voxels per lane: even extent, 16-byte aligned SDF rows, 8-byte aligned colour rows
+    const bool vec2 = (p.X % 2 == 0) && ((((uintptr_t)vol->ptr | vol->pitch | vol->img_pitch) & 15) == 0) &&
+                      ((((uintptr_t)colorvol->ptr | colorvol->pitch | colorvol->img_pitch) & 7) == 0);
+    bool track = false;
+    if (int e = summary_hookup(p, &track, summary, vol, empty, fuse_tiled_env() && vec2, stream)) return e;
+    if (empty) return 0;
     ColorParams q;
     q.cptr = (unsigned char*)colorvol->ptr;
     q.cpitch = colorvol->pitch;
@@ -2189,12 +2314,10 @@ extern "C" int kfx_sdf_fuse_color(const kfx_volume* vol, const kfx_volume* color
     q.ihb = (float)img->h - 2.0f;
     const bool fast = math_mode() == KFX_MATH_FAST;
     hipStream_t s = (hipStream_t)stream;
-    // two voxels per lane: even extent, 16-byte aligned SDF rows, 8-byte aligned colour rows
-    const bool vec2 = (p.X % 2 == 0) && ((((uintptr_t)vol->ptr | vol->pitch | vol->img_pitch) & 15) == 0) &&
-                      ((((uintptr_t)colorvol->ptr | colorvol->pitch | colorvol->img_pitch) & 7) == 0);
     if (fuse_tiled_env() && vec2) {
         // per z-range LDS capacities as in fuse_launch: the depth / normal tile (16 B texels) by the depth camera's
         // pixels-per-voxel ratio, the RGB tile (4 B texels, a third more room) by the colour camera's
+        // (the tracked instantiation's statics are 768 bytes more, s_part: 63 488 + 992 bytes at the most)
         auto rgb_cap = [&](int a, int b) { const int c = tile_cap(p, q.Ti, q.Ki, a, b) * 4 / 3; return c > 3584 ? 3584 : c; }; // 48 + 14 KiB + statics < 64 KiB
         int z0 = 0;
         while (z0 < p.Z) {
@@ -2206,8 +2329,11 @@ extern "C" int kfx_sdf_fuse_color(const kfx_volume* vol, const kfx_volume* color
             qq.cptr = q.cptr + (size_t)z0 * q.cimg_pitch;
             dim3 grid(ceil_div(pp.X, TB_X), ceil_div(pp.Y, TB_Y), ceil_div(pp.Z, FUSE_ZC));
             const size_t lds = (size_t)cap_px * sizeof(float4) + (size_t)cap_cpx * sizeof(unsigned);
-            if (fast) hipLaunchKernelGGL(k_sdf_fuse_color_tiled<true>, grid, dim3(256), lds, s, pp, qq, cap_px, cap_cpx);
-            else hipLaunchKernelGGL(k_sdf_fuse_color_tiled<false>, grid, dim3(256), lds, s, pp, qq, cap_px, cap_cpx);
+            if (track) { // (the ranges start on multiples of FUSE_ZSTEP = 64 planes: whole summary bricks, zoff_local / 8 is exact)
+                if (fast) hipLaunchKernelGGL((k_sdf_fuse_color_tiled<true, true>), grid, dim3(256), lds, s, pp, qq, cap_px, cap_cpx);
+                else hipLaunchKernelGGL((k_sdf_fuse_color_tiled<false, true>), grid, dim3(256), lds, s, pp, qq, cap_px, cap_cpx);
+            } else if (fast) hipLaunchKernelGGL((k_sdf_fuse_color_tiled<true, false>), grid, dim3(256), lds, s, pp, qq, cap_px, cap_cpx);
+            else hipLaunchKernelGGL((k_sdf_fuse_color_tiled<false, false>), grid, dim3(256), lds, s, pp, qq, cap_px, cap_cpx);
             z0 = z1;
         }
     } else {
@@ -2216,6 +2342,22 @@ extern "C" int kfx_sdf_fuse_color(const kfx_volume* vol, const kfx_volume* color
         else hipLaunchKernelGGL(k_sdf_fuse_color<false>, grid, dim3(256), 0, s, p, q);
     }
     return check_launch("kfx_sdf_fuse_color");
+}
+
+extern "C" int kfx_sdf_fuse_color(const kfx_volume* vol, const kfx_volume* colorvol, const kfx_image* depth, const kfx_image* norm,
+                                  const float T_cw[12], const float K[4], const kfx_image* img, const float T_iw[12], const float Kimg[4],
+                                  float trunc_dist, float max_w, float mincostheta, unsigned flags, kfx_stream stream)
+{
+    return fuse_color_launch(vol, colorvol, depth, norm, T_cw, K, img, T_iw, Kimg, trunc_dist, max_w, mincostheta, flags, stream);
+}
+
+// kfx_sdf_fuse_color that keeps the brick summary current (include/kfx_color.h): the contract of kfx_sdf_fuse_tracked
+extern "C" int kfx_sdf_fuse_color_tracked(const kfx_volume* vol, const kfx_volume* colorvol, kfx_sdf_summary* summary, const kfx_image* depth,
+                                          const kfx_image* norm, const float T_cw[12], const float K[4], const kfx_image* img, const float T_iw[12],
+                                          const float Kimg[4], float trunc_dist, float max_w, float mincostheta, unsigned flags, kfx_stream stream)
+{
+    if (!summary) return set_error(KFX_E_NULL, "kfx_sdf_fuse_color_tracked: null summary");
+    return fuse_color_launch(vol, colorvol, depth, norm, T_cw, K, img, T_iw, Kimg, trunc_dist, max_w, mincostheta, flags, stream, summary);
 }
 
 // SdfReset(BoundedVolume<float>) (cu_sdffusion.cu:166-169): every cell of the span, padding included, = 0.5

@@ -14,6 +14,7 @@
 #include "../../include/kfx.h"
 #include "../../include/kfx_extras.h"
 #include "../../include/kfx_summary_h.h"
+#include "../../include/kfx_color.h"
 
 namespace kfx {
 

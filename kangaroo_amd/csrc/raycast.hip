@@ -639,6 +639,47 @@ __global__ __launch_bounds__(256) void k_raycast_sdf_levels_classes(const RayPar
 }
 
 // ---------------------------------------------------------------------------------------
+// The colour image of any rendering (kfx_raycast_color_hits, include/kfx_color.h).  The colour variant of RaycastSdf differs
+// from the grey one in one value per hit pixel, colorVol.GetUnitsTrilinearClamped(c_w + ray_w * depth) (write_ray), which
+// depends on the pixel, the pose, the intrinsics and the depth the march stored -- so any march (plain, class tables, all
+// levels in one launch) renders colour by being followed by this pass: one grid over the pixels of all levels, laid out as
+// k_raycast_sdf_levels lays them out (dense 64 x 4 pixel workgroups).  The position is ray_box()'s and the sample
+// trilinear<RayC32>'s, the expressions of write_ray in the same translation unit: in exact numerics the image is
+// k_raycast_sdf<CELL, true>'s bit for bit.  Pixels without a hit keep the 0 the march wrote.
+// ---------------------------------------------------------------------------------------
+struct ColorHitLevel {
+    const unsigned char* dptr;
+    unsigned char* iptr;
+    size_t dpitch, ipitch;
+    int w, h;
+    Intr K;
+    int first_block, blocks_x; // this level's workgroups are [first_block, next level's first_block), row-major
+};
+struct ColorHitLevels {
+    ColorHitLevel lv[RAY_MAX_LEVELS];
+    int n;
+};
+
+__global__ __launch_bounds__(256) void k_raycast_color_hits(const Pose T, const ColorGeom cv, const ColorHitLevels L)
+{
+    int l = 0;
+    for (int k = 1; k < L.n; ++k)
+        if ((int)blockIdx.x >= L.lv[k].first_block) l = k;
+    const ColorHitLevel& lv = L.lv[l];
+    const int b = (int)blockIdx.x - lv.first_block;
+    const int u = (b % lv.blocks_x) * 64 + (int)(threadIdx.x & 63), v = (b / lv.blocks_x) * 4 + (int)(threadIdx.x >> 6);
+    if (u >= lv.w || v >= lv.h) return;
+    const float depth = reinterpret_cast<const float*>(lv.dptr + (size_t)v * lv.dpitch)[u];
+    if (depth > 0) { // (a miss holds NaN)
+        RayParams p{};   // ray_box reads the pose and the intrinsics for c_w / ray_w; its slab test is not used here
+        p.T = T;
+        p.K = lv.K;
+        const RayBox r = ray_box(p, u, v);
+        reinterpret_cast<float*>(lv.iptr + (size_t)v * lv.ipitch)[u] = trilinear<RayC32>(cv, r.c_w + r.ray_w * depth);
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // Exact multi-GPU march ("exact variant").  The volume is split into Z-slabs; a ray's
 // march state (lambda, last_sdf, delta) is carried from slab to slab in ray order, so every sample is
 // taken at exactly the position, and from exactly the cells, of the single-volume march.  `p` describes
@@ -1215,6 +1256,44 @@ extern "C" int kfx_raycast_sdf_color(const kfx_image* depth, const kfx_image* no
 {
     if (!colorvol) return set_error(KFX_E_NULL, "RaycastSdf(colour): null colour volume");
     return raycast_launch<RayF32>(depth, norm, img, vol, T_wc, K, near, far, trunc_dist, subpix, stream, colorvol);
+}
+
+// The colour image of renderings already marched (include/kfx_color.h): img[l](u, v) = colorvol's trilinear sample at the hit
+// of pixel (u, v) of depth[l], for every pixel with depth > 0; one launch for all levels.
+extern "C" int kfx_raycast_color_hits(int n_levels, const kfx_image* const* depth, const kfx_image* const* img, const kfx_volume* colorvol,
+                                      const float T_wc[12], const float* K, kfx_stream stream)
+{
+    if (n_levels < 1 || n_levels > RAY_MAX_LEVELS) return set_error(KFX_E_RANGE, "RaycastSdf(colour pass): number of levels");
+    if (!depth || !img || !colorvol || !T_wc || !K) return set_error(KFX_E_NULL, "RaycastSdf(colour pass): null argument");
+    if (int e = check_volume(colorvol, 4, 2, VOLUME_ANY_DIM, "RaycastSdf(colour pass)")) return e;
+    ColorHitLevels L{};
+    int blocks = 0;
+    for (int l = 0; l < n_levels; ++l) {
+        const kfx_image *d = depth[l], *i = img[l];
+        if (!d || !i || !d->ptr || !i->ptr) return set_error(KFX_E_NULL, "RaycastSdf(colour pass): null image");
+        if (d->w != i->w || d->h != i->h) return set_error(KFX_E_SHAPE, "RaycastSdf(colour pass): depth and colour image of different sizes");
+        if (d->pitch < d->w * 4 || i->pitch < i->w * 4) return set_error(KFX_E_SHAPE, "RaycastSdf(colour pass): image pitch");
+        if (d->w > 0x7fffffffu || d->h > 0x7fffffffu) return set_error(KFX_E_RANGE, "RaycastSdf(colour pass): image dimensions");
+        if (((uintptr_t)d->ptr | d->pitch | (uintptr_t)i->ptr | i->pitch) & 3) return set_error(KFX_E_ALIGN, "RaycastSdf(colour pass): image alignment");
+        if (d->w == 0 || d->h == 0) continue; // an empty level launches nothing
+        ColorHitLevel& lv = L.lv[L.n++];
+        lv.dptr = (const unsigned char*)d->ptr; lv.iptr = (unsigned char*)i->ptr;
+        lv.dpitch = d->pitch; lv.ipitch = i->pitch;
+        lv.w = (int)d->w; lv.h = (int)d->h;
+        lv.K = Intr{K[4 * l], K[4 * l + 1], K[4 * l + 2], K[4 * l + 3]};
+        lv.first_block = blocks;
+        lv.blocks_x = ceil_div(lv.w, 64);
+        const long long nb = (long long)lv.blocks_x * ceil_div(lv.h, 4);
+        if (blocks + nb > 0x7fffffffLL) return set_error(KFX_E_RANGE, "RaycastSdf(colour pass): too many pixels");
+        blocks += (int)nb;
+    }
+    if (L.n == 0) return 0;
+    ColorGeom cv{};
+    set_geometry(cv, colorvol);
+    Pose T;
+    for (int k = 0; k < 12; ++k) T.m[k] = T_wc[k];
+    hipLaunchKernelGGL(k_raycast_color_hits, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, T, cv, L);
+    return check_launch("kfx_raycast_color_hits");
 }
 
 // Exact multi-GPU march: one round of a rank (see k_raycast_sdf_slab).  `vol` holds planes

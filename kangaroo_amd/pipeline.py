@@ -45,8 +45,15 @@ class FramePipeline:
 
     def __init__(self, ops, dims, boxmin, boxmax, w, h, K=None, near=0.4, far=8.0, bilateral=None,
                  trunc_factor=scenes.TRUNC_DIST_FACTOR, max_w=scenes.MAX_W, mincostheta=scenes.MIN_COS_THETA,
-                 contiguous_images=False, track=False, cal_first=None, cal_block=None, cal_margin=None, timing_slots=None, kind=None):
-        """kind: the volume's cells, "f32" (SDF_t, the default) or "f16" (SDF_h, config C5); an f16 volume runs the separate
+                 contiguous_images=False, track=False, cal_first=None, cal_block=None, cal_margin=None, timing_slots=None, kind=None,
+                 color=False, color_size=None, T_cd=None):
+        """color: the reference application's fuse_color mode (main.cpp:233, :238, :284, :353): the pipeline owns a colour volume
+        (kind "c32", `cvol`) beside the SDF volume and an RGB image (`rgb`, "u8x3", color_size = (w, h) of the colour camera,
+        default the depth camera's; its intrinsics `Kimg` are the application's for that size); step() fuses with SdfFuseColor at
+        T_iw = T_cd * T_cw (T_cd: colour <- depth camera, 3x4 or 4x4, default identity) and renders the colour volume into ray_i.
+        It runs the separate operators (the one-call frame is grey) and takes track=True / False; the tracking loop, whose
+        calibration uses the host clock, also takes "auto".
+        kind: the volume's cells, "f32" (SDF_t, the default) or "f16" (SDF_h, config C5); an f16 volume runs the separate
         operators (the one-call frame is fp32-only) and takes track=True / False, not "auto" (its host-clock calibration does not
         synchronise the frames it times).
         track: keep a brick summary of the volume (ops.SdfSummary) current in SdfFuse and let RaycastSdf step through
@@ -64,6 +71,11 @@ class FramePipeline:
             raise ValueError("FramePipeline: kind must be 'f32' or 'f16', not %r" % (self.kind,))
         if track == "auto" and self.kind != "f32":
             raise ValueError("FramePipeline: track='auto' needs fp32 cells (its calibration times whole frames of the one-call frame)")
+        self.color = bool(color)
+        if self.color and self.kind != "f32":
+            raise ValueError("FramePipeline: color=True needs fp32 cells")
+        if self.color and track == "auto" and self.USE_FRAME:
+            raise ValueError("FramePipeline: color=True takes track=True / False (track='auto' times whole frames of the one-call frame, which is grey)")
         self.track_policy = "auto" if track == "auto" else ("on" if track else "off")
         self.track = bool(track) and hasattr(ops, "SdfSummary")
         if self.track_policy == "auto" and not self.track:
@@ -94,7 +106,15 @@ class FramePipeline:
         self.ray_d = I(w, h, "f32", pitch=pf(4))
         self.ray_n = I(w, h, "f32x4", pitch=pf(16))
         self.ray_i = I(w, h, "f32", pitch=pf(4))
-        if self.USE_FRAME and hasattr(ops, "Frame") and getattr(self.vol, "kind", "f32") == "f32":
+        if self.color:
+            cw, ch = (self.w, self.h) if color_size is None else (int(color_size[0]), int(color_size[1]))
+            self.cvol = ops.BoundedVolume(self.dims[0], self.dims[1], self.dims[2], boxmin, boxmax, kind="c32")
+            self.rgb = I(cw, ch, "u8x3")
+            self.Kimg = scenes.intrinsics(cw, ch)
+            T_cd = scenes.identity_pose() if T_cd is None else np.asarray(T_cd, np.float32).reshape(-1, 4)[:3]
+            self.T_cd = np.vstack([T_cd, [0, 0, 0, 1]]).astype(np.float32)
+            self._rgb_now = self.rgb
+        if self.USE_FRAME and hasattr(ops, "Frame") and getattr(self.vol, "kind", "f32") == "f32" and not self.color:
             self.kframe = ops.Frame(self.vol, self.raw, self.filtered, self.vbo, self.normals, self.ray_d, self.ray_n, self.ray_i, self.K,
                                     self.bil, self.near, self.far, self.trunc, self.max_w, self.mincostheta,
                                     timing_slots=max(256, 3 * self.cal_block + 16, int(timing_slots or 0)))
@@ -158,6 +178,17 @@ class FramePipeline:
             self.ops.SdfReset(self.vol, float("nan"), summary=self.summary)
         else:
             self.ops.SdfReset(self.vol, float("nan"))
+        if self.color:
+            self.ops.ColorReset(self.cvol)   # SdfReset(colorVol) (main.cpp:233)
+
+    def color_pose(self, T_cw):
+        """T_iw = T_cd * T_cw (3x4 float32): world -> colour camera"""
+        return (self.T_cd @ np.vstack([np.asarray(T_cw, np.float32).reshape(3, 4), [0, 0, 0, 1]]).astype(np.float32))[:3].astype(np.float32)
+
+    def _fuse_color(self, maps_d, maps_n, T_cw):
+        """SdfFuse(vol, colorVol, ...) of the given maps and the current RGB image (main.cpp:238 / :353)"""
+        self._timed_fuse(lambda kw: self.ops.SdfFuseColor(self.vol, self.cvol, maps_d, maps_n, T_cw, self.K, self._rgb_now, self.color_pose(T_cw), self.Kimg,
+                                                          self.trunc, self.max_w, self.mincostheta, **kw))
 
     def preprocess(self, raw_image=None):
         if self.kframe is not None:
@@ -237,6 +268,9 @@ class FramePipeline:
         if self.kframe is not None:
             self.kframe.step(T_wc, scenes.se3_inverse(T_wc), None, self.kframe.FUSE)
             return
+        if self.color:
+            self._fuse_color(self.filtered, self.normals, scenes.se3_inverse(T_wc))
+            return
         self._timed_fuse(lambda kw: self.ops.SdfFuse(self.vol, self.filtered, self.normals, scenes.se3_inverse(T_wc), self.K, self.trunc,
                                                      self.max_w, self.mincostheta, **kw))
 
@@ -244,11 +278,18 @@ class FramePipeline:
         if self.kframe is not None:
             self.kframe.step(T_wc, None, None, self.kframe.RAYCAST)
             return
+        if self.color:   # RaycastSdf(..., vol, colorVol, ...) (main.cpp:284)
+            self._timed_raycast(lambda kw: self.ops.RaycastSdfColor(self.ray_d, self.ray_n, self.ray_i, self.vol, self.cvol, T_wc, self.K, self.near,
+                                                                    self.far, self.trunc, True, **kw))
+            return
         self._timed_raycast(lambda kw: self.ops.RaycastSdf(self.ray_d, self.ray_n, self.ray_i, self.vol, T_wc, self.K, self.near, self.far,
                                                            self.trunc, True, **kw))
 
-    def step(self, T_wc, raw_image=None):
-        """One frame: preprocess the new depth image, integrate it, render the model."""
+    def step(self, T_wc, raw_image=None, rgb_image=None):
+        """One frame: preprocess the new depth image, integrate it, render the model.  rgb_image (color=True): the frame's RGB
+        image ("u8x3", the colour camera's size; default self.rgb)."""
+        if self.color:
+            self._rgb_now = self.rgb if rgb_image is None else rgb_image
         cal = self._cal is not None and self.frames_done >= self._cal["first"]
         if cal:
             self._policy_before()
@@ -278,7 +319,8 @@ class TrackingPipeline(FramePipeline):
     def __init__(self, ops, dims, boxmin, boxmax, w, h, its=None, icp_c=0.1, max_rmse=0.10, device_icp=False, one_raycast=None, **kw):
         """device_icp: run the whole refinement loop on the GPU (ops.IcpRefine, one synchronisation per frame) instead
         of one PoseRefinementProjectiveIcpPointPlane call + host solve per iteration.  one_raycast: render all pyramid
-        levels with one launch (ops.RaycastSdfLevels; default: when the operator set has it)."""
+        levels with one launch (ops.RaycastSdfLevels; default: when the operator set has it).  color=True (see FramePipeline):
+        SdfFuseColor at the tracked pose and colour renderings of every level (ops.RaycastSdfColorLevels, or the per-level calls)."""
         from . import tracking
         super().__init__(ops, dims, boxmin, boxmax, w, h, **kw)
         self.tracking = tracking
@@ -325,14 +367,17 @@ class TrackingPipeline(FramePipeline):
         self.preprocess(image, into=self._kin_back)
         self._prefetched = image
 
-    def step(self, T_wl_init=None, raw_image=None, next_image=None):
+    def step(self, T_wl_init=None, raw_image=None, next_image=None, rgb_image=None):
         """One frame.  The first frame is fused at T_wl_init (identity if None); later frames are tracked
         against the model.  Returns the current T_wl (4x4 float64).
         next_image: the depth image the NEXT step will be given (already in device memory).  With the device-resident
         refinement its pre-amble -- which does not depend on any pose -- is enqueued behind the refinement, before this thread
         waits for the pose: the device works on it while the thread wakes up instead of idling until SdfFuse arrives.  The
-        next step finds its maps ready when it is given the same image object; same images, same poses."""
+        next step finds its maps ready when it is given the same image object; same images, same poses.
+        rgb_image (color=True): the frame's RGB image (default self.rgb)."""
         o, tr = self.ops, self.tracking
+        if self.color:
+            self._rgb_now = self.rgb if rgb_image is None else rgb_image
         cal = self._cal is not None and self.frames_done >= self._cal["first"]
         if cal:   # track="auto": whole frames of the three blocks, host clock around the step (the pose read-back synchronises)
             self._policy_before()
@@ -360,7 +405,16 @@ class TrackingPipeline(FramePipeline):
             lv = [l for l in range(self.LEVELS) if self.its[l] > 0]
 
             def render(kw):
-                if self.one_raycast:   # the per-level RaycastSdf + DepthToVbo calls as one launch: same images, overlapping marches
+                if self.color:   # main.cpp:284 on every level, the colour image into pyr_i
+                    outs = [(self.pyr_d[l], self.pyr_n[l], self.pyr_i[l], self.pyr_v[l]) for l in lv]
+                    if self.one_raycast:
+                        o.RaycastSdfColorLevels(outs, self.vol, self.cvol, T34, [self.K_levels[l] for l in lv], self.near, self.far, self.trunc, True, **kw)
+                    else:
+                        for l in lv:
+                            o.RaycastSdfColor(self.pyr_d[l], self.pyr_n[l], self.pyr_i[l], self.vol, self.cvol, T34, self.K_levels[l], self.near,
+                                              self.far, self.trunc, True, **kw)
+                            o.DepthToVbo(self.pyr_v[l], self.pyr_d[l], self.K_levels[l])
+                elif self.one_raycast:   # the per-level RaycastSdf + DepthToVbo calls as one launch: same images, overlapping marches
                     o.RaycastSdfLevels([(self.pyr_d[l], self.pyr_n[l], self.pyr_i[l], self.pyr_v[l]) for l in lv], self.vol, T34,
                                        [self.K_levels[l] for l in lv], self.near, self.far, self.trunc, True, **kw)
                 else:
@@ -377,7 +431,7 @@ class TrackingPipeline(FramePipeline):
                 T_lp, self.rmse, self.tracking_good = tr.refine_pose(o, self.kin_v, self.pyr_v, self.pyr_n, self.K_levels,
                                                                      self.scratch, self.debug, self.its, self.icp_c, self.max_rmse)
             if self.tracking_good:
-                if hasattr(o, "PoseStep") and hasattr(o, "SdfFuseBound"):
+                if hasattr(o, "PoseStep") and hasattr(o, "SdfFuseBound") and not self.color:
                     # the device idles from the pose's arrival to the SdfFuse launch: the update in one host call, the launch with
                     # its arguments bound beforehand
                     self.T_wl, T_cw = o.PoseStep(self.T_wl, T_lp)
@@ -403,6 +457,9 @@ class TrackingPipeline(FramePipeline):
 
     def _fuse_at(self, T_wl):
         T_cw = self.tracking.se3_inv(T_wl)[:3].astype(np.float32)
+        if self.color:
+            self._fuse_color(self.kin_d[0], self.kin_n[0], T_cw)
+            return
         self._timed_fuse(lambda kw: self.ops.SdfFuse(self.vol, self.kin_d[0], self.kin_n[0], T_cw, self.K, self.trunc, self.max_w,
                                                      self.mincostheta, **kw))
 
@@ -412,6 +469,8 @@ class TrackingPipeline(FramePipeline):
             self.ops.SdfReset(self.vol, float("nan"), summary=self.summary)
         else:
             self.ops.SdfReset(self.vol, float("nan"))
+        if self.color:
+            self.ops.ColorReset(self.cvol)
 
 
 def slab_range(d, rank, world):
@@ -513,6 +572,8 @@ class SlabPipeline(FramePipeline):
         assert driver in ("python", "c")
         self.driver, self.sframe, self.comm = driver, None, comm
         timing_slots = kw.pop("timing_slots", None)
+        if kw.get("color"):
+            raise ValueError("SlabPipeline: colour mode is not built for Z-slabs")
         super().__init__(ops, dims, boxmin, boxmax, w, h, **kw)
         if driver == "c":
             if raycast == "exact_allreduce" or images != "all" or kind != "f32":

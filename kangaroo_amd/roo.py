@@ -679,23 +679,55 @@ def PoseRefinementProjectiveIcpPointPlane(dPl, dPr, dNr, KT_lr, T_rl, c, dWorksp
     return LeastSquaresSystem(list(out.JTy), list(out.JTJ), out.sqErr, out.obs)
 
 
-def SdfFuseColor(vol, colorVol, depth, norm, T_cw, K, img, T_iw, Kimg, trunc_dist, max_w, mincostheta, full_extent=False, stream=None):
+def SdfFuseColor(vol, colorVol, depth, norm, T_cw, K, img, T_iw, Kimg, trunc_dist, max_w, mincostheta, full_extent=False, stream=None, summary=None):
     """SdfFuse(vol, colorVol, depth, norm, T_cw, K, img, T_iw, Kimg, trunc_dist, max_w, mincostheta)
-    (cu_sdffusion.h colour overload, cu_sdffusion.cu:70-138).  colorVol: BoundedVolume(kind="c32"), img: Image("u8x3")."""
+    (cu_sdffusion.h colour overload, cu_sdffusion.cu:70-138).  colorVol: BoundedVolume(kind="c32"), img: Image("u8x3").
+    summary: keep this SdfSummary current (kfx_sdf_fuse_color_tracked, same SDF and colour bits)."""
     t, _t = _fp(T_cw, 12)
     k, _k = _fp(K, 4)
     ti, _ti = _fp(T_iw, 12)
     ki, _ki = _fp(Kimg, 4)
+    if summary is not None:
+        _lib.check(_lib.load().kfx_sdf_fuse_color_tracked(vol.ref(), colorVol.ref(), summary.handle, depth.ref(), norm.ref(), t, k, img.ref(), ti, ki,
+                                                          trunc_dist, max_w, mincostheta, 1 if full_extent else 0, _stream(stream)))
+        return
     _lib.check(_lib.load().kfx_sdf_fuse_color(vol.ref(), colorVol.ref(), depth.ref(), norm.ref(), t, k, img.ref(), ti, ki, trunc_dist,
                                               max_w, mincostheta, 1 if full_extent else 0, _stream(stream)))
 
 
-def RaycastSdfColor(depth, norm, img, vol, colorVol, T_wc, K, near, far, trunc_dist, subpix=True, stream=None):
-    """RaycastSdf(depth, norm, img, vol, colorVol, T_wc, K, near, far, trunc_dist, subpix) (cu_raycast.cu:119-196)."""
+def RaycastColorHits(outputs, colorVol, T_wc, K_levels, stream=None):
+    """kfx_raycast_color_hits: the colour image of renderings that were already marched.  outputs = [(depth, img), ...] per
+    level; every pixel with depth > 0 gets colorVol's trilinear sample at its hit, the others are left alone."""
+    n = len(outputs)
+    assert n == len(K_levels)
+    views = [[o[k].view() for o in outputs] for k in range(2)]   # KfxImage structs, kept alive over the call
+    ptrs = [(_lib.PI * n)(*[C.pointer(v) for v in views[k]]) for k in range(2)]
+    t, _t = _fp(T_wc, 12)
+    k, _k = _fp(np.concatenate([np.asarray(K, np.float32).reshape(4) for K in K_levels]) if n else np.zeros(0, np.float32), 4 * n)
+    _lib.check(_lib.load().kfx_raycast_color_hits(n, ptrs[0], ptrs[1], colorVol.ref(), t, k, _stream(stream)))
+
+
+def RaycastSdfColor(depth, norm, img, vol, colorVol, T_wc, K, near, far, trunc_dist, subpix=True, stream=None, summary=None):
+    """RaycastSdf(depth, norm, img, vol, colorVol, T_wc, K, near, far, trunc_dist, subpix) (cu_raycast.cu:119-196).
+    summary: the march through this SdfSummary's class tables (RaycastSdf(..., summary=)) followed by the colour pass
+    (RaycastColorHits): in exact numerics the same three images bit for bit.  None: the single launch with the colour in the march."""
+    if summary is not None:
+        RaycastSdf(depth, norm, img, vol, T_wc, K, near, far, trunc_dist, subpix, stream, summary=summary)
+        RaycastColorHits([(depth, img)], colorVol, T_wc, [K], stream)
+        return
     t, _t = _fp(T_wc, 12)
     k, _k = _fp(K, 4)
     _lib.check(_lib.load().kfx_raycast_sdf_color(depth.ref(), norm.ref(), img.ref(), vol.ref(), colorVol.ref(), t, k, near, far,
                                                  trunc_dist, 1 if subpix else 0, _stream(stream)))
+
+
+def RaycastSdfColorLevels(outputs, vol, colorVol, T_wc, K_levels, near, far, trunc_dist, subpix=True, stream=None, summary=None):
+    """The colour renderings of every pyramid level (main.cpp:280-288 in the fuse_color branch) in two launches: RaycastSdfLevels
+    (with the summary, if given) plus the colour pass.  outputs as RaycastSdfLevels'; images identical to per-level
+    RaycastSdfColor calls of the same numerics mode."""
+    RaycastSdfLevels(outputs, vol, T_wc, K_levels, near, far, trunc_dist, subpix, stream, summary=summary)
+    if len(outputs):
+        RaycastColorHits([(o[0], o[2]) for o in outputs], colorVol, T_wc, K_levels, stream)
 
 
 def ColorReset(colorVol, stream=None):

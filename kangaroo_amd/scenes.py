@@ -102,3 +102,19 @@ def render_depth(scene, w, h, T_wc=None, K=None, noise_sigma=0.0, seed=1234):
         rng = np.random.default_rng(seed)
         d = (d + rng.normal(0.0, noise_sigma, d.shape).astype(np.float32)).astype(np.float32)
     return np.ascontiguousarray(d)
+
+
+def render_rgb(scene, w, h, T_wi=None, Kimg=None):
+    """The colour camera's view of the synthetic scenes: uint8 (h, w, 3).  The albedo is a fixed, smooth, view-independent
+    function of the world hit point P (metres): r, g, b = round(127.5 + 100 sin(5 P + phi)) with P's x, y, z and
+    phi = 1, 2, 3.  Pixels that see nothing are (0, 0, 0)."""
+    K = intrinsics(w, h) if Kimg is None else np.asarray(Kimg, np.float32)
+    T = identity_pose() if T_wi is None else np.asarray(T_wi, np.float32).reshape(3, 4)
+    d = render_depth(scene, w, h, T, K).astype(np.float64)
+    u = np.arange(w, dtype=np.float64)[None, :]
+    v = np.arange(h, dtype=np.float64)[:, None]
+    rc = np.stack(np.broadcast_arrays((u - K[2]) / K[0], (v - K[3]) / K[1], 1.0), -1)
+    P = T[:, 3].astype(np.float64) + (rc @ T[:, :3].T.astype(np.float64)) * d[..., None]
+    hit = np.isfinite(d)
+    rgb = np.rint(127.5 + 100.0 * np.sin(5.0 * np.where(hit[..., None], P, 0.0) + np.array([1.0, 2.0, 3.0])))
+    return np.ascontiguousarray(np.where(hit[..., None], rgb, 0.0).astype(np.uint8))
