@@ -9,6 +9,11 @@
 //   --transport threads  --ranks R host threads of this process share one GPU (emulation: exercises the same slab code on
 //                        a 1-GPU box; not a performance mode)
 //
+//   --color              the reference application's fuse_color mode on the slabs (include/kfx_slab_color.h): a synthetic RGB stream as in
+//                        kinectfusion_headless --color, a colour slab beside every rank's SDF slab, the colour SdfFuse, colour
+//                        renderings, colours in --save-mesh; ` colour=` at the end of the checksum line is the checksum of the whole
+//                        colour volume (the owned planes of all ranks)
+//
 // Rank 0 prints the frame time and checksums of the final raycast images and of the whole volume (sum of the owned cells'
 // bit patterns over all ranks): with --raycast exact they equal the checksums of a --ranks 1 run bit for bit.
 #include <chrono>
@@ -42,6 +47,7 @@ struct Options {
     SlabVolume::MergeMode merge = SlabVolume::MergeDirect;
     std::string rendezvous;   // default: /tmp/kfx_slabs.<uid>.<launch id>.id (default_rendezvous)
     std::string save_mesh;    // --save-mesh PREFIX: after the last frame every rank writes its part of the mesh as PREFIX.r<rank>.ply
+    bool color = false;       // --color: colour volume, colour SdfFuse, colour renderings
 };
 
 // analytic depth of the synthetic room: same scene as kinectfusion_headless.cpp / kangaroo_amd/scenes.py
@@ -68,6 +74,50 @@ static void RenderRoom(std::vector<float>& out, int w, int h, const Mat<float,3,
         }
 }
 
+// the colour camera's view of the same room (kinectfusion_headless.cpp, kangaroo_amd/scenes.py render_rgb): the albedo at the hit point
+// P (metres), r, g, b = round(127.5 + 100 sin(5 P + phi)) with P's x, y, z and phi = 1, 2, 3; (0, 0, 0) where the ray sees nothing
+static void RenderRoomRgb(std::vector<uchar3>& out, int w, int h, const Mat<float,3,4>& T_wi, const ImageIntrinsics& Kimg)
+{
+    std::vector<float> depth;
+    RenderRoom(depth, w, h, T_wi, Kimg);
+    out.resize((size_t)w * h);
+    const float3 c = SE3Translation(T_wi);
+    for (int v = 0; v < h; ++v)
+        for (int u = 0; u < w; ++u) {
+            const float d = depth[(size_t)v * w + u];
+            uchar3 px = make_uchar3(0, 0, 0);
+            if (std::isfinite(d)) {
+                const float3 r = mulSO3(T_wi, Kimg.Unproject((float)u, (float)v));
+                const double P[3] = {(double)c.x + (double)r.x * d, (double)c.y + (double)r.y * d, (double)c.z + (double)r.z * d};
+                px.x = (unsigned char)std::lrint(127.5 + 100.0 * std::sin(5.0 * P[0] + 1.0));
+                px.y = (unsigned char)std::lrint(127.5 + 100.0 * std::sin(5.0 * P[1] + 2.0));
+                px.z = (unsigned char)std::lrint(127.5 + 100.0 * std::sin(5.0 * P[2] + 3.0));
+            }
+            out[(size_t)v * w + u] = px;
+        }
+}
+
+// colour <- depth camera: 25 mm beside it (kinectfusion_headless.cpp)
+static Mat<float,3,4> ColourFromDepth()
+{
+    Mat<float,3,4> T_cd = SE3Identity();
+    T_cd(0,3) = 0.025f; T_cd(1,3) = -0.003f; T_cd(2,3) = 0.002f;
+    return T_cd;
+}
+// T_iw = T_cd * T_cw in float, the sums in index order: what kfx_slab_frame_step evaluates (include/kfx_slab_color.h), so both drivers
+// integrate at the same colour pose
+static Mat<float,3,4> ColourPose(const Mat<float,3,4>& T_cd, const Mat<float,3,4>& T_cw)
+{
+    Mat<float,3,4> T;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 4; ++j) {
+            float a = 0.f;
+            for (int k = 0; k < 3; ++k) a += T_cd(i,k) * T_cw(k,j);
+            T(i,j) = j == 3 ? a + T_cd(i,3) : a;
+        }
+    return T;
+}
+
 static Mat<float,3,4> OrbitPose(int i, int n)
 {
     const float ph = 2.0f * (float)M_PI * i / n;
@@ -88,12 +138,12 @@ static unsigned BitSum(const void* p, size_t bytes)
     return s;
 }
 
-struct Result { double ms_per_frame = 0; unsigned chk_d = 0, chk_n = 0, chk_i = 0, chk_vol = 0, chk_hist = 0; size_t hits = 0; int rounds = 0; int status = 0;
+struct Result { double ms_per_frame = 0; unsigned chk_d = 0, chk_n = 0, chk_i = 0, chk_vol = 0, chk_hist = 0, chk_col = 0; size_t hits = 0; int rounds = 0; int status = 0;
                 size_t mesh_tris = 0; };
 
 // the frame loop of one rank
-static void RunRank(const Options& o, kfx_comm* comm, const std::vector<std::vector<float> >& depth_mm, const std::vector<Mat<float,3,4> >& poses,
-                    Result* res)
+static void RunRank(const Options& o, kfx_comm* comm, const std::vector<std::vector<float> >& depth_mm, const std::vector<std::vector<uchar3> >& rgb,
+                    const std::vector<Mat<float,3,4> >& poses, Result* res)
 {
     const int w = o.w, h = o.h;
     const double depth_focal = w * 570.342 / 640.0;
@@ -122,6 +172,12 @@ static void RunRank(const Options& o, kfx_comm* comm, const std::vector<std::vec
     slab.merge = o.merge;
     slab.tiles = o.tiles;
     SdfReset(slab.local, std::numeric_limits<float>::quiet_NaN());
+    // --color: this rank's planes of the colour volume (reset to 0.5), the frame's RGB image, the colour camera (the depth camera's
+    // intrinsics, T_cd beside it)
+    if (o.color) slab.EnableColor();
+    Image<uchar3, TargetDevice, Manage> drgb(w, h);
+    const ImageIntrinsics Kimg = K;
+    const Mat<float,3,4> T_cd = ColourFromDepth();
 
     // --driver frame: the same frame as ONE library call per rank (kfx_slab_frame, include/kfx_slab.h)
     kfx_slab_frame* kframe = nullptr;
@@ -153,6 +209,10 @@ static void RunRank(const Options& o, kfx_comm* comm, const std::vector<std::vec
             }
         }
         GpuCheckStatus(kfx_slab_frame_create(&kframe, &fc, comm));
+        if (o.color) {
+            const float Ki[4] = {(float)Kimg.fu, (float)Kimg.fv, (float)Kimg.u0, (float)Kimg.v0};
+            GpuCheckStatus(kfx_slab_frame_set_color(kframe, slab.color->abi(), drgb.abi(), Ki, T_cd.m));
+        }
     }
     // every frame's rendered depth image, kept on the device (one row-block per frame): `history` in the output is a checksum over ALL
     // frames' renderings, not only the last one's
@@ -165,9 +225,14 @@ static void RunRank(const Options& o, kfx_comm* comm, const std::vector<std::vec
         // frame), the frames are stepped back to back -- no synchronisation, no barrier -- and the rendering of frame k is picked up
         // when frame k + D is about to take its image set.
         std::vector<std::unique_ptr<Image<float, TargetDevice, Manage> > > dmm(o.frames);
+        std::vector<std::unique_ptr<Image<uchar3, TargetDevice, Manage> > > drgbs(o.color ? o.frames : 0);
         for (int f = 0; f < o.frames; ++f) {
             dmm[f].reset(new Image<float, TargetDevice, Manage>(w, h));
             dmm[f]->MemcpyFromHost(const_cast<float*>(depth_mm[f].data()));
+            if (o.color) {
+                drgbs[f].reset(new Image<uchar3, TargetDevice, Manage>(w, h));
+                drgbs[f]->MemcpyFromHost(const_cast<uchar3*>(rgb[f].data()));
+            }
         }
         kfx_stream_synchronize(0);
         comm->barrier(comm);
@@ -181,6 +246,7 @@ static void RunRank(const Options& o, kfx_comm* comm, const std::vector<std::vec
                 keep(f - D, d);
             }
             ElementwiseScaleBias<float,float,float>(dMeters, *dmm[f], 1.0f / 1000.0f);
+            if (o.color) drgb.CopyFrom(*drgbs[f]);   // (a device copy in stream order: behind the SdfFuse of frame f - 1, which read the image)
             const Mat<float,3,4> T_cw = SE3inv(poses[f]);
             GpuCheckStatus(kfx_slab_frame_step(kframe, 0, poses[f].m, T_cw.m, 0, 0));
         }
@@ -208,6 +274,7 @@ static void RunRank(const Options& o, kfx_comm* comm, const std::vector<std::vec
     for (int f = 0; f < o.frames && !piped; ++f) {
         const Mat<float,3,4> T_wl = poses[f];
         dMeters.MemcpyFromHost(const_cast<float*>(depth_mm[f].data()));
+        if (o.color) drgb.MemcpyFromHost(const_cast<uchar3*>(rgb[f].data()));
         comm->barrier(comm);
         const auto t0 = std::chrono::steady_clock::now();
         if (kframe) {
@@ -228,7 +295,8 @@ static void RunRank(const Options& o, kfx_comm* comm, const std::vector<std::vec
             NormalsFromVbo(dNormals, dVbo);
         }
         if (o.broadcast_inputs) slab.BroadcastInputs(dFiltered, dNormals, 0);
-        slab.Fuse(dFiltered, dNormals, SE3inv(T_wl), K, trunc_dist, max_w, mincostheta);
+        if (o.color) slab.Fuse(dFiltered, dNormals, SE3inv(T_wl), K, drgb, ColourPose(T_cd, SE3inv(T_wl)), Kimg, trunc_dist, max_w, mincostheta);
+        else slab.Fuse(dFiltered, dNormals, SE3inv(T_wl), K, trunc_dist, max_w, mincostheta);
         slab.Raycast(ray_d, ray_n, ray_i, T_wl, K, knear, kfar, trunc_dist, true);
         kfx_stream_synchronize(0);
         comm->barrier(comm);
@@ -273,15 +341,31 @@ static void RunRank(const Options& o, kfx_comm* comm, const std::vector<std::vec
                 vs_sum += bits * 2654435761u + (unsigned)((L.z0 + z) * 7919u + y * 104729u + x);
             }
         }
+    unsigned col_sum = 0;   // --color: the same over the owned planes of the colour volume
+    if (o.color) {
+        const size_t cplane = slab.color->img_pitch;
+        std::vector<unsigned char> hc(cplane * own);
+        GpuCheckStatus(kfx_memcpy_2d(hc.data(), cplane, (unsigned char*)slab.color->ptr + (L.z0 - L.s0) * cplane, cplane, cplane, own, 2, 0));
+        for (size_t z = 0; z < own; ++z)
+            for (size_t y = 0; y < slab.color->h; ++y) {
+                const unsigned* row = reinterpret_cast<const unsigned*>(hc.data() + z * cplane + y * slab.color->pitch);
+                for (size_t x = 0; x < slab.color->w; ++x) {
+                    unsigned bits = row[x];
+                    if ((bits & 0x7fffffffu) > 0x7f800000u) bits = 0x7fc00000u;   // any NaN
+                    col_sum += bits * 2654435761u + (unsigned)((L.z0 + z) * 7919u + y * 104729u + x);
+                }
+            }
+    }
     void* dsum = nullptr;
     size_t pitch;
     GpuCheckStatus(kfx_alloc_pitched(&dsum, &pitch, 64, 1));
-    int hsum[2] = {(int)vs_sum, 0};
+    int hsum[2] = {(int)vs_sum, (int)col_sum};
     GpuCheckStatus(kfx_memcpy_2d(dsum, 64, hsum, 8, 8, 1, 1, 0));
     GpuCheckStatus(comm->all_reduce(comm, dsum, 2, KFX_COMM_SUM_I32, 0));
     GpuCheckStatus(kfx_memcpy_2d(hsum, 8, dsum, 64, 8, 1, 2, 0));
     kfx_free(dsum);
     res->chk_vol = (unsigned)hsum[0];
+    res->chk_col = (unsigned)hsum[1];
     if (!o.save_mesh.empty())   // this rank's cubes; the ghost planes the normals read are current after the last fuse
         res->mesh_tris = slab.SaveMesh(o.save_mesh + ".r" + std::to_string(comm->rank));
 }
@@ -311,6 +395,7 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--ghost") && i + 1 < argc) { ++i; o.ghost = !strcmp(argv[i], "auto") ? -1 : atoi(argv[i]); }
         else if (!strcmp(argv[i], "--overlap")) o.overlap = true;
         else if (!strcmp(argv[i], "--save-mesh") && i + 1 < argc) o.save_mesh = argv[++i];
+        else if (!strcmp(argv[i], "--color") || !strcmp(argv[i], "--colour")) o.color = true;
         else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
     const int ndev = kfx_device_count();
@@ -326,6 +411,8 @@ int main(int argc, char** argv)
         RenderRoom(depth_mm[f], o.w, o.h, poses[f], K);
         for (float& d : depth_mm[f]) d *= 1000.0f;
     }
+    std::vector<std::vector<uchar3> > rgb(o.color ? o.frames : 0);
+    for (int f = 0; f < (int)rgb.size(); ++f) RenderRoomRgb(rgb[f], o.w, o.h, SE3inv(ColourPose(ColourFromDepth(), SE3inv(poses[f]))), K);
 
     Result r0;
     int world = o.ranks, rank = 0;
@@ -344,7 +431,7 @@ int main(int argc, char** argv)
         kfx_comm comm;
         const int st = kfx_comm_create_rccl(&comm, rank, world, o.rendezvous.c_str(), 120);
         if (st != 0) { fprintf(stderr, "kfx_comm_create_rccl failed: %d\n", st); return 3; }
-        RunRank(o, &comm, depth_mm, poses, &r0);
+        RunRank(o, &comm, depth_mm, rgb, poses, &r0);
         comm.destroy(&comm);
     } else {
         std::vector<kfx_comm> comms(world);
@@ -352,8 +439,8 @@ int main(int argc, char** argv)
         else GpuCheckStatus(kfx_comm_create_threads(comms.data(), world));
         std::vector<Result> results(world);
         std::vector<std::thread> threads;
-        for (int r = 1; r < world; ++r) threads.emplace_back(RunRank, std::cref(o), &comms[r], std::cref(depth_mm), std::cref(poses), &results[r]);
-        RunRank(o, &comms[0], depth_mm, poses, &results[0]);
+        for (int r = 1; r < world; ++r) threads.emplace_back(RunRank, std::cref(o), &comms[r], std::cref(depth_mm), std::cref(rgb), std::cref(poses), &results[r]);
+        RunRank(o, &comms[0], depth_mm, rgb, poses, &results[0]);
         for (auto& t : threads) t.join();
         r0 = results[0];
         for (int r = 1; r < world; ++r) r0.mesh_tris += results[r].mesh_tris;
@@ -366,8 +453,10 @@ int main(int argc, char** argv)
                o.volres, world, o.rccl ? "RCCL, one process per GPU" : "threads sharing one GPU", o.frame_driver ? "; one kfx_slab_frame_step per frame" : "", o.w, o.h, o.frames, o.fast ? "fast" : "exact",
                o.halo == SlabVolume::HaloExchange ? "exchange" : "recompute", o.raycast == SlabVolume::Exact ? "exact (hand-over)" : (o.raycast == SlabVolume::ExactAllReduce ? "exact (all-reduce per round)" : (o.merge == SlabVolume::MergeDirect ? "composite (direct-send merge)" : "composite (all-reduce merge)")),
                o.raycast != SlabVolume::Composite ? (" (" + std::to_string(r0.rounds) + " rounds)").c_str() : "", r0.ms_per_frame, 1e3 / r0.ms_per_frame);
-        printf("checksums depth=%08x norm=%08x img=%08x volume=%08x history=%08x hits=%zu ranks_agree=%d%s\n", r0.chk_d, r0.chk_n, r0.chk_i, r0.chk_vol, r0.chk_hist,
-               r0.hits, r0.status == 0 ? 1 : 0, o.pipeline ? (" pipeline=" + std::to_string(o.pipeline)).c_str() : "");
+        char colour[32] = "";
+        if (o.color) snprintf(colour, sizeof(colour), " colour=%08x", r0.chk_col);
+        printf("checksums depth=%08x norm=%08x img=%08x volume=%08x history=%08x hits=%zu ranks_agree=%d%s%s\n", r0.chk_d, r0.chk_n, r0.chk_i, r0.chk_vol, r0.chk_hist,
+               r0.hits, r0.status == 0 ? 1 : 0, o.pipeline ? (" pipeline=" + std::to_string(o.pipeline)).c_str() : "", colour);
         if (!o.save_mesh.empty())
             printf("mesh: %zu triangles written to %s.r<rank>.ply%s\n", r0.mesh_tris, o.save_mesh.c_str(), o.rccl ? " (rank 0's part)" : "");
     }

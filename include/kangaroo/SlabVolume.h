@@ -9,9 +9,15 @@
 //   per frame:  slab.Fuse(depth, normals, T_cw, K, trunc, max_w, mincostheta);           // + halo exchange
 //               slab.Raycast(d, n, i, T_wc, K, near, far, trunc);                        // identical images on every rank
 //   at the end: slab.SaveMesh("mesh.r" + std::to_string(rank));                         // this rank's part of the mesh
+// Colour mode (the reference application's fuse_color, include/kfx_slab_color.h): slab.EnableColor() allocates this rank's planes of the
+// colour volume beside `local` (same planes, same box; reset to 0.5); the colour overload of Fuse integrates both, Raycast then renders
+// the colour volume into img, and SaveMesh writes colours -- all bit-identical to the single-volume colour operators.
 #pragma once
 
+#include <memory>
+
 #include <kfx_slab.h>
+#include <kfx_slab_color.h>
 
 #include <kangaroo/BoundedVolume.h>
 #include <kangaroo/Image.h>
@@ -37,6 +43,7 @@ public:
 
     kfx_slab_layout layout;
     BoundedVolume<SDF_t, TargetDevice, Manage> local; // planes [layout.s0, layout.s1) of the whole volume
+    std::unique_ptr<BoundedVolume<float, TargetDevice, Manage> > color;   // the same planes of the colour volume (EnableColor), else null
     BoundingBox full_bbox;
     kfx_comm* comm;
     HaloMode halo;
@@ -61,6 +68,15 @@ public:
     SlabVolume(const SlabVolume&) = delete;
     SlabVolume& operator=(const SlabVolume&) = delete;
 
+    // the colour slab beside the SDF slab: the dimensions and the box of `local`, SdfReset(colorVol) = 0.5
+    void EnableColor()
+    {
+        if (color) return;
+        color.reset(new BoundedVolume<float, TargetDevice, Manage>(local.w, local.h, local.d, local.bbox));
+        GpuCheckStatus(kfx_color_reset(color->abi(), 0));
+    }
+    bool HasColor() const { return (bool)color; }
+
     // SdfFuse of this rank's planes, evaluated with the whole volume's voxel positions and over the whole volume's
     // extents (bit-identical to the same planes of a single-GPU volume), then the ghost planes are brought up to date
     void Fuse(Image<float> depth, Image<float4> norm, Mat<float,3,4> T_cw, ImageIntrinsics K, float trunc_dist, float maxw, float mincostheta)
@@ -75,6 +91,27 @@ public:
         if (own_only) GpuCheckStatus(kfx_slab_exchange_halos(local.abi(), &layout, comm, 0));
     }
 
+    // ... and the colour SdfFuse (SdfFuse(vol, colorVol, ...), cu_sdffusion.h) on the two slabs; with HaloExchange the colour volume's
+    // ghost planes follow the SDF volume's (the same order on every rank).  Needs EnableColor().
+    void Fuse(Image<float> depth, Image<float4> norm, Mat<float,3,4> T_cw, ImageIntrinsics K, Image<uchar3> img, Mat<float,3,4> T_iw,
+              ImageIntrinsics Kimg, float trunc_dist, float maxw, float mincostheta)
+    {
+        EnableColor();
+        const bool own_only = halo == HaloExchange && layout.world > 1;
+        const size_t first = own_only ? layout.z0 : layout.s0, count = own_only ? layout.z1 - layout.z0 : layout.s1 - layout.s0;
+        kfx_volume v = *local.abi(), c = *color->abi();
+        v.ptr = (unsigned char*)v.ptr + (first - layout.s0) * v.img_pitch;
+        c.ptr = (unsigned char*)c.ptr + (first - layout.s0) * c.img_pitch;
+        v.d = c.d = count;
+        const kfx_slab s = {layout.full_d, first, layout.full_zmin, layout.full_zmax};
+        GpuCheckStatus(kfx_sdf_fuse_color_slab(&v, &c, &s, depth.abi(), norm.abi(), T_cw.m, &K.fu, img.abi(), T_iw.m, &Kimg.fu, trunc_dist, maxw, mincostheta,
+                                               KFX_FUSE_SLAB_EXTENT, 0));
+        if (own_only) {
+            GpuCheckStatus(kfx_slab_exchange_halos(local.abi(), &layout, comm, 0));
+            GpuCheckStatus(kfx_slab_exchange_halos(color->abi(), &layout, comm, 0));
+        }
+    }
+
     // Input distribution (the alternative to every rank preprocessing the frame itself): rank `root` holds the filtered depth
     // and the normal map, afterwards every rank does
     void BroadcastInputs(Image<float> depth, Image<float4> norm, int root = 0)
@@ -83,12 +120,27 @@ public:
         GpuCheckStatus(kfx_slab_broadcast_inputs(depth.abi(), norm.abi(), payload_, root, comm, 0));   // payload_: 20 B per pixel
     }
 
-    // RaycastSdf of the whole model; every rank returns with the same images
+    // RaycastSdf of the whole model; every rank returns with the same images.  With a colour slab (EnableColor) img is the colour
+    // rendering, RaycastSdf(depth, norm, img, vol, colorVol, ...): Composite renders each local view in colour and merges as ever; Exact
+    // hands the march over in row-tiles (one tile where `tiles` is 0: the whole-image stages have no colour form), and so does
+    // ExactAllReduce (the grey hand-over's cross-check has none either).
     void Raycast(Image<float> depth, Image<float4> norm, Image<float> img, Mat<float,3,4> T_wc, ImageIntrinsics K, float near, float far,
                  float trunc_dist, bool subpix = true)
     {
         Reserve(depth.w * depth.h);
-        if (raycast == Exact && tiles > 0) {
+        const int tiles = (color && raycast != Composite && this->tiles < 1) ? 1 : this->tiles;
+        if (color && raycast != Composite) {
+            const size_t need = kfx_slab_exact_tiled_scratch_bytes(depth.w, depth.h, tiles, comm->world);
+            if (need > tiled_cap_) {
+                size_t pitch;
+                kfx_free(tiled_);
+                tiled_ = 0; tiled_cap_ = 0;
+                GpuCheckStatus(kfx_alloc_pitched(&tiled_, &pitch, need, 1));
+                tiled_cap_ = need;
+            }
+            GpuCheckStatus(kfx_slab_raycast_exact_tiled_color(depth.abi(), norm.abi(), img.abi(), tiled_, local.abi(), color->abi(), &layout, T_wc.m, &K.fu, near,
+                                                              far, trunc_dist, subpix ? 1 : 0, tiles, comm, 0, 0, &last_rounds));
+        } else if (raycast == Exact && tiles > 0) {
             const size_t need = kfx_slab_exact_tiled_scratch_bytes(depth.w, depth.h, tiles, comm->world);
             if (need > tiled_cap_) {
                 size_t pitch;
@@ -106,7 +158,8 @@ public:
             GpuCheckStatus(kfx_slab_raycast_exact_allreduce(depth.abi(), norm.abi(), img.abi(), (float*)state_, scratch_, local.abi(), &layout, T_wc.m,
                                                             &K.fu, near, far, trunc_dist, subpix ? 1 : 0, comm, 0, &last_rounds));
         } else {
-            RaycastSdf(depth, norm, img, local, T_wc, K, near, far, trunc_dist, subpix);
+            if (color) RaycastSdf(depth, norm, img, local, *color, T_wc, K, near, far, trunc_dist, subpix);
+            else RaycastSdf(depth, norm, img, local, T_wc, K, near, far, trunc_dist, subpix);
             if (merge == MergeDirect && comm->all_to_all && comm->all_gather) {
                 const size_t need = kfx_slab_composite_direct_scratch_bytes(depth.w, depth.h, comm->world);
                 if (need > strips_cap_) {
@@ -124,12 +177,14 @@ public:
     }
 
     // SaveMesh of this rank's part: the cubes whose lower plane it owns, every triangle bit-identical to the single-volume mesh's,
-    // in emission order (include/kfx_mesh.h; the ghost planes must be current: Fuse leaves them so).  Writes filename + ".ply", no
-    // colour; returns the triangle count.
+    // in emission order (include/kfx_mesh.h; the ghost planes must be current: Fuse leaves them so).  Writes filename + ".ply", with
+    // the single-volume mesh's colours where the slab has a colour volume (as SaveMesh(filename, vol, volColor): when the whole colour
+    // volume IsValid()); returns the triangle count.
     size_t SaveMesh(std::string filename)
     {
         const kfx_slab s = {layout.full_d, layout.s0, layout.full_zmin, layout.full_zmax};
-        const mesh_detail::HostMesh m = mesh_detail::Extract(local.abi(), KFX_CELL_F32, &s, (int)layout.z0, (int)layout.z1, nullptr);
+        const bool with_color = color && local.w >= 8 && local.h >= 8 && layout.full_d >= 8;
+        const mesh_detail::HostMesh m = mesh_detail::Extract(local.abi(), KFX_CELL_F32, &s, (int)layout.z0, (int)layout.z1, with_color ? color->abi() : nullptr);
         return mesh_detail::WritePly(filename + ".ply", m);
     }
 

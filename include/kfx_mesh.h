@@ -20,8 +20,10 @@
  *            bit-identical to the same cube's triangle in the single-volume mesh, and cube_index is the global index.  The stored
  *            planes must cover [own_lo - 2, own_hi + 2) within [0, full_d) -- the corners' planes z, z + 1 and the normals' gradient
  *            stencil (base plane clamp(floor(vertex z), 1, full_d - 2) and one plane either side) -- so a ghost of 2 planes per
- *            side suffices; otherwise KFX_E_RANGE before any launch.  Slab meshes carry no colour.
- *   colorvol a BoundedVolume<float>; sampled only when it IsValid() (every dimension >= 8) and `colors` is not null.
+ *            side suffices (a vertex's colour reads planes up to z + 2, inside the stencil's); otherwise KFX_E_RANGE before any launch.
+ *   colorvol a BoundedVolume<float>; sampled only when it IsValid() (every dimension >= 8) and `colors` is not null.  With a slab
+ *            (fp32 cells): the rank's colour slab -- the same planes of a colour volume with the SDF volume's dimensions and box, so
+ *            it has the w, h, d and box of `vol` (KFX_E_SHAPE otherwise); colours equal the single volume's bit for bit.
  *   scratch  device memory of kfx_mesh_scratch_bytes() bytes, 256-byte aligned: the per-segment counts (2 bytes each) and the
  *            scan's block sums and offsets.  The library never allocates.  2048^3 cells, whole volume: 274 460 416 bytes (512^3: 4 277 504).
  *

@@ -61,7 +61,7 @@ class KfxError(RuntimeError):
 
 PI, PV, PF = C.POINTER(KfxImage), C.POINTER(KfxVolume), C.POINTER(C.c_float)
 
-# name -> (restype, argtypes); every symbol include/kfx.h declares (and kfx_summary_h.h, kfx_mesh.h, kfx_color.h)
+# name -> (restype, argtypes); every symbol include/kfx.h declares (and kfx_summary_h.h, kfx_mesh.h, kfx_color.h, kfx_slab_color.h)
 SIGNATURES = {
     "kfx_sdf_fuse": (C.c_int, [PV, PI, PI, PF, PF, C.c_float, C.c_float, C.c_float, C.c_uint, C.c_void_p]),
     "kfx_sdf_fuse_slab": (C.c_int, [PV, C.POINTER(KfxSlab), PI, PI, PF, PF, C.c_float, C.c_float, C.c_float, C.c_uint, C.c_void_p]),
@@ -98,6 +98,16 @@ SIGNATURES = {
     "kfx_color_reset": (C.c_int, [PV, C.c_void_p]),
     "kfx_sdf_fuse_color_tracked": (C.c_int, [PV, PV, C.c_void_p, PI, PI, PF, PF, PI, PF, PF, C.c_float, C.c_float, C.c_float, C.c_uint, C.c_void_p]),
     "kfx_raycast_color_hits": (C.c_int, [C.c_int, C.POINTER(PI), C.POINTER(PI), PV, PF, PF, C.c_void_p]),
+    # include/kfx_slab_color.h (kfx_slab_layout*, kfx_comm* and the frame handle as void*: kangaroo_amd/slab.py owns those types)
+    "kfx_sdf_fuse_color_slab": (C.c_int, [PV, PV, C.POINTER(KfxSlab), PI, PI, PF, PF, PI, PF, PF, C.c_float, C.c_float, C.c_float, C.c_uint, C.c_void_p]),
+    "kfx_raycast_sdf_slab_color": (C.c_int, [C.c_void_p, C.c_int, PV, PV, C.POINTER(KfxSlab), C.c_int, C.c_int, C.c_int, C.c_int, PF, PF,
+                                             C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p]),
+    "kfx_raycast_sdf_slab_tiles_color": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                   C.c_int, PV, PV, C.POINTER(KfxSlab), C.c_int, C.c_int, C.c_int, C.c_int, PF, PF, C.c_float, C.c_float, C.c_float,
+                                                   C.c_int, C.c_void_p]),
+    "kfx_slab_raycast_exact_tiled_color": (C.c_int, [PI, PI, PI, C.c_void_p, PV, PV, C.c_void_p, PF, PF, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int,
+                                                     C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "kfx_slab_frame_set_color": (C.c_int, [C.c_void_p, PV, PI, PF, PF]),
     "kfx_depth_to_vbo_normals_f32": (C.c_int, [PI, PI, PI, PF, C.c_float, C.c_void_p]),
     "kfx_depth_pyramid_vbo_normals_f32": (C.c_int, [PI, PI, PI, PF, C.c_int, C.c_float, C.c_void_p]),
     "kfx_bilateral_guided_f32": (C.c_int, [PI, PI, PI, C.c_float, C.c_float, C.c_float, C.c_uint, C.c_void_p]),

@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "kfx_device.h"
+#include "../../include/kfx_slab_color.h"
 #include "host_args.h"
 
 // The tiled kernels stage their pixel rectangle by LDS-DMA from a packed texel image (round 6: k_pack_texels / the fused preprocess of
@@ -1362,7 +1363,7 @@ __global__ __launch_bounds__(256) void k_sdf_fuse_color(const FuseParams p, cons
     const int y = blockIdx.y * FUSE_ROWS + wv;
     const int zbeg = blockIdx.z * FUSE_ZC;
     const int zend = min(zbeg + FUSE_ZC, p.Z);
-    if (threadIdx.x < FUSE_ZC) s_pz[threadIdx.x] = slice_z(p, zbeg + (int)threadIdx.x);   // (p.zoff = 0: kfx_sdf_fuse_color takes no slab)
+    if (threadIdx.x < FUSE_ZC) s_pz[threadIdx.x] = slice_z(p, zbeg + (int)threadIdx.x);   // (the only z-dependent term: cam / ccam take pz)
     __syncthreads();
     if (x >= p.X || y >= p.Y) return;
 
@@ -2279,15 +2280,25 @@ extern "C" int kfx_sdf_sphere_h(const kfx_volume* vol, const float center[3], fl
 }
 
 // SdfFuse(vol, colorVol, depth, norm, T_cw, K, img, T_iw, Kimg, trunc_dist, max_w, mincostheta) (cu_sdffusion.cu:120-138)
+// slab (kfx_sdf_fuse_color_slab, include/kfx_slab_color.h): vol and colorvol hold planes [z_offset, z_offset + d) of the volumes `slab`
+// describes.  As in fuse_launch the positions come from the full volume's expression through p.zoff / p.d1 (slice_z is the kernels' only
+// z-dependent term: the depth camera's and the colour camera's terms and the brick culls all take its value), the extents are the
+// reference's on the whole volume -- x / y to multiples of 16, every plane: nothing to clip in z -- and the z-ranges carry zoff_local;
+// the alignment test of the tiled kernel is made on the local views, so a slab whose storage breaks it takes the untiled kernel
+// (same bits).  The tracked form stays single-volume: slabs march without a summary.
 static int fuse_color_launch(const kfx_volume* vol, const kfx_volume* colorvol, const kfx_image* depth, const kfx_image* norm,
                              const float T_cw[12], const float K[4], const kfx_image* img, const float T_iw[12], const float Kimg[4],
-                             float trunc_dist, float max_w, float mincostheta, unsigned flags, kfx_stream stream, kfx_sdf_summary* summary = nullptr)
+                             float trunc_dist, float max_w, float mincostheta, unsigned flags, kfx_stream stream, kfx_sdf_summary* summary = nullptr,
+                             const kfx_slab* slab = nullptr)
 {
     FuseParams p;
     bool small_images = false;
-    if (int e = fuse_params(p, &small_images, vol, depth, norm, T_cw, K, trunc_dist, max_w, mincostheta, flags | KFX_FUSE_FULL_EXTENT, 8, nullptr)) return e;
+    if (int e = fuse_params(p, &small_images, vol, depth, norm, T_cw, K, trunc_dist, max_w, mincostheta, flags | KFX_FUSE_FULL_EXTENT, 8, slab)) return e;
     if (int e = check_volume(colorvol, 4, 1, VOLUME_MAX_DIM, "SdfFuse(colour)")) return e;
     if (!img || !img->ptr || !T_iw || !Kimg) return set_error(KFX_E_NULL, "SdfFuse(colour): null argument");
+    if (slab) {
+        if (int e = kfx::check_color_slab(vol, colorvol, "SdfFuse(colour, slab)")) return e;
+    }
     if (colorvol->w < vol->w || colorvol->h < vol->h || colorvol->d < vol->d) return set_error(KFX_E_SHAPE, "SdfFuse(colour): colour volume smaller than the SDF volume");
     if (img->w < 4 || img->h < 4 || img->pitch < img->w * 3) return set_error(KFX_E_SHAPE, "SdfFuse(colour): rgb image dimensions");
     if (!(flags & KFX_FUSE_FULL_EXTENT)) { // the reference's 16x16 launch over x / y, all of z (cu_sdffusion.cu:132-135)
@@ -2358,6 +2369,15 @@ extern "C" int kfx_sdf_fuse_color_tracked(const kfx_volume* vol, const kfx_volum
 {
     if (!summary) return set_error(KFX_E_NULL, "kfx_sdf_fuse_color_tracked: null summary");
     return fuse_color_launch(vol, colorvol, depth, norm, T_cw, K, img, T_iw, Kimg, trunc_dist, max_w, mincostheta, flags, stream, summary);
+}
+
+// kfx_sdf_fuse_color on a Z-slab (include/kfx_slab_color.h)
+extern "C" int kfx_sdf_fuse_color_slab(const kfx_volume* vol, const kfx_volume* colorvol, const kfx_slab* slab, const kfx_image* depth,
+                                       const kfx_image* norm, const float T_cw[12], const float K[4], const kfx_image* img, const float T_iw[12],
+                                       const float Kimg[4], float trunc_dist, float max_w, float mincostheta, unsigned flags, kfx_stream stream)
+{
+    if (!slab) return set_error(KFX_E_NULL, "kfx_sdf_fuse_color_slab: null slab");
+    return fuse_color_launch(vol, colorvol, depth, norm, T_cw, K, img, T_iw, Kimg, trunc_dist, max_w, mincostheta, flags, stream, nullptr, slab);
 }
 
 // SdfReset(BoundedVolume<float>) (cu_sdffusion.cu:166-169): every cell of the span, padding included, = 0.5

@@ -4,6 +4,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #include "kfx_device.h"
 
@@ -40,6 +41,23 @@ inline kfx_volume slab_full_volume(const kfx_volume* vol, const kfx_slab* slab)
     full.boxmin[2] = slab->full_zmin;
     full.boxmax[2] = slab->full_zmax;
     return full;
+}
+
+// A rank's colour slab beside its SDF slab (include/kfx_slab_color.h): the colour volume is partitioned exactly like the SDF volume,
+// so the two local views have the same dimensions and the same box.  Both volumes non-null (the callers have checked).
+inline int check_color_slab(const kfx_volume* vol, const kfx_volume* colorvol, const char* what)
+{
+    char msg[200];
+    if (colorvol->w != vol->w || colorvol->h != vol->h || colorvol->d != vol->d) {
+        snprintf(msg, sizeof(msg), "%s: the colour slab's dimensions differ from the SDF slab's", what);
+        return set_error(KFX_E_SHAPE, msg);
+    }
+    for (int i = 0; i < 3; ++i)
+        if (memcmp(&colorvol->boxmin[i], &vol->boxmin[i], sizeof(float)) != 0 || memcmp(&colorvol->boxmax[i], &vol->boxmax[i], sizeof(float)) != 0) {
+            snprintf(msg, sizeof(msg), "%s: the colour slab's box differs from the SDF slab's", what);
+            return set_error(KFX_E_SHAPE, msg);
+        }
+    return 0;
 }
 
 // A numeric knob of the environment (clamped to [lo, hi]); callers keep it in a function-local static: read once, at first use.

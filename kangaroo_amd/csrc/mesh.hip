@@ -22,6 +22,7 @@
 // loops and winding equal the classic tables' in all 256 cases (tests/test_mesh_cpu.py).
 #include "kfx_device.h"
 #include "sampling.h"
+#include "host_args.h"
 #include "../../include/kfx_mesh.h"
 
 namespace kfx {
@@ -107,7 +108,8 @@ __global__ __launch_bounds__(256) void k_mc_count(const MeshParams p, unsigned c
 
 // One thread per ACTIVE cube (cube_index lists the cubes with triangles in emission order; tri_offset their first
 // triangle): dense lanes instead of the ~1 % active lanes of a thread-per-cube sweep.  CELL: fp32 or half cells; SLAB: p holds
-// the full volume's geometry over a slab's planes [avail_lo, avail_hi) (virtual base pointer, slab_full_volume).
+// the full volume's geometry over a slab's planes [avail_lo, avail_hi) (virtual base pointer, slab_full_volume), and so does cv for
+// the rank's colour slab, which has the SDF slab's geometry.
 template <typename CELL, bool SLAB>
 __global__ __launch_bounds__(128) void k_mc_emit(const MeshParams p, const ColorGeom cv, const int has_color,
                                                  const long long* __restrict__ cube_index, const unsigned* __restrict__ tri_offset,
@@ -144,13 +146,15 @@ __global__ __launch_bounds__(128) void k_mc_emit(const MeshParams p, const Color
                     dz = (float)(corner_dz(c1) - corner_dz(c0));
         const V3 pos = v3(p0.x + (ox + off * dx) * p.voxel.x, p0.y + (oy + off * dy) * p.voxel.y, p0.z + (oz + off * dz) * p.voxel.z);
         ev[e] = pos;
+        bool stored = true;   // SLAB: the planes this vertex's normal and colour read are stored here
         V3 n;
         if constexpr (SLAB) {
             // the stencil's planes (gradient<>: base plane clamped to [1, d - 2], one plane either side) must be stored; they are
             // for any vertex within a voxel of its cube, which float positions are unless the box lies ~2^20 voxels from the origin
             const float pfz = (pos.z - p.vol.bmin.z) / p.size.z * p.dims1.z;
             const int iz = (int)fmaxf(fminf(p.hi2.z, floorf(pfz)), 1.f);
-            if (iz - 1 >= p.avail_lo && iz + 1 < p.avail_hi) {
+            stored = iz - 1 >= p.avail_lo && iz + 1 < p.avail_hi;
+            if (stored) {
                 const V3 deriv = gradient<CELL>(p, pos);
                 n = div_s(deriv, length(deriv));
             } else {
@@ -162,7 +166,8 @@ __global__ __launch_bounds__(128) void k_mc_emit(const MeshParams p, const Color
         }
         if (!isfinite(n.x) || !isfinite(n.y) || !isfinite(n.z)) n = v3(0.f, 0.f, 0.f);
         en[e] = n;
-        ec[e] = has_color ? trilinear<RayC32>(cv, pos) : 0.f;
+        // (SLAB: the colour sample's planes, base clamp(floor(pfz), 0, d - 2) and the next, lie inside the stencil's three: equal geometry)
+        ec[e] = (has_color && stored) ? trilinear<RayC32>(cv, pos) : 0.f;
     }
     size_t o = (size_t)tri_offset[t_id] * 3; // first output vertex of this cube
     for (int t = 0; t < ntri * 3; ++t, ++o) {
@@ -610,8 +615,16 @@ extern "C" int kfx_mesh_emit(const kfx_volume* vol, int cell, const kfx_slab* sl
         return set_error(KFX_E_ALIGN, "kfx_mesh_emit: output alignment");
     ColorGeom cv;
     int has_color = 0;
-    if (!slab)
+    if (!slab) {
         if (int e = color_params(cv, has_color, colorvol, colors)) return e;
+    } else if (colorvol && colorvol->ptr && colors) {
+        // the rank's colour slab: the planes of `vol` of a colour volume with the SDF volume's geometry, seen through the full volume
+        if (cell != KFX_CELL_F32) return set_error(KFX_E_RANGE, "kfx_mesh_emit: colour on slabs needs fp32 SDF cells");
+        if (int e = check_volume(colorvol, 4, 1, VOLUME_ANY_DIM, "SaveMesh(colour, slab)")) return e;
+        if (int e = check_color_slab(vol, colorvol, "SaveMesh(colour, slab)")) return e;
+        const kfx_volume cfull = slab_full_volume(colorvol, slab);
+        if (int e = color_params(cv, has_color, &cfull, colors)) return e;   // (IsValid() of the FULL colour volume)
+    }
     if (!has_color) cv = ColorGeom{};
     if (int e = load_tables()) return e;
     const hipStream_t st = (hipStream_t)stream;
@@ -622,7 +635,7 @@ extern "C" int kfx_mesh_emit(const kfx_volume* vol, int cell, const kfx_slab* sl
     if (he != hipSuccess) return set_error((int)he, hipGetErrorString(he));
     if (planned[0] != totals[0] || planned[1] != totals[1]) return set_error(KFX_E_RANGE, "kfx_mesh_emit: totals are not the plan's");
     if (cell == KFX_CELL_F32) {
-        if (slab) mesh_emit_launch<RayF32, true>(p, r, s, cv, 0, totals, cube_index, tri_offset, verts, norms, nullptr, st);
+        if (slab) mesh_emit_launch<RayF32, true>(p, r, s, cv, has_color, totals, cube_index, tri_offset, verts, norms, has_color ? colors : nullptr, st);
         else mesh_emit_launch<RayF32, false>(p, r, s, cv, has_color, totals, cube_index, tri_offset, verts, norms, colors, st);
     } else {
         if (slab) mesh_emit_launch<RayF16, true>(p, r, s, cv, 0, totals, cube_index, tri_offset, verts, norms, nullptr, st);

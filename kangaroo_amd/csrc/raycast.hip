@@ -14,6 +14,7 @@
 
 #include "kfx_device.h"
 #include "sampling.h"
+#include "../../include/kfx_slab_color.h"
 
 namespace kfx {
 
@@ -741,8 +742,24 @@ __device__ __forceinline__ int grad_cell_z(const RayParams& p, const V3 pos_w)
     return (int)fmaxf(fminf(p.hi2.z, floorf(pfz)), 1.f);
 }
 
-template <typename CELL>
-__global__ __launch_bounds__(256) void k_raycast_sdf_slab(const RayParams p, const SlabRay sl)
+// COLOR (include/kfx_slab_color.h): the rank that finalises a hit writes the colour volume's sample at the hit into the shade plane
+// instead of the Phong shade -- write_ray<.., COLOR>'s expression on the slab's ColorGeom: the full colour volume's geometry over a
+// virtual base pointer, as p is for the SDF volume.  The colour volume has the SDF volume's dimensions and box, so that geometry is
+// p's own but for where the cells lie (SlabColor: the kernel carries no second copy of the box in scalar registers).  The colour
+// travels where the shade travels.
+struct SlabColor { unsigned char* ptr; size_t pitch, img_pitch; int off32; };
+__device__ __forceinline__ ColorGeom slab_color_geom(const RayParams& p, const SlabColor& sc)
+{
+    ColorGeom cv;
+    cv.vol = p.vol;
+    cv.vol.ptr = sc.ptr; cv.vol.pitch = sc.pitch; cv.vol.img_pitch = sc.img_pitch;
+    cv.size = p.size; cv.dims1 = p.dims1; cv.hi2 = p.hi2; cv.inv_size = p.inv_size;
+    cv.fastdiv = p.fastdiv; cv.off32 = sc.off32;
+    return cv;
+}
+
+template <typename CELL, bool COLOR>
+__global__ __launch_bounds__(256) void k_raycast_sdf_slab(const RayParams p, const SlabRay sl, const SlabColor sc)
 {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int u = blockIdx.x * 64 + (wv & 1) * 32 + (lane & 31); // wave = 32 x 2 pixels, as k_raycast_sdf's default
@@ -818,7 +835,12 @@ __global__ __launch_bounds__(256) void k_raycast_sdf_slab(const RayParams p, con
         if ((sl.normals_here || (gz >= sl.own_lo && gz < sl.own_hi)) && gz - 1 >= sl.avail_lo && gz + 1 < sl.avail_hi) {
             const V3 n_c = normal_c<CELL>(p, pos);
             rs[0] = n_c.x; rs[plane] = n_c.y; rs[2 * plane] = n_c.z;
-            rs[3 * plane] = phong(ray_c * lambda, n_c);
+            // The finaliser always holds the colour sample's planes: the sample's base plane is iz = clamp(floor(pfz), 0, d - 2), the
+            // gradient's gz = clamp(floor(pfz), 1, d - 2) with the same pfz -- the colour volume has the SDF volume's dimensions and box
+            // (check_color_slab) -- so iz is gz or gz - 1 and planes iz, iz + 1 lie inside [gz - 1, gz + 1], which the test above has
+            // just found stored; with and without normals_here.
+            if constexpr (COLOR) rs[3 * plane] = trilinear<RayC32>(slab_color_geom(p, sc), pos);
+            else rs[3 * plane] = phong(ray_c * lambda, n_c);
             status = 1.f;
         }
     }
@@ -1299,12 +1321,18 @@ extern "C" int kfx_raycast_color_hits(int n_levels, const kfx_image* const* dept
 // Exact multi-GPU march: one round of a rank (see k_raycast_sdf_slab).  `vol` holds planes
 // [slab->z_offset, slab->z_offset + vol->d) of the full volume described by `slab`; the rank owns the
 // trilinear base cells [own_lo, own_hi).  `state` is KFX_RAY_STATE_PLANES dense planes of h*w floats; init != 0 starts the rays.
+// colorvol (fp32 cells only): the rank's colour slab, the planes of `vol` of a colour volume with the SDF volume's geometry; the
+// shade plane receives the colour of the hits this rank finalises.
 template <typename CELL>
 static int raycast_slab_launch(const SlabRay& geom, const kfx_volume* vol, const kfx_slab* slab, int own_lo, int own_hi,
                                     int w, int h, const float T_wc[12], const float K[4], float near, float far,
-                                    float trunc_dist, int subpix, kfx_stream stream)
+                                    float trunc_dist, int subpix, kfx_stream stream, const kfx_volume* colorvol = nullptr)
 {
     if (!geom.state || !geom.result || !vol || !vol->ptr || !slab || !T_wc || !K) return set_error(KFX_E_NULL, "RaycastSdf(slab): null argument");
+    if (colorvol) {
+        if (int e = check_volume(colorvol, 4, 1, VOLUME_MAX_DIM, "RaycastSdf(slab, colour)")) return e;
+        if (int e = check_color_slab(vol, colorvol, "RaycastSdf(slab, colour)")) return e;
+    }
     if (w <= 0 || h <= 0 || geom.v1 <= geom.v0) return 0;
     if (geom.R < 1 || geom.v0 < 0 || geom.v1 > h || geom.P < (size_t)geom.R * (size_t)w) return set_error(KFX_E_SHAPE, "RaycastSdf(slab): tile geometry");
     if (slab->full_d < 3 || slab->z_offset + vol->d > slab->full_d || vol->w < 3 || vol->h < 3)
@@ -1332,7 +1360,20 @@ static int raycast_slab_launch(const SlabRay& geom, const kfx_volume* vol, const
     sl.own_lo = own_lo; sl.own_hi = own_hi;
     sl.avail_lo = (int)slab->z_offset; sl.avail_hi = (int)(slab->z_offset + vol->d);
     dim3 grid(ceil_div(w, 64), ceil_div(sl.v1 - sl.v0, 4));
-    hipLaunchKernelGGL(k_raycast_sdf_slab<CELL>, grid, dim3(256), 0, (hipStream_t)stream, p, sl);
+    SlabColor sc{};
+    if constexpr (CELL::BYTES == 8) {
+        if (colorvol) {
+            // the slab's ColorGeom: set_geometry on the full colour volume gives p's box members (equal dimensions and box:
+            // check_color_slab) and the colour cells' own addressing
+            const kfx_volume cfull = slab_full_volume(colorvol, slab);
+            ColorGeom cv{};
+            set_geometry(cv, &cfull);
+            sc = SlabColor{cv.vol.ptr, cv.vol.pitch, cv.vol.img_pitch, cv.off32};
+            hipLaunchKernelGGL((k_raycast_sdf_slab<CELL, true>), grid, dim3(256), 0, (hipStream_t)stream, p, sl, sc);
+            return check_launch("kfx_raycast_sdf_slab_color");
+        }
+    }
+    hipLaunchKernelGGL((k_raycast_sdf_slab<CELL, false>), grid, dim3(256), 0, (hipStream_t)stream, p, sl, sc);
     return check_launch("kfx_raycast_sdf_slab");
 }
 
@@ -1347,10 +1388,10 @@ static SlabRay dense_state(float* state, int init, int w, int h)
     return g;
 }
 
-extern "C" int kfx_raycast_sdf_slab_tiles(float* state, float* result, size_t plane_stride, int rows_per_tile, int v0, int v1, int init, int* fin,
-                                          int claim_misses, const float* adopt_lo, const float* adopt_hi, int layout_flags, const kfx_volume* vol,
-                                          const kfx_slab* slab, int own_lo, int own_hi, int w, int h, const float T_wc[12], const float K[4], float near,
-                                          float far, float trunc_dist, int subpix, kfx_stream stream)
+static int raycast_slab_tiles(float* state, float* result, size_t plane_stride, int rows_per_tile, int v0, int v1, int init, int* fin,
+                              int claim_misses, const float* adopt_lo, const float* adopt_hi, int layout_flags, const kfx_volume* vol,
+                              const kfx_volume* colorvol, const kfx_slab* slab, int own_lo, int own_hi, int w, int h, const float T_wc[12],
+                              const float K[4], float near, float far, float trunc_dist, int subpix, kfx_stream stream)
 {
     SlabRay g{};
     g.state = state; g.result = result; g.P = plane_stride; g.R = rows_per_tile; g.v0 = v0; g.v1 = v1; g.fin = fin; g.claim_misses = claim_misses ? 1 : 0;
@@ -1363,7 +1404,36 @@ extern "C" int kfx_raycast_sdf_slab_tiles(float* state, float* result, size_t pl
     if (((uintptr_t)adopt_lo | (uintptr_t)adopt_hi) & 3) return set_error(KFX_E_ALIGN, "RaycastSdf(slab): alignment of the received snapshots");
     if (!adopt_tile_major && (adopt_lo || adopt_hi) && rows_per_tile > 0 && (v0 / rows_per_tile != (v1 - 1) / rows_per_tile))
         return set_error(KFX_E_SHAPE, "RaycastSdf(slab): one-tile snapshots with rows of several tiles");
-    return raycast_slab_launch<RayF32>(g, vol, slab, own_lo, own_hi, w, h, T_wc, K, near, far, trunc_dist, subpix, stream);
+    return raycast_slab_launch<RayF32>(g, vol, slab, own_lo, own_hi, w, h, T_wc, K, near, far, trunc_dist, subpix, stream, colorvol);
+}
+
+extern "C" int kfx_raycast_sdf_slab_tiles(float* state, float* result, size_t plane_stride, int rows_per_tile, int v0, int v1, int init, int* fin,
+                                          int claim_misses, const float* adopt_lo, const float* adopt_hi, int layout_flags, const kfx_volume* vol,
+                                          const kfx_slab* slab, int own_lo, int own_hi, int w, int h, const float T_wc[12], const float K[4], float near,
+                                          float far, float trunc_dist, int subpix, kfx_stream stream)
+{
+    return raycast_slab_tiles(state, result, plane_stride, rows_per_tile, v0, v1, init, fin, claim_misses, adopt_lo, adopt_hi, layout_flags, vol, nullptr, slab,
+                              own_lo, own_hi, w, h, T_wc, K, near, far, trunc_dist, subpix, stream);
+}
+
+// the colour forms (include/kfx_slab_color.h): the same launches with the rank's colour slab
+extern "C" int kfx_raycast_sdf_slab_tiles_color(float* state, float* result, size_t plane_stride, int rows_per_tile, int v0, int v1, int init, int* fin,
+                                                int claim_misses, const float* adopt_lo, const float* adopt_hi, int layout_flags, const kfx_volume* vol,
+                                                const kfx_volume* colorvol, const kfx_slab* slab, int own_lo, int own_hi, int w, int h,
+                                                const float T_wc[12], const float K[4], float near, float far, float trunc_dist, int subpix,
+                                                kfx_stream stream)
+{
+    if (!colorvol) return set_error(KFX_E_NULL, "RaycastSdf(slab, colour): null colour volume");
+    return raycast_slab_tiles(state, result, plane_stride, rows_per_tile, v0, v1, init, fin, claim_misses, adopt_lo, adopt_hi, layout_flags, vol, colorvol, slab,
+                              own_lo, own_hi, w, h, T_wc, K, near, far, trunc_dist, subpix, stream);
+}
+
+extern "C" int kfx_raycast_sdf_slab_color(float* state, int init, const kfx_volume* vol, const kfx_volume* colorvol, const kfx_slab* slab, int own_lo,
+                                          int own_hi, int w, int h, const float T_wc[12], const float K[4], float near, float far, float trunc_dist,
+                                          int subpix, kfx_stream stream)
+{
+    if (!colorvol) return set_error(KFX_E_NULL, "RaycastSdf(slab, colour): null colour volume");
+    return raycast_slab_launch<RayF32>(dense_state(state, init, w, h), vol, slab, own_lo, own_hi, w, h, T_wc, K, near, far, trunc_dist, subpix, stream, colorvol);
 }
 
 extern "C" int kfx_raycast_sdf_slab(float* state, int init, const kfx_volume* vol, const kfx_slab* slab, int own_lo, int own_hi,

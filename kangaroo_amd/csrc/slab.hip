@@ -922,7 +922,7 @@ extern "C" int kfx_slab_set_normals_stage(int keep)
 // set).  Everything here is ordered on `stream`; the collectives are neighbour exchanges only (comm->exchange_v).
 int kfx::exact_tiled_march(void* scratch, const ExactFinalBufs* into, const kfx_volume* local, const kfx_slab_layout* L, const float T_wc[12],
                            const float K[4], float near, float far, float trunc_dist, int subpix, int tiles, int w, int h, kfx_comm* comm,
-                           kfx_stream stream, int* steps_out)
+                           kfx_stream stream, int* steps_out, const kfx_volume* color_local)
 {
     const int world = comm->world, rank = comm->rank;
     TiledScratch t;
@@ -945,9 +945,15 @@ int kfx::exact_tiled_march(void* scratch, const ExactFinalBufs* into, const kfx_
     // one launch per visit of a tile: it initialises the tile's rays when this is the rank's first visit, takes over what the
     // neighbours handed on (their newer, still open snapshots), and marches what lies in the rank's own planes
     auto march = [&](int v0, int v1, int init, const int* from_lo, const int* from_hi, int tile_major) {
-        note(kfx_raycast_sdf_slab_tiles(reinterpret_cast<float*>(t.M), reinterpret_cast<float*>(t.Rz), P, R, v0, v1, init, t.fin, rank == 0 ? 1 : 0,
-                                        reinterpret_cast<const float*>(from_lo), reinterpret_cast<const float*>(from_hi), (tile_major ? 1 : 0) | (packed ? 2 : 0) | (self_normals ? 4 : 0), local, &slab,
-                                        (int)L->z0, (int)L->z1, w, h, T_wc, K, near, far, trunc_dist, subpix, stream));
+        const int layout_flags = (tile_major ? 1 : 0) | (packed ? 2 : 0) | (self_normals ? 4 : 0);
+        if (color_local)
+            note(kfx_raycast_sdf_slab_tiles_color(reinterpret_cast<float*>(t.M), reinterpret_cast<float*>(t.Rz), P, R, v0, v1, init, t.fin, rank == 0 ? 1 : 0,
+                                                  reinterpret_cast<const float*>(from_lo), reinterpret_cast<const float*>(from_hi), layout_flags, local, color_local,
+                                                  &slab, (int)L->z0, (int)L->z1, w, h, T_wc, K, near, far, trunc_dist, subpix, stream));
+        else
+            note(kfx_raycast_sdf_slab_tiles(reinterpret_cast<float*>(t.M), reinterpret_cast<float*>(t.Rz), P, R, v0, v1, init, t.fin, rank == 0 ? 1 : 0,
+                                            reinterpret_cast<const float*>(from_lo), reinterpret_cast<const float*>(from_hi), layout_flags, local, &slab,
+                                            (int)L->z0, (int)L->z1, w, h, T_wc, K, near, far, trunc_dist, subpix, stream));
     };
     auto rows_of = [&](int tile, int& v0, int& v1) { v0 = tile * R; v1 = v0 + R < h ? v0 + R : h; };
     int steps = 0;
@@ -1071,16 +1077,20 @@ int kfx::exact_tiled_finalise(const kfx_image* depth, const kfx_image* norm, con
     return status;
 }
 
-extern "C" int kfx_slab_raycast_exact_tiled(const kfx_image* depth, const kfx_image* norm, const kfx_image* img, void* scratch,
-                                            const kfx_volume* local, const kfx_slab_layout* L, const float T_wc[12], const float K[4],
-                                            float near, float far, float trunc_dist, int subpix, int tiles, kfx_comm* comm, kfx_stream stream,
-                                            int* h_open, int* steps_out)
+static int exact_tiled(const kfx_image* depth, const kfx_image* norm, const kfx_image* img, void* scratch, const kfx_volume* local,
+                       const kfx_volume* color_local, const kfx_slab_layout* L, const float T_wc[12], const float K[4], float near, float far,
+                       float trunc_dist, int subpix, int tiles, kfx_comm* comm, kfx_stream stream, int* h_open, int* steps_out)
 {
     if (int e = exact_tiled_args(depth, norm, img, scratch, local, L, comm, T_wc, K)) return e;
+    if (color_local) {   // (every rank makes the same call with volumes of the same geometry: an argument error is every rank's)
+        if (!local->ptr) return set_error(KFX_E_NULL, "kfx_slab_raycast_exact_tiled_color: null volume");
+        if (int e = check_volume(color_local, 4, 1, VOLUME_MAX_DIM, "kfx_slab_raycast_exact_tiled_color")) return e;
+        if (int e = check_color_slab(local, color_local, "kfx_slab_raycast_exact_tiled_color")) return e;
+    }
     const int w = (int)img->w, h = (int)img->h;
     if (w == 0 || h == 0) return 0;
     // (a local failure of the march does not keep this rank out of the final exchange its peers enter)
-    int status = exact_tiled_march(scratch, nullptr, local, L, T_wc, K, near, far, trunc_dist, subpix, tiles, w, h, comm, stream, steps_out);
+    int status = exact_tiled_march(scratch, nullptr, local, L, T_wc, K, near, far, trunc_dist, subpix, tiles, w, h, comm, stream, steps_out, color_local);
     int n_open = 0;
     const int e = exact_tiled_finalise(depth, norm, img, scratch, nullptr, tiles, comm, stream, h_open ? h_open : nullptr);
     if (e && !status) status = e;
@@ -1094,4 +1104,22 @@ extern "C" int kfx_slab_raycast_exact_tiled(const kfx_image* depth, const kfx_im
     if (y && !status) status = y;
     if (!status && n_open) status = set_error(KFX_E_RANGE, "kfx_slab_raycast_exact_tiled: rays without a final status after the hand-over");
     return status;
+}
+
+extern "C" int kfx_slab_raycast_exact_tiled(const kfx_image* depth, const kfx_image* norm, const kfx_image* img, void* scratch,
+                                            const kfx_volume* local, const kfx_slab_layout* L, const float T_wc[12], const float K[4],
+                                            float near, float far, float trunc_dist, int subpix, int tiles, kfx_comm* comm, kfx_stream stream,
+                                            int* h_open, int* steps_out)
+{
+    return exact_tiled(depth, norm, img, scratch, local, nullptr, L, T_wc, K, near, far, trunc_dist, subpix, tiles, comm, stream, h_open, steps_out);
+}
+
+// the hand-over with this rank's colour slab (include/kfx_slab_color.h): the images of kfx_raycast_sdf_color on the whole volumes
+extern "C" int kfx_slab_raycast_exact_tiled_color(const kfx_image* depth, const kfx_image* norm, const kfx_image* img, void* scratch,
+                                                  const kfx_volume* local, const kfx_volume* color_local, const kfx_slab_layout* L,
+                                                  const float T_wc[12], const float K[4], float near, float far, float trunc_dist, int subpix,
+                                                  int tiles, kfx_comm* comm, kfx_stream stream, int* h_open, int* steps_out)
+{
+    if (!color_local) return set_error(KFX_E_NULL, "kfx_slab_raycast_exact_tiled_color: null colour volume");
+    return exact_tiled(depth, norm, img, scratch, local, color_local, L, T_wc, K, near, far, trunc_dist, subpix, tiles, comm, stream, h_open, steps_out);
 }

@@ -10,6 +10,7 @@
 #include <new>
 
 #include "kfx_device.h"
+#include "host_args.h"
 #include "../../include/kfx_slab.h"
 #include "slab_internal.h"
 
@@ -60,6 +61,12 @@ struct kfx_slab_frame {
     // the packed texel image of the frame (owned; fuse.hip): written by the fused vbo / normals launch, staged by the SdfFuse of the same step
     kfx_image texels;
     int* agree;                              // a device word: the ranks' common verdict on a configure
+    // colour mode (kfx_slab_frame_set_color, include/kfx_slab_color.h): the rank's colour slab, the frame's RGB image, the colour camera
+    int color;
+    kfx_volume cvol;
+    kfx_image rgb;
+    float Kimg[4];
+    float T_cd[12];
     // timing ring
     int slots;
     unsigned timing;                         // which of the five events the next steps record (bit k: event k)
@@ -411,7 +418,28 @@ extern "C" int kfx_slab_frame_configure(kfx_slab_frame* f, int halo, int raycast
 extern "C" int kfx_slab_frame_reset(kfx_slab_frame* f, kfx_stream stream)
 {
     if (!f) return set_error(KFX_E_NULL, "kfx_slab_frame_reset: null frame");
-    return kfx_sdf_reset(&f->cfg.local, __builtin_nanf(""), stream);   // "never observed" = (NaN, 0) (main.cpp:229)
+    if (int e = kfx_sdf_reset(&f->cfg.local, __builtin_nanf(""), stream)) return e;   // "never observed" = (NaN, 0) (main.cpp:229)
+    return f->color ? kfx_color_reset(&f->cvol, stream) : 0;                          // SdfReset(colorVol) (main.cpp:233)
+}
+
+extern "C" int kfx_slab_frame_set_color(kfx_slab_frame* f, const kfx_volume* color_local, const kfx_image* rgb, const float Kimg[4], const float* T_cd)
+{
+    if (!f) return set_error(KFX_E_NULL, "kfx_slab_frame_set_color: null frame");
+    if (!color_local) {
+        f->color = 0;
+        return 0;
+    }
+    if (!rgb || !rgb->ptr || !Kimg) return set_error(KFX_E_NULL, "kfx_slab_frame_set_color: null argument");
+    if (int e = check_volume(color_local, 4, 1, VOLUME_MAX_DIM, "kfx_slab_frame_set_color")) return e;
+    if (int e = check_color_slab(&f->cfg.local, color_local, "kfx_slab_frame_set_color")) return e;
+    if (rgb->w < 4 || rgb->h < 4 || rgb->pitch < rgb->w * 3) return set_error(KFX_E_SHAPE, "kfx_slab_frame_set_color: rgb image dimensions");
+    f->cvol = *color_local;
+    f->rgb = *rgb;
+    for (int i = 0; i < 4; ++i) f->Kimg[i] = Kimg[i];
+    static const float identity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    for (int i = 0; i < 12; ++i) f->T_cd[i] = T_cd ? T_cd[i] : identity[i];
+    f->color = 1;
+    return 0;
 }
 
 extern "C" int kfx_slab_frame_step(kfx_slab_frame* f, const kfx_image* raw, const float T_wc[12], const float* T_cw, unsigned parts, kfx_stream stream)
@@ -487,8 +515,26 @@ extern "C" int kfx_slab_frame_step(kfx_slab_frame* f, const kfx_image* raw, cons
         v.ptr = (unsigned char*)v.ptr + (first - L.s0) * v.img_pitch;
         v.d = count;
         const kfx_slab sl = {L.full_d, first, L.full_zmin, L.full_zmax};
-        note(kfx::sdf_fuse_slab_texels(&v, &sl, &c.filtered, &c.normals, tex, T_cw, c.K, c.trunc_dist, c.max_w, c.mincostheta, KFX_FUSE_SLAB_EXTENT, stream));
+        if (f->color) {
+            kfx_volume cv = f->cvol;
+            cv.ptr = (unsigned char*)cv.ptr + (first - L.s0) * cv.img_pitch;
+            cv.d = count;
+            // T_iw = T_cd * T_cw in float, row by row as a 4 x 4 float product with the rows (0, 0, 0, 1) evaluates it
+            float T_iw[12];
+            for (int i = 0; i < 3; ++i)
+                for (int j = 0; j < 4; ++j) {
+                    float a = 0.f;
+                    for (int k = 0; k < 3; ++k) a += f->T_cd[i * 4 + k] * T_cw[k * 4 + j];
+                    T_iw[i * 4 + j] = j == 3 ? a + f->T_cd[i * 4 + 3] : a;
+                }
+            note(kfx_sdf_fuse_color_slab(&v, &cv, &sl, &c.filtered, &c.normals, T_cw, c.K, &f->rgb, T_iw, f->Kimg, c.trunc_dist, c.max_w, c.mincostheta,
+                                         KFX_FUSE_SLAB_EXTENT, stream));
+        } else {
+            note(kfx::sdf_fuse_slab_texels(&v, &sl, &c.filtered, &c.normals, tex, T_cw, c.K, c.trunc_dist, c.max_w, c.mincostheta, KFX_FUSE_SLAB_EXTENT, stream));
+        }
+        // ghost planes: the SDF volume's, then the colour volume's -- the same order on every rank
         if (own_only) note(kfx_slab_exchange_halos(&c.local, &L, comm, stream));
+        if (own_only && f->color) note(kfx_slab_exchange_halos(&f->cvol, &L, comm, stream));
     }
     record(2, s);
     if (parts & KFX_FRAME_RAYCAST) {
@@ -511,7 +557,7 @@ extern "C" int kfx_slab_frame_step(kfx_slab_frame* f, const kfx_image* raw, cons
                     f->fin_inflight[set] = 0;
                 }
                 note(kfx::exact_tiled_march(f->exact, &f->fin[set], &c.local, &L, T_wc, c.K, c.near, c.far, c.trunc_dist, 1, tiles, (int)c.ray_img.w,
-                                            (int)c.ray_img.h, comm, stream, &steps));
+                                            (int)c.ray_img.h, comm, stream, &steps, f->color ? &f->cvol : nullptr));
                 f->last_steps = steps;
                 record(3, s);
                 note(hip_status(hipEventRecord(f->marched_ev[set], s), "kfx_slab_frame_step: hipEventRecord"));
@@ -521,15 +567,21 @@ extern "C" int kfx_slab_frame_step(kfx_slab_frame* f, const kfx_image* raw, cons
                 const int lag = (f->side_comm.flags & KFX_COMM_HOST_BLOCKING) ? f->pipe - 1 : 0;
                 while (f->n_pending > lag) note(finalise_oldest(f));
             } else {
-                note(kfx_slab_raycast_exact_tiled(&c.ray_depth, &c.ray_norm, &c.ray_img, f->exact, &c.local, &L, T_wc, c.K, c.near, c.far, c.trunc_dist, 1,
-                                                  tiles, comm, stream, f->h_open + os, &steps));
+                if (f->color)
+                    note(kfx_slab_raycast_exact_tiled_color(&c.ray_depth, &c.ray_norm, &c.ray_img, f->exact, &c.local, &f->cvol, &L, T_wc, c.K, c.near, c.far,
+                                                            c.trunc_dist, 1, tiles, comm, stream, f->h_open + os, &steps));
+                else
+                    note(kfx_slab_raycast_exact_tiled(&c.ray_depth, &c.ray_norm, &c.ray_img, f->exact, &c.local, &L, T_wc, c.K, c.near, c.far, c.trunc_dist, 1,
+                                                      tiles, comm, stream, f->h_open + os, &steps));
                 f->last_steps = steps;
                 if (hipEventRecord(f->open_done[os], s) == hipSuccess) f->open_frame[os] = f->frames;
                 else (void)hipGetLastError();
                 record(3, s);
             }
         } else {
-            note(kfx_raycast_sdf(&c.ray_depth, &c.ray_norm, &c.ray_img, &c.local, T_wc, c.K, c.near, c.far, c.trunc_dist, 1, stream));
+            // composite: each rank renders its local view (colour: kfx_raycast_sdf_color on its two slabs); the merge carries img either way
+            if (f->color) note(kfx_raycast_sdf_color(&c.ray_depth, &c.ray_norm, &c.ray_img, &c.local, &f->cvol, T_wc, c.K, c.near, c.far, c.trunc_dist, 1, stream));
+            else note(kfx_raycast_sdf(&c.ray_depth, &c.ray_norm, &c.ray_img, &c.local, T_wc, c.K, c.near, c.far, c.trunc_dist, 1, stream));
             record(3, s);
             if (world > 1) {
                 hipStream_t ms = s;

@@ -34,7 +34,8 @@ def ExtractMesh(vol, colorVol=None, stream=None, slab=None, with_index=False):
 
     vol.kind "f32" or "f16".  slab = (full_d, z_offset, full_zmin, full_zmax, own_lo, own_hi): `vol` holds planes
     [z_offset, z_offset + vol.d) of that volume and the cubes with lower plane in [own_lo, min(own_hi, full_d - 1)) are meshed,
-    each triangle bit-identical to the single-volume mesh's (no colour).  with_index: also return cube_index (int64, global) and
+    each triangle bit-identical to the single-volume mesh's; colorVol is then the rank's colour slab (kind "c32", the planes and the
+    box of `vol`; fp32 SDF cells) and the colours equal the single-volume mesh's too.  with_index: also return cube_index (int64, global) and
     tri_offset (int32: the first triangle of each active cube, uint32 bits)."""
     L = _lib.load()
     if vol.kind not in CELL:
@@ -44,7 +45,6 @@ def ExtractMesh(vol, colorVol=None, stream=None, slab=None, with_index=False):
     if slab is not None:
         full_d, z_offset, zmin, zmax, lo, hi = slab
         sl = C.byref(_lib.KfxSlab(int(full_d), int(z_offset), float(zmin), float(zmax)))
-        colorVol = None
     nbytes = L.kfx_mesh_scratch_bytes(vol.ref(), cell, sl, int(lo), int(hi))
     if nbytes == 0:
         _lib.check(L.kfx_mesh_plan(vol.ref(), cell, sl, int(lo), int(hi), None, 0, None, None))   # the reason
@@ -60,7 +60,8 @@ def ExtractMesh(vol, colorVol=None, stream=None, slab=None, with_index=False):
     tri_offset = torch.empty(na, dtype=torch.int32, device=dev)
     verts = torch.empty((3 * ntri, 3), dtype=torch.float32, device=dev)
     norms = torch.empty((3 * ntri, 3), dtype=torch.float32, device=dev)
-    has_color = colorVol is not None and min(colorVol.w, colorVol.h, colorVol.d) >= 8
+    # IsValid() of the colour volume -- of the FULL one where colorVol is a slab of it
+    has_color = colorVol is not None and min(colorVol.w, colorVol.h, colorVol.d if slab is None else int(slab[0])) >= 8
     colors = torch.empty((3 * ntri, 4), dtype=torch.float32, device=dev) if has_color else None
     if na:
         _lib.check(L.kfx_mesh_emit(vol.ref(), cell, sl, int(lo), int(hi), colorVol.ref() if has_color else None, C.c_void_p(scratch.data_ptr()),

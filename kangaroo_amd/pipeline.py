@@ -108,7 +108,7 @@ class FramePipeline:
         self.ray_i = I(w, h, "f32", pitch=pf(4))
         if self.color:
             cw, ch = (self.w, self.h) if color_size is None else (int(color_size[0]), int(color_size[1]))
-            self.cvol = ops.BoundedVolume(self.dims[0], self.dims[1], self.dims[2], boxmin, boxmax, kind="c32")
+            self.cvol = self._alloc_color_volume(boxmin, boxmax)
             self.rgb = I(cw, ch, "u8x3")
             self.Kimg = scenes.intrinsics(cw, ch)
             T_cd = scenes.identity_pose() if T_cd is None else np.asarray(T_cd, np.float32).reshape(-1, 4)[:3]
@@ -132,6 +132,9 @@ class FramePipeline:
         if self.kind != "f32":
             return self.ops.BoundedVolume(self.dims[0], self.dims[1], self.dims[2], boxmin, boxmax, kind=self.kind)
         return self.ops.BoundedVolume(self.dims[0], self.dims[1], self.dims[2], boxmin, boxmax)
+
+    def _alloc_color_volume(self, boxmin, boxmax):
+        return self.ops.BoundedVolume(self.dims[0], self.dims[1], self.dims[2], boxmin, boxmax, kind="c32")
 
     def set_track(self, on):
         """Switch between the tracked pair of kernels and the plain pair.  Switching on (re)builds the summary from what the
@@ -572,8 +575,14 @@ class SlabPipeline(FramePipeline):
         assert driver in ("python", "c")
         self.driver, self.sframe, self.comm = driver, None, comm
         timing_slots = kw.pop("timing_slots", None)
+        # color=True (FramePipeline): the colour volume is partitioned like the SDF volume -- `cvol` holds this rank's planes with the
+        # local box -- and every path stays bit-identical to the single-volume colour pipeline (include/kfx_slab_color.h)
         if kw.get("color"):
-            raise ValueError("SlabPipeline: colour mode is not built for Z-slabs")
+            if kind != "f32":
+                raise ValueError("SlabPipeline: color=True needs fp32 cells (kind='f16': the colour operators have no half-cell form)")
+            if raycast == "exact_allreduce":
+                raise ValueError("SlabPipeline: color=True renders with raycast='exact' or 'composite' ('exact_allreduce' is the grey hand-over's "
+                                 "cross-check: its state merge does not carry the colour plane's rank)")
         super().__init__(ops, dims, boxmin, boxmax, w, h, **kw)
         if driver == "c":
             if raycast == "exact_allreduce" or images != "all" or kind != "f32":
@@ -591,6 +600,8 @@ class SlabPipeline(FramePipeline):
                                       self.bil, self.near, self.far, self.trunc, self.max_w, self.mincostheta, halo=halo, raycast=raycast, merge=merge,
                                       inputs=inputs, overlap=overlap, tiles=tiles, unchecked=unchecked, timing_slots=int(timing_slots or 256),
                                       pipe_images=extra)
+            if self.color:
+                self.sframe.set_color(self.cvol, self.rgb, self.Kimg, self.T_cd)
 
     def configure(self, **kw):
         """Change policies between frames (halo, raycast, merge, inputs, overlap, tiles): bench.py times the variants on one pipeline."""
@@ -603,12 +614,17 @@ class SlabPipeline(FramePipeline):
             if k in names:
                 setattr(self, names[k], v)
 
-    def step(self, T_wc, raw_image=None):
+    def step(self, T_wc, raw_image=None, rgb_image=None):
+        """rgb_image (color=True): the frame's RGB image; the C driver reads the image it was bound to (self.rgb) unless another one
+        is given, which it is then bound to from this frame on."""
         if self.sframe is not None:
+            if self.color and rgb_image is not None and rgb_image is not self._rgb_now:
+                self._rgb_now = rgb_image
+                self.sframe.set_color(self.cvol, rgb_image, self.Kimg, self.T_cd)
             self.sframe.step(T_wc, scenes.se3_inverse(T_wc), raw_image)
             self.frames_done += 1
             return
-        super().step(T_wc, raw_image)
+        super().step(T_wc, raw_image, rgb_image)
 
     def _alloc_volume(self, boxmin, boxmax):
         W, H, D = self.dims
@@ -622,6 +638,10 @@ class SlabPipeline(FramePipeline):
         if self.kind != "f32":
             return self.ops.BoundedVolume(W, H, self.s1 - self.s0, lo, hi, kind=self.kind)
         return self.ops.BoundedVolume(W, H, self.s1 - self.s0, lo, hi)
+
+    def _alloc_color_volume(self, boxmin, boxmax):
+        """This rank's planes [s0, s1) of the colour volume, with the SDF slab's box."""
+        return self.ops.BoundedVolume(self.vol.w, self.vol.h, self.vol.d, self.vol.boxmin, self.vol.boxmax, kind="c32")
 
     def preprocess(self, raw_image=None):
         if self.sframe is not None:
@@ -645,14 +665,23 @@ class SlabPipeline(FramePipeline):
         # integrates on the whole volume (x / y extents (dim/8)*8, planes below (D/8)*8), whatever the partition
         D = self.dims[2]
         zmin, zmax = float(self.full_boxmin[2]), float(self.full_boxmax[2])
+        ctarget = self.cvol if self.color else None
         if self.halo == "recompute" or self.world == 1:
             target, first = self.vol, self.s0
         else:
             target, first = self.vol.ZSlab(self.z0 - self.s0, self.z1 - self.s0), self.z0  # owned planes only
+            if self.color:
+                ctarget = self.cvol.ZSlab(self.z0 - self.s0, self.z1 - self.s0)
+                ctarget.boxmin, ctarget.boxmax = target.boxmin, target.boxmax   # (the SDF view's box, bit for bit)
         # slab entry point: voxel positions by the FULL volume's expression, so every plane is integrated
         # bit-identically to the same plane of a single-GPU volume
-        self.ops.SdfFuse(target, self.filtered, self.normals, scenes.se3_inverse(T_wc) if T_cw is None else T_cw, self.K, self.trunc,
-                         self.max_w, self.mincostheta, full_extent="slab", slab=(D, first, zmin, zmax))
+        T_cw = scenes.se3_inverse(T_wc) if T_cw is None else T_cw
+        if self.color:
+            self.ops.SdfFuseColorSlab(target, ctarget, (D, first, zmin, zmax), self.filtered, self.normals, T_cw, self.K, self._rgb_now,
+                                      self.color_pose(T_cw), self.Kimg, self.trunc, self.max_w, self.mincostheta, full_extent="slab")
+        else:
+            self.ops.SdfFuse(target, self.filtered, self.normals, T_cw, self.K, self.trunc,
+                             self.max_w, self.mincostheta, full_extent="slab", slab=(D, first, zmin, zmax))
         if target is not self.vol:
             self.exchange_halos()
 
@@ -688,17 +717,19 @@ class SlabPipeline(FramePipeline):
         lo_ghost = self.z0 - self.s0              # planes [s0, z0) come from rank-1
         hi_ghost = self.s1 - self.z1              # planes [z1, s1) come from rank+1
         own0, own1 = self.z0 - self.s0, self.z1 - self.s0   # local indices of the owned range
-        if self.rank > 0 and lo_ghost > 0:
-            ops.append(dist.P2POp(dist.isend, self.vol.planes(own0, own0 + lo_ghost), self.rank - 1))
-            ops.append(dist.P2POp(dist.irecv, self.vol.planes(0, lo_ghost), self.rank - 1))
-        if self.rank < self.world - 1 and hi_ghost > 0:
-            ops.append(dist.P2POp(dist.isend, self.vol.planes(own1 - hi_ghost, own1), self.rank + 1))
-            ops.append(dist.P2POp(dist.irecv, self.vol.planes(own1, own1 + hi_ghost), self.rank + 1))
+        for vol in (self.vol, self.cvol) if self.color else (self.vol,):   # (the colour planes in the same batch, behind the SDF planes on every rank)
+            if self.rank > 0 and lo_ghost > 0:
+                ops.append(dist.P2POp(dist.isend, vol.planes(own0, own0 + lo_ghost), self.rank - 1))
+                ops.append(dist.P2POp(dist.irecv, vol.planes(0, lo_ghost), self.rank - 1))
+            if self.rank < self.world - 1 and hi_ghost > 0:
+                ops.append(dist.P2POp(dist.isend, vol.planes(own1 - hi_ghost, own1), self.rank + 1))
+                ops.append(dist.P2POp(dist.irecv, vol.planes(own1, own1 + hi_ghost), self.rank + 1))
         self._p2p(ops)
 
     def ExtractMesh(self):
         """This rank's part of the model's mesh (include/kfx_mesh.h): the cubes whose lower plane it owns, [z0, min(z1, D - 1)),
-        every triangle bit-identical to the single-volume mesh's, in emission order; (verts, norms) device tensors.  No colour.
+        every triangle bit-identical to the single-volume mesh's, in emission order; (verts, norms) device tensors, or -- color=True --
+        (verts, norms, colors) with the single-volume mesh's colours.
         With halo = "exchange" the ghost planes the normals read are refreshed first (a collective step: every rank calls)."""
         from . import mesh
         if self.sframe is not None:
@@ -707,14 +738,15 @@ class SlabPipeline(FramePipeline):
             self.exchange_halos()     # (the C driver's fuse step leaves them current itself)
         D = self.dims[2]
         slab = (D, self.s0, float(self.full_boxmin[2]), float(self.full_boxmax[2]), self.z0, self.z1)
-        verts, norms, _ = mesh.ExtractMesh(self.vol, slab=slab)
-        return verts, norms
+        verts, norms, colors = mesh.ExtractMesh(self.vol, self.cvol if self.color else None, slab=slab)
+        return (verts, norms, colors) if self.color else (verts, norms)
 
     def SaveMesh(self, prefix, binary=True):
-        """Writes this rank's part as prefix.r<rank>.ply; returns its triangle count."""
+        """Writes this rank's part as prefix.r<rank>.ply (with colours when color=True); returns its triangle count."""
         from . import mesh
-        verts, norms = self.ExtractMesh()
-        mesh.write_ply("%s.r%d.ply" % (prefix, self.rank), verts.cpu().numpy(), norms.cpu().numpy(), None, binary)
+        verts, norms, *colors = self.ExtractMesh()
+        mesh.write_ply("%s.r%d.ply" % (prefix, self.rank), verts.cpu().numpy(), norms.cpu().numpy(),
+                       colors[0].cpu().numpy() if colors and colors[0] is not None else None, binary)
         return len(verts) // 3
 
     def raycast(self, T_wc):
@@ -737,7 +769,10 @@ class SlabPipeline(FramePipeline):
             self.raycast_exact_allreduce(T_wc, d, n, i, K)
             return
         self.wait_composite()   # the previous frame's merge still reads these images
-        self.ops.RaycastSdf(d, n, i, self.vol, T_wc, K, self.near, self.far, self.trunc, True)
+        if self.color:   # each rank renders its local view in colour; the merge carries img as it carries the shade
+            self.ops.RaycastSdfColor(d, n, i, self.vol, self.cvol, T_wc, K, self.near, self.far, self.trunc, True)
+        else:
+            self.ops.RaycastSdf(d, n, i, self.vol, T_wc, K, self.near, self.far, self.trunc, True)
         if self.world > 1:
             if self.overlap and (self.halo == "exchange" or self.inputs == "broadcast"):
                 raise RuntimeError("SlabPipeline: overlapped merge with halo='exchange' or inputs='broadcast' (see __init__)")
@@ -846,7 +881,10 @@ class SlabPipeline(FramePipeline):
         from_lo = self._scratch("from_lo", (5, h, w), torch.int32, d) if self.rank > 0 else None
         from_hi = self._scratch("from_hi", (5, h, w), torch.int32, d) if self.rank < self.world - 1 else None
         for stage in range(stages):
-            o.RaycastSdfSlab(st, stage == 0, self.vol, slab, self.z0, self.z1, w, h, T_wc, K, self.near, self.far, self.trunc, True)
+            if self.color:   # the finalising rank writes the hit's colour into the shade plane: it travels where the shade travels
+                o.RaycastSdfSlabColor(st, stage == 0, self.vol, self.cvol, slab, self.z0, self.z1, w, h, T_wc, K, self.near, self.far, self.trunc, True)
+            else:
+                o.RaycastSdfSlab(st, stage == 0, self.vol, slab, self.z0, self.z1, w, h, T_wc, K, self.near, self.far, self.trunc, True)
             if self.world == 1:
                 break
             status, touched = st[3], march[4] != 0
@@ -1075,6 +1113,9 @@ class TrackingSlabPipeline(SlabPipeline):
 
     def __init__(self, ops, dist, dims, boxmin, boxmax, w, h, its=None, icp_c=0.1, max_rmse=0.10, **kw):
         from . import tracking
+        if kw.get("color"):
+            raise ValueError("TrackingSlabPipeline: color=True is not built (tracked colour slabs: the tracker fuses its pyramids' level 0 and renders "
+                             "pyramid levels, the colour slab path fuses and renders the frame's own images)")
         if kw.get("inputs", "replicate") != "replicate":
             raise ValueError("TrackingSlabPipeline: inputs='broadcast' is not implemented (every rank builds the frame's pyramids itself)")
         if kw.get("overlap"):

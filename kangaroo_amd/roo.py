@@ -645,6 +645,17 @@ def RaycastSdfSlab(state, init, vol, slab, own_lo, own_hi, w, h, T_wc, K, near, 
                                                 w, h, t, k, near, far, trunc_dist, 1 if subpix else 0, _stream(stream)))
 
 
+def RaycastSdfSlabColor(state, init, vol, colorVol, slab, own_lo, own_hi, w, h, T_wc, K, near, far, trunc_dist, subpix=True, stream=None):
+    """kfx_raycast_sdf_slab_color (include/kfx_slab_color.h): RaycastSdfSlab whose finalising rank writes the colour volume's sample
+    at the hit into the shade plane.  colorVol: the rank's colour slab (kind "c32"), the planes and the box of `vol`."""
+    assert state.dtype == torch.float32 and state.is_contiguous() and tuple(state.shape) == (9, h, w)
+    t, _t = _fp(T_wc, 12)
+    k, _k = _fp(K, 4)
+    sl = _lib.KfxSlab(int(slab[0]), int(slab[1]), float(slab[2]), float(slab[3]))
+    _lib.check(_lib.load().kfx_raycast_sdf_slab_color(C.c_void_p(state.data_ptr()), 1 if init else 0, vol.ref(), colorVol.ref(), C.byref(sl), own_lo, own_hi,
+                                                      w, h, t, k, near, far, trunc_dist, 1 if subpix else 0, _stream(stream)))
+
+
 def RaycastStateToImages(depth, norm, img, state, stream=None):
     """kfx_raycast_state_to_images: final march state -> depth / normal / shade images."""
     _lib.check(_lib.load().kfx_raycast_state_to_images(depth.ref(), norm.ref(), img.ref(), C.c_void_p(state.data_ptr()), _stream(stream)))
@@ -693,6 +704,19 @@ def SdfFuseColor(vol, colorVol, depth, norm, T_cw, K, img, T_iw, Kimg, trunc_dis
         return
     _lib.check(_lib.load().kfx_sdf_fuse_color(vol.ref(), colorVol.ref(), depth.ref(), norm.ref(), t, k, img.ref(), ti, ki, trunc_dist,
                                               max_w, mincostheta, 1 if full_extent else 0, _stream(stream)))
+
+
+def SdfFuseColorSlab(vol, colorVol, slab, depth, norm, T_cw, K, img, T_iw, Kimg, trunc_dist, max_w, mincostheta, full_extent="slab", stream=None):
+    """kfx_sdf_fuse_color_slab (include/kfx_slab_color.h): SdfFuseColor on planes [z_offset, z_offset + d) of a larger volume,
+    slab = (full_d, z_offset, full_zmin, full_zmax), bit-identical to the same planes of the monolithic colour fuse.  colorVol: the
+    same planes of the colour volume (kind "c32"), with the dimensions and the box of `vol`.  full_extent as SdfFuse's with a slab."""
+    t, _t = _fp(T_cw, 12)
+    k, _k = _fp(K, 4)
+    ti, _ti = _fp(T_iw, 12)
+    ki, _ki = _fp(Kimg, 4)
+    sl = _lib.KfxSlab(int(slab[0]), int(slab[1]), float(slab[2]), float(slab[3]))
+    _lib.check(_lib.load().kfx_sdf_fuse_color_slab(vol.ref(), colorVol.ref(), C.byref(sl), depth.ref(), norm.ref(), t, k, img.ref(), ti, ki, trunc_dist,
+                                                   max_w, mincostheta, 2 if full_extent == "slab" else (1 if full_extent else 0), _stream(stream)))
 
 
 def RaycastColorHits(outputs, colorVol, T_wc, K_levels, stream=None):

@@ -389,6 +389,21 @@ class SlabFrame:
     def reset(self, stream=None):
         _lib.check(_L().kfx_slab_frame_reset(self.handle, _stream(stream)))
 
+    def set_color(self, cvol, rgb=None, Kimg=None, T_cd=None):
+        """kfx_slab_frame_set_color (include/kfx_slab_color.h): from now on step() fuses with the colour SdfFuse at T_iw = T_cd * T_cw
+        and renders colour.  cvol: this rank's colour slab (kind "c32", the geometry of the frame's volume), rgb: the "u8x3" image
+        the steps read, Kimg: the colour camera's intrinsics, T_cd: colour <- depth camera (3x4 or 4x4; None: identity).
+        cvol = None returns the frame to grey.  Every rank makes the same call."""
+        if cvol is None:
+            self._color_keep = None
+            _lib.check(_L().kfx_slab_frame_set_color(self.handle, None, None, None, None))
+            return
+        ki = np.ascontiguousarray(np.asarray(Kimg, np.float32).reshape(4))
+        tcd = None if T_cd is None else np.ascontiguousarray(np.asarray(T_cd, np.float32).reshape(-1, 4)[:3].reshape(-1))
+        self._color_keep = (cvol, rgb)   # the frame holds raw pointers into these
+        _lib.check(_L().kfx_slab_frame_set_color(self.handle, cvol.ref(), rgb.ref(), ki.ctypes.data_as(_lib.PF),
+                                                 None if tcd is None else tcd.ctypes.data_as(_lib.PF)))
+
     @property
     def count(self):
         return int(_L().kfx_slab_frame_count(self.handle))
