@@ -48,6 +48,12 @@ int kfx_debug_summary_export(kfx_sdf_summary* s, float tol, float vref, int fine
  * builds that built, out[1] = conditional builds that returned early, both since the summary was created (waits for `stream`). */
 int kfx_debug_summary_conditional_builds(kfx_sdf_summary* s, int out[2], kfx_stream stream);
 
+/* The kept set of the last tracked SdfFuse launch on the summary's volume (KFX_FUSE_KEEP_MB): the rows of y-bricks (8 voxel
+ * rows each, indexed in the summary's volume) whose cells the launch read with ordinary loads, so that they stay in the
+ * memory-side cache for the next frame.  out = {stride (0: nothing kept), first row the launch covered, rows it covered};
+ * kept[r] = 1 for every kept row r < n_rows of the volume, else 0 (kept may be NULL).  Host-side state: nothing to wait for. */
+int kfx_debug_fuse_keep(const kfx_sdf_summary* s, int out[3], unsigned char* kept, int n_rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -300,3 +300,12 @@ extern "C" int kfx_debug_summary_conditional_builds(kfx_sdf_summary* s, int out[
         return set_error(KFX_E_RANGE, "kfx_debug_summary_conditional_builds: copy");
     return 0;
 }
+
+extern "C" int kfx_debug_fuse_keep(const kfx_sdf_summary* s, int out[3], unsigned char* kept, int n_rows)
+{
+    if (!s || !out) return set_error(KFX_E_NULL, "kfx_debug_fuse_keep: null argument");
+    out[0] = s->keep_stride; out[1] = s->keep_row0; out[2] = s->keep_rows;
+    for (int r = 0; kept && r < n_rows; ++r)
+        kept[r] = (r >= s->keep_row0 && r < s->keep_row0 + s->keep_rows && keep_row(r, s->keep_stride)) ? 1 : 0;
+    return 0;
+}

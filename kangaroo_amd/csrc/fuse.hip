@@ -63,9 +63,9 @@ struct FuseParams {
     float trunc, max_w, mincos;
     unsigned dpitch, npitch; // image pitches as 32-bit values (valid when `small_images`)
     int exact_shared;        // exact mode: camera / thresholds allow the shared-reciprocal arithmetic (see finish_shared)
-    // serpentine sweep of the tracked launches (fuse_launch): z-bricks from the far end, and the planes [keep_z0, keep_z1) of
-    // this launch read with ordinary loads
-    int z_rev, keep_z0, keep_z1;
+    // serpentine sweep of the tracked launches (fuse_launch): z-bricks from the far end; and the kept set: the workgroups whose
+    // y-brick row in the PARENT volume, keep_row0 + blockIdx.y, is a multiple of keep_stride read with ordinary loads (0: none)
+    int z_rev, keep_stride, keep_row0;
     // brick summary maintained by the TRACK kernels (kfx_sdf_summary, summary.hip): one float4 {lo, hi, state, -} per
     // 8 x 8 x 8 cells of the PARENT volume; (sum_bx0, sum_by0, sum_bz0) = brick index of this view's first cell
     float4* sum_R;
@@ -594,7 +594,7 @@ __global__ __launch_bounds__(64 * NW, (FAST && ZU == 2) ? 8 : (!FAST ? 6 : 1)) v
     const int x0 = (bxi * LX + (lane & (LX - 1))) * 2;
     const int y = blockIdx.y * BY + (wv % WY) * RW + lane / LX;
     const int zbeg = bzi * ZC;
-    const bool keep = TRACK && zbeg >= p.keep_z0 && zbeg < p.keep_z1;
+    const bool keep = TRACK && keep_row(p.keep_row0 + (int)blockIdx.y, p.keep_stride);
     const int zend = min(zbeg + ZC, p.Z);
     const int wz0 = zbeg + (wv / WY) * ZW, wz1 = min(wz0 + ZW, zend); // this wave's slices
     const bool live = x0 < p.X && y < p.Y;
@@ -884,12 +884,13 @@ __global__ __launch_bounds__(64 * NW, (FAST && ZU == 2) ? 8 : (!FAST ? 6 : 1)) v
         };
         const bool upd = !TRACK || live;   // TRACK: a lane outside the extents observes like the others and updates nothing
 
-        // the cell pairs of up to ZU slices.  `keep` bricks (TRACK: the planes the next sweep starts with) use ordinary loads,
+        // the cell pairs of up to ZU slices.  `keep` bricks (TRACK: the kept rows of y-bricks, fuse_launch) use ordinary loads,
         // which leave the lines in the 256 MiB memory-side cache.  Written as asm: given `keep ? plain load : nontemporal
         // load` of one address hipcc emits a single plain load for both cases.  The compiler does not know the loads are in
         // flight: the wait's "+v" operands keep the destination registers allocated and untouched until the data has arrived
         // (the idiom of RayF32::issue / finish, sampling.h); tests/test_gpu_chain.py and test_gpu_summary.py compare the
-        // tracked volume with the untracked one bit for bit, at sizes where all and where a quarter of the planes take this path.
+        // tracked volume with the untracked one bit for bit, at sizes where all and where a quarter of the bricks take this path
+        // (tests/test_gpu_fuse_keep.py: further strides, a ragged volume and views of a larger one).
         auto load_cells = [&](float4 (&c)[ZU], const bool (&any)[ZU], const unsigned char* at) {
             // (half cells take the streamed loads on the keep planes too: the same asm for their 8-byte pairs left the fast tracked
             // half kernels waiting for the previous iteration's stores inside the observation blocks, scripts/check_fuse_codegen.py)
@@ -1486,7 +1487,7 @@ __device__ __forceinline__ void color_track_epilogue(const FuseParams& p, const 
 
 // TRACK: besides the update the kernel keeps the brick summary current, as k_sdf_fuse_tiled<.., TRACK = true> does: every lane
 // stays in the march (`live` only gates the updates), so the ballots and DPP reductions run in wave-uniform control flow; the
-// workgroup-uniform early exits leave the summary as it is (nothing was written).  No serpentine sweep, no "keep" planes.
+// workgroup-uniform early exits leave the summary as it is (nothing was written).  No serpentine sweep, no kept set.
 template <bool FAST, bool TRACK = false>
 __global__ __launch_bounds__(256) void k_sdf_fuse_color_tiled(const FuseParams p, const ColorParams q, const int cap_px, const int cap_cpx)
 {
@@ -2080,20 +2081,27 @@ static int fuse_launch(const kfx_volume* vol, const kfx_image* depth, const kfx_
             if (t.dxt && !all_dxt) { t = TilePlan{0, tile_cap(p, p.T, p.K, za, zb, fast), 0}; if (cap_env) t.cap = cap_env; }
             return t;
         };
-        // Tracked launches sweep the planes in serpentine order -- every other launch from the far end -- and read the last
-        // KFX_FUSE_KEEP_MB (default 256) of a sweep with ordinary loads: those planes stay in the 256 MiB memory-side cache
-        // and the next sweep starts on them.  (The volume is otherwise streamed nontemporally, which leaves nothing behind;
-        // untracked launches belong to loops whose plain march reads ~500 MB of the volume in between and evicts the tail.)
+        // The kept set of the tracked launches.  The volume is streamed nontemporally, which leaves nothing behind in the 256 MiB
+        // memory-side cache; the workgroups of every keep_stride-th row of y-bricks (8 voxel rows, counted in the PARENT volume:
+        // the same cells whatever view, z-range or frame a launch belongs to) read their cells with ordinary loads instead, and
+        // those lines are still there when the next frame asks for them.  KFX_FUSE_KEEP_MB (default 256, 0: off) is the size of
+        // the set: stride = ceil(volume bytes / kept bytes), a volume within the budget is kept whole.  The rows are spread
+        // through every z-layer, so the hits arrive evenly in time -- a launch co-limited by vector issue can only use the HBM
+        // relief it gets while it is waiting for HBM (a kept range of planes gave its hits all at once: DESIGN 5.1).
+        // Tracked launches also sweep the planes in serpentine order, every other launch from the far end: the kept set and the
+        // frame's other ordinary traffic (images, texels, the march's samples: 55-70 MB) do not quite fit the cache together at the
+        // default size, and a set read forwards then backwards loses its oldest lines only, where one read forwards every time
+        // loses them all (512^3, 256 MB: 0.3245 ms with the reversal, 0.3536 ms without; EXPERIMENTS section 2).
+        // (Untracked launches belong to loops whose plain march reads ~500 MB of the volume in between and evicts the set.)
         static const int keep_mb = env_int("KFX_FUSE_KEEP_MB", 256);
         const int rev = (track && keep_mb > 0) ? (int)(summary->sweeps++ & 1u) : 0;
-        int keep_lo = 0, keep_hi = 0;   // planes read with ordinary loads (this view's local coordinates)
-        if (track && keep_mb > 0) {
-            const size_t plane = (size_t)p.vimg_pitch;
-            int n = (int)(((size_t)keep_mb << 20) / (plane ? plane : 1));
-            n = n / FUSE_ZC * FUSE_ZC;
-            if (n > p.Z) n = p.Z;
-            if (rev) { keep_lo = 0; keep_hi = n; } else { keep_lo = p.Z - n; keep_hi = p.Z; }
+        int keep_stride = 0;
+        if (track && keep_mb > 0 && fast && CELL::BYTES == 8) {   // (the kernels with the ordinary-load path: load_cells)
+            const size_t vol_bytes = summary->img_pitch * (size_t)summary->d, budget = (size_t)keep_mb << 20;
+            keep_stride = (int)((vol_bytes + budget - 1) / budget);
+            if (keep_stride < 1) keep_stride = 1;
         }
+        if (track) { summary->keep_stride = keep_stride; summary->keep_row0 = p.sum_by0; summary->keep_rows = ceil_div(p.Y, TB_Y); }
         struct Range { int z0, z1; TilePlan plan; };
         Range ranges[64];
         int n_ranges = 0;
@@ -2137,7 +2145,7 @@ static int fuse_launch(const kfx_volume* vol, const kfx_image* depth, const kfx_
             const int cap_px = plan.cap;
             FuseParams q = z_range(p, rg.z0, rg.z1);
             q.z_rev = rev;
-            q.keep_z0 = keep_lo - rg.z0; q.keep_z1 = keep_hi - rg.z0;
+            q.keep_stride = keep_stride; q.keep_row0 = p.sum_by0;
             const size_t lds = (size_t)cap_px * sizeof(float4) * (plan.dxt ? 2 : 1);
             const int zu = zu_env ? zu_env : (fast ? (cap_px > 2560 ? 4 : 2) : 1);
             const bool nw8 = fast && nw8_from > 0 && cap_px > nw8_from;

@@ -218,6 +218,9 @@ struct VolView {
 
 __host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// The tracked SdfFuse's kept set (fuse.hip, fuse_launch): y-brick row `row` of the parent volume belongs to it
+__host__ __device__ inline bool keep_row(int row, int stride) { return stride > 0 && (unsigned)row % (unsigned)stride == 0u; }
+
 } // namespace kfx
 
 // ---- brick summary of a TSDF volume (kfx_sdf_summary, include/kfx.h; summary.hip) -----------------------------------
@@ -256,6 +259,9 @@ struct kfx_sdf_summary {
     unsigned builds;             // table builds issued so far
     unsigned plain_calls;        // tracked raycasts since the choice last fell on the plain march (the tables are then rebuilt every 8th call only)
     unsigned sweeps;             // tracked SdfFuse launches so far: every other one walks the planes from the far end (fuse.hip)
+    // the kept set of the last tracked SdfFuse launch (fuse.hip, fuse_launch; read by kfx_debug_fuse_keep): the y-brick rows
+    // [keep_row0, keep_row0 + keep_rows) of the parent volume it covered, those with keep_row(row, keep_stride) read with ordinary loads
+    int keep_stride, keep_row0, keep_rows;
 };
 namespace kfx {
 // The class tables the march stages in LDS.  Per entry (a cube of 2^shift cells, together with the +1 cells a trilinear sample

@@ -390,6 +390,7 @@ static int summary_create(kfx_sdf_summary** out, const kfx_volume* vol, int cell
     s->pitch = vol->pitch; s->img_pitch = vol->img_pitch;
     s->R = nullptr; s->C = nullptr; s->d_count = nullptr; s->h_skippable = nullptr; s->d_skippable = nullptr;
     s->c_dirty = 2; s->c_tol = -1.f; s->c_vref = 0.f; s->c_shift = 0; s->c_global = 0; s->sweeps = 0;
+    s->keep_stride = 0; s->keep_row0 = 0; s->keep_rows = 0;
     s->c_lo_ok = 0.f; s->c_hi_ok = 0.f; s->d_dirty = nullptr;
     s->builds = 0; s->plain_calls = 0;
     for (auto& e : s->build_done) e = nullptr;

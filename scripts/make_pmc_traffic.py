@@ -30,7 +30,7 @@ def sections(path):
 
 # (name prefixes: the summaries cut kernel names at 60 characters, and later template arguments -- waves per workgroup -- follow)
 FUSE = {"fast": "k_sdf_fuse_tiled<true, 2, CellF32, 32, 4, 16, false, false", "fast_tracked": "k_sdf_fuse_tiled<true, 2, CellF32, 32, 4, 16, true, false"}
-RAY = {"fast": "k_raycast_sdf<RayF32, false>", "fast_tracked": "k_raycast_sdf_classes<RayF32>"}
+RAY = {"fast": "k_raycast_sdf<RayF32, false>", "fast_tracked": "k_raycast_sdf_classes<RayF32, false>"}   # (<RAY, COLOR>)
 
 
 def main():
