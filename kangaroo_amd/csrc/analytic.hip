@@ -113,8 +113,8 @@ __global__ __launch_bounds__(256) void k_sdf_distance(const DistParams p)
 
 static int pix_params(PixParams& p, const kfx_image* imgd, const kfx_image* img, const float T_wc[12], const float K[4], const char* what)
 {
-    if (!imgd || !imgd->ptr || !T_wc || !K) return set_error(KFX_E_NULL, what);
-    if (imgd->pitch < imgd->w * 4 || (((uintptr_t)imgd->ptr | imgd->pitch) & 3)) return set_error(KFX_E_SHAPE, what);
+    if (!T_wc || !K) return set_error(KFX_E_NULL, what);
+    if (int e = check_image(imgd, 4, 0, 0, what)) return e;
     p.dptr = (unsigned char*)imgd->ptr;
     p.dpitch = imgd->pitch;
     p.w = (int)imgd->w;
@@ -122,7 +122,7 @@ static int pix_params(PixParams& p, const kfx_image* imgd, const kfx_image* img,
     p.iptr = nullptr;
     p.ipitch = 0;
     if (img && img->ptr) {
-        if (img->w < imgd->w || img->h < imgd->h || img->pitch < imgd->w * 4 || (((uintptr_t)img->ptr | img->pitch) & 3)) return set_error(KFX_E_SHAPE, what);
+        if (int e = check_image(img, 4, imgd->w, imgd->h, what)) return e;
         p.iptr = (unsigned char*)img->ptr;
         p.ipitch = img->pitch;
     }
@@ -147,7 +147,7 @@ extern "C" int kfx_raycast_box(const kfx_image* imgd, const float T_wc[12], cons
     if (p.w == 0 || p.h == 0) return 0;
     p.a = V3{boxmin[0], boxmin[1], boxmin[2]};
     p.b = V3{boxmax[0], boxmax[1], boxmax[2]};
-    hipLaunchKernelGGL(k_raycast_box, dim3(ceil_div(p.w, 64), ceil_div(p.h, 4)), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(k_raycast_box, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("kfx_raycast_box");
 }
 
@@ -164,7 +164,7 @@ extern "C" int kfx_raycast_sphere(const kfx_image* imgd, const kfx_image* img, c
     const float ax = center[0] - T[3], ay = center[1] - T[7], az = center[2] - T[11]; // MatUtils.h:192-200
     p.a = V3{T[0] * ax + T[4] * ay + T[8] * az, T[1] * ax + T[5] * ay + T[9] * az, T[2] * ax + T[6] * ay + T[10] * az};
     p.r = r;
-    hipLaunchKernelGGL(k_raycast_sphere, dim3(ceil_div(p.w, 64), ceil_div(p.h, 4)), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(k_raycast_sphere, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("kfx_raycast_sphere");
 }
 
@@ -181,7 +181,7 @@ extern "C" int kfx_raycast_plane(const kfx_image* imgd, const kfx_image* img, co
     const float dn = T[3] * n_w[0] + T[7] * n_w[1] + T[11] * n_w[2] + 1.0f;
     p.a = V3{(T[0] * n_w[0] + T[4] * n_w[1] + T[8] * n_w[2]) / dn, (T[1] * n_w[0] + T[5] * n_w[1] + T[9] * n_w[2]) / dn,
              (T[2] * n_w[0] + T[6] * n_w[1] + T[10] * n_w[2]) / dn};
-    hipLaunchKernelGGL(k_raycast_plane, dim3(ceil_div(p.w, 64), ceil_div(p.h, 4)), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(k_raycast_plane, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("kfx_raycast_plane");
 }
 
@@ -193,10 +193,9 @@ extern "C" int kfx_sdf_distance(const kfx_image* dist, const kfx_image* depth, c
     (void)trunc_distance;
     if (!dist || !depth || !vol || !dist->ptr || !depth->ptr || !vol->ptr || !T_wc || !K) return set_error(KFX_E_NULL, "SdfDistance: null argument");
     if (depth->w == 0 || depth->h == 0) return 0;
-    if (dist->w < depth->w || dist->h < depth->h || dist->pitch < depth->w * 4 || depth->pitch < depth->w * 4)
-        return set_error(KFX_E_SHAPE, "SdfDistance: image sizes");
+    if (int e = check_image(depth, 4, 0, 0, "SdfDistance: depth image")) return e;
+    if (int e = check_image(dist, 4, depth->w, depth->h, "SdfDistance: distance image")) return e;
     if (int e = check_volume(vol, 8, 2, VOLUME_ANY_DIM, "SdfDistance")) return e;
-    if (((uintptr_t)dist->ptr | dist->pitch | (uintptr_t)depth->ptr | depth->pitch) & 3) return set_error(KFX_E_ALIGN, "SdfDistance: image alignment");
     DistParams p;
     set_geometry(p, vol);
     p.optr = (unsigned char*)dist->ptr; p.opitch = dist->pitch;
@@ -204,6 +203,6 @@ extern "C" int kfx_sdf_distance(const kfx_image* dist, const kfx_image* depth, c
     p.w = (int)depth->w; p.h = (int)depth->h;
     for (int i = 0; i < 12; ++i) p.T.m[i] = T_wc[i];
     p.K = Intr{K[0], K[1], K[2], K[3]};
-    hipLaunchKernelGGL(k_sdf_distance, dim3(ceil_div(p.w, 64), ceil_div(p.h, 4)), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(k_sdf_distance, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("kfx_sdf_distance");
 }

@@ -16,6 +16,7 @@
 // seven links at once) against 2 x 7/8 x (2.4 + 4.9) MB in 14 dependent ring steps; same winner per pixel as the key's minimum.
 // No reference counterpart (the reference is single-GPU).
 #include "kfx_device.h"
+#include "host_args.h"
 
 namespace kfx {
 
@@ -137,12 +138,10 @@ using namespace kfx;
 static int comp_params(CompParams& p, const kfx_image* depth, const kfx_image* norm, const kfx_image* img, long long* key,
                        float* payload, int rank)
 {
-    if (!depth || !norm || !img || !depth->ptr || !norm->ptr || !img->ptr || !key) return set_error(KFX_E_NULL, "composite: null argument");
-    if (norm->w < depth->w || norm->h < depth->h || img->w < depth->w || img->h < depth->h) return set_error(KFX_E_SHAPE, "composite: image sizes");
+    if (!key) return set_error(KFX_E_NULL, "composite: null argument");
     if (rank < 0 || rank > 255) return set_error(KFX_E_RANGE, "composite: rank must fit 8 bits");
-    if ((((uintptr_t)norm->ptr | norm->pitch) & 15) || (((uintptr_t)depth->ptr | depth->pitch | (uintptr_t)img->ptr | img->pitch) & 3) ||
-        ((uintptr_t)key & 7) || ((uintptr_t)payload & 15))
-        return set_error(KFX_E_ALIGN, "composite: alignment");
+    if (int e = check_render_images(depth, norm, img, depth, "composite")) return e;
+    if (((uintptr_t)key & 7) || ((uintptr_t)payload & 15)) return set_error(KFX_E_ALIGN, "composite: alignment");
     p = CompParams{(unsigned char*)depth->ptr, (unsigned char*)norm->ptr, (unsigned char*)img->ptr, depth->pitch, norm->pitch, img->pitch,
                    key, payload, (int)depth->w, (int)depth->h, rank};
     return 0;
@@ -153,7 +152,7 @@ extern "C" int kfx_composite_pack(const kfx_image* depth, const kfx_image* norm,
     CompParams p;
     if (int e = comp_params(p, depth, norm, img, key, nullptr, rank)) return e;
     if (p.w == 0 || p.h == 0) return 0;
-    hipLaunchKernelGGL(k_composite_pack, dim3(ceil_div(p.w, 64), ceil_div(p.h, 4)), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(k_composite_pack, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("kfx_composite_pack");
 }
 
@@ -164,7 +163,7 @@ extern "C" int kfx_composite_select(const kfx_image* depth, const kfx_image* nor
     if (!payload) return set_error(KFX_E_NULL, "composite: null payload");
     if (int e = comp_params(p, depth, norm, img, const_cast<long long*>(key), payload, rank)) return e;
     if (p.w == 0 || p.h == 0) return 0;
-    hipLaunchKernelGGL(k_composite_select, dim3(ceil_div(p.w, 64), ceil_div(p.h, 4)), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(k_composite_select, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("kfx_composite_select");
 }
 
@@ -175,7 +174,7 @@ extern "C" int kfx_composite_unpack(const kfx_image* depth, const kfx_image* nor
     if (!payload) return set_error(KFX_E_NULL, "composite: null payload");
     if (int e = comp_params(p, depth, norm, img, const_cast<long long*>(key), const_cast<float*>(payload), 0)) return e;
     if (p.w == 0 || p.h == 0) return 0;
-    hipLaunchKernelGGL(k_composite_unpack, dim3(ceil_div(p.w, 64), ceil_div(p.h, 4)), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(k_composite_unpack, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("kfx_composite_unpack");
 }
 
@@ -189,11 +188,10 @@ extern "C" size_t kfx_composite_strip_pixels(size_t w, size_t h, int world)
 
 static int strip_params(StripParams& p, const kfx_image* depth, const kfx_image* norm, const kfx_image* img, float* buf, size_t stride, int world)
 {
-    if (!depth || !norm || !img || !depth->ptr || !norm->ptr || !img->ptr || !buf) return set_error(KFX_E_NULL, "composite strips: null argument");
-    if (norm->w < depth->w || norm->h < depth->h || img->w < depth->w || img->h < depth->h) return set_error(KFX_E_SHAPE, "composite strips: image sizes");
+    if (!buf) return set_error(KFX_E_NULL, "composite strips: null argument");
     if (world < 1 || world > 256) return set_error(KFX_E_RANGE, "composite strips: world in [1, 256]");
-    if ((((uintptr_t)norm->ptr | norm->pitch) & 15) || (((uintptr_t)depth->ptr | depth->pitch | (uintptr_t)img->ptr | img->pitch | (uintptr_t)buf) & 3))
-        return set_error(KFX_E_ALIGN, "composite strips: alignment");
+    if (int e = check_render_images(depth, norm, img, depth, "composite strips")) return e;
+    if ((uintptr_t)buf & 3) return set_error(KFX_E_ALIGN, "composite strips: alignment");
     const size_t S = kfx_composite_strip_pixels(depth->w, depth->h, world);
     if (S > 0x7fffffffull) return set_error(KFX_E_RANGE, "composite strips: image too large");
     if (stride && stride < KFX_COMPOSITE_STRIP_PLANES * S) return set_error(KFX_E_SHAPE, "composite strips: rank stride smaller than a strip");
@@ -230,6 +228,6 @@ extern "C" int kfx_composite_strips_unpack(const kfx_image* depth, const kfx_ima
     StripParams p;
     if (int e = strip_params(p, depth, norm, img, const_cast<float*>(strips), rank_stride, world)) return e;
     if (p.w == 0 || p.h == 0) return 0;
-    hipLaunchKernelGGL(k_strips_unpack, dim3(ceil_div(p.w, 64), ceil_div(p.h, 4)), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(k_strips_unpack, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("kfx_composite_strips_unpack");
 }

@@ -1794,12 +1794,9 @@ static int fuse_params(FuseParams& p, bool* small_images, const kfx_volume* vol,
                        float mincostheta, unsigned flags, size_t cell, const kfx_slab* slab)
 {
     if (int e = check_volume(vol, cell, 1, VOLUME_MAX_DIM, "SdfFuse")) return e;
-    if (!depth || !norm || !depth->ptr || !norm->ptr || !T_cw || !K) return set_error(KFX_E_NULL, "SdfFuse: null argument");
-    if (depth->w < 4 || depth->h < 4 || norm->w < depth->w || norm->h < depth->h)
-        return set_error(KFX_E_SHAPE, "SdfFuse: depth/normal image dimensions");
-    if (depth->pitch < depth->w * 4 || norm->pitch < depth->w * 16) return set_error(KFX_E_SHAPE, "SdfFuse: image pitch");
-    if ((((uintptr_t)depth->ptr | depth->pitch) & 3) || (((uintptr_t)norm->ptr | norm->pitch) & 15))
-        return set_error(KFX_E_ALIGN, "SdfFuse: image alignment");
+    if (!T_cw || !K) return set_error(KFX_E_NULL, "SdfFuse: null argument");
+    if (int e = check_image(depth, 4, 4, 4, "SdfFuse: depth image (4 x 4 or larger)")) return e;
+    if (int e = check_image(norm, 16, depth->w, depth->h, "SdfFuse: normal image")) return e;
     p = FuseParams{};   // no slab offset, no summary, no packed texels, no serpentine sweep: fuse_launch fills in what a launch has
     p.vptr = (unsigned char*)vol->ptr;
     p.vpitch = vol->pitch;
@@ -2126,7 +2123,7 @@ static int fuse_launch(const kfx_volume* vol, const kfx_image* depth, const kfx_
             } else {
                 void* buf = tex_scratch(tl.bytes, s);   // (tpitch < 2^24: small_images bounds the normal map's pitch, which is at least as long)
                 if (!buf) return set_error((int)hipErrorOutOfMemory, "SdfFuse: no device memory for the packed texel image");
-                hipLaunchKernelGGL(k_pack_texels, dim3(ceil_div((int)depth->w, 64), ceil_div((int)depth->h, 4)), dim3(256), 0, s, p.depth, p.norm,
+                hipLaunchKernelGGL(k_pack_texels, pixel_grid((int)depth->w, (int)depth->h), dim3(256), 0, s, p.depth, p.norm,
                                    (unsigned char*)buf, tl.tpitch, reinterpret_cast<float*>((unsigned char*)buf + tl.bmax_off), tl.bw8);
                 p.tex = (const unsigned char*)buf;
             }
@@ -2303,12 +2300,12 @@ static int fuse_color_launch(const kfx_volume* vol, const kfx_volume* colorvol, 
     bool small_images = false;
     if (int e = fuse_params(p, &small_images, vol, depth, norm, T_cw, K, trunc_dist, max_w, mincostheta, flags | KFX_FUSE_FULL_EXTENT, 8, slab)) return e;
     if (int e = check_volume(colorvol, 4, 1, VOLUME_MAX_DIM, "SdfFuse(colour)")) return e;
-    if (!img || !img->ptr || !T_iw || !Kimg) return set_error(KFX_E_NULL, "SdfFuse(colour): null argument");
+    if (!T_iw || !Kimg) return set_error(KFX_E_NULL, "SdfFuse(colour): null argument");
     if (slab) {
         if (int e = kfx::check_color_slab(vol, colorvol, "SdfFuse(colour, slab)")) return e;
     }
     if (colorvol->w < vol->w || colorvol->h < vol->h || colorvol->d < vol->d) return set_error(KFX_E_SHAPE, "SdfFuse(colour): colour volume smaller than the SDF volume");
-    if (img->w < 4 || img->h < 4 || img->pitch < img->w * 3) return set_error(KFX_E_SHAPE, "SdfFuse(colour): rgb image dimensions");
+    if (int e = check_image(img, 3, 4, 4, "SdfFuse(colour): rgb image (4 x 4 or larger)")) return e;
     if (!(flags & KFX_FUSE_FULL_EXTENT)) { // the reference's 16x16 launch over x / y, all of z (cu_sdffusion.cu:132-135)
         p.X = (int)(vol->w / 16) * 16;
         p.Y = (int)(vol->h / 16) * 16;

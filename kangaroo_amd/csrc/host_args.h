@@ -1,5 +1,5 @@
-// host_args.h -- what the launchers decide alike on the host: what a usable kfx_volume is, how a Z-slab is seen through the
-// whole volume's geometry, how a process-wide knob is read.
+// host_args.h -- what the launchers decide alike on the host: what a usable kfx_volume and a usable kfx_image are, the grid of a
+// per-pixel launch, how a Z-slab is seen through the whole volume's geometry, how a process-wide knob is read.
 #pragma once
 
 #include <cstdio>
@@ -15,13 +15,17 @@ constexpr size_t VOLUME_MAX_DIM = 65535, VOLUME_ANY_DIM = ~(size_t)0;
 
 // A usable volume of cell_bytes-byte cells: non-null, every dimension in [min_dim, max_dim], a row / a slice within its pitch,
 // pointer and pitches aligned to the cell -- in that order at every entry point.  `what` names the operator in the message.
+// "<what>: <rule>" as the last error
+inline int fail_rule(const char* what, int code, const char* rule)
+{
+    char msg[200];
+    snprintf(msg, sizeof(msg), "%s: %s", what, rule);
+    return set_error(code, msg);
+}
+
 inline int check_volume(const kfx_volume* vol, size_t cell_bytes, size_t min_dim, size_t max_dim, const char* what)
 {
-    auto fail = [what](int code, const char* rule) {
-        char msg[160];
-        snprintf(msg, sizeof(msg), "%s: %s", what, rule);
-        return set_error(code, msg);
-    };
+    auto fail = [what](int code, const char* rule) { return fail_rule(what, code, rule); };
     if (!vol || !vol->ptr) return fail(KFX_E_NULL, "null volume");
     if (vol->w < min_dim || vol->h < min_dim || vol->d < min_dim || vol->w > max_dim || vol->h > max_dim || vol->d > max_dim)
         return fail(KFX_E_SHAPE, "volume dimensions");
@@ -30,6 +34,39 @@ inline int check_volume(const kfx_volume* vol, size_t cell_bytes, size_t min_dim
     if (((uintptr_t)vol->ptr | vol->pitch | vol->img_pitch) & (cell_bytes - 1)) return fail(KFX_E_ALIGN, "volume not aligned to its cell size");
     return 0;
 }
+
+// A usable image of elem-byte pixels that covers min_w x min_h (the consumer's launch; 0, 0: any size): non-null; at least that
+// large, a row of its OWN w pixels within its pitch (rows of a usable view do not overlap), no dimension above 2^30 (kernels keep
+// pixel coordinates in int); pointer and pitch aligned to the largest power of two in elem, 16 at the most (3-byte RGB: bytes,
+// float4: 16) -- in that order at every entry point.  `what` names the operator and the image in the message.
+inline int check_image(const kfx_image* im, size_t elem, size_t min_w, size_t min_h, const char* what)
+{
+    if (!im || !im->ptr) return fail_rule(what, KFX_E_NULL, "null image");
+    if (im->w < min_w || im->h < min_h) return fail_rule(what, KFX_E_SHAPE, "image smaller than the launch");
+    if (im->pitch < im->w * elem) return fail_rule(what, KFX_E_SHAPE, "image pitch smaller than a row");
+    if (im->w > (1u << 30) || im->h > (1u << 30)) return fail_rule(what, KFX_E_SHAPE, "image dimensions above 2^30");
+    const size_t pow2 = elem & (~elem + 1), al = pow2 < 16 ? pow2 : 16;
+    if (((uintptr_t)im->ptr | im->pitch) & (al - 1)) return fail_rule(what, KFX_E_ALIGN, "image not aligned to its pixel size");
+    return 0;
+}
+
+// What the input of a launch bounded by `out` has to cover where the entry point answers an empty launch with 0 before it compares
+// sizes: nothing then.
+inline size_t cover_w(const kfx_image* out) { return out->h ? out->w : 0; }
+inline size_t cover_h(const kfx_image* out) { return out->w ? out->h : 0; }
+
+// The rendering trio -- depth (float), normals (float4), shading image (float) -- each covering `lead`, the one of the three that
+// bounds the launch (RaycastSdf: img, as the reference; the composite: depth).
+inline int check_render_images(const kfx_image* depth, const kfx_image* norm, const kfx_image* img, const kfx_image* lead, const char* what)
+{
+    if (!lead) return fail_rule(what, KFX_E_NULL, "null image");
+    if (int e = check_image(depth, 4, lead->w, lead->h, what)) return e;
+    if (int e = check_image(norm, 16, lead->w, lead->h, what)) return e;
+    return check_image(img, 4, lead->w, lead->h, what);
+}
+
+// the grid of a per-pixel launch: workgroups of 256 = 64 x 4 pixels
+inline dim3 pixel_grid(int w, int h) { return dim3(ceil_div(w, 64), ceil_div(h, 4)); }
 
 // The full volume a Z-slab (planes [z_offset, z_offset + d) of full_d) belongs to, for set_geometry / set_voxel_size: the base
 // pointer moved back by z_offset planes -- a virtual base, dereferenced only inside the stored planes -- and the full extent in z.

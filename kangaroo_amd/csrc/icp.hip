@@ -707,6 +707,15 @@ static bool icp_mailbox_env()
 
 using namespace kfx;
 
+// the float4 maps of one level: dPr / dNr cover dPl; a debug image, when given, covers dbg_w x dbg_h
+static int check_icp_images(const kfx_image* Pl, const kfx_image* Pr, const kfx_image* Nr, const kfx_image* debug, size_t dbg_w, size_t dbg_h, const char* what)
+{
+    if (int e = check_image(Pl, 16, 0, 0, what)) return e;
+    if (int e = check_image(Pr, 16, Pl->w, Pl->h, what)) return e;
+    if (int e = check_image(Nr, 16, Pl->w, Pl->h, what)) return e;
+    return debug ? check_image(debug, 16, dbg_w, dbg_h, what) : 0;
+}
+
 // LeastSquaresSystem<float,6> PoseRefinementProjectiveIcpPointPlane(dPl, dPr, dNr, KT_lr, T_rl, c, dWorkspace,
 // dDebug) (cu_model_refinement.cu:595-608).  Launch geometry as InitDimFromOutputImage(dPl, 16, 16)
 // (launch_utils.h:61-65): block = (gcd(w,16), gcd(h,16)), grid = (w / bx, h / by).  Blocks until the 116-byte
@@ -720,11 +729,8 @@ extern "C" int kfx_icp_point_plane(const kfx_image* Pl, const kfx_image* Pr, con
         return set_error(KFX_E_NULL, "PoseRefinementProjectiveIcpPointPlane: null argument");
     memset(out, 0, sizeof(*out));
     if (Pl->w == 0 || Pl->h == 0) return 0;
-    if (Pr->w < Pl->w || Pr->h < Pl->h || Nr->w < Pl->w || Nr->h < Pl->h || (debug && debug->ptr && (debug->w < Pl->w || debug->h < Pl->h)))
-        return set_error(KFX_E_SHAPE, "PoseRefinementProjectiveIcpPointPlane: dPr / dNr / dDebug smaller than dPl");
-    if ((((uintptr_t)Pl->ptr | Pl->pitch | (uintptr_t)Pr->ptr | Pr->pitch | (uintptr_t)Nr->ptr | Nr->pitch) & 15) || ((uintptr_t)workspace->ptr & 3) ||
-        (debug && debug->ptr && (((uintptr_t)debug->ptr | debug->pitch) & 15)))
-        return set_error(KFX_E_ALIGN, "PoseRefinementProjectiveIcpPointPlane: float4 images must be 16-byte aligned");
+    if (int e = check_icp_images(Pl, Pr, Nr, (debug && debug->ptr) ? debug : nullptr, Pl->w, Pl->h, "PoseRefinementProjectiveIcpPointPlane")) return e;
+    if ((uintptr_t)workspace->ptr & 3) return set_error(KFX_E_ALIGN, "PoseRefinementProjectiveIcpPointPlane: workspace alignment");
     const unsigned bx = gcd_u((unsigned)Pl->w, 16), by = gcd_u((unsigned)Pl->h, 16);
     const dim3 block(bx, by), grid((unsigned)(Pl->w / bx), (unsigned)(Pl->h / by));
     const size_t nblocks = (size_t)grid.x * grid.y;
@@ -819,10 +825,8 @@ static int icp_refine_impl(const kfx_icp_level* levels, int n_levels, float c, f
     size_t max_blocks = 0;
     for (int l = 0; l < n_levels; ++l) {
         const kfx_icp_level& L = levels[l];
-        if (!L.Pl.ptr || !L.Pr.ptr || !L.Nr.ptr) return set_error(KFX_E_NULL, "kfx_icp_refine: null image");
-        if (L.Pr.w < L.Pl.w || L.Pr.h < L.Pl.h || L.Nr.w < L.Pl.w || L.Nr.h < L.Pl.h) return set_error(KFX_E_SHAPE, "kfx_icp_refine: dPr / dNr smaller than dPl");
-        if (((uintptr_t)L.Pl.ptr | L.Pl.pitch | (uintptr_t)L.Pr.ptr | L.Pr.pitch | (uintptr_t)L.Nr.ptr | L.Nr.pitch) & 15)
-            return set_error(KFX_E_ALIGN, "kfx_icp_refine: float4 images must be 16-byte aligned");
+        // (a debug image smaller than a level is not written at that level)
+        if (int e = check_icp_images(&L.Pl, &L.Pr, &L.Nr, (debug && debug->ptr) ? debug : nullptr, 0, 0, "kfx_icp_refine")) return e;
         if (L.Pl.w == 0 || L.Pl.h == 0) continue;
         const unsigned bx = gcd_u((unsigned)L.Pl.w, 16), by = gcd_u((unsigned)L.Pl.h, 16);
         const size_t nb = (L.Pl.w / bx) * (L.Pl.h / by);
@@ -878,7 +882,7 @@ static int icp_refine_impl(const kfx_icp_level* levels, int n_levels, float c, f
             }
             q.n_levels = n_levels;
             q.c = c; q.max_rmse = max_rmse;
-            const bool dbg = debug && debug->ptr && !(((uintptr_t)debug->ptr | debug->pitch) & 15);
+            const bool dbg = debug && debug->ptr;
             q.dbg = dbg ? (unsigned char*)debug->ptr : nullptr;
             q.dbg_pitch = dbg ? debug->pitch : 0;
             q.dbg_w = dbg ? (int)debug->w : 0; q.dbg_h = dbg ? (int)debug->h : 0;
@@ -959,7 +963,7 @@ static int icp_refine_impl(const kfx_icp_level* levels, int n_levels, float c, f
         p.Pl = ImgView{(const unsigned char*)L.Pl.ptr, L.Pl.pitch, (int)L.Pl.w, (int)L.Pl.h};
         p.Pr = ImgView{(const unsigned char*)L.Pr.ptr, L.Pr.pitch, (int)L.Pr.w, (int)L.Pr.h};
         p.Nr = ImgView{(const unsigned char*)L.Nr.ptr, L.Nr.pitch, (int)L.Nr.w, (int)L.Nr.h};
-        const bool dbg = debug && debug->ptr && debug->w >= L.Pl.w && debug->h >= L.Pl.h && !(((uintptr_t)debug->ptr | debug->pitch) & 15);
+        const bool dbg = debug && debug->ptr && debug->w >= L.Pl.w && debug->h >= L.Pl.h;
         p.dbg = dbg ? (unsigned char*)debug->ptr : nullptr;
         p.dbg_pitch = dbg ? debug->pitch : 0;
         p.c = c;

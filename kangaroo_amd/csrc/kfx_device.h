@@ -365,6 +365,7 @@ int summary_view_offset(const kfx_sdf_summary* s, const kfx_volume* view, int* o
 namespace kfx {
 int set_error(int code, const char* what);
 int check_launch(const char* what);
+int hip_status(hipError_t e, const char* what);   // 0, or the error cleared and reported as `what`
 int math_mode(); // KFX_MATH_EXACT / KFX_MATH_FAST
 // kfx_frame_step's pair (frame.hip): the fused vbo / normals launch also writes the packed texel image {nx, ny, nz, depth} that the
 // SdfFuse of the same frame stages by LDS-DMA (preprocess.hip, fuse.hip); texels may be null

@@ -493,25 +493,13 @@ __global__ __launch_bounds__(256) void k_texture_depth(const TextureParams p)
 
 using namespace kfx;
 
-static int check_image(const kfx_image* im, size_t elem, const char* what)
-{
-    if (!im || !im->ptr) return set_error(KFX_E_NULL, what);
-    if (im->pitch < im->w * elem) return set_error(KFX_E_SHAPE, what);
-    const size_t al = elem >= 16 ? 16 : elem;
-    if (((uintptr_t)im->ptr | im->pitch) & (al - 1)) return set_error(KFX_E_ALIGN, what);
-    if (im->w > (1u << 30) || im->h > (1u << 30)) return set_error(KFX_E_SHAPE, what);
-    return 0;
-}
-
 template <typename Ti>
 static int bilateral_launch(const kfx_image* out, const kfx_image* in, float gs, float gr, unsigned size,
                             float minval, int use_minval, kfx_stream stream)
 {
-    if (int e = check_image(out, 4, "BilateralFilter: output image")) return e;
-    if (int e = check_image(in, sizeof(Ti), "BilateralFilter: input image")) return e;
+    if (int e = check_image(out, 4, 0, 0, "BilateralFilter: output image")) return e;
+    if (int e = check_image(in, sizeof(Ti), cover_w(out), cover_h(out), "BilateralFilter: input image")) return e;
     if (out->w == 0 || out->h == 0) return 0;
-    if (in->w == 0 || in->h == 0) return set_error(KFX_E_SHAPE, "BilateralFilter: empty input");
-    if (in->w < out->w || in->h < out->h) return set_error(KFX_E_SHAPE, "BilateralFilter: input smaller than output");
     if (size > 1024) return set_error(KFX_E_RANGE, "BilateralFilter: window radius");
     BilParams p;
     p.in = (const unsigned char*)in->ptr;
@@ -553,8 +541,7 @@ static int bilateral_launch(const kfx_image* out, const kfx_image* in, float gs,
         }
 #undef KFX_BIL
     } else {
-        dim3 grid(ceil_div(p.w, 64), ceil_div(p.h, 4));
-        hipLaunchKernelGGL(k_bilateral_global<Ti>, grid, dim3(256), 0, s, p);
+        hipLaunchKernelGGL(k_bilateral_global<Ti>, pixel_grid(p.w, p.h), dim3(256), 0, s, p);
     }
     return check_launch("kfx_bilateral");
 }
@@ -578,15 +565,13 @@ extern "C" int kfx_bilateral_u8(const kfx_image* out, const kfx_image* in, float
 template <typename Ti>
 static int vbo_launch(const kfx_image* vbo, const kfx_image* depth, const float K[4], float scale, kfx_stream stream)
 {
-    if (int e = check_image(vbo, 16, "DepthToVbo: vbo image")) return e;
-    if (int e = check_image(depth, sizeof(Ti), "DepthToVbo: depth image")) return e;
+    if (int e = check_image(vbo, 16, 0, 0, "DepthToVbo: vbo image")) return e;
+    if (int e = check_image(depth, sizeof(Ti), cover_w(vbo), cover_h(vbo), "DepthToVbo: depth image")) return e;
     if (!K) return set_error(KFX_E_NULL, "DepthToVbo: null intrinsics");
     if (vbo->w == 0 || vbo->h == 0) return 0;
-    if (depth->w < vbo->w || depth->h < vbo->h) return set_error(KFX_E_SHAPE, "DepthToVbo: depth smaller than vbo");
     VboParams p{(const unsigned char*)depth->ptr, depth->pitch, (unsigned char*)vbo->ptr, vbo->pitch,
                 (int)vbo->w, (int)vbo->h, Intr{K[0], K[1], K[2], K[3]}, scale};
-    dim3 grid(ceil_div(p.w, 64), ceil_div(p.h, 4));
-    hipLaunchKernelGGL(k_depth_to_vbo<Ti>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(k_depth_to_vbo<Ti>, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("kfx_depth_to_vbo");
 }
 
@@ -603,90 +588,80 @@ extern "C" int kfx_depth_to_vbo_u16(const kfx_image* vbo, const kfx_image* depth
 
 extern "C" int kfx_normals_from_vbo(const kfx_image* nrm, const kfx_image* vbo, kfx_stream stream)
 {
-    if (int e = check_image(nrm, 16, "NormalsFromVbo: normal image")) return e;
-    if (int e = check_image(vbo, 16, "NormalsFromVbo: vbo image")) return e;
+    if (int e = check_image(nrm, 16, 0, 0, "NormalsFromVbo: normal image")) return e;
+    if (int e = check_image(vbo, 16, cover_w(nrm), cover_h(nrm), "NormalsFromVbo: vbo image")) return e;
     if (nrm->w == 0 || nrm->h == 0) return 0;
-    if (vbo->w < nrm->w || vbo->h < nrm->h) return set_error(KFX_E_SHAPE, "NormalsFromVbo: vbo smaller than normals");
     NrmParams p{(const unsigned char*)vbo->ptr, vbo->pitch, (unsigned char*)nrm->ptr, nrm->pitch, (int)nrm->w, (int)nrm->h};
-    dim3 grid(ceil_div(p.w, 64), ceil_div(p.h, 4));
-    hipLaunchKernelGGL(k_normals_from_vbo, grid, dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(k_normals_from_vbo, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("kfx_normals_from_vbo");
 }
 
 extern "C" int kfx_elementwise_scale_bias_f32(const kfx_image* out, const kfx_image* in, float s, float offset, kfx_stream stream)
 {
-    if (int e = check_image(out, 4, "ElementwiseScaleBias: output image")) return e;
-    if (int e = check_image(in, 4, "ElementwiseScaleBias: input image")) return e;
+    if (int e = check_image(out, 4, 0, 0, "ElementwiseScaleBias: output image")) return e;
+    if (int e = check_image(in, 4, cover_w(out), cover_h(out), "ElementwiseScaleBias: input image")) return e;
     if (out->w == 0 || out->h == 0) return 0;
-    if (in->w < out->w || in->h < out->h) return set_error(KFX_E_SHAPE, "ElementwiseScaleBias: input smaller than output");
     EwParams p{(const unsigned char*)in->ptr, in->pitch, (unsigned char*)out->ptr, out->pitch, (int)out->w, (int)out->h, s, offset};
-    dim3 grid(ceil_div(p.w, 64), ceil_div(p.h, 4));
-    hipLaunchKernelGGL(k_scale_bias_f32, grid, dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(k_scale_bias_f32, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("kfx_elementwise_scale_bias_f32");
 }
 
 extern "C" int kfx_box_half_ignore_invalid_f32(const kfx_image* out, const kfx_image* in, kfx_stream stream)
 {
-    if (int e = check_image(out, 4, "BoxHalfIgnoreInvalid: output image")) return e;
-    if (int e = check_image(in, 4, "BoxHalfIgnoreInvalid: input image")) return e;
+    if (int e = check_image(out, 4, 0, 0, "BoxHalfIgnoreInvalid: output image")) return e;
+    if (int e = check_image(in, 4, 2 * cover_w(out), 2 * cover_h(out), "BoxHalfIgnoreInvalid: input image (2x the output)")) return e;
     if (out->w == 0 || out->h == 0) return 0;
-    if (in->w < 2 * out->w || in->h < 2 * out->h) return set_error(KFX_E_SHAPE, "BoxHalfIgnoreInvalid: input smaller than 2x output");
     if (((uintptr_t)in->ptr | in->pitch) & 7) return set_error(KFX_E_ALIGN, "BoxHalfIgnoreInvalid: input not 8-byte aligned");
     EwParams p{(const unsigned char*)in->ptr, in->pitch, (unsigned char*)out->ptr, out->pitch, (int)out->w, (int)out->h, 0.f, 0.f};
-    dim3 grid(ceil_div(p.w, 64), ceil_div(p.h, 4));
-    hipLaunchKernelGGL(k_box_half_ignore_invalid_f32, grid, dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(k_box_half_ignore_invalid_f32, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("kfx_box_half_ignore_invalid_f32");
 }
 
 // Disp2Depth(dIn, dOut, fu, fBaseline, fMinDisp) (cu_depth_tools.cu:15-30; the launch is bounded by dOut)
 extern "C" int kfx_disp2depth(const kfx_image* in, const kfx_image* out, float fu, float baseline, float min_disp, kfx_stream stream)
 {
-    if (int e = check_image(out, 4, "Disp2Depth: output image")) return e;
-    if (int e = check_image(in, 4, "Disp2Depth: input image")) return e;
+    if (int e = check_image(out, 4, 0, 0, "Disp2Depth: output image")) return e;
+    if (int e = check_image(in, 4, cover_w(out), cover_h(out), "Disp2Depth: input image")) return e;
     if (out->w == 0 || out->h == 0) return 0;
-    if (in->w < out->w || in->h < out->h) return set_error(KFX_E_SHAPE, "Disp2Depth: input smaller than output");
     PixIO p{(const unsigned char*)in->ptr, in->pitch, (unsigned char*)out->ptr, out->pitch, (int)out->w, (int)out->h};
-    hipLaunchKernelGGL(k_disp2depth, dim3(ceil_div(p.w, 64), ceil_div(p.h, 4)), dim3(256), 0, (hipStream_t)stream, p, fu, baseline, min_disp);
+    hipLaunchKernelGGL(k_disp2depth, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p, fu, baseline, min_disp);
     return check_launch("kfx_disp2depth");
 }
 
 // FilterBadKinectData(dFiltered, dKinectDepth) (cu_depth_tools.cu:32-53), float and unsigned short readings
 extern "C" int kfx_filter_bad_kinect_f32(const kfx_image* out, const kfx_image* in, kfx_stream stream)
 {
-    if (int e = check_image(out, 4, "FilterBadKinectData: output image")) return e;
-    if (int e = check_image(in, 4, "FilterBadKinectData: input image")) return e;
+    if (int e = check_image(out, 4, 0, 0, "FilterBadKinectData: output image")) return e;
+    if (int e = check_image(in, 4, cover_w(out), cover_h(out), "FilterBadKinectData: input image")) return e;
     if (out->w == 0 || out->h == 0) return 0;
-    if (in->w < out->w || in->h < out->h) return set_error(KFX_E_SHAPE, "FilterBadKinectData: input smaller than output");
     PixIO p{(const unsigned char*)in->ptr, in->pitch, (unsigned char*)out->ptr, out->pitch, (int)out->w, (int)out->h};
-    hipLaunchKernelGGL(k_filter_bad_kinect<float>, dim3(ceil_div(p.w, 64), ceil_div(p.h, 4)), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(k_filter_bad_kinect<float>, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("kfx_filter_bad_kinect_f32");
 }
 extern "C" int kfx_filter_bad_kinect_u16(const kfx_image* out, const kfx_image* in, kfx_stream stream)
 {
-    if (int e = check_image(out, 4, "FilterBadKinectData: output image")) return e;
-    if (int e = check_image(in, 2, "FilterBadKinectData: input image")) return e;
+    if (int e = check_image(out, 4, 0, 0, "FilterBadKinectData: output image")) return e;
+    if (int e = check_image(in, 2, cover_w(out), cover_h(out), "FilterBadKinectData: input image")) return e;
     if (out->w == 0 || out->h == 0) return 0;
-    if (in->w < out->w || in->h < out->h) return set_error(KFX_E_SHAPE, "FilterBadKinectData: input smaller than output");
     PixIO p{(const unsigned char*)in->ptr, in->pitch, (unsigned char*)out->ptr, out->pitch, (int)out->w, (int)out->h};
-    hipLaunchKernelGGL(k_filter_bad_kinect<unsigned short>, dim3(ceil_div(p.w, 64), ceil_div(p.h, 4)), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(k_filter_bad_kinect<unsigned short>, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("kfx_filter_bad_kinect_u16");
 }
 
 // ColourVbo(dId, dPd, dIc, KT_cd) (cu_depth_tools.cu:86-119)
 extern "C" int kfx_colour_vbo(const kfx_image* id, const kfx_image* vbo, const kfx_image* rgb, const float KT_cd[12], kfx_stream stream)
 {
-    if (int e = check_image(id, 4, "ColourVbo: output image")) return e;
-    if (int e = check_image(vbo, 16, "ColourVbo: vbo image")) return e;
-    if (int e = check_image(rgb, 1, "ColourVbo: rgb image")) return e;
+    if (int e = check_image(id, 4, 0, 0, "ColourVbo: output image")) return e;
+    if (int e = check_image(vbo, 16, cover_w(id), cover_h(id), "ColourVbo: vbo image")) return e;
+    if (int e = check_image(rgb, 3, 0, 0, "ColourVbo: rgb image")) return e;
     if (!KT_cd) return set_error(KFX_E_NULL, "ColourVbo: null transform");
     if (id->w == 0 || id->h == 0) return 0;
-    if (vbo->w < id->w || vbo->h < id->h || rgb->pitch < rgb->w * 3) return set_error(KFX_E_SHAPE, "ColourVbo: image sizes");
     ColourVboParams p;
     p.vbo = (const unsigned char*)vbo->ptr; p.vpitch = vbo->pitch;
     p.rgb = (const unsigned char*)rgb->ptr; p.rpitch = rgb->pitch; p.rw = (int)rgb->w; p.rh = (int)rgb->h;
     p.out = (unsigned char*)id->ptr; p.opitch = id->pitch; p.w = (int)id->w; p.h = (int)id->h;
     for (int i = 0; i < 12; ++i) p.KT.m[i] = KT_cd[i];
-    hipLaunchKernelGGL(k_colour_vbo, dim3(ceil_div(p.w, 64), ceil_div(p.h, 4)), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(k_colour_vbo, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("kfx_colour_vbo");
 }
 
@@ -695,12 +670,10 @@ template <typename Tg>
 static int guided_launch(const kfx_image* out, const kfx_image* in, const kfx_image* guide, float gs, float gr, float gc, unsigned size,
                          kfx_stream stream)
 {
-    if (int e = check_image(out, 4, "BilateralFilter(guided): output image")) return e;
-    if (int e = check_image(in, 4, "BilateralFilter(guided): input image")) return e;
-    if (int e = check_image(guide, sizeof(Tg), "BilateralFilter(guided): guide image")) return e;
+    if (int e = check_image(out, 4, 0, 0, "BilateralFilter(guided): output image")) return e;
+    if (int e = check_image(in, 4, cover_w(out), cover_h(out), "BilateralFilter(guided): input image")) return e;
+    if (int e = check_image(guide, sizeof(Tg), cover_w(out), cover_h(out), "BilateralFilter(guided): guide image")) return e;
     if (out->w == 0 || out->h == 0) return 0;
-    if (in->w < out->w || in->h < out->h || guide->w < out->w || guide->h < out->h)
-        return set_error(KFX_E_SHAPE, "BilateralFilter(guided): inputs smaller than the output");
     if (size > 64) return set_error(KFX_E_RANGE, "BilateralFilter(guided): window too large");
     GuidedParams g;
     g.b = BilParams{(const unsigned char*)in->ptr, in->pitch, (unsigned char*)out->ptr, out->pitch, (int)out->w, (int)out->h,
@@ -710,7 +683,7 @@ static int guided_launch(const kfx_image* out, const kfx_image* in, const kfx_im
     g.gw = (int)guide->w;
     g.gh = (int)guide->h;
     g.gc = gc;
-    hipLaunchKernelGGL(k_bilateral_guided<Tg>, dim3(ceil_div(g.b.w, 64), ceil_div(g.b.h, 4)), dim3(256), 0, (hipStream_t)stream, g);
+    hipLaunchKernelGGL(k_bilateral_guided<Tg>, pixel_grid(g.b.w, g.b.h), dim3(256), 0, (hipStream_t)stream, g);
     return check_launch("kfx_bilateral_guided");
 }
 extern "C" int kfx_bilateral_guided_f32(const kfx_image* out, const kfx_image* in, const kfx_image* guide, float gs, float gr, float gc,
@@ -739,13 +712,12 @@ extern "C" int kfx_depth_to_vbo_normals_f32(const kfx_image* vbo, const kfx_imag
 int kfx::depth_to_vbo_normals_texels(const kfx_image* vbo, const kfx_image* nrm, const kfx_image* depth, const float K[4], float scale,
                                      const kfx_image* texels, kfx_stream stream)
 {
-    if (int e = check_image(vbo, 16, "DepthToVbo+Normals: vbo image")) return e;
-    if (int e = check_image(nrm, 16, "DepthToVbo+Normals: normal image")) return e;
-    if (int e = check_image(depth, 4, "DepthToVbo+Normals: depth image")) return e;
+    if (int e = check_image(vbo, 16, 0, 0, "DepthToVbo+Normals: vbo image")) return e;
+    if (int e = check_image(nrm, 16, 0, 0, "DepthToVbo+Normals: normal image")) return e;
+    if (int e = check_image(depth, 4, cover_w(vbo), cover_h(vbo), "DepthToVbo+Normals: depth image")) return e;
     if (!K) return set_error(KFX_E_NULL, "DepthToVbo+Normals: null intrinsics");
     if (vbo->w == 0 || vbo->h == 0) return 0;
-    if (nrm->w != vbo->w || nrm->h != vbo->h || depth->w < vbo->w || depth->h < vbo->h)
-        return set_error(KFX_E_SHAPE, "DepthToVbo+Normals: image sizes");
+    if (nrm->w != vbo->w || nrm->h != vbo->h) return set_error(KFX_E_SHAPE, "DepthToVbo+Normals: vbo and normals differ in size");
     // texels: a buffer of kfx::texel_image_bytes(w, h) bytes in the layout of fuse.hip's tex_layout -- rows of `pitch` = w * 16 rounded up
     // to 256 bytes, the block maxima behind them in rows of ceil(w / 64) * 8 floats
     const size_t tpitch = (vbo->w * 16 + 255) / 256 * 256;
@@ -754,7 +726,7 @@ int kfx::depth_to_vbo_normals_texels(const kfx_image* vbo, const kfx_image* nrm,
     VboNrmParams p{(const unsigned char*)depth->ptr, depth->pitch, (unsigned char*)vbo->ptr, (unsigned char*)nrm->ptr, vbo->pitch, nrm->pitch,
                    (int)vbo->w, (int)vbo->h, Intr{K[0], K[1], K[2], K[3]}, scale, texels ? (unsigned char*)texels->ptr : nullptr, texels ? tpitch : 0,
                    texels ? reinterpret_cast<float*>((unsigned char*)texels->ptr + tpitch * vbo->h) : nullptr, (unsigned)((vbo->w + 63) / 64 * 8)};
-    hipLaunchKernelGGL(k_vbo_normals_f32, dim3(ceil_div(p.w, 64), ceil_div(p.h, 4)), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(k_vbo_normals_f32, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("kfx_depth_to_vbo_normals_f32");
 }
 
@@ -864,9 +836,9 @@ extern "C" int kfx_depth_pyramid_vbo_normals_f32(const kfx_image* depth, const k
         p.K[l] = Intr{1.f, 1.f, 0.f, 0.f};
     }
     for (int l = 0; l < levels; ++l) {
-        if (int e = check_image(&depth[l], 4, "DepthPyramidVboNormals: depth image")) return e;
-        if (int e = check_image(&vbo[l], 16, "DepthPyramidVboNormals: vbo image")) return e;
-        if (int e = check_image(&nrm[l], 16, "DepthPyramidVboNormals: normal image")) return e;
+        if (int e = check_image(&depth[l], 4, 0, 0, "DepthPyramidVboNormals: depth image")) return e;
+        if (int e = check_image(&vbo[l], 16, 0, 0, "DepthPyramidVboNormals: vbo image")) return e;
+        if (int e = check_image(&nrm[l], 16, 0, 0, "DepthPyramidVboNormals: normal image")) return e;
         if (vbo[l].w != depth[l].w || vbo[l].h != depth[l].h || nrm[l].w != depth[l].w || nrm[l].h != depth[l].h)
             return set_error(KFX_E_SHAPE, "DepthPyramidVboNormals: the maps of a level differ in size from its depth image");
         if (l > 0 && (depth[l - 1].w < 2 * depth[l].w || depth[l - 1].h < 2 * depth[l].h))
@@ -889,16 +861,14 @@ extern "C" int kfx_depth_pyramid_vbo_normals_f32(const kfx_image* depth, const k
 extern "C" int kfx_texture_depth(const kfx_image* img, const kfx_keyframe* kfs, int n_kf, const kfx_image* depth, const kfx_image* norm,
                                  const kfx_image* phong, const float T_wd[12], const float Kdepth[4], kfx_stream stream)
 {
-    if (int e = check_image(img, 16, "TextureDepth: output image")) return e;
-    if (int e = check_image(depth, 4, "TextureDepth: depth image")) return e;
-    if (int e = check_image(norm, 16, "TextureDepth: normal image")) return e;
+    if (int e = check_image(img, 16, 0, 0, "TextureDepth: output image")) return e;
+    if (int e = check_image(depth, 4, cover_w(img), cover_h(img), "TextureDepth: depth image")) return e;
+    if (int e = check_image(norm, 16, cover_w(img), cover_h(img), "TextureDepth: normal image")) return e;
     if (!kfs || n_kf < 1 || n_kf > TEX_MAX_KF || !T_wd || !Kdepth) return set_error(KFX_E_NULL, "TextureDepth: keyframes / transforms");
     const bool single = phong == nullptr;
-    if (!single) { if (int e = check_image(phong, 4, "TextureDepth: phong image")) return e; }
+    if (!single) { if (int e = check_image(phong, 4, cover_w(img), cover_h(img), "TextureDepth: phong image")) return e; }
     if (single && n_kf != 1) return set_error(KFX_E_RANGE, "TextureDepth: the single-keyframe form takes exactly one keyframe");
     if (img->w == 0 || img->h == 0) return 0;
-    if (depth->w < img->w || depth->h < img->h || norm->w < img->w || norm->h < img->h || (!single && (phong->w < img->w || phong->h < img->h)))
-        return set_error(KFX_E_SHAPE, "TextureDepth: inputs smaller than the output");
     TextureParams p;
     p.out = (unsigned char*)img->ptr; p.opitch = img->pitch;
     p.depth = (const unsigned char*)depth->ptr; p.dpitch = depth->pitch;
@@ -920,6 +890,6 @@ extern "C" int kfx_texture_depth(const kfx_image* img, const kfx_keyframe* kfs, 
         }
     }
     if (single && !p.kf[0].img) return set_error(KFX_E_NULL, "TextureDepth: keyframe image is null");
-    hipLaunchKernelGGL(k_texture_depth, dim3(ceil_div(p.w, 64), ceil_div(p.h, 4)), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(k_texture_depth, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("kfx_texture_depth");
 }

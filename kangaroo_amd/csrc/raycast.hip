@@ -881,14 +881,8 @@ static int ray_params(RayParams& p, const kfx_image* depth, const kfx_image* nor
                       const kfx_volume* vol, const float T_wc[12], const float K[4], float near,
                       float far, float trunc_dist, int subpix)
 {
-    if (!depth || !norm || !img || !vol || !T_wc || !K || !depth->ptr || !norm->ptr || !img->ptr || !vol->ptr)
-        return set_error(KFX_E_NULL, "RaycastSdf: null argument");
-    if (depth->w < img->w || depth->h < img->h || norm->w < img->w || norm->h < img->h)
-        return set_error(KFX_E_SHAPE, "RaycastSdf: output images smaller than img");
-    if (depth->pitch < img->w * 4 || img->pitch < img->w * 4 || norm->pitch < img->w * 16)
-        return set_error(KFX_E_SHAPE, "RaycastSdf: image pitch");
-    if ((((uintptr_t)depth->ptr | depth->pitch | (uintptr_t)img->ptr | img->pitch) & 3) || (((uintptr_t)norm->ptr | norm->pitch) & 15))
-        return set_error(KFX_E_ALIGN, "RaycastSdf: image alignment");
+    if (!T_wc || !K) return set_error(KFX_E_NULL, "RaycastSdf: null argument");
+    if (int e = check_render_images(depth, norm, img, img, "RaycastSdf")) return e;
     // the gradient stencil reads cells [1-1, (dim-2)+1] (Volume.h:271-273)
     if (int e = check_volume(vol, CELL::BYTES, 3, VOLUME_MAX_DIM, "RaycastSdf")) return e;
     set_geometry(p, vol);
@@ -1062,9 +1056,7 @@ static int raycast_levels_launch(int n_levels, const kfx_image* const* depth, co
         lv.vpitch = 0;
         if (vbo && vbo[l]) {
             const kfx_image* vb = vbo[l];
-            if (!vb->ptr) return set_error(KFX_E_NULL, "RaycastSdf(levels): null vertex map");
-            if (vb->w < (size_t)p.w || vb->h < (size_t)p.h || vb->pitch < (size_t)p.w * 16) return set_error(KFX_E_SHAPE, "RaycastSdf(levels): vertex map smaller than img");
-            if (((uintptr_t)vb->ptr | vb->pitch) & 15) return set_error(KFX_E_ALIGN, "RaycastSdf(levels): vertex map alignment");
+            if (int e = check_image(vb, 16, (size_t)p.w, (size_t)p.h, "RaycastSdf(levels): vertex map")) return e;
             lv.vptr = (unsigned char*)vb->ptr;
             lv.vpitch = vb->pitch;
         }
@@ -1149,7 +1141,7 @@ static int count_params(RayParams& p, dim3& grid, const kfx_volume* vol, unsigne
     kfx_image dummy = {(size_t)w * 16, (void*)(uintptr_t)16, w, h};
     if (int e = ray_params<CELL>(p, &dummy, &dummy, &dummy, vol, T_wc, K, near, far, trunc_dist, subpix)) return e;
     p.dptr = p.nptr = p.iptr = nullptr;
-    grid = dim3(ceil_div(p.w, 64), ceil_div(p.h, 4));
+    grid = pixel_grid(p.w, p.h);
     return 0;
 }
 
@@ -1294,9 +1286,9 @@ extern "C" int kfx_raycast_color_hits(int n_levels, const kfx_image* const* dept
         const kfx_image *d = depth[l], *i = img[l];
         if (!d || !i || !d->ptr || !i->ptr) return set_error(KFX_E_NULL, "RaycastSdf(colour pass): null image");
         if (d->w != i->w || d->h != i->h) return set_error(KFX_E_SHAPE, "RaycastSdf(colour pass): depth and colour image of different sizes");
-        if (d->pitch < d->w * 4 || i->pitch < i->w * 4) return set_error(KFX_E_SHAPE, "RaycastSdf(colour pass): image pitch");
         if (d->w > 0x7fffffffu || d->h > 0x7fffffffu) return set_error(KFX_E_RANGE, "RaycastSdf(colour pass): image dimensions");
-        if (((uintptr_t)d->ptr | d->pitch | (uintptr_t)i->ptr | i->pitch) & 3) return set_error(KFX_E_ALIGN, "RaycastSdf(colour pass): image alignment");
+        if (int e = check_image(d, 4, 0, 0, "RaycastSdf(colour pass): depth image")) return e;
+        if (int e = check_image(i, 4, 0, 0, "RaycastSdf(colour pass): colour image")) return e;
         if (d->w == 0 || d->h == 0) continue; // an empty level launches nothing
         ColorHitLevel& lv = L.lv[L.n++];
         lv.dptr = (const unsigned char*)d->ptr; lv.iptr = (unsigned char*)i->ptr;
@@ -1359,7 +1351,7 @@ static int raycast_slab_launch(const SlabRay& geom, const kfx_volume* vol, const
     SlabRay sl = geom;
     sl.own_lo = own_lo; sl.own_hi = own_hi;
     sl.avail_lo = (int)slab->z_offset; sl.avail_hi = (int)(slab->z_offset + vol->d);
-    dim3 grid(ceil_div(w, 64), ceil_div(sl.v1 - sl.v0, 4));
+    const dim3 grid = pixel_grid(w, sl.v1 - sl.v0);
     SlabColor sc{};
     if constexpr (CELL::BYTES == 8) {
         if (colorvol) {
@@ -1453,13 +1445,15 @@ extern "C" int kfx_raycast_sdf_slab_h(float* state, int init, const kfx_volume* 
 extern "C" int kfx_raycast_state_to_images(const kfx_image* depth, const kfx_image* norm, const kfx_image* img, const float* state,
                                            kfx_stream stream)
 {
-    if (!depth || !norm || !img || !state || !depth->ptr || !norm->ptr || !img->ptr) return set_error(KFX_E_NULL, "raycast state: null argument");
+    if (!state) return set_error(KFX_E_NULL, "raycast state: null argument");
+    if (int e = check_image(img, 4, 0, 0, "raycast state")) return e;
+    if (int e = check_image(depth, 4, cover_w(img), cover_h(img), "raycast state")) return e;
+    if (int e = check_image(norm, 16, cover_w(img), cover_h(img), "raycast state")) return e;
     if (img->w == 0 || img->h == 0) return 0;
-    if (depth->w < img->w || depth->h < img->h || norm->w < img->w || norm->h < img->h) return set_error(KFX_E_SHAPE, "raycast state: image sizes");
     RayParams p{};
     p.dptr = (unsigned char*)depth->ptr; p.nptr = (unsigned char*)norm->ptr; p.iptr = (unsigned char*)img->ptr;
     p.dpitch = depth->pitch; p.npitch = norm->pitch; p.ipitch = img->pitch;
     p.w = (int)img->w; p.h = (int)img->h;
-    hipLaunchKernelGGL(k_raycast_state_to_images, dim3(ceil_div(p.w, 64), ceil_div(p.h, 4)), dim3(256), 0, (hipStream_t)stream, p, state);
+    hipLaunchKernelGGL(k_raycast_state_to_images, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p, state);
     return check_launch("kfx_raycast_state_to_images");
 }

@@ -248,13 +248,6 @@ struct ThreadGroup {
     }
 };
 
-static int hip_status(hipError_t e, const char* what)
-{
-    if (e == hipSuccess) return 0;
-    (void)hipGetLastError();
-    return set_error((int)e, what);
-}
-
 // Every rank passes both barriers of a collective whatever happened locally: a rank that returned early on its own error
 // would leave its peers waiting on the condition variable for ever.  Local errors are posted in err[parity][rank]; after the
 // last barrier every rank returns the first error any rank posted for THIS collective, so all ranks return the same status.
@@ -580,9 +573,10 @@ extern "C" int kfx_slab_layout_init(kfx_slab_layout* L, size_t full_d, float ful
 
 extern "C" int kfx_slab_broadcast_inputs(const kfx_image* depth, const kfx_image* norm, void* scratch, int root, kfx_comm* comm, kfx_stream stream)
 {
-    if (!depth || !norm || !comm || !depth->ptr || !norm->ptr) return set_error(KFX_E_NULL, "kfx_slab_broadcast_inputs: null argument");
+    if (!comm) return set_error(KFX_E_NULL, "kfx_slab_broadcast_inputs: null argument");
+    if (int e = check_image(depth, 4, 0, 0, "kfx_slab_broadcast_inputs: depth image")) return e;
+    if (int e = check_image(norm, 16, 0, 0, "kfx_slab_broadcast_inputs: normal image")) return e;
     if (norm->w != depth->w || norm->h != depth->h) return set_error(KFX_E_SHAPE, "kfx_slab_broadcast_inputs: depth and normals differ in size");
-    if (depth->pitch < depth->w * 4 || norm->pitch < norm->w * 16) return set_error(KFX_E_SHAPE, "kfx_slab_broadcast_inputs: image pitch");
     if (comm->world == 1) return 0;
     if (!comm->broadcast) return set_error(KFX_E_NULL, "kfx_slab_broadcast_inputs: the transport has no broadcast");
     const size_t w = depth->w, h = depth->h;
@@ -680,7 +674,7 @@ static int exact_args(const kfx_image* depth, const kfx_image* norm, const kfx_i
     if (!depth || !norm || !img || !state || !scratch || !local || !L || !comm) return set_error(KFX_E_NULL, who);
     if (local->d != L->s1 - L->s0 || comm->rank != L->rank || comm->world != L->world)
         return set_error(KFX_E_SHAPE, "kfx_slab_raycast_exact: volume / communicator do not match the layout");
-    return 0;
+    return check_render_images(depth, norm, img, img, "kfx_slab_raycast_exact");   // (what kfx_raycast_state_to_images asks at the end)
 }
 
 // The blueprint's hand-over: world + 1 march stages with a neighbour exchange of the march planes between
@@ -862,15 +856,11 @@ void kfx::exact_final_carve(ExactFinalBufs& b, void* mem, size_t w, size_t h, in
 static int exact_tiled_args(const kfx_image* depth, const kfx_image* norm, const kfx_image* img, void* scratch, const kfx_volume* local,
                             const kfx_slab_layout* L, kfx_comm* comm, const float* T_wc, const float* K)
 {
-    if (!depth || !norm || !img || !scratch || !local || !L || !comm || !T_wc || !K || !depth->ptr || !norm->ptr || !img->ptr)
-        return set_error(KFX_E_NULL, "kfx_slab_raycast_exact_tiled: null argument");
+    if (!scratch || !local || !L || !comm || !T_wc || !K) return set_error(KFX_E_NULL, "kfx_slab_raycast_exact_tiled: null argument");
     if (local->d != L->s1 - L->s0 || comm->rank != L->rank || comm->world != L->world)
         return set_error(KFX_E_SHAPE, "kfx_slab_raycast_exact_tiled: volume / communicator do not match the layout");
-    if (depth->w < img->w || depth->h < img->h || norm->w < img->w || norm->h < img->h || depth->pitch < img->w * 4 || img->pitch < img->w * 4 ||
-        norm->pitch < img->w * 16)
-        return set_error(KFX_E_SHAPE, "kfx_slab_raycast_exact_tiled: image sizes");
-    if ((((uintptr_t)depth->ptr | depth->pitch | (uintptr_t)img->ptr | img->pitch) & 3) || (((uintptr_t)norm->ptr | norm->pitch) & 15) || ((uintptr_t)scratch & 15))
-        return set_error(KFX_E_ALIGN, "kfx_slab_raycast_exact_tiled: alignment");
+    if (int e = check_render_images(depth, norm, img, img, "kfx_slab_raycast_exact_tiled")) return e;
+    if ((uintptr_t)scratch & 15) return set_error(KFX_E_ALIGN, "kfx_slab_raycast_exact_tiled: scratch alignment");
     if (comm->world > 1 && !comm->exchange_v) return set_error(KFX_E_RANGE, "kfx_slab_raycast_exact_tiled: the transport has no exchange_v");
     return 0;
 }
@@ -1027,7 +1017,7 @@ int kfx::exact_tiled_march(void* scratch, const ExactFinalBufs* into, const kfx_
     // the exchange that follows (exact_tiled_finalise)
     const bool direct = world > 1 && !finalise_by_allreduce() && comm->all_to_all && comm->all_gather;
     const unsigned S = direct ? (unsigned)t.S : 0u;
-    const dim3 grid2(ceil_div(w, 64), ceil_div(h, 4));
+    const dim3 grid2 = pixel_grid(w, h);
     if (direct && (size_t)world * t.S > t.n)   // the last strip's padding travels too: defined (and summed as zero)
         note(hip_status(hipMemsetAsync(fb.contrib + ((size_t)(world - 1) * 6) * t.S, 0, 6 * t.S * sizeof(int), s), "kfx_slab_raycast_exact_tiled"));
     hipLaunchKernelGGL(k_tiles_contrib, grid2, dim3(256), 0, s, t.M, t.Rz, t.fin, fb.contrib, w, h, R, P, S, packed);
@@ -1058,7 +1048,7 @@ int kfx::exact_tiled_finalise(const kfx_image* depth, const kfx_image* norm, con
     note(hip_status(hipMemsetAsync(fb.open, 0, sizeof(int), s), "kfx_slab_raycast_exact_tiled"));
     const bool direct = world > 1 && !finalise_by_allreduce() && comm->all_to_all && comm->all_gather;
     const unsigned S = direct ? (unsigned)t.S : 0u;
-    const dim3 grid2(ceil_div(w, 64), ceil_div(h, 4));
+    const dim3 grid2 = pixel_grid(w, h);
     const int* final_planes = fb.contrib;
     if (direct) {
         const size_t words = 6 * t.S;

@@ -10,7 +10,7 @@
 #include <new>
 
 #include "kfx_device.h"
-#include "host_args.h"
+#include "frame_host.h"
 #include "../../include/kfx_slab.h"
 #include "slab_internal.h"
 
@@ -19,7 +19,7 @@ constexpr int EV = 5;          // events per frame: before preprocess, before Sd
 constexpr int OPEN_SLOTS = 8;  // exact march: frames whose "rays left open" word may still be on its way to the host
 constexpr int PIPE_MAX = KFX_SLAB_PIPE_MAX;
 // a frame of the pipelined exact raycast whose final exchange has not been enqueued yet (host-blocking transports trail by pipe - 1 frames)
-struct PendingFinal { long long frame; int set, os, slot, tiles; unsigned timing; };
+struct PendingFinal { long long frame; int set, os, tiles; };
 }
 
 struct kfx_slab_frame {
@@ -58,8 +58,7 @@ struct kfx_slab_frame {
     PendingFinal pending[PIPE_MAX];
     int n_pending;
     long long rendered;                      // the latest frame whose final exchange has been enqueued (-1: none)
-    // the packed texel image of the frame (owned; fuse.hip): written by the fused vbo / normals launch, staged by the SdfFuse of the same step
-    kfx_image texels;
+    kfx_image texels;                        // (frame_host.h)
     int* agree;                              // a device word: the ranks' common verdict on a configure
     // colour mode (kfx_slab_frame_set_color, include/kfx_slab_color.h): the rank's colour slab, the frame's RGB image, the colour camera
     int color;
@@ -67,24 +66,11 @@ struct kfx_slab_frame {
     kfx_image rgb;
     float Kimg[4];
     float T_cd[12];
-    // timing ring
-    int slots;
+    kfx::EventRing ring;                     // EV events per frame; the merge's may be recorded on the side stream
     unsigned timing;                         // which of the five events the next steps record (bit k: event k)
-    hipEvent_t* ev;
-    long long* ev_frame;
-    unsigned char* ev_mask;
 };
 
 using namespace kfx;
-
-static int hip_status(hipError_t e, const char* what)
-{
-    if (e == hipSuccess) return 0;
-    (void)hipGetLastError();
-    return set_error((int)e, what);
-}
-
-static int valid_image(const kfx_image& im, size_t elem) { return im.ptr && im.w > 0 && im.h > 0 && im.pitch >= im.w * elem; }
 
 static int check_policies(const kfx_slab_frame_config& c, int world)
 {
@@ -102,10 +88,9 @@ static int check_policies(const kfx_slab_frame_config& c, int world)
     if (c.overlap && world > 1 && c.raycast == KFX_SLAB_RAYCAST_EXACT) {
         if (c.pipe_depth < 2 || c.pipe_depth > PIPE_MAX) return set_error(KFX_E_RANGE, "kfx_slab_frame: the exact raycast's overlap needs pipe_depth in [2, KFX_SLAB_PIPE_MAX]");
         for (int k = 0; k < 3 * (c.pipe_depth - 1); ++k) {
-            const kfx_image& im = c.pipe_images[k];
-            const size_t elem = (k % 3 == 1) ? 16 : 4;
-            if (!im.ptr || im.w < c.ray_img.w || im.h < c.ray_img.h || im.pitch < c.ray_img.w * elem || (((uintptr_t)im.ptr | im.pitch) & (elem - 1)))
-                return set_error(KFX_E_SHAPE, "kfx_slab_frame: pipe_images (sets 1 .. pipe_depth - 1 of {ray_depth, ray_norm, ray_img})");
+            const char* what = "kfx_slab_frame: pipe_images (sets 1 .. pipe_depth - 1 of {ray_depth, ray_norm, ray_img})";
+            if (!c.pipe_images[k].ptr) return set_error(KFX_E_SHAPE, what);   // (a malformed configuration, as a missing view)
+            if (int e = check_image(&c.pipe_images[k], (k % 3 == 1) ? 16 : 4, c.ray_img.w, c.ray_img.h, what)) return e;
         }
     }
     return 0;
@@ -184,12 +169,7 @@ extern "C" int kfx_slab_frame_create(kfx_slab_frame** out, const kfx_slab_frame_
     if (!out || !cfg || !comm) return set_error(KFX_E_NULL, "kfx_slab_frame_create: null argument");
     *out = nullptr;
     if (!cfg->local.ptr) return set_error(KFX_E_NULL, "kfx_slab_frame_create: null volume");
-    if (!valid_image(cfg->raw, 4) || !valid_image(cfg->filtered, 4) || !valid_image(cfg->vbo, 16) || !valid_image(cfg->normals, 16) ||
-        !valid_image(cfg->ray_depth, 4) || !valid_image(cfg->ray_norm, 16) || !valid_image(cfg->ray_img, 4))
-        return set_error(KFX_E_SHAPE, "kfx_slab_frame_create: image views");
-    if (cfg->filtered.w != cfg->raw.w || cfg->filtered.h != cfg->raw.h || cfg->vbo.w != cfg->raw.w || cfg->vbo.h != cfg->raw.h ||
-        cfg->normals.w != cfg->raw.w || cfg->normals.h != cfg->raw.h)
-        return set_error(KFX_E_SHAPE, "kfx_slab_frame_create: the preprocess images differ in size");
+    if (int e = check_frame_views(cfg->raw, cfg->filtered, cfg->vbo, cfg->normals, cfg->ray_depth, cfg->ray_norm, cfg->ray_img, "kfx_slab_frame_create")) return e;
     if (cfg->ray_depth.w < cfg->ray_img.w || cfg->ray_depth.h < cfg->ray_img.h || cfg->ray_norm.w < cfg->ray_img.w || cfg->ray_norm.h < cfg->ray_img.h)
         return set_error(KFX_E_SHAPE, "kfx_slab_frame_create: rendering images smaller than ray_img");
     const kfx_slab_layout& L = cfg->layout;
@@ -201,17 +181,11 @@ extern "C" int kfx_slab_frame_create(kfx_slab_frame** out, const kfx_slab_frame_
     if (!f) return set_error(KFX_E_RANGE, "kfx_slab_frame_create: out of memory");
     f->cfg = *cfg;
     f->comm = comm;
-    f->slots = cfg->timing_slots;
     f->timing = 31u;
     for (int i = 0; i < OPEN_SLOTS; ++i) f->open_frame[i] = -1;
     f->rendered = -1;
     f->pipe = (cfg->overlap && cfg->raycast == KFX_SLAB_RAYCAST_EXACT && comm->world > 1) ? cfg->pipe_depth : 0;
-    {   // the packed texel image of the frame's SdfFuse (no memory: the fuse packs per call instead)
-        const size_t tpitch = (cfg->filtered.w * 16 + 255) / 256 * 256;
-        void* buf = nullptr;
-        if (tpitch < (1u << 24) && hipMalloc(&buf, kfx::texel_image_bytes(cfg->filtered.w, cfg->filtered.h)) == hipSuccess) f->texels = kfx_image{tpitch, buf, cfg->filtered.w, cfg->filtered.h};
-        else (void)hipGetLastError();
-    }
+    f->texels = texel_image_alloc(cfg->filtered.w, cfg->filtered.h);
     int e = hip_status(hipMalloc((void**)&f->agree, 64), "kfx_slab_frame_create: hipMalloc");
     if (!e) e = ensure_scratch(f, f->cfg);
     if (!e) e = hip_status(hipHostMalloc((void**)&f->h_open, OPEN_SLOTS * sizeof(int), hipHostMallocDefault), "kfx_slab_frame_create: hipHostMalloc");
@@ -220,14 +194,7 @@ extern "C" int kfx_slab_frame_create(kfx_slab_frame** out, const kfx_slab_frame_
     if (!e) e = hip_status(hipStreamCreateWithFlags(&f->side, hipStreamNonBlocking), "kfx_slab_frame_create: hipStreamCreate");
     if (!e) e = hip_status(hipEventCreateWithFlags(&f->marched, hipEventDisableTiming), "kfx_slab_frame_create: hipEventCreate");
     if (!e) e = hip_status(hipEventCreateWithFlags(&f->merged, hipEventDisableTiming), "kfx_slab_frame_create: hipEventCreate");
-    if (!e && f->slots) {
-        f->ev = new (std::nothrow) hipEvent_t[(size_t)f->slots * EV]();
-        f->ev_frame = new (std::nothrow) long long[f->slots];
-        f->ev_mask = new (std::nothrow) unsigned char[f->slots];
-        if (!f->ev || !f->ev_frame || !f->ev_mask) e = set_error(KFX_E_RANGE, "kfx_slab_frame_create: out of memory");
-        for (int i = 0; !e && i < f->slots; ++i) { f->ev_frame[i] = -1; f->ev_mask[i] = 0; }
-        for (int i = 0; !e && i < f->slots * EV; ++i) e = hip_status(hipEventCreate(&f->ev[i]), "kfx_slab_frame_create: hipEventCreate");
-    }
+    if (!e) e = ring_create(f->ring, EV, cfg->timing_slots, EV - 1, "kfx_slab_frame_create");
     if (e) {
         kfx_slab_frame_destroy(f);
         return e;
@@ -243,12 +210,7 @@ extern "C" int kfx_slab_frame_destroy(kfx_slab_frame* f)
     if (!f) return 0;
     (void)flush_pending(f);   // (collectives: every rank destroys its frame at the same point)
     (void)hipDeviceSynchronize();
-    if (f->ev) {
-        for (int i = 0; i < f->slots * EV; ++i) if (f->ev[i]) (void)hipEventDestroy(f->ev[i]);
-        delete[] f->ev;
-    }
-    delete[] f->ev_frame;
-    delete[] f->ev_mask;
+    ring_destroy(f->ring);
     for (int i = 0; i < OPEN_SLOTS; ++i) if (f->open_done[i]) (void)hipEventDestroy(f->open_done[i]);
     if (f->marched) (void)hipEventDestroy(f->marched);
     if (f->merged) (void)hipEventDestroy(f->merged);
@@ -258,7 +220,7 @@ extern "C" int kfx_slab_frame_destroy(kfx_slab_frame* f)
         if (f->fin_mem[k]) (void)hipFree(f->fin_mem[k]);
     }
     if (f->have_side_comm && f->side_comm.destroy) f->side_comm.destroy(&f->side_comm);
-    if (f->texels.ptr) (void)hipFree(f->texels.ptr);
+    texel_image_free(f->texels);
     if (f->agree) (void)hipFree(f->agree);
     if (f->side) (void)hipStreamDestroy(f->side);
     if (f->h_open) (void)hipHostFree(f->h_open);
@@ -325,10 +287,7 @@ static int finalise_oldest(kfx_slab_frame* f)
     note(kfx::exact_tiled_finalise(d, n, i, f->exact, &f->fin[P.set], P.tiles, &f->side_comm, (kfx_stream)f->side, f->h_open + P.os));
     if (hipEventRecord(f->open_done[P.os], f->side) == hipSuccess) f->open_frame[P.os] = P.frame;
     else (void)hipGetLastError();
-    if (P.slot >= 0 && (P.timing & 16u) && f->ev_frame[P.slot] == P.frame) {
-        if (hipEventRecord(f->ev[(size_t)P.slot * EV + 4], f->side) == hipSuccess) f->ev_mask[P.slot] |= 16u;
-        else (void)hipGetLastError();
-    }
+    (void)ring_record(f->ring, P.frame, 4, f->side);   // (if the frame still holds its slot of the ring)
     note(hip_status(hipEventRecord(f->fin_done[P.set], f->side), "kfx_slab_frame: hipEventRecord"));
     f->fin_inflight[P.set] = 1;
     f->rendered = P.frame;
@@ -432,7 +391,7 @@ extern "C" int kfx_slab_frame_set_color(kfx_slab_frame* f, const kfx_volume* col
     if (!rgb || !rgb->ptr || !Kimg) return set_error(KFX_E_NULL, "kfx_slab_frame_set_color: null argument");
     if (int e = check_volume(color_local, 4, 1, VOLUME_MAX_DIM, "kfx_slab_frame_set_color")) return e;
     if (int e = check_color_slab(&f->cfg.local, color_local, "kfx_slab_frame_set_color")) return e;
-    if (rgb->w < 4 || rgb->h < 4 || rgb->pitch < rgb->w * 3) return set_error(KFX_E_SHAPE, "kfx_slab_frame_set_color: rgb image dimensions");
+    if (int e = check_image(rgb, 3, 4, 4, "kfx_slab_frame_set_color: rgb image (4 x 4 or larger)")) return e;
     f->cvol = *color_local;
     f->rgb = *rgb;
     for (int i = 0; i < 4; ++i) f->Kimg[i] = Kimg[i];
@@ -452,15 +411,8 @@ extern "C" int kfx_slab_frame_step(kfx_slab_frame* f, const kfx_image* raw, cons
     const int world = comm->world, rank = comm->rank;
     const kfx_image* src = raw ? raw : &c.raw;
     float inv[12];
-    if (!T_cw) {   // SE3inv: [R^T | -R^T t], evaluated in double and rounded once (as kfx_frame_step)
-        for (int i = 0; i < 3; ++i) {
-            double t = 0.0;
-            for (int j = 0; j < 3; ++j) {
-                inv[i * 4 + j] = T_wc[j * 4 + i];
-                t += (double)T_wc[j * 4 + i] * (double)T_wc[j * 4 + 3];
-            }
-            inv[i * 4 + 3] = (float)-t;
-        }
+    if (!T_cw) {
+        se3_inverse(T_wc, inv);
         T_cw = inv;
     }
     if ((parts & KFX_FRAME_RAYCAST) &&
@@ -473,18 +425,9 @@ extern "C" int kfx_slab_frame_step(kfx_slab_frame* f, const kfx_image* raw, cons
     // From here on nothing returns early: a local failure must not keep this rank out of a collective its peers enter
     int status = 0;
     const auto note = [&](int e) { if (e && !status) status = e; };
-    hipEvent_t* ev = nullptr;
-    int slot = -1;
-    if (f->slots) {
-        slot = (int)(f->frames % f->slots);
-        f->ev_frame[slot] = f->timing ? f->frames : -1;
-        f->ev_mask[slot] = 0;
-        if (f->timing) ev = f->ev + (size_t)slot * EV;
-    }
+    ring_begin(f->ring, f->frames, f->timing);
     const auto record = [&](int k, hipStream_t on) {
-        if (!ev || !(f->timing & (1u << k))) return;
-        if (hipEventRecord(ev[k], on) == hipSuccess) f->ev_mask[slot] |= (unsigned char)(1u << k);
-        else { (void)hipGetLastError(); note(set_error(KFX_E_RANGE, "kfx_slab_frame_step: hipEventRecord")); }
+        if (ring_record(f->ring, f->frames, k, on) != hipSuccess) note(set_error(KFX_E_RANGE, "kfx_slab_frame_step: hipEventRecord"));
     };
     // the previous frame's overlapped merge still reads the rendering this frame will overwrite, and its strips
     if (f->merge_pending && (parts & KFX_FRAME_RAYCAST)) {
@@ -561,7 +504,7 @@ extern "C" int kfx_slab_frame_step(kfx_slab_frame* f, const kfx_image* raw, cons
                 f->last_steps = steps;
                 record(3, s);
                 note(hip_status(hipEventRecord(f->marched_ev[set], s), "kfx_slab_frame_step: hipEventRecord"));
-                f->pending[f->n_pending++] = PendingFinal{f->frames, set, os, slot, tiles, ev ? f->timing : 0u};
+                f->pending[f->n_pending++] = PendingFinal{f->frames, set, os, tiles};
                 // a host that blocks in collectives trails the final exchange by pipe - 1 frames (it meets its peers there: the last
                 // rank of the token chain is that far behind the first); RCCL enqueues and goes on
                 const int lag = (f->side_comm.flags & KFX_COMM_HOST_BLOCKING) ? f->pipe - 1 : 0;
@@ -610,51 +553,19 @@ extern "C" int kfx_slab_frame_step(kfx_slab_frame* f, const kfx_image* raw, cons
     return status;
 }
 
+// preprocess, SdfFuse (+ ghost planes), the march, the merge, first to last recorded event, the period to the next frame
+static void slab_frame_spans(const EventRing& r, long long fr, float* o, hipError_t& he)
+{
+    for (int k = 0; k < 4; ++k) o[k] = ring_span(r, fr, k, k + 1, he);
+    const unsigned m = ring_recorded(r, fr);
+    if (first_event(m) != last_event(m)) o[4] = ring_span(r, fr, first_event(m), last_event(m), he);
+    o[5] = ring_period(r, fr, he);
+}
+
 extern "C" int kfx_slab_frame_timings(kfx_slab_frame* f, long long first_frame, int n_frames, float* ms)
 {
     if (!f || !ms) return set_error(KFX_E_NULL, "kfx_slab_frame_timings: null argument");
-    if (!f->slots) return set_error(KFX_E_RANGE, "kfx_slab_frame_timings: the frame was created without timing slots");
-    if (n_frames <= 0) return 0;
-    const long long last = first_frame + n_frames - 1;
-    if (first_frame < 0 || last >= f->frames || f->frames - first_frame > f->slots) return set_error(KFX_E_RANGE, "kfx_slab_frame_timings: frames not in the ring");
-    const float nan = __builtin_nanf("");
-    for (int i = 0; i < n_frames; ++i) {
-        const long long fr = first_frame + i;
-        const int slot = (int)(fr % f->slots);
-        float* o = ms + (size_t)i * KFX_SLAB_FRAME_TIMING_FIELDS;
-        for (int k = 0; k < KFX_SLAB_FRAME_TIMING_FIELDS; ++k) o[k] = nan;
-        if (f->ev_frame[slot] != fr) {
-            if (f->ev_frame[slot] > fr) return set_error(KFX_E_RANGE, "kfx_slab_frame_timings: frame overwritten");
-            continue;   // stepped with the events switched off
-        }
-        const unsigned m = f->ev_mask[slot];
-        hipEvent_t* e = f->ev + (size_t)slot * EV;
-        int lastk = -1;
-        for (int k = 0; k < EV; ++k) if (m & (1u << k)) lastk = k;
-        if (lastk < 0) continue;
-        hipError_t he = hipEventSynchronize(e[lastk]);
-        if (he == hipSuccess && (m & 16u)) he = hipEventSynchronize(e[4]);   // (the merge's event may live on the side stream)
-        const auto span = [&](int a, int b, float* out) {
-            if (he == hipSuccess && (m & (1u << a)) && (m & (1u << b))) he = hipEventElapsedTime(out, e[a], e[b]);
-        };
-        int firstk = 0;
-        while (!(m & (1u << firstk))) ++firstk;
-        span(0, 1, &o[0]);
-        span(1, 2, &o[1]);
-        span(2, 3, &o[2]);
-        span(3, 4, &o[3]);
-        if (firstk != lastk) span(firstk, lastk, &o[4]);
-        // period: this frame's first recorded event to the same event of the next frame
-        if (he == hipSuccess && fr + 1 < f->frames) {
-            const int ns = (int)((fr + 1) % f->slots);
-            if (f->ev_frame[ns] == fr + 1 && (f->ev_mask[ns] & (1u << firstk))) {
-                he = hipEventSynchronize(f->ev[(size_t)ns * EV + firstk]);
-                if (he == hipSuccess) he = hipEventElapsedTime(&o[5], e[firstk], f->ev[(size_t)ns * EV + firstk]);
-            }
-        }
-        if (he != hipSuccess) { (void)hipGetLastError(); return set_error((int)he, "kfx_slab_frame_timings: hipEventElapsedTime"); }
-    }
-    return 0;
+    return ring_timings(f->ring, f->frames, first_frame, n_frames, KFX_SLAB_FRAME_TIMING_FIELDS, ms, slab_frame_spans, "kfx_slab_frame_timings");
 }
 
 // synchronise everything this frame object has in flight and report a failed exact march
