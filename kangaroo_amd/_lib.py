@@ -61,7 +61,7 @@ class KfxError(RuntimeError):
 
 PI, PV, PF = C.POINTER(KfxImage), C.POINTER(KfxVolume), C.POINTER(C.c_float)
 
-# name -> (restype, argtypes); every symbol include/kfx.h declares (and kfx_summary_h.h, kfx_mesh.h, kfx_color.h, kfx_slab_color.h)
+# name -> (restype, argtypes); every symbol include/kfx.h declares (and kfx_summary_h.h, kfx_mesh.h, kfx_color.h, kfx_slab_color.h, kfx_sensor.h)
 SIGNATURES = {
     "kfx_sdf_fuse": (C.c_int, [PV, PI, PI, PF, PF, C.c_float, C.c_float, C.c_float, C.c_uint, C.c_void_p]),
     "kfx_sdf_fuse_slab": (C.c_int, [PV, C.POINTER(KfxSlab), PI, PI, PF, PF, C.c_float, C.c_float, C.c_float, C.c_uint, C.c_void_p]),
@@ -179,6 +179,16 @@ SIGNATURES = {
     "kfx_frame_timings": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, PF]),
     "kfx_frame_set_timing": (C.c_int, [C.c_void_p, C.c_uint]),
     "kfx_raycast_sdf_levels_tracked": (C.c_int, [C.c_int, C.POINTER(PI), C.POINTER(PI), C.POINTER(PI), C.POINTER(PI), PV, C.c_void_p, PF, PF, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p]),
+    # include/kfx_sensor.h (the ring and the frame as void*)
+    "kfx_elementwise_scale_bias_u16": (C.c_int, [PI, PI, C.c_float, C.c_float, C.c_void_p]),
+    "kfx_bilateral_depth": (C.c_int, [PI, PI, PI, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint, C.c_float, C.c_void_p]),
+    "kfx_depth_input_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t, C.c_size_t, C.c_int, C.c_float, C.c_float, C.c_int]),
+    "kfx_depth_input_destroy": (C.c_int, [C.c_void_p]),
+    "kfx_depth_input_acquire": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "kfx_depth_input_submit": (C.c_int, [C.c_void_p]),
+    "kfx_depth_input_pending": (C.c_int, [C.c_void_p]),
+    "kfx_depth_input_filter": (C.c_int, [C.c_void_p, PI, PI, C.c_float, C.c_float, C.c_uint, C.c_float, C.c_void_p]),
+    "kfx_frame_set_input": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

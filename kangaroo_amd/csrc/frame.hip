@@ -10,6 +10,7 @@
 
 #include "kfx_device.h"
 #include "frame_host.h"
+#include "sensor_host.h"
 
 struct kfx_frame {
     kfx_frame_config cfg;
@@ -19,6 +20,7 @@ struct kfx_frame {
     kfx::EventRing ring;        // four events per frame: before preprocess, before SdfFuse, after SdfFuse, after RaycastSdf
     unsigned mask;              // which events the next steps record (kfx_frame_set_timing)
     kfx_image texels;           // (frame_host.h; a step that integrates without preprocessing lets kfx_sdf_fuse pack its own)
+    kfx_depth_input* input;     // not owned (kfx_frame_set_input, include/kfx_sensor.h): where a step without `raw` takes its image from
 };
 
 using namespace kfx;
@@ -37,6 +39,7 @@ extern "C" int kfx_frame_create(kfx_frame** out, const kfx_frame_config* cfg)
     f->track = 0;
     f->frames = 0;
     f->mask = KFX_FRAME_EVENTS_ALL;
+    f->input = nullptr;
     f->texels = texel_image_alloc(cfg->filtered.w, cfg->filtered.h);
     if (int e = ring_create(f->ring, 4, cfg->timing_slots, -1, "kfx_frame_create")) {
         texel_image_free(f->texels);
@@ -87,7 +90,15 @@ extern "C" int kfx_frame_set_track(kfx_frame* f, int on, kfx_stream stream)
     return 0;
 }
 
-// SdfReset(vol, NaN): "never observed" = (NaN, 0) (main.cpp:229)
+extern "C" int kfx_frame_set_input(kfx_frame* f, kfx_depth_input* in)
+{
+    if (!f) return set_error(KFX_E_NULL, "kfx_frame_set_input: null frame");
+    if (in && !depth_input_matches(in, f->cfg.filtered.w, f->cfg.filtered.h)) return set_error(KFX_E_SHAPE, "kfx_frame_set_input: the ring's image size differs from the frame's");
+    f->input = in;
+    return 0;
+}
+
+// SdfReset(vol, NaN): "never observed" = (NaN, 0) (main.cpp:229); images pending in an attached upload ring stay pending
 extern "C" int kfx_frame_reset(kfx_frame* f, kfx_stream stream)
 {
     if (!f) return set_error(KFX_E_NULL, "kfx_frame_reset: null frame");
@@ -107,6 +118,11 @@ extern "C" int kfx_frame_step(kfx_frame* f, const kfx_image* raw, const float T_
         se3_inverse(T_wc, inv);
         T_cw = inv;
     }
+    // the sensor image of this step: the oldest pending upload, which the stream waits for BEFORE the first timing event (the
+    // preprocess span stays kernel time; a late upload lengthens the period)
+    kfx_depth_input* const sensor = (!raw && (parts & KFX_FRAME_PREPROCESS)) ? f->input : nullptr;
+    if (sensor)
+        if (int e0 = depth_input_wait(sensor, stream)) return e0;
     ring_begin(f->ring, f->frames, f->mask);
     int e = 0;
     const auto record = [&](int k) {   // (a failed record is reported, the frame stops)
@@ -117,7 +133,8 @@ extern "C" int kfx_frame_step(kfx_frame* f, const kfx_image* raw, const float T_
     // the packed texels travel from this step's preprocess to this step's SdfFuse only (nobody else can have touched the maps in between)
     const kfx_image* tex = ((parts & KFX_FRAME_PREPROCESS) && (parts & KFX_FRAME_FUSE) && f->texels.ptr) ? &f->texels : nullptr;
     if (!e && (parts & KFX_FRAME_PREPROCESS)) {
-        e = kfx_bilateral_f32(&c.filtered, src, c.bilateral_gs, c.bilateral_gr, c.bilateral_size, c.bilateral_minval, 1, stream);
+        if (sensor) e = depth_input_consume(sensor, &c.filtered, &c.raw, c.bilateral_gs, c.bilateral_gr, c.bilateral_size, c.bilateral_minval, stream);
+        else e = kfx_bilateral_f32(&c.filtered, src, c.bilateral_gs, c.bilateral_gr, c.bilateral_size, c.bilateral_minval, 1, stream);
         if (!e) e = depth_to_vbo_normals_texels(&c.vbo, &c.normals, &c.filtered, c.K, 1.0f, tex, stream);
     }
     record(1);

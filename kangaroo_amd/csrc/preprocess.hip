@@ -9,6 +9,7 @@
 
 #include "kfx_device.h"
 #include "host_args.h"
+#include "sensor_host.h"
 
 namespace kfx {
 
@@ -35,13 +36,40 @@ __device__ __forceinline__ float load_clamped(const BilParams& p, int x, int y)
     return (float)reinterpret_cast<const Ti*>(p.in + (size_t)y * p.in_pitch)[x];
 }
 
+// KernElementwiseScaleBias (cu_operations.cu:39-49), b = s*a + offset: the ONE statement behind k_scale_bias_f32 / _u16 and behind the
+// converting loads of the k_bilateral_depth* kernels, so that a sensor image filtered in one launch carries the bits of ScaleBias
+// followed by BilateralFilter in both numerics modes.
+__device__ __forceinline__ float scale_bias(float a, float s, float offset) { return s * a + offset; }
+
+// What a bilateral kernel makes of a loaded pixel.  AsLoaded: the image is what is filtered (k_bilateral*).  ToMetres: the image is
+// in sensor units (include/kfx_sensor.h); what is filtered is scale_bias() of it, and a workgroup writes that value of its own
+// output pixels (not of the apron) to the optional `metres` image.
+struct AsLoaded {
+    __device__ __forceinline__ float operator()(float v) const { return v; }
+    __device__ __forceinline__ void keep(int, int, float) const {}
+};
+struct ToMetres {
+    unsigned char* metres;   // Image<float> of the output's size, or null
+    size_t mpitch;
+    float s, offset;
+    __device__ __forceinline__ float operator()(float v) const { return scale_bias(v, s, offset); }
+    __device__ __forceinline__ void keep(int x, int y, float m) const
+    {
+        if (metres) reinterpret_cast<float*>(metres + (size_t)y * mpitch)[x] = m;
+    }
+};
+struct BilDepthParams {
+    BilParams b;
+    ToMetres c;
+};
+
 // Workgroup = TX x TY threads (256), each thread filters PY pixels of one column, so the LDS
 // tile is (TX + 2R) x (TY*PY + 2R): taller tiles amortise the apron (7x7 window at TX x TY*PY =
 // 32x8: 2.1 loads per output pixel, 32x32: 1.4).  Integer inputs are held as float in LDS: every
 // uchar/ushort value and every difference of two is exactly representable, so (float)(p - q),
 // q >= minval and w * q give the reference's results.
-template <typename Ti, int TX, int TY, int PY>
-__global__ __launch_bounds__(TX * TY) void k_bilateral(const BilParams p)
+template <typename Ti, int TX, int TY, int PY, typename Conv>
+__device__ __forceinline__ void bilateral_tile(const BilParams p, const Conv conv)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int NT = TX * TY;
@@ -54,7 +82,7 @@ __global__ __launch_bounds__(TX * TY) void k_bilateral(const BilParams p)
 
     for (int i = tid; i < TW * TH; i += NT) {
         const int ty = i / TW, tx = i - ty * TW;
-        tile[i] = load_clamped<Ti>(p, bx + tx - R, by + ty - R);
+        tile[i] = conv(load_clamped<Ti>(p, bx + tx - R, by + ty - R));
     }
     for (int i = tid; i < D * D; i += NT) {
         const int r = i / D - R, c = i % D - R;
@@ -73,6 +101,7 @@ __global__ __launch_bounds__(TX * TY) void k_bilateral(const BilParams p)
         const int y = by + ly;
         if (y >= p.h) break;
         const float pc = tile[(ly + R) * TW + lx + R];
+        conv.keep(x, y, pc);
         float sum = 0.f, sumw = 0.f;
         if (!p.use_minval || pc >= p.minval) {
             for (int r = 0; r < D; ++r) {
@@ -94,14 +123,24 @@ __global__ __launch_bounds__(TX * TY) void k_bilateral(const BilParams p)
         reinterpret_cast<float*>(p.out + (size_t)y * p.out_pitch)[x] = sum / sumw;
     }
 }
+template <typename Ti, int TX, int TY, int PY>
+__global__ __launch_bounds__(TX * TY) void k_bilateral(const BilParams p)
+{
+    bilateral_tile<Ti, TX, TY, PY>(p, AsLoaded{});
+}
+template <typename Ti, int TX, int TY, int PY>
+__global__ __launch_bounds__(TX * TY) void k_bilateral_depth(const BilDepthParams p)
+{
+    bilateral_tile<Ti, TX, TY, PY>(p.b, p.c);
+}
 
 // Fast-numerics variant (kfx_set_math_mode(KFX_MATH_FAST)) for a compile-time radius: the exact kernel spends most of
 // its time in the correctly rounded division -(id2) / (2 gr^2) of every tap (49 per pixel at R = 3) and in a
 // data-dependent branch per tap.  Here the exponent argument is id2 * (-1 / (2 gr^2)) (one reciprocal per thread:
 // the argument moves by <= 1.5 ulp, far inside the accuracy of the hardware exp), validity is a select and the
 // (2R+1)^2 taps are fully unrolled.  Same tile, same tap order, same hardware exp.
-template <typename Ti, int R>
-__global__ __launch_bounds__(256) void k_bilateral_fast(const BilParams p)
+template <typename Ti, int R, typename Conv>
+__device__ __forceinline__ void bilateral_fast_tile(const BilParams& p, const Conv& conv)
 {
     constexpr int TX = 16, TY = 16, D = 2 * R + 1, TW = TX + 2 * R, TH = TY + 2 * R;
     __shared__ float tile[TH * TW];
@@ -110,7 +149,7 @@ __global__ __launch_bounds__(256) void k_bilateral_fast(const BilParams p)
     const int bx = blockIdx.x * TX, by = blockIdx.y * TY;
     for (int i = tid; i < TW * TH; i += 256) {
         const int ty = i / TW, tx = i - ty * TW;
-        tile[i] = load_clamped<Ti>(p, bx + tx - R, by + ty - R);
+        tile[i] = conv(load_clamped<Ti>(p, bx + tx - R, by + ty - R));
     }
     if (tid < D * D) {
         const int r = tid / D - R, c = tid % D - R;
@@ -122,6 +161,7 @@ __global__ __launch_bounds__(256) void k_bilateral_fast(const BilParams p)
     if (x >= p.w || y >= p.h) return;
     const float k = -1.0f / (2 * p.gr * p.gr);
     const float pc = tile[(ly + R) * TW + lx + R];
+    conv.keep(x, y, pc);
     const bool check = p.use_minval != 0;
     float sum = 0.f, sumw = 0.f;
 #pragma unroll
@@ -138,19 +178,30 @@ __global__ __launch_bounds__(256) void k_bilateral_fast(const BilParams p)
     if (check && !(pc >= p.minval)) sum = sumw = 0.f; // the reference skips the window: 0 / 0 = NaN
     reinterpret_cast<float*>(p.out + (size_t)y * p.out_pitch)[x] = sum / sumw;
 }
+template <typename Ti, int R>
+__global__ __launch_bounds__(256) void k_bilateral_fast(const BilParams p)
+{
+    bilateral_fast_tile<Ti, R>(p, AsLoaded{});
+}
+template <typename Ti, int R>
+__global__ __launch_bounds__(256) void k_bilateral_depth_fast(const BilDepthParams p)
+{
+    bilateral_fast_tile<Ti, R>(p.b, p.c);
+}
 
 // Window too large for the LDS tile: straight global gathers.
-template <typename Ti>
-__global__ __launch_bounds__(256) void k_bilateral_global(const BilParams p)
+template <typename Ti, typename Conv>
+__device__ __forceinline__ void bilateral_gather(const BilParams& p, const Conv& conv)
 {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= p.w || y >= p.h) return;
-    const float pc = (float)reinterpret_cast<const Ti*>(p.in + (size_t)y * p.in_pitch)[x];
+    const float pc = conv((float)reinterpret_cast<const Ti*>(p.in + (size_t)y * p.in_pitch)[x]);
+    conv.keep(x, y, pc);
     float sum = 0.f, sumw = 0.f;
     if (!p.use_minval || pc >= p.minval) {
         for (int r = -p.R; r <= p.R; ++r)
             for (int c = -p.R; c <= p.R; ++c) {
-                const float q = load_clamped<Ti>(p, x + c, y + r);
+                const float q = conv(load_clamped<Ti>(p, x + c, y + r));
                 if (!p.use_minval || q >= p.minval) {
                     const float sd2 = (float)(r * r + c * c);
                     const float id = pc - q;
@@ -162,6 +213,16 @@ __global__ __launch_bounds__(256) void k_bilateral_global(const BilParams p)
             }
     }
     reinterpret_cast<float*>(p.out + (size_t)y * p.out_pitch)[x] = sum / sumw;
+}
+template <typename Ti>
+__global__ __launch_bounds__(256) void k_bilateral_global(const BilParams p)
+{
+    bilateral_gather<Ti>(p, AsLoaded{});
+}
+template <typename Ti>
+__global__ __launch_bounds__(256) void k_bilateral_depth_global(const BilDepthParams p)
+{
+    bilateral_gather<Ti>(p.b, p.c);
 }
 
 // Joint ("cross") bilateral filter with an external guide image (cu_bilateral.cu:110-143): weights
@@ -318,7 +379,15 @@ __global__ __launch_bounds__(256) void k_scale_bias_f32(const EwParams p)
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= p.w || y >= p.h) return;
     const float v1 = reinterpret_cast<const float*>(p.in + (size_t)y * p.in_pitch)[x];
-    reinterpret_cast<float*>(p.out + (size_t)y * p.out_pitch)[x] = p.s * v1 + p.offset;
+    reinterpret_cast<float*>(p.out + (size_t)y * p.out_pitch)[x] = scale_bias(v1, p.s, p.offset);
+}
+// KernElementwiseScaleBias<float,unsigned short,float>: a sensor's 16-bit readings, each exactly a float
+__global__ __launch_bounds__(256) void k_scale_bias_u16(const EwParams p)
+{
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= p.w || y >= p.h) return;
+    const float v1 = (float)reinterpret_cast<const unsigned short*>(p.in + (size_t)y * p.in_pitch)[x];
+    reinterpret_cast<float*>(p.out + (size_t)y * p.out_pitch)[x] = scale_bias(v1, p.s, p.offset);
 }
 
 // KernBoxHalfIgnoreInvalid<float,float,float> (cu_resample.cu:89-111): mean of the finite samples of
@@ -546,6 +615,79 @@ static int bilateral_launch(const kfx_image* out, const kfx_image* in, float gs,
     return check_launch("kfx_bilateral");
 }
 
+// BilateralFilter of a sensor image (include/kfx_sensor.h): bilateral_launch's choice of kernel and grid, the k_bilateral_depth*
+// instantiation of each.  launch = false: the argument checks alone (the upload ring consumes an image only once they pass).
+template <typename Ti>
+static int bilateral_depth_launch(const kfx_image* out, const kfx_image* metres, const kfx_image* in, float s, float offset, float gs, float gr,
+                                  unsigned size, float minval, bool launch, kfx_stream stream)
+{
+    if (int e = check_image(out, 4, 0, 0, "BilateralFilterDepth: filtered image")) return e;
+    if (metres) { if (int e = check_image(metres, 4, cover_w(out), cover_h(out), "BilateralFilterDepth: metres image")) return e; }
+    if (int e = check_image(in, sizeof(Ti), cover_w(out), cover_h(out), "BilateralFilterDepth: sensor image")) return e;
+    if (out->w == 0 || out->h == 0) return 0;
+    if (size > 1024) return set_error(KFX_E_RANGE, "BilateralFilterDepth: window radius");
+    if (!launch) return 0;
+    BilDepthParams q;
+    BilParams& p = q.b;
+    p.in = (const unsigned char*)in->ptr;
+    p.in_pitch = in->pitch;
+    p.out = (unsigned char*)out->ptr;
+    p.out_pitch = out->pitch;
+    p.w = (int)out->w;
+    p.h = (int)out->h;
+    p.iw = (int)in->w;
+    p.ih = (int)in->h;
+    p.R = (int)size;
+    p.gs = gs;
+    p.gr = gr;
+    p.minval = minval;
+    p.use_minval = 1;
+    q.c = ToMetres{metres ? (unsigned char*)metres->ptr : nullptr, metres ? metres->pitch : 0, s, offset};
+    hipStream_t st = (hipStream_t)stream;
+    if (math_mode() == KFX_MATH_FAST && p.R >= 1 && p.R <= 3) {
+        dim3 grid(ceil_div(p.w, 16), ceil_div(p.h, 16));
+        if (p.R == 3) hipLaunchKernelGGL((k_bilateral_depth_fast<Ti, 3>), grid, dim3(256), 0, st, q);
+        else if (p.R == 2) hipLaunchKernelGGL((k_bilateral_depth_fast<Ti, 2>), grid, dim3(256), 0, st, q);
+        else hipLaunchKernelGGL((k_bilateral_depth_fast<Ti, 1>), grid, dim3(256), 0, st, q);
+    } else if (p.R <= BIL_MAX_R) {
+        const int D = 2 * p.R + 1;
+        static const int shape = env_int("KFX_BILATERAL_TILE", 2);   // (bilateral_launch's knob and shapes)
+#define KFX_BIL(TX_, TY_, PY_)                                                                                   \
+    do {                                                                                                        \
+        const size_t lds = (size_t)((TX_ + 2 * p.R) * (TY_ * PY_ + 2 * p.R) + D * D) * sizeof(float);           \
+        dim3 grid(ceil_div(p.w, TX_), ceil_div(p.h, TY_ * PY_));                                                \
+        hipLaunchKernelGGL((k_bilateral_depth<Ti, TX_, TY_, PY_>), grid, dim3(TX_ * TY_), lds, st, q);          \
+    } while (0)
+        switch (shape) {
+        case 0: KFX_BIL(32, 8, 1); break;
+        case 1: KFX_BIL(64, 4, 1); break;
+        case 3: KFX_BIL(32, 8, 2); break;
+        case 4: KFX_BIL(32, 8, 4); break;
+        case 5: KFX_BIL(64, 4, 4); break;
+        default: KFX_BIL(16, 16, 1); break;
+        }
+#undef KFX_BIL
+    } else {
+        hipLaunchKernelGGL(k_bilateral_depth_global<Ti>, pixel_grid(p.w, p.h), dim3(256), 0, st, q);
+    }
+    return check_launch("kfx_bilateral_depth");
+}
+
+int kfx::bilateral_depth(const kfx_image* filtered, const kfx_image* metres, const kfx_image* raw, int format, float s, float offset, float gs,
+                         float gr, unsigned size, float minval, bool launch, kfx_stream stream)
+{
+    if (format == KFX_DEPTH_U16) return bilateral_depth_launch<unsigned short>(filtered, metres, raw, s, offset, gs, gr, size, minval, launch, stream);
+    if (format == KFX_DEPTH_F32) return bilateral_depth_launch<float>(filtered, metres, raw, s, offset, gs, gr, size, minval, launch, stream);
+    return set_error(KFX_E_RANGE, "BilateralFilterDepth: format is KFX_DEPTH_U16 or KFX_DEPTH_F32");
+}
+
+// BilateralFilter(filtered, s * raw + offset, gs, gr, size, minval) with the converted image kept in `metres` (may be null)
+extern "C" int kfx_bilateral_depth(const kfx_image* filtered, const kfx_image* metres, const kfx_image* raw, int format, float s, float offset,
+                                   float gs, float gr, unsigned size, float minval, kfx_stream stream)
+{
+    return kfx::bilateral_depth(filtered, metres, raw, format, s, offset, gs, gr, size, minval, true, stream);
+}
+
 extern "C" int kfx_bilateral_f32(const kfx_image* out, const kfx_image* in, float gs, float gr, unsigned size,
                                  float minval, int use_minval, kfx_stream stream)
 {
@@ -604,6 +746,17 @@ extern "C" int kfx_elementwise_scale_bias_f32(const kfx_image* out, const kfx_im
     EwParams p{(const unsigned char*)in->ptr, in->pitch, (unsigned char*)out->ptr, out->pitch, (int)out->w, (int)out->h, s, offset};
     hipLaunchKernelGGL(k_scale_bias_f32, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("kfx_elementwise_scale_bias_f32");
+}
+
+// ElementwiseScaleBias<float, unsigned short, float> (cu_operations.cu:39-57)
+extern "C" int kfx_elementwise_scale_bias_u16(const kfx_image* out, const kfx_image* in, float s, float offset, kfx_stream stream)
+{
+    if (int e = check_image(out, 4, 0, 0, "ElementwiseScaleBias: output image")) return e;
+    if (int e = check_image(in, 2, cover_w(out), cover_h(out), "ElementwiseScaleBias: input image")) return e;
+    if (out->w == 0 || out->h == 0) return 0;
+    EwParams p{(const unsigned char*)in->ptr, in->pitch, (unsigned char*)out->ptr, out->pitch, (int)out->w, (int)out->h, s, offset};
+    hipLaunchKernelGGL(k_scale_bias_u16, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
+    return check_launch("kfx_elementwise_scale_bias_u16");
 }
 
 extern "C" int kfx_box_half_ignore_invalid_f32(const kfx_image* out, const kfx_image* in, kfx_stream stream)

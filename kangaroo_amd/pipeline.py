@@ -46,8 +46,12 @@ class FramePipeline:
     def __init__(self, ops, dims, boxmin, boxmax, w, h, K=None, near=0.4, far=8.0, bilateral=None,
                  trunc_factor=scenes.TRUNC_DIST_FACTOR, max_w=scenes.MAX_W, mincostheta=scenes.MIN_COS_THETA,
                  contiguous_images=False, track=False, cal_first=None, cal_block=None, cal_margin=None, timing_slots=None, kind=None,
-                 color=False, color_size=None, T_cd=None):
-        """color: the reference application's fuse_color mode (main.cpp:233, :238, :284, :353): the pipeline owns a colour volume
+                 color=False, color_size=None, T_cd=None, sensor=None, sensor_scale=1e-3, sensor_slots=2):
+        """sensor: "u16" or "f32" -- the frames arrive as raw sensor images on the host (main.cpp:202-209): the pipeline owns an upload
+        ring (ops.DepthInput, `input`) of sensor_slots slots that converts with sensor_scale (millimetres: 1e-3) while it filters.
+        submit(array) hands it the next image -- one frame ahead, its copy runs beside the current frame -- and a step / preprocess
+        that is given no image consumes the oldest submitted one; self.raw then holds that frame's depth in metres.
+        color: the reference application's fuse_color mode (main.cpp:233, :238, :284, :353): the pipeline owns a colour volume
         (kind "c32", `cvol`) beside the SDF volume and an RGB image (`rgb`, "u8x3", color_size = (w, h) of the colour camera,
         default the depth camera's; its intrinsics `Kimg` are the application's for that size); step() fuses with SdfFuseColor at
         T_iw = T_cd * T_cw (T_cd: colour <- depth camera, 3x4 or 4x4, default identity) and renders the colour volume into ray_i.
@@ -88,6 +92,12 @@ class FramePipeline:
         self._cal = None
         self.summary = None
         self.kframe = None
+        self.input = None
+        if sensor is not None:
+            if not hasattr(ops, "DepthInput"):
+                raise ValueError("FramePipeline: sensor= needs an operator set with DepthInput")
+            if sensor not in ("u16", "f32"):
+                raise ValueError("FramePipeline: sensor must be 'u16' or 'f32', not %r" % (sensor,))
         self.dims = tuple(int(d) for d in dims)
         self.w, self.h = int(w), int(h)
         self.K = scenes.intrinsics(w, h) if K is None else np.asarray(K, np.float32)
@@ -123,6 +133,10 @@ class FramePipeline:
         self.timing = 0
         if self.kframe is not None:
             self.kframe.set_timing(self.timing)
+        if sensor is not None:
+            self.input = ops.DepthInput(self.w, self.h, sensor, sensor_scale, 0.0, sensor_slots)
+            if self.kframe is not None:
+                self.kframe.set_input(self.input)
         track_now, self.track = self.track, False
         self.set_track(track_now)
         self.reset()
@@ -193,14 +207,25 @@ class FramePipeline:
         self._timed_fuse(lambda kw: self.ops.SdfFuseColor(self.vol, self.cvol, maps_d, maps_n, T_cw, self.K, self._rgb_now, self.color_pose(T_cw), self.Kimg,
                                                           self.trunc, self.max_w, self.mincostheta, **kw))
 
+    def submit(self, array):
+        """sensor=: the next frame's raw image (h x w, the sensor's type) into the upload ring; its copy is enqueued at once."""
+        self.input.submit(array)
+
+    def _filter(self, filtered, raw_image):
+        """BilateralFilter of the frame's image into `filtered`: the given image, else the oldest one in the upload ring (whose
+        metres go to self.raw), else self.raw"""
+        b = self.bil
+        if raw_image is None and self.input is not None:
+            self.input.filter(filtered, self.raw, b["gs"], b["gr"], b["size"], b["minval"])
+        else:
+            self.ops.BilateralFilter(filtered, self.raw if raw_image is None else raw_image, b["gs"], b["gr"], b["size"], b["minval"])
+
     def preprocess(self, raw_image=None):
-        if self.kframe is not None:
+        if self.kframe is not None:   # (with an upload ring attached, a step without an image consumes from it)
             self.kframe.step(_IDENTITY, None, raw_image, self.kframe.PREPROCESS)
             return
-        o = self.ops
-        src = self.raw if raw_image is None else raw_image
-        o.BilateralFilter(self.filtered, src, self.bil["gs"], self.bil["gr"], self.bil["size"], self.bil["minval"])
-        vbo_normals(o, self.vbo, self.normals, self.filtered, self.K)
+        self._filter(self.filtered, raw_image)
+        vbo_normals(self.ops, self.vbo, self.normals, self.filtered, self.K)
 
     # -- the auto policy ------------------------------------------------------------
     def _policy_before(self):
@@ -309,6 +334,9 @@ class FramePipeline:
 
 _IDENTITY = np.array([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, 0]], np.float32)
 
+# TrackingPipeline.step(next_image=FROM_SENSOR): the next frame's image is the next one in the upload ring (sensor=)
+FROM_SENSOR = "the next image of the upload ring"
+
 
 class TrackingPipeline(FramePipeline):
     """The reference application's loop with pose estimation switched on (main.cpp:200-356): depth pyramid,
@@ -352,9 +380,8 @@ class TrackingPipeline(FramePipeline):
 
     def preprocess(self, raw_image=None, into=None):
         o = self.ops
-        src = self.raw if raw_image is None else raw_image
         kin_d, kin_v, kin_n = (self.kin_d, self.kin_v, self.kin_n) if into is None else into
-        o.BilateralFilter(kin_d[0], src, self.bil["gs"], self.bil["gr"], self.bil["size"], self.bil["minval"])
+        self._filter(kin_d[0], None if raw_image is FROM_SENSOR else raw_image)
         if hasattr(o, "DepthPyramidVboNormals"):   # the pyramid and its maps from one launch (same images)
             o.DepthPyramidVboNormals(kin_d, kin_v, kin_n, self.K_levels)
             return
@@ -373,7 +400,8 @@ class TrackingPipeline(FramePipeline):
     def step(self, T_wl_init=None, raw_image=None, next_image=None, rgb_image=None):
         """One frame.  The first frame is fused at T_wl_init (identity if None); later frames are tracked
         against the model.  Returns the current T_wl (4x4 float64).
-        next_image: the depth image the NEXT step will be given (already in device memory).  With the device-resident
+        next_image: the depth image the NEXT step will be given (already in device memory; sensor=: FROM_SENSOR, the image
+        submitted after this frame's, and the next step is given no image).  With the device-resident
         refinement its pre-amble -- which does not depend on any pose -- is enqueued behind the refinement, before this thread
         waits for the pose: the device works on it while the thread wakes up instead of idling until SdfFuse arrives.  The
         next step finds its maps ready when it is given the same image object; same images, same poses.
@@ -384,6 +412,8 @@ class TrackingPipeline(FramePipeline):
         cal = self._cal is not None and self.frames_done >= self._cal["first"]
         if cal:   # track="auto": whole frames of the three blocks, host clock around the step (the pose read-back synchronises)
             self._policy_before()
+        if raw_image is None and self.input is not None:
+            raw_image = FROM_SENSOR
         if raw_image is not None and self._prefetched is raw_image:
             (self.kin_d, self.kin_v, self.kin_n), self._kin_back = self._kin_back, (self.kin_d, self.kin_v, self.kin_n)
         else:
@@ -510,6 +540,9 @@ class SlabPipeline(FramePipeline):
         deterministic per voxel, so no traffic is needed) -- the cross-check of the exchange path."""
         assert halo in ("exchange", "recompute")
         assert raycast in ("composite", "exact", "exact_allreduce")
+        if kw.get("sensor") is not None:
+            raise ValueError("SlabPipeline: sensor= (the upload ring of raw sensor images) is a single-GPU option; give the slab pipelines "
+                             "depth images in metres")
         # inputs (SURVEY.md 8(e) "input distribution"): "replicate" = every rank filters the frame and derives the normal map
         # itself (no traffic); "broadcast" = rank 0 does, and its filtered depth + normal map (20 B per pixel) are broadcast
         assert inputs in ("replicate", "broadcast")

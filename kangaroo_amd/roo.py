@@ -372,6 +372,12 @@ class Frame:
         if e:
             _lib.check(e)
 
+    def set_input(self, depth_input):
+        """kfx_frame_set_input (include/kfx_sensor.h): a step with raw=None then consumes the oldest image pending in the
+        DepthInput -- filtered into `filtered`, its metres into `raw` -- instead of filtering `raw`.  None detaches."""
+        _lib.check(_lib.load().kfx_frame_set_input(self.handle, depth_input.handle if depth_input is not None else None))
+        self._input = depth_input   # (kept alive while attached)
+
     def timings(self, first, n):
         """(n, 5) float32 array in ms for frames first .. first + n - 1: preprocess, SdfFuse, RaycastSdf, whole frame, period
         (start of the frame to the start of the next; NaN for the most recent frame).  Waits for the last of them only."""
@@ -561,8 +567,71 @@ def SdfSphere(vol, center, r, stream=None):
 
 
 def ElementwiseScaleBias(b, a, s, offset=0.0, stream=None):
-    """roo::ElementwiseScaleBias<float,float,float> (cu_operations.h; main.cpp:208): b = s*a + offset."""
-    _lib.check(_lib.load().kfx_elementwise_scale_bias_f32(b.ref(), a.ref(), s, offset, _stream(stream)))
+    """roo::ElementwiseScaleBias<float,float,float> and <float,unsigned short,float> (cu_operations.h; main.cpp:207-208):
+    b = s*a + offset, a of kind "f32" or "u16"."""
+    L = _lib.load()
+    fn = {"f32": L.kfx_elementwise_scale_bias_f32, "u16": L.kfx_elementwise_scale_bias_u16}.get(a.kind)
+    if fn is None:
+        raise TypeError("ElementwiseScaleBias: input kind %r" % (a.kind,))
+    _lib.check(fn(b.ref(), a.ref(), s, offset, _stream(stream)))
+
+
+DEPTH_FORMAT = {"u16": 0, "f32": 1}   # KFX_DEPTH_U16 / KFX_DEPTH_F32 (include/kfx_sensor.h)
+
+
+def BilateralFilterDepth(dFiltered, dMetres, dRaw, s, offset, gs, gr, size, minval, stream=None):
+    """kfx_bilateral_depth: BilateralFilter(dFiltered, s * dRaw + offset, gs, gr, size, minval) in one launch; dRaw is a "u16" or
+    "f32" image in sensor units, dMetres (may be None) receives s * dRaw + offset.  Both outputs carry the bits of
+    ElementwiseScaleBias followed by BilateralFilter."""
+    if dRaw.kind not in DEPTH_FORMAT:
+        raise TypeError("BilateralFilterDepth: sensor image kind %r" % (dRaw.kind,))
+    _lib.check(_lib.load().kfx_bilateral_depth(dFiltered.ref(), dMetres.ref() if dMetres is not None else None, dRaw.ref(), DEPTH_FORMAT[dRaw.kind],
+                                               s, offset, gs, gr, size, minval, _stream(stream)))
+
+
+class DepthInput:
+    """kfx_depth_input (include/kfx_sensor.h): an upload ring for sensor depth images.  acquire() hands out a page-locked host
+    buffer as a numpy array (h, w) of the format's type; submit() copies it to the device on the ring's own stream; filter()
+    consumes the oldest pending image through BilateralFilterDepth on the current stream.  Submitting frame k + 1 before
+    filter() of frame k overlaps the copy with the frame."""
+
+    def __init__(self, w, h, kind="u16", s=1e-3, offset=0.0, slots=2):
+        if kind not in DEPTH_FORMAT:
+            raise TypeError("DepthInput: kind %r" % (kind,))
+        self.w, self.h, self.kind, self.slots = int(w), int(h), kind, int(slots)
+        self.s, self.offset = float(s), float(offset)
+        self.handle = C.c_void_p()
+        _lib.check(_lib.load().kfx_depth_input_create(C.byref(self.handle), self.w, self.h, DEPTH_FORMAT[kind], self.s, self.offset, self.slots))
+
+    def __del__(self):
+        try:
+            if self.handle is not None and self.handle.value:
+                _lib.load().kfx_depth_input_destroy(self.handle)
+                self.handle = None
+        except Exception:   # interpreter shutdown
+            pass
+
+    def acquire(self):
+        """The next slot's host buffer, valid until submit(); KfxError(KFX_E_RANGE) when every slot holds an unconsumed image."""
+        ptr, pitch = C.c_void_p(), C.c_size_t()
+        _lib.check(_lib.load().kfx_depth_input_acquire(self.handle, C.byref(ptr), C.byref(pitch)))
+        dt = np.dtype(_ELEM[self.kind][0])
+        buf = (C.c_char * (pitch.value * self.h)).from_address(ptr.value)
+        return np.frombuffer(buf, dtype=dt).reshape(self.h, pitch.value // dt.itemsize)[:, :self.w]
+
+    def submit(self, array=None):
+        """Enqueue the copy of the acquired buffer; with `array`, acquire a buffer and fill it with the array first."""
+        if array is not None:
+            self.acquire()[...] = array
+        _lib.check(_lib.load().kfx_depth_input_submit(self.handle))
+
+    @property
+    def pending(self):
+        return int(_lib.load().kfx_depth_input_pending(self.handle))
+
+    def filter(self, dFiltered, dMetres, gs, gr, size, minval, stream=None):
+        _lib.check(_lib.load().kfx_depth_input_filter(self.handle, dFiltered.ref(), dMetres.ref() if dMetres is not None else None, gs, gr, size,
+                                                      minval, _stream(stream)))
 
 
 def BoxHalfIgnoreInvalid(out, inp, stream=None):
