@@ -50,6 +50,9 @@ inline int check_image(const kfx_image* im, size_t elem, size_t min_w, size_t mi
     return 0;
 }
 
+// the device's view of a usable image
+inline ImgView img_view(const kfx_image& im) { return ImgView{(const unsigned char*)im.ptr, im.pitch, (int)im.w, (int)im.h}; }
+
 // What the input of a launch bounded by `out` has to cover where the entry point answers an empty launch with 0 before it compares
 // sizes: nothing then.
 inline size_t cover_w(const kfx_image* out) { return out->h ? out->w : 0; }

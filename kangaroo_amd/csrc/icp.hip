@@ -74,6 +74,30 @@ __device__ __forceinline__ void lss_store_agent(float* dst, const Lss& s)
     __hip_atomic_store(dst + 28, __uint_as_float(s.obs), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// The sum over the blocks' systems in the fixed order: thread t of the 256 adds blocks t, t + 256, ... in turn (lss_tree over the
+// 256 partial sums follows).  AgentLoads: the systems were written by other workgroups of this same launch (lss_store_agent), so
+// they are read with device-scope atomic loads, which go past this XCD's L2 as the stores did.
+template <bool AgentLoads>
+__device__ __forceinline__ void lss_block_sum(Lss& acc, const float* sums, const int nblocks, const int tid)
+{
+    lss_zero(acc);
+    for (int b = tid; b < nblocks; b += 256) {
+        const float* s = sums + (size_t)b * LSS_WORDS;
+        const auto word = [s](const int k) { return AgentLoads ? __hip_atomic_load(s + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : s[k]; };
+#pragma unroll
+        for (int k = 0; k < 28; ++k) acc.f[k] += word(k);
+        acc.obs += __float_as_uint(word(28));
+    }
+}
+
+// The result mailbox (ResultPort below), 128 bytes of mapped host memory: a kernel writes its payload -- the 29 words of a summed
+// system, or the 15 doubles {T, rmse, obs, good} -- and then, system-scope release, the call's sequence number into byte 124.
+constexpr int MAILBOX_BYTES = 128, MAILBOX_SEQ_WORD = 31;
+__device__ __forceinline__ void mailbox_post(void* mailbox, const unsigned seq)
+{
+    __hip_atomic_store(reinterpret_cast<unsigned*>(mailbox) + MAILBOX_SEQ_WORD, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 struct IcpParams {
     ImgView Pl, Pr, Nr;
     unsigned char* dbg; // may be null
@@ -159,27 +183,20 @@ __global__ __launch_bounds__(256) void k_icp_point_plane(const IcpParams p)
     if (tid == 0) lss_store(p.sums + (size_t)(blockIdx.y * gridDim.x + blockIdx.x) * LSS_WORDS, sum);
 }
 
-// sum of the per-block systems, fixed order; the result replaces sums[0..28].  mailbox (optional): 32 words of host memory mapped
-// into the device's address space -- the system again, then the sequence word `seq` with system-scope release: the host thread
-// that launched this spins on that word instead of enqueueing a copy and synchronising the stream (kfx_icp_point_plane).
+// sum of the per-block systems, fixed order; the result replaces sums[0..28].  mailbox (optional): the system again, then the
+// sequence word: the host thread spins on it instead of enqueueing a copy and synchronising the stream (kfx_icp_point_plane).
 __global__ __launch_bounds__(256) void k_lss_final(float* sums, const int nblocks, float* mailbox, const unsigned seq)
 {
     __shared__ float lds[LSS_WORDS * 128];
     const int tid = threadIdx.x;
     Lss acc;
-    lss_zero(acc);
-    for (int b = tid; b < nblocks; b += 256) {
-        const float* s = sums + (size_t)b * LSS_WORDS;
-#pragma unroll
-        for (int k = 0; k < 28; ++k) acc.f[k] += s[k];
-        acc.obs += __float_as_uint(s[28]);
-    }
+    lss_block_sum<false>(acc, sums, nblocks, tid);
     lss_tree(acc, tid, 256, lds); // its first __syncthreads orders every read above before the store below
     if (tid == 0) {
         lss_store(sums, acc);
         if (mailbox) {
             lss_store(mailbox, acc);
-            __hip_atomic_store(reinterpret_cast<unsigned*>(mailbox) + 31, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            mailbox_post(mailbox, seq);
         }
     }
 }
@@ -193,9 +210,10 @@ __global__ __launch_bounds__(256) void k_lss_final(float* sums, const int nblock
 // device memory for the next k_icp_point_plane.  The host enqueues all iterations back to back and synchronises once.
 // State (doubles): T_lp row-major 3x4 [0..11], rmse [12], obs [13], tracking flag [14]; floats: KT_lr[12], T_rl[12].
 // ---------------------------------------------------------------------------------------
+struct Verdict { double rmse, obs, good; };
 struct RefineState {
     double T[12];
-    double rmse, obs, good;
+    Verdict v;
     float pose[24];
 };
 
@@ -313,18 +331,49 @@ __device__ void publish_pose(RefineState* st, const float K[4]) { publish_pose(s
 
 struct K4 { float k[4]; };
 
-__global__ void k_icp_refine_init(RefineState* st, const K4 K)
+// element i of the identity pose (row-major 3x4)
+__host__ __device__ constexpr double identity12(const int i) { return i % 5 == 0 ? 1.0 : 0.0; }
+
+// the state before any evaluation: the identity, no residual, tracking good; K: intrinsics of the first evaluation's level
+__device__ void refine_state_init(RefineState* st, const float K[4])
 {
-    for (int i = 0; i < 12; ++i) st->T[i] = (i % 5 == 0) ? 1.0 : 0.0;
-    st->rmse = 0.0; st->obs = 0.0; st->good = 1.0;
-    publish_pose(st, K.k);
+    for (int i = 0; i < 12; ++i) st->T[i] = identity12(i);
+    st->v = Verdict{0.0, 0.0, 1.0};
+    publish_pose(st, K);
+}
+
+__global__ void k_icp_refine_init(RefineState* st, const K4 K) { refine_state_init(st, K.k); }
+
+// what a summed system says about the pose it was evaluated at (main.cpp:334-337)
+__device__ __forceinline__ Verdict lss_verdict(const float* sums, const float max_rmse)
+{
+    const float sq = sums[27];
+    const unsigned obs = __float_as_uint(sums[28]);
+    const float rmse = sqrtf(sq / (float)obs);
+    return Verdict{(double)rmse, (double)obs, rmse < max_rmse ? 1.0 : 0.0};
+}
+
+// T <- T * exp(-x_raw), x_raw the solution of the 6 x 6 system (rotation only: of its 3 x 3 block, the translation stays zero).
+// A full step with a non-finite component is refused: T is left alone and the result is false.
+__device__ bool apply_step(double T[12], const double* x_raw, const bool rotation_only)
+{
+    double x[6] = {0, 0, 0, 0, 0, 0};
+    bool moved = true;
+    if (rotation_only) {   // (the flag a literal at either call: one copy of the exponential that takes it at run time cost the chain 1 us per frame, profiles/icp_refactor)
+        for (int a = 0; a < 3; ++a) x[3 + a] = -x_raw[a];
+        se3_right_multiply_exp(T, x, true);
+    } else {
+        for (int a = 0; a < 6; ++a) { x[a] = -x_raw[a]; moved = moved && isfinite(x[a]); }
+        if (moved) se3_right_multiply_exp(T, x, false);
+    }
+    return moved;
 }
 
 // one Gauss-Newton step from the summed system in sums[0..28] (main.cpp:312-333); K_next: intrinsics of the level the
 // NEXT evaluation runs on
 __device__ void icp_solve_step(RefineState* st, const float* sums, const int rotation_only, const float max_rmse, const float K_next[4], SolveLds& w)
 {
-    double JTJ[36], JTy[6], x[6] = {0, 0, 0, 0, 0, 0};
+    double JTJ[36], JTy[6], x[6];
     int i = 6;
     for (int r = 0; r < 6; ++r)
         for (int c = 0; c <= r; ++c) {
@@ -333,27 +382,18 @@ __device__ void icp_solve_step(RefineState* st, const float* sums, const int rot
             JTJ[c * 6 + r] = e;
         }
     for (int r = 0; r < 6; ++r) { JTy[r] = (double)sums[r]; JTJ[r * 7] += 0.1 / 0.2; } // weak pose prior: depthSigma / motionSigma
-    const float sq = sums[27];
-    const unsigned obs = __float_as_uint(sums[28]);
-    const float rmse = sqrtf(sq / (float)obs);
-    st->rmse = (double)rmse;
-    st->obs = (double)obs;
-    st->good = rmse < max_rmse ? 1.0 : 0.0;
+    st->v = lss_verdict(sums, max_rmse);
     if (rotation_only) {
         double A3[9], b3[3];
         for (int a = 0; a < 3; ++a) {
             b3[a] = JTy[3 + a];
             for (int b = 0; b < 3; ++b) A3[a * 3 + b] = JTJ[(3 + a) * 6 + 3 + b];
         }
-        lu_solve_full_piv<3>(w, A3, b3, x + 3);
-        for (int a = 3; a < 6; ++a) x[a] = -x[a];
-        se3_right_multiply_exp(st->T, x, true);
+        lu_solve_full_piv<3>(w, A3, b3, x);
     } else {
         lu_solve_full_piv<6>(w, JTJ, JTy, x);
-        bool finite = true;
-        for (int a = 0; a < 6; ++a) { x[a] = -x[a]; finite = finite && isfinite(x[a]); }
-        if (finite) se3_right_multiply_exp(st->T, x, false);
     }
+    apply_step(st->T, x, rotation_only != 0);
     publish_pose(st, K_next);
 }
 
@@ -480,8 +520,8 @@ __device__ void lu_solve_wave(const float* sums, SolveLds& w)   // leaves x[0 ..
 // T_lane: st->T[lane] in lanes 0 .. 11, requested by the caller before the block sums were added up (one memory round trip
 // less on the one-lane tail)
 // always_store: write T even when the step is refused (the first evaluation of a call: st->T still holds the previous call's pose)
-// mailbox (optional): 16 doubles of host memory mapped into the device's address space -- the call's result {T, rmse, obs, good} goes
-// there too, then the sequence word (system-scope release) the host spins on (kfx_icp_refine: no copy command for the read-back)
+// mailbox (optional): the call's result {T, rmse, obs, good} goes there too, then the sequence word the host spins on
+// (kfx_icp_refine: no copy command for the read-back)
 __device__ void icp_solve_step_wave(RefineState* st, const float* sums, const int rotation_only, const float max_rmse, const float K_next[4], SolveLds& w,
                                     const double T_lane, const bool always_store = false, double* mailbox = nullptr, const unsigned seq = 0u)
 {
@@ -493,30 +533,15 @@ __device__ void icp_solve_step_wave(RefineState* st, const float* sums, const in
 #pragma unroll
     for (int m = 0; m < 12; ++m) T[m] = readlane_f64(T_lane, m);
     if (lane != 0) return;
-    const float sq = sums[27];
-    const unsigned obs = __float_as_uint(sums[28]);
-    const float rmse = sqrtf(sq / (float)obs);
-    st->rmse = (double)rmse;
-    st->obs = (double)obs;
-    st->good = rmse < max_rmse ? 1.0 : 0.0;
-    double x[6] = {0, 0, 0, 0, 0, 0};
-    bool moved = true;
-    if (rotation_only) {
-        for (int a = 0; a < 3; ++a) x[3 + a] = -w.x[a];
-        se3_right_multiply_exp(T, x, true);
-    } else {
-        for (int a = 0; a < 6; ++a) { x[a] = -w.x[a]; moved = moved && isfinite(x[a]); }
-        if (moved) se3_right_multiply_exp(T, x, false);
-    }
+    const Verdict v = st->v = lss_verdict(sums, max_rmse);
+    const bool moved = apply_step(T, w.x, rotation_only != 0);
     if (moved || always_store)
         for (int m = 0; m < 12; ++m) st->T[m] = T[m];
     publish_pose(st, K_next, T);
     if (mailbox) {   // (T is what st->T holds now: the step, or the pose before it when the step was refused)
         for (int m = 0; m < 12; ++m) mailbox[m] = T[m];
-        mailbox[12] = (double)rmse;
-        mailbox[13] = (double)obs;
-        mailbox[14] = rmse < max_rmse ? 1.0 : 0.0;
-        __hip_atomic_store(reinterpret_cast<unsigned*>(mailbox + 15), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        mailbox[12] = v.rmse; mailbox[13] = v.obs; mailbox[14] = v.good;
+        mailbox_post(mailbox, seq);
     }
 }
 
@@ -531,15 +556,9 @@ __global__ __launch_bounds__(256) void k_lss_final_solve(float* sums, const int 
     __shared__ float s_sum[LSS_WORDS];
     __shared__ SolveLds s_solve;
     const int tid = threadIdx.x;
-    const double T_lane = tid < 12 ? (first ? ((tid % 5 == 0) ? 1.0 : 0.0) : st->T[tid]) : 0.0;   // (for the tail of the solve: on its way while the sums are added up)
+    const double T_lane = tid < 12 ? (first ? identity12(tid) : st->T[tid]) : 0.0;   // (for the tail of the solve: on its way while the sums are added up)
     Lss acc;
-    lss_zero(acc);
-    for (int b = tid; b < nblocks; b += 256) {
-        const float* s = sums + (size_t)b * LSS_WORDS;
-#pragma unroll
-        for (int k = 0; k < 28; ++k) acc.f[k] += s[k];
-        acc.obs += __float_as_uint(s[28]);
-    }
+    lss_block_sum<false>(acc, sums, nblocks, tid);
     lss_tree(acc, tid, 256, lds);
     if (tid == 0) {
         lss_store(sums, acc);
@@ -616,6 +635,14 @@ __device__ __forceinline__ bool grid_barrier(unsigned* bar, const unsigned n_gro
     return s_ok != 0;
 }
 
+// the next level after l that is evaluated, or -1
+__device__ __forceinline__ int next_active(const IcpPersistent& q, const int l)
+{
+    for (int m = l + 1; m < q.n_levels; ++m)
+        if (q.lv[m].iterations > 0 && q.lv[m].gx > 0 && q.lv[m].gy > 0) return m;
+    return -1;
+}
+
 __global__ __launch_bounds__(256) void k_icp_refine_persistent(const IcpPersistent q)
 {
     __shared__ float lds[LSS_WORDS * 128];
@@ -625,15 +652,11 @@ __global__ __launch_bounds__(256) void k_icp_refine_persistent(const IcpPersiste
     const int tid = threadIdx.x;
     const unsigned G = gridDim.x;
     unsigned gen = 0;   // (the host zeroes the barrier words before the launch)
-    int first = -1;
-    for (int l = 0; l < q.n_levels; ++l)
-        if (q.lv[l].iterations > 0 && q.lv[l].gx > 0 && q.lv[l].gy > 0) { first = l; break; }
+    const int first = next_active(q, -1);
     if (tid == 0) {
-        for (int i = 0; i < 12; ++i) s_st.T[i] = (i % 5 == 0) ? 1.0 : 0.0;
-        s_st.rmse = 0.0; s_st.obs = 0.0; s_st.good = 1.0;
         float k0[4] = {0.f, 0.f, 0.f, 0.f};
         if (first >= 0) for (int i = 0; i < 4; ++i) k0[i] = q.lv[first].K[i];
-        publish_pose(&s_st, k0);
+        refine_state_init(&s_st, k0);
     }
     __syncthreads();
     int parity = 0;
@@ -643,9 +666,7 @@ __global__ __launch_bounds__(256) void k_icp_refine_persistent(const IcpPersiste
         if (L.iterations <= 0 || L.gx <= 0 || L.gy <= 0) continue;
         const int n = L.bx * L.by, nblocks = L.gx * L.gy;
         const int tx = tid % L.bx, ty = tid / L.bx;
-        int nxt = -1;
-        for (int m = l + 1; m < q.n_levels; ++m)
-            if (q.lv[m].iterations > 0 && q.lv[m].gx > 0 && q.lv[m].gy > 0) { nxt = m; break; }
+        const int nxt = next_active(q, l);
         const bool dbg_on = q.dbg && q.dbg_w >= L.Pl.w && q.dbg_h >= L.Pl.h;
         for (int it = 0; it < L.iterations && alive; ++it, parity ^= 1) {
             float* sums = q.sums[parity];
@@ -671,13 +692,7 @@ __global__ __launch_bounds__(256) void k_icp_refine_persistent(const IcpPersiste
             if (!alive) break;
             // ---- C: the sum over the blocks in k_lss_final's order, and the step ----
             Lss acc;
-            lss_zero(acc);
-            for (int b = tid; b < nblocks; b += 256) {
-                const float* sp = sums + (size_t)b * LSS_WORDS;
-#pragma unroll
-                for (int k = 0; k < 28; ++k) acc.f[k] += __hip_atomic_load(sp + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (written by other workgroups during this launch)
-                acc.obs += __float_as_uint(__hip_atomic_load(sp + 28, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-            }
+            lss_block_sum<true>(acc, sums, nblocks, tid);
             lss_tree(acc, tid, 256, lds);
             if (tid == 0) {
                 lss_store(s_sum, acc);
@@ -689,18 +704,139 @@ __global__ __launch_bounds__(256) void k_icp_refine_persistent(const IcpPersiste
         }
     }
     if (blockIdx.x == 0 && tid == 0) {
-        if (!alive) s_st.good = -1.0;   // the grid never met: reported by the host
+        if (!alive) s_st.v.good = -1.0;   // the grid never met: reported by the host
         *q.st = s_st;
     }
 }
 
 static unsigned gcd_u(unsigned a, unsigned b) { return b == 0 ? a : gcd_u(b, a % b); }
 
-// KFX_ICP_MAILBOX=0: no mapped mailbox, the results are copied to the host (kfx_icp_point_plane, kfx_icp_refine)
-static bool icp_mailbox_env()
+// How one level is launched: InitDimFromOutputImage(dPl, 16, 16) (launch_utils.h:61-65) -- blocks of gcd(w, 16) x gcd(h, 16) pixels,
+// w / bx x h / by of them (none for an empty image) -- and the LDS of lss_tree's levels that cross wavefronts.  n: pixels
+// (= threads) of a block; active: the level is evaluated at all (kfx_icp_point_plane: iterations = 1).
+struct IcpGeom { unsigned bx, by, gx, gy; int n; size_t blocks, lds_bytes; bool active; };
+static IcpGeom icp_geom(const kfx_image& Pl, int iterations)
 {
-    static const bool on = env_int("KFX_ICP_MAILBOX", 1) != 0;
-    return on;
+    IcpGeom g;
+    g.bx = gcd_u((unsigned)Pl.w, 16); g.by = gcd_u((unsigned)Pl.h, 16);
+    g.gx = (unsigned)(Pl.w / g.bx); g.gy = (unsigned)(Pl.h / g.by);
+    g.n = (int)(g.bx * g.by); g.blocks = (size_t)g.gx * g.gy;
+    g.lds_bytes = g.n >= 128 ? (size_t)LSS_WORDS * (g.n / 2) * sizeof(float) : 0;
+    g.active = iterations > 0 && Pl.w && Pl.h;
+    return g;
+}
+// the next level after l that is evaluated, or -1 (l = -1: the first)
+static int next_active(const kfx_icp_level* levels, int n_levels, int l)
+{
+    for (int m = l + 1; m < n_levels; ++m)
+        if (icp_geom(levels[m].Pl, levels[m].iterations).active) return m;
+    return -1;
+}
+
+// one evaluation's arguments but for the pose; debug: null where the level does not write one
+static IcpParams icp_params(const kfx_image& Pl, const kfx_image& Pr, const kfx_image& Nr, const kfx_image* debug, float c, float* sums)
+{
+    IcpParams p = {};
+    p.Pl = img_view(Pl); p.Pr = img_view(Pr); p.Nr = img_view(Nr);
+    p.dbg = debug ? (unsigned char*)debug->ptr : nullptr;
+    p.dbg_pitch = debug ? debug->pitch : 0;
+    p.c = c;
+    p.sums = sums;
+    return p;
+}
+
+// a spinning thread's hint to its core; nothing where the host has none
+#if defined(__x86_64__) || defined(__i386__)
+#define KFX_SPIN_HINT() __builtin_ia32_pause()
+#elif defined(__aarch64__) || defined(__arm__)
+#define KFX_SPIN_HINT() __asm__ __volatile__("yield")
+#else
+#define KFX_SPIN_HINT() ((void)0)
+#endif
+
+// A result's way to the host, one per calling thread, shared by kfx_icp_point_plane (the reference's thrust::reduce blocks too; the
+// application solves on the host between two of these calls, six times per frame, main.cpp:301-342) and kfx_icp_refine.
+//  * The mailbox: 128 bytes of page-locked, portable host memory mapped into the device's address space.  The call's last kernel
+//    writes the payload and then the call's sequence number there and this thread spins on that word -- no copy command, no stream
+//    synchronisation, no wait for an event (profiles/r06_tracked: the copy's own 4.3 us and the wake-up after hipStreamSynchronize
+//    were 8 % of the drop-in application's frame; 4 us of the stream per frame for kfx_icp_refine).
+//  * KFX_ICP_MAILBOX=0, no mapped memory, or a word that did not arrive: the round-5 path, a copy into a pinned staging buffer (a
+//    device -> pageable copy is staged by the runtime and costs a second synchronisation; without pinned memory it is that copy).
+// The hook of kfx_icp_refine_then (enqueue_more: work that does not depend on the result, the next frame's pre-amble) is called
+// exactly ONCE per successfully enqueued call: before the spin on the mailbox path -- the copy after a word that did not arrive
+// does not call it again -- else between the copy and the wait, which is on an event: for the copy only, not for the hook's work.
+struct ResultPort {
+    void *mail = nullptr, *mail_dev = nullptr;   // the mailbox's host address, and its device address on device mail_device
+    int mail_device = -1;
+    unsigned seq = 0;                            // of the last call through the mailbox; never 0, the word's initial value
+    void* stage = nullptr;
+    hipEvent_t copied = nullptr;
+    ~ResultPort()   // rank threads come and go: the pages go back (errors ignored and cleared: the runtime may already be gone)
+    {
+        if (mail) (void)hipHostFree(mail);
+        if (stage) (void)hipHostFree(stage);
+        if (copied) (void)hipEventDestroy(copied);
+        (void)hipGetLastError();
+    }
+    // the mailbox's address on the device that is current now (another one than at the last call: asked for again); null: take
+    // the copy path (KFX_ICP_MAILBOX=0, or no mapped memory)
+    void* mailbox()
+    {
+        static const bool on = env_int("KFX_ICP_MAILBOX", 1) != 0;
+        int dev = 0;
+        if (!on || hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        if (!mail) {
+            if (hipHostMalloc(&mail, MAILBOX_BYTES, hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable) != hipSuccess) { (void)hipGetLastError(); mail = nullptr; return nullptr; }
+            memset(mail, 0, MAILBOX_BYTES);
+        }
+        if (mail_device != dev) {
+            if (hipHostGetDevicePointer(&mail_dev, mail, 0) != hipSuccess) { (void)hipGetLastError(); mail_device = -1; return nullptr; }
+            mail_device = dev;
+        }
+        return mail_dev;
+    }
+    unsigned next_seq() { return ++seq ? seq : ++seq; }
+    // Has the word arrived?  Bounded: every 4096 looks the stream is asked whether it is still running -- a launch that failed on the
+    // device, or a word that never arrives, ends in the copy path instead of a hang.
+    bool wait_mailbox(unsigned want, hipStream_t stream) const
+    {
+        const unsigned* word = static_cast<const unsigned*>(mail) + MAILBOX_SEQ_WORD;
+        for (unsigned spins = 0;; ++spins) {
+            if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == want) return true;
+            KFX_SPIN_HINT();
+            if ((spins & 4095u) == 4095u && hipStreamQuery(stream) != hipErrorNotReady) {   // finished (or failed): one last look
+                (void)hipGetLastError();
+                return __atomic_load_n(word, __ATOMIC_ACQUIRE) == want;
+            }
+        }
+    }
+    // dst[0 .. bytes) <- device memory at src (bytes <= 128), blocking
+    int read_back(void* dst, const void* src, size_t bytes, hipStream_t stream, void (*enqueue_more)(void*), void* user)
+    {
+        if (!stage && hipHostMalloc(&stage, MAILBOX_BYTES, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); stage = nullptr; }
+        void* to = stage ? stage : dst;
+        hipError_t e = hipMemcpyAsync(to, src, bytes, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess && enqueue_more) {
+            if (!copied) e = hipEventCreateWithFlags(&copied, hipEventDisableTiming);
+            if (e == hipSuccess) e = hipEventRecord(copied, stream);
+            if (e == hipSuccess) { enqueue_more(user); e = hipEventSynchronize(copied); }
+        } else if (e == hipSuccess) {
+            e = hipStreamSynchronize(stream);
+        }
+        if (e != hipSuccess) return set_error((int)e, hipGetErrorString(e));
+        if (to != dst) memcpy(dst, to, bytes);
+        return 0;
+    }
+};
+static thread_local ResultPort result_port;
+
+// a RefineState's first 15 doubles {T, rmse, obs, good} into the caller's variables
+static void deliver(const double r[15], double T_lp[12], float* rmse, unsigned* obs, int* tracking_good)
+{
+    for (int i = 0; i < 12; ++i) T_lp[i] = r[i];
+    if (rmse) *rmse = (float)r[12];
+    if (obs) *obs = (unsigned)r[13];
+    if (tracking_good) *tracking_good = r[14] != 0.0 ? 1 : 0;
 }
 
 } // namespace kfx
@@ -717,9 +853,7 @@ static int check_icp_images(const kfx_image* Pl, const kfx_image* Pr, const kfx_
 }
 
 // LeastSquaresSystem<float,6> PoseRefinementProjectiveIcpPointPlane(dPl, dPr, dNr, KT_lr, T_rl, c, dWorkspace,
-// dDebug) (cu_model_refinement.cu:595-608).  Launch geometry as InitDimFromOutputImage(dPl, 16, 16)
-// (launch_utils.h:61-65): block = (gcd(w,16), gcd(h,16)), grid = (w / bx, h / by).  Blocks until the 116-byte
-// result is on the host (the reference's thrust::reduce blocks too).
+// dDebug) (cu_model_refinement.cu:595-608).  Blocks until the 116-byte result is on the host (ResultPort).
 extern "C" int kfx_icp_point_plane(const kfx_image* Pl, const kfx_image* Pr, const kfx_image* Nr, const float KT_lr[12],
                                    const float T_rl[12], float c, const kfx_image* workspace, const kfx_image* debug,
                                    kfx_lss6* out, kfx_stream stream)
@@ -729,86 +863,27 @@ extern "C" int kfx_icp_point_plane(const kfx_image* Pl, const kfx_image* Pr, con
         return set_error(KFX_E_NULL, "PoseRefinementProjectiveIcpPointPlane: null argument");
     memset(out, 0, sizeof(*out));
     if (Pl->w == 0 || Pl->h == 0) return 0;
-    if (int e = check_icp_images(Pl, Pr, Nr, (debug && debug->ptr) ? debug : nullptr, Pl->w, Pl->h, "PoseRefinementProjectiveIcpPointPlane")) return e;
+    if (debug && !debug->ptr) debug = nullptr;
+    if (int e = check_icp_images(Pl, Pr, Nr, debug, Pl->w, Pl->h, "PoseRefinementProjectiveIcpPointPlane")) return e;
     if ((uintptr_t)workspace->ptr & 3) return set_error(KFX_E_ALIGN, "PoseRefinementProjectiveIcpPointPlane: workspace alignment");
-    const unsigned bx = gcd_u((unsigned)Pl->w, 16), by = gcd_u((unsigned)Pl->h, 16);
-    const dim3 block(bx, by), grid((unsigned)(Pl->w / bx), (unsigned)(Pl->h / by));
-    const size_t nblocks = (size_t)grid.x * grid.y;
+    const IcpGeom g = icp_geom(*Pl, 1);
     // Image::PackedImage asserts the workspace holds gridDim.x * gridDim.y systems (Image.h:464-468)
-    if (nblocks * sizeof(kfx_lss6) > workspace->pitch * workspace->h)
+    if (g.blocks * sizeof(kfx_lss6) > workspace->pitch * workspace->h)
         return set_error(KFX_E_SHAPE, "PoseRefinementProjectiveIcpPointPlane: workspace too small");
-    if (nblocks > 0x7fffffff) return set_error(KFX_E_RANGE, "PoseRefinementProjectiveIcpPointPlane: image too large");
-    IcpParams p;
-    p.Pl = ImgView{(const unsigned char*)Pl->ptr, Pl->pitch, (int)Pl->w, (int)Pl->h};
-    p.Pr = ImgView{(const unsigned char*)Pr->ptr, Pr->pitch, (int)Pr->w, (int)Pr->h};
-    p.Nr = ImgView{(const unsigned char*)Nr->ptr, Nr->pitch, (int)Nr->w, (int)Nr->h};
-    p.dbg = (debug && debug->ptr) ? (unsigned char*)debug->ptr : nullptr;
-    p.dbg_pitch = p.dbg ? debug->pitch : 0;
+    if (g.blocks > 0x7fffffff) return set_error(KFX_E_RANGE, "PoseRefinementProjectiveIcpPointPlane: image too large");
+    const hipStream_t s = (hipStream_t)stream;
+    IcpParams p = icp_params(*Pl, *Pr, *Nr, debug, c, (float*)workspace->ptr);
     for (int i = 0; i < 12; ++i) { p.KT_lr.m[i] = KT_lr[i]; p.T_rl.m[i] = T_rl[i]; }
-    p.c = c;
-    p.dev_pose = nullptr;
-    p.sums = (float*)workspace->ptr;
-    const int n = (int)(bx * by);
-    const size_t lds_bytes = n >= 128 ? (size_t)LSS_WORDS * (n / 2) * sizeof(float) : 0;
-    // The result's way to the host (the reference's thrust::reduce blocks too; the application solves on the host between two of
-    // these calls, six times per frame, main.cpp:301-342).  A mailbox per calling thread: 128 bytes of page-locked host memory
-    // mapped into the device's address space; k_lss_final writes the 29 words and then a sequence word there (system-scope release)
-    // and this thread spins on the word -- no copy command, no stream synchronisation (profiles/r06_tracked: the copy's own
-    // 4.3 us and the wake-up after hipStreamSynchronize were 8 % of the drop-in application's frame).  KFX_ICP_MAILBOX=0, or no
-    // mapped memory: the round-5 path (a copy into a pinned staging word + hipStreamSynchronize).
-    struct Mailbox { float* host; float* dev; unsigned seq; };
-    thread_local Mailbox mb = {nullptr, nullptr, 0u};
-    const bool mailbox_env = icp_mailbox_env();
-    if (mailbox_env && !mb.host) {
-        void* h = nullptr;
-        void* d = nullptr;
-        if (hipHostMalloc(&h, 128, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess && hipHostGetDevicePointer(&d, h, 0) == hipSuccess) {
-            memset(h, 0, 128);
-            mb.host = (float*)h; mb.dev = (float*)d;
-        } else {
-            (void)hipGetLastError();
-            if (h) (void)hipHostFree(h);
-            mb.host = nullptr;
-        }
+    void* mail = result_port.mailbox();
+    const unsigned seq = mail ? result_port.next_seq() : 0u;
+    hipLaunchKernelGGL(k_icp_point_plane, dim3(g.gx, g.gy), dim3(g.bx, g.by), g.lds_bytes, s, p);
+    hipLaunchKernelGGL(k_lss_final, dim3(1), dim3(256), 0, s, p.sums, (int)g.blocks, (float*)mail, seq);
+    if (int e = check_launch("kfx_icp_point_plane")) return e;
+    if (mail && result_port.wait_mailbox(seq, s)) {
+        memcpy(out, result_port.mail, sizeof(*out));
+        return 0;
     }
-    const bool use_mailbox = mailbox_env && mb.host != nullptr;
-    const unsigned seq = use_mailbox ? (++mb.seq ? mb.seq : ++mb.seq) : 0u;   // (never 0: the word's initial value)
-    hipLaunchKernelGGL(k_icp_point_plane, grid, block, lds_bytes, (hipStream_t)stream, p);
-    hipLaunchKernelGGL(k_lss_final, dim3(1), dim3(256), 0, (hipStream_t)stream, p.sums, (int)nblocks, use_mailbox ? mb.dev : nullptr, seq);
-    int st = check_launch("kfx_icp_point_plane");
-    if (st) return st;
-    if (use_mailbox) {
-        volatile unsigned* word = reinterpret_cast<volatile unsigned*>(mb.host) + 31;
-        // bounded: every 4096 looks the stream is asked whether it is still running -- a launch that failed on the device, or a
-        // word that never arrives, ends in the synchronising path below instead of a hang
-        bool arrived = false;
-        for (unsigned spins = 0; !arrived; ++spins) {
-            if (__atomic_load_n(const_cast<unsigned*>(word), __ATOMIC_ACQUIRE) == seq) { arrived = true; break; }
-            __builtin_ia32_pause();
-            if ((spins & 4095u) == 4095u) {
-                const hipError_t q = hipStreamQuery((hipStream_t)stream);
-                if (q != hipErrorNotReady) {   // finished (or failed): one last look, then the copy path decides
-                    (void)hipGetLastError();
-                    arrived = __atomic_load_n(const_cast<unsigned*>(word), __ATOMIC_ACQUIRE) == seq;
-                    break;
-                }
-            }
-        }
-        if (arrived) {
-            memcpy(out, mb.host, sizeof(*out));
-            return 0;
-        }
-    }
-    // read-back through a pinned staging word per calling thread: a device -> pageable copy is staged by the runtime
-    // and costs a second synchronisation
-    thread_local kfx_lss6* stage = nullptr;
-    if (!stage && hipHostMalloc((void**)&stage, sizeof(kfx_lss6), hipHostMallocDefault) != hipSuccess) stage = nullptr;
-    kfx_lss6* dst = stage ? stage : out;
-    hipError_t e = hipMemcpyAsync(dst, p.sums, sizeof(*out), hipMemcpyDeviceToHost, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    if (e != hipSuccess) return set_error((int)e, hipGetErrorString(e));
-    if (dst != out) memcpy(out, dst, sizeof(*out));
-    return 0;
+    return result_port.read_back(out, p.sums, sizeof(*out), s, nullptr, nullptr);
 }
 
 // The coarse-to-fine loop of main.cpp:301-337 enqueued as one chain of kernels: for every level (coarsest first) and
@@ -822,15 +897,16 @@ static int icp_refine_impl(const kfx_icp_level* levels, int n_levels, float c, f
                            void* user, kfx_stream stream)
 {
     if (!levels || n_levels <= 0 || !workspace || !workspace->ptr || !T_lp) return set_error(KFX_E_NULL, "kfx_icp_refine: null argument");
+    if (debug && !debug->ptr) debug = nullptr;
     size_t max_blocks = 0;
+    int evaluations = 0;
     for (int l = 0; l < n_levels; ++l) {
         const kfx_icp_level& L = levels[l];
         // (a debug image smaller than a level is not written at that level)
-        if (int e = check_icp_images(&L.Pl, &L.Pr, &L.Nr, (debug && debug->ptr) ? debug : nullptr, 0, 0, "kfx_icp_refine")) return e;
-        if (L.Pl.w == 0 || L.Pl.h == 0) continue;
-        const unsigned bx = gcd_u((unsigned)L.Pl.w, 16), by = gcd_u((unsigned)L.Pl.h, 16);
-        const size_t nb = (L.Pl.w / bx) * (L.Pl.h / by);
-        if (nb > max_blocks) max_blocks = nb;
+        if (int e = check_icp_images(&L.Pl, &L.Pr, &L.Nr, debug, 0, 0, "kfx_icp_refine")) return e;
+        const IcpGeom g = icp_geom(L.Pl, L.iterations);
+        if (g.blocks > max_blocks) max_blocks = g.blocks;
+        if (g.active) evaluations += L.iterations;
     }
     const size_t state_off = (max_blocks * sizeof(kfx_lss6) + 255) / 256 * 256;
     if (state_off + sizeof(RefineState) > workspace->pitch * workspace->h || ((uintptr_t)workspace->ptr & 7))
@@ -839,19 +915,22 @@ static int icp_refine_impl(const kfx_icp_level* levels, int n_levels, float c, f
     float* sums = (float*)workspace->ptr;
     RefineState* st = (RefineState*)((unsigned char*)workspace->ptr + state_off);
     // KFX_ICP_PERSISTENT=1: one persistent launch (k_icp_refine_persistent) where the workspace has room for the second set of block
-    // systems and the barrier words, the levels fit its table and the device can hold the grid.  Same bits as the chain of launches
+    // systems and the barrier words, the levels fit its table (a block's gcd(w, 16) x gcd(h, 16) pixels always fit its 256 threads)
+    // and the device can hold the grid.  Same bits as the chain of launches
     // below, which stays the default: measured on MI355X (512^3 tracked frame, C++ loop) the chain takes 0.655 ms per frame, the
     // persistent launch 0.754 (128 workgroups) - 0.844 ms (512) -- a grid-wide barrier across the eight XCDs and a 6 x 6 float64
     // step in every workgroup cost more than the launch boundaries they replace (EXPERIMENTS.md 7.3).
     static const int persistent_env = env_int("KFX_ICP_PERSISTENT", 0);
     const size_t sums2_off = (state_off + sizeof(RefineState) + 255) / 256 * 256, bar_off = sums2_off + state_off;
-    bool fits = persistent_env != 0 && n_levels <= 4 && bar_off + 256 <= workspace->pitch * workspace->h;
-    for (int l = 0; l < n_levels && fits; ++l) {
-        const kfx_icp_level& L = levels[l];
-        if (L.iterations <= 0 || L.Pl.w == 0 || L.Pl.h == 0) continue;
-        if (gcd_u((unsigned)L.Pl.w, 16) * gcd_u((unsigned)L.Pl.h, 16) > 256u || L.Pl.w > 0x7fffffffull || L.Pl.h > 0x7fffffffull) fits = false;
-    }
-    if (fits) {
+    // the copy path's end (hook: null where it has been called already)
+    const auto copy_result = [&](void (*hook)(void*)) {
+        double r[15];
+        if (int e = result_port.read_back(r, st, sizeof(r), s, hook, user)) return e;
+        if (r[14] < 0.0) return set_error(KFX_E_RANGE, "kfx_icp_refine: the persistent grid never met at its barrier (not resident)");
+        deliver(r, T_lp, rmse, obs, tracking_good);
+        return 0;
+    };
+    if (persistent_env != 0 && n_levels <= 4 && bar_off + 256 <= workspace->pitch * workspace->h) {
         static int capacity = -1;   // workgroups of this kernel the device holds at once
         if (capacity < 0) {
             int dev = 0, cus = 0, per_cu = 0;
@@ -868,24 +947,22 @@ static int icp_refine_impl(const kfx_icp_level* levels, int n_levels, float c, f
             size_t most = 1;
             for (int l = 0; l < n_levels; ++l) {
                 const kfx_icp_level& L = levels[l];
+                const IcpGeom g = icp_geom(L.Pl, L.iterations);
                 IcpLevelDev& d = q.lv[l];
-                d.iterations = (L.Pl.w && L.Pl.h) ? L.iterations : 0;
+                d.iterations = g.active ? L.iterations : 0;
                 d.rotation_only = L.rotation_only ? 1 : 0;
                 for (int i = 0; i < 4; ++i) d.K[i] = L.K[i];
-                if (d.iterations <= 0) continue;
-                d.Pl = ImgView{(const unsigned char*)L.Pl.ptr, L.Pl.pitch, (int)L.Pl.w, (int)L.Pl.h};
-                d.Pr = ImgView{(const unsigned char*)L.Pr.ptr, L.Pr.pitch, (int)L.Pr.w, (int)L.Pr.h};
-                d.Nr = ImgView{(const unsigned char*)L.Nr.ptr, L.Nr.pitch, (int)L.Nr.w, (int)L.Nr.h};
-                d.bx = (int)gcd_u((unsigned)L.Pl.w, 16); d.by = (int)gcd_u((unsigned)L.Pl.h, 16);
-                d.gx = (int)(L.Pl.w / d.bx); d.gy = (int)(L.Pl.h / d.by);
-                if ((size_t)d.gx * d.gy > most) most = (size_t)d.gx * d.gy;
+                if (!g.active) continue;
+                d.Pl = img_view(L.Pl); d.Pr = img_view(L.Pr); d.Nr = img_view(L.Nr);
+                d.bx = (int)g.bx; d.by = (int)g.by;
+                d.gx = (int)g.gx; d.gy = (int)g.gy;
+                if (g.blocks > most) most = g.blocks;
             }
             q.n_levels = n_levels;
             q.c = c; q.max_rmse = max_rmse;
-            const bool dbg = debug && debug->ptr;
-            q.dbg = dbg ? (unsigned char*)debug->ptr : nullptr;
-            q.dbg_pitch = dbg ? debug->pitch : 0;
-            q.dbg_w = dbg ? (int)debug->w : 0; q.dbg_h = dbg ? (int)debug->h : 0;
+            q.dbg = debug ? (unsigned char*)debug->ptr : nullptr;
+            q.dbg_pitch = debug ? debug->pitch : 0;
+            q.dbg_w = debug ? (int)debug->w : 0; q.dbg_h = debug ? (int)debug->h : 0;
             q.sums[0] = sums;
             q.sums[1] = (float*)((unsigned char*)workspace->ptr + sums2_off);
             q.st = st;
@@ -897,153 +974,54 @@ static int icp_refine_impl(const kfx_icp_level* levels, int n_levels, float c, f
             hipError_t he = hipMemsetAsync(q.bar, 0, 64, s);
             if (he != hipSuccess) { (void)hipGetLastError(); return set_error((int)he, "kfx_icp_refine: hipMemsetAsync"); }
             hipLaunchKernelGGL(k_icp_refine_persistent, dim3(grid), dim3(256), 0, s, q);
-            if (int e0 = check_launch("kfx_icp_refine")) return e0;
-            thread_local double* stage_p = nullptr;
-            if (!stage_p && hipHostMalloc((void**)&stage_p, 15 * sizeof(double), hipHostMallocDefault) != hipSuccess) return set_error(KFX_E_RANGE, "kfx_icp_refine: pinned staging");
-            hipError_t e = hipMemcpyAsync(stage_p, st, 15 * sizeof(double), hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess && enqueue_more) enqueue_more(user);   // (the hook's contract: called once per successful enqueue)
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e != hipSuccess) return set_error((int)e, hipGetErrorString(e));
-            if (stage_p[14] < 0.0) return set_error(KFX_E_RANGE, "kfx_icp_refine: the persistent grid never met at its barrier (not resident)");
-            for (int i = 0; i < 12; ++i) T_lp[i] = stage_p[i];
-            if (rmse) *rmse = (float)stage_p[12];
-            if (obs) *obs = (unsigned)stage_p[13];
-            if (tracking_good) *tracking_good = stage_p[14] != 0.0 ? 1 : 0;
-            return 0;
+            if (int e = check_launch("kfx_icp_refine")) return e;
+            return copy_result(enqueue_more);
         }
     }
-    // flatten the schedule so that every solve knows the intrinsics of the evaluation that follows it
-    int first = -1;
-    for (int l = 0; l < n_levels; ++l)
-        if (levels[l].iterations > 0 && levels[l].Pl.w && levels[l].Pl.h) { first = l; break; }
+    // every solve knows the intrinsics of the evaluation that follows it
+    const int first = next_active(levels, n_levels, -1);
     K4 k0;
     for (int i = 0; i < 4; ++i) k0.k[i] = first >= 0 ? levels[first].K[i] : 0.f;
     // The pose starts at the identity: the first evaluation takes K * I and I^-1 as launch arguments (the floats pose_floats gives:
     // what the initialising launch used to leave in device memory) and its solve starts from the identity itself -- one launch
     // less per call.  Only a call without any evaluation initialises the state by a launch (it returns the identity).
     float pose0[24];
-    {
-        const double I12[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-        pose_floats(pose0, k0.k, I12);
-    }
+    const double I12[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    pose_floats(pose0, k0.k, I12);
     if (first < 0) hipLaunchKernelGGL(k_icp_refine_init, dim3(1), dim3(1), 0, s, st, k0);
-    // The result's way to the host: the LAST solve writes {T, rmse, obs, good} and a sequence word into a mailbox of page-locked host
-    // memory mapped into the device's address space (one per calling thread) and this thread spins on the word -- no copy command
-    // (4 us of the stream per frame), no wait for an event (as kfx_icp_point_plane's mailbox; KFX_ICP_MAILBOX=0: the copy below)
-    struct Mailbox { double* host; double* dev; unsigned seq; };
-    thread_local Mailbox mb = {nullptr, nullptr, 0u};
-    const bool mailbox_env = icp_mailbox_env();
-    if (mailbox_env && !mb.host) {
-        void* h = nullptr;
-        void* d = nullptr;
-        if (hipHostMalloc(&h, 128, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess && hipHostGetDevicePointer(&d, h, 0) == hipSuccess) {
-            memset(h, 0, 128);
-            mb.host = (double*)h; mb.dev = (double*)d;
-        } else {
-            (void)hipGetLastError();
-            if (h) (void)hipHostFree(h);
-            mb.host = nullptr;
-        }
-    }
-    int evaluations = 0;
-    for (int l = 0; l < n_levels; ++l)
-        if (levels[l].iterations > 0 && levels[l].Pl.w && levels[l].Pl.h) evaluations += levels[l].iterations;
-    const bool use_mailbox = mailbox_env && mb.host != nullptr && evaluations > 0;
-    const unsigned seq = use_mailbox ? (++mb.seq ? mb.seq : ++mb.seq) : 0u;   // (never 0: the word's initial value)
+    // the LAST solve leaves {T, rmse, obs, good} in the mailbox as well (a call without any evaluation has no solve: the copy path)
+    void* mail = evaluations > 0 ? result_port.mailbox() : nullptr;
+    const unsigned seq = mail ? result_port.next_seq() : 0u;
     int evaluation = 0;
-    bool first_eval = true;
     for (int l = 0; l < n_levels; ++l) {
         const kfx_icp_level& L = levels[l];
-        if (L.iterations <= 0 || L.Pl.w == 0 || L.Pl.h == 0) continue;
-        const unsigned bx = gcd_u((unsigned)L.Pl.w, 16), by = gcd_u((unsigned)L.Pl.h, 16);
-        const dim3 block(bx, by), grid((unsigned)(L.Pl.w / bx), (unsigned)(L.Pl.h / by));
-        const int nblocks = (int)(grid.x * grid.y), n = (int)(bx * by);
-        const size_t lds_bytes = n >= 128 ? (size_t)LSS_WORDS * (n / 2) * sizeof(float) : 0;
-        IcpParams p;
-        p.Pl = ImgView{(const unsigned char*)L.Pl.ptr, L.Pl.pitch, (int)L.Pl.w, (int)L.Pl.h};
-        p.Pr = ImgView{(const unsigned char*)L.Pr.ptr, L.Pr.pitch, (int)L.Pr.w, (int)L.Pr.h};
-        p.Nr = ImgView{(const unsigned char*)L.Nr.ptr, L.Nr.pitch, (int)L.Nr.w, (int)L.Nr.h};
-        const bool dbg = debug && debug->ptr && debug->w >= L.Pl.w && debug->h >= L.Pl.h;
-        p.dbg = dbg ? (unsigned char*)debug->ptr : nullptr;
-        p.dbg_pitch = dbg ? debug->pitch : 0;
-        p.c = c;
-        p.dev_pose = st->pose;
-        p.sums = sums;
+        const IcpGeom g = icp_geom(L.Pl, L.iterations);
+        if (!g.active) continue;
+        const bool dbg = debug && debug->w >= L.Pl.w && debug->h >= L.Pl.h;
+        IcpParams p = icp_params(L.Pl, L.Pr, L.Nr, dbg ? debug : nullptr, c, sums);
         // next evaluation's intrinsics: this level while iterations remain, else the next level that has any
-        int nxt = -1;
-        for (int m = l + 1; m < n_levels; ++m)
-            if (levels[m].iterations > 0 && levels[m].Pl.w && levels[m].Pl.h) { nxt = m; break; }
+        const int nxt = next_active(levels, n_levels, l);
         for (int it = 0; it < L.iterations; ++it) {
             K4 kn;
             const float* Kn = (it + 1 < L.iterations || nxt < 0) ? L.K : levels[nxt].K;
             for (int i = 0; i < 4; ++i) kn.k[i] = Kn[i];
-            if (first_eval) {
-                IcpParams p0 = p;
-                p0.dev_pose = nullptr;
-                for (int i = 0; i < 12; ++i) { p0.KT_lr.m[i] = pose0[i]; p0.T_rl.m[i] = pose0[12 + i]; }
-                hipLaunchKernelGGL(k_icp_point_plane, grid, block, lds_bytes, s, p0);
-            } else {
-                hipLaunchKernelGGL(k_icp_point_plane, grid, block, lds_bytes, s, p);
-            }
-            const bool last = ++evaluation == evaluations;
-            hipLaunchKernelGGL(k_lss_final_solve, dim3(1), dim3(256), 0, s, sums, nblocks, st, L.rotation_only ? 1 : 0, max_rmse, kn, first_eval ? 1 : 0,
-                               (use_mailbox && last) ? mb.dev : nullptr, seq);
-            first_eval = false;
+            const bool first_eval = evaluation == 0, last = ++evaluation == evaluations;
+            if (first_eval) for (int i = 0; i < 12; ++i) { p.KT_lr.m[i] = pose0[i]; p.T_rl.m[i] = pose0[12 + i]; }
+            p.dev_pose = first_eval ? nullptr : st->pose;
+            hipLaunchKernelGGL(k_icp_point_plane, dim3(g.gx, g.gy), dim3(g.bx, g.by), g.lds_bytes, s, p);
+            hipLaunchKernelGGL(k_lss_final_solve, dim3(1), dim3(256), 0, s, sums, (int)g.blocks, st, L.rotation_only ? 1 : 0, max_rmse, kn, first_eval ? 1 : 0,
+                               last ? (double*)mail : nullptr, seq);
         }
     }
-    int e0 = check_launch("kfx_icp_refine");
-    if (e0) return e0;
-    const auto deliver = [&](const double* r) {
-        for (int i = 0; i < 12; ++i) T_lp[i] = r[i];
-        if (rmse) *rmse = (float)r[12];
-        if (obs) *obs = (unsigned)r[13];
-        if (tracking_good) *tracking_good = r[14] != 0.0 ? 1 : 0;
-    };
-    if (use_mailbox) {
-        // the caller's work that does not depend on the pose (the next frame's pre-amble) goes behind the chain first and runs while
-        // this thread looks at the word
+    if (int e = check_launch("kfx_icp_refine")) return e;
+    if (mail) {
         if (enqueue_more) enqueue_more(user);
-        volatile unsigned* word = reinterpret_cast<volatile unsigned*>(mb.host + 15);
-        // bounded: every 4096 looks the stream is asked whether it is still running -- a launch that failed on the device, or a word
-        // that never arrives, ends in the synchronising path below instead of a hang
-        bool arrived = false;
-        for (unsigned spins = 0; !arrived; ++spins) {
-            if (__atomic_load_n(const_cast<unsigned*>(word), __ATOMIC_ACQUIRE) == seq) { arrived = true; break; }
-            __builtin_ia32_pause();
-            if ((spins & 4095u) == 4095u) {
-                const hipError_t q = hipStreamQuery(s);
-                if (q != hipErrorNotReady) {
-                    (void)hipGetLastError();
-                    arrived = __atomic_load_n(const_cast<unsigned*>(word), __ATOMIC_ACQUIRE) == seq;
-                    break;
-                }
-            }
-        }
-        if (arrived) {
-            deliver(mb.host);
+        if (result_port.wait_mailbox(seq, s)) {
+            deliver((const double*)result_port.mail, T_lp, rmse, obs, tracking_good);
             return 0;
         }
-        enqueue_more = nullptr;   // (already called)
     }
-    thread_local double* stage = nullptr;
-    if (!stage && hipHostMalloc((void**)&stage, 15 * sizeof(double), hipHostMallocDefault) != hipSuccess) return set_error(KFX_E_RANGE, "kfx_icp_refine: pinned staging");
-    hipError_t e = hipMemcpyAsync(stage, st, 15 * sizeof(double), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && enqueue_more) {
-        // the caller has work that does not depend on the pose (the next frame's pre-amble): enqueued behind the read-back, it
-        // runs while this thread wakes up from the wait -- which is for the read-back only, not for the stream
-        thread_local hipEvent_t arrived = nullptr;
-        if (!arrived) e = hipEventCreateWithFlags(&arrived, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventRecord(arrived, s);
-        if (e == hipSuccess) {
-            enqueue_more(user);
-            e = hipEventSynchronize(arrived);
-        }
-    } else if (e == hipSuccess) {
-        e = hipStreamSynchronize(s);
-    }
-    if (e != hipSuccess) return set_error((int)e, hipGetErrorString(e));
-    deliver(stage);
-    return 0;
+    return copy_result(mail ? nullptr : enqueue_more);
 }
 
 extern "C" int kfx_icp_refine(const kfx_icp_level* levels, int n_levels, float c, float max_rmse, const kfx_image* workspace,

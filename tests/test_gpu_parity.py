@@ -1472,6 +1472,113 @@ print("RESULT " + json.dumps(out))
             assert res[other][k] == res[other][k + 1] == res[other][k + 2]
 
 
+def test_gpu_icp_results_through_the_mailbox_equal_the_copy_path(tmp_path):
+    """The ICP results' two ways to the host -- the mapped mailbox the last kernel writes (KFX_ICP_MAILBOX=1, the default) and the
+    copy through the pinned staging buffer (=0, also where every mailbox failure ends) -- bit for bit, in two fresh processes:
+    kfx_icp_point_plane at one block of 256 threads (both LDS levels of the tree), 4 blocks, 289 blocks of 4 x 4 pixels (the
+    strided loop of the fixed-order block sum wraps) and 867 one-thread blocks (the tree's empty case), each called twice (the
+    sequence word advances); kfx_icp_refine for three schedules, one of them without any evaluation (the identity), each twice
+    and once with a hook, which runs exactly once per call; the two entry points interleaved on one thread (one mailbox, one
+    counter).  The 289- and 867-block systems, their per-block systems and debug images are the oracle's."""
+    import sys
+    import test_tracking_cpu as TT
+    from kangaroo_amd import tracking
+    shapes = ((16, 16, False), (32, 32, True), (68, 68, True), (51, 17, True))
+    schedules = ((1, 0, 2, 3), (2, 0, 0, 0), (0, 0, 0, 0))
+    code = r"""
+import sys
+import numpy as np
+sys.path.insert(0, %r); sys.path.insert(0, %r)
+from kangaroo_amd import roo, scenes, tracking
+import kfx_testlib as T
+import test_tracking_cpu as TT
+shapes, schedules, dst = %r, %r, %r
+out = {}
+T_lp = tracking.se3_exp([0.004, -0.003, 0.002, 0.003, -0.002, 0.001])
+def point_plane(tag, w, h, holes):
+    K, Pl, Pr, Nr, _, _ = TT.icp_inputs("room", w, h, holes)
+    KT = (tracking.k_matrix(K) @ T_lp[:3]).astype(np.float32)
+    T_pl = tracking.se3_inv(T_lp)[:3].astype(np.float32)
+    gPl, gPr, gNr = T.upload_image(roo, Pl.data), T.upload_image(roo, Pr.data), T.upload_image(roo, Nr.data)
+    nblocks = (w // np.gcd(w, 16)) * (h // np.gcd(h, 16))
+    ws, dbg = roo.Image(116 * nblocks, 1, "u8"), roo.Image(w, h, "f32x4")
+    for rep in range(2):
+        got = roo.PoseRefinementProjectiveIcpPointPlane(gPl, gPr, gNr, KT, T_pl, 0.1, ws, dbg)
+        k = "pp_%%s_%%d_" %% (tag, rep)
+        out[k + "JTy"], out[k + "JTJ"], out[k + "sqErr"], out[k + "obs"] = got.JTy, got.raw, np.float32(got.sqErr), np.uint32(got.obs)
+        out[k + "ws"], out[k + "dbg"] = ws.MemcpyToHost().copy(), dbg.MemcpyToHost().copy()
+for i in (0, 1):
+    point_plane(str(i), *shapes[i])
+w, h = 160, 120
+K = scenes.intrinsics(w, h)
+_, ray_v, ray_n, Ks = TT.pyramid_maps("room", w, h, scenes.orbit_pose(0, 60), K)
+_, kin_v, _, _ = TT.pyramid_maps("room", w, h, scenes.orbit_pose(1, 60), K)
+up = lambda imgs: [T.upload_image(roo, im.data) for im in imgs]
+g_kin, g_rv, g_rn = up(kin_v), up(ray_v), up(ray_n)
+ws, dbg = roo.Image(w * 232, h, "u8"), roo.Image(w, h, "f32x4")
+for si, its in enumerate(schedules):
+    for rep in range(3):
+        ran = []
+        Tm, rmse, obs, good = roo.IcpRefine(g_kin, g_rv, g_rn, Ks, its, 0.1, 0.10, ws, dbg, before_wait=(lambda: ran.append(1)) if rep == 2 else None)
+        k = "refine_%%d_%%d_" %% (si, rep)
+        out[k + "T"], out[k + "rmse"], out[k + "obs"], out[k + "good"] = np.asarray(Tm, np.float64), np.float32(rmse), np.uint32(obs), np.bool_(good)
+        out[k + "hook"] = np.int32(len(ran))
+for i in (2, 3):
+    point_plane(str(i), *shapes[i])
+point_plane("again", *shapes[0])
+np.savez(dst, **out)
+print("DONE")
+"""
+    res = {}
+    for mailbox in ("1", "0"):
+        dst = str(tmp_path / ("mailbox%s.npz" % mailbox))
+        o = subprocess.run([sys.executable, "-c", code % (T.ROOT, os.path.join(T.ROOT, "tests"), shapes, schedules, dst)],
+                           env=dict(os.environ, KFX_ICP_MAILBOX=mailbox), capture_output=True, text=True, timeout=300, cwd=T.ROOT)
+        assert o.returncode == 0 and "DONE" in o.stdout, o.stdout[-2000:] + o.stderr[-3000:]
+        with np.load(dst) as z:
+            res[mailbox] = {k: z[k] for k in z.files}
+    a, b = res["1"], res["0"]
+    assert sorted(a) == sorted(b) and len(a) == 5 * 2 * 6 + 3 * 3 * 5
+    for k in a:   # bit for bit
+        assert a[k].dtype == b[k].dtype and a[k].tobytes() == b[k].tobytes(), k
+    for r in (a, b):
+        for i, obs in enumerate((100, 575, 3340, 425)):
+            for rep in (0, 1):
+                assert int(r["pp_%d_%d_obs" % (i, rep)]) == obs
+        for f in ("JTy", "JTJ", "sqErr", "obs", "ws", "dbg"):   # repeated and interleaved calls give the same answer
+            for i in range(4):
+                assert r["pp_%d_0_%s" % (i, f)].tobytes() == r["pp_%d_1_%s" % (i, f)].tobytes()
+            assert r["pp_again_1_" + f].tobytes() == r["pp_0_0_" + f].tobytes()
+        for si, its in enumerate(schedules):
+            for rep in range(3):
+                k = "refine_%d_%d_" % (si, rep)
+                assert int(r[k + "hook"]) == (1 if rep == 2 else 0)
+                for f in ("T", "rmse", "obs", "good"):
+                    assert r[k + f].tobytes() == r["refine_%d_0_%s" % (si, f)].tobytes()
+                if sum(its) == 0:   # no evaluation: the initial state
+                    assert np.array_equal(r[k + "T"], np.eye(4)) and float(r[k + "rmse"]) == 0.0 and int(r[k + "obs"]) == 0 and bool(r[k + "good"])
+                else:
+                    assert int(r[k + "obs"]) > 0 and not np.array_equal(r[k + "T"], np.eye(4))
+    # test_gpu_icp_point_plane_vs_oracle's assertions at the two shapes it does not have
+    T_lp = tracking.se3_exp([0.004, -0.003, 0.002, 0.003, -0.002, 0.001])
+    for i, nblocks in ((2, 289), (3, 867)):
+        w, h, holes = shapes[i]
+        K, Pl, Pr, Nr, _, _ = TT.icp_inputs("room", w, h, holes)
+        KT = (tracking.k_matrix(K) @ T_lp[:3]).astype(np.float32)
+        T_pl = tracking.se3_inv(T_lp)[:3].astype(np.float32)
+        odbg = oracle.Image(w, h, channels=4)
+        want, blocks = oracle.icp_point_plane(Pl, Pr, Nr, KT, T_pl, 0.1, odbg, want_blocks=True)
+        assert len(blocks) == nblocks
+        k = "pp_%d_0_" % i
+        assert int(a[k + "obs"]) == int(want["obs"]) and int(a[k + "obs"]) > 0
+        assert a[k + "JTy"].tobytes() == want["JTy"].tobytes() and a[k + "JTJ"].tobytes() == want["JTJ"].tobytes()
+        assert a[k + "sqErr"].tobytes() == want["sqErr"].tobytes()
+        assert T.nan_equal(a[k + "dbg"], odbg.data)
+        left = np.frombuffer(a[k + "ws"].tobytes()[:116 * len(blocks)], oracle.LSS_DTYPE)
+        assert left[1:].tobytes() == blocks[1:].tobytes()       # slot 0 holds the final sum
+        assert left[0].tobytes() == want.tobytes()
+
+
 def test_gpu_texture_depth(roo):
     """TextureDepth, single-keyframe and blended forms, against the oracle (bit-identical)."""
     from test_oracle_cpu import texture_inputs
