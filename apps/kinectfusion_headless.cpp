@@ -101,6 +101,7 @@ int main(int argc, char** argv)
     int warm = 0;          // --warmup F: the first F frames run but do not count in the reported frame time (clocks, first launches)
     int drop_frame = -1;   // --drop-frame F: frame F arrives with no valid depth at all (a sensor drop-out): tracking is lost, the next frame recovers
     const char* save_mesh = nullptr;   // --save-mesh PREFIX: roo::SaveMesh of the model after the last frame (the application's 's' key) -> PREFIX.ply
+    bool mesh_indexed = false;         // --mesh-indexed: ... through roo::SaveMeshIndexed: welded vertices and a face list
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--res") && i + 1 < argc) volres = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--frames") && i + 1 < argc) frames = atoi(argv[++i]);
@@ -116,6 +117,7 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--drop-frame") && i + 1 < argc) drop_frame = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--warmup") && i + 1 < argc) warm = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--save-mesh") && i + 1 < argc) save_mesh = argv[++i];
+        else if (!strcmp(argv[i], "--mesh-indexed")) mesh_indexed = true;
     }
     if (warm < 0 || warm >= frames) warm = 0;
     if (kfx_device_count() < 1) { fprintf(stderr, "no HIP device\n"); return 2; }
@@ -425,7 +427,11 @@ int main(int argc, char** argv)
            use_summary ? " (brick summary)" : "", depth_sum, use_colour ? "colour" : "shade", image_sum);
     if (track) printf("  tracking: worst position error %.2f mm over the orbit (step between poses up to %.1f mm), final rmse %.4f, %d frames lost, %d resets\n",
                       1e3 * worst_pos_err, 1e3 * 0.0105, rmse, lost, resets);
-    if (save_mesh) {
+    if (save_mesh && mesh_indexed) {
+        size_t nvert = 0;
+        const size_t ntri = use_colour ? SaveMeshIndexed(save_mesh, vol, colorVol, &nvert) : SaveMeshIndexed(save_mesh, vol, &nvert);
+        printf("  mesh: %zu triangles, %zu vertices written to %s.ply\n", ntri, nvert, save_mesh);
+    } else if (save_mesh) {
         const size_t ntri = use_colour ? SaveMesh(save_mesh, vol, colorVol) : SaveMesh(save_mesh, vol);   // main.cpp:187
         printf("  mesh: %zu triangles written to %s.ply\n", ntri, save_mesh);
     }

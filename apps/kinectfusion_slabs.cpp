@@ -47,6 +47,7 @@ struct Options {
     SlabVolume::MergeMode merge = SlabVolume::MergeDirect;
     std::string rendezvous;   // default: /tmp/kfx_slabs.<uid>.<launch id>.id (default_rendezvous)
     std::string save_mesh;    // --save-mesh PREFIX: after the last frame every rank writes its part of the mesh as PREFIX.r<rank>.ply
+    bool mesh_indexed = false;   // --mesh-indexed: ... through SlabVolume::SaveMeshIndexed: welded vertices and a face list, per rank
     bool color = false;       // --color: colour volume, colour SdfFuse, colour renderings
 };
 
@@ -139,7 +140,7 @@ static unsigned BitSum(const void* p, size_t bytes)
 }
 
 struct Result { double ms_per_frame = 0; unsigned chk_d = 0, chk_n = 0, chk_i = 0, chk_vol = 0, chk_hist = 0, chk_col = 0; size_t hits = 0; int rounds = 0; int status = 0;
-                size_t mesh_tris = 0; };
+                size_t mesh_tris = 0, mesh_verts = 0; };
 
 // the frame loop of one rank
 static void RunRank(const Options& o, kfx_comm* comm, const std::vector<std::vector<float> >& depth_mm, const std::vector<std::vector<uchar3> >& rgb,
@@ -367,7 +368,8 @@ static void RunRank(const Options& o, kfx_comm* comm, const std::vector<std::vec
     res->chk_vol = (unsigned)hsum[0];
     res->chk_col = (unsigned)hsum[1];
     if (!o.save_mesh.empty())   // this rank's cubes; the ghost planes the normals read are current after the last fuse
-        res->mesh_tris = slab.SaveMesh(o.save_mesh + ".r" + std::to_string(comm->rank));
+        res->mesh_tris = o.mesh_indexed ? slab.SaveMeshIndexed(o.save_mesh + ".r" + std::to_string(comm->rank), &res->mesh_verts)
+                                        : slab.SaveMesh(o.save_mesh + ".r" + std::to_string(comm->rank));
 }
 
 int main(int argc, char** argv)
@@ -395,6 +397,7 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--ghost") && i + 1 < argc) { ++i; o.ghost = !strcmp(argv[i], "auto") ? -1 : atoi(argv[i]); }
         else if (!strcmp(argv[i], "--overlap")) o.overlap = true;
         else if (!strcmp(argv[i], "--save-mesh") && i + 1 < argc) o.save_mesh = argv[++i];
+        else if (!strcmp(argv[i], "--mesh-indexed")) o.mesh_indexed = true;
         else if (!strcmp(argv[i], "--color") || !strcmp(argv[i], "--colour")) o.color = true;
         else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
@@ -443,7 +446,7 @@ int main(int argc, char** argv)
         RunRank(o, &comms[0], depth_mm, rgb, poses, &results[0]);
         for (auto& t : threads) t.join();
         r0 = results[0];
-        for (int r = 1; r < world; ++r) r0.mesh_tris += results[r].mesh_tris;
+        for (int r = 1; r < world; ++r) { r0.mesh_tris += results[r].mesh_tris; r0.mesh_verts += results[r].mesh_verts; }
         for (int r = 1; r < world; ++r)   // after the merge every rank must hold the same images
             if (results[r].chk_d != r0.chk_d || results[r].chk_n != r0.chk_n || results[r].chk_i != r0.chk_i || results[r].chk_hist != r0.chk_hist) r0.status = 4;
         comms[0].destroy(&comms[0]);
@@ -457,7 +460,9 @@ int main(int argc, char** argv)
         if (o.color) snprintf(colour, sizeof(colour), " colour=%08x", r0.chk_col);
         printf("checksums depth=%08x norm=%08x img=%08x volume=%08x history=%08x hits=%zu ranks_agree=%d%s%s\n", r0.chk_d, r0.chk_n, r0.chk_i, r0.chk_vol, r0.chk_hist,
                r0.hits, r0.status == 0 ? 1 : 0, o.pipeline ? (" pipeline=" + std::to_string(o.pipeline)).c_str() : "", colour);
-        if (!o.save_mesh.empty())
+        if (!o.save_mesh.empty() && o.mesh_indexed)
+            printf("mesh: %zu triangles, %zu vertices written to %s.r<rank>.ply%s\n", r0.mesh_tris, r0.mesh_verts, o.save_mesh.c_str(), o.rccl ? " (rank 0's part)" : "");
+        else if (!o.save_mesh.empty())
             printf("mesh: %zu triangles written to %s.r<rank>.ply%s\n", r0.mesh_tris, o.save_mesh.c_str(), o.rccl ? " (rank 0's part)" : "");
     }
     if (r0.status) return r0.status;

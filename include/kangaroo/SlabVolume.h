@@ -188,6 +188,17 @@ public:
         return mesh_detail::WritePly(filename + ".ply", m);
     }
 
+    // SaveMesh's part of the mesh welded by lattice edge (include/kfx_mesh_index.h): the weld of this rank's triangles, so a vertex on a
+    // slab boundary exists once per rank that uses it.  nvert, if given, receives the vertex count; returns the triangle count.
+    size_t SaveMeshIndexed(std::string filename, size_t* nvert = nullptr)
+    {
+        const kfx_slab s = {layout.full_d, layout.s0, layout.full_zmin, layout.full_zmax};
+        const bool with_color = color && local.w >= 8 && local.h >= 8 && layout.full_d >= 8;
+        const mesh_detail::HostIndexedMesh m = mesh_detail::ExtractIndexed(local.abi(), KFX_CELL_F32, &s, (int)layout.z0, (int)layout.z1, with_color ? color->abi() : nullptr);
+        if (nvert) *nvert = m.nvert;
+        return mesh_detail::WritePly(filename + ".ply", m);
+    }
+
 private:
     static kfx_slab_layout MakeLayout(size_t d, const BoundingBox& bbox, kfx_comm* c, int ghost)
     {

@@ -28,7 +28,9 @@
  *            scan's block sums and offsets.  The library never allocates.  2048^3 cells, whole volume: 274 460 416 bytes (512^3: 4 277 504).
  *
  * Returns 0 or KFX_E_*: null pointers KFX_E_NULL, an unknown cell kind KFX_E_RANGE, too little scratch KFX_E_SHAPE, all before any
- * HIP call; a mesh of 2^32/3 triangles or more (32-bit vertex offsets) KFX_E_RANGE from kfx_mesh_plan, with the totals filled in. */
+ * HIP call; a mesh of 2^32/3 triangles or more (32-bit vertex offsets) KFX_E_RANGE from kfx_mesh_plan, with the totals filled in.
+ *
+ * Indexed output (one vertex per lattice edge and a face list, welded on the device from the same plan): kfx_mesh_index.h. */
 #ifndef KFX_MESH_H
 #define KFX_MESH_H
 

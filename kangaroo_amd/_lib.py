@@ -61,7 +61,7 @@ class KfxError(RuntimeError):
 
 PI, PV, PF = C.POINTER(KfxImage), C.POINTER(KfxVolume), C.POINTER(C.c_float)
 
-# name -> (restype, argtypes); every symbol include/kfx.h declares (and kfx_summary_h.h, kfx_mesh.h, kfx_color.h, kfx_slab_color.h, kfx_sensor.h)
+# name -> (restype, argtypes); every symbol include/kfx.h declares (and kfx_summary_h.h, kfx_mesh.h, kfx_mesh_index.h, kfx_color.h, kfx_slab_color.h, kfx_sensor.h)
 SIGNATURES = {
     "kfx_sdf_fuse": (C.c_int, [PV, PI, PI, PF, PF, C.c_float, C.c_float, C.c_float, C.c_uint, C.c_void_p]),
     "kfx_sdf_fuse_slab": (C.c_int, [PV, C.POINTER(KfxSlab), PI, PI, PF, PF, C.c_float, C.c_float, C.c_float, C.c_uint, C.c_void_p]),
@@ -127,6 +127,12 @@ SIGNATURES = {
     "kfx_mesh_plan": (C.c_int, [PV, C.c_int, C.POINTER(KfxSlab), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_ulonglong), C.c_void_p]),
     "kfx_mesh_emit": (C.c_int, [PV, C.c_int, C.POINTER(KfxSlab), C.c_int, C.c_int, PV, C.c_void_p, C.c_size_t, C.POINTER(C.c_ulonglong), C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # include/kfx_mesh_index.h
+    "kfx_mesh_index_scratch_bytes": (C.c_size_t, [PV, C.c_int, C.POINTER(KfxSlab), C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]),
+    "kfx_mesh_index_plan": (C.c_int, [PV, C.c_int, C.POINTER(KfxSlab), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_ulonglong),
+                                      C.c_void_p, C.c_size_t, C.POINTER(C.c_ulonglong), C.c_void_p]),
+    "kfx_mesh_emit_indexed": (C.c_int, [PV, C.c_int, C.POINTER(KfxSlab), C.c_int, C.c_int, PV, C.c_void_p, C.c_size_t, C.POINTER(C.c_ulonglong),
+                                        C.c_ulonglong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kfx_icp_refine": (C.c_int, [C.POINTER(KfxIcpLevel), C.c_int, C.c_float, C.c_float, PI, PI, C.POINTER(C.c_double), PF,
                                  C.POINTER(C.c_uint), C.POINTER(C.c_int), C.c_void_p]),
     "kfx_pose_step": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), PF]),

@@ -24,6 +24,7 @@
 #include "sampling.h"
 #include "host_args.h"
 #include "../../include/kfx_mesh.h"
+#include "../../include/kfx_mesh_index.h"
 
 namespace kfx {
 
@@ -106,6 +107,58 @@ __global__ __launch_bounds__(256) void k_mc_count(const MeshParams p, unsigned c
     }
 }
 
+// VoxelPositionInUnits(x,y,z) (BoundedVolume.h:115-125): the cube's corner 0
+__device__ __forceinline__ V3 cube_origin(const MeshParams& p, int x, int y, int z)
+{
+    return v3(p.vol.bmin.x + p.size.x * (float)x / p.dims1.x, p.vol.bmin.y + p.size.y * (float)y / p.dims1.y,
+              p.vol.bmin.z + p.size.z * (float)z / p.dims1.z);
+}
+
+// edges 0-3: bottom ring, 4-7: top ring, 8-11: verticals (MarchingCubes tables' numbering); the corners edge e joins
+__device__ __forceinline__ constexpr int edge_c0(int e) { return e < 8 ? e : e - 8; }
+__device__ __forceinline__ constexpr int edge_c1(int e) { return e < 4 ? (e + 1) & 3 : (e < 8 ? 4 + ((e + 1) & 3) : e - 4); }
+
+// the vertex of the cube at p0 (corner values v) on its edge e; VoxelSizeUnits() (BoundedVolume.h:67-76) in p.voxel
+__device__ __forceinline__ V3 edge_position(const MeshParams& p, const V3& p0, const float v[8], int e)
+{
+    const int c0 = edge_c0(e), c1 = edge_c1(e);
+    // fGetOffset (MarchingCubes.h:25-32): the difference is a float, the quotient a double
+    const double delta = (double)(v[c1] - v[c0]);
+    const float off = delta == 0.0 ? 0.5f : (float)((double)(0.0f - v[c0]) / delta);
+    const float ox = (float)corner_dx(c0), oy = (float)corner_dy(c0), oz = (float)corner_dz(c0);
+    const float dx = (float)(corner_dx(c1) - corner_dx(c0)), dy = (float)(corner_dy(c1) - corner_dy(c0)),
+                dz = (float)(corner_dz(c1) - corner_dz(c0));
+    return v3(p0.x + (ox + off * dx) * p.voxel.x, p0.y + (oy + off * dy) * p.voxel.y, p0.z + (oz + off * dz) * p.voxel.z);
+}
+
+// normal and grey colour of the vertex at pos.  SLAB: zero where the planes they read are not stored here
+template <typename CELL, bool SLAB>
+__device__ __forceinline__ void edge_attributes(const MeshParams& p, const ColorGeom& cv, int has_color, const V3& pos, V3& normal, float& grey)
+{
+    bool stored = true;   // SLAB: the planes this vertex's normal and colour read are stored here
+    V3 n;
+    if constexpr (SLAB) {
+        // the stencil's planes (gradient<>: base plane clamped to [1, d - 2], one plane either side) must be stored; they are
+        // for any vertex within a voxel of its cube, which float positions are unless the box lies ~2^20 voxels from the origin
+        const float pfz = (pos.z - p.vol.bmin.z) / p.size.z * p.dims1.z;
+        const int iz = (int)fmaxf(fminf(p.hi2.z, floorf(pfz)), 1.f);
+        stored = iz - 1 >= p.avail_lo && iz + 1 < p.avail_hi;
+        if (stored) {
+            const V3 deriv = gradient<CELL>(p, pos);
+            n = div_s(deriv, length(deriv));
+        } else {
+            n = v3(0.f, 0.f, 0.f);
+        }
+    } else {
+        const V3 deriv = gradient<CELL>(p, pos);
+        n = div_s(deriv, length(deriv));
+    }
+    if (!isfinite(n.x) || !isfinite(n.y) || !isfinite(n.z)) n = v3(0.f, 0.f, 0.f);
+    normal = n;
+    // (SLAB: the colour sample's planes, base clamp(floor(pfz), 0, d - 2) and the next, lie inside the stencil's three: equal geometry)
+    grey = (has_color && stored) ? trilinear<RayC32>(cv, pos) : 0.f;
+}
+
 // One thread per ACTIVE cube (cube_index lists the cubes with triangles in emission order; tri_offset their first
 // triangle): dense lanes instead of the ~1 % active lanes of a thread-per-cube sweep.  CELL: fp32 or half cells; SLAB: p holds
 // the full volume's geometry over a slab's planes [avail_lo, avail_hi) (virtual base pointer, slab_full_volume), and so does cv for
@@ -128,46 +181,14 @@ __global__ __launch_bounds__(128) void k_mc_emit(const MeshParams p, const Color
     const int ntri = c_num_tris[flag];
     if (ntri == 0) return;
     const unsigned mask = c_edge_mask[flag];
-    // VoxelPositionInUnits(x,y,z) and VoxelSizeUnits() (BoundedVolume.h:115-125, :67-76)
-    const V3 p0 = v3(p.vol.bmin.x + p.size.x * (float)x / p.dims1.x, p.vol.bmin.y + p.size.y * (float)y / p.dims1.y,
-                     p.vol.bmin.z + p.size.z * (float)z / p.dims1.z);
+    const V3 p0 = cube_origin(p, x, y, z);
     V3 ev[12], en[12];
     float ec[12];
 #pragma unroll
     for (int e = 0; e < 12; ++e) {
         if (!(mask & (1u << e))) continue;
-        // edges 0-3: bottom ring, 4-7: top ring, 8-11: verticals (MarchingCubes tables' numbering)
-        const int c0 = e < 8 ? e : e - 8, c1 = e < 4 ? (e + 1) & 3 : (e < 8 ? 4 + ((e + 1) & 3) : e - 4);
-        // fGetOffset (MarchingCubes.h:25-32): the difference is a float, the quotient a double
-        const double delta = (double)(v[c1] - v[c0]);
-        const float off = delta == 0.0 ? 0.5f : (float)((double)(0.0f - v[c0]) / delta);
-        const float ox = (float)corner_dx(c0), oy = (float)corner_dy(c0), oz = (float)corner_dz(c0);
-        const float dx = (float)(corner_dx(c1) - corner_dx(c0)), dy = (float)(corner_dy(c1) - corner_dy(c0)),
-                    dz = (float)(corner_dz(c1) - corner_dz(c0));
-        const V3 pos = v3(p0.x + (ox + off * dx) * p.voxel.x, p0.y + (oy + off * dy) * p.voxel.y, p0.z + (oz + off * dz) * p.voxel.z);
-        ev[e] = pos;
-        bool stored = true;   // SLAB: the planes this vertex's normal and colour read are stored here
-        V3 n;
-        if constexpr (SLAB) {
-            // the stencil's planes (gradient<>: base plane clamped to [1, d - 2], one plane either side) must be stored; they are
-            // for any vertex within a voxel of its cube, which float positions are unless the box lies ~2^20 voxels from the origin
-            const float pfz = (pos.z - p.vol.bmin.z) / p.size.z * p.dims1.z;
-            const int iz = (int)fmaxf(fminf(p.hi2.z, floorf(pfz)), 1.f);
-            stored = iz - 1 >= p.avail_lo && iz + 1 < p.avail_hi;
-            if (stored) {
-                const V3 deriv = gradient<CELL>(p, pos);
-                n = div_s(deriv, length(deriv));
-            } else {
-                n = v3(0.f, 0.f, 0.f);
-            }
-        } else {
-            const V3 deriv = gradient<CELL>(p, pos);
-            n = div_s(deriv, length(deriv));
-        }
-        if (!isfinite(n.x) || !isfinite(n.y) || !isfinite(n.z)) n = v3(0.f, 0.f, 0.f);
-        en[e] = n;
-        // (SLAB: the colour sample's planes, base clamp(floor(pfz), 0, d - 2) and the next, lie inside the stencil's three: equal geometry)
-        ec[e] = (has_color && stored) ? trilinear<RayC32>(cv, pos) : 0.f;
+        ev[e] = edge_position(p, p0, v, e);
+        edge_attributes<CELL, SLAB>(p, cv, has_color, ev[e], en[e], ec[e]);
     }
     size_t o = (size_t)tri_offset[t_id] * 3; // first output vertex of this cube
     for (int t = 0; t < ntri * 3; ++t, ++o) {
@@ -506,6 +527,256 @@ static MeshScratch mesh_scratch(const MeshRange& r, void* scratch)
     return s;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Indexed extraction (include/kfx_mesh_index.h): the soup welded by LATTICE EDGE -- (minimum corner, axis) of the cube edge a
+// vertex lies on -- into the sequential first-occurrence mesh.  A lattice edge belongs to up to four cubes; its OWNER is the first
+// of them in emission order that is meshed.  A cube with a sign change on an edge and eight finite corners has triangles, so
+// "meshed" is "listed in cube_index", answered by a binary search in the compacted, ascending list: no table per voxel or edge.
+//   k_mesh_compact      as above, into the index scratch
+//   k_mesh_own          one lane per active cube: case flag and the 12-bit mask of the edges it owns (4 bytes), block sums
+//   k_mesh_scan_partials   as above: the blocks' first vertex ids, the vertex total
+//   k_mesh_vertex_base  every active cube's first vertex id (4 bytes)
+//   k_mc_emit_indexed   one lane per active cube: owned edges write their vertex at base + rank, rank = first use among the owned
+//                       edges in c_tris[flag]; every triangle corner writes base(owner) + rank(edge in owner)
+constexpr int MESH_IDX_BLOCK = 256;
+
+// position of cube c in the ascending cube_index[0, n), -1 if it is not listed
+__device__ __forceinline__ long long find_cube(const long long* __restrict__ cube_index, long long n, long long c)
+{
+    long long lo = 0, hi = n;
+    while (lo < hi) {
+        const long long mid = lo + ((hi - lo) >> 1);
+        if (cube_index[mid] < c) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < n && cube_index[lo] == c ? lo : -1;
+}
+
+// The owner of the lattice edge under edge e of active cube t = (x, y, z), index ci: its position in cube_index, and in owner_e the
+// edge's number there.  The edge's axis is a; along the other two axes u < w (x before y before z: the emission order's
+// significance) the four cubes around it sit at the edge's minimum corner minus (su, sw) in {0, 1}^2, this cube at its own
+// minimum-corner offsets.  The candidates before this cube are looked up in ascending order; without one the cube owns the edge.
+__device__ __forceinline__ long long edge_owner(const MeshParams& p, const long long* __restrict__ cube_index, long long t, long long ci,
+                                                int x, int y, int z, int e, int& owner_e)
+{
+    const int c0 = edge_c0(e), c1 = edge_c1(e);
+    const int m[3] = {min(corner_dx(c0), corner_dx(c1)), min(corner_dy(c0), corner_dy(c1)), min(corner_dz(c0), corner_dz(c1))};
+    const int a = corner_dx(c0) != corner_dx(c1) ? 0 : (corner_dy(c0) != corner_dy(c1) ? 1 : 2);
+    const int u = a == 0 ? 1 : 0, w = a == 2 ? 1 : 2;
+    const int at[3] = {x, y, z}, cubes[3] = {p.cx, p.cy, p.cz};
+    const long long stride[3] = {(long long)p.cy * p.cz, (long long)p.cz, 1};
+#pragma unroll
+    for (int su = 1; su >= 0; --su) {
+#pragma unroll
+        for (int sw = 1; sw >= 0; --sw) {
+            const int du = m[u] - su, dw = m[w] - sw;
+            if (!(du < 0 || (du == 0 && dw < 0))) continue;   // this cube or a later one
+            const int nu = at[u] + du, nw = at[w] + dw;
+            if (nu < 0 || nu >= cubes[u] || nw < 0 || nw >= cubes[w]) continue;
+            const long long j = find_cube(cube_index, t, ci + du * stride[u] + dw * stride[w]);
+            if (j >= 0) {
+                // the edge of axis a with minimum corner (su, sw) in the owner
+                owner_e = a == 0 ? 2 * su + 4 * sw : (a == 1 ? (su ? 1 : 3) + 4 * sw : 8 + (sw ? 3 - su : su));
+                return j;
+            }
+        }
+    }
+    owner_e = e;
+    return t;
+}
+
+// ranks of a cube's owned edges by first use in its triangle list, 4 bits per edge
+__device__ __forceinline__ unsigned long long edge_ranks(int flag, unsigned own)
+{
+    unsigned long long ranks = 0;
+    unsigned seen = 0, r = 0;
+    const int n = c_num_tris[flag] * 3;
+    for (int k = 0; k < n; ++k) {
+        const int q = c_tris[flag][k];
+        if ((seen >> q) & 1u) continue;
+        seen |= 1u << q;
+        if ((own >> q) & 1u) ranks |= (unsigned long long)(r++) << (4 * q);
+    }
+    return ranks;
+}
+__device__ __forceinline__ unsigned rank_of(unsigned long long ranks, int e) { return (unsigned)(ranks >> (4 * e)) & 15u; }
+
+__device__ __forceinline__ void cube_xyz(const MeshParams& p, long long ci, int& x, int& y, int& z)
+{
+    z = (int)(ci % p.cz);
+    y = (int)((ci / p.cz) % p.cy);
+    x = (int)(ci / ((long long)p.cz * p.cy));
+}
+
+// info[t] = flag | owned edges << 8; part[2 b] = vertices, part[2 b + 1] = triangles of block b's cubes.  hdr[2], hdr[3]: the totals
+// this index was planned for (hdr[0], hdr[1] are the scan's: vertices, triangles).
+template <typename CELL>
+__global__ __launch_bounds__(MESH_IDX_BLOCK) void k_mesh_own(const MeshParams p, const long long* __restrict__ cube_index, const long long n_active,
+                                                             const unsigned long long n_tris, unsigned* __restrict__ info,
+                                                             unsigned* __restrict__ part, unsigned long long* __restrict__ hdr)
+{
+    __shared__ unsigned lds[2][MESH_IDX_BLOCK / 64];
+    const long long t = (long long)blockIdx.x * MESH_IDX_BLOCK + threadIdx.x;
+    unsigned nv = 0, nt = 0;
+    if (t < n_active) {
+        const long long ci = cube_index[t];
+        int x, y, z, flag;
+        cube_xyz(p, ci, x, y, z);
+        float v[8];
+        cube_case<CELL>(p, x, y, z, v, flag);
+        const unsigned mask = c_edge_mask[flag];
+        unsigned own = 0;
+#pragma unroll
+        for (int e = 0; e < 12; ++e) {
+            if (!(mask & (1u << e))) continue;
+            int oe;
+            if (edge_owner(p, cube_index, t, ci, x, y, z, e, oe) == t) own |= 1u << e;
+        }
+        info[t] = (unsigned)flag | (own << 8);
+        nv = __popc(own);
+        nt = c_num_tris[flag];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        nv += __shfl_xor(nv, o, 64);
+        nt += __shfl_xor(nt, o, 64);
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) { lds[0][wv] = nv; lds[1][wv] = nt; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned sv = 0, st = 0;
+        for (int i = 0; i < MESH_IDX_BLOCK / 64; ++i) { sv += lds[0][i]; st += lds[1][i]; }
+        part[2 * (size_t)blockIdx.x] = sv;
+        part[2 * (size_t)blockIdx.x + 1] = st;
+        if (blockIdx.x == 0) { hdr[2] = (unsigned long long)n_active; hdr[3] = n_tris; }
+    }
+}
+
+__global__ __launch_bounds__(MESH_IDX_BLOCK) void k_mesh_vertex_base(const unsigned* __restrict__ info, const long long n_active,
+                                                                     const unsigned long long* __restrict__ base, unsigned* __restrict__ vbase)
+{
+    __shared__ unsigned lds[MESH_IDX_BLOCK / 64];
+    const long long t = (long long)blockIdx.x * MESH_IDX_BLOCK + threadIdx.x;
+    const unsigned n = t < n_active ? __popc(info[t] >> 8) : 0u;
+    unsigned total;
+    const unsigned ex = block_exclusive_scan<unsigned, MESH_IDX_BLOCK / 64>(n, lds, &total);
+    if (t < n_active) vbase[t] = (unsigned)base[2 * (size_t)blockIdx.x] + ex;
+}
+
+// k_mc_emit with shared vertices: positions, normals and colours by k_mc_emit's expressions, computed by the owner only
+template <typename CELL, bool SLAB>
+__global__ __launch_bounds__(128) void k_mc_emit_indexed(const MeshParams p, const ColorGeom cv, const int has_color,
+                                                         const long long* __restrict__ cube_index, const unsigned* __restrict__ tri_offset,
+                                                         const unsigned* __restrict__ info, const unsigned* __restrict__ vbase,
+                                                         const long long n_active, const unsigned long long n_verts, float* __restrict__ verts,
+                                                         float* __restrict__ norms, float* __restrict__ colors, unsigned* __restrict__ faces)
+{
+    const long long t_id = (long long)blockIdx.x * 128 + threadIdx.x;
+    if (t_id >= n_active) return;
+    const long long ci = cube_index[t_id];
+    int x, y, z, flag;
+    cube_xyz(p, ci, x, y, z);
+    float v[8];
+    if (!cube_case<CELL>(p, x, y, z, v, flag)) return;
+    const int ntri = c_num_tris[flag];
+    if (ntri == 0) return;
+    const unsigned mask = c_edge_mask[flag];
+    const unsigned own = info[t_id] >> 8, first = vbase[t_id];
+    const unsigned long long ranks = edge_ranks(flag, own);
+    const V3 p0 = cube_origin(p, x, y, z);
+    unsigned id[12];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) {
+        id[e] = 0;
+        if (!(mask & (1u << e))) continue;
+        if (own & (1u << e)) {
+            const size_t i = first + rank_of(ranks, e);
+            id[e] = (unsigned)i;
+            if (i >= n_verts) continue;
+            const V3 pos = edge_position(p, p0, v, e);
+            V3 n;
+            float c;
+            edge_attributes<CELL, SLAB>(p, cv, has_color, pos, n, c);
+            verts[i * 3 + 0] = pos.x; verts[i * 3 + 1] = pos.y; verts[i * 3 + 2] = pos.z;
+            norms[i * 3 + 0] = n.x; norms[i * 3 + 1] = n.y; norms[i * 3 + 2] = n.z;
+            if (has_color) { // as k_mc_emit
+                colors[i * 4 + 0] = c; colors[i * 4 + 1] = c; colors[i * 4 + 2] = c; colors[i * 4 + 3] = 1.0f;
+            }
+        } else {
+            int oe;
+            const long long j = edge_owner(p, cube_index, t_id, ci, x, y, z, e, oe);
+            const unsigned oi = info[j];
+            id[e] = vbase[j] + rank_of(edge_ranks((int)(oi & 255u), oi >> 8), oe);
+        }
+    }
+    size_t o = (size_t)tri_offset[t_id] * 3; // first face corner of this cube
+    for (int t = 0; t < ntri * 3; ++t, ++o) {
+        const int e = c_tris[flag][t];
+        unsigned I = 0;
+#pragma unroll
+        for (int k = 0; k < 12; ++k)   // select without dynamic register indexing
+            if (k == e) I = id[k];
+        faces[o] = I;
+    }
+}
+
+// index scratch: [header: vertices, triangles, planned cubes, planned triangles][cube_index, 8 B][tri_offset, 4 B][info, 4 B]
+// [vbase, 4 B] per active cube, [block sums, 8 B][block offsets, 16 B] per MESH_IDX_BLOCK active cubes
+struct MeshIndexScratch {
+    unsigned long long* hdr;
+    long long* cube_index;
+    unsigned *tri_offset, *info, *vbase, *part;
+    unsigned long long* base;
+    long long nblk;
+    size_t bytes;
+};
+static MeshIndexScratch mesh_index_scratch(unsigned long long n_active, void* scratch)
+{
+    MeshIndexScratch s;
+    unsigned char* b = (unsigned char*)scratch;
+    size_t o = 0;
+    s.nblk = (long long)((n_active + MESH_IDX_BLOCK - 1) / MESH_IDX_BLOCK);
+    s.hdr = (unsigned long long*)(b + o); o += MESH_HEADER;
+    s.cube_index = (long long*)(b + o); o += align256((size_t)n_active * 8);
+    s.tri_offset = (unsigned*)(b + o); o += align256((size_t)n_active * 4);
+    s.info = (unsigned*)(b + o); o += align256((size_t)n_active * 4);
+    s.vbase = (unsigned*)(b + o); o += align256((size_t)n_active * 4);
+    s.part = (unsigned*)(b + o); o += align256((size_t)s.nblk * 8);
+    s.base = (unsigned long long*)(b + o); o += align256((size_t)s.nblk * 16);
+    s.bytes = o;
+    return s;
+}
+
+static bool totals_in_range(const unsigned long long totals[2]) { return totals[1] < MESH_MAX_TRIS && totals[0] <= totals[1]; }
+
+// the colour volume of a planned emit (kfx_mesh.h: colorvol)
+static int mesh_color_params(ColorGeom& cv, int& has_color, const kfx_volume* vol, int cell, const kfx_slab* slab, const kfx_volume* colorvol,
+                             const float* colors)
+{
+    has_color = 0;
+    if (!slab) {
+        if (int e = color_params(cv, has_color, colorvol, colors)) return e;
+    } else if (colorvol && colorvol->ptr && colors) {
+        // the rank's colour slab: the planes of `vol` of a colour volume with the SDF volume's geometry, seen through the full volume
+        if (cell != KFX_CELL_F32) return set_error(KFX_E_RANGE, "kfx_mesh_emit: colour on slabs needs fp32 SDF cells");
+        if (int e = check_volume(colorvol, 4, 1, VOLUME_ANY_DIM, "SaveMesh(colour, slab)")) return e;
+        if (int e = check_color_slab(vol, colorvol, "SaveMesh(colour, slab)")) return e;
+        const kfx_volume cfull = slab_full_volume(colorvol, slab);
+        if (int e = color_params(cv, has_color, &cfull, colors)) return e;   // (IsValid() of the FULL colour volume)
+    }
+    if (!has_color) cv = ColorGeom{};
+    return 0;
+}
+
+// n 64-bit words of a scratch header, once the stream's earlier work is done
+static int read_header(unsigned long long* host, const unsigned long long* dev, int n, hipStream_t st)
+{
+    hipError_t e = hipMemcpyAsync(host, dev, (size_t)n * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    return e == hipSuccess ? 0 : set_error((int)e, hipGetErrorString(e));
+}
+
 } // namespace kfx
 
 using namespace kfx;
@@ -615,24 +886,12 @@ extern "C" int kfx_mesh_emit(const kfx_volume* vol, int cell, const kfx_slab* sl
         return set_error(KFX_E_ALIGN, "kfx_mesh_emit: output alignment");
     ColorGeom cv;
     int has_color = 0;
-    if (!slab) {
-        if (int e = color_params(cv, has_color, colorvol, colors)) return e;
-    } else if (colorvol && colorvol->ptr && colors) {
-        // the rank's colour slab: the planes of `vol` of a colour volume with the SDF volume's geometry, seen through the full volume
-        if (cell != KFX_CELL_F32) return set_error(KFX_E_RANGE, "kfx_mesh_emit: colour on slabs needs fp32 SDF cells");
-        if (int e = check_volume(colorvol, 4, 1, VOLUME_ANY_DIM, "SaveMesh(colour, slab)")) return e;
-        if (int e = check_color_slab(vol, colorvol, "SaveMesh(colour, slab)")) return e;
-        const kfx_volume cfull = slab_full_volume(colorvol, slab);
-        if (int e = color_params(cv, has_color, &cfull, colors)) return e;   // (IsValid() of the FULL colour volume)
-    }
-    if (!has_color) cv = ColorGeom{};
+    if (int e = mesh_color_params(cv, has_color, vol, cell, slab, colorvol, colors)) return e;
     if (int e = load_tables()) return e;
     const hipStream_t st = (hipStream_t)stream;
     // the totals must be this scratch's plan's: the emit kernel trusts the compacted lists to fit the caller's buffers
     unsigned long long planned[2];
-    hipError_t he = hipMemcpyAsync(planned, s.totals, sizeof(planned), hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess) he = hipStreamSynchronize(st);
-    if (he != hipSuccess) return set_error((int)he, hipGetErrorString(he));
+    if (int e = read_header(planned, s.totals, 2, st)) return e;
     if (planned[0] != totals[0] || planned[1] != totals[1]) return set_error(KFX_E_RANGE, "kfx_mesh_emit: totals are not the plan's");
     if (cell == KFX_CELL_F32) {
         if (slab) mesh_emit_launch<RayF32, true>(p, r, s, cv, has_color, totals, cube_index, tri_offset, verts, norms, has_color ? colors : nullptr, st);
@@ -642,4 +901,103 @@ extern "C" int kfx_mesh_emit(const kfx_volume* vol, int cell, const kfx_slab* sl
         else mesh_emit_launch<RayF16, false>(p, r, s, cv, has_color, totals, cube_index, tri_offset, verts, norms, colors, st);
     }
     return check_launch("kfx_mesh_emit");
+}
+
+// ---- indexed extraction (include/kfx_mesh_index.h) ----
+
+extern "C" size_t kfx_mesh_index_scratch_bytes(const kfx_volume* vol, int cell, const kfx_slab* slab, int own_lo, int own_hi,
+                                               const unsigned long long totals[2])
+{
+    MeshParams p;
+    MeshRange r;
+    if (mesh_setup(p, r, vol, cell, slab, own_lo, own_hi)) return 0;
+    if (!totals) { set_error(KFX_E_NULL, "kfx_mesh_index_scratch_bytes: null totals"); return 0; }
+    if (!totals_in_range(totals)) { set_error(KFX_E_RANGE, "kfx_mesh_index_scratch_bytes: totals out of range"); return 0; }
+    return mesh_index_scratch(totals[0], nullptr).bytes;
+}
+
+template <typename CELL>
+static void mesh_index_plan_launch(const MeshParams& p, const MeshRange& r, const MeshScratch& s, const MeshIndexScratch& x,
+                                   const unsigned long long totals[2], hipStream_t st)
+{
+    hipLaunchKernelGGL(k_mesh_compact<CELL>, dim3((unsigned)r.nblk), dim3(256), 0, st, p, r, s.seg, s.base, x.cube_index, x.tri_offset,
+                       totals[0], totals[1]);
+    const long long n_active = (long long)totals[0];
+    hipLaunchKernelGGL(k_mesh_own<CELL>, dim3((unsigned)x.nblk), dim3(MESH_IDX_BLOCK), 0, st, p, x.cube_index, n_active, totals[1], x.info,
+                       x.part, x.hdr);
+    hipLaunchKernelGGL(k_mesh_scan_partials, dim3(1), dim3(MESH_SCAN_THREADS), 0, st, x.part, x.nblk, x.base, x.hdr);
+    hipLaunchKernelGGL(k_mesh_vertex_base, dim3((unsigned)x.nblk), dim3(MESH_IDX_BLOCK), 0, st, x.info, n_active, x.base, x.vbase);
+}
+
+extern "C" int kfx_mesh_index_plan(const kfx_volume* vol, int cell, const kfx_slab* slab, int own_lo, int own_hi, const void* scratch,
+                                   size_t scratch_bytes, const unsigned long long totals[2], void* index_scratch,
+                                   size_t index_scratch_bytes, unsigned long long* n_verts, kfx_stream stream)
+{
+    MeshParams p;
+    MeshRange r;
+    if (int e = mesh_setup(p, r, vol, cell, slab, own_lo, own_hi)) return e;
+    if (!scratch || !totals || !index_scratch || !n_verts) return set_error(KFX_E_NULL, "kfx_mesh_index_plan: null scratch, totals or vertex count");
+    if (!totals_in_range(totals)) return set_error(KFX_E_RANGE, "kfx_mesh_index_plan: totals out of range");
+    if (((uintptr_t)scratch | (uintptr_t)index_scratch) & 255) return set_error(KFX_E_ALIGN, "kfx_mesh_index_plan: scratch not 256-byte aligned");
+    const MeshScratch s = mesh_scratch(r, (void*)scratch);
+    const MeshIndexScratch x = mesh_index_scratch(totals[0], index_scratch);
+    if (scratch_bytes < s.bytes) return set_error(KFX_E_SHAPE, "kfx_mesh_index_plan: scratch smaller than kfx_mesh_scratch_bytes");
+    if (index_scratch_bytes < x.bytes) return set_error(KFX_E_SHAPE, "kfx_mesh_index_plan: index scratch smaller than kfx_mesh_index_scratch_bytes");
+    *n_verts = 0;
+    if (totals[0] == 0) return 0;
+    if (int e = load_tables()) return e;
+    const hipStream_t st = (hipStream_t)stream;
+    // the totals must be the plan's: the compaction trusts the lists to fit the index scratch sized from them
+    unsigned long long planned[2];
+    if (int e = read_header(planned, s.totals, 2, st)) return e;
+    if (planned[0] != totals[0] || planned[1] != totals[1]) return set_error(KFX_E_RANGE, "kfx_mesh_index_plan: totals are not the plan's");
+    if (cell == KFX_CELL_F32) mesh_index_plan_launch<RayF32>(p, r, s, x, totals, st);
+    else mesh_index_plan_launch<RayF16>(p, r, s, x, totals, st);
+    if (int e = check_launch("kfx_mesh_index_plan")) return e;
+    unsigned long long host[2];
+    if (int e = read_header(host, x.hdr, 2, st)) return e;
+    *n_verts = host[0];
+    return 0;
+}
+
+extern "C" int kfx_mesh_emit_indexed(const kfx_volume* vol, int cell, const kfx_slab* slab, int own_lo, int own_hi, const kfx_volume* colorvol,
+                                     const void* index_scratch, size_t index_scratch_bytes, const unsigned long long totals[2],
+                                     unsigned long long n_verts, float* verts, float* norms, float* colors, unsigned* faces, kfx_stream stream)
+{
+    MeshParams p;
+    MeshRange r;
+    if (int e = mesh_setup(p, r, vol, cell, slab, own_lo, own_hi)) return e;
+    if (!index_scratch || !totals) return set_error(KFX_E_NULL, "kfx_mesh_emit_indexed: null scratch or totals");
+    if (!totals_in_range(totals) || n_verts > 3 * totals[1]) return set_error(KFX_E_RANGE, "kfx_mesh_emit_indexed: totals out of range");
+    if ((uintptr_t)index_scratch & 255) return set_error(KFX_E_ALIGN, "kfx_mesh_emit_indexed: scratch not 256-byte aligned");
+    const MeshIndexScratch x = mesh_index_scratch(totals[0], (void*)index_scratch);
+    if (index_scratch_bytes < x.bytes) return set_error(KFX_E_SHAPE, "kfx_mesh_emit_indexed: index scratch smaller than kfx_mesh_index_scratch_bytes");
+    if (totals[0] == 0) return 0;
+    if (!verts || !norms || !faces) return set_error(KFX_E_NULL, "kfx_mesh_emit_indexed: null output");
+    if (((uintptr_t)verts | (uintptr_t)norms | (uintptr_t)colors | (uintptr_t)faces) & 3) return set_error(KFX_E_ALIGN, "kfx_mesh_emit_indexed: output alignment");
+    ColorGeom cv;
+    int has_color = 0;
+    if (int e = mesh_color_params(cv, has_color, vol, cell, slab, colorvol, colors)) return e;
+    if (int e = load_tables()) return e;
+    const hipStream_t st = (hipStream_t)stream;
+    // the totals and the vertex count must be this scratch's index plan's: the kernel trusts its lists to fit the caller's buffers
+    unsigned long long planned[4];
+    if (int e = read_header(planned, x.hdr, 4, st)) return e;
+    if (planned[0] != n_verts || planned[1] != totals[1] || planned[2] != totals[0] || planned[3] != totals[1])
+        return set_error(KFX_E_RANGE, "kfx_mesh_emit_indexed: totals are not the index plan's");
+    const long long n_active = (long long)totals[0];
+    const dim3 grid((unsigned)((n_active + 127) / 128)), block(128);
+    float* const cols = has_color ? colors : nullptr;
+#define KFX_EMIT_INDEXED(CELL, SLAB)                                                                                                  \
+    hipLaunchKernelGGL((k_mc_emit_indexed<CELL, SLAB>), grid, block, 0, st, p, cv, has_color, x.cube_index, x.tri_offset, x.info, x.vbase, \
+                       n_active, n_verts, verts, norms, cols, faces)
+    if (cell == KFX_CELL_F32) {
+        if (slab) KFX_EMIT_INDEXED(RayF32, true);
+        else KFX_EMIT_INDEXED(RayF32, false);
+    } else {
+        if (slab) KFX_EMIT_INDEXED(RayF16, true);
+        else KFX_EMIT_INDEXED(RayF16, false);
+    }
+#undef KFX_EMIT_INDEXED
+    return check_launch("kfx_mesh_emit_indexed");
 }

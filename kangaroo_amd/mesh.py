@@ -8,6 +8,15 @@ their slots).  fp32 (SDF_t) and half (SDF_h, meshed as the exactly widened volum
 partitioned one.  The arrays equal the host algorithm's element for element (tests compare with the oracle); only the
 finished arrays cross PCIe.
 
+Indexed output (include/kfx_mesh_index.h), opt-in with indexed=True: the same mesh with one vertex per lattice edge and a face
+list -- the sequential first-occurrence weld of the soup above, keyed by the lattice edge (minimum corner, axis) each vertex lies
+on: a key seen for the first time gets the next id and that soup vertex's position, normal and colour bit for bit; faces[k] is the
+id of soup vertex k's key.  Welded on the device (kfx_mesh_index_plan finds every active cube's owned edges by binary searches in
+the compacted cube list and scans them, kfx_mesh_emit_indexed writes V vertices and T faces): a closed surface has V = T/2 + 2, so
+a grey mesh shrinks from 72 to 24 bytes per triangle (24 V + 12 T) and a colour mesh from 120 to 32, and adjacency can be read off
+the faces as they are.
+A slab's indexed mesh is the weld of that rank's soup: vertices on a slab boundary exist once per rank.
+
 Case tables: kangaroo_amd/csrc/mc_tables.inc, derived by scripts/gen_mc_tables.py.  Their boundary loops and
 winding agree with the classic tables the reference uses in all 256 cases; 158 cases split a polygon along a
 different interior diagonal (an equally valid triangulation of the same loop), so meshes are the same surface
@@ -29,8 +38,10 @@ from .roo import _stream
 CELL = {"f32": 0, "f16": 1}   # KFX_CELL_F32 / KFX_CELL_F16
 
 
-def ExtractMesh(vol, colorVol=None, stream=None, slab=None, with_index=False):
+def ExtractMesh(vol, colorVol=None, stream=None, slab=None, with_index=False, indexed=False):
     """Returns (verts, norms, colors): float32 device tensors of shape (3T, 3), (3T, 3) and (3T, 4) or None.
+    indexed=True: (verts, norms, colors, faces) with V rows each and faces (T, 3), uint32 ids held in an int32 tensor (the weld
+    of the arrays above by lattice edge, see the module docstring).
 
     vol.kind "f32" or "f16".  slab = (full_d, z_offset, full_zmin, full_zmax, own_lo, own_hi): `vol` holds planes
     [z_offset, z_offset + vol.d) of that volume and the cubes with lower plane in [own_lo, min(own_hi, full_d - 1)) are meshed,
@@ -56,12 +67,31 @@ def ExtractMesh(vol, colorVol=None, stream=None, slab=None, with_index=False):
         raise ValueError("mesh too large for 32-bit vertex offsets")
     _lib.check(code)
     na, ntri = int(totals[0]), int(totals[1])
+    # IsValid() of the colour volume -- of the FULL one where colorVol is a slab of it
+    has_color = colorVol is not None and min(colorVol.w, colorVol.h, colorVol.d if slab is None else int(slab[0])) >= 8
+    if indexed:
+        if with_index:
+            raise ValueError("ExtractMesh: with_index lists the soup's cubes; not with indexed=True")
+        xbytes = L.kfx_mesh_index_scratch_bytes(vol.ref(), cell, sl, int(lo), int(hi), totals)
+        xscratch = torch.empty(xbytes, dtype=torch.uint8, device=dev)
+        nv = C.c_ulonglong(0)
+        _lib.check(L.kfx_mesh_index_plan(vol.ref(), cell, sl, int(lo), int(hi), C.c_void_p(scratch.data_ptr()), nbytes, totals,
+                                         C.c_void_p(xscratch.data_ptr()), xbytes, C.byref(nv), st))
+        nv = int(nv.value)
+        verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        norms = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        colors = torch.empty((nv, 4), dtype=torch.float32, device=dev) if has_color else None
+        faces = torch.empty((ntri, 3), dtype=torch.int32, device=dev)
+        if na:
+            _lib.check(L.kfx_mesh_emit_indexed(vol.ref(), cell, sl, int(lo), int(hi), colorVol.ref() if has_color else None,
+                                               C.c_void_p(xscratch.data_ptr()), xbytes, totals, nv, C.c_void_p(verts.data_ptr()),
+                                               C.c_void_p(norms.data_ptr()), C.c_void_p(colors.data_ptr()) if has_color else None,
+                                               C.c_void_p(faces.data_ptr()), st))
+        return verts, norms, colors, faces
     cube_index = torch.empty(na, dtype=torch.int64, device=dev)
     tri_offset = torch.empty(na, dtype=torch.int32, device=dev)
     verts = torch.empty((3 * ntri, 3), dtype=torch.float32, device=dev)
     norms = torch.empty((3 * ntri, 3), dtype=torch.float32, device=dev)
-    # IsValid() of the colour volume -- of the FULL one where colorVol is a slab of it
-    has_color = colorVol is not None and min(colorVol.w, colorVol.h, colorVol.d if slab is None else int(slab[0])) >= 8
     colors = torch.empty((3 * ntri, 4), dtype=torch.float32, device=dev) if has_color else None
     if na:
         _lib.check(L.kfx_mesh_emit(vol.ref(), cell, sl, int(lo), int(hi), colorVol.ref() if has_color else None, C.c_void_p(scratch.data_ptr()),
@@ -72,35 +102,38 @@ def ExtractMesh(vol, colorVol=None, stream=None, slab=None, with_index=False):
     return verts, norms, colors
 
 
-def write_ply(path, verts, norms, colors=None, binary=True):
+def write_ply(path, verts, norms, colors=None, binary=True, faces=None):
+    """faces=None: one triangle per three consecutive vertices; otherwise the (T, 3) vertex ids of an indexed mesh."""
     verts, norms = np.asarray(verts, np.float32), np.asarray(norms, np.float32)
     n = len(verts)
+    ids = np.arange(n, dtype=np.uint32).reshape(-1, 3) if faces is None else np.asarray(faces).astype(np.uint32, copy=False).reshape(-1, 3)
     cols = [verts, norms] + ([np.asarray(colors, np.float32)] if colors is not None else [])
     table = np.concatenate(cols, axis=1)
     names = ["x", "y", "z", "nx", "ny", "nz"] + (["red", "green", "blue", "alpha"] if colors is not None else [])
     head = ["ply", "format %s 1.0" % ("binary_little_endian" if binary else "ascii"),
             "comment kangaroo_amd marching cubes", "element vertex %d" % n]
     head += ["property float %s" % nm for nm in names]
-    head += ["element face %d" % (n // 3), "property list uchar uint vertex_indices", "end_header"]
+    head += ["element face %d" % len(ids), "property list uchar uint vertex_indices", "end_header"]
     with open(path, "wb") as f:
         f.write(("\n".join(head) + "\n").encode())
         if binary:
             f.write(table.astype("<f4").tobytes())
-            faces = np.empty(n // 3, dtype=[("k", "u1"), ("i", "<u4", 3)])
-            faces["k"] = 3
-            faces["i"] = np.arange(n, dtype=np.uint32).reshape(-1, 3)
-            f.write(faces.tobytes())
+            rows = np.empty(len(ids), dtype=[("k", "u1"), ("i", "<u4", 3)])
+            rows["k"] = 3
+            rows["i"] = ids
+            f.write(rows.tobytes())
         else:
             for row in table:
                 f.write((" ".join("%.9g" % v for v in row) + "\n").encode())
-            for i in range(0, n, 3):
-                f.write(("3 %d %d %d\n" % (i, i + 1, i + 2)).encode())
+            for a, b, c in ids:
+                f.write(("3 %d %d %d\n" % (a, b, c)).encode())
 
 
-def SaveMesh(filename, vol, colorVol=None, binary=True, slab=None):
+def SaveMesh(filename, vol, colorVol=None, binary=True, slab=None, indexed=False):
     """SaveMesh(filename, vol[, volColor]) (MarchingCubes.h:246-262): writes filename + ".ply"; returns the triangle count.
-    fp32 or half volumes; slab: ExtractMesh's."""
-    verts, norms, colors = ExtractMesh(vol, colorVol, slab=slab)
+    fp32 or half volumes; slab: ExtractMesh's.  indexed=True: V welded vertices and T faces (ExtractMesh's) instead of 3T vertices."""
+    verts, norms, colors, *faces = ExtractMesh(vol, colorVol, slab=slab, indexed=indexed)
     torch.cuda.synchronize() if verts.is_cuda else None
-    write_ply(filename + ".ply", verts.cpu().numpy(), norms.cpu().numpy(), None if colors is None else colors.cpu().numpy(), binary)
-    return len(verts) // 3
+    faces = faces[0].cpu().numpy().view(np.uint32) if indexed else None
+    write_ply(filename + ".ply", verts.cpu().numpy(), norms.cpu().numpy(), None if colors is None else colors.cpu().numpy(), binary, faces)
+    return len(verts) // 3 if faces is None else len(faces)

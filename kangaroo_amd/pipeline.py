@@ -759,11 +759,13 @@ class SlabPipeline(FramePipeline):
                 ops.append(dist.P2POp(dist.irecv, vol.planes(own1, own1 + hi_ghost), self.rank + 1))
         self._p2p(ops)
 
-    def ExtractMesh(self):
+    def ExtractMesh(self, indexed=False):
         """This rank's part of the model's mesh (include/kfx_mesh.h): the cubes whose lower plane it owns, [z0, min(z1, D - 1)),
         every triangle bit-identical to the single-volume mesh's, in emission order; (verts, norms) device tensors, or -- color=True --
         (verts, norms, colors) with the single-volume mesh's colours.
-        With halo = "exchange" the ghost planes the normals read are refreshed first (a collective step: every rank calls)."""
+        With halo = "exchange" the ghost planes the normals read are refreshed first (a collective step: every rank calls).
+        indexed=True: (verts, norms[, colors], faces) -- the weld of this rank's part by lattice edge (include/kfx_mesh_index.h): V
+        vertices, faces (T, 3); a vertex on a slab boundary exists once per rank that uses it."""
         from . import mesh
         if self.sframe is not None:
             self.wait_composite()
@@ -771,16 +773,18 @@ class SlabPipeline(FramePipeline):
             self.exchange_halos()     # (the C driver's fuse step leaves them current itself)
         D = self.dims[2]
         slab = (D, self.s0, float(self.full_boxmin[2]), float(self.full_boxmax[2]), self.z0, self.z1)
-        verts, norms, colors = mesh.ExtractMesh(self.vol, self.cvol if self.color else None, slab=slab)
-        return (verts, norms, colors) if self.color else (verts, norms)
+        verts, norms, colors, *faces = mesh.ExtractMesh(self.vol, self.cvol if self.color else None, slab=slab, indexed=indexed)
+        return ((verts, norms, colors) if self.color else (verts, norms)) + tuple(faces)
 
-    def SaveMesh(self, prefix, binary=True):
-        """Writes this rank's part as prefix.r<rank>.ply (with colours when color=True); returns its triangle count."""
+    def SaveMesh(self, prefix, binary=True, indexed=False):
+        """Writes this rank's part as prefix.r<rank>.ply (with colours when color=True); returns its triangle count.
+        indexed=True: welded vertices and a face list (ExtractMesh's)."""
         from . import mesh
-        verts, norms, *colors = self.ExtractMesh()
+        verts, norms, *rest = self.ExtractMesh(indexed=indexed)
+        faces = rest.pop().cpu().numpy().view("uint32") if indexed else None
         mesh.write_ply("%s.r%d.ply" % (prefix, self.rank), verts.cpu().numpy(), norms.cpu().numpy(),
-                       colors[0].cpu().numpy() if colors and colors[0] is not None else None, binary)
-        return len(verts) // 3
+                       rest[0].cpu().numpy() if rest and rest[0] is not None else None, binary, faces)
+        return len(verts) // 3 if faces is None else len(faces)
 
     def raycast(self, T_wc):
         """raycast = "composite": every rank marches its own slab from the slab's entry point and the nearest

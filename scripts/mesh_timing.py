@@ -8,6 +8,9 @@ Volumes:
 Each case reports the median wall time of kfx_mesh_plan (count + reduce + scan + the 16-byte read-back), kfx_mesh_emit (compact +
 emit + the totals check) and the whole ExtractMesh call, interleaved with the old path; the count pass's fraction of 8 TB/s by
 unique volume bytes comes from the kernel time of a rocprofv3 --kernel-trace run of this script (pass --count-ms to fold it in).
+The indexed output (include/kfx_mesh_index.h) is timed in the same process, so that the soup figures beside it are this build's own:
+indexed_ms is the whole ExtractMesh(indexed=True) call (plan + index plan + indexed emit, to set against extract_ms), index_plan_ms
+and emit_indexed_ms its two added calls alone; ply_bytes / ply_bytes_indexed are the sizes of the binary files of either mesh.
 Usage: python scripts/mesh_timing.py --out profiles/r07_mesh/mesh_timing.jsonl [--cases 512,1024,2048h] [--reps 7]"""
 import argparse
 import ctypes as C
@@ -77,7 +80,18 @@ def run_case(name, reps):
     emit = lambda: _lib.check(L.kfx_mesh_emit(vol.ref(), cell, None, 0, 0, None, C.c_void_p(scratch.data_ptr()), nbytes, totals,
                                               C.c_void_p(ci.data_ptr()), C.c_void_p(to.data_ptr()), C.c_void_p(vv.data_ptr()),
                                               C.c_void_p(nn.data_ptr()), None, None))
-    fns = {"plan_ms": plan, "emit_ms": emit, "extract_ms": lambda: mesh.ExtractMesh(vol)}
+    xbytes = L.kfx_mesh_index_scratch_bytes(vol.ref(), cell, None, 0, 0, totals)
+    xscratch = torch.empty(xbytes, dtype=torch.uint8, device="cuda")
+    nvert = C.c_ulonglong(0)
+    index_plan = lambda: _lib.check(L.kfx_mesh_index_plan(vol.ref(), cell, None, 0, 0, C.c_void_p(scratch.data_ptr()), nbytes, totals,
+                                                          C.c_void_p(xscratch.data_ptr()), xbytes, C.byref(nvert), None))
+    index_plan()
+    nv = int(nvert.value)
+    ff = torch.empty((nt, 3), dtype=torch.int32, device="cuda")
+    emit_indexed = lambda: _lib.check(L.kfx_mesh_emit_indexed(vol.ref(), cell, None, 0, 0, None, C.c_void_p(xscratch.data_ptr()), xbytes, totals, nv,
+                                                              C.c_void_p(vv.data_ptr()), C.c_void_p(nn.data_ptr()), None, C.c_void_p(ff.data_ptr()), None))
+    fns = {"plan_ms": plan, "emit_ms": emit, "extract_ms": lambda: mesh.ExtractMesh(vol), "index_plan_ms": index_plan,
+           "emit_indexed_ms": emit_indexed, "indexed_ms": lambda: mesh.ExtractMesh(vol, indexed=True)}
     if kind == "f32":
         fns["old_path_ms"] = lambda: old_path(vol)
     for f in fns.values():   # warm-up
@@ -87,8 +101,10 @@ def run_case(name, reps):
         for k, f in fns.items():
             times[k].append(wall(f))
     rec = dict(case=name, dims=[N, N, N], cell=kind, active_cubes=na, triangles=nt, scratch_bytes=int(nbytes),
-               volume_bytes=int(vol.img_pitch * N), reps=reps)
+               volume_bytes=int(vol.img_pitch * N), reps=reps, vertices=nv, index_scratch_bytes=int(xbytes),
+               ply_bytes=(72 + 13) * nt, ply_bytes_indexed=24 * nv + 13 * nt)   # (without the ~300-byte header)
     rec.update({k: round(float(np.median(v)), 4) for k, v in times.items()})
+    rec.update({k.replace("_ms", "_spread_ms"): [round(float(min(v)), 4), round(float(max(v)), 4)] for k, v in times.items()})
     if kind == "f32":
         ov = old_path(vol)
         nv = mesh.ExtractMesh(vol)
