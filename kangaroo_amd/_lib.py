@@ -53,6 +53,11 @@ class KfxFrameConfig(C.Structure):
                 ("fuse_flags", C.c_uint), ("timing_slots", C.c_int)]
 
 
+class KfxShiftStep(C.Structure):
+    """kfx_shift_step (include/kfx_shift.h): one launch of a volume shift's plan."""
+    _fields_ = [("kind", C.c_int), ("dst_z0", C.c_int), ("dst_z1", C.c_int), ("src_z0", C.c_int), ("src_z1", C.c_int)]
+
+
 class KfxError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libkfx error %d: %s" % (code, msg))
@@ -61,7 +66,7 @@ class KfxError(RuntimeError):
 
 PI, PV, PF = C.POINTER(KfxImage), C.POINTER(KfxVolume), C.POINTER(C.c_float)
 
-# name -> (restype, argtypes); every symbol include/kfx.h declares (and kfx_summary_h.h, kfx_mesh.h, kfx_mesh_index.h, kfx_color.h, kfx_slab_color.h, kfx_sensor.h)
+# name -> (restype, argtypes); every symbol include/kfx.h declares (and kfx_summary_h.h, kfx_mesh.h, kfx_mesh_index.h, kfx_color.h, kfx_slab_color.h, kfx_sensor.h, kfx_shift.h)
 SIGNATURES = {
     "kfx_sdf_fuse": (C.c_int, [PV, PI, PI, PF, PF, C.c_float, C.c_float, C.c_float, C.c_uint, C.c_void_p]),
     "kfx_sdf_fuse_slab": (C.c_int, [PV, C.POINTER(KfxSlab), PI, PI, PF, PF, C.c_float, C.c_float, C.c_float, C.c_uint, C.c_void_p]),
@@ -195,6 +200,12 @@ SIGNATURES = {
     "kfx_depth_input_pending": (C.c_int, [C.c_void_p]),
     "kfx_depth_input_filter": (C.c_int, [C.c_void_p, PI, PI, C.c_float, C.c_float, C.c_uint, C.c_float, C.c_void_p]),
     "kfx_frame_set_input": (C.c_int, [C.c_void_p, C.c_void_p]),
+    # include/kfx_shift.h
+    "kfx_volume_shift_scratch_bytes": (C.c_size_t, [PV, C.c_int, C.POINTER(C.c_int)]),
+    "kfx_volume_shift_box": (C.c_int, [PV, C.POINTER(C.c_int), PF, PF]),
+    "kfx_volume_shift_plan": (C.c_int, [PV, C.c_int, C.POINTER(C.c_int), C.c_size_t, C.POINTER(KfxShiftStep), C.c_int, C.POINTER(C.c_int)]),
+    "kfx_volume_shift": (C.c_int, [PV, C.c_int, C.POINTER(C.c_int), C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "kfx_frame_shift": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 _lib = None

@@ -11,6 +11,7 @@
 #include "kfx_device.h"
 #include "frame_host.h"
 #include "sensor_host.h"
+#include "shift_host.h"
 
 struct kfx_frame {
     kfx_frame_config cfg;
@@ -74,6 +75,10 @@ extern "C" int kfx_frame_set_timing(kfx_frame* f, unsigned mask)
 extern "C" int kfx_frame_get_track(const kfx_frame* f) { return f ? f->track : set_error(KFX_E_NULL, "kfx_frame_get_track: null frame"); }
 extern "C" kfx_sdf_summary* kfx_frame_summary(kfx_frame* f) { return f ? f->summary : nullptr; }
 extern "C" long long kfx_frame_count(const kfx_frame* f) { return f ? f->frames : 0; }
+
+// for kfx_frame_shift (shift.hip, shift_host.h)
+kfx_volume* kfx::frame_volume(kfx_frame* f) { return &f->cfg.vol; }
+kfx_sdf_summary* kfx::frame_tracked_summary(kfx_frame* f) { return f->track ? f->summary : nullptr; }
 
 extern "C" int kfx_frame_set_track(kfx_frame* f, int on, kfx_stream stream)
 {

@@ -34,6 +34,19 @@ def vbo_normals(ops, vbo, normals, depth, K):
         ops.NormalsFromVbo(normals, vbo)
 
 
+def follow_shift(boxmin, boxmax, dims, T_wc, focus, quantum=8, slack=16):
+    """The whole-cell shift that lets the box follow the camera (host, float64).  target = camera centre + focus * the camera's +z
+    axis in the world; o = (target - box centre) / voxel size; per axis 0 while |o| < slack, else quantum * rint(o / quantum)
+    (rint: ties to even)."""
+    lo, hi = np.asarray(boxmin, np.float64).reshape(3), np.asarray(boxmax, np.float64).reshape(3)
+    T = np.asarray(T_wc, np.float64).reshape(-1, 4)[:3]
+    target = T[:, 3] + float(focus) * T[:, 2]
+    voxel = (hi - lo) / (np.asarray(dims, np.float64).reshape(3) - 1.0)
+    o = (target - 0.5 * (lo + hi)) / voxel
+    q = float(quantum)
+    return tuple(0 if abs(v) < slack else int(q * np.rint(v / q)) for v in o)
+
+
 class FramePipeline:
     # track="auto": the stream itself is the benchmark.  From frame CAL_FIRST on, three blocks of CAL_BLOCK frames each:
     # tracked pair (SdfFuse keeping the summary + march through the class tables), plain pair (the summary goes stale), tracked
@@ -46,8 +59,14 @@ class FramePipeline:
     def __init__(self, ops, dims, boxmin, boxmax, w, h, K=None, near=0.4, far=8.0, bilateral=None,
                  trunc_factor=scenes.TRUNC_DIST_FACTOR, max_w=scenes.MAX_W, mincostheta=scenes.MIN_COS_THETA,
                  contiguous_images=False, track=False, cal_first=None, cal_block=None, cal_margin=None, timing_slots=None, kind=None,
-                 color=False, color_size=None, T_cd=None, sensor=None, sensor_scale=1e-3, sensor_slots=2):
-        """sensor: "u16" or "f32" -- the frames arrive as raw sensor images on the host (main.cpp:202-209): the pipeline owns an upload
+                 color=False, color_size=None, T_cd=None, sensor=None, sensor_scale=1e-3, sensor_slots=2, follow=None):
+        """follow: None, or dict(focus=, quantum=, slack=) -- a volume that follows the camera.  At the start of a step, before anything
+        is enqueued for the frame, follow_shift() of the current box and the frame's pose (the tracking loop: the previous frame's)
+        gives a whole-cell shift; when it is not zero the volume is shifted in place on the device (ops.VolumeShift, fill NaN; the
+        one-call frame: its shift()), the colour volume with it (fill 0.5), the summary is rebuilt when tracking, vol.boxmin / boxmax
+        move, and (frame index, shift) is appended to self.shifts.  focus=None: the distance from the camera centre to the box centre
+        at the first step.  trunc stays what it was at construction.
+        sensor: "u16" or "f32" -- the frames arrive as raw sensor images on the host (main.cpp:202-209): the pipeline owns an upload
         ring (ops.DepthInput, `input`) of sensor_slots slots that converts with sensor_scale (millimetres: 1e-3) while it filters.
         submit(array) hands it the next image -- one frame ahead, its copy runs beside the current frame -- and a step / preprocess
         that is given no image consumes the oldest submitted one; self.raw then holds that frame's depth in metres.
@@ -93,6 +112,16 @@ class FramePipeline:
         self.summary = None
         self.kframe = None
         self.input = None
+        self.follow, self.shifts, self._shift_scratch = None, [], None
+        if follow is not None:
+            if not hasattr(ops, "VolumeShift"):
+                raise ValueError("FramePipeline: follow= needs an operator set with VolumeShift")
+            unknown = set(follow) - {"focus", "quantum", "slack"}
+            if unknown:
+                raise ValueError("FramePipeline: follow= takes focus, quantum and slack, not %s" % sorted(unknown))
+            self.follow = {"focus": follow.get("focus"), "quantum": int(follow.get("quantum", 8)), "slack": float(follow.get("slack", 16))}
+            if self.follow["quantum"] < 1:
+                raise ValueError("FramePipeline: follow= needs quantum >= 1")
         if sensor is not None:
             if not hasattr(ops, "DepthInput"):
                 raise ValueError("FramePipeline: sensor= needs an operator set with DepthInput")
@@ -197,6 +226,30 @@ class FramePipeline:
             self.ops.SdfReset(self.vol, float("nan"))
         if self.color:
             self.ops.ColorReset(self.cvol)   # SdfReset(colorVol) (main.cpp:233)
+
+    def shift_volume(self, shift):
+        """Shift the model by whole cells (ops.VolumeShift): the SDF volume with fill NaN -- through the one-call frame where it is in
+        use -- the colour volume with fill 0.5, the summary rebuilt when tracking; vol.boxmin / boxmax (and cvol's) move."""
+        if self._shift_scratch is None:   # one scratch for both volumes: 16 packed planes of the SDF volume's cells
+            self._shift_scratch = self.ops.shift_scratch(self.vol, shift)
+        if self.kframe is not None:
+            self.kframe.shift(shift, self._shift_scratch)
+        else:
+            self.ops.VolumeShift(self.vol, shift, float("nan"), self._shift_scratch, summary=self.summary if self.track else None)
+        if self.color:
+            self.ops.VolumeShift(self.cvol, shift, 0.5, self._shift_scratch)
+
+    def _follow(self, T_wc):
+        """follow=: the shift this pose asks for, applied before the frame's first launch"""
+        f = self.follow
+        T = np.asarray(T_wc, np.float64).reshape(-1, 4)[:3]
+        if f["focus"] is None:
+            centre = 0.5 * (np.asarray(self.vol.boxmin, np.float64) + np.asarray(self.vol.boxmax, np.float64))
+            f["focus"] = float(np.linalg.norm(centre - T[:, 3]))
+        shift = follow_shift(self.vol.boxmin, self.vol.boxmax, self.dims, T, f["focus"], f["quantum"], f["slack"])
+        if any(shift):
+            self.shift_volume(shift)
+            self.shifts.append((self.frames_done, shift))
 
     def color_pose(self, T_cw):
         """T_iw = T_cd * T_cw (3x4 float32): world -> colour camera"""
@@ -318,6 +371,8 @@ class FramePipeline:
         image ("u8x3", the colour camera's size; default self.rgb)."""
         if self.color:
             self._rgb_now = self.rgb if rgb_image is None else rgb_image
+        if self.follow is not None:
+            self._follow(T_wc)
         cal = self._cal is not None and self.frames_done >= self._cal["first"]
         if cal:
             self._policy_before()
@@ -409,6 +464,8 @@ class TrackingPipeline(FramePipeline):
         o, tr = self.ops, self.tracking
         if self.color:
             self._rgb_now = self.rgb if rgb_image is None else rgb_image
+        if self.follow is not None and self.frame > 0:   # the previous frame's pose: this frame's is not known yet
+            self._follow(self.T_wl)
         cal = self._cal is not None and self.frames_done >= self._cal["first"]
         if cal:   # track="auto": whole frames of the three blocks, host clock around the step (the pose read-back synchronises)
             self._policy_before()
@@ -478,6 +535,10 @@ class TrackingPipeline(FramePipeline):
             self._policy_after()
         return self.T_wl
 
+    def shift_volume(self, shift):
+        super().shift_volume(shift)
+        self._bound = {}   # (the bound SdfFuse calls marshalled the volume with its old box)
+
     def _fuse_bound(self, T_cw):
         """SdfFuse of the frame's maps at T_cw (3x4 float32) through a call whose other arguments were marshalled once (per set of
         maps and per tracked / plain choice)."""
@@ -540,6 +601,9 @@ class SlabPipeline(FramePipeline):
         deterministic per voxel, so no traffic is needed) -- the cross-check of the exchange path."""
         assert halo in ("exchange", "recompute")
         assert raycast in ("composite", "exact", "exact_allreduce")
+        if kw.get("follow") is not None:
+            raise ValueError("SlabPipeline: follow= (a volume that follows the camera) is a single-volume option: a shift along z moves "
+                             "planes from one rank's slab to another's, and shifts on Z-slabs are not implemented")
         if kw.get("sensor") is not None:
             raise ValueError("SlabPipeline: sensor= (the upload ring of raw sensor images) is a single-GPU option; give the slab pipelines "
                              "depth images in metres")

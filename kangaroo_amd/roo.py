@@ -16,6 +16,7 @@ import torch
 
 from . import _lib
 from ._lib import KfxError, KfxImage, KfxVolume  # noqa: F401
+from .pipeline import follow_shift  # noqa: F401  (roo.follow_shift: the host rule of a volume that follows the camera)
 
 _ELEM = {
     "f32": (np.float32, 1), "f32x4": (np.float32, 4), "u16": (np.uint16, 1), "u8": (np.uint8, 1),
@@ -372,6 +373,19 @@ class Frame:
         if e:
             _lib.check(e)
 
+    def shift(self, shift, scratch=None, stream=None):
+        """kfx_frame_shift (include/kfx_shift.h): VolumeShift of the frame's volume with fill NaN; the frame and the Python volume
+        take the shifted box, and a tracking frame rebuilds its summary."""
+        vol, s3 = self._keep[0], _shift3(shift)
+        if not any(s3):
+            return
+        if scratch is None:
+            scratch = shift_scratch(vol, s3)
+        lo, hi = VolumeShiftBox(vol, s3)
+        ptr, nbytes = (scratch.data_ptr(), scratch.numel() * scratch.element_size()) if scratch is not None else (None, 0)
+        _lib.check(_lib.load().kfx_frame_shift(self.handle, s3, ptr, nbytes, _stream(stream)))
+        vol.boxmin, vol.boxmax = lo, hi
+
     def set_input(self, depth_input):
         """kfx_frame_set_input (include/kfx_sensor.h): a step with raw=None then consumes the oldest image pending in the
         DepthInput -- filtered into `filtered`, its metres into `raw` -- instead of filtering `raw`.  None detaches."""
@@ -564,6 +578,69 @@ def SdfSphere(vol, center, r, stream=None):
     c, _c = _fp(center, 3)
     fn = _lib.load().kfx_sdf_sphere_h if vol.kind == "f16" else _lib.load().kfx_sdf_sphere
     _lib.check(fn(vol.ref(), c, r, _stream(stream)))
+
+
+# ---- moving volume (include/kfx_shift.h) ---------------------------------------------
+
+CELL_KIND = {"f32": 0, "f16": 1, "c32": 2}   # KFX_CELL_F32 / KFX_CELL_F16 / KFX_CELL_COLOR
+SHIFT_FILL, SHIFT_DIRECT, SHIFT_STAGE, SHIFT_PLACE = 0, 1, 2, 3
+SHIFT_SCRATCH_PLANES = 16   # the scratch VolumeShift allocates when it is given none
+
+
+def _shift3(shift):
+    s = [int(v) for v in shift]
+    if len(s) != 3:
+        raise ValueError("expected a shift of 3 whole cells, got %r" % (shift,))
+    return (C.c_int * 3)(*s)
+
+
+def VolumeShiftBox(vol, shift):
+    """kfx_volume_shift_box: (boxmin, boxmax) of `vol` shifted by `shift` cells -- VoxelPositionInUnits of its first and last voxel."""
+    lo, hi = np.empty(3, np.float32), np.empty(3, np.float32)
+    _lib.check(_lib.load().kfx_volume_shift_box(vol.ref(), _shift3(shift), lo.ctypes.data_as(_lib.PF), hi.ctypes.data_as(_lib.PF)))
+    return lo, hi
+
+
+def VolumeShiftScratchBytes(vol, shift):
+    """kfx_volume_shift_scratch_bytes: the least scratch this shift needs (0: none)."""
+    return int(_lib.load().kfx_volume_shift_scratch_bytes(vol.ref(), CELL_KIND[vol.kind], _shift3(shift)))
+
+
+def VolumeShiftPlan(vol, shift, scratch_bytes):
+    """kfx_volume_shift_plan: the launches of this shift as (kind, dst_z0, dst_z1, src_z0, src_z1) tuples, in stream order."""
+    L, n, s3 = _lib.load(), C.c_int(0), _shift3(shift)
+    _lib.check(L.kfx_volume_shift_plan(vol.ref(), CELL_KIND[vol.kind], s3, int(scratch_bytes), None, 0, C.byref(n)))
+    steps = (_lib.KfxShiftStep * max(n.value, 1))()
+    _lib.check(L.kfx_volume_shift_plan(vol.ref(), CELL_KIND[vol.kind], s3, int(scratch_bytes), steps, n.value, C.byref(n)))
+    return [(s.kind, s.dst_z0, s.dst_z1, s.src_z0, s.src_z1) for s in steps[:n.value]]
+
+
+def shift_scratch(vol, shift, planes=SHIFT_SCRATCH_PLANES):
+    """A scratch tensor for VolumeShift(vol, shift): `planes` packed z-planes (or the whole volume if it has fewer); None where
+    the shift needs none."""
+    need = VolumeShiftScratchBytes(vol, shift)
+    if not need:
+        return None
+    return torch.empty(max(need, min(int(planes), vol.d) * vol.w * vol.h * vol.ELEM), dtype=torch.uint8, device=vol.storage.device)
+
+
+def VolumeShift(vol, shift, fill, scratch=None, stream=None, summary=None):
+    """kfx_volume_shift: new(x, y, z) = old(x + sx, y + sy, z + sz) where that cell lies inside `vol` (a volume or a view of one),
+    `fill` elsewhere (SDF cells: what SdfReset(vol, fill) writes; a colour volume: fill), in place on the device; vol.boxmin /
+    boxmax become the shifted box.  scratch: a uint8 device tensor (shift_scratch(); allocated here when None and one is needed --
+    torch's memory, whose reuse is ordered on torch's current stream: with another `stream` pass a scratch of your own).
+    summary: the volume's SdfSummary, rebuilt from the moved cells."""
+    s3 = _shift3(shift)
+    if not any(s3):
+        return
+    if scratch is None:
+        scratch = shift_scratch(vol, s3)
+    lo, hi = VolumeShiftBox(vol, s3)
+    ptr, nbytes = (scratch.data_ptr(), scratch.numel() * scratch.element_size()) if scratch is not None else (None, 0)
+    _lib.check(_lib.load().kfx_volume_shift(vol.ref(), CELL_KIND[vol.kind], s3, float(fill), ptr, nbytes, _stream(stream)))
+    vol.boxmin, vol.boxmax = lo, hi
+    if summary is not None:
+        summary.rebuild(stream)
 
 
 def ElementwiseScaleBias(b, a, s, offset=0.0, stream=None):
