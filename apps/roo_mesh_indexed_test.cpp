@@ -65,7 +65,7 @@ static Ply ReadPly(const std::string& path)
 }
 
 // the file holds the arrays of the plain calls
-static bool HoldsArrays(const Ply& p, const mesh_detail::HostIndexedMesh& m)
+static bool HoldsArrays(const Ply& p, const mesh_detail::HostMesh& m)
 {
     const int f = m.color ? 10 : 6;
     if (!p.ok || p.floats != f || p.nvert != m.nvert || p.ntri != m.ntri) return false;
@@ -108,7 +108,7 @@ static void WholeVolume(const std::string& tmp, size_t W, size_t H, size_t D, co
     const int cell = mesh_detail::Cell<CELL>::kind;
     size_t nvert = 0;
     const size_t ntri = SaveMeshIndexed(tmp + ".i", vol, &nvert);
-    const mesh_detail::HostIndexedMesh m = mesh_detail::ExtractIndexed(vol.abi(), cell, nullptr, 0, 0, nullptr);
+    const mesh_detail::HostMesh m = mesh_detail::Extract(vol.abi(), cell, nullptr, 0, 0, nullptr, true);
     const Ply got = ReadPly(tmp + ".i.ply");
     CHECK(ntri == m.ntri && nvert == m.nvert && m.ntri > 2000 && m.nvert < m.ntri);   // (a soup has 3 vertices per triangle)
     CHECK(HoldsArrays(got, m));
@@ -116,7 +116,7 @@ static void WholeVolume(const std::string& tmp, size_t W, size_t H, size_t D, co
     CHECK(DeindexesTo(got, ReadPly(tmp + ".s.ply"), tol));
     // with a colour volume
     const size_t ntc = SaveMeshIndexed(tmp + ".ic", vol, col, &nvert);
-    const mesh_detail::HostIndexedMesh mc = mesh_detail::ExtractIndexed(vol.abi(), cell, nullptr, 0, 0, col.abi());
+    const mesh_detail::HostMesh mc = mesh_detail::Extract(vol.abi(), cell, nullptr, 0, 0, col.abi(), true);
     const Ply gotc = ReadPly(tmp + ".ic.ply");
     CHECK(ntc == ntri && nvert == m.nvert && mc.color && gotc.floats == 10 && HoldsArrays(gotc, mc));
     CHECK(SaveMesh(tmp + ".sc", vol, col) == ntri);

@@ -27,123 +27,91 @@ namespace roo
 
 namespace mesh_detail
 {
-inline void* DeviceBytes(size_t n)
+// n bytes of device memory (at least one), freed with the object; move-only
+class DeviceBuffer
 {
-    void* p = nullptr;
-    size_t pitch = 0;
-    GpuCheckStatus(kfx_alloc_pitched(&p, &pitch, n ? n : 1, 1));
-    return p;
-}
+public:
+    DeviceBuffer() = default;
+    explicit DeviceBuffer(size_t n)
+    {
+        size_t pitch = 0;
+        GpuCheckStatus(kfx_alloc_pitched(&ptr_, &pitch, n ? n : 1, 1));
+    }
+    DeviceBuffer(DeviceBuffer&& o) noexcept : ptr_(o.ptr_) { o.ptr_ = nullptr; }
+    DeviceBuffer& operator=(DeviceBuffer&& o) noexcept
+    {
+        if (this != &o) { Free(); ptr_ = o.ptr_; o.ptr_ = nullptr; }
+        return *this;
+    }
+    ~DeviceBuffer() { Free(); }
+    template<typename T = void> T* get() const { return (T*)ptr_; }
+    // its first n bytes into host memory
+    void CopyTo(void* host, size_t n) const
+    {
+        if (n) GpuCheckStatus(kfx_memcpy_2d(host, n, ptr_, n, n, 1, 2, 0));
+    }
+private:
+    void Free() { if (ptr_) kfx_free(ptr_); ptr_ = nullptr; }
+    void* ptr_ = nullptr;
+};
 
 template<typename T> struct Cell;
 template<> struct Cell<SDF_t> { static constexpr int kind = KFX_CELL_F32; };
 template<> struct Cell<SDF_h> { static constexpr int kind = KFX_CELL_F16; };
 
-// The mesh of `vol` (slab: its cubes [own_lo, own_hi) of the volume `slab` describes) as host arrays: 3 vertices per triangle
+// A mesh as host arrays.  The soup: three vertices per triangle, nvert = 3 ntri, faces empty (triangle t is vertices 3t, 3t + 1, 3t + 2).
+// The indexed mesh (include/kfx_mesh_index.h): the soup welded by lattice edge on the device, three vertex ids per triangle in faces.
 struct HostMesh {
-    std::vector<float> v, n, c;   // x y z, nx ny nz, r g b a
-    size_t ntri = 0;
-    bool color = false;
-};
-inline HostMesh Extract(const kfx_volume* vol, int cell, const kfx_slab* slab, int own_lo, int own_hi, const kfx_volume* colorvol)
-{
-    HostMesh m;
-    const size_t nbytes = kfx_mesh_scratch_bytes(vol, cell, slab, own_lo, own_hi);
-    if (!nbytes) GpuCheckStatus(kfx_mesh_plan(vol, cell, slab, own_lo, own_hi, nullptr, 0, nullptr, 0));   // the reason
-    void* scratch = DeviceBytes(nbytes);
-    unsigned long long totals[2] = {0, 0};
-    const int e = kfx_mesh_plan(vol, cell, slab, own_lo, own_hi, scratch, nbytes, totals, 0);
-    if (e) { kfx_free(scratch); GpuCheckStatus(e); }
-    const size_t na = totals[0], nv = 3 * totals[1];
-    m.ntri = totals[1];
-    m.color = colorvol != nullptr;
-    long long* dactive = (long long*)DeviceBytes(na * 8);
-    unsigned* doffsets = (unsigned*)DeviceBytes(na * 4);
-    float* dv = (float*)DeviceBytes(nv * 12);
-    float* dn = (float*)DeviceBytes(nv * 12);
-    float* dc = m.color ? (float*)DeviceBytes(nv * 16) : nullptr;
-    if (na) GpuCheckStatus(kfx_mesh_emit(vol, cell, slab, own_lo, own_hi, colorvol, scratch, nbytes, totals, dactive, doffsets, dv, dn, dc, 0));
-    m.v.resize(nv * 3); m.n.resize(nv * 3); m.c.resize(m.color ? nv * 4 : 0);
-    if (nv) {
-        GpuCheckStatus(kfx_memcpy_2d(m.v.data(), nv * 12, dv, nv * 12, nv * 12, 1, 2, 0));
-        GpuCheckStatus(kfx_memcpy_2d(m.n.data(), nv * 12, dn, nv * 12, nv * 12, 1, 2, 0));
-        if (m.color) GpuCheckStatus(kfx_memcpy_2d(m.c.data(), nv * 16, dc, nv * 16, nv * 16, 1, 2, 0));
-    }
-    kfx_free(scratch); kfx_free(dactive); kfx_free(doffsets); kfx_free(dv); kfx_free(dn);
-    if (dc) kfx_free(dc);
-    return m;
-}
-
-// binary little-endian PLY; returns the triangle count, 0 if the file cannot be written
-inline size_t WritePly(const std::string& path, const HostMesh& m)
-{
-    FILE* f = fopen(path.c_str(), "wb");
-    if (!f) return 0;
-    const size_t nv = 3 * m.ntri;
-    fprintf(f, "ply\nformat binary_little_endian 1.0\ncomment kangaroo_amd marching cubes\nelement vertex %zu\n", nv);
-    fprintf(f, "property float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz\n");
-    if (m.color) fprintf(f, "property float red\nproperty float green\nproperty float blue\nproperty float alpha\n");
-    fprintf(f, "element face %zu\nproperty list uchar uint vertex_indices\nend_header\n", m.ntri);
-    for (size_t i = 0; i < nv; ++i) {
-        fwrite(&m.v[i * 3], 4, 3, f);
-        fwrite(&m.n[i * 3], 4, 3, f);
-        if (m.color) fwrite(&m.c[i * 4], 4, 4, f);
-    }
-    for (size_t t = 0; t < m.ntri; ++t) {
-        const unsigned char k = 3;
-        const uint32_t idx[3] = {(uint32_t)(3 * t), (uint32_t)(3 * t + 1), (uint32_t)(3 * t + 2)};
-        fwrite(&k, 1, 1, f);
-        fwrite(idx, 4, 3, f);
-    }
-    fclose(f);
-    return m.ntri;
-}
-
-// The indexed mesh (include/kfx_mesh_index.h): the soup above welded by lattice edge on the device -- nvert vertices in v, n, c and
-// three vertex ids per triangle in faces.
-struct HostIndexedMesh {
     std::vector<float> v, n, c;   // x y z, nx ny nz, r g b a
     std::vector<uint32_t> faces;
     size_t ntri = 0, nvert = 0;
     bool color = false;
 };
-inline HostIndexedMesh ExtractIndexed(const kfx_volume* vol, int cell, const kfx_slab* slab, int own_lo, int own_hi, const kfx_volume* colorvol)
+
+// The mesh of `vol` (slab: its cubes [own_lo, own_hi) of the volume `slab` describes)
+inline HostMesh Extract(const kfx_volume* vol, int cell, const kfx_slab* slab, int own_lo, int own_hi, const kfx_volume* colorvol, bool indexed = false)
 {
-    HostIndexedMesh m;
     const size_t nbytes = kfx_mesh_scratch_bytes(vol, cell, slab, own_lo, own_hi);
     if (!nbytes) GpuCheckStatus(kfx_mesh_plan(vol, cell, slab, own_lo, own_hi, nullptr, 0, nullptr, 0));   // the reason
-    void* scratch = DeviceBytes(nbytes);
+    DeviceBuffer scratch(nbytes), xscratch, active, offsets, faces;
     unsigned long long totals[2] = {0, 0}, nvert = 0;
-    int e = kfx_mesh_plan(vol, cell, slab, own_lo, own_hi, scratch, nbytes, totals, 0);
-    if (e) { kfx_free(scratch); GpuCheckStatus(e); }
-    const size_t xbytes = kfx_mesh_index_scratch_bytes(vol, cell, slab, own_lo, own_hi, totals);
-    void* xscratch = DeviceBytes(xbytes);
-    e = kfx_mesh_index_plan(vol, cell, slab, own_lo, own_hi, scratch, nbytes, totals, xscratch, xbytes, &nvert, 0);
-    kfx_free(scratch);
-    if (e) { kfx_free(xscratch); GpuCheckStatus(e); }
-    const size_t nv = nvert, nf = 3 * totals[1];
+    GpuCheckStatus(kfx_mesh_plan(vol, cell, slab, own_lo, own_hi, scratch.get(), nbytes, totals, 0));
+    HostMesh m;
     m.ntri = totals[1];
-    m.nvert = nv;
+    m.nvert = 3 * m.ntri;
     m.color = colorvol != nullptr;
-    float* dv = (float*)DeviceBytes(nv * 12);
-    float* dn = (float*)DeviceBytes(nv * 12);
-    float* dc = m.color ? (float*)DeviceBytes(nv * 16) : nullptr;
-    unsigned* df = (unsigned*)DeviceBytes(nf * 4);
-    if (totals[0]) GpuCheckStatus(kfx_mesh_emit_indexed(vol, cell, slab, own_lo, own_hi, colorvol, xscratch, xbytes, totals, nvert, dv, dn, dc, df, 0));
-    m.v.resize(nv * 3); m.n.resize(nv * 3); m.c.resize(m.color ? nv * 4 : 0); m.faces.resize(nf);
-    if (nv) {
-        GpuCheckStatus(kfx_memcpy_2d(m.v.data(), nv * 12, dv, nv * 12, nv * 12, 1, 2, 0));
-        GpuCheckStatus(kfx_memcpy_2d(m.n.data(), nv * 12, dn, nv * 12, nv * 12, 1, 2, 0));
-        if (m.color) GpuCheckStatus(kfx_memcpy_2d(m.c.data(), nv * 16, dc, nv * 16, nv * 16, 1, 2, 0));
-        GpuCheckStatus(kfx_memcpy_2d(m.faces.data(), nf * 4, df, nf * 4, nf * 4, 1, 2, 0));
+    size_t xbytes = 0;
+    if (indexed) {
+        xbytes = kfx_mesh_index_scratch_bytes(vol, cell, slab, own_lo, own_hi, totals);
+        xscratch = DeviceBuffer(xbytes);
+        GpuCheckStatus(kfx_mesh_index_plan(vol, cell, slab, own_lo, own_hi, scratch.get(), nbytes, totals, xscratch.get(), xbytes, &nvert, 0));
+        scratch = DeviceBuffer();   // (the indexed emit reads the index scratch alone)
+        m.nvert = nvert;
+        m.faces.resize(3 * m.ntri);
+        faces = DeviceBuffer(m.faces.size() * 4);
+    } else {
+        active = DeviceBuffer(totals[0] * 8);
+        offsets = DeviceBuffer(totals[0] * 4);
     }
-    kfx_free(xscratch); kfx_free(dv); kfx_free(dn); kfx_free(df);
-    if (dc) kfx_free(dc);
+    const size_t nv = m.nvert;
+    DeviceBuffer dv(nv * 12), dn(nv * 12), dc;
+    if (m.color) dc = DeviceBuffer(nv * 16);
+    if (totals[0] && indexed)
+        GpuCheckStatus(kfx_mesh_emit_indexed(vol, cell, slab, own_lo, own_hi, colorvol, xscratch.get(), xbytes, totals, nvert, dv.get<float>(),
+                                             dn.get<float>(), dc.get<float>(), faces.get<unsigned>(), 0));
+    else if (totals[0])
+        GpuCheckStatus(kfx_mesh_emit(vol, cell, slab, own_lo, own_hi, colorvol, scratch.get(), nbytes, totals, active.get<long long>(),
+                                     offsets.get<unsigned>(), dv.get<float>(), dn.get<float>(), dc.get<float>(), 0));
+    m.v.resize(nv * 3); m.n.resize(nv * 3); m.c.resize(m.color ? nv * 4 : 0);
+    dv.CopyTo(m.v.data(), nv * 12);
+    dn.CopyTo(m.n.data(), nv * 12);
+    dc.CopyTo(m.c.data(), m.c.size() * 4);
+    faces.CopyTo(m.faces.data(), m.faces.size() * 4);
     return m;
 }
 
-// binary little-endian PLY of an indexed mesh: nvert vertex records, ntri faces; returns the triangle count, 0 if the file cannot be written
-inline size_t WritePly(const std::string& path, const HostIndexedMesh& m)
+// binary little-endian PLY: nvert vertex records, ntri faces; returns the triangle count, 0 if the file cannot be written
+inline size_t WritePly(const std::string& path, const HostMesh& m)
 {
     FILE* f = fopen(path.c_str(), "wb");
     if (!f) return 0;
@@ -158,46 +126,43 @@ inline size_t WritePly(const std::string& path, const HostIndexedMesh& m)
     }
     for (size_t t = 0; t < m.ntri; ++t) {
         const unsigned char k = 3;
+        const uint32_t soup[3] = {(uint32_t)(3 * t), (uint32_t)(3 * t + 1), (uint32_t)(3 * t + 2)};
         fwrite(&k, 1, 1, f);
-        fwrite(&m.faces[t * 3], 4, 3, f);
+        fwrite(m.faces.empty() ? soup : &m.faces[t * 3], 4, 3, f);
     }
     fclose(f);
     return m.ntri;
 }
+
+// SaveMesh / SaveMeshIndexed of a BoundedVolume<T>; a T without a Cell<T> does not compile
+template<typename T, typename Manage1, typename Manage2>
+inline size_t Save(const std::string& filename, BoundedVolume<T,TargetDevice,Manage1>& vol, BoundedVolume<float,TargetDevice,Manage2>* volColor, bool indexed, size_t* nvert)
+{
+    const bool color = volColor && volColor->IsValid();
+    const HostMesh m = Extract(vol.abi(), Cell<T>::kind, nullptr, 0, 0, color ? volColor->abi() : nullptr, indexed);
+    if (nvert) *nvert = m.nvert;
+    return WritePly(filename + ".ply", m);
+}
 }
 
-// Returns the number of triangles written.  T = SDF_t or SDF_h (half cells: the mesh of the widened volume).
+// SaveMesh(filename, vol[, volColor]): returns the number of triangles written.  T = SDF_t or SDF_h (half cells, config C5: the mesh
+// of the widened volume).
 template<typename T, typename Manage1, typename Manage2>
 inline size_t SaveMesh(std::string filename, BoundedVolume<T,TargetDevice,Manage1>& vol, BoundedVolume<float,TargetDevice,Manage2>* volColor)
 {
-    const bool color = volColor && volColor->IsValid();
-    const mesh_detail::HostMesh m = mesh_detail::Extract(vol.abi(), mesh_detail::Cell<T>::kind, nullptr, 0, 0, color ? volColor->abi() : nullptr);
-    return mesh_detail::WritePly(filename + ".ply", m);
+    return mesh_detail::Save(filename, vol, volColor, false, nullptr);
 }
 
-template<typename Manage>
-inline size_t SaveMesh(std::string filename, BoundedVolume<SDF_t,TargetDevice,Manage>& vol)
+template<typename T, typename Manage>
+inline size_t SaveMesh(std::string filename, BoundedVolume<T,TargetDevice,Manage>& vol)
 {
-    return SaveMesh<SDF_t,Manage,Manage>(filename, vol, nullptr);
+    return SaveMesh<T,Manage,Manage>(filename, vol, nullptr);
 }
 
-template<typename Manage1, typename Manage2>
-inline size_t SaveMesh(std::string filename, BoundedVolume<SDF_t,TargetDevice,Manage1>& vol, BoundedVolume<float,TargetDevice,Manage2>& volColor)
+template<typename T, typename Manage1, typename Manage2>
+inline size_t SaveMesh(std::string filename, BoundedVolume<T,TargetDevice,Manage1>& vol, BoundedVolume<float,TargetDevice,Manage2>& volColor)
 {
-    return SaveMesh<SDF_t,Manage1,Manage2>(filename, vol, &volColor);
-}
-
-// half cells (BoundedVolume<SDF_h>, config C5)
-template<typename Manage>
-inline size_t SaveMesh(std::string filename, BoundedVolume<SDF_h,TargetDevice,Manage>& vol)
-{
-    return SaveMesh<SDF_h,Manage,Manage>(filename, vol, nullptr);
-}
-
-template<typename Manage1, typename Manage2>
-inline size_t SaveMesh(std::string filename, BoundedVolume<SDF_h,TargetDevice,Manage1>& vol, BoundedVolume<float,TargetDevice,Manage2>& volColor)
-{
-    return SaveMesh<SDF_h,Manage1,Manage2>(filename, vol, &volColor);
+    return SaveMesh<T,Manage1,Manage2>(filename, vol, &volColor);
 }
 
 // SaveMeshIndexed(filename, vol[, volColor]): SaveMesh's mesh welded by lattice edge (include/kfx_mesh_index.h) -- the first-occurrence
@@ -206,34 +171,19 @@ inline size_t SaveMesh(std::string filename, BoundedVolume<SDF_h,TargetDevice,Ma
 template<typename T, typename Manage1, typename Manage2>
 inline size_t SaveMeshIndexed(std::string filename, BoundedVolume<T,TargetDevice,Manage1>& vol, BoundedVolume<float,TargetDevice,Manage2>* volColor, size_t* nvert = nullptr)
 {
-    const bool color = volColor && volColor->IsValid();
-    const mesh_detail::HostIndexedMesh m = mesh_detail::ExtractIndexed(vol.abi(), mesh_detail::Cell<T>::kind, nullptr, 0, 0, color ? volColor->abi() : nullptr);
-    if (nvert) *nvert = m.nvert;
-    return mesh_detail::WritePly(filename + ".ply", m);
+    return mesh_detail::Save(filename, vol, volColor, true, nvert);
 }
 
-template<typename Manage>
-inline size_t SaveMeshIndexed(std::string filename, BoundedVolume<SDF_t,TargetDevice,Manage>& vol, size_t* nvert = nullptr)
+template<typename T, typename Manage>
+inline size_t SaveMeshIndexed(std::string filename, BoundedVolume<T,TargetDevice,Manage>& vol, size_t* nvert = nullptr)
 {
-    return SaveMeshIndexed<SDF_t,Manage,Manage>(filename, vol, nullptr, nvert);
+    return SaveMeshIndexed<T,Manage,Manage>(filename, vol, nullptr, nvert);
 }
 
-template<typename Manage1, typename Manage2>
-inline size_t SaveMeshIndexed(std::string filename, BoundedVolume<SDF_t,TargetDevice,Manage1>& vol, BoundedVolume<float,TargetDevice,Manage2>& volColor, size_t* nvert = nullptr)
+template<typename T, typename Manage1, typename Manage2>
+inline size_t SaveMeshIndexed(std::string filename, BoundedVolume<T,TargetDevice,Manage1>& vol, BoundedVolume<float,TargetDevice,Manage2>& volColor, size_t* nvert = nullptr)
 {
-    return SaveMeshIndexed<SDF_t,Manage1,Manage2>(filename, vol, &volColor, nvert);
-}
-
-template<typename Manage>
-inline size_t SaveMeshIndexed(std::string filename, BoundedVolume<SDF_h,TargetDevice,Manage>& vol, size_t* nvert = nullptr)
-{
-    return SaveMeshIndexed<SDF_h,Manage,Manage>(filename, vol, nullptr, nvert);
-}
-
-template<typename Manage1, typename Manage2>
-inline size_t SaveMeshIndexed(std::string filename, BoundedVolume<SDF_h,TargetDevice,Manage1>& vol, BoundedVolume<float,TargetDevice,Manage2>& volColor, size_t* nvert = nullptr)
-{
-    return SaveMeshIndexed<SDF_h,Manage1,Manage2>(filename, vol, &volColor, nvert);
+    return SaveMeshIndexed<T,Manage1,Manage2>(filename, vol, &volColor, nvert);
 }
 
 }

@@ -180,26 +180,22 @@ public:
     // in emission order (include/kfx_mesh.h; the ghost planes must be current: Fuse leaves them so).  Writes filename + ".ply", with
     // the single-volume mesh's colours where the slab has a colour volume (as SaveMesh(filename, vol, volColor): when the whole colour
     // volume IsValid()); returns the triangle count.
-    size_t SaveMesh(std::string filename)
-    {
-        const kfx_slab s = {layout.full_d, layout.s0, layout.full_zmin, layout.full_zmax};
-        const bool with_color = color && local.w >= 8 && local.h >= 8 && layout.full_d >= 8;
-        const mesh_detail::HostMesh m = mesh_detail::Extract(local.abi(), KFX_CELL_F32, &s, (int)layout.z0, (int)layout.z1, with_color ? color->abi() : nullptr);
-        return mesh_detail::WritePly(filename + ".ply", m);
-    }
+    size_t SaveMesh(std::string filename) { return SaveRankMesh(filename, false, nullptr); }
 
     // SaveMesh's part of the mesh welded by lattice edge (include/kfx_mesh_index.h): the weld of this rank's triangles, so a vertex on a
     // slab boundary exists once per rank that uses it.  nvert, if given, receives the vertex count; returns the triangle count.
-    size_t SaveMeshIndexed(std::string filename, size_t* nvert = nullptr)
+    size_t SaveMeshIndexed(std::string filename, size_t* nvert = nullptr) { return SaveRankMesh(filename, true, nvert); }
+
+private:
+    size_t SaveRankMesh(const std::string& filename, bool indexed, size_t* nvert)
     {
         const kfx_slab s = {layout.full_d, layout.s0, layout.full_zmin, layout.full_zmax};
         const bool with_color = color && local.w >= 8 && local.h >= 8 && layout.full_d >= 8;
-        const mesh_detail::HostIndexedMesh m = mesh_detail::ExtractIndexed(local.abi(), KFX_CELL_F32, &s, (int)layout.z0, (int)layout.z1, with_color ? color->abi() : nullptr);
+        const mesh_detail::HostMesh m = mesh_detail::Extract(local.abi(), KFX_CELL_F32, &s, (int)layout.z0, (int)layout.z1, with_color ? color->abi() : nullptr, indexed);
         if (nvert) *nvert = m.nvert;
         return mesh_detail::WritePly(filename + ".ply", m);
     }
 
-private:
     static kfx_slab_layout MakeLayout(size_t d, const BoundingBox& bbox, kfx_comm* c, int ghost)
     {
         kfx_slab_layout L;

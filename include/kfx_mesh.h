@@ -1,6 +1,7 @@
-/* kfx_mesh.h -- planned mesh extraction: roo::SaveMesh's marching cubes (reference include/kangaroo/MarchingCubes.h) for fp32 and
- * half-cell volumes, whole or as one Z-slab of a partitioned volume, compacted on the device.  Same library (libkfx.so); kept out of
- * kfx.h, whose kfx_mc_count / kfx_mc_emit stay as they are.
+/* kfx_mesh.h -- mesh extraction as SaveMesh and ExtractMesh call it: roo::SaveMesh's marching cubes (reference
+ * include/kangaroo/MarchingCubes.h) for fp32 and half-cell volumes, whole or as one Z-slab of a partitioned volume, counted, scanned
+ * and compacted on the device.  Same library (libkfx.so) as kfx.h, whose kfx_mc_count / kfx_mc_emit (a byte per cube, compacted by
+ * the caller; fp32, whole volumes) stay beside it as the tests' independent comparator.
  *
  * Two calls.  kfx_mesh_plan counts the active cubes and triangles per SEGMENT (up to 64 consecutive cubes along z in one (x, y)
  * column) and scans the counts in the reference's emission order ((x*(h-1) + y)*(d-1) + z); it blocks until the totals are in host

@@ -6,18 +6,19 @@
 // colour volume) inside the loop nest of SaveMesh (:226-232: x outer, y, z inner, three fresh vertices per
 // triangle).  The reference does this on the host, one cube at a time, after copying the volume back.
 //
-// Here the volume never leaves HBM.  Two passes over the (w-1)(h-1)(d-1) cubes:
-//   k_mc_count  one thread per cube, x fastest (coalesced corner rows): number of triangles of the cube's case,
-//               written at the cube's position in the REFERENCE's emission order ((x*(h-1) + y)*(d-1) + z)
-//               through an LDS transpose (the order is z-fastest);
-//   (host side: exclusive prefix sum of the counts = every cube's output slot; the non-zero positions = the list
-//    of active cubes, already in emission order -- torch.cumsum / torch.nonzero, or a host loop in the C++ header)
-//   k_mc_emit   one thread per active cube: edge vertices, normals, colours, written to the cube's slots.  The
-//               vertex / normal / colour arithmetic keeps the reference's expressions (double division in
-//               fGetOffset, multiply-by-reciprocal normalisation), so the output arrays are bit-identical to the
-//               CPU oracle's and arrive in the reference's order.
-// kfx_mc_count / kfx_mc_emit keep that two-pass form; the planned extraction of include/kfx_mesh.h (below: segments counted and
-// scanned on the device, half cells, Z-slabs) replaces the host / torch compaction in SaveMesh and ExtractMesh.
+// Here the volume never leaves HBM.  The cubes are numbered in the REFERENCE's emission order, ci = (x*(h-1) + y)*(d-1) + z, and every
+// path ends in one thread per ACTIVE cube (a cube with triangles) whose vertex / normal / colour arithmetic keeps the reference's
+// expressions (double division in fGetOffset, multiply-by-reciprocal normalisation): the arrays are bit-identical to the CPU oracle's
+// and arrive in the reference's order.  Three paths, each on top of the one before:
+//   byte per cube (kfx.h: kfx_mc_count / kfx_mc_emit)   k_mc_count writes every cube's triangle count, the CALLER compacts (prefix sum,
+//               non-zero positions) and k_mc_emit writes three vertices per triangle.  fp32, whole volumes; kept as the independent
+//               comparator of the tests, and built from nothing the other two share but the corner read and k_mc_emit.
+//   soup (kfx_mesh.h: kfx_mesh_plan / kfx_mesh_emit)   what SaveMesh and ExtractMesh call: counts per SEGMENT of a column, scanned and
+//               compacted on the device, then k_mc_emit.  fp32 and half cells, whole volumes and Z-slabs.
+//   indexed (kfx_mesh_index.h: kfx_mesh_index_plan / kfx_mesh_emit_indexed)   the soup's plan, then its vertices welded by lattice edge:
+//               one vertex per edge and a face list, k_mc_emit_indexed.
+// What the emit kernels and the ownership pass share -- the cube's decode and corner read, the vertex's position, attributes and
+// store -- is defined once, so that the indexed mesh stays the weld of the soup bit for bit.
 // The case tables (mc_tables.inc) are derived by scripts/gen_mc_tables.py from the cube's topology; their boundary
 // loops and winding equal the classic tables' in all 256 cases (tests/test_mesh_cpu.py).
 #include "kfx_device.h"
@@ -159,6 +160,44 @@ __device__ __forceinline__ void edge_attributes(const MeshParams& p, const Color
     grey = (has_color && stored) ? trilinear<RayC32>(cv, pos) : 0.f;
 }
 
+__device__ __forceinline__ void cube_xyz(const MeshParams& p, long long ci, int& x, int& y, int& z)
+{
+    z = (int)(ci % p.cz);
+    y = (int)((ci / p.cz) % p.cy);
+    x = (int)(ci / ((long long)p.cz * p.cy));
+}
+
+// A listed cube as its thread sees it: position, case, triangle count, the mask of its edges with a vertex, corner values
+struct ActiveCube {
+    int x, y, z, flag, ntri;
+    unsigned mask;
+    float v[8];
+};
+
+// cube ci; false if it has no triangles or a corner that is not finite (a cube of a plan's list has neither).  For k_mc_emit_indexed
+// and k_mesh_own; k_mc_emit keeps the same steps in locals.
+template <typename CELL>
+__device__ __forceinline__ bool active_cube(const MeshParams& p, long long ci, ActiveCube& c)
+{
+    cube_xyz(p, ci, c.x, c.y, c.z);
+    const bool finite = cube_case<CELL>(p, c.x, c.y, c.z, c.v, c.flag);
+    c.ntri = c_num_tris[c.flag];
+    c.mask = c_edge_mask[c.flag];
+    return finite && c.ntri != 0;
+}
+
+// vertex i of the output: position, normal and, with a colour volume, the grey C as ConvertPixel<float3,float>(c) = (c,c,c) in
+// aiColor4D(c, c, c, 1)
+__device__ __forceinline__ void store_vertex(float* verts, float* norms, float* colors, size_t i,
+                                             const V3& P, const V3& N, float C, int has_color)
+{
+    verts[i * 3 + 0] = P.x; verts[i * 3 + 1] = P.y; verts[i * 3 + 2] = P.z;
+    norms[i * 3 + 0] = N.x; norms[i * 3 + 1] = N.y; norms[i * 3 + 2] = N.z;
+    if (has_color) {
+        colors[i * 4 + 0] = C; colors[i * 4 + 1] = C; colors[i * 4 + 2] = C; colors[i * 4 + 3] = 1.0f;
+    }
+}
+
 // One thread per ACTIVE cube (cube_index lists the cubes with triangles in emission order; tri_offset their first
 // triangle): dense lanes instead of the ~1 % active lanes of a thread-per-cube sweep.  CELL: fp32 or half cells; SLAB: p holds
 // the full volume's geometry over a slab's planes [avail_lo, avail_hi) (virtual base pointer, slab_full_volume), and so does cv for
@@ -171,12 +210,11 @@ __global__ __launch_bounds__(128) void k_mc_emit(const MeshParams p, const Color
 {
     const long long t_id = (long long)blockIdx.x * 128 + threadIdx.x;
     if (t_id >= n_active) return;
-    const long long ci = cube_index[t_id];
-    const int z = (int)(ci % p.cz);
-    const int y = (int)((ci / p.cz) % p.cy);
-    const int x = (int)(ci / ((long long)p.cz * p.cy));
+    // active_cube's steps in locals: through the struct this kernel -- 36 per-edge values live -- compiles to other code, which
+    // measured 1 % slower at 1024^3 (profiles/mesh_refactor/ab_timing.txt)
+    int x, y, z, flag;
+    cube_xyz(p, cube_index[t_id], x, y, z);
     float v[8];
-    int flag;
     if (!cube_case<CELL>(p, x, y, z, v, flag)) return;
     const int ntri = c_num_tris[flag];
     if (ntri == 0) return;
@@ -196,13 +234,9 @@ __global__ __launch_bounds__(128) void k_mc_emit(const MeshParams p, const Color
         V3 P = v3(0.f, 0.f, 0.f), N = P;
         float C = 0.f;
 #pragma unroll
-        for (int k = 0; k < 12; ++k)   // select without dynamic register indexing
-            if (k == e) { P = ev[k]; N = en[k]; C = ec[k]; }
-        verts[o * 3 + 0] = P.x; verts[o * 3 + 1] = P.y; verts[o * 3 + 2] = P.z;
-        norms[o * 3 + 0] = N.x; norms[o * 3 + 1] = N.y; norms[o * 3 + 2] = N.z;
-        if (has_color) { // ConvertPixel<float3,float>(c) = (c,c,c); aiColor4D(c, c, c, 1)
-            colors[o * 4 + 0] = C; colors[o * 4 + 1] = C; colors[o * 4 + 2] = C; colors[o * 4 + 3] = 1.0f;
-        }
+        for (int k = 0; k < 12; ++k)   // select without dynamic register indexing (one loop for the three arrays: a shared
+            if (k == e) { P = ev[k]; N = en[k]; C = ec[k]; }   // per-array select measured slower here, same file)
+        store_vertex(verts, norms, colors, o, P, N, C, has_color);
     }
 }
 
@@ -234,11 +268,11 @@ static int color_params(ColorGeom& cv, int& has_color, const kfx_volume* colorvo
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// Planned extraction (include/kfx_mesh.h): the per-cube byte array and the host / torch compaction replaced by four passes
-// over SEGMENTS -- runs of up to MESH_SEG consecutive cubes along z in one (x, y) column, numbered in emission order
+// The soup (include/kfx_mesh.h): no array per cube and no compaction by the caller, but four passes over SEGMENTS -- runs of up
+// to MESH_SEG consecutive cubes along z in one (x, y) column, numbered in emission order
 // s = (x*cy + y)*nsz + k (x outer, z inner: a segment's cubes are consecutive in the reference's order):
 //   k_mesh_count     one lane per segment, lanes of a wave on x-adjacent columns (coalesced corner rows); the lane walks z and
-//                    keeps plane z+1's corner pairs as the next cube's plane z.  Writes (active cubes << 9 | triangles), 16 bits.
+//                    keeps plane z+1's corner pairs as the next cube's plane z.  Writes seg_pack(active cubes, triangles), 16 bits.
 //   k_mesh_reduce    sums of MESH_BLOCK consecutive segments (the scan's upsweep)
 //   k_mesh_scan_partials  one workgroup: exclusive 64-bit scan of the block sums, and the totals
 //   k_mesh_compact   the downsweep inside each block (LDS), then one lane per ACTIVE segment re-walks its cubes and writes the
@@ -260,7 +294,10 @@ struct MeshRange {
     long long nblk;    // ceil(nseg / MESH_BLOCK)
 };
 
+// a segment's count, 16 bits: active cubes (<= MESH_SEG) above 9 bits of triangles (<= 5 MESH_SEG)
 __device__ __forceinline__ unsigned seg_pack(unsigned active, unsigned tris) { return (active << 9) | tris; }
+__device__ __forceinline__ unsigned seg_active(unsigned n) { return n >> 9; }
+__device__ __forceinline__ unsigned seg_tris(unsigned n) { return n & 511u; }
 
 // The cubes [za, zb) of column (x, y) from the bottom up, plane z + 1's corner pairs kept as the next cube's plane z: each(z, n)
 // gets every cube's plane and triangle count.  Plan and emit both walk with this, so they agree on which cubes are active.
@@ -345,17 +382,11 @@ __device__ __forceinline__ T block_exclusive_scan(T v, T* lds, T* total)
     return base + inc - v;
 }
 
-// sums of MESH_BLOCK consecutive segments: part[2 b] = active cubes, part[2 b + 1] = triangles
-__global__ __launch_bounds__(256) void k_mesh_reduce(const unsigned short* __restrict__ seg, const MeshRange r, unsigned* __restrict__ part)
+// the sums of a pair of counters over a workgroup of 256 threads, one value of each per thread: part[2 b] = sum of a,
+// part[2 b + 1] = sum of t for workgroup b (written by its thread 0)
+__device__ __forceinline__ void store_block_sums(unsigned a, unsigned t, unsigned* __restrict__ part)
 {
     __shared__ unsigned lds[2][4];
-    const long long s0 = (long long)blockIdx.x * MESH_BLOCK + (long long)threadIdx.x * MESH_PER_THREAD;
-    unsigned a = 0, t = 0;
-    for (int j = 0; j < MESH_PER_THREAD; ++j) {
-        const unsigned n = s0 + j < r.nseg ? seg[s0 + j] : 0u;
-        a += n >> 9;
-        t += n & 511u;
-    }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         a += __shfl_xor(a, o, 64);
@@ -368,6 +399,19 @@ __global__ __launch_bounds__(256) void k_mesh_reduce(const unsigned short* __res
         part[2 * (size_t)blockIdx.x] = lds[0][0] + lds[0][1] + lds[0][2] + lds[0][3];
         part[2 * (size_t)blockIdx.x + 1] = lds[1][0] + lds[1][1] + lds[1][2] + lds[1][3];
     }
+}
+
+// sums of MESH_BLOCK consecutive segments: part[2 b] = active cubes, part[2 b + 1] = triangles
+__global__ __launch_bounds__(256) void k_mesh_reduce(const unsigned short* __restrict__ seg, const MeshRange r, unsigned* __restrict__ part)
+{
+    const long long s0 = (long long)blockIdx.x * MESH_BLOCK + (long long)threadIdx.x * MESH_PER_THREAD;
+    unsigned a = 0, t = 0;
+    for (int j = 0; j < MESH_PER_THREAD; ++j) {
+        const unsigned n = s0 + j < r.nseg ? seg[s0 + j] : 0u;
+        a += seg_active(n);
+        t += seg_tris(n);
+    }
+    store_block_sums(a, t, part);
 }
 
 // one workgroup: exclusive 64-bit offsets of the blocks (base[2 b] cubes, base[2 b + 1] triangles) and the totals
@@ -428,8 +472,8 @@ __global__ __launch_bounds__(256) void k_mesh_compact(const MeshParams p, const 
     for (int j = 0; j < MESH_PER_THREAD; ++j) {
         const unsigned short n = blk0 + j0 + j < r.nseg ? seg[blk0 + j0 + j] : (unsigned short)0;
         cnt[j0 + j] = n;
-        sa += n >> 9;
-        st += n & 511u;
+        sa += seg_active(n);
+        st += seg_tris(n);
     }
     unsigned ta, tt;
     unsigned ea = block_exclusive_scan<unsigned, 4>(sa, lds[0], &ta);
@@ -437,8 +481,8 @@ __global__ __launch_bounds__(256) void k_mesh_compact(const MeshParams p, const 
     for (int j = 0; j < MESH_PER_THREAD; ++j) {
         off_a[j0 + j] = ea;
         off_t[j0 + j] = et;
-        ea += cnt[j0 + j] >> 9;
-        et += cnt[j0 + j] & 511u;
+        ea += seg_active(cnt[j0 + j]);
+        et += seg_tris(cnt[j0 + j]);
     }
     __syncthreads();
     const unsigned long long ba = base[2 * (size_t)blockIdx.x], bt = base[2 * (size_t)blockIdx.x + 1];
@@ -504,7 +548,18 @@ static int mesh_setup(MeshParams& p, MeshRange& r, const kfx_volume* vol, int ce
     return 0;
 }
 
-static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+// A caller's scratch handed out front to back, every sub-buffer on a 256-byte boundary of it; `bytes` is what has been taken.
+// (An integer address: a layout is also carved from a null scratch, for its size alone.)
+struct Carver {
+    uintptr_t scratch;
+    size_t bytes = 0;
+    template <typename T> T* take(size_t count)
+    {
+        T* const at = (T*)(scratch + bytes);
+        bytes += (count * sizeof(T) + 255) & ~(size_t)255;
+        return at;
+    }
+};
 
 // scratch: [header: totals][segment counts, 2 B, nblk * MESH_BLOCK][block sums, 8 B per block][block offsets, 16 B per block]
 struct MeshScratch {
@@ -514,16 +569,15 @@ struct MeshScratch {
     unsigned long long* base;
     size_t bytes;
 };
-static MeshScratch mesh_scratch(const MeshRange& r, void* scratch)
+static MeshScratch mesh_scratch(const MeshRange& r, const void* scratch)
 {
+    Carver c{(uintptr_t)scratch};
     MeshScratch s;
-    unsigned char* b = (unsigned char*)scratch;
-    size_t o = 0;
-    s.totals = (unsigned long long*)(b + o); o += MESH_HEADER;
-    s.seg = (unsigned short*)(b + o); o += align256((size_t)r.nblk * MESH_BLOCK * 2);
-    s.part = (unsigned*)(b + o); o += align256((size_t)r.nblk * 8);
-    s.base = (unsigned long long*)(b + o); o += align256((size_t)r.nblk * 16);
-    s.bytes = o;
+    s.totals = c.take<unsigned long long>(MESH_HEADER / 8);
+    s.seg = c.take<unsigned short>((size_t)r.nblk * MESH_BLOCK);
+    s.part = c.take<unsigned>((size_t)r.nblk * 2);
+    s.base = c.take<unsigned long long>((size_t)r.nblk * 2);
+    s.bytes = c.bytes;
     return s;
 }
 
@@ -601,13 +655,6 @@ __device__ __forceinline__ unsigned long long edge_ranks(int flag, unsigned own)
 }
 __device__ __forceinline__ unsigned rank_of(unsigned long long ranks, int e) { return (unsigned)(ranks >> (4 * e)) & 15u; }
 
-__device__ __forceinline__ void cube_xyz(const MeshParams& p, long long ci, int& x, int& y, int& z)
-{
-    z = (int)(ci % p.cz);
-    y = (int)((ci / p.cz) % p.cy);
-    x = (int)(ci / ((long long)p.cz * p.cy));
-}
-
 // info[t] = flag | owned edges << 8; part[2 b] = vertices, part[2 b + 1] = triangles of block b's cubes.  hdr[2], hdr[3]: the totals
 // this index was planned for (hdr[0], hdr[1] are the scan's: vertices, triangles).
 template <typename CELL>
@@ -615,42 +662,26 @@ __global__ __launch_bounds__(MESH_IDX_BLOCK) void k_mesh_own(const MeshParams p,
                                                              const unsigned long long n_tris, unsigned* __restrict__ info,
                                                              unsigned* __restrict__ part, unsigned long long* __restrict__ hdr)
 {
-    __shared__ unsigned lds[2][MESH_IDX_BLOCK / 64];
+    static_assert(MESH_IDX_BLOCK == 256, "store_block_sums");
     const long long t = (long long)blockIdx.x * MESH_IDX_BLOCK + threadIdx.x;
     unsigned nv = 0, nt = 0;
     if (t < n_active) {
         const long long ci = cube_index[t];
-        int x, y, z, flag;
-        cube_xyz(p, ci, x, y, z);
-        float v[8];
-        cube_case<CELL>(p, x, y, z, v, flag);
-        const unsigned mask = c_edge_mask[flag];
+        ActiveCube c;
+        active_cube<CELL>(p, ci, c);   // (listed by the plan: it is active)
         unsigned own = 0;
 #pragma unroll
         for (int e = 0; e < 12; ++e) {
-            if (!(mask & (1u << e))) continue;
+            if (!(c.mask & (1u << e))) continue;
             int oe;
-            if (edge_owner(p, cube_index, t, ci, x, y, z, e, oe) == t) own |= 1u << e;
+            if (edge_owner(p, cube_index, t, ci, c.x, c.y, c.z, e, oe) == t) own |= 1u << e;
         }
-        info[t] = (unsigned)flag | (own << 8);
+        info[t] = (unsigned)c.flag | (own << 8);
         nv = __popc(own);
-        nt = c_num_tris[flag];
+        nt = c.ntri;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        nv += __shfl_xor(nv, o, 64);
-        nt += __shfl_xor(nt, o, 64);
-    }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) { lds[0][wv] = nv; lds[1][wv] = nt; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned sv = 0, st = 0;
-        for (int i = 0; i < MESH_IDX_BLOCK / 64; ++i) { sv += lds[0][i]; st += lds[1][i]; }
-        part[2 * (size_t)blockIdx.x] = sv;
-        part[2 * (size_t)blockIdx.x + 1] = st;
-        if (blockIdx.x == 0) { hdr[2] = (unsigned long long)n_active; hdr[3] = n_tris; }
-    }
+    store_block_sums(nv, nt, part);
+    if (threadIdx.x == 0 && blockIdx.x == 0) { hdr[2] = (unsigned long long)n_active; hdr[3] = n_tris; }
 }
 
 __global__ __launch_bounds__(MESH_IDX_BLOCK) void k_mesh_vertex_base(const unsigned* __restrict__ info, const long long n_active,
@@ -675,44 +706,35 @@ __global__ __launch_bounds__(128) void k_mc_emit_indexed(const MeshParams p, con
     const long long t_id = (long long)blockIdx.x * 128 + threadIdx.x;
     if (t_id >= n_active) return;
     const long long ci = cube_index[t_id];
-    int x, y, z, flag;
-    cube_xyz(p, ci, x, y, z);
-    float v[8];
-    if (!cube_case<CELL>(p, x, y, z, v, flag)) return;
-    const int ntri = c_num_tris[flag];
-    if (ntri == 0) return;
-    const unsigned mask = c_edge_mask[flag];
+    ActiveCube c;
+    if (!active_cube<CELL>(p, ci, c)) return;
     const unsigned own = info[t_id] >> 8, first = vbase[t_id];
-    const unsigned long long ranks = edge_ranks(flag, own);
-    const V3 p0 = cube_origin(p, x, y, z);
+    const unsigned long long ranks = edge_ranks(c.flag, own);
+    const V3 p0 = cube_origin(p, c.x, c.y, c.z);
     unsigned id[12];
 #pragma unroll
     for (int e = 0; e < 12; ++e) {
         id[e] = 0;
-        if (!(mask & (1u << e))) continue;
+        if (!(c.mask & (1u << e))) continue;
         if (own & (1u << e)) {
             const size_t i = first + rank_of(ranks, e);
             id[e] = (unsigned)i;
             if (i >= n_verts) continue;
-            const V3 pos = edge_position(p, p0, v, e);
+            const V3 pos = edge_position(p, p0, c.v, e);
             V3 n;
-            float c;
-            edge_attributes<CELL, SLAB>(p, cv, has_color, pos, n, c);
-            verts[i * 3 + 0] = pos.x; verts[i * 3 + 1] = pos.y; verts[i * 3 + 2] = pos.z;
-            norms[i * 3 + 0] = n.x; norms[i * 3 + 1] = n.y; norms[i * 3 + 2] = n.z;
-            if (has_color) { // as k_mc_emit
-                colors[i * 4 + 0] = c; colors[i * 4 + 1] = c; colors[i * 4 + 2] = c; colors[i * 4 + 3] = 1.0f;
-            }
+            float grey;
+            edge_attributes<CELL, SLAB>(p, cv, has_color, pos, n, grey);
+            store_vertex(verts, norms, colors, i, pos, n, grey, has_color);
         } else {
             int oe;
-            const long long j = edge_owner(p, cube_index, t_id, ci, x, y, z, e, oe);
+            const long long j = edge_owner(p, cube_index, t_id, ci, c.x, c.y, c.z, e, oe);
             const unsigned oi = info[j];
             id[e] = vbase[j] + rank_of(edge_ranks((int)(oi & 255u), oi >> 8), oe);
         }
     }
     size_t o = (size_t)tri_offset[t_id] * 3; // first face corner of this cube
-    for (int t = 0; t < ntri * 3; ++t, ++o) {
-        const int e = c_tris[flag][t];
+    for (int t = 0; t < c.ntri * 3; ++t, ++o) {
+        const int e = c_tris[c.flag][t];
         unsigned I = 0;
 #pragma unroll
         for (int k = 0; k < 12; ++k)   // select without dynamic register indexing
@@ -731,26 +753,25 @@ struct MeshIndexScratch {
     long long nblk;
     size_t bytes;
 };
-static MeshIndexScratch mesh_index_scratch(unsigned long long n_active, void* scratch)
+static MeshIndexScratch mesh_index_scratch(unsigned long long n_active, const void* scratch)
 {
+    Carver c{(uintptr_t)scratch};
     MeshIndexScratch s;
-    unsigned char* b = (unsigned char*)scratch;
-    size_t o = 0;
     s.nblk = (long long)((n_active + MESH_IDX_BLOCK - 1) / MESH_IDX_BLOCK);
-    s.hdr = (unsigned long long*)(b + o); o += MESH_HEADER;
-    s.cube_index = (long long*)(b + o); o += align256((size_t)n_active * 8);
-    s.tri_offset = (unsigned*)(b + o); o += align256((size_t)n_active * 4);
-    s.info = (unsigned*)(b + o); o += align256((size_t)n_active * 4);
-    s.vbase = (unsigned*)(b + o); o += align256((size_t)n_active * 4);
-    s.part = (unsigned*)(b + o); o += align256((size_t)s.nblk * 8);
-    s.base = (unsigned long long*)(b + o); o += align256((size_t)s.nblk * 16);
-    s.bytes = o;
+    s.hdr = c.take<unsigned long long>(MESH_HEADER / 8);
+    s.cube_index = c.take<long long>((size_t)n_active);
+    s.tri_offset = c.take<unsigned>((size_t)n_active);
+    s.info = c.take<unsigned>((size_t)n_active);
+    s.vbase = c.take<unsigned>((size_t)n_active);
+    s.part = c.take<unsigned>((size_t)s.nblk * 2);
+    s.base = c.take<unsigned long long>((size_t)s.nblk * 2);
+    s.bytes = c.bytes;
     return s;
 }
 
 static bool totals_in_range(const unsigned long long totals[2]) { return totals[1] < MESH_MAX_TRIS && totals[0] <= totals[1]; }
 
-// the colour volume of a planned emit (kfx_mesh.h: colorvol)
+// the colour volume of a soup or indexed emit (kfx_mesh.h: colorvol)
 static int mesh_color_params(ColorGeom& cv, int& has_color, const kfx_volume* vol, int cell, const kfx_slab* slab, const kfx_volume* colorvol,
                              const float* colors)
 {
@@ -775,6 +796,57 @@ static int read_header(unsigned long long* host, const unsigned long long* dev, 
     hipError_t e = hipMemcpyAsync(host, dev, (size_t)n * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     return e == hipSuccess ? 0 : set_error((int)e, hipGetErrorString(e));
+}
+
+// "The totals are the plan's": the first n words of a scratch's header are those the caller's totals stand for.  The kernels trust
+// the lists planned in that scratch to fit the buffers the caller sized from its totals.
+static int check_planned(const unsigned long long* hdr, const unsigned long long* want, int n, const char* what, hipStream_t st)
+{
+    unsigned long long planned[4];
+    if (int e = read_header(planned, hdr, n, st)) return e;
+    if (memcmp(planned, want, (size_t)n * 8) != 0) return fail_rule(what, KFX_E_RANGE, "totals are not the plan's");
+    return 0;
+}
+
+// How the entry points of kfx_mesh.h and kfx_mesh_index.h open: the geometry, the meshed range and the carved scratches of a call
+// that `takes` a plan's scratch, an index scratch (sizing: null, SIZE_MAX bytes), totals of the caller's.  The checks come in one
+// order, which the code of a refusal depends on: the volume and the slab (mesh_setup); the entry point's pointers (`any_null`); with
+// an index scratch, whose layout they decide, the totals' range (and n_verts <= 3 triangles); the scratches' alignment; their sizes;
+// without an index scratch, the totals' range.
+enum { MESH_PLAN_SCRATCH = 1, MESH_INDEX_SCRATCH = 2, MESH_TOTALS = 4 };
+struct MeshCall {
+    MeshParams p;
+    MeshRange r;
+    MeshScratch s;        // with MESH_PLAN_SCRATCH
+    MeshIndexScratch x;   // with MESH_INDEX_SCRATCH
+};
+static int mesh_call(MeshCall& c, const char* what, int takes, const kfx_volume* vol, int cell, const kfx_slab* slab, int own_lo, int own_hi,
+                     bool any_null, const void* scratch, size_t scratch_bytes, const void* index_scratch, size_t index_scratch_bytes,
+                     const unsigned long long* totals, unsigned long long n_verts = 0)
+{
+    if (int e = mesh_setup(c.p, c.r, vol, cell, slab, own_lo, own_hi)) return e;
+    if (any_null) return fail_rule(what, KFX_E_NULL, "null scratch, totals or count");
+    const bool plan = takes & MESH_PLAN_SCRATCH, index = takes & MESH_INDEX_SCRATCH;
+    if (index && (!totals_in_range(totals) || n_verts > 3 * totals[1])) return fail_rule(what, KFX_E_RANGE, "totals out of range");
+    if (((plan ? (uintptr_t)scratch : 0) | (index ? (uintptr_t)index_scratch : 0)) & 255)
+        return fail_rule(what, KFX_E_ALIGN, "scratch not 256-byte aligned");
+    if (plan) c.s = mesh_scratch(c.r, scratch);
+    if (index) c.x = mesh_index_scratch(totals[0], index_scratch);
+    if (plan && scratch_bytes < c.s.bytes) return fail_rule(what, KFX_E_SHAPE, "scratch smaller than kfx_mesh_scratch_bytes");
+    if (index && index_scratch_bytes < c.x.bytes) return fail_rule(what, KFX_E_SHAPE, "index scratch smaller than kfx_mesh_index_scratch_bytes");
+    if (!index && (takes & MESH_TOTALS) && !totals_in_range(totals)) return fail_rule(what, KFX_E_RANGE, "totals out of range");
+    return 0;
+}
+
+// One call of f with the tag of a (cell, slab) pair: the template arguments of the kernels
+template <typename CELL_, bool SLAB_> struct MeshKind { using CELL = CELL_; static constexpr bool SLAB = SLAB_; };
+template <typename F>
+static void for_mesh_kind(int cell, bool slab, F f)
+{
+    if (cell == KFX_CELL_F32 && slab) f(MeshKind<RayF32, true>{});
+    else if (cell == KFX_CELL_F32) f(MeshKind<RayF32, false>{});
+    else if (slab) f(MeshKind<RayF16, true>{});
+    else f(MeshKind<RayF16, false>{});
 }
 
 } // namespace kfx
@@ -819,67 +891,45 @@ extern "C" size_t kfx_mesh_scratch_bytes(const kfx_volume* vol, int cell, const 
     return mesh_scratch(r, nullptr).bytes;
 }
 
-template <typename CELL>
-static void mesh_plan_launch(const MeshParams& p, const MeshRange& r, const MeshScratch& s, hipStream_t st)
-{
-    dim3 grid(ceil_div(p.cx, 64), p.cy, ceil_div(r.nsz, MESH_SEG_TILE));
-    hipLaunchKernelGGL(k_mesh_count<CELL>, grid, dim3(256), 0, st, p, r, s.seg);
-    hipLaunchKernelGGL(k_mesh_reduce, dim3((unsigned)r.nblk), dim3(256), 0, st, s.seg, r, s.part);
-    hipLaunchKernelGGL(k_mesh_scan_partials, dim3(1), dim3(MESH_SCAN_THREADS), 0, st, s.part, r.nblk, s.base, s.totals);
-}
-
 extern "C" int kfx_mesh_plan(const kfx_volume* vol, int cell, const kfx_slab* slab, int own_lo, int own_hi, void* scratch,
                              size_t scratch_bytes, unsigned long long totals[2], kfx_stream stream)
 {
-    MeshParams p;
-    MeshRange r;
-    if (int e = mesh_setup(p, r, vol, cell, slab, own_lo, own_hi)) return e;
-    if (!scratch || !totals) return set_error(KFX_E_NULL, "kfx_mesh_plan: null scratch or totals");
-    if ((uintptr_t)scratch & 255) return set_error(KFX_E_ALIGN, "kfx_mesh_plan: scratch not 256-byte aligned");
-    const MeshScratch s = mesh_scratch(r, scratch);
-    if (scratch_bytes < s.bytes) return set_error(KFX_E_SHAPE, "kfx_mesh_plan: scratch smaller than kfx_mesh_scratch_bytes");
+    MeshCall c;
+    if (int e = mesh_call(c, "kfx_mesh_plan", MESH_PLAN_SCRATCH, vol, cell, slab, own_lo, own_hi, !scratch || !totals, scratch, scratch_bytes,
+                          nullptr, 0, nullptr))
+        return e;
+    const MeshParams& p = c.p;
+    const MeshRange& r = c.r;
+    const MeshScratch& s = c.s;
     if (r.nblk > 0x7fffffffLL) return set_error(KFX_E_RANGE, "kfx_mesh_plan: volume too large");
     totals[0] = totals[1] = 0;
     if (r.nseg == 0) return 0;
     if (int e = load_tables()) return e;
     const hipStream_t st = (hipStream_t)stream;
-    if (cell == KFX_CELL_F32) mesh_plan_launch<RayF32>(p, r, s, st);
-    else mesh_plan_launch<RayF16>(p, r, s, st);
+    for_mesh_kind(cell, false, [&](auto kind) {   // (the plan's kernels see a slab through p and r alone)
+        using CELL = typename decltype(kind)::CELL;
+        dim3 grid(ceil_div(p.cx, 64), p.cy, ceil_div(r.nsz, MESH_SEG_TILE));
+        hipLaunchKernelGGL(k_mesh_count<CELL>, grid, dim3(256), 0, st, p, r, s.seg);
+        hipLaunchKernelGGL(k_mesh_reduce, dim3((unsigned)r.nblk), dim3(256), 0, st, s.seg, r, s.part);
+        hipLaunchKernelGGL(k_mesh_scan_partials, dim3(1), dim3(MESH_SCAN_THREADS), 0, st, s.part, r.nblk, s.base, s.totals);
+    });
     if (int e = check_launch("kfx_mesh_plan")) return e;
     unsigned long long host[2];
-    hipError_t e = hipMemcpyAsync(host, s.totals, sizeof(host), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return set_error((int)e, hipGetErrorString(e));
+    if (int e = read_header(host, s.totals, 2, st)) return e;
     totals[0] = host[0];
     totals[1] = host[1];
-    if (host[1] >= MESH_MAX_TRIS) return set_error(KFX_E_RANGE, "kfx_mesh_plan: 2^32/3 triangles or more (32-bit vertex offsets)");
+    if (totals[1] >= MESH_MAX_TRIS) return set_error(KFX_E_RANGE, "kfx_mesh_plan: 2^32/3 triangles or more (32-bit vertex offsets)");
     return 0;
-}
-
-template <typename CELL, bool SLAB>
-static void mesh_emit_launch(const MeshParams& p, const MeshRange& r, const MeshScratch& s, const ColorGeom& cv, int has_color,
-                             const unsigned long long totals[2], long long* cube_index, unsigned* tri_offset, float* verts,
-                             float* norms, float* colors, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_mesh_compact<CELL>, dim3((unsigned)r.nblk), dim3(256), 0, st, p, r, s.seg, s.base, cube_index, tri_offset,
-                       totals[0], totals[1]);
-    const long long n_active = (long long)totals[0];
-    hipLaunchKernelGGL((k_mc_emit<CELL, SLAB>), dim3((unsigned)((n_active + 127) / 128)), dim3(128), 0, st, p, cv, has_color,
-                       cube_index, tri_offset, n_active, verts, norms, colors);
 }
 
 extern "C" int kfx_mesh_emit(const kfx_volume* vol, int cell, const kfx_slab* slab, int own_lo, int own_hi, const kfx_volume* colorvol,
                              const void* scratch, size_t scratch_bytes, const unsigned long long totals[2], long long* cube_index,
                              unsigned* tri_offset, float* verts, float* norms, float* colors, kfx_stream stream)
 {
-    MeshParams p;
-    MeshRange r;
-    if (int e = mesh_setup(p, r, vol, cell, slab, own_lo, own_hi)) return e;
-    if (!scratch || !totals) return set_error(KFX_E_NULL, "kfx_mesh_emit: null scratch or totals");
-    if ((uintptr_t)scratch & 255) return set_error(KFX_E_ALIGN, "kfx_mesh_emit: scratch not 256-byte aligned");
-    const MeshScratch s = mesh_scratch(r, (void*)scratch);
-    if (scratch_bytes < s.bytes) return set_error(KFX_E_SHAPE, "kfx_mesh_emit: scratch smaller than kfx_mesh_scratch_bytes");
-    if (totals[1] >= MESH_MAX_TRIS || totals[0] > totals[1]) return set_error(KFX_E_RANGE, "kfx_mesh_emit: totals out of range");
+    MeshCall c;
+    if (int e = mesh_call(c, "kfx_mesh_emit", MESH_PLAN_SCRATCH | MESH_TOTALS, vol, cell, slab, own_lo, own_hi, !scratch || !totals, scratch,
+                          scratch_bytes, nullptr, 0, totals))
+        return e;
     if (totals[0] == 0) return 0;
     if (!cube_index || !tri_offset || !verts || !norms) return set_error(KFX_E_NULL, "kfx_mesh_emit: null output");
     if ((((uintptr_t)cube_index) & 7) || (((uintptr_t)tri_offset | (uintptr_t)verts | (uintptr_t)norms | (uintptr_t)colors) & 3))
@@ -889,17 +939,18 @@ extern "C" int kfx_mesh_emit(const kfx_volume* vol, int cell, const kfx_slab* sl
     if (int e = mesh_color_params(cv, has_color, vol, cell, slab, colorvol, colors)) return e;
     if (int e = load_tables()) return e;
     const hipStream_t st = (hipStream_t)stream;
-    // the totals must be this scratch's plan's: the emit kernel trusts the compacted lists to fit the caller's buffers
-    unsigned long long planned[2];
-    if (int e = read_header(planned, s.totals, 2, st)) return e;
-    if (planned[0] != totals[0] || planned[1] != totals[1]) return set_error(KFX_E_RANGE, "kfx_mesh_emit: totals are not the plan's");
-    if (cell == KFX_CELL_F32) {
-        if (slab) mesh_emit_launch<RayF32, true>(p, r, s, cv, has_color, totals, cube_index, tri_offset, verts, norms, has_color ? colors : nullptr, st);
-        else mesh_emit_launch<RayF32, false>(p, r, s, cv, has_color, totals, cube_index, tri_offset, verts, norms, colors, st);
-    } else {
-        if (slab) mesh_emit_launch<RayF16, true>(p, r, s, cv, 0, totals, cube_index, tri_offset, verts, norms, nullptr, st);
-        else mesh_emit_launch<RayF16, false>(p, r, s, cv, has_color, totals, cube_index, tri_offset, verts, norms, colors, st);
-    }
+    if (int e = check_planned(c.s.totals, totals, 2, "kfx_mesh_emit", st)) return e;
+    const long long n_active = (long long)totals[0];
+    // Every (cell, slab) gets has_color as computed and the colours pointer only with it.  The launches once differed in this arm
+    // by arm (a literal 0 for half-cell slabs, `colors` as passed for whole volumes) without a difference in effect:
+    // mesh_color_params has refused colour on half-cell slabs, and the kernels write colours only under has_color.
+    for_mesh_kind(cell, slab != nullptr, [&](auto kind) {
+        using K = decltype(kind);
+        hipLaunchKernelGGL(k_mesh_compact<typename K::CELL>, dim3((unsigned)c.r.nblk), dim3(256), 0, st, c.p, c.r, c.s.seg, c.s.base, cube_index,
+                           tri_offset, totals[0], totals[1]);
+        hipLaunchKernelGGL((k_mc_emit<typename K::CELL, K::SLAB>), dim3((unsigned)((n_active + 127) / 128)), dim3(128), 0, st, c.p, cv, has_color,
+                           cube_index, tri_offset, n_active, verts, norms, has_color ? colors : nullptr);
+    });
     return check_launch("kfx_mesh_emit");
 }
 
@@ -908,51 +959,36 @@ extern "C" int kfx_mesh_emit(const kfx_volume* vol, int cell, const kfx_slab* sl
 extern "C" size_t kfx_mesh_index_scratch_bytes(const kfx_volume* vol, int cell, const kfx_slab* slab, int own_lo, int own_hi,
                                                const unsigned long long totals[2])
 {
-    MeshParams p;
-    MeshRange r;
-    if (mesh_setup(p, r, vol, cell, slab, own_lo, own_hi)) return 0;
-    if (!totals) { set_error(KFX_E_NULL, "kfx_mesh_index_scratch_bytes: null totals"); return 0; }
-    if (!totals_in_range(totals)) { set_error(KFX_E_RANGE, "kfx_mesh_index_scratch_bytes: totals out of range"); return 0; }
-    return mesh_index_scratch(totals[0], nullptr).bytes;
-}
-
-template <typename CELL>
-static void mesh_index_plan_launch(const MeshParams& p, const MeshRange& r, const MeshScratch& s, const MeshIndexScratch& x,
-                                   const unsigned long long totals[2], hipStream_t st)
-{
-    hipLaunchKernelGGL(k_mesh_compact<CELL>, dim3((unsigned)r.nblk), dim3(256), 0, st, p, r, s.seg, s.base, x.cube_index, x.tri_offset,
-                       totals[0], totals[1]);
-    const long long n_active = (long long)totals[0];
-    hipLaunchKernelGGL(k_mesh_own<CELL>, dim3((unsigned)x.nblk), dim3(MESH_IDX_BLOCK), 0, st, p, x.cube_index, n_active, totals[1], x.info,
-                       x.part, x.hdr);
-    hipLaunchKernelGGL(k_mesh_scan_partials, dim3(1), dim3(MESH_SCAN_THREADS), 0, st, x.part, x.nblk, x.base, x.hdr);
-    hipLaunchKernelGGL(k_mesh_vertex_base, dim3((unsigned)x.nblk), dim3(MESH_IDX_BLOCK), 0, st, x.info, n_active, x.base, x.vbase);
+    MeshCall c;
+    if (mesh_call(c, "kfx_mesh_index_scratch_bytes", MESH_INDEX_SCRATCH, vol, cell, slab, own_lo, own_hi, !totals, nullptr, 0, nullptr, SIZE_MAX, totals))
+        return 0;
+    return c.x.bytes;
 }
 
 extern "C" int kfx_mesh_index_plan(const kfx_volume* vol, int cell, const kfx_slab* slab, int own_lo, int own_hi, const void* scratch,
                                    size_t scratch_bytes, const unsigned long long totals[2], void* index_scratch,
                                    size_t index_scratch_bytes, unsigned long long* n_verts, kfx_stream stream)
 {
-    MeshParams p;
-    MeshRange r;
-    if (int e = mesh_setup(p, r, vol, cell, slab, own_lo, own_hi)) return e;
-    if (!scratch || !totals || !index_scratch || !n_verts) return set_error(KFX_E_NULL, "kfx_mesh_index_plan: null scratch, totals or vertex count");
-    if (!totals_in_range(totals)) return set_error(KFX_E_RANGE, "kfx_mesh_index_plan: totals out of range");
-    if (((uintptr_t)scratch | (uintptr_t)index_scratch) & 255) return set_error(KFX_E_ALIGN, "kfx_mesh_index_plan: scratch not 256-byte aligned");
-    const MeshScratch s = mesh_scratch(r, (void*)scratch);
-    const MeshIndexScratch x = mesh_index_scratch(totals[0], index_scratch);
-    if (scratch_bytes < s.bytes) return set_error(KFX_E_SHAPE, "kfx_mesh_index_plan: scratch smaller than kfx_mesh_scratch_bytes");
-    if (index_scratch_bytes < x.bytes) return set_error(KFX_E_SHAPE, "kfx_mesh_index_plan: index scratch smaller than kfx_mesh_index_scratch_bytes");
+    MeshCall c;
+    if (int e = mesh_call(c, "kfx_mesh_index_plan", MESH_PLAN_SCRATCH | MESH_INDEX_SCRATCH, vol, cell, slab, own_lo, own_hi,
+                          !scratch || !totals || !index_scratch || !n_verts, scratch, scratch_bytes, index_scratch, index_scratch_bytes, totals))
+        return e;
+    const MeshIndexScratch& x = c.x;
     *n_verts = 0;
     if (totals[0] == 0) return 0;
     if (int e = load_tables()) return e;
     const hipStream_t st = (hipStream_t)stream;
-    // the totals must be the plan's: the compaction trusts the lists to fit the index scratch sized from them
-    unsigned long long planned[2];
-    if (int e = read_header(planned, s.totals, 2, st)) return e;
-    if (planned[0] != totals[0] || planned[1] != totals[1]) return set_error(KFX_E_RANGE, "kfx_mesh_index_plan: totals are not the plan's");
-    if (cell == KFX_CELL_F32) mesh_index_plan_launch<RayF32>(p, r, s, x, totals, st);
-    else mesh_index_plan_launch<RayF16>(p, r, s, x, totals, st);
+    if (int e = check_planned(c.s.totals, totals, 2, "kfx_mesh_index_plan", st)) return e;
+    const long long n_active = (long long)totals[0];
+    for_mesh_kind(cell, false, [&](auto kind) {   // (as the plan's)
+        using CELL = typename decltype(kind)::CELL;
+        hipLaunchKernelGGL(k_mesh_compact<CELL>, dim3((unsigned)c.r.nblk), dim3(256), 0, st, c.p, c.r, c.s.seg, c.s.base, x.cube_index,
+                           x.tri_offset, totals[0], totals[1]);
+        hipLaunchKernelGGL(k_mesh_own<CELL>, dim3((unsigned)x.nblk), dim3(MESH_IDX_BLOCK), 0, st, c.p, x.cube_index, n_active, totals[1], x.info,
+                           x.part, x.hdr);
+        hipLaunchKernelGGL(k_mesh_scan_partials, dim3(1), dim3(MESH_SCAN_THREADS), 0, st, x.part, x.nblk, x.base, x.hdr);
+        hipLaunchKernelGGL(k_mesh_vertex_base, dim3((unsigned)x.nblk), dim3(MESH_IDX_BLOCK), 0, st, x.info, n_active, x.base, x.vbase);
+    });
     if (int e = check_launch("kfx_mesh_index_plan")) return e;
     unsigned long long host[2];
     if (int e = read_header(host, x.hdr, 2, st)) return e;
@@ -964,14 +1000,11 @@ extern "C" int kfx_mesh_emit_indexed(const kfx_volume* vol, int cell, const kfx_
                                      const void* index_scratch, size_t index_scratch_bytes, const unsigned long long totals[2],
                                      unsigned long long n_verts, float* verts, float* norms, float* colors, unsigned* faces, kfx_stream stream)
 {
-    MeshParams p;
-    MeshRange r;
-    if (int e = mesh_setup(p, r, vol, cell, slab, own_lo, own_hi)) return e;
-    if (!index_scratch || !totals) return set_error(KFX_E_NULL, "kfx_mesh_emit_indexed: null scratch or totals");
-    if (!totals_in_range(totals) || n_verts > 3 * totals[1]) return set_error(KFX_E_RANGE, "kfx_mesh_emit_indexed: totals out of range");
-    if ((uintptr_t)index_scratch & 255) return set_error(KFX_E_ALIGN, "kfx_mesh_emit_indexed: scratch not 256-byte aligned");
-    const MeshIndexScratch x = mesh_index_scratch(totals[0], (void*)index_scratch);
-    if (index_scratch_bytes < x.bytes) return set_error(KFX_E_SHAPE, "kfx_mesh_emit_indexed: index scratch smaller than kfx_mesh_index_scratch_bytes");
+    MeshCall c;
+    if (int e = mesh_call(c, "kfx_mesh_emit_indexed", MESH_INDEX_SCRATCH, vol, cell, slab, own_lo, own_hi, !index_scratch || !totals, nullptr, 0,
+                          index_scratch, index_scratch_bytes, totals, n_verts))
+        return e;
+    const MeshIndexScratch& x = c.x;
     if (totals[0] == 0) return 0;
     if (!verts || !norms || !faces) return set_error(KFX_E_NULL, "kfx_mesh_emit_indexed: null output");
     if (((uintptr_t)verts | (uintptr_t)norms | (uintptr_t)colors | (uintptr_t)faces) & 3) return set_error(KFX_E_ALIGN, "kfx_mesh_emit_indexed: output alignment");
@@ -980,24 +1013,15 @@ extern "C" int kfx_mesh_emit_indexed(const kfx_volume* vol, int cell, const kfx_
     if (int e = mesh_color_params(cv, has_color, vol, cell, slab, colorvol, colors)) return e;
     if (int e = load_tables()) return e;
     const hipStream_t st = (hipStream_t)stream;
-    // the totals and the vertex count must be this scratch's index plan's: the kernel trusts its lists to fit the caller's buffers
-    unsigned long long planned[4];
-    if (int e = read_header(planned, x.hdr, 4, st)) return e;
-    if (planned[0] != n_verts || planned[1] != totals[1] || planned[2] != totals[0] || planned[3] != totals[1])
-        return set_error(KFX_E_RANGE, "kfx_mesh_emit_indexed: totals are not the index plan's");
+    // (the index plan's header: vertices, triangles, and the totals it was planned for)
+    const unsigned long long planned[4] = {n_verts, totals[1], totals[0], totals[1]};
+    if (int e = check_planned(x.hdr, planned, 4, "kfx_mesh_emit_indexed", st)) return e;
     const long long n_active = (long long)totals[0];
-    const dim3 grid((unsigned)((n_active + 127) / 128)), block(128);
-    float* const cols = has_color ? colors : nullptr;
-#define KFX_EMIT_INDEXED(CELL, SLAB)                                                                                                  \
-    hipLaunchKernelGGL((k_mc_emit_indexed<CELL, SLAB>), grid, block, 0, st, p, cv, has_color, x.cube_index, x.tri_offset, x.info, x.vbase, \
-                       n_active, n_verts, verts, norms, cols, faces)
-    if (cell == KFX_CELL_F32) {
-        if (slab) KFX_EMIT_INDEXED(RayF32, true);
-        else KFX_EMIT_INDEXED(RayF32, false);
-    } else {
-        if (slab) KFX_EMIT_INDEXED(RayF16, true);
-        else KFX_EMIT_INDEXED(RayF16, false);
-    }
-#undef KFX_EMIT_INDEXED
+    for_mesh_kind(cell, slab != nullptr, [&](auto kind) {   // (colours: as kfx_mesh_emit)
+        using K = decltype(kind);
+        hipLaunchKernelGGL((k_mc_emit_indexed<typename K::CELL, K::SLAB>), dim3((unsigned)((n_active + 127) / 128)), dim3(128), 0, st, c.p, cv,
+                           has_color, x.cube_index, x.tri_offset, x.info, x.vbase, n_active, n_verts, verts, norms, has_color ? colors : nullptr,
+                           faces);
+    });
     return check_launch("kfx_mesh_emit_indexed");
 }

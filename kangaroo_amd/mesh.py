@@ -38,6 +38,11 @@ from .roo import _stream
 CELL = {"f32": 0, "f16": 1}   # KFX_CELL_F32 / KFX_CELL_F16
 
 
+def _ptr(t):
+    """a tensor's device address as a C argument; None (NULL) for None"""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
 def ExtractMesh(vol, colorVol=None, stream=None, slab=None, with_index=False, indexed=False):
     """Returns (verts, norms, colors): float32 device tensors of shape (3T, 3), (3T, 3) and (3T, 4) or None.
     indexed=True: (verts, norms, colors, faces) with V rows each and faces (T, 3), uint32 ids held in an int32 tensor (the weld
@@ -56,47 +61,43 @@ def ExtractMesh(vol, colorVol=None, stream=None, slab=None, with_index=False, in
     if slab is not None:
         full_d, z_offset, zmin, zmax, lo, hi = slab
         sl = C.byref(_lib.KfxSlab(int(full_d), int(z_offset), float(zmin), float(zmax)))
-    nbytes = L.kfx_mesh_scratch_bytes(vol.ref(), cell, sl, int(lo), int(hi))
+    args = (vol.ref(), cell, sl, int(lo), int(hi))
+    nbytes = L.kfx_mesh_scratch_bytes(*args)
     if nbytes == 0:
-        _lib.check(L.kfx_mesh_plan(vol.ref(), cell, sl, int(lo), int(hi), None, 0, None, None))   # the reason
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        _lib.check(L.kfx_mesh_plan(*args, None, 0, None, None))   # the reason
+    empty = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+    scratch = empty(nbytes, torch.uint8)
     totals = (C.c_ulonglong * 2)()
     st = _stream(stream)
-    code = L.kfx_mesh_plan(vol.ref(), cell, sl, int(lo), int(hi), C.c_void_p(scratch.data_ptr()), nbytes, totals, st)
+    code = L.kfx_mesh_plan(*args, _ptr(scratch), nbytes, totals, st)
     if code == -4 and totals[1] >= 2 ** 32 // 3:   # KFX_E_RANGE
         raise ValueError("mesh too large for 32-bit vertex offsets")
     _lib.check(code)
     na, ntri = int(totals[0]), int(totals[1])
     # IsValid() of the colour volume -- of the FULL one where colorVol is a slab of it
     has_color = colorVol is not None and min(colorVol.w, colorVol.h, colorVol.d if slab is None else int(slab[0])) >= 8
+    cref = colorVol.ref() if has_color else None
+    nv = 3 * ntri
     if indexed:
         if with_index:
             raise ValueError("ExtractMesh: with_index lists the soup's cubes; not with indexed=True")
-        xbytes = L.kfx_mesh_index_scratch_bytes(vol.ref(), cell, sl, int(lo), int(hi), totals)
-        xscratch = torch.empty(xbytes, dtype=torch.uint8, device=dev)
-        nv = C.c_ulonglong(0)
-        _lib.check(L.kfx_mesh_index_plan(vol.ref(), cell, sl, int(lo), int(hi), C.c_void_p(scratch.data_ptr()), nbytes, totals,
-                                         C.c_void_p(xscratch.data_ptr()), xbytes, C.byref(nv), st))
-        nv = int(nv.value)
-        verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
-        norms = torch.empty((nv, 3), dtype=torch.float32, device=dev)
-        colors = torch.empty((nv, 4), dtype=torch.float32, device=dev) if has_color else None
-        faces = torch.empty((ntri, 3), dtype=torch.int32, device=dev)
+        xbytes = L.kfx_mesh_index_scratch_bytes(*args, totals)
+        xscratch = empty(xbytes, torch.uint8)
+        nvert = C.c_ulonglong(0)
+        _lib.check(L.kfx_mesh_index_plan(*args, _ptr(scratch), nbytes, totals, _ptr(xscratch), xbytes, C.byref(nvert), st))
+        nv = int(nvert.value)
+    verts, norms = empty((nv, 3), torch.float32), empty((nv, 3), torch.float32)
+    colors = empty((nv, 4), torch.float32) if has_color else None
+    if indexed:
+        faces = empty((ntri, 3), torch.int32)
         if na:
-            _lib.check(L.kfx_mesh_emit_indexed(vol.ref(), cell, sl, int(lo), int(hi), colorVol.ref() if has_color else None,
-                                               C.c_void_p(xscratch.data_ptr()), xbytes, totals, nv, C.c_void_p(verts.data_ptr()),
-                                               C.c_void_p(norms.data_ptr()), C.c_void_p(colors.data_ptr()) if has_color else None,
-                                               C.c_void_p(faces.data_ptr()), st))
+            _lib.check(L.kfx_mesh_emit_indexed(*args, cref, _ptr(xscratch), xbytes, totals, nv, _ptr(verts), _ptr(norms), _ptr(colors),
+                                               _ptr(faces), st))
         return verts, norms, colors, faces
-    cube_index = torch.empty(na, dtype=torch.int64, device=dev)
-    tri_offset = torch.empty(na, dtype=torch.int32, device=dev)
-    verts = torch.empty((3 * ntri, 3), dtype=torch.float32, device=dev)
-    norms = torch.empty((3 * ntri, 3), dtype=torch.float32, device=dev)
-    colors = torch.empty((3 * ntri, 4), dtype=torch.float32, device=dev) if has_color else None
+    cube_index, tri_offset = empty(na, torch.int64), empty(na, torch.int32)
     if na:
-        _lib.check(L.kfx_mesh_emit(vol.ref(), cell, sl, int(lo), int(hi), colorVol.ref() if has_color else None, C.c_void_p(scratch.data_ptr()),
-                                   nbytes, totals, C.c_void_p(cube_index.data_ptr()), C.c_void_p(tri_offset.data_ptr()), C.c_void_p(verts.data_ptr()),
-                                   C.c_void_p(norms.data_ptr()), C.c_void_p(colors.data_ptr()) if has_color else None, st))
+        _lib.check(L.kfx_mesh_emit(*args, cref, _ptr(scratch), nbytes, totals, _ptr(cube_index), _ptr(tri_offset), _ptr(verts), _ptr(norms),
+                                   _ptr(colors), st))
     if with_index:
         return verts, norms, colors, cube_index, tri_offset
     return verts, norms, colors

@@ -173,6 +173,60 @@ def test_gpu_indexed_mesh_refuses_totals_that_are_not_the_plans(roo):
     assert int(faces.max()) == V - 1 and int(faces.min()) == 0
 
 
+@pytest.mark.parametrize("kind", ["f32", "f16"])
+def test_gpu_mesh_colours_are_written_only_when_asked_for(roo, kind):
+    """kfx_mesh_emit and kfx_mesh_emit_indexed with a `colors` buffer but no colour volume to sample -- colorvol null, or (whole
+    volume) one that is not IsValid(), 24 x 20 x 7 -- on a 24 x 20 x 28 sphere, whole and as the upper of two slab views with a ghost of
+    two planes (there a colour slab must have the SDF slab's dimensions, so only the null one cannot be sampled): the buffer keeps its
+    sentinel in every element, and every other array is that of the call with `colors` null, bit for bit."""
+    import ctypes as C
+    import torch
+    from kangaroo_amd import _lib, mesh
+    L = _lib.load()
+    D, cell = 28, mesh.CELL[kind]
+    bmin, bmax = (-1.0, -0.8, -1.1), (1.0, 0.9, 1.2)
+    vol = roo.BoundedVolume(24, 20, D, bmin, bmax, kind=kind)
+    roo.SdfSphere(vol, (0.1, -0.05, 0.15), 0.7)
+    small = roo.BoundedVolume(24, 20, 7, bmin, bmax, kind="c32")
+    assert not small.IsValid()
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    ref = lambda v: None if v is None else v.ref()
+    z0, z1, s0, s1 = list(TV.slab_bounds(D, 2, 2))[1]
+    views = [(vol, None, 0, 0, (None, small)), (vol.ZSlab(s0, s1), C.byref(_lib.KfxSlab(D, s0, bmin[2], bmax[2])), z0, z1, (None,))]
+    for view, sl, lo, hi, colour_volumes in views:
+        nbytes = L.kfx_mesh_scratch_bytes(view.ref(), cell, sl, lo, hi)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+        totals = (C.c_ulonglong * 2)()
+        _lib.check(L.kfx_mesh_plan(view.ref(), cell, sl, lo, hi, ptr(scratch), nbytes, totals, None))
+        na, nt = int(totals[0]), int(totals[1])
+        xbytes = L.kfx_mesh_index_scratch_bytes(view.ref(), cell, sl, lo, hi, totals)
+        xscratch = torch.empty(xbytes, dtype=torch.uint8, device="cuda")
+        nvert = C.c_ulonglong(0)
+        _lib.check(L.kfx_mesh_index_plan(view.ref(), cell, sl, lo, hi, ptr(scratch), nbytes, totals, ptr(xscratch), xbytes, C.byref(nvert), None))
+        V = int(nvert.value)
+        assert na > 100 and nt > 200 and 0 < V < 3 * nt
+
+        def run(cvol, colors, xcolors):
+            full = lambda shape, dt: torch.full(shape, -7, dtype=dt, device="cuda")
+            ci, to, f = full((na,), torch.int64), full((na,), torch.int32), full((nt, 3), torch.int32)
+            v, n, xv, xn = (full((rows, 3), torch.float32) for rows in (3 * nt, 3 * nt, V, V))
+            _lib.check(L.kfx_mesh_emit(view.ref(), cell, sl, lo, hi, ref(cvol), ptr(scratch), nbytes, totals, ptr(ci), ptr(to), ptr(v), ptr(n),
+                                       ptr(colors), None))
+            _lib.check(L.kfx_mesh_emit_indexed(view.ref(), cell, sl, lo, hi, ref(cvol), ptr(xscratch), xbytes, totals, V, ptr(xv), ptr(xn),
+                                               ptr(xcolors), ptr(f), None))
+            torch.cuda.synchronize()
+            return ci.view(torch.int32), to, v, n, xv, xn, f
+
+        plain = run(None, None, None)
+        assert not any(bool((a == -7).any()) for a in plain)   # every element of every array is written
+        for cvol in colour_volumes:
+            colors = torch.full((3 * nt, 4), -7.0, dtype=torch.float32, device="cuda")
+            xcolors = torch.full((V, 4), -7.0, dtype=torch.float32, device="cuda")
+            got = run(cvol, colors, xcolors)
+            assert bool((colors == -7.0).all()) and bool((xcolors == -7.0).all()), (sl is not None, cvol is not None)
+            assert all(TV.bits_equal(a, b) for a, b in zip(got, plain)), (sl is not None, cvol is not None)
+
+
 def read_ply(path):
     raw = open(path, "rb").read()
     end = raw.index(b"end_header\n") + len(b"end_header\n")

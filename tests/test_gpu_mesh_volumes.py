@@ -199,6 +199,29 @@ def test_gpu_slab_pipeline_rank_meshes(halo, tmp_path):
         assert (tmp_path / ("m.r%d.ply" % r)).exists()
 
 
+def test_gpu_mesh_scan_carries_across_chunks_of_block_sums(roo):
+    """k_mesh_scan_partials walks the block sums in chunks of 1024 x 8 = 8192 blocks and carries the running totals from chunk to
+    chunk.  2050 x 2050 x 3 fp32 (101 MB): cz = 2, one segment per column, 2049^2 = 4 198 401 segments = 8201 blocks of 512, nine of
+    them in the second chunk.  All NaN but the columns x < 10 and x >= 2040, which the plane z = 0.5 voxels crosses: active cubes in the
+    first blocks and, from segment 2040 * 2049 (block 8164) on, up to the last, whose offsets are right only if the carry is."""
+    import torch
+    from kangaroo_amd import mesh
+    N = 2050
+    vol = roo.BoundedVolume(N, N, 3, (-1, -1, 0), (1, 1, 0.002))
+    t = vol.tensor()
+    t[...] = float("nan")
+    for xs in (slice(0, 10), slice(N - 10, N)):
+        t[:, :, xs, 0] = (torch.arange(3, device=t.device, dtype=torch.float32) - 0.5)[:, None, None] * 0.25
+        t[:, :, xs, 1] = 1.0
+    v, n, _, ci, to = mesh.ExtractMesh(vol, with_index=True)
+    ov, on, _, oa, oto, counts = old_path(vol)
+    assert len(ci) == 2 * 9 * (N - 1) and int(ci[0]) == 0 and int(ci[-1]) == ((N - 2) * (N - 1) + N - 2) * 2
+    assert int((ci // 2 >= 8192 * 512).sum()) == 2 * (N - 1) - 1   # cubes whose segment (ci / cz) lies in the second chunk
+    assert bits_equal(ci, oa) and bits_equal(to, oto) and bits_equal(v, ov) and bits_equal(n, on)
+    del vol, t, v, n, ov, on, counts
+    torch.cuda.empty_cache()
+
+
 def test_gpu_mesh_1024_f32_equals_the_byte_per_cube_path(roo):
     import torch
     from kangaroo_amd import mesh
