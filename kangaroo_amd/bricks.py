@@ -1,0 +1,133 @@
+"""Sparse brick snapshots on the host (include/kfx_bricks.h underneath): where the bricks a moving volume loses are kept, which
+boxes of a shift leave and enter, and a whole volume as one file.
+
+A brick is 8 x 8 x 8 cells.  A volume that follows the camera in steps of whole bricks keeps its cells on one world lattice: with
+`origin` the running sum of its shifts (new(x) = old(x + s), so the view's cell 0 is world cell `origin`), the brick at view cell
+(8 i, 8 j, 8 k) has the world key (origin / 8 + (i, j, k)).  Pure numpy up to SaveBricks / LoadBricks, which call the operators.
+"""
+import numpy as np
+
+BRICK = 8
+
+
+def _retained(dim, s):
+    """[lo, hi) of the old cells of one axis a shift by s keeps: those whose destination x - s lies inside"""
+    return max(0, s), min(dim, dim + s)
+
+
+def leaving_boxes(dims, shift):
+    """The cells a shift discards (those whose destination is outside the view), in the coordinates before the shift: up to three
+    disjoint (start, size) boxes that cover them exactly.  The retained cells are a box, [max(0, s), min(dim, dim + s)) per axis;
+    what is left of the view is peeled off axis by axis: the z-planes outside it, then the y-rows outside it within its z-range,
+    then the x-cells outside it within its z- and y-range.  A shift has one sign per axis, so each peel is one box."""
+    dims = [int(v) for v in dims]
+    keep = [_retained(d, int(s)) for d, s in zip(dims, shift)]
+    if any(lo >= hi for lo, hi in keep):
+        return [((0, 0, 0), tuple(dims))]
+    boxes = []
+    lo, hi = [0, 0, 0], list(dims)   # the part of the view not yet peeled
+    for axis in (2, 1, 0):
+        klo, khi = keep[axis]
+        for a, b in ((0, klo), (khi, dims[axis])):
+            if a < b:
+                start, size = list(lo), [hi[i] - lo[i] for i in range(3)]
+                start[axis], size[axis] = a, b - a
+                boxes.append((tuple(start), tuple(size)))
+        lo[axis], hi[axis] = klo, khi
+    return boxes
+
+
+def entering_boxes(dims, shift):
+    """The cells a shift fills (those whose source is outside the view), in the coordinates after the shift: the cells the
+    opposite shift would discard."""
+    return leaving_boxes(dims, tuple(-int(s) for s in shift))
+
+
+def world_keys(origin_cells, start, size):
+    """The world brick keys (n, 3) int64 = (bx, by, bz) of the bricks of the box (start, size) of a view whose cell 0 is world cell
+    origin_cells, in the order of the box's own brick ids ((bz * nby + by) * nbx + bx).  Everything a multiple of 8."""
+    o = np.asarray(origin_cells, np.int64) + np.asarray(start, np.int64)
+    size = np.asarray(size, np.int64)
+    if np.any(o % BRICK) or np.any(size % BRICK):
+        raise ValueError("world_keys: origin %s + start %s and size %s must be whole bricks" % (tuple(origin_cells), tuple(start), tuple(size)))
+    nb = size // BRICK
+    bz, by, bx = np.meshgrid(np.arange(nb[2]), np.arange(nb[1]), np.arange(nb[0]), indexing="ij")
+    return np.stack([bx.reshape(-1), by.reshape(-1), bz.reshape(-1)], 1).astype(np.int64) + o // BRICK
+
+
+def box_brick_ids(origin_cells, start, size, keys):
+    """the brick ids, within the box (start, size), of world keys that lie in it: the inverse of world_keys"""
+    rel = np.asarray(keys, np.int64).reshape(-1, 3) - (np.asarray(origin_cells, np.int64) + np.asarray(start, np.int64)) // BRICK
+    nb = np.asarray(size, np.int64) // BRICK
+    return (rel[:, 2] * nb[1] + rel[:, 1]) * nb[0] + rel[:, 0]
+
+
+class BrickStore:
+    """Host memory for the bricks of one volume that are outside its box: world brick key (bx, by, bz) -> the brick's bytes
+    (512 cells, x fastest).  No limit and no eviction."""
+
+    def __init__(self, kind="f32"):
+        self.kind = kind
+        self.brick_bytes = BRICK ** 3 * {"f32": 8, "f16": 4, "c32": 4}[kind]
+        self._bricks = {}
+
+    def __len__(self):
+        return len(self._bricks)
+
+    @property
+    def nbytes(self):
+        return len(self._bricks) * self.brick_bytes
+
+    def clear(self):
+        self._bricks.clear()
+
+    def put(self, keys, cells):
+        """keys (n, 3) integers, cells n bricks of bytes; a key already present is replaced"""
+        keys = np.asarray(keys, np.int64).reshape(-1, 3)
+        cells = np.ascontiguousarray(cells).view(np.uint8).reshape(len(keys), self.brick_bytes)
+        for k, c in zip(keys.tolist(), cells):
+            self._bricks[tuple(k)] = c.copy()
+
+    def take(self, keys):
+        """(found keys (m, 3) int64, their cells (m, brick bytes) uint8), in the order of `keys`; what is found leaves the store"""
+        keys = np.asarray(keys, np.int64).reshape(-1, 3)
+        found, cells = [], []
+        for k in keys.tolist():
+            c = self._bricks.pop(tuple(k), None)
+            if c is not None:
+                found.append(k)
+                cells.append(c)
+        if not found:
+            return np.empty((0, 3), np.int64), np.empty((0, self.brick_bytes), np.uint8)
+        return np.asarray(found, np.int64), np.stack(cells)
+
+
+def SaveBricks(path, vol, fill, ops=None):
+    """A snapshot of a whole volume as one .npz: its dims, box, cell kind, the bits of `fill`, and the ids and cells of the bricks
+    that differ from the fill cell (ops.BrickPack).  Returns the number of bricks written."""
+    if ops is None:
+        from . import roo as ops
+    ids, cells = ops.BrickPack(vol, fill)
+    with open(path, "wb") as f:
+        np.savez(f, dims=np.array([vol.w, vol.h, vol.d], np.int64), boxmin=np.asarray(vol.boxmin, np.float32), boxmax=np.asarray(vol.boxmax, np.float32),
+                 kind=np.array(vol.kind), fill_bits=np.array([fill], np.float32).view(np.uint32),
+                 ids=ids.cpu().numpy().view(np.uint32), cells=cells.cpu().numpy())
+    return int(ids.numel())
+
+
+def LoadBricks(path, vol, ops=None):
+    """Read a SaveBricks file into `vol`: refuses a volume of other dims or another cell kind; every cell becomes the file's fill
+    cell, then the bricks are unpacked; vol takes the file's box.  Returns the number of bricks read."""
+    if ops is None:
+        from . import roo as ops
+    with np.load(path) as z:
+        dims, kind = tuple(int(v) for v in z["dims"]), str(z["kind"])
+        if dims != (vol.w, vol.h, vol.d) or kind != vol.kind:
+            raise ValueError("LoadBricks: the file holds a %s volume of %s, not a %s volume of %s" % (kind, dims, vol.kind, (vol.w, vol.h, vol.d)))
+        fill = float(z["fill_bits"].view(np.float32)[0])
+        ids, cells = z["ids"], z["cells"]
+        vol.boxmin, vol.boxmax = z["boxmin"].astype(np.float32), z["boxmax"].astype(np.float32)
+    ops.VolumeFill(vol, fill)
+    if ids.size:
+        ops.BrickUnpack(vol, ids, cells)
+    return int(ids.size)

@@ -24,6 +24,7 @@
 #include "kfx_device.h"
 #include "sampling.h"
 #include "host_args.h"
+#include "block_scan.h"
 #include "../../include/kfx_mesh.h"
 #include "../../include/kfx_mesh_index.h"
 
@@ -356,30 +357,6 @@ __global__ __launch_bounds__(256) void k_mesh_count(const MeshParams p, const Me
             if (k < r.nsz) dst[k] = tile[xr][kk];
         }
     }
-}
-
-// inclusive scan of one value per thread over a workgroup of 64 * NW threads; returns the exclusive prefix, *total the sum
-template <typename T, int NW>
-__device__ __forceinline__ T block_exclusive_scan(T v, T* lds, T* total)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    T inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) lds[wv] = inc;
-    __syncthreads();
-    T base = 0, sum = 0;
-    for (int i = 0; i < NW; ++i) {
-        const T w = lds[i];
-        if (i < wv) base += w;
-        sum += w;
-    }
-    __syncthreads();
-    *total = sum;
-    return base + inc - v;
 }
 
 // the sums of a pair of counters over a workgroup of 256 threads, one value of each per thread: part[2 b] = sum of a,

@@ -114,7 +114,7 @@ static int shift_check_scratch(const ShiftGeom& g, const void* scratch, size_t s
     return 0;
 }
 
-static unsigned long long shift_fill_bytes(int cell, float fill)
+unsigned long long kfx::shift_fill_bytes(int cell, float fill)
 {
     unsigned u;
     memcpy(&u, &fill, 4);

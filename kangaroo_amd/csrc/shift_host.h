@@ -93,4 +93,8 @@ inline void shift_box(const kfx_volume& v, const int shift[3], float bmin[3], fl
 kfx_volume* frame_volume(kfx_frame* f);
 kfx_sdf_summary* frame_tracked_summary(kfx_frame* f);
 
+// the fill cell's bytes (shift.hip): {fill, 0} as SDF_t, the half of fill and a zero weight as SDF_h, fill itself as a colour cell (the
+// 4-byte cells: the low word).  bricks.hip compares against the same bytes.
+unsigned long long shift_fill_bytes(int cell, float fill);
+
 } // namespace kfx

@@ -21,7 +21,7 @@ partitioning and compositing logic under gloo without a GPU.
 """
 import numpy as np
 
-from . import scenes
+from . import bricks, scenes
 
 
 def vbo_normals(ops, vbo, normals, depth, K):
@@ -66,6 +66,12 @@ class FramePipeline:
         one-call frame: its shift()), the colour volume with it (fill 0.5), the summary is rebuilt when tracking, vol.boxmin / boxmax
         move, and (frame index, shift) is appended to self.shifts.  focus=None: the distance from the camera centre to the box centre
         at the first step.  trunc stays what it was at construction.
+        follow=dict(..., spill=True): the volume keeps what leaves.  Before a shift the live 8^3 bricks of the boxes it discards are
+        packed on the device (ops.BrickPack), copied to the host and kept in self.store (a bricks.BrickStore; colour: self.cstore, fill
+        0.5) under world brick keys; after it the bricks the store holds of the boxes that entered are unpacked into them, and a shift
+        that restored something rebuilds the summary once more.  self.origin is the running sum of the shifts in cells.  Needs a
+        quantum and dims that are multiples of 8 (leaving and entering boxes are whole bricks of one world lattice); reset() forgets
+        the store.  Off by default: nothing changes and no brick code runs.
         sensor: "u16" or "f32" -- the frames arrive as raw sensor images on the host (main.cpp:202-209): the pipeline owns an upload
         ring (ops.DepthInput, `input`) of sensor_slots slots that converts with sensor_scale (millimetres: 1e-3) while it filters.
         submit(array) hands it the next image -- one frame ahead, its copy runs beside the current frame -- and a step / preprocess
@@ -113,15 +119,26 @@ class FramePipeline:
         self.kframe = None
         self.input = None
         self.follow, self.shifts, self._shift_scratch = None, [], None
+        self.spill, self.store, self.cstore, self.origin, self.restored = False, None, None, (0, 0, 0), 0
         if follow is not None:
             if not hasattr(ops, "VolumeShift"):
                 raise ValueError("FramePipeline: follow= needs an operator set with VolumeShift")
-            unknown = set(follow) - {"focus", "quantum", "slack"}
+            unknown = set(follow) - {"focus", "quantum", "slack", "spill"}
             if unknown:
-                raise ValueError("FramePipeline: follow= takes focus, quantum and slack, not %s" % sorted(unknown))
+                raise ValueError("FramePipeline: follow= takes focus, quantum, slack and spill, not %s" % sorted(unknown))
             self.follow = {"focus": follow.get("focus"), "quantum": int(follow.get("quantum", 8)), "slack": float(follow.get("slack", 16))}
             if self.follow["quantum"] < 1:
                 raise ValueError("FramePipeline: follow= needs quantum >= 1")
+            if follow.get("spill"):
+                # leaving and entering regions must be whole bricks of one world brick lattice
+                if self.follow["quantum"] % bricks.BRICK or any(int(d) % bricks.BRICK for d in dims):
+                    raise ValueError("FramePipeline: follow=dict(spill=True) needs a quantum and dimensions that are multiples of 8, not "
+                                     "quantum %d and dims %s" % (self.follow["quantum"], tuple(int(d) for d in dims)))
+                if not hasattr(ops, "BrickPack"):
+                    raise ValueError("FramePipeline: follow=dict(spill=True) needs an operator set with BrickPack")
+                self.spill = True
+                self.store = bricks.BrickStore(self.kind)
+                self.cstore = bricks.BrickStore("c32") if self.color else None
         if sensor is not None:
             if not hasattr(ops, "DepthInput"):
                 raise ValueError("FramePipeline: sensor= needs an operator set with DepthInput")
@@ -226,18 +243,58 @@ class FramePipeline:
             self.ops.SdfReset(self.vol, float("nan"))
         if self.color:
             self.ops.ColorReset(self.cvol)   # SdfReset(colorVol) (main.cpp:233)
+        self._forget_spilled()
+
+    def _forget_spilled(self):
+        """the model starts over: what its predecessor left outside the box is not part of it"""
+        for store in (self.store, self.cstore):
+            if store is not None:
+                store.clear()
 
     def shift_volume(self, shift):
         """Shift the model by whole cells (ops.VolumeShift): the SDF volume with fill NaN -- through the one-call frame where it is in
         use -- the colour volume with fill 0.5, the summary rebuilt when tracking; vol.boxmin / boxmax (and cvol's) move."""
+        shift = tuple(int(s) for s in shift)
+        if self.spill and any(s % bricks.BRICK for s in shift):
+            raise ValueError("FramePipeline: with follow=dict(spill=True) a shift is whole bricks (multiples of 8), not %s" % (shift,))
         if self._shift_scratch is None:   # one scratch for both volumes: 16 packed planes of the SDF volume's cells
             self._shift_scratch = self.ops.shift_scratch(self.vol, shift)
+        volumes = [(self.vol, self.store, float("nan"))] + ([(self.cvol, self.cstore, 0.5)] if self.color else [])
+        if self.spill:
+            for vol, store, fill in volumes:
+                self._spill(vol, store, fill, shift)
         if self.kframe is not None:
             self.kframe.shift(shift, self._shift_scratch)
         else:
             self.ops.VolumeShift(self.vol, shift, float("nan"), self._shift_scratch, summary=self.summary if self.track else None)
         if self.color:
             self.ops.VolumeShift(self.cvol, shift, 0.5, self._shift_scratch)
+        self.origin = tuple(o + s for o, s in zip(self.origin, shift))
+        if self.spill:
+            restored = sum([self._restore(vol, store, shift) for vol, store, _ in volumes])
+            self.restored += restored
+            if restored and self.track:   # the summary and the class tables describe the volume as it is after the restore
+                self.summary.rebuild()
+
+    def _spill(self, vol, store, fill, shift):
+        """follow=dict(spill=True), before the shift: the live bricks of the boxes that leave go to the host, under their world keys"""
+        for start, size in bricks.leaving_boxes(self.dims, shift):
+            ids, cells = self.ops.BrickPack(vol.SubVolume(start, size), fill)
+            if ids.numel():
+                store.put(bricks.world_keys(self.origin, start, size)[ids.cpu().numpy()], cells.cpu().numpy())
+
+    def _restore(self, vol, store, shift):
+        """after the shift (self.origin is the new one): the bricks the store holds of the boxes that entered go back into them;
+        returns how many"""
+        n = 0
+        for start, size in bricks.entering_boxes(self.dims, shift):
+            if not len(store):
+                break
+            keys, cells = store.take(bricks.world_keys(self.origin, start, size))
+            if len(keys):
+                self.ops.BrickUnpack(vol.SubVolume(start, size), bricks.box_brick_ids(self.origin, start, size, keys), cells)
+                n += len(keys)
+        return n
 
     def _follow(self, T_wc):
         """follow=: the shift this pose asks for, applied before the frame's first launch"""
@@ -565,6 +622,7 @@ class TrackingPipeline(FramePipeline):
             self.ops.SdfReset(self.vol, float("nan"))
         if self.color:
             self.ops.ColorReset(self.cvol)
+        self._forget_spilled()
 
 
 def slab_range(d, rank, world):

@@ -643,6 +643,65 @@ def VolumeShift(vol, shift, fill, scratch=None, stream=None, summary=None):
         summary.rebuild(stream)
 
 
+# ---- sparse brick snapshots (include/kfx_bricks.h) -------------------------------------
+
+BRICK = 8   # cells per brick edge
+
+
+def brick_bytes(vol):
+    """bytes of one packed brick of this volume's cells"""
+    return BRICK ** 3 * vol.ELEM
+
+
+def BrickScratchBytes(vol):
+    """kfx_bricks_scratch_bytes: the scratch a BrickPack of `vol` (a volume or a view of one) needs."""
+    return int(_lib.load().kfx_bricks_scratch_bytes(vol.ref(), CELL_KIND[vol.kind]))
+
+
+def BrickPack(vol, fill, scratch=None, stream=None):
+    """kfx_bricks_plan + kfx_bricks_pack: the 8 x 8 x 8 bricks of `vol` (a volume or a view of one) that differ bitwise from the fill
+    cell (SDF cells: what SdfReset(vol, fill) writes; a colour volume: fill).  Returns (ids, cells): ids int32 (n,), ascending brick
+    ids ((bz * nby + by) * nbx + bx); cells uint8 (n, 512 * cell bytes), each brick [8][8][8] with x fastest, verbatim.  scratch: a
+    uint8 device tensor of BrickScratchBytes(vol) bytes (allocated here when None)."""
+    L, kind, dev = _lib.load(), CELL_KIND[vol.kind], vol.storage.device
+    need = BrickScratchBytes(vol)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    nbytes, n = scratch.numel() * scratch.element_size(), C.c_ulonglong(0)
+    _lib.check(L.kfx_bricks_plan(vol.ref(), kind, float(fill), scratch.data_ptr(), nbytes, C.byref(n), _stream(stream)))
+    ids = torch.empty(n.value, dtype=torch.int32, device=dev)
+    cells = torch.empty((n.value, brick_bytes(vol)), dtype=torch.uint8, device=dev)
+    _lib.check(L.kfx_bricks_pack(vol.ref(), kind, float(fill), scratch.data_ptr(), nbytes, n.value, ids.data_ptr() if n.value else None,
+                                 cells.data_ptr() if n.value else None, _stream(stream)))
+    return ids, cells
+
+
+def BrickUnpack(vol, ids, cells, stream=None):
+    """kfx_bricks_unpack: write the cells inside `vol` of the listed bricks from the payload, and nothing else.  ids (strictly
+    ascending; checked here when given on the host) and cells as BrickPack returns them, torch tensors or host arrays (uploaded here
+    into torch's memory, whose reuse is ordered on torch's current stream: with another `stream` pass device tensors of your own)."""
+    dev = vol.storage.device
+    if not torch.is_tensor(ids):
+        host = np.ascontiguousarray(np.asarray(ids).reshape(-1), dtype=np.int64)
+        if host.size and (host.min() < 0 or host.max() > 0xffffffff or np.any(np.diff(host) <= 0)):
+            raise ValueError("BrickUnpack: ids must be brick ids in strictly ascending order")
+        ids = torch.from_numpy(host.astype(np.uint32).view(np.int32)).to(dev)
+    if not torch.is_tensor(cells):
+        cells = torch.from_numpy(np.ascontiguousarray(cells).view(np.uint8).reshape(-1)).to(dev)
+    ids, cells = ids.contiguous(), cells.contiguous()
+    n = ids.numel()
+    if cells.numel() * cells.element_size() != n * brick_bytes(vol):
+        raise ValueError("BrickUnpack: %d ids need %d bytes of cells, got %d" % (n, n * brick_bytes(vol), cells.numel() * cells.element_size()))
+    _lib.check(_lib.load().kfx_bricks_unpack(vol.ref(), CELL_KIND[vol.kind], ids.data_ptr() if n else None, cells.data_ptr() if n else None, n,
+                                             _stream(stream)))
+
+
+def VolumeFill(vol, fill, stream=None):
+    """Every cell of `vol` (a volume or a view of one) = the fill cell, the box unchanged: kfx_volume_shift by the view's whole
+    width, which is one fill -- the bytes a shift exposes and BrickPack compares against, for all three cell kinds."""
+    _lib.check(_lib.load().kfx_volume_shift(vol.ref(), CELL_KIND[vol.kind], _shift3((vol.w, 0, 0)), float(fill), None, 0, _stream(stream)))
+
+
 def ElementwiseScaleBias(b, a, s, offset=0.0, stream=None):
     """roo::ElementwiseScaleBias<float,float,float> and <float,unsigned short,float> (cu_operations.h; main.cpp:207-208):
     b = s*a + offset, a of kind "f32" or "u16"."""
