@@ -20,7 +20,9 @@
 #include <kangaroo/Sdf.h>
 #include <kangaroo/VolumeShift.h>
 #include <kangaroo/launch_utils.h>
+#include <kangaroo/MarchingCubes.h>
 #include <kfx_bricks.h>
+#include <kfx_mesh_bricks.h>
 
 namespace roo
 {
@@ -55,6 +57,85 @@ template<typename T, typename M>
 inline void BrickUnpack(BoundedVolume<T, TargetDevice, M>& vol, const unsigned* ids, const void* cells, size_t n)
 {
     GpuCheckStatus(kfx_bricks_unpack(vol.abi(), shift_detail::Cell<T>::kind, ids, cells, n, 0));
+}
+
+// ---- the mesh of packed bricks (kfx_mesh_bricks_*, include/kfx_mesh_bricks.h): SaveMesh's mesh of the volume the bricks would unpack
+// into -- NaN where no brick is listed, colour 0.5 -- without that volume.  The frame is the virtual volume's dimensions and box; `cell`
+// is KFX_CELL_F32 or KFX_CELL_F16, the kind of the bricks in `cells`.
+//
+//   const kfx_volume frame = roo::BrickFrame(w, h, d, boxmin, boxmax);
+//   roo::SaveMeshBricks("world", frame, KFX_CELL_F32, ids.ptr, cells.ptr, n);                         // -> world.ply
+//   roo::SaveMeshBricks("world", frame, KFX_CELL_F32, ids.ptr, cells.ptr, n, cids.ptr, ccells.ptr, nc);   // with colours
+
+// a frame: only the dimensions and the box of the kfx_volume are read
+inline kfx_volume BrickFrame(size_t w, size_t h, size_t d, float3 boxmin, float3 boxmax)
+{
+    kfx_volume f = {};
+    f.w = w; f.h = h; f.d = d;
+    f.boxmin[0] = boxmin.x; f.boxmin[1] = boxmin.y; f.boxmin[2] = boxmin.z;
+    f.boxmax[0] = boxmax.x; f.boxmax[1] = boxmax.y; f.boxmax[2] = boxmax.z;
+    return f;
+}
+
+inline size_t MeshBricksScratchBytes(size_t n, size_t n_color = 0) { return kfx_mesh_bricks_scratch_bytes(n, n_color); }
+
+// totals[0] = active cubes, totals[1] = triangles; the scratch then belongs to the MeshBricksEmit that follows
+inline void MeshBricksPlan(const kfx_volume& frame, int cell, const unsigned* ids, const void* cells, size_t n, void* scratch, size_t scratch_bytes,
+                           unsigned long long totals[2])
+{
+    GpuCheckStatus(kfx_mesh_bricks_plan(&frame, cell, ids, cells, n, scratch, scratch_bytes, totals, 0));
+}
+
+inline void MeshBricksEmit(const kfx_volume& frame, int cell, const unsigned* ids, const void* cells, size_t n, const unsigned* color_ids,
+                           const void* color_cells, size_t n_color, void* scratch, size_t scratch_bytes, const unsigned long long totals[2],
+                           long long* cube_index, unsigned* tri_offset, float* verts, float* norms, float* colors)
+{
+    GpuCheckStatus(kfx_mesh_bricks_emit(&frame, cell, ids, cells, n, color_ids, color_cells, n_color, scratch, scratch_bytes, totals, cube_index,
+                                        tri_offset, verts, norms, colors, 0));
+}
+
+namespace mesh_detail
+{
+// the brick mesh as host arrays; cube_index, if given, receives every active cube's dense index in the list's order
+inline HostMesh ExtractBricks(const kfx_volume& frame, int cell, const unsigned* ids, const void* cells, size_t n, const unsigned* color_ids,
+                              const void* color_cells, size_t n_color, bool color, std::vector<long long>* cube_index = nullptr,
+                              std::vector<unsigned>* tri_offset = nullptr)
+{
+    const size_t nbytes = MeshBricksScratchBytes(n, color ? n_color : 0);
+    DeviceBuffer scratch(nbytes);
+    unsigned long long totals[2] = {0, 0};
+    MeshBricksPlan(frame, cell, ids, cells, n, scratch.get(), nbytes, totals);
+    HostMesh m;
+    m.ntri = totals[1];
+    m.nvert = 3 * m.ntri;
+    m.color = color && frame.w >= 8 && frame.h >= 8 && frame.d >= 8;
+    const size_t nv = m.nvert;
+    DeviceBuffer active(totals[0] * 8), offsets(totals[0] * 4), dv(nv * 12), dn(nv * 12), dc;
+    if (m.color) dc = DeviceBuffer(nv * 16);
+    if (totals[0])
+        MeshBricksEmit(frame, cell, ids, cells, n, m.color ? color_ids : nullptr, m.color ? color_cells : nullptr, m.color ? n_color : 0, scratch.get(),
+                       nbytes, totals, active.get<long long>(), offsets.get<unsigned>(), dv.get<float>(), dn.get<float>(), dc.get<float>());
+    m.v.resize(nv * 3); m.n.resize(nv * 3); m.c.resize(m.color ? nv * 4 : 0);
+    dv.CopyTo(m.v.data(), nv * 12);
+    dn.CopyTo(m.n.data(), nv * 12);
+    dc.CopyTo(m.c.data(), m.c.size() * 4);
+    if (cube_index) { cube_index->resize(totals[0]); active.CopyTo(cube_index->data(), totals[0] * 8); }
+    if (tri_offset) { tri_offset->resize(totals[0]); offsets.CopyTo(tri_offset->data(), totals[0] * 4); }
+    return m;
+}
+}
+
+// SaveMeshBricks(filename, frame, cell, ids, cells, n[, color_ids, color_cells, n_color]): <filename>.ply through SaveMesh's writer;
+// returns the number of triangles written
+inline size_t SaveMeshBricks(std::string filename, const kfx_volume& frame, int cell, const unsigned* ids, const void* cells, size_t n)
+{
+    return mesh_detail::WritePly(filename + ".ply", mesh_detail::ExtractBricks(frame, cell, ids, cells, n, nullptr, nullptr, 0, false));
+}
+
+inline size_t SaveMeshBricks(std::string filename, const kfx_volume& frame, int cell, const unsigned* ids, const void* cells, size_t n,
+                             const unsigned* color_ids, const void* color_cells, size_t n_color)
+{
+    return mesh_detail::WritePly(filename + ".ply", mesh_detail::ExtractBricks(frame, cell, ids, cells, n, color_ids, color_cells, n_color, true));
 }
 
 }

@@ -3,7 +3,8 @@ boxes of a shift leave and enter, and a whole volume as one file.
 
 A brick is 8 x 8 x 8 cells.  A volume that follows the camera in steps of whole bricks keeps its cells on one world lattice: with
 `origin` the running sum of its shifts (new(x) = old(x + s), so the view's cell 0 is world cell `origin`), the brick at view cell
-(8 i, 8 j, 8 k) has the world key (origin / 8 + (i, j, k)).  Pure numpy up to SaveBricks / LoadBricks, which call the operators.
+(8 i, 8 j, 8 k) has the world key (origin / 8 + (i, j, k)).  world_frame puts a volume's live bricks and its store's on one frame,
+the input of the brick mesh (mesh.ExtractBrickMesh).  Pure numpy up to world_bricks and SaveBricks / LoadBricks, which call the operators.
 """
 import numpy as np
 
@@ -88,6 +89,12 @@ class BrickStore:
         for k, c in zip(keys.tolist(), cells):
             self._bricks[tuple(k)] = c.copy()
 
+    def items(self):
+        """(every key (m, 3) int64, their cells (m, brick bytes) uint8), copies; the store keeps them"""
+        if not self._bricks:
+            return np.empty((0, 3), np.int64), np.empty((0, self.brick_bytes), np.uint8)
+        return np.asarray(list(self._bricks.keys()), np.int64).reshape(-1, 3), np.stack(list(self._bricks.values()))
+
     def take(self, keys):
         """(found keys (m, 3) int64, their cells (m, brick bytes) uint8), in the order of `keys`; what is found leaves the store"""
         keys = np.asarray(keys, np.int64).reshape(-1, 3)
@@ -100,6 +107,66 @@ class BrickStore:
         if not found:
             return np.empty((0, 3), np.int64), np.empty((0, self.brick_bytes), np.uint8)
         return np.asarray(found, np.int64), np.stack(cells)
+
+
+def world_frame(store_keys, live_keys, origin, vol_dims, vol_boxmin, vol_boxmax, cover=None):
+    """The frame of a volume's live bricks and its store's together (numpy only): the bounding box, in whole bricks, of the volume's
+    own box (cells [origin, origin + vol_dims) of the world lattice), the store's keys and the keys of `cover` (a second store whose
+    bricks are to share the frame: a colour store beside the SDF store).
+
+    Returns (lo, dims, boxmin, boxmax, ids, order): lo the frame's first world cell, a multiple of 8; dims its cells; its box in float32
+    from float64 arithmetic on the volume's lattice -- voxel = (vol_boxmax - vol_boxmin) / (vol_dims - 1), boxmin = vol_boxmin +
+    (lo - origin) * voxel, boxmax = vol_boxmin + (lo + dims - 1 - origin) * voxel; ids (uint32, strictly ascending) the brick ids in
+    the frame's grid of all bricks, and order the rows of concatenate([live_keys, store_keys]) they stand for.  store_keys are world
+    keys, live_keys the volume's own brick coordinates (bx, by, bz).  With nothing stored there is no alignment to ask for: the frame
+    is the volume (lo = origin, its dims and its box).  A brick in both lists is refused: the store holds what is OUTSIDE the box."""
+    origin, vol_dims = np.asarray(origin, np.int64), np.asarray(vol_dims, np.int64)
+    store_keys, live_keys = np.asarray(store_keys, np.int64).reshape(-1, 3), np.asarray(live_keys, np.int64).reshape(-1, 3)
+    bmin64, bmax64 = np.asarray(vol_boxmin, np.float32).astype(np.float64), np.asarray(vol_boxmax, np.float32).astype(np.float64)
+    bound = store_keys if cover is None else np.concatenate([store_keys, np.asarray(cover, np.int64).reshape(-1, 3)])
+    if len(bound) == 0:
+        lo, dims, first, vol_first = origin.copy(), vol_dims.copy(), np.zeros(3, np.int64), np.zeros(3, np.int64)
+    else:
+        if np.any(origin % BRICK) or np.any(vol_dims % BRICK):
+            raise ValueError("world_frame: with stored bricks the volume's origin %s and dims %s must be whole bricks" % (tuple(origin), tuple(vol_dims)))
+        first = np.minimum(origin // BRICK, bound.min(0))
+        last = np.maximum((origin + vol_dims) // BRICK, bound.max(0) + 1)
+        lo, dims, vol_first = first * BRICK, (last - first) * BRICK, origin // BRICK
+    rel = np.concatenate([live_keys + vol_first, store_keys]) - first
+    nb = (dims + BRICK - 1) // BRICK
+    ids = (rel[:, 2] * nb[1] + rel[:, 1]) * nb[0] + rel[:, 0]
+    order = np.argsort(ids, kind="stable")
+    ids = ids[order]
+    if np.any(np.diff(ids) == 0):
+        raise ValueError("world_frame: a brick is both in the store and live in the volume")
+    voxel = (bmax64 - bmin64) / (vol_dims - 1).astype(np.float64)
+    boxmin = (bmin64 + (lo - origin).astype(np.float64) * voxel).astype(np.float32)
+    boxmax = (bmin64 + (lo + dims - 1 - origin).astype(np.float64) * voxel).astype(np.float32)
+    return lo, dims, boxmin, boxmax, ids.astype(np.uint32), order
+
+
+def world_bricks(store, vol, origin, fill, ops=None, cover=None):
+    """Everything a moving volume has seen as one brick list: the live bricks of `vol` (ops.BrickPack(vol, fill); its cell 0 is world
+    cell `origin`) merged with the bricks of `store` (None: none) under world keys, on the frame world_frame() gives them (cover: world_frame's).
+    Returns
+    (lo, dims, boxmin, boxmax, ids, cells): ids uint32 (n,) ascending in the frame's grid, on the host; cells a uint8 device tensor
+    (n, brick bytes) in that order -- the live bricks never leave the device.  What mesh.ExtractBrickMesh and ops.BrickUnpack take.
+    The store is left as it is."""
+    import torch
+    if ops is None:
+        from . import roo as ops
+    live_ids, live_cells = ops.BrickPack(vol, fill)
+    dims = (vol.w, vol.h, vol.d)
+    nbx, nby = (vol.w + BRICK - 1) // BRICK, (vol.h + BRICK - 1) // BRICK
+    lid = live_ids.cpu().numpy().view(np.uint32).astype(np.int64)
+    live_keys = np.stack([lid % nbx, (lid // nbx) % nby, lid // (nbx * nby)], 1)
+    store_keys, store_cells = store.items() if store is not None else (np.empty((0, 3), np.int64), None)
+    lo, fdims, boxmin, boxmax, ids, order = world_frame(store_keys, live_keys, origin, dims, vol.boxmin, vol.boxmax, cover)
+    cells = live_cells
+    if len(store_keys):
+        cells = torch.cat([live_cells, torch.from_numpy(store_cells).to(live_cells.device)])
+    cells = cells[torch.from_numpy(order).to(cells.device)].contiguous()
+    return lo, fdims, boxmin, boxmax, ids, cells
 
 
 def SaveBricks(path, vol, fill, ops=None):

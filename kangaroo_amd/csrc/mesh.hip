@@ -18,51 +18,19 @@
 //   indexed (kfx_mesh_index.h: kfx_mesh_index_plan / kfx_mesh_emit_indexed)   the soup's plan, then its vertices welded by lattice edge:
 //               one vertex per edge and a face list, k_mc_emit_indexed.
 // What the emit kernels and the ownership pass share -- the cube's decode and corner read, the vertex's position, attributes and
-// store -- is defined once, so that the indexed mesh stays the weld of the soup bit for bit.
+// store -- is defined once, so that the indexed mesh stays the weld of the soup bit for bit; the part that does not depend on how a
+// cell is read lives in mesh_cube.h, which the extractor of packed bricks (mesh_bricks.hip, kfx_mesh_bricks.h) includes too.
 // The case tables (mc_tables.inc) are derived by scripts/gen_mc_tables.py from the cube's topology; their boundary
 // loops and winding equal the classic tables' in all 256 cases (tests/test_mesh_cpu.py).
-#include "kfx_device.h"
-#include "sampling.h"
-#include "host_args.h"
-#include "block_scan.h"
+#include "mesh_cube.h"   // the case tables and everything about one cube that the brick extractor (mesh_bricks.hip) shares
 #include "../../include/kfx_mesh.h"
 #include "../../include/kfx_mesh_index.h"
 
 namespace kfx {
 
-#include "mc_tables.inc"
-
 __constant__ unsigned char c_num_tris[256];
 __constant__ unsigned short c_edge_mask[256];
 __constant__ signed char c_tris[256][15];
-
-struct MeshParams {
-    VolView vol;
-    V3 size, dims1, hi2, voxel;  // members trilinear<>() / gradient<>() expect
-    V3 inv_size;
-    int fastdiv, off32;
-    int cx, cy, cz;              // cubes per axis = dims - 1
-    int avail_lo, avail_hi;      // planes that may be read: [0, d) of a whole volume, the stored planes of a slab
-};
-
-// corner i of the cube at (x, y, z): offsets (0,0,0) (1,0,0) (1,1,0) (0,1,0) (0,0,1) (1,0,1) (1,1,1) (0,1,1)
-__device__ __forceinline__ int corner_dx(int i) { return ((i + 1) >> 1) & 1; }
-__device__ __forceinline__ int corner_dy(int i) { return (i >> 1) & 1; }
-__device__ __forceinline__ int corner_dz(int i) { return i >> 2; }
-
-// the case index of 8 corner values; false if a corner is not finite (MarchingCubes.h:58-74)
-__device__ __forceinline__ bool corner_case(const float v[8], int& flag)
-{
-    bool finite = true;
-    int bits = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        finite = finite && isfinite(v[i]);
-        if (v[i] <= 0.0f) bits |= 1 << i;
-    }
-    flag = bits;
-    return finite;
-}
 
 // values at the 8 corners and their corner_case.  Half cells are widened
 // exactly (SDF_h's operator float), so a half volume's cubes are those of the widened fp32 volume.
@@ -109,30 +77,6 @@ __global__ __launch_bounds__(256) void k_mc_count(const MeshParams p, unsigned c
     }
 }
 
-// VoxelPositionInUnits(x,y,z) (BoundedVolume.h:115-125): the cube's corner 0
-__device__ __forceinline__ V3 cube_origin(const MeshParams& p, int x, int y, int z)
-{
-    return v3(p.vol.bmin.x + p.size.x * (float)x / p.dims1.x, p.vol.bmin.y + p.size.y * (float)y / p.dims1.y,
-              p.vol.bmin.z + p.size.z * (float)z / p.dims1.z);
-}
-
-// edges 0-3: bottom ring, 4-7: top ring, 8-11: verticals (MarchingCubes tables' numbering); the corners edge e joins
-__device__ __forceinline__ constexpr int edge_c0(int e) { return e < 8 ? e : e - 8; }
-__device__ __forceinline__ constexpr int edge_c1(int e) { return e < 4 ? (e + 1) & 3 : (e < 8 ? 4 + ((e + 1) & 3) : e - 4); }
-
-// the vertex of the cube at p0 (corner values v) on its edge e; VoxelSizeUnits() (BoundedVolume.h:67-76) in p.voxel
-__device__ __forceinline__ V3 edge_position(const MeshParams& p, const V3& p0, const float v[8], int e)
-{
-    const int c0 = edge_c0(e), c1 = edge_c1(e);
-    // fGetOffset (MarchingCubes.h:25-32): the difference is a float, the quotient a double
-    const double delta = (double)(v[c1] - v[c0]);
-    const float off = delta == 0.0 ? 0.5f : (float)((double)(0.0f - v[c0]) / delta);
-    const float ox = (float)corner_dx(c0), oy = (float)corner_dy(c0), oz = (float)corner_dz(c0);
-    const float dx = (float)(corner_dx(c1) - corner_dx(c0)), dy = (float)(corner_dy(c1) - corner_dy(c0)),
-                dz = (float)(corner_dz(c1) - corner_dz(c0));
-    return v3(p0.x + (ox + off * dx) * p.voxel.x, p0.y + (oy + off * dy) * p.voxel.y, p0.z + (oz + off * dz) * p.voxel.z);
-}
-
 // normal and grey colour of the vertex at pos.  SLAB: zero where the planes they read are not stored here
 template <typename CELL, bool SLAB>
 __device__ __forceinline__ void edge_attributes(const MeshParams& p, const ColorGeom& cv, int has_color, const V3& pos, V3& normal, float& grey)
@@ -161,13 +105,6 @@ __device__ __forceinline__ void edge_attributes(const MeshParams& p, const Color
     grey = (has_color && stored) ? trilinear<RayC32>(cv, pos) : 0.f;
 }
 
-__device__ __forceinline__ void cube_xyz(const MeshParams& p, long long ci, int& x, int& y, int& z)
-{
-    z = (int)(ci % p.cz);
-    y = (int)((ci / p.cz) % p.cy);
-    x = (int)(ci / ((long long)p.cz * p.cy));
-}
-
 // A listed cube as its thread sees it: position, case, triangle count, the mask of its edges with a vertex, corner values
 struct ActiveCube {
     int x, y, z, flag, ntri;
@@ -185,18 +122,6 @@ __device__ __forceinline__ bool active_cube(const MeshParams& p, long long ci, A
     c.ntri = c_num_tris[c.flag];
     c.mask = c_edge_mask[c.flag];
     return finite && c.ntri != 0;
-}
-
-// vertex i of the output: position, normal and, with a colour volume, the grey C as ConvertPixel<float3,float>(c) = (c,c,c) in
-// aiColor4D(c, c, c, 1)
-__device__ __forceinline__ void store_vertex(float* verts, float* norms, float* colors, size_t i,
-                                             const V3& P, const V3& N, float C, int has_color)
-{
-    verts[i * 3 + 0] = P.x; verts[i * 3 + 1] = P.y; verts[i * 3 + 2] = P.z;
-    norms[i * 3 + 0] = N.x; norms[i * 3 + 1] = N.y; norms[i * 3 + 2] = N.z;
-    if (has_color) {
-        colors[i * 4 + 0] = C; colors[i * 4 + 1] = C; colors[i * 4 + 2] = C; colors[i * 4 + 3] = 1.0f;
-    }
 }
 
 // One thread per ACTIVE cube (cube_index lists the cubes with triangles in emission order; tri_offset their first
@@ -284,9 +209,6 @@ constexpr int MESH_SEG = 64;         // cubes per segment: 8 segments per column
 constexpr int MESH_SEG_TILE = 32;    // segments per column and count workgroup (grid z covers the rest)
 constexpr int MESH_PER_THREAD = 2;   // segments per thread of the reduce / compact workgroups (small blocks: enough compact waves)
 constexpr int MESH_BLOCK = 256 * MESH_PER_THREAD;
-constexpr int MESH_SCAN_THREADS = 1024, MESH_SCAN_PER_THREAD = 8;
-constexpr unsigned long long MESH_MAX_TRIS = 4294967296ull / 3;   // 2^32 / 3: vertex offsets stay 32-bit
-constexpr size_t MESH_HEADER = 256;
 
 struct MeshRange {
     int zlo, zhi;      // cube planes meshed: [zlo, zhi)
@@ -359,25 +281,6 @@ __global__ __launch_bounds__(256) void k_mesh_count(const MeshParams p, const Me
     }
 }
 
-// the sums of a pair of counters over a workgroup of 256 threads, one value of each per thread: part[2 b] = sum of a,
-// part[2 b + 1] = sum of t for workgroup b (written by its thread 0)
-__device__ __forceinline__ void store_block_sums(unsigned a, unsigned t, unsigned* __restrict__ part)
-{
-    __shared__ unsigned lds[2][4];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        a += __shfl_xor(a, o, 64);
-        t += __shfl_xor(t, o, 64);
-    }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) { lds[0][wv] = a; lds[1][wv] = t; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        part[2 * (size_t)blockIdx.x] = lds[0][0] + lds[0][1] + lds[0][2] + lds[0][3];
-        part[2 * (size_t)blockIdx.x + 1] = lds[1][0] + lds[1][1] + lds[1][2] + lds[1][3];
-    }
-}
-
 // sums of MESH_BLOCK consecutive segments: part[2 b] = active cubes, part[2 b + 1] = triangles
 __global__ __launch_bounds__(256) void k_mesh_reduce(const unsigned short* __restrict__ seg, const MeshRange r, unsigned* __restrict__ part)
 {
@@ -395,40 +298,7 @@ __global__ __launch_bounds__(256) void k_mesh_reduce(const unsigned short* __res
 __global__ __launch_bounds__(MESH_SCAN_THREADS) void k_mesh_scan_partials(const unsigned* __restrict__ part, const long long nblk,
                                                                           unsigned long long* __restrict__ base, unsigned long long* __restrict__ totals)
 {
-    __shared__ unsigned long long lds[2][MESH_SCAN_THREADS / 64];
-    unsigned long long run_a = 0, run_t = 0;
-    constexpr int CHUNK = MESH_SCAN_THREADS * MESH_SCAN_PER_THREAD;
-    for (long long c0 = 0; c0 < nblk; c0 += CHUNK) {
-        const long long b0 = c0 + (long long)threadIdx.x * MESH_SCAN_PER_THREAD;
-        unsigned va[MESH_SCAN_PER_THREAD], vt[MESH_SCAN_PER_THREAD];
-        unsigned long long sa = 0, st = 0;
-#pragma unroll
-        for (int j = 0; j < MESH_SCAN_PER_THREAD; ++j) {
-            const bool in = b0 + j < nblk;
-            va[j] = in ? part[2 * (b0 + j)] : 0u;
-            vt[j] = in ? part[2 * (b0 + j) + 1] : 0u;
-            sa += va[j];
-            st += vt[j];
-        }
-        unsigned long long ta, tt;
-        unsigned long long ea = block_exclusive_scan<unsigned long long, MESH_SCAN_THREADS / 64>(sa, lds[0], &ta) + run_a;
-        unsigned long long et = block_exclusive_scan<unsigned long long, MESH_SCAN_THREADS / 64>(st, lds[1], &tt) + run_t;
-#pragma unroll
-        for (int j = 0; j < MESH_SCAN_PER_THREAD; ++j) {
-            if (b0 + j < nblk) {
-                base[2 * (b0 + j)] = ea;
-                base[2 * (b0 + j) + 1] = et;
-            }
-            ea += va[j];
-            et += vt[j];
-        }
-        run_a += ta;
-        run_t += tt;
-    }
-    if (threadIdx.x == 0) {
-        totals[0] = run_a;
-        totals[1] = run_t;
-    }
+    scan_block_sums(part, nblk, base, totals);
 }
 
 // One workgroup per block of MESH_BLOCK segments: the block's exclusive offsets in LDS (thread t scans its MESH_PER_THREAD
@@ -524,19 +394,6 @@ static int mesh_setup(MeshParams& p, MeshRange& r, const kfx_volume* vol, int ce
     r.nblk = (r.nseg + MESH_BLOCK - 1) / MESH_BLOCK;
     return 0;
 }
-
-// A caller's scratch handed out front to back, every sub-buffer on a 256-byte boundary of it; `bytes` is what has been taken.
-// (An integer address: a layout is also carved from a null scratch, for its size alone.)
-struct Carver {
-    uintptr_t scratch;
-    size_t bytes = 0;
-    template <typename T> T* take(size_t count)
-    {
-        T* const at = (T*)(scratch + bytes);
-        bytes += (count * sizeof(T) + 255) & ~(size_t)255;
-        return at;
-    }
-};
 
 // scratch: [header: totals][segment counts, 2 B, nblk * MESH_BLOCK][block sums, 8 B per block][block offsets, 16 B per block]
 struct MeshScratch {
@@ -746,8 +603,6 @@ static MeshIndexScratch mesh_index_scratch(unsigned long long n_active, const vo
     return s;
 }
 
-static bool totals_in_range(const unsigned long long totals[2]) { return totals[1] < MESH_MAX_TRIS && totals[0] <= totals[1]; }
-
 // the colour volume of a soup or indexed emit (kfx_mesh.h: colorvol)
 static int mesh_color_params(ColorGeom& cv, int& has_color, const kfx_volume* vol, int cell, const kfx_slab* slab, const kfx_volume* colorvol,
                              const float* colors)
@@ -764,24 +619,6 @@ static int mesh_color_params(ColorGeom& cv, int& has_color, const kfx_volume* vo
         if (int e = color_params(cv, has_color, &cfull, colors)) return e;   // (IsValid() of the FULL colour volume)
     }
     if (!has_color) cv = ColorGeom{};
-    return 0;
-}
-
-// n 64-bit words of a scratch header, once the stream's earlier work is done
-static int read_header(unsigned long long* host, const unsigned long long* dev, int n, hipStream_t st)
-{
-    hipError_t e = hipMemcpyAsync(host, dev, (size_t)n * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    return e == hipSuccess ? 0 : set_error((int)e, hipGetErrorString(e));
-}
-
-// "The totals are the plan's": the first n words of a scratch's header are those the caller's totals stand for.  The kernels trust
-// the lists planned in that scratch to fit the buffers the caller sized from its totals.
-static int check_planned(const unsigned long long* hdr, const unsigned long long* want, int n, const char* what, hipStream_t st)
-{
-    unsigned long long planned[4];
-    if (int e = read_header(planned, hdr, n, st)) return e;
-    if (memcmp(planned, want, (size_t)n * 8) != 0) return fail_rule(what, KFX_E_RANGE, "totals are not the plan's");
     return 0;
 }
 

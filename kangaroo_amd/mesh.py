@@ -17,6 +17,10 @@ a grey mesh shrinks from 72 to 24 bytes per triangle (24 V + 12 T) and a colour 
 the faces as they are.
 A slab's indexed mesh is the weld of that rank's soup: vertices on a slab boundary exist once per rank.
 
+Brick mesh (include/kfx_mesh_bricks.h), ExtractBrickMesh / SaveBrickMesh: the soup of packed 8 x 8 x 8 bricks (roo.BrickPack's lists, the
+bricks a moving volume spilled) on a frame of any size -- what ExtractMesh returns for the dense volume those bricks would unpack into,
+cube by cube and bit for bit, listed brick by brick -- with memory in proportion to the bricks, not the frame.
+
 Case tables: kangaroo_amd/csrc/mc_tables.inc, derived by scripts/gen_mc_tables.py.  Their boundary loops and
 winding agree with the classic tables the reference uses in all 256 cases; 158 cases split a polygon along a
 different interior diagonal (an equally valid triangulation of the same loop), so meshes are the same surface
@@ -101,6 +105,84 @@ def ExtractMesh(vol, colorVol=None, stream=None, slab=None, with_index=False, in
     if with_index:
         return verts, norms, colors, cube_index, tri_offset
     return verts, norms, colors
+
+
+BRICK_BYTES = {"f32": 4096, "f16": 2048, "c32": 2048}   # one packed 8 x 8 x 8 brick of each cell kind
+
+
+def _brick_list(what, ids, cells, brick_bytes, dev):
+    """(ids int32 tensor of uint32 bits, cells uint8 tensor, n) on `dev`; host ids are checked to ascend strictly, as roo.BrickUnpack's"""
+    if not torch.is_tensor(ids):
+        host = np.ascontiguousarray(np.asarray(ids).reshape(-1), dtype=np.int64)
+        if host.size and (host.min() < 0 or host.max() > 0xffffffff or np.any(np.diff(host) <= 0)):
+            raise ValueError("%s: ids must be brick ids in strictly ascending order" % what)
+        ids = torch.from_numpy(host.astype(np.uint32).view(np.int32)).to(dev)
+    if not torch.is_tensor(cells):
+        cells = torch.from_numpy(np.ascontiguousarray(cells).view(np.uint8).reshape(-1)).to(dev)
+    ids, cells = ids.contiguous(), cells.contiguous()
+    n = ids.numel()
+    if cells.numel() * cells.element_size() != n * brick_bytes:
+        raise ValueError("%s: %d ids need %d bytes of cells, got %d" % (what, n, n * brick_bytes, cells.numel() * cells.element_size()))
+    return ids, cells, n
+
+
+def BrickMeshScratchBytes(n, n_color=0):
+    """kfx_mesh_bricks_scratch_bytes: the scratch of a brick mesh of n SDF and n_color colour bricks -- whatever the frame."""
+    return int(_lib.load().kfx_mesh_bricks_scratch_bytes(int(n), int(n_color)))
+
+
+def ExtractBrickMesh(dims, boxmin, boxmax, kind, ids, cells, color_ids=None, color_cells=None, with_index=False, stream=None):
+    """The mesh of packed 8 x 8 x 8 bricks (include/kfx_mesh_bricks.h): what ExtractMesh returns for the dense volume of `dims` cells and
+    the box (boxmin, boxmax) that is NaN everywhere and then gets BrickUnpack(ids, cells) -- the same cubes, each with the same triangles
+    bit for bit -- without that volume; memory in proportion to the bricks and the mesh.  Only the order differs: brick by brick in
+    ascending id, within a brick by ascending cube index (with_index=True returns cube_index and tri_offset, as ExtractMesh).
+
+    kind "f32" or "f16"; ids / cells as roo.BrickPack returns them for a view of these dimensions: torch tensors, or host arrays, which
+    are uploaded (host ids are checked to ascend strictly).  color_ids / color_cells: a second list of "c32" bricks on the same frame;
+    an absent colour brick reads 0.5.  Colours are returned when color_ids is given and every dimension is >= 8."""
+    L = _lib.load()
+    if kind not in CELL:
+        raise ValueError("ExtractBrickMesh: cell kind %r (fp32 or half SDF cells)" % (kind,))
+    if (color_ids is None) != (color_cells is None):
+        raise ValueError("ExtractBrickMesh: color_ids and color_cells come together (both, or neither)")
+    device = ids.device if torch.is_tensor(ids) else (cells.device if torch.is_tensor(cells) else torch.device("cuda", torch.cuda.current_device()))
+    ids, cells, n = _brick_list("ExtractBrickMesh", ids, cells, BRICK_BYTES[kind], device)
+    want_color = color_ids is not None and min(int(d) for d in dims) >= 8
+    cids, ccells, nc = (None, None, 0)
+    if want_color:
+        cids, ccells, nc = _brick_list("ExtractBrickMesh(colour)", color_ids, color_cells, BRICK_BYTES["c32"], device)
+    frame = _lib.KfxVolume(0, None, int(dims[0]), int(dims[1]), 0, int(dims[2]))
+    for i in range(3):
+        frame.boxmin[i], frame.boxmax[i] = float(np.float32(boxmin[i])), float(np.float32(boxmax[i]))
+    empty = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=device)
+    nbytes = BrickMeshScratchBytes(n, nc)   # (0: the counts are refused -- the plan says why)
+    scratch = empty(max(nbytes, 256), torch.uint8)
+    totals = (C.c_ulonglong * 2)()
+    st = _stream(stream)
+    lists = (_ptr(ids) if n else None, _ptr(cells) if n else None, n)
+    code = L.kfx_mesh_bricks_plan(C.byref(frame), CELL[kind], *lists, _ptr(scratch), nbytes, totals, st)
+    if code == -4 and totals[1] >= 2 ** 32 // 3:   # KFX_E_RANGE
+        raise ValueError("mesh too large for 32-bit vertex offsets")
+    _lib.check(code)
+    na, ntri = int(totals[0]), int(totals[1])
+    verts, norms = empty((3 * ntri, 3), torch.float32), empty((3 * ntri, 3), torch.float32)
+    colors = empty((3 * ntri, 4), torch.float32) if want_color else None
+    cube_index, tri_offset = empty(na, torch.int64), empty(na, torch.int32)
+    if na:
+        _lib.check(L.kfx_mesh_bricks_emit(C.byref(frame), CELL[kind], *lists, _ptr(cids) if nc else None, _ptr(ccells) if nc else None, nc,
+                                          _ptr(scratch), nbytes, totals, _ptr(cube_index), _ptr(tri_offset), _ptr(verts), _ptr(norms),
+                                          _ptr(colors), st))
+    if with_index:
+        return verts, norms, colors, cube_index, tri_offset
+    return verts, norms, colors
+
+
+def SaveBrickMesh(filename, dims, boxmin, boxmax, kind, ids, cells, color_ids=None, color_cells=None, binary=True):
+    """ExtractBrickMesh's mesh as filename + ".ply" (write_ply); returns the triangle count."""
+    verts, norms, colors = ExtractBrickMesh(dims, boxmin, boxmax, kind, ids, cells, color_ids, color_cells)
+    torch.cuda.synchronize() if verts.is_cuda else None
+    write_ply(filename + ".ply", verts.cpu().numpy(), norms.cpu().numpy(), None if colors is None else colors.cpu().numpy(), binary)
+    return len(verts) // 3
 
 
 def write_ply(path, verts, norms, colors=None, binary=True, faces=None):

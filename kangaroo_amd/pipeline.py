@@ -296,6 +296,36 @@ class FramePipeline:
                 n += len(keys)
         return n
 
+    def world_bricks(self):
+        """Everything the model holds as brick lists on one frame: (sdf, colour) with each bricks.world_bricks()'s tuple (lo, dims,
+        boxmin, boxmax, ids, cells) -- the live volume's bricks and, with follow=dict(spill=True), the store's; colour None without
+        color=True.  The two lists share the frame (each covers the other's store).  The stores are left as they are."""
+        if not hasattr(self.ops, "BrickPack"):
+            raise ValueError("FramePipeline: the world mesh needs an operator set with BrickPack")
+        ckeys = self.cstore.items()[0] if self.cstore is not None else None
+        sdf = bricks.world_bricks(self.store, self.vol, self.origin, float("nan"), ops=self.ops, cover=ckeys)
+        if not self.color:
+            return sdf, None
+        skeys = self.store.items()[0] if self.store is not None else None
+        return sdf, bricks.world_bricks(self.cstore, self.cvol, self.origin, 0.5, ops=self.ops, cover=skeys)
+
+    def ExtractWorldMesh(self, with_index=False):
+        """The mesh of everything the model has seen -- the live volume and what it spilled -- as mesh.ExtractBrickMesh returns it:
+        continuous across the faces of the volume that no longer exist.  Without a store: the brick mesh of the live volume."""
+        from . import mesh
+        (lo, dims, bmin, bmax, ids, cells), col = self.world_bricks()
+        cids, ccells = (col[4], col[5]) if col is not None else (None, None)
+        return mesh.ExtractBrickMesh(dims, bmin, bmax, self.kind, ids, cells, cids, ccells, with_index=with_index)
+
+    def SaveWorldMesh(self, filename, binary=True):
+        """ExtractWorldMesh's mesh as filename + ".ply"; returns the triangle count."""
+        import torch
+        from . import mesh
+        verts, norms, colors = self.ExtractWorldMesh()
+        torch.cuda.synchronize() if verts.is_cuda else None
+        mesh.write_ply(filename + ".ply", verts.cpu().numpy(), norms.cpu().numpy(), None if colors is None else colors.cpu().numpy(), binary)
+        return len(verts) // 3
+
     def _follow(self, T_wc):
         """follow=: the shift this pose asks for, applied before the frame's first launch"""
         f = self.follow
@@ -880,6 +910,10 @@ class SlabPipeline(FramePipeline):
                 ops.append(dist.P2POp(dist.isend, vol.planes(own1 - hi_ghost, own1), self.rank + 1))
                 ops.append(dist.P2POp(dist.irecv, vol.planes(own1, own1 + hi_ghost), self.rank + 1))
         self._p2p(ops)
+
+    def world_bricks(self):
+        raise ValueError("SlabPipeline: the world mesh belongs to a volume that follows the camera (follow=), a single-volume option; "
+                         "a rank's part of the model's mesh is ExtractMesh")
 
     def ExtractMesh(self, indexed=False):
         """This rank's part of the model's mesh (include/kfx_mesh.h): the cubes whose lower plane it owns, [z0, min(z1, D - 1)),

@@ -1,0 +1,17 @@
+"""roo::MeshBricksPlan / MeshBricksEmit / SaveMeshBricks from C++ (include/kangaroo/VolumeBricks.h over include/kfx_mesh_bricks.h): a
+small volume is packed, its bricks are meshed, the volume is meshed, and the two are compared by cube (apps/roo_brick_mesh_test)."""
+import os
+import subprocess
+
+import pytest
+
+import kfx_testlib as T
+
+APPS = os.path.join(T.ROOT, "apps")
+pytestmark = pytest.mark.gpu
+
+
+def test_cpp_roo_brick_mesh_test():
+    subprocess.check_call(["make", "-C", APPS, "roo_brick_mesh_test"], stdout=subprocess.DEVNULL)
+    out = subprocess.run([os.path.join(APPS, "roo_brick_mesh_test")], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "passed" in out.stdout, out.stdout + out.stderr
