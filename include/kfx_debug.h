@@ -48,6 +48,16 @@ int kfx_debug_summary_export(kfx_sdf_summary* s, float tol, float vref, int fine
  * builds that built, out[1] = conditional builds that returned early, both since the summary was created (waits for `stream`). */
 int kfx_debug_summary_conditional_builds(kfx_sdf_summary* s, int out[2], kfx_stream stream);
 
+/* The 64^3- and 128^3-cell levels of the class tables the summary holds (the words behind those kfx_debug_summary_export copies;
+ * same two planes per entry, an entry = the combination of the 2 x 2 x 2 entries of the level below, edge entries repeating a
+ * neighbour), as the last build for a fine level of 2^fine_shift cells left them: call kfx_debug_summary_export with C_out
+ * first, which brings the tables up to date.  dims_out = {64^3 level: first word in top_out, words per row, entries along y, x,
+ * z, words of the level; the same six for the 128^3 level}.  top_out: device buffer of dims_out[5] + dims_out[11] words (NULL:
+ * the layout only).  launches_out (may be NULL): kernel launches the table builds of this summary have issued since it was
+ * created -- a host-side counter, one launch per build while the tables are staged in LDS. */
+int kfx_debug_summary_top_levels(kfx_sdf_summary* s, int fine_shift, void* top_out, int dims_out[12], unsigned long long* launches_out,
+                                 kfx_stream stream);
+
 /* The kept set of the last tracked SdfFuse launch on the summary's volume (KFX_FUSE_KEEP_MB): the rows of y-bricks (8 voxel
  * rows each, indexed in the summary's volume) whose cells the launch read with ordinary loads, so that they stay in the
  * memory-side cache for the next frame.  out = {stride (0: nothing kept), first row the launch covered, rows it covered};

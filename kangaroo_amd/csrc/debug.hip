@@ -267,6 +267,14 @@ extern "C" int kfx_debug_rmw(const kfx_volume* vol, int variant, kfx_stream stre
     return check_launch("kfx_debug_rmw");
 }
 
+// the count the last table build issued has published (-1: it has not yet; -2: no build so far, or no ring)
+static int last_published(const kfx_sdf_summary* s)
+{
+    if (!s->h_skippable || !s->builds) return -2;
+    const uint64_t v = __atomic_load_n(s->h_skippable + summary_ring_index(s->builds - 1), __ATOMIC_ACQUIRE);
+    return summary_ring_slot_stamp(v) == summary_ring_stamp(s->builds - 1) ? summary_ring_slot_count(v) : -1;
+}
+
 // test / diagnostics aid (include/kfx_debug.h): copies of R (float4 per brick) and of the class tables built for (tol, vref,
 // fine_shift) into caller buffers
 extern "C" int kfx_debug_summary_export(kfx_sdf_summary* s, float tol, float vref, int fine_shift, void* R_out, void* C_out, int dims_out[12],
@@ -279,7 +287,7 @@ extern "C" int kfx_debug_summary_export(kfx_sdf_summary* s, float tol, float vre
     dims_out[0] = s->nbx; dims_out[1] = s->nby; dims_out[2] = s->nbz;
     dims_out[3] = cv.fine.first; dims_out[4] = cv.fine.rw; dims_out[5] = cv.fine.ny;
     dims_out[6] = cv.coarse.first; dims_out[7] = cv.coarse.rw; dims_out[8] = cv.coarse.ny;
-    dims_out[9] = cv.words; dims_out[10] = s->n_coarse; dims_out[11] = (s->h_skippable && s->builds) ? ((volatile int*)s->h_skippable)[(s->builds - 1) % KFX_SUMMARY_RING] : -2;
+    dims_out[9] = cv.words; dims_out[10] = s->n_coarse; dims_out[11] = last_published(s);
     const size_t n = (size_t)s->nbx * s->nby * s->nbz;
     hipStream_t st = (hipStream_t)stream;
     if (R_out && hipMemcpyAsync(R_out, s->R, n * sizeof(float4), hipMemcpyDeviceToDevice, st) != hipSuccess) return set_error(KFX_E_RANGE, "kfx_debug_summary_export: copy");
@@ -287,7 +295,7 @@ extern "C" int kfx_debug_summary_export(kfx_sdf_summary* s, float tol, float vre
         if (int e = summary_classes_prepare(s, tol, vref, fine_shift, st)) return e;
         if (hipMemcpyAsync(C_out, s->C, (size_t)cv.words * sizeof(unsigned), hipMemcpyDeviceToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
             return set_error(KFX_E_RANGE, "kfx_debug_summary_export: copy");
-        dims_out[11] = (s->h_skippable && s->builds) ? ((volatile int*)s->h_skippable)[(s->builds - 1) % KFX_SUMMARY_RING] : -2;   // (the build has finished: its count is published)
+        dims_out[11] = last_published(s);   // (the build has finished: its count is published)
     }
     return 0;
 }
@@ -298,6 +306,29 @@ extern "C" int kfx_debug_summary_conditional_builds(kfx_sdf_summary* s, int out[
     hipStream_t st = (hipStream_t)stream;
     if (hipMemcpyAsync(out, s->d_count + 3, 2 * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
         return set_error(KFX_E_RANGE, "kfx_debug_summary_conditional_builds: copy");
+    return 0;
+}
+
+extern "C" int kfx_debug_summary_top_levels(kfx_sdf_summary* s, int fine_shift, void* top_out, int dims_out[12], unsigned long long* launches_out, kfx_stream stream)
+{
+    if (!s || !dims_out) return set_error(KFX_E_NULL, "kfx_debug_summary_top_levels: null argument");
+    if (fine_shift < 3 || fine_shift > 5) return set_error(KFX_E_RANGE, "kfx_debug_summary_top_levels: fine_shift in [3, 5]");
+    ClassView cv;
+    summary_class_layout(s, fine_shift, cv);
+    cv.nx5 = ceil_div(s->w, 32); cv.nz5 = ceil_div(s->d, 32);
+    ClassLevel l6, l7;
+    int w6, w7;
+    summary_top_layout(cv, l6, l7, w6, w7);
+    const int nx6 = (cv.nx5 + 1) >> 1, nz6 = (cv.nz5 + 1) >> 1;
+    dims_out[0] = l6.first - cv.words; dims_out[1] = l6.rw; dims_out[2] = l6.ny; dims_out[3] = nx6; dims_out[4] = nz6; dims_out[5] = w6;
+    dims_out[6] = l7.first - cv.words; dims_out[7] = l7.rw; dims_out[8] = l7.ny; dims_out[9] = (nx6 + 1) >> 1; dims_out[10] = (nz6 + 1) >> 1; dims_out[11] = w7;
+    if (launches_out) *launches_out = s->launches;
+    if (top_out) {
+        if (s->c_shift != fine_shift) return set_error(KFX_E_RANGE, "kfx_debug_summary_top_levels: the tables held were built for another fine level");
+        hipStream_t st = (hipStream_t)stream;
+        if (hipMemcpyAsync(top_out, s->C + cv.words, (size_t)(w6 + w7) * sizeof(unsigned), hipMemcpyDeviceToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+            return set_error(KFX_E_RANGE, "kfx_debug_summary_top_levels: copy");
+    }
     return 0;
 }
 

@@ -15,6 +15,7 @@
 #include "../../include/kfx_extras.h"
 #include "../../include/kfx_summary_h.h"
 #include "../../include/kfx_color.h"
+#include "summary_ring_host.h"
 
 namespace kfx {
 
@@ -227,7 +228,7 @@ __host__ __device__ inline bool keep_row(int row, int stride) { return stride > 
 // R: one float4 {lo, hi, state, -} per 8 x 8 x 8 cells, kept current by the TRACK fuse kernels (state 0: every cell holds
 // a value in [lo, hi]; 1: every cell is NaN; 2: every cell is NaN or holds a value in [lo, hi] -- an invalidated brick has
 // the infinite range).  C: what the ray-march reads (ClassView below), built from R on demand.
-#define KFX_SUMMARY_RING 8
+// (KFX_SUMMARY_RING and the layout of a ring slot: summary_ring_host.h)
 struct kfx_sdf_summary {
     float4* R;
     int nbx, nby, nbz;
@@ -243,20 +244,22 @@ struct kfx_sdf_summary {
     int c_shift;                 // fine level C was built for (log2 of its cells per entry)
     int c_global;                // C also holds the 64^3- and 128^3-cell levels (the global-table mode, raycast.hip class_view)
     int n_coarse;                // 32^3-cell entries
-    // device: {running count of 32^3-cell entries of class != 0, workgroups that have added theirs, the count of the last real
-    // build, conditional builds that built, conditional builds that returned early}
+    // device: {running count of 32^3-cell entries of class != 0, workgroups of the build's counting launch that have arrived
+    // (all of them, those of the fine level included, where one launch builds both levels), the count of the last real build,
+    // conditional builds that built, conditional builds that returned early -- one increment of either per conditional build}
     int* d_count;
     // device word: some brick's class mask (brick_class_mask) changed since C was built.  Set by the tracked SdfFuse kernels,
-    // read by the conditional table builds (summary.hip), cleared by the last workgroup of a build.
+    // read by every workgroup of a conditional table build (summary.hip) before anything else, cleared by the last one to arrive.
     int* d_dirty;
-    // The table builds publish their count of 32^3-cell entries of class != 0 in a host-visible ring (pinned, mapped): build b
-    // writes slot b % KFX_SUMMARY_RING and records build_done[b % KFX_SUMMARY_RING] behind it.  The tracked raycast chooses its
-    // kernel from the count of build b - 2 (raycast.hip, class_view): old enough to have finished without anybody waiting,
-    // and -- unlike "whatever the last finished build said" -- the same choice for the same sequence of calls.
-    int* h_skippable;            // the ring, host address (nullptr: no pinned memory; the tables are always used)
-    int* d_skippable;            // the ring, device address
-    hipEvent_t build_done[8];
+    // The table builds publish their count of 32^3-cell entries of class != 0 in a host-visible ring (pinned, mapped) of 64-bit
+    // slots {stamp of the build, count} (summary_ring_host.h): build b writes slot b % KFX_SUMMARY_RING with one system-scope
+    // store, nothing is recorded behind it.  The tracked raycast chooses its kernel from the count of build b - 2 (raycast.hip,
+    // class_view): old enough to have finished without anybody waiting -- the slot carries that build's stamp by then, and the
+    // reader looks until it does -- and, unlike "whatever the last finished build said", the same choice for the same sequence of calls.
+    unsigned long long* h_skippable;   // the ring, host address (nullptr: no pinned memory; the tables are always used)
+    unsigned long long* d_skippable;   // the ring, device address
     unsigned builds;             // table builds issued so far
+    unsigned long long launches; // kernel launches summary_classes_prepare has issued so far (kfx_debug_summary_top_levels)
     unsigned plain_calls;        // tracked raycasts since the choice last fell on the plain march (the tables are then rebuilt every 8th call only)
     unsigned sweeps;             // tracked SdfFuse launches so far: every other one walks the planes from the far end (fuse.hip)
     // the kept set of the last tracked SdfFuse launch (fuse.hip, fuse_launch; read by kfx_debug_fuse_keep): the y-brick rows

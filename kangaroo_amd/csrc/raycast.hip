@@ -9,6 +9,7 @@
 // the gradient stencil is 20 distinct cells instead of 32 loads; missed rays skip the
 // (discarded) normal evaluation of the reference.
 #include <cmath>
+#include <thread>
 
 #include <hip/hip_fp16.h>
 
@@ -457,7 +458,7 @@ __device__ __forceinline__ float raycast_pixel_classes(const RayParams& p, const
 
 // workgroup prologue of the class-table kernels: the tables into LDS (16-byte loads, all in flight together) -- the fine and the
 // 32^3-cell level and, behind them, as many of the 64^3- and 128^3-cell levels as the march consults (cl.top_n): the table
-// build derived those once (k_summary_classes_coarse, summary.hip), nothing is derived here
+// build derived those once (classes_count_and_top, summary.hip), nothing is derived here
 // (GT: only the 64^3- and 128^3-cell levels, staged at word 0)
 template <bool GT = false>
 __device__ __forceinline__ void classes_stage(const ClassView& cl, unsigned* tab, TopLevels& top)
@@ -970,7 +971,7 @@ static int class_view(ClassView& cl, size_t* lds_bytes, int* usable, kfx_sdf_sum
     // Worth it?  The march through the tables costs ~8 % per sampled step (table look-ups, staging); it pays where a fair part
     // of the volume can be crossed without sampling: at least a quarter of the 32^3-cell entries of class != 0.  Every table
     // build publishes that count in a host-visible ring; the choice is made from the count of the build BEFORE THE PREVIOUS ONE
-    // (two frames old: finished long ago, so the event wait below returns at once) -- it only steers a choice between two
+    // (two frames old: finished long ago, so its slot carries its stamp at the first look below) -- it only steers a choice between two
     // kernels that render the same images, but in fast numerics "the same" means within tolerance, so the choice is made a
     // function of the sequence of calls, not of how far the GPU happens to have got (round-3 advice).  Exact numerics on a
     // running stream, where only never-observed space qualifies, fall back to the plain march this way; while the choice is
@@ -981,10 +982,23 @@ static int class_view(ClassView& cl, size_t* lds_bytes, int* usable, kfx_sdf_sum
     if (steer && summary->plain_calls && (summary->plain_calls++ % 8u) != 0u) return 0;   // still plain: no build, no look
     if (int e = summary_classes_prepare(summary, tol, vref, fine, (hipStream_t)stream, cl.global)) return e;
     if (steer && summary->builds >= 3) {
-        const unsigned ref = (summary->builds - 3) % KFX_SUMMARY_RING;   // builds - 1 is the one just issued (or the last one)
-        (void)hipEventSynchronize(summary->build_done[ref]);
-        const int known = ((volatile int*)summary->h_skippable)[ref];
-        if (known >= 0 && (long long)known * 4 < summary->n_coarse) {   // less than a quarter
+        // builds - 1 is the one just issued (or the last one).  Build builds - 3 has published long ago as a rule: its slot
+        // carries its stamp at the first look.  With the host far ahead of the stream the looks go on, the thread yielding in
+        // between -- 2^20 of them at most (a second or so), then the stream is synchronised and the slot looked at once more; a
+        // slot that does not carry the stamp even then (a build on a stream that does not make progress) is an error, never a count.
+        const unsigned ref = summary->builds - 3;
+        const unsigned long long* slot = summary->h_skippable + summary_ring_index(ref);
+        int known = 0;
+        const int seen = summary_ring_wait(
+            ref, 1ull << 20,
+            [&]() {
+                const uint64_t v = __atomic_load_n(slot, __ATOMIC_ACQUIRE);
+                if (summary_ring_slot_stamp(v) != summary_ring_stamp(ref)) std::this_thread::yield();
+                return v;
+            },
+            [&]() { (void)hipStreamSynchronize((hipStream_t)stream); }, &known);
+        if (seen < 0) return set_error(KFX_E_TIMEOUT, "RaycastSdf(tracked): the class-table build the choice of the march rests on has not published its count");
+        if ((long long)known * 4 < summary->n_coarse) {   // less than a quarter
             if (!summary->plain_calls) summary->plain_calls = 1;
             return 0;
         }

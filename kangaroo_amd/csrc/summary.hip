@@ -21,12 +21,15 @@ __global__ __launch_bounds__(256) void k_summary_fill(float4* __restrict__ R, si
 // the wave's ballots.
 //   fine level (2^shift cells, shift 3 or 4): from the summary bricks [b << (shift - 3), (b + 1) << (shift - 3)] per axis
 //   (the last one holds the +1 cells), clamped to the grid;
-//   32^3-cell level: from the fine level's entries -- the cells [32 c, 32 c + 32] of entry c are exactly those of the fine
-//   entries [c m, c m + m) per axis (m = 32 >> shift; each fine entry already includes its +1 cells), so the class is the
-//   combination of m^3 two-bit reads instead of 125 brick ranges.  `src` = the fine level's words (same kernel, second launch).
-// count != nullptr (the 32^3-cell level): the waves add up their entries of class != 0; the last one to arrive publishes the
-// total in host-visible memory (*publish) and clears the counters for the next build -- the host reads that word without
-// synchronising (raycast.hip, class_view).
+//   32^3-cell level: the cells [32 c, 32 c + 32] of entry c are exactly those of the fine entries [c m, c m + m) per axis
+//   (m = 32 >> shift; each fine entry already includes its +1 cells), i.e. of the bricks [4 c, 4 c + 4], and a class is an AND
+//   over bricks: the same bits either from the 125 brick ranges (M = 4) or from m^3 two-bit reads of the fine level's words
+//   (M = 0, `src`).  LDS mode: from R, by further workgroups of the launch that builds the fine level -- no workgroup reads
+//   what another one of the launch writes, so one launch per build does (k_summary_classes_build).  Global-table mode (built on
+//   every call, tables of ~2000^3 volumes): from the fine level's words, in a launch of its own behind the fine level's.
+// The workgroups of the 32^3-cell level add up their entries of class != 0; the last workgroup to arrive publishes the total
+// with the build's stamp in host-visible memory (*publish) and clears the counters for the next build -- the host reads that
+// slot without synchronising (raycast.hip, class_view; summary_ring_host.h).
 struct ClassBuild {
     const float4* R;
     unsigned* C;
@@ -85,16 +88,26 @@ __device__ __forceinline__ int class_row(const ClassBuild& b, const long long wa
                             all_either = all_either && c != 0;
                         }
             }
-        } else if constexpr (M > 2) {   // 125 ranges per entry: a loop (volumes whose finer tables do not fit LDS)
+        } else if constexpr (M > 2) {
+            // 125 ranges per entry: loops over z and y (kept loops: unrolled, or with a plane's 25 ranges requested together, the
+            // build kernel spills 16-34 SGPRs and its no-fine-level variant takes scratch), the five ranges of a row along x
+            // requested together
+#pragma unroll 1
             for (int z = bz * M; z <= bz * M + M; ++z)
-                for (int y = by * M; y <= by * M + M; ++y)
-                    for (int x = bx * M; x <= bx * M + M; ++x) {
-                        const float4 r = R[((size_t)min(z, nbz - 1) * nby + min(y, nby - 1)) * nbx + min(x, nbx - 1)];
-                        const unsigned m = brick_class_mask(r.x, r.y, __float_as_int(r.z), lo_ok, hi_ok);
+#pragma unroll 1
+                for (int y = by * M; y <= by * M + M; ++y) {
+                    const float4* __restrict__ Rrow = R + ((size_t)min(z, nbz - 1) * nby + min(y, nby - 1)) * nbx;
+                    float4 r[M + 1];
+#pragma unroll
+                    for (int dx = 0; dx <= M; ++dx) r[dx] = Rrow[min(bx * M + dx, nbx - 1)];
+#pragma unroll
+                    for (int dx = 0; dx <= M; ++dx) {
+                        const unsigned m = brick_class_mask(r[dx].x, r[dx].y, __float_as_int(r[dx].z), lo_ok, hi_ok);
                         all_nan = all_nan && (m & 1u);
                         all_free = all_free && (m & 2u);
                         all_either = all_either && (m & 4u);
                     }
+                }
         } else {
             // (M + 1)^3 brick ranges, all requested before the first is looked at (fully unrolled: the loop form waited for
             // each row of loads in turn, 9.5 us per launch at 512^3 against ~3)
@@ -126,42 +139,37 @@ __device__ __forceinline__ int class_row(const ClassBuild& b, const long long wa
     return __popcll(p0 | p1);
 }
 
-// the fine level: one wave per row of 64 entries.  dirty != nullptr (a conditional build: the host knows of nothing but tracked
-// SdfFuse launches since the last build): the tables are rebuilt only if one of those launches saw a brick change its class
-// mask (*dirty, kfx_sdf_summary::d_dirty); otherwise they are the bits this launch would write.
-template <int M>
-__global__ __launch_bounds__(256) void k_summary_classes(const ClassBuild b, const long long n_waves, const int* __restrict__ dirty)
+// What the workgroups of a build's counting launch do first (conditional: the host knows of nothing but tracked SdfFuse launches
+// since the last build): the tables are rebuilt only if one of those launches saw a brick change its class mask (*dirty,
+// kfx_sdf_summary::d_dirty); otherwise they are the bits this launch would write, nothing is built, and one thread publishes
+// the retained total under this build's stamp, so the host sees what it would have seen.  Every workgroup reads *dirty before
+// any other work; true: leave.
+__device__ __forceinline__ bool classes_up_to_date(int* __restrict__ count, unsigned long long* __restrict__ publish, const unsigned stamp,
+                                                   const int* __restrict__ dirty, const int conditional)
 {
-    if (dirty && *dirty == 0) return;   // (uniform)
-    const long long wave = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (wave < n_waves) class_row<M>(b, wave);
+    if (!conditional || *dirty != 0) return false;   // (uniform)
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        __hip_atomic_store(publish, ((unsigned long long)stamp << 32) | (unsigned)count[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        count[4] += 1;
+    }
+    return true;
 }
 
-// the 32^3-cell level: the workgroups add up their entries of class != 0 (LDS), take a ticket, and the last one publishes the
-// total in host-visible memory and clears the counters for the next build -- the host reads that word without synchronising
-// (raycast.hip, class_view).  count = {running total, tickets taken, the total of the last real build, conditional builds that
-// built, conditional builds that returned early}.  conditional: as k_summary_classes -- with *dirty == 0 nothing is built and
-// one thread publishes the retained total, so the host sees what it would have seen.  The last workgroup of a real build
-// retains the total and clears *dirty: every workgroup of both launches has read it by then.  It also derives the two coarser
-// levels (TopBuild) from rows that other workgroups -- on other XCDs, whose L2s are not coherent with this one's -- wrote: the
-// writers' agent-scope fence before the ticket and this workgroup's agent-scope fence after it order those rows before the reads.
-template <int M>
-__global__ __launch_bounds__(256) void k_summary_classes_coarse(const ClassBuild b, const long long n_waves, int* __restrict__ count, int* __restrict__ publish,
-                                                                int* __restrict__ dirty, const int conditional, const TopBuild t)
+// ... and last.  n: this wave's entries of the 32^3-cell level with class != 0 (lane 0; 0 for a wave that built fine rows).  The
+// workgroups add theirs up (LDS), take a ticket, and the last of ALL the launch's workgroups publishes the total with the
+// build's stamp in one 64-bit store to host-visible memory and clears the counters for the next build.  count = {running total,
+// tickets taken, the total of the last real build, conditional builds that built, conditional builds that returned early}.  The
+// last workgroup retains the total and clears *dirty: every workgroup of the launch -- of both levels: a ticket over the
+// 32^3-cell level's alone would let a fine workgroup dispatched late read the cleared word and leave stale rows -- has read it
+// by then.  It also derives the two coarser levels (TopBuild) from rows that other workgroups -- on other XCDs, whose L2s are
+// not coherent with this one's -- wrote: the writers' agent-scope fence before the ticket and this workgroup's agent-scope
+// fence after it order those rows before the reads.
+__device__ __forceinline__ void classes_count_and_top(const int n, int* __restrict__ count, unsigned long long* __restrict__ publish, const unsigned stamp,
+                                                      int* __restrict__ dirty, const int conditional, const TopBuild& t)
 {
     __shared__ int s_count[4];
     __shared__ int s_last;
-    if (conditional && *dirty == 0) {   // (uniform)
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            __hip_atomic_store(publish, count[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            count[4] += 1;
-        }
-        return;
-    }
-    const int wv = threadIdx.x >> 6;
-    const long long wave = (long long)blockIdx.x * 4 + wv;
-    const int n = wave < n_waves ? class_row<M>(b, wave) : 0;
-    if ((threadIdx.x & 63) == 0) s_count[wv] = n;
+    if ((threadIdx.x & 63) == 0) s_count[threadIdx.x >> 6] = n;
     __threadfence();   // (release, agent scope: this thread's rows, for the workgroup that derives the coarser levels)
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -176,7 +184,7 @@ __global__ __launch_bounds__(256) void k_summary_classes_coarse(const ClassBuild
             count[2] = total;
             if (conditional) count[3] += 1;
             *dirty = 0;
-            __hip_atomic_store(publish, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(publish, ((unsigned long long)stamp << 32) | (unsigned)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
     __syncthreads();
@@ -187,6 +195,56 @@ __global__ __launch_bounds__(256) void k_summary_classes_coarse(const ClassBuild
         __syncthreads();
         classes_level_up(t.tab, t.l6, t.nx6, t.nz6, t.l7, t.nx7, t.nz7);
     }
+}
+
+// LDS mode, one launch per build: workgroups [0, f.blocks) write the fine level's rows (MF = 1: 8^3 cells, 2: 16^3, 0: no fine
+// level, f.blocks = 0), the others the 32^3-cell level's (c) straight from R.  No workgroup waits for another.
+struct FineRows {   // what the fine level's ClassBuild differs in from the 32^3-cell level's
+    unsigned* C;
+    int shift, nx, ny, nz, rw;
+    int blocks;
+    long long waves;
+};
+template <int MF>
+__global__ __launch_bounds__(256) void k_summary_classes_build(const FineRows f, const ClassBuild c, const long long c_waves, int* __restrict__ count,
+                                                               unsigned long long* __restrict__ publish, const unsigned stamp, int* __restrict__ dirty,
+                                                               const int conditional, const TopBuild t)
+{
+    if (classes_up_to_date(count, publish, stamp, dirty, conditional)) return;
+    int n = 0;
+    bool fine_row = false;
+    if constexpr (MF != 0) {
+        fine_row = (int)blockIdx.x < f.blocks;   // (uniform)
+        if (fine_row) {
+            ClassBuild b = c;
+            b.C = f.C; b.shift = f.shift; b.nx = f.nx; b.ny = f.ny; b.nz = f.nz; b.rw = f.rw;
+            const long long wave = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+            if (wave < f.waves) class_row<MF>(b, wave);
+        }
+    }
+    if (!fine_row) {
+        const long long wave = (long long)((int)blockIdx.x - f.blocks) * 4 + (threadIdx.x >> 6);
+        if (wave < c_waves) n = class_row<4>(c, wave);
+    }
+    classes_count_and_top(n, count, publish, stamp, dirty, conditional, t);
+}
+
+// Global-table mode: a level in a launch of its own, one wave per row of 64 entries (M = 1, 2: the fine level; 0: the 64^3- and
+// 128^3-cell levels, each from the level below it) ...
+template <int M>
+__global__ __launch_bounds__(256) void k_summary_classes(const ClassBuild b, const long long n_waves)
+{
+    const long long wave = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (wave < n_waves) class_row<M>(b, wave);
+}
+
+// ... and the 32^3-cell level from the fine level's words, with the count (never conditional: this mode builds on every call)
+__global__ __launch_bounds__(256) void k_summary_classes_coarse(const ClassBuild b, const long long n_waves, int* __restrict__ count,
+                                                                unsigned long long* __restrict__ publish, const unsigned stamp, int* __restrict__ dirty, const TopBuild t)
+{
+    const long long wave = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int n = wave < n_waves ? class_row<0>(b, wave) : 0;
+    classes_count_and_top(n, count, publish, stamp, dirty, 0, t);
 }
 
 // kfx_sdf_summary_rebuild: R from the volume itself.  One wave per 8 x 8 x 8 brick: a lane reads one row of eight cells (four
@@ -289,11 +347,10 @@ int summary_classes_prepare(kfx_sdf_summary* s, float tol, float vref, int fine_
 {
     const bool same = s->c_tol == tol && s->c_vref == vref && s->c_shift == fine_shift && s->c_global == global;
     if (!s->c_dirty && same) return 0;
-    // Only tracked SdfFuse launches since the tables were built for these parameters: the same launches, which return at once
-    // unless one of those saw a brick change its class mask (d_dirty).  Everything else -- and the global-table mode, whose two
-    // further levels are built by launches of their own and which the headline does not run -- builds unconditionally.
+    // Only tracked SdfFuse launches since the tables were built for these parameters: the same launch, which returns at once
+    // unless one of those saw a brick change its class mask (d_dirty).  Everything else -- and the global-table mode, whose
+    // levels are built by launches of their own and which the headline does not run -- builds unconditionally.
     const int conditional = (s->c_dirty == 1 && same && !global) ? 1 : 0;
-    const int* fine_dirty = conditional ? s->d_dirty : nullptr;
     ClassView cv;
     summary_class_layout(s, fine_shift, cv);
     cv.nx5 = ceil_div(s->w, 32); cv.nz5 = ceil_div(s->d, 32);
@@ -308,50 +365,57 @@ int summary_classes_prepare(kfx_sdf_summary* s, float tol, float vref, int fine_
     top.nx6 = (top.nx5 + 1) >> 1; top.nz6 = (top.nz5 + 1) >> 1;
     top.nx7 = (top.nx6 + 1) >> 1; top.nz7 = (top.nz6 + 1) >> 1;
     const float lo_ok = vref - tol * vref, hi_ok = vref + tol * vref;
-    for (int pass = 0; pass < (global ? 4 : 2); ++pass) {
-        if (pass >= 2) {
-            // global-table mode: the 64^3- and 128^3-cell levels, each the combination of the level below it (m = 2) -- the
-            // same entries classes_level_up derives in the LDS mode's build
-            const ClassLevel& L = pass == 2 ? l6 : l7;
-            const ClassLevel& S = pass == 2 ? cv.coarse : l6;
-            ClassBuild b;
-            b.R = s->R; b.C = s->C + L.first;
-            b.nbx = s->nbx; b.nby = s->nby; b.nbz = s->nbz;
-            b.shift = L.shift; b.nx = ceil_div(s->w, 1 << L.shift); b.ny = L.ny; b.nz = ceil_div(s->d, 1 << L.shift); b.rw = L.rw;
-            b.lo_ok = lo_ok; b.hi_ok = hi_ok;
-            b.src = s->C + S.first;
-            b.src_shift = S.shift; b.src_nx = ceil_div(s->w, 1 << S.shift); b.src_ny = S.ny; b.src_nz = ceil_div(s->d, 1 << S.shift); b.src_rw = S.rw;
-            const long long waves = (long long)ceil_div(b.nx, 64) * b.ny * b.nz;
-            hipLaunchKernelGGL(k_summary_classes<0>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, b, waves, (const int*)nullptr);
-            if (int e = check_launch("kfx_sdf_summary (classes)")) return e;
-            continue;
-        }
-        const ClassLevel& L = pass ? cv.coarse : cv.fine;
-        if (!pass && fine_shift >= 5) continue;
+    // the rows of level L: from R, or (src) from the words of the level below it
+    auto level = [&](const ClassLevel& L, const ClassLevel* src) {
+        const ClassLevel& S = src ? *src : L;
         ClassBuild b;
         b.R = s->R; b.C = s->C + L.first;
         b.nbx = s->nbx; b.nby = s->nby; b.nbz = s->nbz;
         b.shift = L.shift; b.nx = ceil_div(s->w, 1 << L.shift); b.ny = L.ny; b.nz = ceil_div(s->d, 1 << L.shift); b.rw = L.rw;
         b.lo_ok = lo_ok; b.hi_ok = hi_ok;
-        const bool from_fine = pass && fine_shift < 5;   // the 32^3-cell level combines the fine level's entries
-        b.src = from_fine ? s->C + cv.fine.first : nullptr;
-        b.src_shift = cv.fine.shift; b.src_nx = ceil_div(s->w, 1 << cv.fine.shift); b.src_ny = cv.fine.ny;
-        b.src_nz = ceil_div(s->d, 1 << cv.fine.shift); b.src_rw = cv.fine.rw;
-        const long long waves = (long long)ceil_div(b.nx, 64) * b.ny * b.nz;
-        if (pass) {
-            const dim3 grid((unsigned)((waves + 3) / 4));
-            const unsigned slot = s->builds % KFX_SUMMARY_RING;
-            int* publish = s->d_skippable + (s->h_skippable ? slot : 0);
-            if (from_fine) hipLaunchKernelGGL(k_summary_classes_coarse<0>, grid, dim3(256), 0, stream, b, waves, s->d_count, publish, s->d_dirty, conditional, top);
-            else hipLaunchKernelGGL(k_summary_classes_coarse<4>, grid, dim3(256), 0, stream, b, waves, s->d_count, publish, s->d_dirty, conditional, top);
-            if (s->h_skippable) (void)hipEventRecord(s->build_done[slot], stream);
-            s->builds += 1;
-        } else if (L.shift == 3) {
-            hipLaunchKernelGGL(k_summary_classes<1>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, b, waves, fine_dirty);
-        } else {
-            hipLaunchKernelGGL(k_summary_classes<2>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, b, waves, fine_dirty);
+        b.src = src ? s->C + S.first : nullptr;
+        b.src_shift = S.shift; b.src_nx = ceil_div(s->w, 1 << S.shift); b.src_ny = S.ny; b.src_nz = ceil_div(s->d, 1 << S.shift); b.src_rw = S.rw;
+        return b;
+    };
+    auto waves_of = [](const ClassBuild& b) { return (long long)ceil_div(b.nx, 64) * b.ny * b.nz; };
+    auto blocks_of = [&](const ClassBuild& b) { return (unsigned)((waves_of(b) + 3) / 4); };
+    auto launched = [&]() { s->launches += 1; return check_launch("kfx_sdf_summary (classes)"); };
+    const bool has_fine = fine_shift < 5;
+    // build number s->builds: its stamp, and its slot of the ring (without pinned memory: a device word nobody reads)
+    const unsigned stamp = summary_ring_stamp(s->builds);
+    unsigned long long* publish = s->d_skippable + (s->h_skippable ? summary_ring_index(s->builds) : 0);
+    if (global && has_fine) {
+        // global-table mode: the fine level, then the 32^3-cell level from its words with the count
+        const ClassBuild f = level(cv.fine, nullptr), c = level(cv.coarse, &cv.fine);
+        if (cv.fine.shift == 3) hipLaunchKernelGGL(k_summary_classes<1>, dim3(blocks_of(f)), dim3(256), 0, stream, f, waves_of(f));
+        else hipLaunchKernelGGL(k_summary_classes<2>, dim3(blocks_of(f)), dim3(256), 0, stream, f, waves_of(f));
+        if (int e = launched()) return e;
+        hipLaunchKernelGGL(k_summary_classes_coarse, dim3(blocks_of(c)), dim3(256), 0, stream, c, waves_of(c), s->d_count, publish, stamp, s->d_dirty, top);
+        if (int e = launched()) return e;
+    } else {
+        // one launch: the fine level's workgroups (none where the 32^3-cell level is the finest), then the 32^3-cell level's
+        const ClassBuild c = level(cv.coarse, nullptr);
+        FineRows f{};
+        if (has_fine) {
+            const ClassBuild b = level(cv.fine, nullptr);
+            f.C = b.C; f.shift = b.shift; f.nx = b.nx; f.ny = b.ny; f.nz = b.nz; f.rw = b.rw;
+            f.blocks = (int)blocks_of(b); f.waves = waves_of(b);
         }
-        if (int e = check_launch("kfx_sdf_summary (classes)")) return e;
+        const dim3 grid((unsigned)f.blocks + blocks_of(c));
+        if (!has_fine) hipLaunchKernelGGL(k_summary_classes_build<0>, grid, dim3(256), 0, stream, f, c, waves_of(c), s->d_count, publish, stamp, s->d_dirty, conditional, top);
+        else if (cv.fine.shift == 3) hipLaunchKernelGGL(k_summary_classes_build<1>, grid, dim3(256), 0, stream, f, c, waves_of(c), s->d_count, publish, stamp, s->d_dirty, conditional, top);
+        else hipLaunchKernelGGL(k_summary_classes_build<2>, grid, dim3(256), 0, stream, f, c, waves_of(c), s->d_count, publish, stamp, s->d_dirty, conditional, top);
+        if (int e = launched()) return e;
+    }
+    s->builds += 1;
+    if (global) {
+        // global-table mode: the 64^3- and 128^3-cell levels, each the combination of the level below it (m = 2) -- the same
+        // entries classes_level_up derives in the LDS mode's build
+        for (int up = 0; up < 2; ++up) {
+            const ClassBuild b = level(up ? l7 : l6, up ? &l6 : &cv.coarse);
+            hipLaunchKernelGGL(k_summary_classes<0>, dim3(blocks_of(b)), dim3(256), 0, stream, b, waves_of(b));
+            if (int e = launched()) return e;
+        }
     }
     s->c_dirty = 0; s->c_tol = tol; s->c_vref = vref; s->c_shift = fine_shift; s->c_global = global;
     s->c_lo_ok = lo_ok; s->c_hi_ok = hi_ok;
@@ -392,8 +456,7 @@ static int summary_create(kfx_sdf_summary** out, const kfx_volume* vol, int cell
     s->c_dirty = 2; s->c_tol = -1.f; s->c_vref = 0.f; s->c_shift = 0; s->c_global = 0; s->sweeps = 0;
     s->keep_stride = 0; s->keep_row0 = 0; s->keep_rows = 0;
     s->c_lo_ok = 0.f; s->c_hi_ok = 0.f; s->d_dirty = nullptr;
-    s->builds = 0; s->plain_calls = 0;
-    for (auto& e : s->build_done) e = nullptr;
+    s->builds = 0; s->plain_calls = 0; s->launches = 0;
     s->n_coarse = ceil_div(s->w, 32) * ceil_div(s->h, 32) * ceil_div(s->d, 32);
     const size_t n = (size_t)s->nbx * s->nby * s->nbz;
     ClassView cv;
@@ -406,13 +469,11 @@ static int summary_create(kfx_sdf_summary** out, const kfx_volume* vol, int cell
     bool ok = hipMalloc((void**)&s->R, n * sizeof(float4)) == hipSuccess && hipMalloc((void**)&s->C, (size_t)words * sizeof(unsigned)) == hipSuccess &&
               hipMalloc((void**)&s->d_count, 64 * sizeof(int)) == hipSuccess && hipMemset(s->d_count, 0, 64 * sizeof(int)) == hipSuccess;
     if (ok) s->d_dirty = s->d_count + 32;   // (a cache line of its own: the kernels that set it store plainly, the counters are atomics)
-    // the published count lives in pinned host memory the device can write; without it the march always uses the tables
-    if (ok && hipHostMalloc((void**)&s->h_skippable, KFX_SUMMARY_RING * sizeof(int), hipHostMallocMapped) == hipSuccess) {
-        for (int i = 0; i < KFX_SUMMARY_RING; ++i) s->h_skippable[i] = -1;
-        bool evs = hipHostGetDevicePointer((void**)&s->d_skippable, s->h_skippable, 0) == hipSuccess;
-        for (int i = 0; evs && i < KFX_SUMMARY_RING; ++i) evs = hipEventCreateWithFlags(&s->build_done[i], hipEventDisableTiming) == hipSuccess;
-        if (!evs) {
-            for (auto& e : s->build_done) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    // the published counts live in pinned host memory the device can write (mapped: coherent, a system-scope store is seen by
+    // the host while the stream runs on); without it the march always uses the tables.  Slots start unstamped (zero).
+    if (ok && hipHostMalloc((void**)&s->h_skippable, KFX_SUMMARY_RING * sizeof(unsigned long long), hipHostMallocMapped) == hipSuccess) {
+        for (int i = 0; i < KFX_SUMMARY_RING; ++i) s->h_skippable[i] = 0ull;
+        if (hipHostGetDevicePointer((void**)&s->d_skippable, s->h_skippable, 0) != hipSuccess) {
             (void)hipHostFree(s->h_skippable);
             s->h_skippable = nullptr;
         }
@@ -421,7 +482,7 @@ static int summary_create(kfx_sdf_summary** out, const kfx_volume* vol, int cell
     }
     if (ok && !s->h_skippable) {   // a device word nobody reads keeps the kernel's interface the same
         (void)hipGetLastError();
-        ok = hipMalloc((void**)&s->d_skippable, sizeof(int)) == hipSuccess;
+        ok = hipMalloc((void**)&s->d_skippable, sizeof(unsigned long long)) == hipSuccess;
     }
     if (!ok) {
         (void)hipGetLastError();
@@ -442,7 +503,6 @@ extern "C" int kfx_sdf_summary_destroy(kfx_sdf_summary* s)
     if (s->R) (void)hipFree(s->R);
     if (s->C) (void)hipFree(s->C);
     if (s->d_count) (void)hipFree(s->d_count);
-    for (auto& e : s->build_done) if (e) (void)hipEventDestroy(e);
     if (s->h_skippable) (void)hipHostFree(s->h_skippable);
     else if (s->d_skippable) (void)hipFree(s->d_skippable);
     delete s;
