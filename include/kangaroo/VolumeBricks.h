@@ -21,8 +21,10 @@
 #include <kangaroo/VolumeShift.h>
 #include <kangaroo/launch_utils.h>
 #include <kangaroo/MarchingCubes.h>
+#include <kangaroo/cu_raycast.h>
 #include <kfx_bricks.h>
 #include <kfx_mesh_bricks.h>
+#include <kfx_raycast_bricks.h>
 
 namespace roo
 {
@@ -136,6 +138,43 @@ inline size_t SaveMeshBricks(std::string filename, const kfx_volume& frame, int 
                              const unsigned* color_ids, const void* color_cells, size_t n_color)
 {
     return mesh_detail::WritePly(filename + ".ply", mesh_detail::ExtractBricks(frame, cell, ids, cells, n, color_ids, color_cells, n_color, true));
+}
+
+// ---- RaycastSdf of packed bricks (kfx_raycast_bricks_*, include/kfx_raycast_bricks.h): RaycastSdf's images of the volume the bricks
+// would unpack into -- NaN where no brick is listed, colour 0.5 -- without that volume, bit for bit.  One plan serves any number of views.
+//
+//   roo::Image<unsigned char, roo::TargetDevice, roo::Manage> plan(roo::RaycastBricksScratchBytes(n), 1);
+//   roo::RaycastBricksPlan(frame, ids.ptr, n, plan.ptr, plan.w);                                     // no read-back
+//   roo::RaycastSdfBricks(depth, norm, img, frame, KFX_CELL_F32, ids.ptr, cells.ptr, n, plan.ptr, plan.w, T_wc, K, near, far, trunc, true);
+
+inline size_t RaycastBricksScratchBytes(size_t n, size_t n_color = 0) { return kfx_raycast_bricks_scratch_bytes(n, n_color); }
+
+inline void RaycastBricksPlan(const kfx_volume& frame, const unsigned* ids, size_t n, void* scratch, size_t scratch_bytes)
+{
+    GpuCheckStatus(kfx_raycast_bricks_plan(&frame, ids, n, nullptr, 0, scratch, scratch_bytes, 0));
+}
+
+inline void RaycastBricksPlan(const kfx_volume& frame, const unsigned* ids, size_t n, const unsigned* color_ids, size_t n_color, void* scratch,
+                              size_t scratch_bytes)
+{
+    GpuCheckStatus(kfx_raycast_bricks_plan(&frame, ids, n, color_ids, n_color, scratch, scratch_bytes, 0));
+}
+
+inline void RaycastSdfBricks(Image<float> depth, Image<float4> norm, Image<float> img, const kfx_volume& frame, int cell, const unsigned* ids,
+                             const void* cells, size_t n, const void* scratch, size_t scratch_bytes, const Mat<float, 3, 4> T_wc, ImageIntrinsics K,
+                             float near, float far, float trunc_dist, bool subpix = true)
+{
+    GpuCheckStatus(kfx_raycast_bricks(depth.abi(), norm.abi(), img.abi(), &frame, cell, ids, cells, n, nullptr, nullptr, 0, 0, scratch, scratch_bytes,
+                                      T_wc.m, &K.fu, near, far, trunc_dist, subpix ? 1 : 0, 0));
+}
+
+// the colour overload: img = the colour bricks' trilinear sample at the hit, 0.5 where no colour brick is listed (fp32 SDF cells)
+inline void RaycastSdfBricks(Image<float> depth, Image<float4> norm, Image<float> img, const kfx_volume& frame, const unsigned* ids, const void* cells,
+                             size_t n, const unsigned* color_ids, const void* color_cells, size_t n_color, const void* scratch, size_t scratch_bytes,
+                             const Mat<float, 3, 4> T_wc, ImageIntrinsics K, float near, float far, float trunc_dist, bool subpix = true)
+{
+    GpuCheckStatus(kfx_raycast_bricks(depth.abi(), norm.abi(), img.abi(), &frame, KFX_CELL_F32, ids, cells, n, color_ids, color_cells, n_color, 1,
+                                      scratch, scratch_bytes, T_wc.m, &K.fu, near, far, trunc_dist, subpix ? 1 : 0, 0));
 }
 
 }

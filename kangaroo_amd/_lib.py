@@ -216,6 +216,11 @@ SIGNATURES = {
     "kfx_mesh_bricks_plan": (C.c_int, [PV, C.c_int, C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_void_p, C.c_size_t, C.POINTER(C.c_ulonglong), C.c_void_p]),
     "kfx_mesh_bricks_emit": (C.c_int, [PV, C.c_int, C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_void_p, C.c_size_t,
                                        C.POINTER(C.c_ulonglong), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # include/kfx_raycast_bricks.h
+    "kfx_raycast_bricks_scratch_bytes": (C.c_size_t, [C.c_ulonglong, C.c_ulonglong]),
+    "kfx_raycast_bricks_plan": (C.c_int, [PV, C.c_void_p, C.c_ulonglong, C.c_void_p, C.c_ulonglong, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "kfx_raycast_bricks": (C.c_int, [PI, PI, PI, PV, C.c_int, C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_int,
+                                     C.c_void_p, C.c_size_t, PF, PF, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p]),
 }
 
 _lib = None

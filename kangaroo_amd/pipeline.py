@@ -47,6 +47,16 @@ def follow_shift(boxmin, boxmax, dims, T_wc, focus, quantum=8, slack=16):
     return tuple(0 if abs(v) < slack else int(q * np.rint(v / q)) for v in o)
 
 
+class WorldView:
+    """What FramePipeline.world_view() returns: the model's brick lists on one frame (bricks.world_bricks) and the plan of their
+    ray-cast (ops.RaycastBricksPlan), device tensors kept alive here.  lo: the frame's first world cell; dims, boxmin, boxmax: the frame;
+    ids / cells the SDF list (cells of `kind`), cids / ccells the colour list (None without colour); plan: the scratch."""
+
+    def __init__(self, kind, lo, dims, boxmin, boxmax, ids, cells, cids, ccells, plan):
+        self.kind, self.lo, self.dims, self.boxmin, self.boxmax = kind, tuple(int(v) for v in lo), tuple(int(v) for v in dims), boxmin, boxmax
+        self.ids, self.cells, self.cids, self.ccells, self.plan = ids, cells, cids, ccells, plan
+
+
 class FramePipeline:
     # track="auto": the stream itself is the benchmark.  From frame CAL_FIRST on, three blocks of CAL_BLOCK frames each:
     # tracked pair (SdfFuse keeping the summary + march through the class tables), plain pair (the summary goes stale), tracked
@@ -325,6 +335,45 @@ class FramePipeline:
         torch.cuda.synchronize() if verts.is_cuda else None
         mesh.write_ply(filename + ".ply", verts.cpu().numpy(), norms.cpu().numpy(), None if colors is None else colors.cpu().numpy(), binary)
         return len(verts) // 3
+
+    def world_view(self):
+        """Everything the model holds, ready to be rendered (include/kfx_raycast_bricks.h): world_bricks() packed and planned once.
+        Returns a WorldView that keeps the lists, the frame and the plan alive; RaycastWorld(..., view=) renders it from any number of
+        poses.  It is the caller's snapshot: a later frame or shift changes the model, not the view."""
+        import torch
+        if not hasattr(self.ops, "RaycastSdfBricks"):
+            raise ValueError("FramePipeline: the world view needs an operator set with RaycastSdfBricks")
+        (lo, dims, bmin, bmax, ids, cells), col = self.world_bricks()
+        dev = cells.device
+        ids = torch.from_numpy(np.ascontiguousarray(ids, np.uint32).view(np.int32)).to(dev)
+        cids = ccells = None
+        if col is not None:
+            cids, ccells = torch.from_numpy(np.ascontiguousarray(col[4], np.uint32).view(np.int32)).to(dev), col[5]
+        plan = self.ops.RaycastBricksPlan(dims, ids, cids)
+        return WorldView(self.kind, lo, dims, bmin, bmax, ids, cells, cids, ccells, plan)
+
+    def RaycastWorld(self, T_wc, K=None, w=None, h=None, color=False, view=None):
+        """The model seen from T_wc -- the live volume and what it spilled, so also from a pose that looks back at where the camera
+        has been: (depth, norm, img), new images of w x h pixels (default: the pipeline's) at the intrinsics K (default: the
+        pipeline's), RaycastSdf's of the dense volume of the whole walk, bit for bit; color=True (a color=True pipeline): RaycastSdfColor's.
+        view: a world_view() to render (None: one is taken for this call).  Without a store (no follow=dict(spill=True)) and without
+        a view the live volume is the world, and it is rendered as it is."""
+        if color and not self.color:
+            raise ValueError("FramePipeline: RaycastWorld(color=True) needs a color=True pipeline")
+        w, h = int(self.w if w is None else w), int(self.h if h is None else h)
+        K = self.K if K is None else np.asarray(K, np.float32)
+        I = self.ops.Image
+        out = (I(w, h, "f32"), I(w, h, "f32x4"), I(w, h, "f32"))
+        if view is None and self.store is None:
+            if color:
+                self.ops.RaycastSdfColor(*out, self.vol, self.cvol, T_wc, K, self.near, self.far, self.trunc, True)
+            else:
+                self.ops.RaycastSdf(*out, self.vol, T_wc, K, self.near, self.far, self.trunc, True)
+            return out
+        v = self.world_view() if view is None else view
+        self.ops.RaycastSdfBricks(*out, v.dims, v.boxmin, v.boxmax, v.kind, v.ids, v.cells, T_wc, K, self.near, self.far, self.trunc, True,
+                                  cids=v.cids, ccells=v.ccells, color=color, plan=v.plan)
+        return out
 
     def _follow(self, T_wc):
         """follow=: the shift this pose asks for, applied before the frame's first launch"""
@@ -914,6 +963,10 @@ class SlabPipeline(FramePipeline):
     def world_bricks(self):
         raise ValueError("SlabPipeline: the world mesh belongs to a volume that follows the camera (follow=), a single-volume option; "
                          "a rank's part of the model's mesh is ExtractMesh")
+
+    def RaycastWorld(self, *args, **kw):
+        raise ValueError("SlabPipeline: the world view belongs to a volume that follows the camera (follow=), a single-volume option; "
+                         "the model's rendering is the frame's composite")
 
     def ExtractMesh(self, indexed=False):
         """This rank's part of the model's mesh (include/kfx_mesh.h): the cubes whose lower plane it owns, [z0, min(z1, D - 1)),

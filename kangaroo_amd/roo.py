@@ -702,6 +702,94 @@ def VolumeFill(vol, fill, stream=None):
     _lib.check(_lib.load().kfx_volume_shift(vol.ref(), CELL_KIND[vol.kind], _shift3((vol.w, 0, 0)), float(fill), None, 0, _stream(stream)))
 
 
+# ---- RaycastSdf straight from packed bricks (include/kfx_raycast_bricks.h) --------------
+
+def _brick_ids(what, ids, dev):
+    """ids as an int32 device tensor of uint32 bits; host ids are checked to ascend strictly, as BrickUnpack's"""
+    if not torch.is_tensor(ids):
+        host = np.ascontiguousarray(np.asarray(ids).reshape(-1), dtype=np.int64)
+        if host.size and (host.min() < 0 or host.max() > 0xffffffff or np.any(np.diff(host) <= 0)):
+            raise ValueError("%s: ids must be brick ids in strictly ascending order" % what)
+        ids = torch.from_numpy(host.astype(np.uint32).view(np.int32)).to(dev)
+    return ids.contiguous()
+
+
+def _brick_cells(what, cells, n, nbytes, dev):
+    if not torch.is_tensor(cells):
+        cells = torch.from_numpy(np.ascontiguousarray(cells).view(np.uint8).reshape(-1)).to(dev)
+    cells = cells.contiguous()
+    if cells.numel() * cells.element_size() != n * nbytes:
+        raise ValueError("%s: %d ids need %d bytes of cells, got %d" % (what, n, n * nbytes, cells.numel() * cells.element_size()))
+    return cells
+
+
+def _brick_frame(dims, boxmin, boxmax):
+    """a frame: the dimensions and the box of a kfx_volume, no storage"""
+    frame = KfxVolume(0, None, int(dims[0]), int(dims[1]), 0, int(dims[2]))
+    for i in range(3):
+        frame.boxmin[i], frame.boxmax[i] = float(np.float32(boxmin[i])), float(np.float32(boxmax[i]))
+    return frame
+
+
+def _device_of(*tensors):
+    for t in tensors:
+        if torch.is_tensor(t):
+            return t.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def RaycastBricksScratchBytes(n, n_color=0):
+    """kfx_raycast_bricks_scratch_bytes: the scratch of a brick ray-cast of n SDF and n_color colour bricks -- whatever the frame."""
+    return int(_lib.load().kfx_raycast_bricks_scratch_bytes(int(n), int(n_color)))
+
+
+def RaycastBricksPlan(dims, ids, cids=None, stream=None):
+    """kfx_raycast_bricks_plan: the tables from brick id to list position a RaycastSdfBricks of these lists reads, for a frame of `dims`
+    cells.  Returns the scratch, a uint8 device tensor; it serves any number of renderings of the same lists (ids, and cids if given,
+    as roo.BrickPack returns them: device tensors, or host arrays, which are uploaded).  Nothing is read back."""
+    dev = _device_of(ids, cids)
+    ids = _brick_ids("RaycastBricksPlan", ids, dev)
+    cids = None if cids is None else _brick_ids("RaycastBricksPlan(colour)", cids, dev)
+    n, nc = ids.numel(), 0 if cids is None else cids.numel()
+    nbytes = RaycastBricksScratchBytes(n, nc)
+    scratch = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+    frame = _brick_frame(dims, (0, 0, 0), (1, 1, 1))   # (a plan reads the dimensions only)
+    _lib.check(_lib.load().kfx_raycast_bricks_plan(C.byref(frame), ids.data_ptr() if n else None, n, cids.data_ptr() if nc else None, nc,
+                                                   scratch.data_ptr(), nbytes, _stream(stream)))
+    return scratch
+
+
+def RaycastSdfBricks(depth, norm, img, dims, boxmin, boxmax, kind, ids, cells, T_wc, K, near, far, trunc, subpix=True, cids=None, ccells=None,
+                     color=False, plan=None, stream=None):
+    """RaycastSdf of packed 8 x 8 x 8 bricks (include/kfx_raycast_bricks.h): the images RaycastSdf writes for the dense volume of `dims`
+    cells and the box (boxmin, boxmax) that is NaN everywhere and then gets BrickUnpack(ids, cells), bit for bit, without that volume.
+    kind "f32" or "f16"; ids / cells as roo.BrickPack returns them for a view of these dimensions.  color=True: RaycastSdfColor's images
+    with the colour volume that is 0.5 everywhere and then gets the "c32" bricks (cids, ccells) unpacked (none given: img = 0.5 at every
+    hit); fp32 cells.  plan: RaycastBricksPlan(dims, ids, cids)'s scratch for these lists (None: planned here, for this call)."""
+    if kind not in ("f32", "f16"):
+        raise ValueError("RaycastSdfBricks: cell kind %r (fp32 or half SDF cells)" % (kind,))
+    if (cids is None) != (ccells is None):
+        raise ValueError("RaycastSdfBricks: cids and ccells come together (both, or neither)")
+    dev = _device_of(ids, cells, depth.storage)
+    ids = _brick_ids("RaycastSdfBricks", ids, dev)
+    n = ids.numel()
+    cells = _brick_cells("RaycastSdfBricks", cells, n, BRICK ** 3 * {"f32": 8, "f16": 4}[kind], dev)
+    nc = 0
+    if cids is not None:
+        cids = _brick_ids("RaycastSdfBricks(colour)", cids, dev)
+        nc = cids.numel()
+        ccells = _brick_cells("RaycastSdfBricks(colour)", ccells, nc, BRICK ** 3 * 4, dev)
+    if plan is None:
+        plan = RaycastBricksPlan(dims, ids, cids, stream)
+    frame = _brick_frame(dims, boxmin, boxmax)
+    t, _t = _fp(T_wc, 12)
+    k, _k = _fp(K, 4)
+    _lib.check(_lib.load().kfx_raycast_bricks(depth.ref(), norm.ref(), img.ref(), C.byref(frame), CELL_KIND[kind], ids.data_ptr() if n else None,
+                                              cells.data_ptr() if n else None, n, cids.data_ptr() if nc else None, ccells.data_ptr() if nc else None,
+                                              nc, 1 if color else 0, plan.data_ptr(), plan.numel(), t, k, near, far, trunc, 1 if subpix else 0,
+                                              _stream(stream)))
+
+
 def ElementwiseScaleBias(b, a, s, offset=0.0, stream=None):
     """roo::ElementwiseScaleBias<float,float,float> and <float,unsigned short,float> (cu_operations.h; main.cpp:207-208):
     b = s*a + offset, a of kind "f32" or "u16"."""
