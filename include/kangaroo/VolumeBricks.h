@@ -25,6 +25,7 @@
 #include <kfx_bricks.h>
 #include <kfx_mesh_bricks.h>
 #include <kfx_raycast_bricks.h>
+#include <kfx_brick_pool.h>
 
 namespace roo
 {
@@ -59,6 +60,61 @@ template<typename T, typename M>
 inline void BrickUnpack(BoundedVolume<T, TargetDevice, M>& vol, const unsigned* ids, const void* cells, size_t n)
 {
     GpuCheckStatus(kfx_bricks_unpack(vol.abi(), shift_detail::Cell<T>::kind, ids, cells, n, 0));
+}
+
+// ---- the brick pool (kfx_brick_pool_*, include/kfx_brick_pool.h): device memory of the caller that keeps the live bricks a moving
+// volume leaves behind under world brick keys, and gives them back; spill and restore are launches on the stream, nothing on the host.
+// T is the cell type of the volumes the pool serves -- SDF_t, SDF_h or float -- deduced where a volume is an argument.  key0: the world
+// key of the view's brick (0, 0, 0).
+//
+//   const size_t cap = 4096, bytes = roo::BrickPoolBytes<roo::SDF_t>(cap);
+//   roo::Image<unsigned char, roo::TargetDevice, roo::Manage> pool(bytes, 1), scratch(roo::BrickPoolScratchBytes(vol, cap), 1);
+//   roo::BrickPoolInit<roo::SDF_t>(pool.ptr, bytes, cap);
+//   roo::BrickPoolSpill(pool.ptr, bytes, cap, vol.SubVolume(...), NAN, key0, scratch.ptr, scratch.w);      // before the shift
+//   roo::BrickPoolRestore(pool.ptr, bytes, cap, vol.SubVolume(...), key1, scratch.ptr, scratch.w);         // after it
+//   unsigned long long st[4]; roo::BrickPoolStats<roo::SDF_t>(pool.ptr, bytes, cap, st);                   // {occupied, spilled, restored, dropped}
+
+template<typename T>
+inline size_t BrickPoolBytes(size_t capacity) { return kfx_brick_pool_bytes(shift_detail::Cell<T>::kind, capacity); }
+
+template<typename T, typename M>
+inline size_t BrickPoolScratchBytes(const BoundedVolume<T, TargetDevice, M>& view, size_t capacity)
+{
+    return kfx_brick_pool_scratch_bytes(view.abi(), shift_detail::Cell<T>::kind, capacity);
+}
+
+template<typename T>
+inline void BrickPoolInit(void* pool, size_t pool_bytes, size_t capacity)
+{
+    GpuCheckStatus(kfx_brick_pool_init(pool, pool_bytes, shift_detail::Cell<T>::kind, capacity, 0));
+}
+
+template<typename T, typename M>
+inline void BrickPoolSpill(void* pool, size_t pool_bytes, size_t capacity, const BoundedVolume<T, TargetDevice, M>& view, float fill, const int key0[3],
+                           void* scratch, size_t scratch_bytes)
+{
+    GpuCheckStatus(kfx_brick_pool_spill(pool, pool_bytes, shift_detail::Cell<T>::kind, capacity, view.abi(), fill, key0, scratch, scratch_bytes, 0));
+}
+
+template<typename T, typename M>
+inline void BrickPoolRestore(void* pool, size_t pool_bytes, size_t capacity, const BoundedVolume<T, TargetDevice, M>& view, const int key0[3], void* scratch,
+                             size_t scratch_bytes)
+{
+    GpuCheckStatus(kfx_brick_pool_restore(pool, pool_bytes, shift_detail::Cell<T>::kind, capacity, view.abi(), key0, scratch, scratch_bytes, 0));
+}
+
+// blocking: out = {occupied, spilled, restored, dropped}
+template<typename T>
+inline void BrickPoolStats(const void* pool, size_t pool_bytes, size_t capacity, unsigned long long out[4])
+{
+    GpuCheckStatus(kfx_brick_pool_stats(pool, pool_bytes, shift_detail::Cell<T>::kind, capacity, out, 0));
+}
+
+// cells_out[i] = the 512 cells of slot slots[i] (device lists)
+template<typename T>
+inline void BrickPoolGather(const void* pool, size_t pool_bytes, size_t capacity, const unsigned* slots, size_t n, void* cells_out)
+{
+    GpuCheckStatus(kfx_brick_pool_gather(pool, pool_bytes, shift_detail::Cell<T>::kind, capacity, slots, n, cells_out, 0));
 }
 
 // ---- the mesh of packed bricks (kfx_mesh_bricks_*, include/kfx_mesh_bricks.h): SaveMesh's mesh of the volume the bricks would unpack

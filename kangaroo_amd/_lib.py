@@ -66,7 +66,7 @@ class KfxError(RuntimeError):
 
 PI, PV, PF = C.POINTER(KfxImage), C.POINTER(KfxVolume), C.POINTER(C.c_float)
 
-# name -> (restype, argtypes); every symbol include/kfx.h declares (and kfx_summary_h.h, kfx_mesh.h, kfx_mesh_index.h, kfx_color.h, kfx_slab_color.h, kfx_sensor.h, kfx_shift.h, kfx_bricks.h, kfx_mesh_bricks.h)
+# name -> (restype, argtypes); every symbol include/kfx.h declares (and kfx_summary_h.h, kfx_mesh.h, kfx_mesh_index.h, kfx_color.h, kfx_slab_color.h, kfx_sensor.h, kfx_shift.h, kfx_bricks.h, kfx_mesh_bricks.h, kfx_raycast_bricks.h, kfx_brick_pool.h)
 SIGNATURES = {
     "kfx_sdf_fuse": (C.c_int, [PV, PI, PI, PF, PF, C.c_float, C.c_float, C.c_float, C.c_uint, C.c_void_p]),
     "kfx_sdf_fuse_slab": (C.c_int, [PV, C.POINTER(KfxSlab), PI, PI, PF, PF, C.c_float, C.c_float, C.c_float, C.c_uint, C.c_void_p]),
@@ -221,6 +221,16 @@ SIGNATURES = {
     "kfx_raycast_bricks_plan": (C.c_int, [PV, C.c_void_p, C.c_ulonglong, C.c_void_p, C.c_ulonglong, C.c_void_p, C.c_size_t, C.c_void_p]),
     "kfx_raycast_bricks": (C.c_int, [PI, PI, PI, PV, C.c_int, C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_int,
                                      C.c_void_p, C.c_size_t, PF, PF, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p]),
+    # include/kfx_brick_pool.h: every call starts with (pool, pool_bytes, cell, capacity)
+    "kfx_brick_pool_bytes": (C.c_size_t, [C.c_int, C.c_ulonglong]),
+    "kfx_brick_pool_scratch_bytes": (C.c_size_t, [PV, C.c_int, C.c_ulonglong]),
+    "kfx_brick_pool_init": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_ulonglong, C.c_void_p]),
+    "kfx_brick_pool_spill": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_ulonglong, PV, C.c_float, C.POINTER(C.c_int), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "kfx_brick_pool_restore": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_ulonglong, PV, C.POINTER(C.c_int), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "kfx_brick_pool_discard": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_ulonglong, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_size_t,
+                                         C.c_void_p]),
+    "kfx_brick_pool_stats": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_ulonglong, C.POINTER(C.c_ulonglong), C.c_void_p]),
+    "kfx_brick_pool_gather": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_ulonglong, C.c_void_p, C.c_ulonglong, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

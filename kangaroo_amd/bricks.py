@@ -1,5 +1,6 @@
-"""Sparse brick snapshots on the host (include/kfx_bricks.h underneath): where the bricks a moving volume loses are kept, which
-boxes of a shift leave and enter, and a whole volume as one file.
+"""Sparse brick snapshots (include/kfx_bricks.h underneath): where the bricks a moving volume loses are kept -- on the host
+(BrickStore) or in a brick pool on the device (DeviceBrickStore, include/kfx_brick_pool.h) -- which boxes of a shift leave and enter, and
+a whole volume as one file.
 
 A brick is 8 x 8 x 8 cells.  A volume that follows the camera in steps of whole bricks keeps its cells on one world lattice: with
 `origin` the running sum of its shifts (new(x) = old(x + s), so the view's cell 0 is world cell `origin`), the brick at view cell
@@ -89,6 +90,10 @@ class BrickStore:
         for k, c in zip(keys.tolist(), cells):
             self._bricks[tuple(k)] = c.copy()
 
+    def keys(self):
+        """every key (m, 3) int64"""
+        return np.asarray(list(self._bricks.keys()), np.int64).reshape(-1, 3)
+
     def items(self):
         """(every key (m, 3) int64, their cells (m, brick bytes) uint8), copies; the store keeps them"""
         if not self._bricks:
@@ -107,6 +112,79 @@ class BrickStore:
         if not found:
             return np.empty((0, 3), np.int64), np.empty((0, self.brick_bytes), np.uint8)
         return np.asarray(found, np.int64), np.stack(cells)
+
+
+class DeviceBrickStore:
+    """Device memory for the bricks of one volume that are outside its box: a brick pool (include/kfx_brick_pool.h) of `capacity`
+    bricks in one uint8 tensor, and the scratch of its calls.  spill() and restore() enqueue launches on torch's current stream and
+    never touch the host.  A spill that finds the pool full DROPS the bricks that do not fit -- they are lost, as every brick is
+    without a store -- and counts them: `dropped` > 0 says that the pool was too small.  No eviction.
+    What it shares with BrickStore: kind, brick_bytes, len() and nbytes (blocking: they read the pool's counters), clear(), items()."""
+
+    def __init__(self, kind, capacity, ops=None, device="cuda"):
+        import torch
+        if ops is None:
+            from . import roo as ops
+        self.ops, self.kind, self.capacity = ops, kind, int(capacity)
+        self.brick_bytes = BRICK ** 3 * {"f32": 8, "f16": 4, "c32": 4}[kind]
+        need = ops.BrickPoolBytes(kind, self.capacity)
+        if not need:
+            raise ValueError("DeviceBrickStore: a pool holds 1 .. 2^31 - 1 bricks, not %d" % self.capacity)
+        self.pool = torch.empty(need, dtype=torch.uint8, device=device)
+        self._scratch = None
+        self.clear()
+
+    def _scratch_for(self, view):
+        import torch
+        need = self.ops.BrickPoolScratchBytes(view, self.capacity)
+        if self._scratch is None or self._scratch.numel() < need:   # (torch's memory: its reuse is ordered on torch's current stream)
+            self._scratch = torch.empty(need, dtype=torch.uint8, device=self.pool.device)
+        return self._scratch
+
+    def clear(self):
+        self.ops.BrickPoolInit(self.pool, self.kind, self.capacity)
+
+    def stats(self):
+        """dict(occupied=, spilled=, restored=, dropped=) -- blocking"""
+        return self.ops.BrickPoolStats(self.pool, self.kind, self.capacity)
+
+    def __len__(self):
+        return self.stats()["occupied"]
+
+    @property
+    def nbytes(self):
+        return len(self) * self.brick_bytes
+
+    @property
+    def dropped(self):
+        return self.stats()["dropped"]
+
+    @property
+    def restored(self):
+        return self.stats()["restored"]
+
+    def spill(self, view, fill, key0):
+        """the live bricks of `view` go into the pool under the keys key0 + (bx, by, bz); what the pool held of that range is replaced"""
+        self.ops.BrickPoolSpill(self.pool, self.capacity, view, fill, key0, self._scratch_for(view))
+
+    def restore(self, view, key0):
+        """the bricks the pool holds of the key range of `view` go back into it and leave the pool"""
+        self.ops.BrickPoolRestore(self.pool, self.capacity, view, key0, self._scratch_for(view))
+
+    def keys(self):
+        """every key (m, 3) int64 -- blocking: a plain copy of the pool's keys block"""
+        return self.ops.BrickPoolKeys(self.pool, self.capacity)[1]
+
+    def device_items(self):
+        """(every key (m, 3) int64 on the host, their cells (m, brick bytes) uint8 on the device, gathered); the store keeps them.
+        Blocking: the keys block is copied to the host; the payload stays on the device."""
+        slots, keys = self.ops.BrickPoolKeys(self.pool, self.capacity)
+        return keys, self.ops.BrickPoolGather(self.pool, self.kind, self.capacity, slots)
+
+    def items(self):
+        """(every key (m, 3) int64, their cells (m, brick bytes) uint8) on the host, copies: for checkpoints and tests"""
+        keys, cells = self.device_items()
+        return keys, cells.cpu().numpy()
 
 
 def world_frame(store_keys, live_keys, origin, vol_dims, vol_boxmin, vol_boxmax, cover=None):
@@ -160,11 +238,16 @@ def world_bricks(store, vol, origin, fill, ops=None, cover=None):
     nbx, nby = (vol.w + BRICK - 1) // BRICK, (vol.h + BRICK - 1) // BRICK
     lid = live_ids.cpu().numpy().view(np.uint32).astype(np.int64)
     live_keys = np.stack([lid % nbx, (lid // nbx) % nby, lid // (nbx * nby)], 1)
-    store_keys, store_cells = store.items() if store is not None else (np.empty((0, 3), np.int64), None)
+    if store is None:
+        store_keys, store_cells = np.empty((0, 3), np.int64), None
+    elif hasattr(store, "device_items"):   # a device store: its payload is gathered where it is, never uploaded
+        store_keys, store_cells = store.device_items()
+    else:
+        store_keys, store_cells = store.items()
     lo, fdims, boxmin, boxmax, ids, order = world_frame(store_keys, live_keys, origin, dims, vol.boxmin, vol.boxmax, cover)
     cells = live_cells
     if len(store_keys):
-        cells = torch.cat([live_cells, torch.from_numpy(store_cells).to(live_cells.device)])
+        cells = torch.cat([live_cells, store_cells if torch.is_tensor(store_cells) else torch.from_numpy(store_cells).to(live_cells.device)])
     cells = cells[torch.from_numpy(order).to(cells.device)].contiguous()
     return lo, fdims, boxmin, boxmax, ids, cells
 

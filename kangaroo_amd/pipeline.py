@@ -82,6 +82,14 @@ class FramePipeline:
         that restored something rebuilds the summary once more.  self.origin is the running sum of the shifts in cells.  Needs a
         quantum and dims that are multiples of 8 (leaving and entering boxes are whole bricks of one world lattice); reset() forgets
         the store.  Off by default: nothing changes and no brick code runs.
+        follow=dict(..., spill="device", pool_bricks=N): the same, with the stores on the device (bricks.DeviceBrickStore over
+        include/kfx_brick_pool.h: one pool of N bricks for the SDF volume and one for the colour volume; N defaults to the number of
+        bricks of the volume).  A shift then makes one spill call per leaving box and one restore call per entering box, all
+        launches on the stream: no copy to the host, no read-back, no synchronisation.  Whether a restore put anything back is not
+        known on the host, so a tracking pipeline rebuilds the summary once after the restores of every shift, and that is the
+        shift's only rebuild.  A pool that is full DROPS the bricks that do not fit: they are lost, as they are without a store;
+        pipe.store.dropped > 0 (a blocking read of the pool's counter) says that pool_bricks was too small.  self.restored reads the
+        pools' counters (blocking).
         sensor: "u16" or "f32" -- the frames arrive as raw sensor images on the host (main.cpp:202-209): the pipeline owns an upload
         ring (ops.DepthInput, `input`) of sensor_slots slots that converts with sensor_scale (millimetres: 1e-3) while it filters.
         submit(array) hands it the next image -- one frame ahead, its copy runs beside the current frame -- and a step / preprocess
@@ -129,13 +137,17 @@ class FramePipeline:
         self.kframe = None
         self.input = None
         self.follow, self.shifts, self._shift_scratch = None, [], None
-        self.spill, self.store, self.cstore, self.origin, self.restored = False, None, None, (0, 0, 0), 0
+        self.spill, self.store, self.cstore, self.origin, self._restored = False, None, None, (0, 0, 0), 0
         if follow is not None:
             if not hasattr(ops, "VolumeShift"):
                 raise ValueError("FramePipeline: follow= needs an operator set with VolumeShift")
-            unknown = set(follow) - {"focus", "quantum", "slack", "spill"}
+            unknown = set(follow) - {"focus", "quantum", "slack", "spill", "pool_bricks"}
             if unknown:
-                raise ValueError("FramePipeline: follow= takes focus, quantum, slack and spill, not %s" % sorted(unknown))
+                raise ValueError("FramePipeline: follow= takes focus, quantum, slack and spill (and pool_bricks with spill='device'), not %s" % sorted(unknown))
+            if follow.get("spill") not in (None, False, True, "device"):
+                raise ValueError("FramePipeline: follow=dict(spill=) is True (a store on the host) or 'device' (a brick pool), not %r" % (follow["spill"],))
+            if follow.get("pool_bricks") is not None and follow.get("spill") != "device":
+                raise ValueError("FramePipeline: follow=dict(pool_bricks=) belongs to spill='device'")
             self.follow = {"focus": follow.get("focus"), "quantum": int(follow.get("quantum", 8)), "slack": float(follow.get("slack", 16))}
             if self.follow["quantum"] < 1:
                 raise ValueError("FramePipeline: follow= needs quantum >= 1")
@@ -147,8 +159,19 @@ class FramePipeline:
                 if not hasattr(ops, "BrickPack"):
                     raise ValueError("FramePipeline: follow=dict(spill=True) needs an operator set with BrickPack")
                 self.spill = True
-                self.store = bricks.BrickStore(self.kind)
-                self.cstore = bricks.BrickStore("c32") if self.color else None
+                if follow["spill"] == "device":
+                    if not hasattr(ops, "BrickPoolSpill"):
+                        raise ValueError("FramePipeline: follow=dict(spill='device') needs an operator set with BrickPoolSpill")
+                    self.spill = "device"
+                    n = follow.get("pool_bricks")
+                    n = int(np.prod([int(d) // bricks.BRICK for d in dims])) if n is None else int(n)
+                    if n < 1:
+                        raise ValueError("FramePipeline: follow=dict(pool_bricks=) is at least 1, not %d" % n)
+                    self.store = bricks.DeviceBrickStore(self.kind, n, ops)
+                    self.cstore = bricks.DeviceBrickStore("c32", n, ops) if self.color else None
+                else:
+                    self.store = bricks.BrickStore(self.kind)
+                    self.cstore = bricks.BrickStore("c32") if self.color else None
         if sensor is not None:
             if not hasattr(ops, "DepthInput"):
                 raise ValueError("FramePipeline: sensor= needs an operator set with DepthInput")
@@ -270,6 +293,8 @@ class FramePipeline:
         if self._shift_scratch is None:   # one scratch for both volumes: 16 packed planes of the SDF volume's cells
             self._shift_scratch = self.ops.shift_scratch(self.vol, shift)
         volumes = [(self.vol, self.store, float("nan"))] + ([(self.cvol, self.cstore, 0.5)] if self.color else [])
+        if self.spill == "device":
+            return self._shift_with_pools(shift, volumes)
         if self.spill:
             for vol, store, fill in volumes:
                 self._spill(vol, store, fill, shift)
@@ -282,9 +307,41 @@ class FramePipeline:
         self.origin = tuple(o + s for o, s in zip(self.origin, shift))
         if self.spill:
             restored = sum([self._restore(vol, store, shift) for vol, store, _ in volumes])
-            self.restored += restored
+            self._restored += restored
             if restored and self.track:   # the summary and the class tables describe the volume as it is after the restore
                 self.summary.rebuild()
+
+    @property
+    def restored(self):
+        """bricks put back so far; follow=dict(spill="device"): the pools' counters, read on demand (blocking)"""
+        if self.spill == "device":
+            return sum(store.restored for store in (self.store, self.cstore) if store is not None)
+        return self._restored
+
+    def _shift_with_pools(self, shift, volumes):
+        """follow=dict(spill="device"): one spill call per leaving box, the shift, one restore call per entering box -- launches only.
+        The summary is rebuilt once, after the restores, whatever they put back: the shift itself runs untracked."""
+        key = lambda start: tuple((o + s) // bricks.BRICK for o, s in zip(self.origin, start))
+        for vol, store, fill in volumes:
+            for start, size in bricks.leaving_boxes(self.dims, shift):
+                store.spill(vol.SubVolume(start, size), fill, key(start))
+        tracked = self.track and self.kframe is not None and self.kframe.track
+        if self.kframe is not None:
+            if tracked:
+                self.kframe.set_track(False)   # (host state only: the frame's summary goes stale, and set_track(True) below rebuilds it)
+            self.kframe.shift(shift, self._shift_scratch)
+        else:
+            self.ops.VolumeShift(self.vol, shift, float("nan"), self._shift_scratch)
+        if self.color:
+            self.ops.VolumeShift(self.cvol, shift, 0.5, self._shift_scratch)
+        self.origin = tuple(o + s for o, s in zip(self.origin, shift))
+        for vol, store, _ in volumes:
+            for start, size in bricks.entering_boxes(self.dims, shift):
+                store.restore(vol.SubVolume(start, size), key(start))
+        if tracked:
+            self.kframe.set_track(True)
+        elif self.track and self.kframe is None:
+            self.summary.rebuild()
 
     def _spill(self, vol, store, fill, shift):
         """follow=dict(spill=True), before the shift: the live bricks of the boxes that leave go to the host, under their world keys"""
@@ -312,11 +369,11 @@ class FramePipeline:
         color=True.  The two lists share the frame (each covers the other's store).  The stores are left as they are."""
         if not hasattr(self.ops, "BrickPack"):
             raise ValueError("FramePipeline: the world mesh needs an operator set with BrickPack")
-        ckeys = self.cstore.items()[0] if self.cstore is not None else None
+        ckeys = self.cstore.keys() if self.cstore is not None else None
         sdf = bricks.world_bricks(self.store, self.vol, self.origin, float("nan"), ops=self.ops, cover=ckeys)
         if not self.color:
             return sdf, None
-        skeys = self.store.items()[0] if self.store is not None else None
+        skeys = self.store.keys() if self.store is not None else None
         return sdf, bricks.world_bricks(self.cstore, self.cvol, self.origin, 0.5, ops=self.ops, cover=skeys)
 
     def ExtractWorldMesh(self, with_index=False):
@@ -738,6 +795,8 @@ class SlabPipeline(FramePipeline):
         deterministic per voxel, so no traffic is needed) -- the cross-check of the exchange path."""
         assert halo in ("exchange", "recompute")
         assert raycast in ("composite", "exact", "exact_allreduce")
+        if (kw.get("follow") or {}).get("spill") == "device":
+            raise ValueError("SlabPipeline: follow=dict(spill='device') (a brick pool) is a single-volume option: a pool per rank is a later step")
         if kw.get("follow") is not None:
             raise ValueError("SlabPipeline: follow= (a volume that follows the camera) is a single-volume option: a shift along z moves "
                              "planes from one rank's slab to another's, and shifts on Z-slabs are not implemented")

@@ -702,6 +702,86 @@ def VolumeFill(vol, fill, stream=None):
     _lib.check(_lib.load().kfx_volume_shift(vol.ref(), CELL_KIND[vol.kind], _shift3((vol.w, 0, 0)), float(fill), None, 0, _stream(stream)))
 
 
+# ---- the brick pool (include/kfx_brick_pool.h) -------------------------------------------
+# A pool is a uint8 device tensor of BrickPoolBytes(kind, capacity) bytes (torch's allocations are 256-byte aligned); every operator
+# takes (pool, kind, capacity), as every call of the library does.
+
+def _int3(what, v):
+    v = [int(x) for x in v]
+    if len(v) != 3:
+        raise ValueError("expected %s of 3 integers, got %r" % (what, v))
+    return (C.c_int * 3)(*v)
+
+
+def _nbytes(t):
+    return t.numel() * t.element_size()
+
+
+def BrickPoolBytes(kind, capacity):
+    """kfx_brick_pool_bytes: the bytes of a pool of `capacity` bricks of this cell kind (0: refused)."""
+    return int(_lib.load().kfx_brick_pool_bytes(CELL_KIND[kind], int(capacity)))
+
+
+def BrickPoolScratchBytes(vol, capacity):
+    """kfx_brick_pool_scratch_bytes: the scratch that serves BrickPoolSpill, BrickPoolRestore and BrickPoolDiscard of `vol` (a volume or a view)."""
+    return int(_lib.load().kfx_brick_pool_scratch_bytes(vol.ref(), CELL_KIND[vol.kind], int(capacity)))
+
+
+def BrickPoolInit(pool, kind, capacity, stream=None):
+    """kfx_brick_pool_init: every slot free, the counters zero."""
+    _lib.check(_lib.load().kfx_brick_pool_init(pool.data_ptr(), _nbytes(pool), CELL_KIND[kind], int(capacity), _stream(stream)))
+
+
+def BrickPoolSpill(pool, capacity, vol, fill, key0, scratch, stream=None):
+    """kfx_brick_pool_spill: the live bricks of `vol` (bitwise against the fill cell, as BrickPack) go into the pool under the world keys
+    key0 + (bx, by, bz), replacing what the pool held of that key range; bricks that find no free slot are dropped and counted.  No
+    read-back, nothing on the host."""
+    _lib.check(_lib.load().kfx_brick_pool_spill(pool.data_ptr(), _nbytes(pool), CELL_KIND[vol.kind], int(capacity), vol.ref(), float(fill),
+                                                _int3("key0", key0), scratch.data_ptr(), _nbytes(scratch), _stream(stream)))
+
+
+def BrickPoolRestore(pool, capacity, vol, key0, scratch, stream=None):
+    """kfx_brick_pool_restore: the bricks the pool holds of the key range of `vol` are written into it (their cells inside the view and
+    nothing else) and leave the pool.  No read-back, nothing on the host."""
+    _lib.check(_lib.load().kfx_brick_pool_restore(pool.data_ptr(), _nbytes(pool), CELL_KIND[vol.kind], int(capacity), vol.ref(), _int3("key0", key0),
+                                                  scratch.data_ptr(), _nbytes(scratch), _stream(stream)))
+
+
+def BrickPoolDiscard(pool, kind, capacity, nb, key0, scratch, stream=None):
+    """kfx_brick_pool_discard: the bricks the pool holds of the box of nb keys from key0 leave the pool."""
+    _lib.check(_lib.load().kfx_brick_pool_discard(pool.data_ptr(), _nbytes(pool), CELL_KIND[kind], int(capacity), _int3("nb", nb), _int3("key0", key0),
+                                                  scratch.data_ptr(), _nbytes(scratch), _stream(stream)))
+
+
+def BrickPoolStats(pool, kind, capacity, stream=None):
+    """kfx_brick_pool_stats (blocking): dict(occupied=, spilled=, restored=, dropped=)."""
+    out = (C.c_ulonglong * 4)()
+    _lib.check(_lib.load().kfx_brick_pool_stats(pool.data_ptr(), _nbytes(pool), CELL_KIND[kind], int(capacity), out, _stream(stream)))
+    return dict(occupied=int(out[0]), spilled=int(out[1]), restored=int(out[2]), dropped=int(out[3]))
+
+
+def BrickPoolKeys(pool, capacity):
+    """The occupied slots of a pool, read with a plain copy of its keys block (16 bytes per slot, blocking): (slots (m,) int64
+    ascending, keys (m, 3) int64)."""
+    k = pool[256:256 + 16 * int(capacity)].cpu().numpy().view(np.int32).reshape(-1, 4)
+    slots = np.flatnonzero(k[:, 3] == 1)
+    return slots, k[slots, :3].astype(np.int64)
+
+
+def BrickPoolGather(pool, kind, capacity, slots, stream=None):
+    """kfx_brick_pool_gather: the cells of the listed slots (host integers or an int32 device tensor) as one uint8 device tensor
+    (n, brick bytes), device to device."""
+    dev = pool.device
+    if not torch.is_tensor(slots):
+        slots = torch.from_numpy(np.ascontiguousarray(np.asarray(slots).reshape(-1), dtype=np.int64).astype(np.uint32).view(np.int32)).to(dev)
+    slots = slots.contiguous()
+    n = slots.numel()
+    cells = torch.empty((n, BRICK ** 3 * {"f32": 8, "f16": 4, "c32": 4}[kind]), dtype=torch.uint8, device=dev)
+    _lib.check(_lib.load().kfx_brick_pool_gather(pool.data_ptr(), _nbytes(pool), CELL_KIND[kind], int(capacity), slots.data_ptr() if n else None, n,
+                                                 cells.data_ptr() if n else None, _stream(stream)))
+    return cells
+
+
 # ---- RaycastSdf straight from packed bricks (include/kfx_raycast_bricks.h) --------------
 
 def _brick_ids(what, ids, dev):
