@@ -4,6 +4,7 @@
 // back-projected depth).  One pixel per lane, 64 x 4 pixel workgroups, IEEE arithmetic in the reference's order.
 #include "kfx_device.h"
 #include "sampling.h"
+#include "raycast_ray.h"   // phong: PhongShade, the ray-march's own
 
 namespace kfx {
 
@@ -17,20 +18,6 @@ struct PixParams {
     V3 a, b;               // box min / max, or sphere centre (camera frame) / plane normal (camera frame)
     float r;
 };
-
-// PhongShade (cu_raycast.cu:14-28)
-__device__ __forceinline__ float phong_shade(const V3 p_c, const V3 n_c)
-{
-    const float ambient = (float)0.4, diffuse = (float)0.4, specular = (float)0.2;
-    const V3 eyedir = div_s(p_c * -1.0f, length(p_c));
-    const V3 l0 = v3((float)0.4, (float)0.4, -1.0f);
-    const V3 lightdir = div_s(l0, length(l0));
-    const float ldotn = dot(lightdir, n_c);
-    const V3 lightreflect = n_c * (2 * ldotn) + lightdir * -1.0f;
-    const float edotr = fmaxf(0.0f, dot(eyedir, lightreflect));
-    const float spec = edotr * edotr * edotr * edotr * edotr * edotr * edotr * edotr * edotr * edotr;
-    return ambient + diffuse * ldotn + specular * spec;
-}
 
 __device__ __forceinline__ bool pixel(const PixParams& p, int& u, int& v)
 {
@@ -69,7 +56,7 @@ __global__ __launch_bounds__(256) void k_raycast_sphere(const PixParams p)
         if (p.iptr) {
             const V3 p_c = ray_c * depth;
             const V3 n_c = p_c - center_c;
-            *(reinterpret_cast<float*>(p.iptr + (size_t)v * p.ipitch) + u) = phong_shade(p_c, div_s(n_c, length(n_c)));
+            *(reinterpret_cast<float*>(p.iptr + (size_t)v * p.ipitch) + u) = phong(p_c, div_s(n_c, length(n_c)));
         }
     }
 }
@@ -84,7 +71,7 @@ __global__ __launch_bounds__(256) void k_raycast_plane(const PixParams p)
     float* pd = reinterpret_cast<float*>(p.dptr + (size_t)v * p.dpitch) + u;
     const float prev = *pd;
     if (depth > 0 && (depth < prev || !isfinite(prev))) {
-        if (p.iptr) *(reinterpret_cast<float*>(p.iptr + (size_t)v * p.ipitch) + u) = phong_shade(ray_c * depth, div_s(n_c, length(n_c)));
+        if (p.iptr) *(reinterpret_cast<float*>(p.iptr + (size_t)v * p.ipitch) + u) = phong(ray_c * depth, div_s(n_c, length(n_c)));
         *pd = depth;
     }
 }

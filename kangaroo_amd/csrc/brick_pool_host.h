@@ -88,20 +88,16 @@ inline BrickRefusal brick_pool_check_kind(int cell, unsigned long long capacity,
     if (capacity == 0 || capacity > BRICK_MAX) return {KFX_E_RANGE, "capacity 0 or above 2^31 - 1"};
     return {0, nullptr};
 }
-// the pool: present, large enough, aligned -- in that order (as the scratch of bricks_host.h)
+// the pool and the scratch (bricks_host.h's rule)
 inline BrickRefusal brick_pool_check_pool(const void* pool, size_t pool_bytes, size_t cb, unsigned long long capacity)
 {
-    if (!pool) return {KFX_E_NULL, "null pool"};
-    if (pool_bytes < brick_pool_layout(cb, capacity).bytes) return {KFX_E_SHAPE, "pool smaller than kfx_brick_pool_bytes()"};
-    if ((uintptr_t)pool & 255) return {KFX_E_ALIGN, "pool not aligned to 256 bytes"};
-    return {0, nullptr};
+    return brick_check_block(pool, pool_bytes, brick_pool_layout(cb, capacity).bytes, "null pool", "pool smaller than kfx_brick_pool_bytes()",
+                             "pool not aligned to 256 bytes");
 }
 inline BrickRefusal brick_pool_check_scratch(unsigned long long view_bricks, unsigned long long capacity, const void* scratch, size_t scratch_bytes)
 {
-    if (!scratch) return {KFX_E_NULL, "null scratch"};
-    if (scratch_bytes < brick_pool_scratch(view_bricks, capacity).bytes) return {KFX_E_SHAPE, "scratch smaller than kfx_brick_pool_scratch_bytes()"};
-    if ((uintptr_t)scratch & 255) return {KFX_E_ALIGN, "scratch not aligned to 256 bytes"};
-    return {0, nullptr};
+    return brick_check_block(scratch, scratch_bytes, brick_pool_scratch(view_bricks, capacity).bytes, "null scratch",
+                             "scratch smaller than kfx_brick_pool_scratch_bytes()", "scratch not aligned to 256 bytes");
 }
 // a key box of nb[a] >= 1 bricks from key0: its last key, key0 + nb - 1, is an int32 on every axis
 inline BrickRefusal brick_pool_check_keys(const int key0[3], const int nb[3])

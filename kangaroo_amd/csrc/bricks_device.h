@@ -214,7 +214,6 @@ struct BrickSetup {
     size_t cb;
     BrickArgs a;
 };
-inline int refuse(const BrickRefusal& r, const char* what) { return r.code ? fail_rule(what, r.code, r.rule) : 0; }
 inline int brick_setup(BrickSetup& s, const kfx_volume* vol, int cell, float fill, const char* what)
 {
     if (!vol || !vol->ptr) return fail_rule(what, KFX_E_NULL, "null volume");

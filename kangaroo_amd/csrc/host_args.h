@@ -22,6 +22,9 @@ inline int fail_rule(const char* what, int code, const char* rule)
     snprintf(msg, sizeof(msg), "%s: %s", what, rule);
     return set_error(code, msg);
 }
+// the verdict {code, rule} of a host-side rule (bricks_host.h: BrickRefusal) as the entry point's answer: 0 where it accepted
+template <typename REFUSAL>
+inline int refuse(const REFUSAL& r, const char* what) { return r.code ? fail_rule(what, r.code, r.rule) : 0; }
 
 inline int check_volume(const kfx_volume* vol, size_t cell_bytes, size_t min_dim, size_t max_dim, const char* what)
 {

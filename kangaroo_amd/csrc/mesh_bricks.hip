@@ -2,8 +2,8 @@
 // dense volume of which only the listed bricks exist and every other cell is NaN (colour: 0.5), without that volume.  The result is
 // the dense extractor's (mesh.hip) on the volume the bricks would unpack into, bit for bit: a cube's case, a vertex's position, the
 // normalisation and the store are mesh_cube.h's, shared with it; the frame's geometry is a MeshParams filled by the same set_geometry;
-// the gradient stencil and the colour blend below restate sampling.h's gradient<> / trilinear_at<> expression for expression over a
-// cell accessor that goes through the brick lists (sampling.h's own read pitched rows and are pinned by the raycast's code tests).
+// the gradient stencil and the colour blend are sampling.h's own (gradient_over, trilinear_over: the dense samplers' base cell and blend)
+// over a cell accessor that goes through the brick lists.
 //
 //   k_bm_neighbours   one lane per (listed brick, neighbour): the neighbour's position in the ascending id list by binary search, -1
 //                     if absent -- 27 positions per brick, the brick's own among them.  After this a frame cell within 8 cells of a
@@ -100,66 +100,6 @@ struct BrickCells {
         return CELL::val(cells + (size_t)s * (BRICK_CELLS * CELL::BYTES), (((z & 7) << 3) | (y & 7)) << 3 | (x & 7));
     }
 };
-
-// sampling.h's gradient<> (BoundedVolume::GetUnitsBackwardDiffDxDyDz), expression for expression, over a cell accessor: the base
-// cell clamp(floor(pf), 1, dim - 2) on the frame's dimensions, the 20 cells of {-1, 0, 1}^3 with at most one coordinate -1
-template <typename ACC>
-__device__ __forceinline__ V3 brick_gradient(const MeshParams& p, const ACC& cell, const V3 pos_w)
-{
-    const V3 pos_v = div_cw(pos_w - p.vol.bmin, p.size);
-    const V3 pf = v3(pos_v.x * p.dims1.x, pos_v.y * p.dims1.y, pos_v.z * p.dims1.z);
-    const int ix = (int)fmaxf(fminf(p.hi2.x, floorf(pf.x)), 1.f);
-    const int iy = (int)fmaxf(fminf(p.hi2.y, floorf(pf.y)), 1.f);
-    const int iz = (int)fmaxf(fminf(p.hi2.z, floorf(pf.z)), 1.f);
-    const float fx = pf.x - (float)ix, fy = pf.y - (float)iy, fz = pf.z - (float)iz;
-    float c[2][2][2], mx[2][2], my[2][2], mz[2][2];
-#pragma unroll
-    for (int dz = 0; dz < 2; ++dz)
-#pragma unroll
-        for (int dy = 0; dy < 2; ++dy) {
-            mx[dz][dy] = cell(ix - 1, iy + dy, iz + dz);
-            c[dz][dy][0] = cell(ix, iy + dy, iz + dz);
-            c[dz][dy][1] = cell(ix + 1, iy + dy, iz + dz);
-        }
-#pragma unroll
-    for (int dz = 0; dz < 2; ++dz) {
-        my[dz][0] = cell(ix, iy - 1, iz + dz);
-        my[dz][1] = cell(ix + 1, iy - 1, iz + dz);
-    }
-#pragma unroll
-    for (int dy = 0; dy < 2; ++dy) {
-        mz[dy][0] = cell(ix, iy + dy, iz - 1);
-        mz[dy][1] = cell(ix + 1, iy + dy, iz - 1);
-    }
-    V3 g[2][2][2];
-#pragma unroll
-    for (int dz = 0; dz < 2; ++dz)
-#pragma unroll
-        for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < 2; ++dx) {
-                const float v0 = c[dz][dy][dx];
-                const float bx = dx ? c[dz][dy][0] : mx[dz][dy];
-                const float by = dy ? c[dz][0][dx] : my[dz][dx];
-                const float bz = dz ? c[0][dy][dx] : mz[dy][dx];
-                g[dz][dy][dx] = v3(v0 - bx, v0 - by, v0 - bz);
-            }
-    const V3 deriv = lerp(lerp(lerp(g[0][0][0], g[0][0][1], fx), lerp(g[0][1][0], g[0][1][1], fx), fy),
-                          lerp(lerp(g[1][0][0], g[1][0][1], fx), lerp(g[1][1][0], g[1][1][1], fx), fy), fz);
-    return div_cw(deriv, p.voxel);
-}
-
-// sampling.h's trilinear<> (GetUnitsTrilinearClamped): its cell_of() -- base cell clamp(.., 0, dim - 2), unclamped fractions -- and
-// trilinear_at<>'s blend over a cell accessor
-template <typename ACC>
-__device__ __forceinline__ float brick_trilinear(const ColorGeom& cv, const ACC& cell, const V3 pos_w)
-{
-    const CellPos c = cell_of(cv, pos_w);
-    const int ix = c.ix, iy = c.iy, iz = c.iz;
-    const float c000 = cell(ix, iy, iz), c001 = cell(ix + 1, iy, iz), c010 = cell(ix, iy + 1, iz), c011 = cell(ix + 1, iy + 1, iz);
-    const float c100 = cell(ix, iy, iz + 1), c101 = cell(ix + 1, iy, iz + 1), c110 = cell(ix, iy + 1, iz + 1), c111 = cell(ix + 1, iy + 1, iz + 1);
-    return lerp(lerp(lerp(c000, c001, c.fx), lerp(c010, c011, c.fx), c.fy), lerp(lerp(c100, c101, c.fx), lerp(c110, c111, c.fx), c.fy), c.fz);
-}
 
 // the first cell of brick id; false if id is no brick of the frame
 __device__ __forceinline__ bool brick_origin(const BrickGrid& g, unsigned id, int& x0, int& y0, int& z0)
@@ -337,16 +277,16 @@ __global__ __launch_bounds__(128) void k_bm_emit(const MeshParams p, const Color
         if (!(mask & (1u << e))) continue;
         ev[e] = edge_position(p, p0, v, e);
         // (mesh.hip's edge_attributes: multiply-by-reciprocal normalisation, zero where that is not finite)
-        const V3 deriv = brick_gradient(p, sdf, ev[e]);
+        const V3 deriv = gradient_over(p, sdf, ev[e]);
         V3 nrm = div_s(deriv, length(deriv));
         if (!isfinite(nrm.x) || !isfinite(nrm.y) || !isfinite(nrm.z)) nrm = v3(0.f, 0.f, 0.f);
         en[e] = nrm;
         ec[e] = 0.f;
         if (has_color && cnbr) {
             const BrickCells<RayC32> grey{color_cells, cnbr + (size_t)home * BRICK_NEIGHBOURS, bx0, by0, bz0, 0.5f};
-            ec[e] = brick_trilinear(cv, grey, ev[e]);
+            ec[e] = trilinear_over(cv, grey, ev[e]);
         } else if (has_color) {   // (no colour bricks at all: every cell reads 0.5)
-            ec[e] = brick_trilinear(cv, [](int, int, int) { return 0.5f; }, ev[e]);
+            ec[e] = trilinear_over(cv, [](int, int, int) { return 0.5f; }, ev[e]);
         }
     }
     // The cube's slots are those the plan counted for it: [tri_offset[t_id], the next cube's offset or the total).  With ascending ids
@@ -374,7 +314,6 @@ struct BrickMeshCall {
     MeshParams p;
     BrickMeshScratch lay;
 };
-static int bm_refuse(const BrickRefusal& r, const char* what) { return r.code ? fail_rule(what, r.code, r.rule) : 0; }
 
 // The checks of a plan or an emit in one order: the frame and the cell kind, the counts, the lists, the scratch (null, short,
 // misaligned), the totals pointer.
@@ -382,11 +321,11 @@ static int bm_call(BrickMeshCall& c, const char* what, const kfx_volume* frame, 
                    const unsigned* color_ids, const void* color_cells, unsigned long long n_color, const void* scratch, size_t scratch_bytes,
                    const unsigned long long* totals)
 {
-    if (int e = bm_refuse(brick_mesh_check_frame(frame, cell, c.geom), what)) return e;
-    if (int e = bm_refuse(brick_mesh_check_counts(n, n_color), what)) return e;
-    if (int e = bm_refuse(brick_check_lists(ids, cells, n), what)) return e;
-    if (int e = bm_refuse(brick_check_lists(color_ids, color_cells, n_color), what)) return e;
-    if (int e = bm_refuse(brick_mesh_check_scratch(n, n_color, scratch, scratch_bytes), what)) return e;
+    if (int e = refuse(brick_check_frame(frame, cell, c.geom), what)) return e;
+    if (int e = refuse(brick_check_counts(n, n_color), what)) return e;
+    if (int e = refuse(brick_check_lists(ids, cells, n), what)) return e;
+    if (int e = refuse(brick_check_lists(color_ids, color_cells, n_color), what)) return e;
+    if (int e = refuse(brick_mesh_check_scratch(n, n_color, scratch, scratch_bytes), what)) return e;
     if (!totals) return fail_rule(what, KFX_E_NULL, "null totals");
     c.grid = BrickGrid{c.geom.nbx, c.geom.nby, c.geom.nbz, (unsigned)c.geom.nb};
     // the frame's geometry as the dense extractor's mesh_setup fills it (no storage behind it: ptr and pitches are not the frame's)
@@ -415,7 +354,7 @@ using namespace kfx;
 
 extern "C" size_t kfx_mesh_bricks_scratch_bytes(unsigned long long n, unsigned long long n_color)
 {
-    if (brick_mesh_check_counts(n, n_color).code) return 0;
+    if (brick_check_counts(n, n_color).code) return 0;
     return brick_mesh_scratch(n, n_color).bytes;
 }
 
@@ -463,7 +402,7 @@ extern "C" int kfx_mesh_bricks_emit(const kfx_volume* frame, int cell, const uns
     if (!totals_in_range(totals)) return fail_rule(what, KFX_E_RANGE, "totals out of range");
     if (n == 0) return totals[0] || totals[1] ? fail_rule(what, KFX_E_RANGE, "totals are not the plan's") : 0;
     if (totals[0] == 0) return 0;
-    if (int e = bm_refuse(brick_mesh_check_outputs(cube_index, tri_offset, verts, norms, colors), what)) return e;
+    if (int e = refuse(brick_mesh_check_outputs(cube_index, tri_offset, verts, norms, colors), what)) return e;
     const int has_color = brick_mesh_has_color(c.geom, colors) ? 1 : 0;
     ColorGeom cv{};
     if (has_color) {   // the colour frame: the SDF frame's dimensions and box

@@ -1,6 +1,6 @@
-// mesh_bricks_host.h -- what mesh_bricks.hip (include/kfx_mesh_bricks.h) decides on the host before it launches anything: which frames
-// it accepts and their brick grid, how the scratch is carved -- from the brick counts alone, never from the frame -- and the refusals of
-// a scratch, of the brick lists and of the outputs.  No HIP in here: scripts/mesh_bricks_host_check.cpp drives it under the host
+// mesh_bricks_host.h -- what mesh_bricks.hip (include/kfx_mesh_bricks.h) decides on the host before it launches anything: how the
+// scratch is carved -- from the brick counts alone, never from the frame -- and the refusals of a scratch and of the outputs (the
+// frame, the counts and the lists: bricks_host.h).  No HIP in here: scripts/mesh_bricks_host_check.cpp drives it under the host
 // sanitizers.
 #pragma once
 
@@ -14,19 +14,6 @@ namespace kfx {
 
 constexpr int BRICK_NEIGHBOURS = 27;               // a brick and the 26 around it: slot (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1)
 constexpr unsigned BRICK_MESH_BLOCK = 256;         // bricks per scan block
-constexpr size_t FRAME_MIN_DIM = 3, FRAME_MAX_DIM = 65535;   // the dimensions kfx_mesh_plan accepts of a dense volume
-
-// The frame: a virtual dense volume, of which only the dimensions and the box are read.  Its brick grid in g.
-inline BrickRefusal brick_mesh_check_frame(const kfx_volume* frame, int cell, BrickGeom& g)
-{
-    if (!frame) return {KFX_E_NULL, "null frame"};
-    if (cell != KFX_CELL_F32 && cell != KFX_CELL_F16) return {KFX_E_RANGE, "unknown cell kind"};
-    if (frame->w < FRAME_MIN_DIM || frame->h < FRAME_MIN_DIM || frame->d < FRAME_MIN_DIM || frame->w > FRAME_MAX_DIM ||
-        frame->h > FRAME_MAX_DIM || frame->d > FRAME_MAX_DIM)
-        return {KFX_E_SHAPE, "frame dimensions"};
-    g = brick_geom(frame->w, frame->h, frame->d);
-    return brick_check_grid(g);
-}
 
 // The scratch of a plan and its emit (offsets in bytes from its start; include/kfx_mesh_bricks.h states the sum):
 //   hdr    256 bytes: words 0, 1 (8 bytes each) = active cubes, triangles
@@ -54,18 +41,11 @@ inline BrickMeshScratch brick_mesh_scratch(unsigned long long n, unsigned long l
     return s;
 }
 
-inline BrickRefusal brick_mesh_check_counts(unsigned long long n, unsigned long long n_color)
-{
-    if (n > BRICK_MAX || n_color > BRICK_MAX) return {KFX_E_RANGE, "more than 2^31 - 1 entries"};
-    return {0, nullptr};
-}
-// the scratch: present, large enough, aligned -- in that order (as bricks_host.h)
+// the scratch (bricks_host.h's rule)
 inline BrickRefusal brick_mesh_check_scratch(unsigned long long n, unsigned long long n_color, const void* scratch, size_t scratch_bytes)
 {
-    if (!scratch) return {KFX_E_NULL, "null scratch"};
-    if (scratch_bytes < brick_mesh_scratch(n, n_color).bytes) return {KFX_E_SHAPE, "scratch smaller than kfx_mesh_bricks_scratch_bytes()"};
-    if ((uintptr_t)scratch & 255) return {KFX_E_ALIGN, "scratch not aligned to 256 bytes"};
-    return {0, nullptr};
+    return brick_check_block(scratch, scratch_bytes, brick_mesh_scratch(n, n_color).bytes, "null scratch",
+                             "scratch smaller than kfx_mesh_bricks_scratch_bytes()", "scratch not aligned to 256 bytes");
 }
 // the arrays of an emit with cubes to write
 inline BrickRefusal brick_mesh_check_outputs(const void* cube_index, const void* tri_offset, const void* verts, const void* norms, const void* colors)

@@ -1,6 +1,6 @@
-// raycast_bricks_host.h -- what raycast_bricks.hip (include/kfx_raycast_bricks.h) decides on the host before it launches anything: which
-// frames it accepts and their brick grid, the capacity of a table and how the scratch is carved -- from the brick counts alone, never
-// from the frame -- the refusals of the counts, the lists and a scratch, and the table itself: where an id hashes to, how it is
+// raycast_bricks_host.h -- what raycast_bricks.hip (include/kfx_raycast_bricks.h) decides on the host before it launches anything: the
+// capacity of a table and how the scratch is carved -- from the brick counts alone, never from the frame -- the refusals of a plan's
+// id list and of a scratch (the frame, the counts and the lists: bricks_host.h), and the table itself: where an id hashes to, how it is
 // inserted and how it is looked up, written once for the kernels and for the host.  No HIP in here:
 // scripts/raycast_bricks_host_check.cpp drives it under the host sanitizers.
 #pragma once
@@ -19,32 +19,7 @@
 
 namespace kfx {
 
-constexpr size_t BRICK_RAY_MIN_DIM = 3, BRICK_RAY_MAX_DIM = 65535;   // the dimensions kfx_raycast_sdf accepts of a dense volume
 constexpr unsigned BRICK_SLOT_EMPTY = 0xffffffffu;                   // no brick id: a frame has 2^31 - 1 bricks at the most
-
-// The frame: a virtual dense volume, of which only the dimensions and the box are read.  Its brick grid in g.
-inline BrickRefusal brick_ray_check_frame(const kfx_volume* frame, BrickGeom& g)
-{
-    if (!frame) return {KFX_E_NULL, "null frame"};
-    if (frame->w < BRICK_RAY_MIN_DIM || frame->h < BRICK_RAY_MIN_DIM || frame->d < BRICK_RAY_MIN_DIM || frame->w > BRICK_RAY_MAX_DIM ||
-        frame->h > BRICK_RAY_MAX_DIM || frame->d > BRICK_RAY_MAX_DIM)
-        return {KFX_E_SHAPE, "frame dimensions"};
-    g = brick_geom(frame->w, frame->h, frame->d);
-    return brick_check_grid(g);
-}
-// ... and the kind of the SDF bricks (before the dimensions, as the brick mesh)
-inline BrickRefusal brick_ray_check_frame(const kfx_volume* frame, int cell, BrickGeom& g)
-{
-    if (!frame) return {KFX_E_NULL, "null frame"};
-    if (cell != KFX_CELL_F32 && cell != KFX_CELL_F16) return {KFX_E_RANGE, "unknown cell kind"};
-    return brick_ray_check_frame(frame, g);
-}
-
-inline BrickRefusal brick_ray_check_counts(unsigned long long n, unsigned long long n_color)
-{
-    if (n > BRICK_MAX || n_color > BRICK_MAX) return {KFX_E_RANGE, "more than 2^31 - 1 entries"};
-    return {0, nullptr};
-}
 
 // the id list of a plan with n entries (n == 0: nothing is asked of it)
 inline BrickRefusal brick_ray_check_ids(const void* ids, unsigned long long n)
@@ -90,13 +65,11 @@ inline BrickRayScratch brick_ray_scratch(unsigned long long n, unsigned long lon
     s.bytes = s.ctab + brick_round256(8 * s.ct.cap);
     return s;
 }
-// the scratch: present, large enough, aligned -- in that order (as bricks_host.h)
+// the scratch (bricks_host.h's rule)
 inline BrickRefusal brick_ray_check_scratch(unsigned long long n, unsigned long long n_color, const void* scratch, size_t scratch_bytes)
 {
-    if (!scratch) return {KFX_E_NULL, "null scratch"};
-    if (scratch_bytes < brick_ray_scratch(n, n_color).bytes) return {KFX_E_SHAPE, "scratch smaller than kfx_raycast_bricks_scratch_bytes()"};
-    if ((uintptr_t)scratch & 255) return {KFX_E_ALIGN, "scratch not aligned to 256 bytes"};
-    return {0, nullptr};
+    return brick_check_block(scratch, scratch_bytes, brick_ray_scratch(n, n_color).bytes, "null scratch",
+                             "scratch smaller than kfx_raycast_bricks_scratch_bytes()", "scratch not aligned to 256 bytes");
 }
 
 // ---- the table: slots of two words {id, position}, BRICK_SLOT_EMPTY in the id word of a free one ----

@@ -1,7 +1,9 @@
-// sampling.h -- the volume samplers shared by the ray-march (raycast.hip) and the mesh extraction (mesh.hip):
-// BoundedVolume::GetUnitsTrilinearClamped and GetUnitsBackwardDiffDxDyDz (reference BoundedVolume.h:93-106 ->
-// Volume.h:224-295) over the cell readers RayF32 / RayF16 / RayC32.  GEOM is any parameter block with the
-// members {VolView vol; V3 size, dims1, hi2[, voxel]; V3 inv_size; int fastdiv, off32;} (RayParams, ColorGeom, MeshParams):
+// sampling.h -- the volume samplers shared by the ray-marches (raycast.hip, raycast_bricks.hip) and the mesh extractions (mesh.hip,
+// mesh_bricks.hip): BoundedVolume::GetUnitsTrilinearClamped and GetUnitsBackwardDiffDxDyDz (reference BoundedVolume.h:93-106 ->
+// Volume.h:224-295).  The arithmetic -- a sample's base cell and its lerp tree, the gradient's base cell, its 20-cell stencil, the
+// backward differences and their blend -- is written once, over the dense cell readers RayF32 / RayF16 / RayC32 (pitched rows, two
+// cells a load) and over any cell accessor float(int x, int y, int z) (trilinear_over, gradient_over: the brick renderers).
+// GEOM is any parameter block with the members {VolView vol; V3 size, dims1, hi2[, voxel]; V3 inv_size; int fastdiv, off32;} (RayParams, ColorGeom, MeshParams):
 // inv_size / fastdiv enable the division shortcut of kfx_device.h (div_uniform), off32 says that every cell of the
 // volume lies within 4 GiB of its base, so addresses are a uniform base plus a 32-bit lane offset (the saddr form of
 // global_load: no 64-bit address arithmetic per lane).
@@ -225,6 +227,14 @@ __device__ __forceinline__ float march_step(const float sdf, const float min_del
     return sdf > 0 ? (min_delta > sdf ? min_delta : sdf) : trunc;
 }
 
+// the blend of a sample's eight cells (Volume.h:244-250), v<dz><dy><dx>: the one lerp tree of every trilinear sample -- the dense
+// row-pair loads below, the class-table march's split loads, the brick samplers (raycast_bricks.hip, mesh_bricks.hip)
+__device__ __forceinline__ float trilinear_blend(const float v000, const float v001, const float v010, const float v011, const float v100,
+                                                 const float v101, const float v110, const float v111, const float fx, const float fy, const float fz)
+{
+    return lerp(lerp(lerp(v000, v001, fx), lerp(v010, v011, fx), fy), lerp(lerp(v100, v101, fx), lerp(v110, v111, fx), fy), fz);
+}
+
 // the eight cells of the sample and their blend (Volume.h:236-250)
 template <typename CELL, typename GEOM>
 __device__ __forceinline__ float trilinear_at(const GEOM& p, const CellPos& c)
@@ -240,8 +250,7 @@ __device__ __forceinline__ float trilinear_at(const GEOM& p, const CellPos& c)
         const size_t o = (size_t)iz * p.vol.img_pitch + (size_t)iy * p.vol.pitch + (size_t)ix * CELL::BYTES;
         CELL::pair4(p.vol.ptr, o, o + p.vol.pitch, o + p.vol.img_pitch, o + p.vol.img_pitch + p.vol.pitch, c00, c10, c01, c11);
     }
-    return lerp(lerp(lerp(c00.x, c00.y, fx), lerp(c10.x, c10.y, fx), fy),
-                lerp(lerp(c01.x, c01.y, fx), lerp(c11.x, c11.y, fx), fy), fz);
+    return trilinear_blend(c00.x, c00.y, c10.x, c10.y, c01.x, c01.y, c11.x, c11.y, fx, fy, fz);
 }
 
 // trilinear_at() in two halves (fp32 or half cells): request the eight cells, and -- later -- wait for them and blend
@@ -262,8 +271,7 @@ __device__ __forceinline__ float trilinear_finish(typename CELL::InFlight& f, co
 {
     float2 c00, c10, c01, c11;
     CELL::finish(f, c00, c10, c01, c11);
-    return lerp(lerp(lerp(c00.x, c00.y, c.fx), lerp(c10.x, c10.y, c.fx), c.fy),
-                lerp(lerp(c01.x, c01.y, c.fx), lerp(c11.x, c11.y, c.fx), c.fy), c.fz);
+    return trilinear_blend(c00.x, c00.y, c10.x, c10.y, c01.x, c01.y, c11.x, c11.y, c.fx, c.fy, c.fz);
 }
 
 template <typename CELL, typename GEOM>
@@ -272,40 +280,79 @@ __device__ __forceinline__ float trilinear(const GEOM& p, const V3 pos_w)
     return trilinear_at<CELL>(p, cell_of(p, pos_w));
 }
 
+// The same sample over any cell source: cell(x, y, z) is the value of a cell of the volume GEOM describes (the brick renderers'
+// accessors go through their brick lists; nothing of p.vol's storage is read).  The base cell and the blend are the dense sample's.
+template <typename GEOM, typename ACC>
+__device__ __forceinline__ float trilinear_over(const GEOM& p, const ACC& cell, const V3 pos_w)
+{
+    const CellPos c = cell_of(p, pos_w);
+    const int ix = c.ix, iy = c.iy, iz = c.iz;
+    const float c000 = cell(ix, iy, iz), c001 = cell(ix + 1, iy, iz), c010 = cell(ix, iy + 1, iz), c011 = cell(ix + 1, iy + 1, iz);
+    const float c100 = cell(ix, iy, iz + 1), c101 = cell(ix + 1, iy, iz + 1), c110 = cell(ix, iy + 1, iz + 1), c111 = cell(ix + 1, iy + 1, iz + 1);
+    return trilinear_blend(c000, c001, c010, c011, c100, c101, c110, c111, c.fx, c.fy, c.fz);
+}
+
 // BoundedVolume::GetUnitsBackwardDiffDxDyDz -> Volume::GetFractionalBackwardDiffDxDyDz.
 // Corner (cx,cy,cz) gradient = v(c) - v(c - e_axis); the 8 corners need the 20 cells of
 // {-1,0,1}^3 (relative to the clamped base) that have at most one coordinate equal to -1.
-template <typename CELL, typename GEOM>
-__device__ __forceinline__ V3 gradient(const GEOM& p, const V3 pos_w)
+// The stencil's base cell, clamped to [1, dim - 2] (Volume.h:271-273), and the fractions against it.  (raycast.hip's grad_cell_z is its z
+// alone; a per-axis helper under both reorders the dense kernels' instructions, so the axis is stated there again.)
+template <typename GEOM>
+__device__ __forceinline__ CellPos gradient_base(const GEOM& p, const V3 pos_w)
 {
     const V3 pos_v = div_cw(pos_w - p.vol.bmin, p.size);
     const V3 pf = v3(pos_v.x * p.dims1.x, pos_v.y * p.dims1.y, pos_v.z * p.dims1.z);
-    const int ix = (int)fmaxf(fminf(p.hi2.x, floorf(pf.x)), 1.f);
-    const int iy = (int)fmaxf(fminf(p.hi2.y, floorf(pf.y)), 1.f);
-    const int iz = (int)fmaxf(fminf(p.hi2.z, floorf(pf.z)), 1.f);
-    const float fx = pf.x - (float)ix, fy = pf.y - (float)iy, fz = pf.z - (float)iz;
-    const VolView& v = p.vol;
+    CellPos b;
+    b.ix = (int)fmaxf(fminf(p.hi2.x, floorf(pf.x)), 1.f);
+    b.iy = (int)fmaxf(fminf(p.hi2.y, floorf(pf.y)), 1.f);
+    b.iz = (int)fmaxf(fminf(p.hi2.z, floorf(pf.z)), 1.f);
+    b.fx = pf.x - (float)b.ix; b.fy = pf.y - (float)b.iy; b.fz = pf.z - (float)b.iz;
+    return b;
+}
+
+// Where the 20 cells come from, a row at a time: pair(x, y, z) = cells x and x + 1 of row (y, z), val(x, y, z) = cell x of it.
+// DenseRows: the pitched rows of a volume in memory, x and x + 1 in one load.  CellRows: any float cell(int x, int y, int z), a cell
+// a call.  The stencil below is ONE body over either -- the loads are what differs, and they are handed in; with the base and the blend
+// as functions over the 20 values instead, hipcc schedules the dense kernels' epilogues differently (profiles/ray_stencil_shared).
+template <typename CELL>
+struct DenseRows {
+    const VolView& v;
+    __device__ __forceinline__ float2 pair(int x, int y, int z) const { return CELL::pair(rowp(v, y, z), x); }
+    __device__ __forceinline__ float val(int x, int y, int z) const { return CELL::val(rowp(v, y, z), x); }
+};
+template <typename ACC>
+struct CellRows {
+    const ACC& cell;
+    __device__ __forceinline__ float2 pair(int x, int y, int z) const { const float a = cell(x, y, z); return make_float2(a, cell(x + 1, y, z)); }
+    __device__ __forceinline__ float val(int x, int y, int z) const { return cell(x, y, z); }
+};
+
+template <typename GEOM, typename ROWS>
+__device__ __forceinline__ V3 gradient_stencil(const GEOM& p, const ROWS& rows, const V3 pos_w)
+{
+    const CellPos b = gradient_base(p, pos_w);
+    const int ix = b.ix, iy = b.iy, iz = b.iz;
+    const float fx = b.fx, fy = b.fy, fz = b.fz;
     // c[dz][dy][dx] for dx,dy,dz in {0,1}; mx/my/mz = the cells one step back along x/y/z.
     float c[2][2][2], mx[2][2], my[2][2], mz[2][2];
 #pragma unroll
     for (int dz = 0; dz < 2; ++dz)
 #pragma unroll
         for (int dy = 0; dy < 2; ++dy) {
-            const unsigned char* r = rowp(v, iy + dy, iz + dz);
-            mx[dz][dy] = CELL::val(r, ix - 1);
-            const float2 cc = CELL::pair(r, ix);
+            mx[dz][dy] = rows.val(ix - 1, iy + dy, iz + dz);
+            const float2 cc = rows.pair(ix, iy + dy, iz + dz);
             c[dz][dy][0] = cc.x;
             c[dz][dy][1] = cc.y;
         }
 #pragma unroll
     for (int dz = 0; dz < 2; ++dz) {
-        const float2 cc = CELL::pair(rowp(v, iy - 1, iz + dz), ix);
+        const float2 cc = rows.pair(ix, iy - 1, iz + dz);
         my[dz][0] = cc.x;
         my[dz][1] = cc.y;
     }
 #pragma unroll
     for (int dy = 0; dy < 2; ++dy) {
-        const float2 cc = CELL::pair(rowp(v, iy + dy, iz - 1), ix);
+        const float2 cc = rows.pair(ix, iy + dy, iz - 1);
         mz[dy][0] = cc.x;
         mz[dy][1] = cc.y;
     }
@@ -325,6 +372,18 @@ __device__ __forceinline__ V3 gradient(const GEOM& p, const V3 pos_w)
     const V3 deriv = lerp(lerp(lerp(g[0][0][0], g[0][0][1], fx), lerp(g[0][1][0], g[0][1][1], fx), fy),
                           lerp(lerp(g[1][0][0], g[1][0][1], fx), lerp(g[1][1][0], g[1][1][1], fx), fy), fz);
     return div_cw(deriv, p.voxel);
+}
+
+template <typename CELL, typename GEOM>
+__device__ __forceinline__ V3 gradient(const GEOM& p, const V3 pos_w)
+{
+    return gradient_stencil(p, DenseRows<CELL>{p.vol}, pos_w);
+}
+// the same gradient over any cell source (trilinear_over's `cell`)
+template <typename GEOM, typename ACC>
+__device__ __forceinline__ V3 gradient_over(const GEOM& p, const ACC& cell, const V3 pos_w)
+{
+    return gradient_stencil(p, CellRows<ACC>{cell}, pos_w);
 }
 
 // Host side: the arithmetic / addressing shortcuts of a geometry block whose vol / size members are set (g.vol.d planes

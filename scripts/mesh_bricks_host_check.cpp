@@ -89,31 +89,31 @@ int main()
     CHECK(brick_mesh_scratch(0, 0).bytes == 256 && brick_mesh_scratch(1, 0).bytes == 256 + 256 + 256 + 256 + 256);
     CHECK(brick_mesh_scratch(70000, 0).bytes == 7847424);
     for (unsigned long long n = 0; n < 3000; ++n) CHECK(brick_mesh_scratch(n + 1, 0).bytes >= brick_mesh_scratch(n, 0).bytes);
-    CHECK(brick_mesh_check_counts(BRICK_MAX, BRICK_MAX).code == 0 && brick_mesh_check_counts(BRICK_MAX + 1, 0).code == KFX_E_RANGE &&
-          brick_mesh_check_counts(0, BRICK_MAX + 1).code == KFX_E_RANGE && brick_mesh_check_counts(~0ull, 0).code == KFX_E_RANGE);
+    CHECK(brick_check_counts(BRICK_MAX, BRICK_MAX).code == 0 && brick_check_counts(BRICK_MAX + 1, 0).code == KFX_E_RANGE &&
+          brick_check_counts(0, BRICK_MAX + 1).code == KFX_E_RANGE && brick_check_counts(~0ull, 0).code == KFX_E_RANGE);
 
     // frames: null, the cell kind, the dimensions kfx_mesh_plan accepts, the brick limit -- in that order
     BrickGeom g{};
     const kfx_volume ok = frame(40, 24, 16), ragged = frame(44, 29, 35), huge = frame(4096, 4096, 4096);
-    CHECK(brick_mesh_check_frame(nullptr, KFX_CELL_F32, g).code == KFX_E_NULL);
-    CHECK(brick_mesh_check_frame(&ok, KFX_CELL_COLOR, g).code == KFX_E_RANGE && brick_mesh_check_frame(&ok, -1, g).code == KFX_E_RANGE);
-    CHECK(brick_mesh_check_frame(&ok, KFX_CELL_F32, g).code == 0 && g.nbx == 5 && g.nby == 3 && g.nbz == 2 && g.nb == 30);
-    CHECK(brick_mesh_check_frame(&ragged, KFX_CELL_F16, g).code == 0 && g.nbx == 6 && g.nby == 4 && g.nbz == 5 && g.w == 44 && g.h == 29 && g.d == 35);
-    CHECK(brick_mesh_check_frame(&huge, KFX_CELL_F32, g).code == 0 && g.nb == 134217728ull);
+    CHECK(brick_check_frame(nullptr, KFX_CELL_F32, g).code == KFX_E_NULL);
+    CHECK(brick_check_frame(&ok, KFX_CELL_COLOR, g).code == KFX_E_RANGE && brick_check_frame(&ok, -1, g).code == KFX_E_RANGE);
+    CHECK(brick_check_frame(&ok, KFX_CELL_F32, g).code == 0 && g.nbx == 5 && g.nby == 3 && g.nbz == 2 && g.nb == 30);
+    CHECK(brick_check_frame(&ragged, KFX_CELL_F16, g).code == 0 && g.nbx == 6 && g.nby == 4 && g.nbz == 5 && g.w == 44 && g.h == 29 && g.d == 35);
+    CHECK(brick_check_frame(&huge, KFX_CELL_F32, g).code == 0 && g.nb == 134217728ull);
     for (const size_t bad : {(size_t)0, (size_t)1, (size_t)2, (size_t)65536, ~(size_t)0}) {
         const kfx_volume a = frame(bad, 24, 16), b = frame(40, bad, 16), c = frame(40, 24, bad);
-        CHECK(brick_mesh_check_frame(&a, KFX_CELL_F32, g).code == KFX_E_SHAPE && brick_mesh_check_frame(&b, KFX_CELL_F32, g).code == KFX_E_SHAPE &&
-              brick_mesh_check_frame(&c, KFX_CELL_F32, g).code == KFX_E_SHAPE);
-        CHECK(brick_mesh_check_frame(&a, 7, g).code == KFX_E_RANGE);   // (the kind before the dimensions)
+        CHECK(brick_check_frame(&a, KFX_CELL_F32, g).code == KFX_E_SHAPE && brick_check_frame(&b, KFX_CELL_F32, g).code == KFX_E_SHAPE &&
+              brick_check_frame(&c, KFX_CELL_F32, g).code == KFX_E_SHAPE);
+        CHECK(brick_check_frame(&a, 7, g).code == KFX_E_RANGE);   // (the kind before the dimensions)
     }
     const kfx_volume edge = frame(3, 3, 3), big = frame(65535, 65535, 65535), most = frame(65535, 65535, 24);
-    CHECK(brick_mesh_check_frame(&edge, KFX_CELL_F32, g).code == 0 && g.nb == 1 && !brick_mesh_has_color(g, &edge));
-    CHECK(brick_mesh_check_frame(&big, KFX_CELL_F32, g).code == KFX_E_RANGE);   // 2^39 bricks
-    CHECK(brick_mesh_check_frame(&most, KFX_CELL_F32, g).code == 0 && g.nb == 201326592ull);
+    CHECK(brick_check_frame(&edge, KFX_CELL_F32, g).code == 0 && g.nb == 1 && !brick_mesh_has_color(g, &edge));
+    CHECK(brick_check_frame(&big, KFX_CELL_F32, g).code == KFX_E_RANGE);   // 2^39 bricks
+    CHECK(brick_check_frame(&most, KFX_CELL_F32, g).code == 0 && g.nb == 201326592ull);
     // colour: asked for and IsValid()
     const kfx_volume thin = frame(40, 7, 16);
-    CHECK(brick_mesh_check_frame(&thin, KFX_CELL_F32, g).code == 0 && !brick_mesh_has_color(g, &thin));
-    CHECK(brick_mesh_check_frame(&ok, KFX_CELL_F32, g).code == 0 && brick_mesh_has_color(g, &ok) && !brick_mesh_has_color(g, nullptr));
+    CHECK(brick_check_frame(&thin, KFX_CELL_F32, g).code == 0 && !brick_mesh_has_color(g, &thin));
+    CHECK(brick_check_frame(&ok, KFX_CELL_F32, g).code == 0 && brick_mesh_has_color(g, &ok) && !brick_mesh_has_color(g, nullptr));
 
     // the outputs: present, then aligned (colours may be absent)
     const char* const p = (const char*)((uintptr_t)1 << 20);

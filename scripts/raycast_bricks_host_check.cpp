@@ -115,8 +115,8 @@ int main()
     CHECK(brick_ray_scratch(0, 0).bytes == 256 && brick_ray_scratch(1, 0).bytes == 512 && brick_ray_scratch(16, 0).bytes == 512 && brick_ray_scratch(17, 0).bytes == 768);
     CHECK(brick_ray_scratch(70000, 0).bytes == 256 + 8 * 262144 && brick_ray_scratch(BRICK_MAX, BRICK_MAX).bytes == 256 + 2 * 8 * (1ull << 32));
     for (unsigned long long n = 0; n < 3000; ++n) CHECK(brick_ray_scratch(n + 1, 0).bytes >= brick_ray_scratch(n, 0).bytes);
-    CHECK(brick_ray_check_counts(BRICK_MAX, BRICK_MAX).code == 0 && brick_ray_check_counts(BRICK_MAX + 1, 0).code == KFX_E_RANGE &&
-          brick_ray_check_counts(0, BRICK_MAX + 1).code == KFX_E_RANGE && brick_ray_check_counts(~0ull, 0).code == KFX_E_RANGE);
+    CHECK(brick_check_counts(BRICK_MAX, BRICK_MAX).code == 0 && brick_check_counts(BRICK_MAX + 1, 0).code == KFX_E_RANGE &&
+          brick_check_counts(0, BRICK_MAX + 1).code == KFX_E_RANGE && brick_check_counts(~0ull, 0).code == KFX_E_RANGE);
     // the largest table: 2^32 slots, the mask all ones, no shift
     {
         const BrickTable t = brick_table(BRICK_MAX);
@@ -127,21 +127,21 @@ int main()
     // frames: null, the cell kind, the dimensions kfx_raycast_sdf accepts, the brick limit -- in that order
     BrickGeom g{};
     const kfx_volume ok = frame(40, 24, 16), ragged = frame(44, 29, 35), huge = frame(4096, 4096, 4096);
-    CHECK(brick_ray_check_frame(nullptr, g).code == KFX_E_NULL && brick_ray_check_frame(nullptr, KFX_CELL_F32, g).code == KFX_E_NULL);
-    CHECK(brick_ray_check_frame(&ok, KFX_CELL_COLOR, g).code == KFX_E_RANGE && brick_ray_check_frame(&ok, -1, g).code == KFX_E_RANGE);
-    CHECK(brick_ray_check_frame(&ok, KFX_CELL_F32, g).code == 0 && g.nbx == 5 && g.nby == 3 && g.nbz == 2 && g.nb == 30);
-    CHECK(brick_ray_check_frame(&ragged, KFX_CELL_F16, g).code == 0 && g.nbx == 6 && g.nby == 4 && g.nbz == 5 && g.w == 44 && g.h == 29 && g.d == 35);
-    CHECK(brick_ray_check_frame(&huge, g).code == 0 && g.nb == 134217728ull);
+    CHECK(brick_check_frame(nullptr, g).code == KFX_E_NULL && brick_check_frame(nullptr, KFX_CELL_F32, g).code == KFX_E_NULL);
+    CHECK(brick_check_frame(&ok, KFX_CELL_COLOR, g).code == KFX_E_RANGE && brick_check_frame(&ok, -1, g).code == KFX_E_RANGE);
+    CHECK(brick_check_frame(&ok, KFX_CELL_F32, g).code == 0 && g.nbx == 5 && g.nby == 3 && g.nbz == 2 && g.nb == 30);
+    CHECK(brick_check_frame(&ragged, KFX_CELL_F16, g).code == 0 && g.nbx == 6 && g.nby == 4 && g.nbz == 5 && g.w == 44 && g.h == 29 && g.d == 35);
+    CHECK(brick_check_frame(&huge, g).code == 0 && g.nb == 134217728ull);
     for (const size_t bad : {(size_t)0, (size_t)1, (size_t)2, (size_t)65536, ~(size_t)0}) {
         const kfx_volume a = frame(bad, 24, 16), b = frame(40, bad, 16), c = frame(40, 24, bad);
-        CHECK(brick_ray_check_frame(&a, g).code == KFX_E_SHAPE && brick_ray_check_frame(&b, KFX_CELL_F32, g).code == KFX_E_SHAPE &&
-              brick_ray_check_frame(&c, KFX_CELL_F16, g).code == KFX_E_SHAPE);
-        CHECK(brick_ray_check_frame(&a, 7, g).code == KFX_E_RANGE);   // (the kind before the dimensions)
+        CHECK(brick_check_frame(&a, g).code == KFX_E_SHAPE && brick_check_frame(&b, KFX_CELL_F32, g).code == KFX_E_SHAPE &&
+              brick_check_frame(&c, KFX_CELL_F16, g).code == KFX_E_SHAPE);
+        CHECK(brick_check_frame(&a, 7, g).code == KFX_E_RANGE);   // (the kind before the dimensions)
     }
     const kfx_volume edge = frame(3, 3, 3), big = frame(65535, 65535, 65535), most = frame(65535, 65535, 24);
-    CHECK(brick_ray_check_frame(&edge, g).code == 0 && g.nb == 1);
-    CHECK(brick_ray_check_frame(&big, g).code == KFX_E_RANGE);   // 2^39 bricks
-    CHECK(brick_ray_check_frame(&most, g).code == 0 && g.nb == 201326592ull);
+    CHECK(brick_check_frame(&edge, g).code == 0 && g.nb == 1);
+    CHECK(brick_check_frame(&big, g).code == KFX_E_RANGE);   // 2^39 bricks
+    CHECK(brick_check_frame(&most, g).code == 0 && g.nb == 201326592ull);
 
     // an id list: nothing asked of an empty one; present, then aligned
     const char* const p = (const char*)((uintptr_t)1 << 20);
