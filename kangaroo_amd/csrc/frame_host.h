@@ -37,14 +37,14 @@ inline void se3_inverse(const float T_wc[12], float out[12])
     }
 }
 
-// The packed texel image {nx, ny, nz, depth} of a frame (fuse.hip: tex_layout), owned by the frame object: written by the fused vbo /
+// The packed texel image {nx, ny, nz, depth} of a frame (host_args.h: tex_layout), owned by the frame object: written by the fused vbo /
 // normals launch of a step, staged by LDS-DMA in the SdfFuse of the SAME step.  No device (the argument checks of tests/test_abi_cpu.py
 // run without one) or no memory: a null image, and the SdfFuse packs per call instead.
 inline kfx_image texel_image_alloc(size_t w, size_t h)
 {
-    const size_t tpitch = (w * 16 + 255) / 256 * 256;
+    const TexLayout tl = tex_layout(w, h);
     void* buf = nullptr;
-    if (tpitch < (1u << 24) && hipMalloc(&buf, texel_image_bytes(w, h)) == hipSuccess) return kfx_image{tpitch, buf, w, h};
+    if (tl.tpitch < (1u << 24) && hipMalloc(&buf, tl.bytes) == hipSuccess) return kfx_image{tl.tpitch, buf, w, h};
     (void)hipGetLastError();
     return kfx_image{0, nullptr, 0, 0};
 }

@@ -1664,42 +1664,21 @@ using namespace kfx;
 // ---- the packed texel image of the tiled kernels' LDS-DMA staging --------------------------------------------------------
 // {nx, ny, nz, depth} per pixel of the depth image: copies of the normal map's xyz and of the depth image (what the kernels'
 // register path packs texel by texel while it stages).
-// ... and the maximum finite depth of every block of 8 x 4 pixels (the workgroup's tile is 64 x 4: eight blocks), -inf where a
-// block has none: what the kernels bound a brick's farthest depth with (bmax: rows of bw8 floats, one row per four image rows).
+// ... and the maximum finite depth of every block of 8 x 4 pixels (the workgroup's tile is 64 x 4: eight blocks): what the kernels
+// bound a brick's farthest depth with.  The stores are texel_put / texel_block_max (kfx_device.h), the geometry tex_layout (host_args.h).
 __global__ __launch_bounds__(256) void k_pack_texels(const ImgView depth, const ImgView norm, unsigned char* __restrict__ tex, const size_t tpitch,
                                                      float* __restrict__ bmax, const unsigned bw8)
 {
-    __shared__ float s_max[8][4];   // per 8-pixel block of the row of tiles: the four image rows' maxima
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int u = blockIdx.x * 64 + lane, v = blockIdx.y * 4 + wv;
+    __shared__ float s_max[PIX_H][8];
+    int u, v, lane, wv;
+    pixel_xy(u, v, lane, wv);
     float d = -__builtin_inff();
     if (u < depth.w && v < depth.h) {
-        const float4 n = row<float4>(norm, (size_t)v)[u];
-        const float dd = row<float>(depth, (size_t)v)[u];
-        reinterpret_cast<float4*>(tex + (size_t)v * tpitch)[u] = make_float4(n.x, n.y, n.z, dd);
-        d = dd;
+        d = row<float>(depth, (size_t)v)[u];
+        texel_put(tex, tpitch, u, v, row<float4>(norm, (size_t)v)[u], d);
     }
-    d = wave8_combine(fmaxf(d, -__builtin_inff()), FMax{});   // (fmaxf drops NaN)
-    if ((lane & 7) == 0) s_max[lane >> 3][wv] = d;
-    __syncthreads();
-    if (threadIdx.x < 8)
-        bmax[(size_t)blockIdx.y * bw8 + blockIdx.x * 8 + threadIdx.x] =
-            block_get<4>(s_max[threadIdx.x], FMax{});
+    texel_block_max(bmax, bw8, lane, wv, d, s_max);
 }
-
-// the packed image's geometry for a w x h depth image: texel rows of tpitch bytes, then the block maxima
-struct TexLayout { size_t tpitch, bmax_off, bytes; unsigned bw8, bh4; };
-static TexLayout tex_layout(size_t w, size_t h)
-{
-    TexLayout t;
-    t.tpitch = (w * 16 + 255) / 256 * 256;
-    t.bw8 = (unsigned)((w + 63) / 64 * 8);
-    t.bh4 = (unsigned)((h + 3) / 4);
-    t.bmax_off = t.tpitch * h;
-    t.bytes = t.bmax_off + (size_t)t.bw8 * t.bh4 * sizeof(float);
-    return t;
-}
-size_t kfx::texel_image_bytes(size_t w, size_t h) { return tex_layout(w, h).bytes; }
 
 // Library scratch for callers that bring depth and normals only (kfx_sdf_fuse and its siblings; kfx_frame_step brings the packed
 // image its fused preprocess wrote).  One buffer per calling thread, device and stream: the pack launch and the SdfFuse launches
@@ -2115,7 +2094,7 @@ static int fuse_launch(const kfx_volume* vol, const kfx_image* depth, const kfx_
         bool any_plain = false;
         for (int ri = 0; ri < n_ranges; ++ri) any_plain = any_plain || !ranges[ri].plan.dxt;
         if (KFX_FUSE_STAGE_DMA && any_plain) {
-            // (the caller's packed image -- kfx::texel_image_bytes(w, h) bytes laid out by tex_layout, written by the fused preprocess --
+            // (the caller's packed image -- tex_layout(w, h).bytes bytes laid out by tex_layout, written by the fused preprocess --
             //  is recognised by its geometry: w, h and pitch of the depth image's layout)
             const TexLayout tl = tex_layout(depth->w, depth->h);
             if (texels && texels->ptr && texels->w == depth->w && texels->h == depth->h && texels->pitch == tl.tpitch && !((uintptr_t)texels->ptr & 15)) {

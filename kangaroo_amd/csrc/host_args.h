@@ -71,8 +71,22 @@ inline int check_render_images(const kfx_image* depth, const kfx_image* norm, co
     return check_image(img, 4, lead->w, lead->h, what);
 }
 
-// the grid of a per-pixel launch: workgroups of 256 = 64 x 4 pixels
-inline dim3 pixel_grid(int w, int h) { return dim3(ceil_div(w, 64), ceil_div(h, 4)); }
+// the grid of a per-pixel launch: workgroups of 256 = PIX_W x PIX_H pixels, whose threads find their pixel with pixel_xy (kfx_device.h)
+inline dim3 pixel_grid(int w, int h) { return dim3(ceil_div(w, PIX_W), ceil_div(h, PIX_H)); }
+
+// The packed texel image of a w x h depth image (kfx_device.h: texel_put / texel_block_max write it, the tiled SdfFuse kernels stage it by LDS-DMA):
+// texel rows of tpitch bytes -- w * 16 rounded up to 256 -- then the maxima of the 8 x 4 pixel blocks, bh4 rows of bw8 floats
+struct TexLayout { size_t tpitch, bmax_off, bytes; unsigned bw8, bh4; };
+inline TexLayout tex_layout(size_t w, size_t h)
+{
+    TexLayout t;
+    t.tpitch = (w * 16 + 255) / 256 * 256;
+    t.bw8 = (unsigned)((w + 63) / 64 * 8);
+    t.bh4 = (unsigned)((h + 3) / 4);
+    t.bmax_off = t.tpitch * h;
+    t.bytes = t.bmax_off + (size_t)t.bw8 * t.bh4 * sizeof(float);
+    return t;
+}
 
 // The full volume a Z-slab (planes [z_offset, z_offset + d) of full_d) belongs to, for set_geometry / set_voxel_size: the base
 // pointer moved back by z_offset planes -- a virtual base, dereferenced only inside the stored planes -- and the full extent in z.

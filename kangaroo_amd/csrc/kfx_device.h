@@ -219,6 +219,85 @@ struct VolView {
 
 __host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// ---- a per-pixel launch and a depth pixel's geometry: one definition each ---------------------------------------------
+// Workgroups of 256 = PIX_W x PIX_H pixels, a wave per image row (host_args.h: pixel_grid is the grid): the thread's pixel, and for a
+// kernel that also works across the lanes of its row the thread's lane (its pixel's column in the tile) and wave (its row)
+constexpr int PIX_W = 64, PIX_H = 4;
+__device__ __forceinline__ void pixel_xy(int& u, int& v, int& lane, int& wv)
+{
+    lane = threadIdx.x % PIX_W;
+    wv = threadIdx.x / PIX_W;
+    u = blockIdx.x * PIX_W + lane;
+    v = blockIdx.y * PIX_H + wv;
+}
+__device__ __forceinline__ void pixel_xy(int& u, int& v)
+{
+    int lane, wv;
+    pixel_xy(u, v, lane, wv);
+}
+// KernDepthToVbo (cu_depth_tools.cu:59-70): Unproject(u, v, kz) (ImageIntrinsics.h:127-131) of a pixel whose depth is kz, w = 1
+__device__ __forceinline__ float4 depth_vertex(const Intr& K, float kz, int u, int v)
+{
+    return make_float4(kz * ((float)u - K.u0) / K.fu, kz * ((float)v - K.v0) / K.fv, kz, 1.0f);
+}
+// KernNormalsFromVbo (cu_normals.cu:12-38): the vertices of a pixel, of its right and of its lower neighbour
+__device__ __forceinline__ float4 vertex_normal(float4 Vc, float4 Vr, float4 Vu)
+{
+    const V3 a = v3(Vr.x - Vc.x, Vr.y - Vc.y, Vr.z - Vc.z);
+    const V3 b = v3(Vu.x - Vc.x, Vu.y - Vc.y, Vu.z - Vc.z);
+    const V3 axb = v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
+    const float mag = length(axb);
+    return make_float4(-axb.x / mag, -axb.y / mag, -axb.z / mag, 1.0f);
+}
+// KernBoxHalfIgnoreInvalid<float,float,float> (cu_resample.cu:89-111): mean of the finite samples of a 2 x 2 block, NaN if
+// none; samples are added in the order tl, tr, bl, br
+__device__ __forceinline__ float box_half(float tl, float tr, float bl, float br)
+{
+    int n = 0;
+    float sum = 0;
+    if (isfinite(tl)) { sum += tl; n++; }
+    if (isfinite(tr)) { sum += tr; n++; }
+    if (isfinite(bl)) { sum += bl; n++; }
+    if (isfinite(br)) { sum += br; n++; }
+    return n > 0 ? (sum / n) : __builtin_nanf("");
+}
+// Image<uchar3>::GetBilinear<float3> (sampling.h lerp(uchar3...): integer difference, converted, times t, plus the first
+// value; rows blended as float3) of an RGB image at (pu, pv), at least one pixel inside it
+struct __attribute__((packed)) Rgb3 { unsigned char x, y, z; };
+__device__ __forceinline__ V3 rgb_bilinear(const unsigned char* ptr, size_t pitch, float pu, float pv)
+{
+    const float ix = floorf(pu), iy = floorf(pv);
+    const float fx = pu - ix, fy = pv - iy;
+    const Rgb3* bl = reinterpret_cast<const Rgb3*>(ptr + (size_t)iy * pitch) + (size_t)ix;
+    const Rgb3* tl = reinterpret_cast<const Rgb3*>(ptr + (size_t)(iy + 1) * pitch) + (size_t)ix;
+    const Rgb3 b0 = bl[0], b1 = bl[1], t0 = tl[0], t1 = tl[1];
+    const V3 lo = v3((float)b0.x + fx * (float)((int)b1.x - (int)b0.x), (float)b0.y + fx * (float)((int)b1.y - (int)b0.y),
+                     (float)b0.z + fx * (float)((int)b1.z - (int)b0.z));
+    const V3 hi = v3((float)t0.x + fx * (float)((int)t1.x - (int)t0.x), (float)t0.y + fx * (float)((int)t1.y - (int)t0.y),
+                     (float)t0.z + fx * (float)((int)t1.z - (int)t0.z));
+    return v3(lo.x + fy * (hi.x - lo.x), lo.y + fy * (hi.y - lo.y), lo.z + fy * (hi.z - lo.z));
+}
+// The packed texel image of the tiled SdfFuse kernels (fuse.hip; its geometry: host_args.h, tex_layout), written by a pixel_xy
+// workgroup in two steps.  texel_put, by the thread of a pixel inside the image: {nx, ny, nz, depth}, copies of the normal's xyz
+// and of the depth image's own value d.  texel_block_max, by every thread, with pixel_xy's lane and wave and that d, or -inf for a
+// thread without a pixel:
+// the maximum finite depth of each 8 x 4 block of the workgroup's 64 x 4 pixels (-inf where a block has none; fmaxf drops NaN),
+// in rows of bw8 floats, one row per four image rows.  s_max: PIX_H x 8 floats of LDS; a barrier inside.
+__device__ __forceinline__ void texel_put(unsigned char* tex, size_t tpitch, int u, int v, float4 N, float d)
+{
+    reinterpret_cast<float4*>(tex + (size_t)v * tpitch)[u] = make_float4(N.x, N.y, N.z, d);
+}
+__device__ __forceinline__ void texel_block_max(float* bmax, unsigned bw8, int lane, int wv, float d, float (*s_max)[8])
+{
+    static_assert(PIX_W == 64 && PIX_H == 4, "eight 8-lane blocks per wave, four waves");
+    d = wave8_combine(fmaxf(d, -__builtin_inff()), FMax{});
+    if ((lane & 7) == 0) s_max[wv][lane >> 3] = d;
+    __syncthreads();
+    if (threadIdx.x < 8)
+        bmax[(size_t)blockIdx.y * bw8 + blockIdx.x * 8 + threadIdx.x] =
+            fmaxf(fmaxf(s_max[0][threadIdx.x], s_max[1][threadIdx.x]), fmaxf(s_max[2][threadIdx.x], s_max[3][threadIdx.x]));
+}
+
 // The tracked SdfFuse's kept set (fuse.hip, fuse_launch): y-brick row `row` of the parent volume belongs to it
 __host__ __device__ inline bool keep_row(int row, int stride) { return stride > 0 && (unsigned)row % (unsigned)stride == 0u; }
 
@@ -371,8 +450,7 @@ int check_launch(const char* what);
 int hip_status(hipError_t e, const char* what);   // 0, or the error cleared and reported as `what`
 int math_mode(); // KFX_MATH_EXACT / KFX_MATH_FAST
 // kfx_frame_step's pair (frame.hip): the fused vbo / normals launch also writes the packed texel image {nx, ny, nz, depth} that the
-// SdfFuse of the same frame stages by LDS-DMA (preprocess.hip, fuse.hip); texels may be null
-size_t texel_image_bytes(size_t w, size_t h);   // the packed image of a w x h depth image: texel rows + block maxima (fuse.hip, tex_layout)
+// SdfFuse of the same frame stages by LDS-DMA (preprocess.hip, fuse.hip; host_args.h: tex_layout); texels may be null
 int depth_to_vbo_normals_texels(const kfx_image* vbo, const kfx_image* nrm, const kfx_image* depth, const float K[4], float scale,
                                 const kfx_image* texels, kfx_stream stream);
 int sdf_fuse_slab_texels(const kfx_volume* vol, const kfx_slab* slab, const kfx_image* depth, const kfx_image* norm, const kfx_image* texels,

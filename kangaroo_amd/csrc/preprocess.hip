@@ -36,14 +36,14 @@ __device__ __forceinline__ float load_clamped(const BilParams& p, int x, int y)
     return (float)reinterpret_cast<const Ti*>(p.in + (size_t)y * p.in_pitch)[x];
 }
 
-// KernElementwiseScaleBias (cu_operations.cu:39-49), b = s*a + offset: the ONE statement behind k_scale_bias_f32 / _u16 and behind the
-// converting loads of the k_bilateral_depth* kernels, so that a sensor image filtered in one launch carries the bits of ScaleBias
-// followed by BilateralFilter in both numerics modes.
+// KernElementwiseScaleBias (cu_operations.cu:39-49), b = s*a + offset: the ONE statement behind k_scale_bias and behind the
+// converting loads of the bilateral kernels' ToMetres form, so that a sensor image filtered in one launch carries the bits of
+// ScaleBias followed by BilateralFilter in both numerics modes.
 __device__ __forceinline__ float scale_bias(float a, float s, float offset) { return s * a + offset; }
 
-// What a bilateral kernel makes of a loaded pixel.  AsLoaded: the image is what is filtered (k_bilateral*).  ToMetres: the image is
-// in sensor units (include/kfx_sensor.h); what is filtered is scale_bias() of it, and a workgroup writes that value of its own
-// output pixels (not of the apron) to the optional `metres` image.
+// What a bilateral kernel makes of a loaded pixel.  AsLoaded: the image is what is filtered (BilateralFilter).  ToMetres: the image
+// is in sensor units (include/kfx_sensor.h); what is filtered is scale_bias() of it, and a workgroup writes that value of its own
+// output pixels (not of the apron) to the optional `metres` image (BilateralFilterDepth).
 struct AsLoaded {
     __device__ __forceinline__ float operator()(float v) const { return v; }
     __device__ __forceinline__ void keep(int, int, float) const {}
@@ -58,10 +58,6 @@ struct ToMetres {
         if (metres) reinterpret_cast<float*>(metres + (size_t)y * mpitch)[x] = m;
     }
 };
-struct BilDepthParams {
-    BilParams b;
-    ToMetres c;
-};
 
 // Workgroup = TX x TY threads (256), each thread filters PY pixels of one column, so the LDS
 // tile is (TX + 2R) x (TY*PY + 2R): taller tiles amortise the apron (7x7 window at TX x TY*PY =
@@ -69,7 +65,7 @@ struct BilDepthParams {
 // uchar/ushort value and every difference of two is exactly representable, so (float)(p - q),
 // q >= minval and w * q give the reference's results.
 template <typename Ti, int TX, int TY, int PY, typename Conv>
-__device__ __forceinline__ void bilateral_tile(const BilParams p, const Conv conv)
+__global__ __launch_bounds__(TX * TY) void k_bilateral(const BilParams p, const Conv conv)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int NT = TX * TY;
@@ -123,16 +119,6 @@ __device__ __forceinline__ void bilateral_tile(const BilParams p, const Conv con
         reinterpret_cast<float*>(p.out + (size_t)y * p.out_pitch)[x] = sum / sumw;
     }
 }
-template <typename Ti, int TX, int TY, int PY>
-__global__ __launch_bounds__(TX * TY) void k_bilateral(const BilParams p)
-{
-    bilateral_tile<Ti, TX, TY, PY>(p, AsLoaded{});
-}
-template <typename Ti, int TX, int TY, int PY>
-__global__ __launch_bounds__(TX * TY) void k_bilateral_depth(const BilDepthParams p)
-{
-    bilateral_tile<Ti, TX, TY, PY>(p.b, p.c);
-}
 
 // Fast-numerics variant (kfx_set_math_mode(KFX_MATH_FAST)) for a compile-time radius: the exact kernel spends most of
 // its time in the correctly rounded division -(id2) / (2 gr^2) of every tap (49 per pixel at R = 3) and in a
@@ -140,7 +126,7 @@ __global__ __launch_bounds__(TX * TY) void k_bilateral_depth(const BilDepthParam
 // the argument moves by <= 1.5 ulp, far inside the accuracy of the hardware exp), validity is a select and the
 // (2R+1)^2 taps are fully unrolled.  Same tile, same tap order, same hardware exp.
 template <typename Ti, int R, typename Conv>
-__device__ __forceinline__ void bilateral_fast_tile(const BilParams& p, const Conv& conv)
+__global__ __launch_bounds__(256) void k_bilateral_fast(const BilParams p, const Conv conv)
 {
     constexpr int TX = 16, TY = 16, D = 2 * R + 1, TW = TX + 2 * R, TH = TY + 2 * R;
     __shared__ float tile[TH * TW];
@@ -178,22 +164,13 @@ __device__ __forceinline__ void bilateral_fast_tile(const BilParams& p, const Co
     if (check && !(pc >= p.minval)) sum = sumw = 0.f; // the reference skips the window: 0 / 0 = NaN
     reinterpret_cast<float*>(p.out + (size_t)y * p.out_pitch)[x] = sum / sumw;
 }
-template <typename Ti, int R>
-__global__ __launch_bounds__(256) void k_bilateral_fast(const BilParams p)
-{
-    bilateral_fast_tile<Ti, R>(p, AsLoaded{});
-}
-template <typename Ti, int R>
-__global__ __launch_bounds__(256) void k_bilateral_depth_fast(const BilDepthParams p)
-{
-    bilateral_fast_tile<Ti, R>(p.b, p.c);
-}
 
 // Window too large for the LDS tile: straight global gathers.
 template <typename Ti, typename Conv>
-__device__ __forceinline__ void bilateral_gather(const BilParams& p, const Conv& conv)
+__global__ __launch_bounds__(256) void k_bilateral_global(const BilParams p, const Conv conv)
 {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    int x, y;
+    pixel_xy(x, y);
     if (x >= p.w || y >= p.h) return;
     const float pc = conv((float)reinterpret_cast<const Ti*>(p.in + (size_t)y * p.in_pitch)[x]);
     conv.keep(x, y, pc);
@@ -214,16 +191,6 @@ __device__ __forceinline__ void bilateral_gather(const BilParams& p, const Conv&
     }
     reinterpret_cast<float*>(p.out + (size_t)y * p.out_pitch)[x] = sum / sumw;
 }
-template <typename Ti>
-__global__ __launch_bounds__(256) void k_bilateral_global(const BilParams p)
-{
-    bilateral_gather<Ti>(p, AsLoaded{});
-}
-template <typename Ti>
-__global__ __launch_bounds__(256) void k_bilateral_depth_global(const BilDepthParams p)
-{
-    bilateral_gather<Ti>(p.b, p.c);
-}
 
 // Joint ("cross") bilateral filter with an external guide image (cu_bilateral.cu:110-143): weights
 // exp(-sd2 / 2gs^2) * exp(-rd2 / 2gr^2) * exp(-cd2 / 2gc^2) with cd the guide difference; sumw == 0 keeps the input.
@@ -238,7 +205,8 @@ template <typename Tg>
 __global__ __launch_bounds__(256) void k_bilateral_guided(const GuidedParams g)
 {
     const BilParams& p = g.b;
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    int x, y;
+    pixel_xy(x, y);
     if (x >= p.w || y >= p.h) return;
     const float pv = reinterpret_cast<const float*>(p.in + (size_t)y * p.in_pitch)[x];
     const float pcv = (float)reinterpret_cast<const Tg*>(g.guide + (size_t)y * g.gpitch)[x];
@@ -261,57 +229,43 @@ __global__ __launch_bounds__(256) void k_bilateral_guided(const GuidedParams g)
     reinterpret_cast<float*>(p.out + (size_t)y * p.out_pitch)[x] = sumw == 0 ? pv : sum / sumw;
 }
 
-struct VboParams {
+// The parameter block of the per-pixel "out <- in" operators: pixel (x, y) of the w x h launch is out's, and in covers it
+struct PixOp {
     const unsigned char* in;
     size_t in_pitch;
     unsigned char* out;
     size_t out_pitch;
     int w, h;
-    Intr K;
-    float scale;
 };
+template <typename T>
+__device__ __forceinline__ const T* in_row(const PixOp& p, int y) { return reinterpret_cast<const T*>(p.in + (size_t)y * p.in_pitch); }
+template <typename T>
+__device__ __forceinline__ T* out_row(const PixOp& p, int y) { return reinterpret_cast<T*>(p.out + (size_t)y * p.out_pitch); }
 
-// KernDepthToVbo (cu_depth_tools.cu:59-70), Unproject(u,v,z) (ImageIntrinsics.h:127-131)
+// KernDepthToVbo (cu_depth_tools.cu:59-70)
 template <typename Ti>
-__global__ __launch_bounds__(256) void k_depth_to_vbo(const VboParams p)
+__global__ __launch_bounds__(256) void k_depth_to_vbo(const PixOp p, const Intr K, const float scale)
 {
-    const int u = blockIdx.x * 64 + (threadIdx.x & 63), v = blockIdx.y * 4 + (threadIdx.x >> 6);
+    int u, v;
+    pixel_xy(u, v);
     if (u >= p.w || v >= p.h) return;
-    const float kz = p.scale * (float)reinterpret_cast<const Ti*>(p.in + (size_t)v * p.in_pitch)[u];
-    const float4 P = make_float4(kz * ((float)u - p.K.u0) / p.K.fu, kz * ((float)v - p.K.v0) / p.K.fv, kz, 1.0f);
-    reinterpret_cast<float4*>(p.out + (size_t)v * p.out_pitch)[u] = P;
+    out_row<float4>(p, v)[u] = depth_vertex(K, scale * (float)in_row<Ti>(p, v)[u], u, v);
 }
 
-struct NrmParams {
-    const unsigned char* in;
-    size_t in_pitch;
-    unsigned char* out;
-    size_t out_pitch;
-    int w, h;
-};
-
 // KernNormalsFromVbo (cu_normals.cu:12-38)
-__global__ __launch_bounds__(256) void k_normals_from_vbo(const NrmParams p)
+__global__ __launch_bounds__(256) void k_normals_from_vbo(const PixOp p)
 {
-    const int u = blockIdx.x * 64 + (threadIdx.x & 63), v = blockIdx.y * 4 + (threadIdx.x >> 6);
+    int u, v;
+    pixel_xy(u, v);
     if (u >= p.w || v >= p.h) return;
     float4 N = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (u + 1 < p.w && v + 1 < p.h) {
-        const float4* r0 = reinterpret_cast<const float4*>(p.in + (size_t)v * p.in_pitch);
-        const float4* r1 = reinterpret_cast<const float4*>(p.in + (size_t)(v + 1) * p.in_pitch);
-        const float4 Vc = r0[u], Vr = r0[u + 1], Vu = r1[u];
-        const V3 a = v3(Vr.x - Vc.x, Vr.y - Vc.y, Vr.z - Vc.z);
-        const V3 b = v3(Vu.x - Vc.x, Vu.y - Vc.y, Vu.z - Vc.z);
-        const V3 axb = v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
-        const float mag = length(axb);
-        N = make_float4(-axb.x / mag, -axb.y / mag, -axb.z / mag, 1.0f);
-    }
-    reinterpret_cast<float4*>(p.out + (size_t)v * p.out_pitch)[u] = N;
+    if (u + 1 < p.w && v + 1 < p.h) N = vertex_normal(in_row<float4>(p, v)[u], in_row<float4>(p, v)[u + 1], in_row<float4>(p, v + 1)[u]);
+    out_row<float4>(p, v)[u] = N;
 }
 
 // DepthToVbo<float> and NormalsFromVbo in one launch (both are latency-sized at VGA: two 4-5 us launches become one).
-// A pixel's normal needs the vertices at (u+1, v) and (u, v+1); they are recomputed from the depth image with the
-// expression DepthToVbo uses, so both outputs carry exactly the bits the two separate operators write.
+// A pixel's normal needs the vertices at (u+1, v) and (u, v+1); they are recomputed from the depth image with depth_vertex,
+// as DepthToVbo does, so both outputs carry exactly the bits the two separate operators write.
 struct VboNrmParams {
     const unsigned char* in;
     size_t in_pitch;
@@ -327,113 +281,70 @@ struct VboNrmParams {
 };
 __device__ __forceinline__ float4 vertex_of(const VboNrmParams& p, int u, int v)
 {
-    const float kz = p.scale * reinterpret_cast<const float*>(p.in + (size_t)v * p.in_pitch)[u];
-    return make_float4(kz * ((float)u - p.K.u0) / p.K.fu, kz * ((float)v - p.K.v0) / p.K.fv, kz, 1.0f);
+    return depth_vertex(p.K, p.scale * reinterpret_cast<const float*>(p.in + (size_t)v * p.in_pitch)[u], u, v);
 }
 __global__ __launch_bounds__(256) void k_vbo_normals_f32(const VboNrmParams p)
 {
-    __shared__ float s_max[4][8];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int u = blockIdx.x * 64 + lane, v = blockIdx.y * 4 + wv;
+    __shared__ float s_max[PIX_H][8];
+    int u, v, lane, wv;
+    pixel_xy(u, v, lane, wv);
     float d = -__builtin_inff();
     if (u < p.w && v < p.h) {
         const float4 Vc = vertex_of(p, u, v);
         reinterpret_cast<float4*>(p.vbo + (size_t)v * p.vpitch)[u] = Vc;
         float4 N = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (u + 1 < p.w && v + 1 < p.h) {
-            const float4 Vr = vertex_of(p, u + 1, v), Vu = vertex_of(p, u, v + 1);
-            const V3 a = v3(Vr.x - Vc.x, Vr.y - Vc.y, Vr.z - Vc.z);
-            const V3 b = v3(Vu.x - Vc.x, Vu.y - Vc.y, Vu.z - Vc.z);
-            const V3 axb = v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
-            const float mag = length(axb);
-            N = make_float4(-axb.x / mag, -axb.y / mag, -axb.z / mag, 1.0f);
-        }
+        if (u + 1 < p.w && v + 1 < p.h) N = vertex_normal(Vc, vertex_of(p, u + 1, v), vertex_of(p, u, v + 1));
         reinterpret_cast<float4*>(p.nrm + (size_t)v * p.npitch)[u] = N;
-        if (p.tex) {   // (uniform) what k_pack_texels (fuse.hip) would write: the normal's xyz and the depth image's own value ...
+        if (p.tex) {   // (uniform) the texel image of this depth image and these normals: the two steps of fuse.hip's k_pack_texels
             d = reinterpret_cast<const float*>(p.in + (size_t)v * p.in_pitch)[u];
-            reinterpret_cast<float4*>(p.tex + (size_t)v * p.tpitch)[u] = make_float4(N.x, N.y, N.z, d);
+            texel_put(p.tex, p.tpitch, u, v, N, d);
         }
     }
-    if (p.tex) {   // ... and the maximum finite depth of each of the tile's eight 8 x 4 pixel blocks
-        d = wave8_combine(fmaxf(d, -__builtin_inff()), [](float a, float b) { return fmaxf(a, b); });
-        if ((lane & 7) == 0) s_max[wv][lane >> 3] = d;
-        __syncthreads();
-        if (threadIdx.x < 8)
-            p.bmax[(size_t)blockIdx.y * p.bw8 + blockIdx.x * 8 + threadIdx.x] =
-                fmaxf(fmaxf(s_max[0][threadIdx.x], s_max[1][threadIdx.x]), fmaxf(s_max[2][threadIdx.x], s_max[3][threadIdx.x]));
-    }
+    if (p.tex) texel_block_max(p.bmax, p.bw8, lane, wv, d, s_max);
 }
 
-struct EwParams {
-    const unsigned char* in;
-    size_t in_pitch;
-    unsigned char* out;
-    size_t out_pitch;
-    int w, h;
-    float s, offset;
-};
-
-// KernElementwiseScaleBias<float,float,float> (cu_operations.cu:39-49): b = s*a + offset
-__global__ __launch_bounds__(256) void k_scale_bias_f32(const EwParams p)
+// KernElementwiseScaleBias<float,Ti,float> (cu_operations.cu:39-49): b = s*a + offset; Ti = unsigned short: a sensor's 16-bit
+// readings, each exactly a float
+template <typename Ti>
+__global__ __launch_bounds__(256) void k_scale_bias(const PixOp p, const float s, const float offset)
 {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    int x, y;
+    pixel_xy(x, y);
     if (x >= p.w || y >= p.h) return;
-    const float v1 = reinterpret_cast<const float*>(p.in + (size_t)y * p.in_pitch)[x];
-    reinterpret_cast<float*>(p.out + (size_t)y * p.out_pitch)[x] = scale_bias(v1, p.s, p.offset);
-}
-// KernElementwiseScaleBias<float,unsigned short,float>: a sensor's 16-bit readings, each exactly a float
-__global__ __launch_bounds__(256) void k_scale_bias_u16(const EwParams p)
-{
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= p.w || y >= p.h) return;
-    const float v1 = (float)reinterpret_cast<const unsigned short*>(p.in + (size_t)y * p.in_pitch)[x];
-    reinterpret_cast<float*>(p.out + (size_t)y * p.out_pitch)[x] = scale_bias(v1, p.s, p.offset);
+    out_row<float>(p, y)[x] = scale_bias((float)in_row<Ti>(p, y)[x], s, offset);
 }
 
-// KernBoxHalfIgnoreInvalid<float,float,float> (cu_resample.cu:89-111): mean of the finite samples of
-// each 2x2 block, NaN if none; samples are added in the order tl, tr, bl, br
-__global__ __launch_bounds__(256) void k_box_half_ignore_invalid_f32(const EwParams p)
+// KernBoxHalfIgnoreInvalid<float,float,float> (cu_resample.cu:89-111): box_half of each 2x2 block
+__global__ __launch_bounds__(256) void k_box_half_ignore_invalid_f32(const PixOp p)
 {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    int x, y;
+    pixel_xy(x, y);
     if (x >= p.w || y >= p.h) return;
-    const float2 t = *reinterpret_cast<const float2*>(p.in + (size_t)(2 * y) * p.in_pitch + (size_t)(2 * x) * 4);
-    const float2 b = *reinterpret_cast<const float2*>(p.in + (size_t)(2 * y + 1) * p.in_pitch + (size_t)(2 * x) * 4);
-    int n = 0;
-    float sum = 0;
-    if (isfinite(t.x)) { sum += t.x; n++; }
-    if (isfinite(t.y)) { sum += t.y; n++; }
-    if (isfinite(b.x)) { sum += b.x; n++; }
-    if (isfinite(b.y)) { sum += b.y; n++; }
-    reinterpret_cast<float*>(p.out + (size_t)y * p.out_pitch)[x] = n > 0 ? (sum / n) : __builtin_nanf("");
+    const float2 t = *reinterpret_cast<const float2*>(in_row<float>(p, 2 * y) + 2 * x);
+    const float2 b = *reinterpret_cast<const float2*>(in_row<float>(p, 2 * y + 1) + 2 * x);
+    out_row<float>(p, y)[x] = box_half(t.x, t.y, b.x, b.y);
 }
-
 
 // ---- the small per-pixel tools of cu_depth_tools.h ------------------------------------------------------------
-struct PixIO {
-    const unsigned char* in;
-    size_t ipitch;
-    unsigned char* out;
-    size_t opitch;
-    int w, h;
-};
-
 // Disp2Depth (cu_depth_tools.cu:15-23): depth = fu * baseline / disparity, NaN below the minimum disparity
-__global__ __launch_bounds__(256) void k_disp2depth(const PixIO p, float fu, float baseline, float min_disp)
+__global__ __launch_bounds__(256) void k_disp2depth(const PixOp p, float fu, float baseline, float min_disp)
 {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    int x, y;
+    pixel_xy(x, y);
     if (x >= p.w || y >= p.h) return;
-    const float d = *(reinterpret_cast<const float*>(p.in + (size_t)y * p.ipitch) + x);
-    *(reinterpret_cast<float*>(p.out + (size_t)y * p.opitch) + x) = d >= min_disp ? fu * baseline / d : __builtin_nanf("");
+    const float d = in_row<float>(p, y)[x];
+    out_row<float>(p, y)[x] = d >= min_disp ? fu * baseline / d : __builtin_nanf("");
 }
 
 // FilterBadKinectData (cu_depth_tools.cu:32-39): millimetre readings below 200 become NaN
 template <typename Ti>
-__global__ __launch_bounds__(256) void k_filter_bad_kinect(const PixIO p)
+__global__ __launch_bounds__(256) void k_filter_bad_kinect(const PixOp p)
 {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    int x, y;
+    pixel_xy(x, y);
     if (x >= p.w || y >= p.h) return;
-    const float z_mm = (float)*(reinterpret_cast<const Ti*>(p.in + (size_t)y * p.ipitch) + x);
-    *(reinterpret_cast<float*>(p.out + (size_t)y * p.opitch) + x) = z_mm >= 200 ? z_mm : __builtin_nanf("");
+    const float z_mm = (float)in_row<Ti>(p, y)[x];
+    out_row<float>(p, y)[x] = z_mm >= 200 ? z_mm : __builtin_nanf("");
 }
 
 struct ColourVboParams {
@@ -447,13 +358,12 @@ struct ColourVboParams {
     int w, h;
     Pose KT;                    // KT_cd
 };
-struct __attribute__((packed)) Rgb3 { unsigned char x, y, z; };
 
-// ColourVbo (cu_depth_tools.cu:86-112): project every vertex with KT_cd, bilinear RGB (sampling.h lerp(uchar3...):
-// integer difference, converted, times t, plus the first value; rows blended as float3), truncated to bytes
+// ColourVbo (cu_depth_tools.cu:86-112): project every vertex with KT_cd, bilinear RGB (rgb_bilinear), truncated to bytes
 __global__ __launch_bounds__(256) void k_colour_vbo(const ColourVboParams p)
 {
-    const int u = blockIdx.x * 64 + (threadIdx.x & 63), v = blockIdx.y * 4 + (threadIdx.x >> 6);
+    int u, v;
+    pixel_xy(u, v);
     if (u >= p.w || v >= p.h) return;
     const float4 Pd = *(reinterpret_cast<const float4*>(p.vbo + (size_t)v * p.vpitch) + u);
     // Mat<3,4> * Mat<4,1> with w = 1: row . (x, y, z, 1), summed left to right (Mat.h operator*)
@@ -463,16 +373,7 @@ __global__ __launch_bounds__(256) void k_colour_vbo(const ColourVboParams p)
     const float pu = k0 / k2, pv = k1 / k2;
     uchar4 id = make_uchar4(0, 0, 0, 0);
     if (1.0f <= pu && pu < ((float)p.rw - 1.0f) && 1.0f <= pv && pv < ((float)p.rh - 1.0f)) {
-        const float ix = floorf(pu), iy = floorf(pv);
-        const float fx = pu - ix, fy = pv - iy;
-        const Rgb3* bl = reinterpret_cast<const Rgb3*>(p.rgb + (size_t)iy * p.rpitch) + (size_t)ix;
-        const Rgb3* tl = reinterpret_cast<const Rgb3*>(p.rgb + (size_t)(iy + 1) * p.rpitch) + (size_t)ix;
-        const Rgb3 b0 = bl[0], b1 = bl[1], t0 = tl[0], t1 = tl[1];
-        const V3 lo = v3((float)b0.x + fx * (float)((int)b1.x - (int)b0.x), (float)b0.y + fx * (float)((int)b1.y - (int)b0.y),
-                         (float)b0.z + fx * (float)((int)b1.z - (int)b0.z));
-        const V3 hi = v3((float)t0.x + fx * (float)((int)t1.x - (int)t0.x), (float)t0.y + fx * (float)((int)t1.y - (int)t0.y),
-                         (float)t0.z + fx * (float)((int)t1.z - (int)t0.z));
-        const V3 c = v3(lo.x + fy * (hi.x - lo.x), lo.y + fy * (hi.y - lo.y), lo.z + fy * (hi.z - lo.z));
+        const V3 c = rgb_bilinear(p.rgb, p.rpitch, pu, pv);
         id = make_uchar4((unsigned char)c.x, (unsigned char)c.y, (unsigned char)c.z, 255);
     }
     *(reinterpret_cast<uchar4*>(p.out + (size_t)v * p.opitch) + u) = id;
@@ -497,28 +398,16 @@ struct TextureParams {
     Intr Kd;
     KeyframeView kf[TEX_MAX_KF];
 };
-// Image<uchar3>::GetBilinear<float3> (see k_colour_vbo)
-__device__ __forceinline__ V3 rgb_bilinear(const KeyframeView& k, float pu, float pv)
-{
-    const float ix = floorf(pu), iy = floorf(pv);
-    const float fx = pu - ix, fy = pv - iy;
-    const Rgb3* bl = reinterpret_cast<const Rgb3*>(k.img + (size_t)iy * k.pitch) + (size_t)ix;
-    const Rgb3* tl = reinterpret_cast<const Rgb3*>(k.img + (size_t)(iy + 1) * k.pitch) + (size_t)ix;
-    const Rgb3 b0 = bl[0], b1 = bl[1], t0 = tl[0], t1 = tl[1];
-    const V3 lo = v3((float)b0.x + fx * (float)((int)b1.x - (int)b0.x), (float)b0.y + fx * (float)((int)b1.y - (int)b0.y),
-                     (float)b0.z + fx * (float)((int)b1.z - (int)b0.z));
-    const V3 hi = v3((float)t0.x + fx * (float)((int)t1.x - (int)t0.x), (float)t0.y + fx * (float)((int)t1.y - (int)t0.y),
-                     (float)t0.z + fx * (float)((int)t1.z - (int)t0.z));
-    return v3(lo.x + fy * (hi.x - lo.x), lo.y + fy * (hi.y - lo.y), lo.z + fy * (hi.z - lo.z));
-}
 __global__ __launch_bounds__(256) void k_texture_depth(const TextureParams p)
 {
-    const int u = blockIdx.x * 64 + (threadIdx.x & 63), v = blockIdx.y * 4 + (threadIdx.x >> 6);
+    int u, v;
+    pixel_xy(u, v);
     if (u >= p.w || v >= p.h) return;
     const float d = reinterpret_cast<const float*>(p.depth + (size_t)v * p.dpitch)[u];
     const float4 N_d = reinterpret_cast<const float4*>(p.norm + (size_t)v * p.npitch)[u];
     const V3 N_w = so3_mul(p.T_wd, v3(N_d.x, N_d.y, N_d.z));
-    const V3 P_d = v3(d * ((float)u - p.Kd.u0) / p.Kd.fu, d * ((float)v - p.Kd.v0) / p.Kd.fv, d);   // Unproject(u, v, z)
+    const float4 V_d = depth_vertex(p.Kd, d, u, v);   // Unproject(u, v, z)
+    const V3 P_d = v3(V_d.x, V_d.y, V_d.z);
     const V3 P_w = se3_mul(p.T_wd, P_d);
     float4 out;
     if (p.single) { // one keyframe: nearest-facing test on the camera-frame normal's z (cu_depth_tools.cu:123-149)
@@ -528,7 +417,7 @@ __global__ __launch_bounds__(256) void k_texture_depth(const TextureParams p)
         const V3 N_c = so3_mul(k.T_iw, N_w);
         const float facing = N_c.x * 0.f + N_c.y * 0.f + N_c.z * 1.f;
         if (2.0f <= pu && pu < ((float)k.w - 2.0f) && 2.0f <= pv && pv < ((float)k.h - 2.0f) && (double)facing < -0.2) { // the literal is a double
-            const V3 c = rgb_bilinear(k, pu, pv) * (1.0f / 255.0f);
+            const V3 c = rgb_bilinear(k.img, k.pitch, pu, pv) * (1.0f / 255.0f);
             out = make_float4(c.x, c.y, c.z, 1.f);
         } else {
             out = make_float4(0.f, 0.f, 0.f, 1.f);
@@ -543,7 +432,7 @@ __global__ __launch_bounds__(256) void k_texture_depth(const TextureParams p)
             const V3 N_c = so3_mul(k.T_iw, N_w);
             const float ndot = dot(N_c, P_kf) / -length(P_kf);
             if (2.0f <= pu && pu < ((float)k.w - 2.0f) && 2.0f <= pv && pv < ((float)k.h - 2.0f) && (double)ndot > 0.1 && P_kf.z > 0.f) {
-                color = color + rgb_bilinear(k, pu, pv) * (ndot / 255.0f);
+                color = color + rgb_bilinear(k.img, k.pitch, pu, pv) * (ndot / 255.0f);
                 w += ndot;
             }
         }
@@ -562,6 +451,51 @@ __global__ __launch_bounds__(256) void k_texture_depth(const TextureParams p)
 
 using namespace kfx;
 
+// the parameter block of every bilateral kernel (the guided one's head included): the launch is out's, clamping is by in's extent
+static BilParams bil_params(const kfx_image* out, const kfx_image* in, float gs, float gr, unsigned size, float minval, int use_minval)
+{
+    return BilParams{(const unsigned char*)in->ptr, in->pitch, (unsigned char*)out->ptr, out->pitch, (int)out->w, (int)out->h,
+                     (int)in->w, (int)in->h, (int)size, gs, gr, minval, use_minval};
+}
+
+// tile shape of the LDS kernel (config C3 sweep, scripts/config_sweep.py): KFX_BILATERAL_TILE = 0..5, read once per process
+static int bilateral_tile_shape()
+{
+    static const int shape = env_int("KFX_BILATERAL_TILE", 2);
+    return shape;
+}
+template <typename Ti, int TX, int TY, int PY, typename Conv>
+static void bilateral_tile_launch(const BilParams& p, const Conv& conv, hipStream_t s)
+{
+    const int D = 2 * p.R + 1;
+    const size_t lds = (size_t)((TX + 2 * p.R) * (TY * PY + 2 * p.R) + D * D) * sizeof(float);
+    hipLaunchKernelGGL((k_bilateral<Ti, TX, TY, PY, Conv>), dim3(ceil_div(p.w, TX), ceil_div(p.h, TY * PY)), dim3(TX * TY), lds, s, p, conv);
+}
+
+// The one choice of kernel, grid and LDS size behind BilateralFilter (Conv = AsLoaded) and BilateralFilterDepth (Conv = ToMetres):
+// the fast kernel in fast numerics up to a 7 x 7 window, the LDS tile up to BIL_MAX_R, global gathers beyond
+template <typename Ti, typename Conv>
+static void bilateral_dispatch(const BilParams& p, const Conv& conv, hipStream_t s)
+{
+    if (math_mode() == KFX_MATH_FAST && p.R >= 1 && p.R <= 3) {
+        dim3 grid(ceil_div(p.w, 16), ceil_div(p.h, 16));
+        if (p.R == 3) hipLaunchKernelGGL((k_bilateral_fast<Ti, 3, Conv>), grid, dim3(256), 0, s, p, conv);
+        else if (p.R == 2) hipLaunchKernelGGL((k_bilateral_fast<Ti, 2, Conv>), grid, dim3(256), 0, s, p, conv);
+        else hipLaunchKernelGGL((k_bilateral_fast<Ti, 1, Conv>), grid, dim3(256), 0, s, p, conv);
+    } else if (p.R <= BIL_MAX_R) {
+        switch (bilateral_tile_shape()) {
+        case 0: bilateral_tile_launch<Ti, 32, 8, 1>(p, conv, s); break;
+        case 1: bilateral_tile_launch<Ti, 64, 4, 1>(p, conv, s); break;
+        case 3: bilateral_tile_launch<Ti, 32, 8, 2>(p, conv, s); break;
+        case 4: bilateral_tile_launch<Ti, 32, 8, 4>(p, conv, s); break;
+        case 5: bilateral_tile_launch<Ti, 64, 4, 4>(p, conv, s); break;
+        default: bilateral_tile_launch<Ti, 16, 16, 1>(p, conv, s); break; // best of the sweep at 1280x960 (profiles/r01_config_sweep.txt)
+        }
+    } else {
+        hipLaunchKernelGGL((k_bilateral_global<Ti, Conv>), pixel_grid(p.w, p.h), dim3(256), 0, s, p, conv);
+    }
+}
+
 template <typename Ti>
 static int bilateral_launch(const kfx_image* out, const kfx_image* in, float gs, float gr, unsigned size,
                             float minval, int use_minval, kfx_stream stream)
@@ -570,53 +504,12 @@ static int bilateral_launch(const kfx_image* out, const kfx_image* in, float gs,
     if (int e = check_image(in, sizeof(Ti), cover_w(out), cover_h(out), "BilateralFilter: input image")) return e;
     if (out->w == 0 || out->h == 0) return 0;
     if (size > 1024) return set_error(KFX_E_RANGE, "BilateralFilter: window radius");
-    BilParams p;
-    p.in = (const unsigned char*)in->ptr;
-    p.in_pitch = in->pitch;
-    p.out = (unsigned char*)out->ptr;
-    p.out_pitch = out->pitch;
-    p.w = (int)out->w;
-    p.h = (int)out->h;
-    p.iw = (int)in->w;
-    p.ih = (int)in->h;
-    p.R = (int)size;
-    p.gs = gs;
-    p.gr = gr;
-    p.minval = minval;
-    p.use_minval = use_minval;
-    hipStream_t s = (hipStream_t)stream;
-    if (math_mode() == KFX_MATH_FAST && p.R >= 1 && p.R <= 3) {
-        dim3 grid(ceil_div(p.w, 16), ceil_div(p.h, 16));
-        if (p.R == 3) hipLaunchKernelGGL((k_bilateral_fast<Ti, 3>), grid, dim3(256), 0, s, p);
-        else if (p.R == 2) hipLaunchKernelGGL((k_bilateral_fast<Ti, 2>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((k_bilateral_fast<Ti, 1>), grid, dim3(256), 0, s, p);
-    } else if (p.R <= BIL_MAX_R) {
-        const int D = 2 * p.R + 1;
-        // tile shape (config C3 sweep, scripts/config_sweep.py): KFX_BILATERAL_TILE = 0..5
-        static const int shape = env_int("KFX_BILATERAL_TILE", 2);
-#define KFX_BIL(TX_, TY_, PY_)                                                                                   \
-    do {                                                                                                        \
-        const size_t lds = (size_t)((TX_ + 2 * p.R) * (TY_ * PY_ + 2 * p.R) + D * D) * sizeof(float);           \
-        dim3 grid(ceil_div(p.w, TX_), ceil_div(p.h, TY_ * PY_));                                                \
-        hipLaunchKernelGGL((k_bilateral<Ti, TX_, TY_, PY_>), grid, dim3(TX_ * TY_), lds, s, p);                 \
-    } while (0)
-        switch (shape) {
-        case 0: KFX_BIL(32, 8, 1); break;
-        case 1: KFX_BIL(64, 4, 1); break;
-        case 3: KFX_BIL(32, 8, 2); break;
-        case 4: KFX_BIL(32, 8, 4); break;
-        case 5: KFX_BIL(64, 4, 4); break;
-        default: KFX_BIL(16, 16, 1); break; // best of the sweep at 1280x960 (profiles/r01_config_sweep.txt)
-        }
-#undef KFX_BIL
-    } else {
-        hipLaunchKernelGGL(k_bilateral_global<Ti>, pixel_grid(p.w, p.h), dim3(256), 0, s, p);
-    }
+    bilateral_dispatch<Ti>(bil_params(out, in, gs, gr, size, minval, use_minval), AsLoaded{}, (hipStream_t)stream);
     return check_launch("kfx_bilateral");
 }
 
-// BilateralFilter of a sensor image (include/kfx_sensor.h): bilateral_launch's choice of kernel and grid, the k_bilateral_depth*
-// instantiation of each.  launch = false: the argument checks alone (the upload ring consumes an image only once they pass).
+// BilateralFilter of a sensor image (include/kfx_sensor.h): bilateral_dispatch with the ToMetres conversion.
+// launch = false: the argument checks alone (the upload ring consumes an image only once they pass).
 template <typename Ti>
 static int bilateral_depth_launch(const kfx_image* out, const kfx_image* metres, const kfx_image* in, float s, float offset, float gs, float gr,
                                   unsigned size, float minval, bool launch, kfx_stream stream)
@@ -627,49 +520,8 @@ static int bilateral_depth_launch(const kfx_image* out, const kfx_image* metres,
     if (out->w == 0 || out->h == 0) return 0;
     if (size > 1024) return set_error(KFX_E_RANGE, "BilateralFilterDepth: window radius");
     if (!launch) return 0;
-    BilDepthParams q;
-    BilParams& p = q.b;
-    p.in = (const unsigned char*)in->ptr;
-    p.in_pitch = in->pitch;
-    p.out = (unsigned char*)out->ptr;
-    p.out_pitch = out->pitch;
-    p.w = (int)out->w;
-    p.h = (int)out->h;
-    p.iw = (int)in->w;
-    p.ih = (int)in->h;
-    p.R = (int)size;
-    p.gs = gs;
-    p.gr = gr;
-    p.minval = minval;
-    p.use_minval = 1;
-    q.c = ToMetres{metres ? (unsigned char*)metres->ptr : nullptr, metres ? metres->pitch : 0, s, offset};
-    hipStream_t st = (hipStream_t)stream;
-    if (math_mode() == KFX_MATH_FAST && p.R >= 1 && p.R <= 3) {
-        dim3 grid(ceil_div(p.w, 16), ceil_div(p.h, 16));
-        if (p.R == 3) hipLaunchKernelGGL((k_bilateral_depth_fast<Ti, 3>), grid, dim3(256), 0, st, q);
-        else if (p.R == 2) hipLaunchKernelGGL((k_bilateral_depth_fast<Ti, 2>), grid, dim3(256), 0, st, q);
-        else hipLaunchKernelGGL((k_bilateral_depth_fast<Ti, 1>), grid, dim3(256), 0, st, q);
-    } else if (p.R <= BIL_MAX_R) {
-        const int D = 2 * p.R + 1;
-        static const int shape = env_int("KFX_BILATERAL_TILE", 2);   // (bilateral_launch's knob and shapes)
-#define KFX_BIL(TX_, TY_, PY_)                                                                                   \
-    do {                                                                                                        \
-        const size_t lds = (size_t)((TX_ + 2 * p.R) * (TY_ * PY_ + 2 * p.R) + D * D) * sizeof(float);           \
-        dim3 grid(ceil_div(p.w, TX_), ceil_div(p.h, TY_ * PY_));                                                \
-        hipLaunchKernelGGL((k_bilateral_depth<Ti, TX_, TY_, PY_>), grid, dim3(TX_ * TY_), lds, st, q);          \
-    } while (0)
-        switch (shape) {
-        case 0: KFX_BIL(32, 8, 1); break;
-        case 1: KFX_BIL(64, 4, 1); break;
-        case 3: KFX_BIL(32, 8, 2); break;
-        case 4: KFX_BIL(32, 8, 4); break;
-        case 5: KFX_BIL(64, 4, 4); break;
-        default: KFX_BIL(16, 16, 1); break;
-        }
-#undef KFX_BIL
-    } else {
-        hipLaunchKernelGGL(k_bilateral_depth_global<Ti>, pixel_grid(p.w, p.h), dim3(256), 0, st, q);
-    }
+    const ToMetres conv{metres ? (unsigned char*)metres->ptr : nullptr, metres ? metres->pitch : 0, s, offset};
+    bilateral_dispatch<Ti>(bil_params(out, in, gs, gr, size, minval, 1), conv, (hipStream_t)stream);
     return check_launch("kfx_bilateral_depth");
 }
 
@@ -704,16 +556,27 @@ extern "C" int kfx_bilateral_u8(const kfx_image* out, const kfx_image* in, float
     return bilateral_launch<unsigned char>(out, in, gs, gr, size, 0.f, 0, stream);
 }
 
+// The preamble of the per-pixel "out <- in" entry points: out usable (out_elem-byte pixels), in usable (in_elem-byte pixels) and
+// covering scale_x x scale_y times the launch; then `p` is the launch's block, and empty(p) says that there is nothing to launch --
+// which the entry point answers with 0 after the checks of its other arguments.
+static int pix_op(PixOp& p, const kfx_image* out, size_t out_elem, const kfx_image* in, size_t in_elem, size_t scale_x, size_t scale_y,
+                  const char* what_out, const char* what_in)
+{
+    if (int e = check_image(out, out_elem, 0, 0, what_out)) return e;
+    if (int e = check_image(in, in_elem, scale_x * cover_w(out), scale_y * cover_h(out), what_in)) return e;
+    p = PixOp{(const unsigned char*)in->ptr, in->pitch, (unsigned char*)out->ptr, out->pitch, (int)out->w, (int)out->h};
+    return 0;
+}
+static bool empty(const PixOp& p) { return p.w == 0 || p.h == 0; }
+
 template <typename Ti>
 static int vbo_launch(const kfx_image* vbo, const kfx_image* depth, const float K[4], float scale, kfx_stream stream)
 {
-    if (int e = check_image(vbo, 16, 0, 0, "DepthToVbo: vbo image")) return e;
-    if (int e = check_image(depth, sizeof(Ti), cover_w(vbo), cover_h(vbo), "DepthToVbo: depth image")) return e;
+    PixOp p;
+    if (int e = pix_op(p, vbo, 16, depth, sizeof(Ti), 1, 1, "DepthToVbo: vbo image", "DepthToVbo: depth image")) return e;
     if (!K) return set_error(KFX_E_NULL, "DepthToVbo: null intrinsics");
-    if (vbo->w == 0 || vbo->h == 0) return 0;
-    VboParams p{(const unsigned char*)depth->ptr, depth->pitch, (unsigned char*)vbo->ptr, vbo->pitch,
-                (int)vbo->w, (int)vbo->h, Intr{K[0], K[1], K[2], K[3]}, scale};
-    hipLaunchKernelGGL(k_depth_to_vbo<Ti>, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
+    if (empty(p)) return 0;
+    hipLaunchKernelGGL(k_depth_to_vbo<Ti>, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p, Intr{K[0], K[1], K[2], K[3]}, scale);
     return check_launch("kfx_depth_to_vbo");
 }
 
@@ -730,42 +593,38 @@ extern "C" int kfx_depth_to_vbo_u16(const kfx_image* vbo, const kfx_image* depth
 
 extern "C" int kfx_normals_from_vbo(const kfx_image* nrm, const kfx_image* vbo, kfx_stream stream)
 {
-    if (int e = check_image(nrm, 16, 0, 0, "NormalsFromVbo: normal image")) return e;
-    if (int e = check_image(vbo, 16, cover_w(nrm), cover_h(nrm), "NormalsFromVbo: vbo image")) return e;
-    if (nrm->w == 0 || nrm->h == 0) return 0;
-    NrmParams p{(const unsigned char*)vbo->ptr, vbo->pitch, (unsigned char*)nrm->ptr, nrm->pitch, (int)nrm->w, (int)nrm->h};
+    PixOp p;
+    if (int e = pix_op(p, nrm, 16, vbo, 16, 1, 1, "NormalsFromVbo: normal image", "NormalsFromVbo: vbo image")) return e;
+    if (empty(p)) return 0;
     hipLaunchKernelGGL(k_normals_from_vbo, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("kfx_normals_from_vbo");
 }
 
+// ElementwiseScaleBias<float, Ti, float> (cu_operations.cu:39-57), float and unsigned short input
+template <typename Ti>
+static int scale_bias_launch(const kfx_image* out, const kfx_image* in, float s, float offset, const char* name, kfx_stream stream)
+{
+    PixOp p;
+    if (int e = pix_op(p, out, 4, in, sizeof(Ti), 1, 1, "ElementwiseScaleBias: output image", "ElementwiseScaleBias: input image")) return e;
+    if (empty(p)) return 0;
+    hipLaunchKernelGGL(k_scale_bias<Ti>, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p, s, offset);
+    return check_launch(name);
+}
 extern "C" int kfx_elementwise_scale_bias_f32(const kfx_image* out, const kfx_image* in, float s, float offset, kfx_stream stream)
 {
-    if (int e = check_image(out, 4, 0, 0, "ElementwiseScaleBias: output image")) return e;
-    if (int e = check_image(in, 4, cover_w(out), cover_h(out), "ElementwiseScaleBias: input image")) return e;
-    if (out->w == 0 || out->h == 0) return 0;
-    EwParams p{(const unsigned char*)in->ptr, in->pitch, (unsigned char*)out->ptr, out->pitch, (int)out->w, (int)out->h, s, offset};
-    hipLaunchKernelGGL(k_scale_bias_f32, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
-    return check_launch("kfx_elementwise_scale_bias_f32");
+    return scale_bias_launch<float>(out, in, s, offset, "kfx_elementwise_scale_bias_f32", stream);
 }
-
-// ElementwiseScaleBias<float, unsigned short, float> (cu_operations.cu:39-57)
 extern "C" int kfx_elementwise_scale_bias_u16(const kfx_image* out, const kfx_image* in, float s, float offset, kfx_stream stream)
 {
-    if (int e = check_image(out, 4, 0, 0, "ElementwiseScaleBias: output image")) return e;
-    if (int e = check_image(in, 2, cover_w(out), cover_h(out), "ElementwiseScaleBias: input image")) return e;
-    if (out->w == 0 || out->h == 0) return 0;
-    EwParams p{(const unsigned char*)in->ptr, in->pitch, (unsigned char*)out->ptr, out->pitch, (int)out->w, (int)out->h, s, offset};
-    hipLaunchKernelGGL(k_scale_bias_u16, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
-    return check_launch("kfx_elementwise_scale_bias_u16");
+    return scale_bias_launch<unsigned short>(out, in, s, offset, "kfx_elementwise_scale_bias_u16", stream);
 }
 
 extern "C" int kfx_box_half_ignore_invalid_f32(const kfx_image* out, const kfx_image* in, kfx_stream stream)
 {
-    if (int e = check_image(out, 4, 0, 0, "BoxHalfIgnoreInvalid: output image")) return e;
-    if (int e = check_image(in, 4, 2 * cover_w(out), 2 * cover_h(out), "BoxHalfIgnoreInvalid: input image (2x the output)")) return e;
-    if (out->w == 0 || out->h == 0) return 0;
+    PixOp p;
+    if (int e = pix_op(p, out, 4, in, 4, 2, 2, "BoxHalfIgnoreInvalid: output image", "BoxHalfIgnoreInvalid: input image (2x the output)")) return e;
+    if (empty(p)) return 0;
     if (((uintptr_t)in->ptr | in->pitch) & 7) return set_error(KFX_E_ALIGN, "BoxHalfIgnoreInvalid: input not 8-byte aligned");
-    EwParams p{(const unsigned char*)in->ptr, in->pitch, (unsigned char*)out->ptr, out->pitch, (int)out->w, (int)out->h, 0.f, 0.f};
     hipLaunchKernelGGL(k_box_half_ignore_invalid_f32, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("kfx_box_half_ignore_invalid_f32");
 }
@@ -773,32 +632,30 @@ extern "C" int kfx_box_half_ignore_invalid_f32(const kfx_image* out, const kfx_i
 // Disp2Depth(dIn, dOut, fu, fBaseline, fMinDisp) (cu_depth_tools.cu:15-30; the launch is bounded by dOut)
 extern "C" int kfx_disp2depth(const kfx_image* in, const kfx_image* out, float fu, float baseline, float min_disp, kfx_stream stream)
 {
-    if (int e = check_image(out, 4, 0, 0, "Disp2Depth: output image")) return e;
-    if (int e = check_image(in, 4, cover_w(out), cover_h(out), "Disp2Depth: input image")) return e;
-    if (out->w == 0 || out->h == 0) return 0;
-    PixIO p{(const unsigned char*)in->ptr, in->pitch, (unsigned char*)out->ptr, out->pitch, (int)out->w, (int)out->h};
+    PixOp p;
+    if (int e = pix_op(p, out, 4, in, 4, 1, 1, "Disp2Depth: output image", "Disp2Depth: input image")) return e;
+    if (empty(p)) return 0;
     hipLaunchKernelGGL(k_disp2depth, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p, fu, baseline, min_disp);
     return check_launch("kfx_disp2depth");
 }
 
 // FilterBadKinectData(dFiltered, dKinectDepth) (cu_depth_tools.cu:32-53), float and unsigned short readings
+template <typename Ti>
+static int filter_bad_kinect_launch(const kfx_image* out, const kfx_image* in, const char* name, kfx_stream stream)
+{
+    PixOp p;
+    if (int e = pix_op(p, out, 4, in, sizeof(Ti), 1, 1, "FilterBadKinectData: output image", "FilterBadKinectData: input image")) return e;
+    if (empty(p)) return 0;
+    hipLaunchKernelGGL(k_filter_bad_kinect<Ti>, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
+    return check_launch(name);
+}
 extern "C" int kfx_filter_bad_kinect_f32(const kfx_image* out, const kfx_image* in, kfx_stream stream)
 {
-    if (int e = check_image(out, 4, 0, 0, "FilterBadKinectData: output image")) return e;
-    if (int e = check_image(in, 4, cover_w(out), cover_h(out), "FilterBadKinectData: input image")) return e;
-    if (out->w == 0 || out->h == 0) return 0;
-    PixIO p{(const unsigned char*)in->ptr, in->pitch, (unsigned char*)out->ptr, out->pitch, (int)out->w, (int)out->h};
-    hipLaunchKernelGGL(k_filter_bad_kinect<float>, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
-    return check_launch("kfx_filter_bad_kinect_f32");
+    return filter_bad_kinect_launch<float>(out, in, "kfx_filter_bad_kinect_f32", stream);
 }
 extern "C" int kfx_filter_bad_kinect_u16(const kfx_image* out, const kfx_image* in, kfx_stream stream)
 {
-    if (int e = check_image(out, 4, 0, 0, "FilterBadKinectData: output image")) return e;
-    if (int e = check_image(in, 2, cover_w(out), cover_h(out), "FilterBadKinectData: input image")) return e;
-    if (out->w == 0 || out->h == 0) return 0;
-    PixIO p{(const unsigned char*)in->ptr, in->pitch, (unsigned char*)out->ptr, out->pitch, (int)out->w, (int)out->h};
-    hipLaunchKernelGGL(k_filter_bad_kinect<unsigned short>, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
-    return check_launch("kfx_filter_bad_kinect_u16");
+    return filter_bad_kinect_launch<unsigned short>(out, in, "kfx_filter_bad_kinect_u16", stream);
 }
 
 // ColourVbo(dId, dPd, dIc, KT_cd) (cu_depth_tools.cu:86-119)
@@ -829,8 +686,7 @@ static int guided_launch(const kfx_image* out, const kfx_image* in, const kfx_im
     if (out->w == 0 || out->h == 0) return 0;
     if (size > 64) return set_error(KFX_E_RANGE, "BilateralFilter(guided): window too large");
     GuidedParams g;
-    g.b = BilParams{(const unsigned char*)in->ptr, in->pitch, (unsigned char*)out->ptr, out->pitch, (int)out->w, (int)out->h,
-                    (int)in->w, (int)in->h, (int)size, gs, gr, 0.f, 0};
+    g.b = bil_params(out, in, gs, gr, size, 0.f, 0);
     g.guide = (const unsigned char*)guide->ptr;
     g.gpitch = guide->pitch;
     g.gw = (int)guide->w;
@@ -871,14 +727,13 @@ int kfx::depth_to_vbo_normals_texels(const kfx_image* vbo, const kfx_image* nrm,
     if (!K) return set_error(KFX_E_NULL, "DepthToVbo+Normals: null intrinsics");
     if (vbo->w == 0 || vbo->h == 0) return 0;
     if (nrm->w != vbo->w || nrm->h != vbo->h) return set_error(KFX_E_SHAPE, "DepthToVbo+Normals: vbo and normals differ in size");
-    // texels: a buffer of kfx::texel_image_bytes(w, h) bytes in the layout of fuse.hip's tex_layout -- rows of `pitch` = w * 16 rounded up
-    // to 256 bytes, the block maxima behind them in rows of ceil(w / 64) * 8 floats
-    const size_t tpitch = (vbo->w * 16 + 255) / 256 * 256;
-    if (texels && (!texels->ptr || texels->w != vbo->w || texels->h != vbo->h || texels->pitch != tpitch || ((uintptr_t)texels->ptr & 15)))
+    // texels: a buffer of tex_layout(w, h).bytes bytes in that layout (host_args.h), its pitch the layout's
+    const TexLayout tl = tex_layout(vbo->w, vbo->h);
+    if (texels && (!texels->ptr || texels->w != vbo->w || texels->h != vbo->h || texels->pitch != tl.tpitch || ((uintptr_t)texels->ptr & 15)))
         return set_error(KFX_E_SHAPE, "DepthToVbo+Normals: texel image");
     VboNrmParams p{(const unsigned char*)depth->ptr, depth->pitch, (unsigned char*)vbo->ptr, (unsigned char*)nrm->ptr, vbo->pitch, nrm->pitch,
-                   (int)vbo->w, (int)vbo->h, Intr{K[0], K[1], K[2], K[3]}, scale, texels ? (unsigned char*)texels->ptr : nullptr, texels ? tpitch : 0,
-                   texels ? reinterpret_cast<float*>((unsigned char*)texels->ptr + tpitch * vbo->h) : nullptr, (unsigned)((vbo->w + 63) / 64 * 8)};
+                   (int)vbo->w, (int)vbo->h, Intr{K[0], K[1], K[2], K[3]}, scale, texels ? (unsigned char*)texels->ptr : nullptr, texels ? tl.tpitch : 0,
+                   texels ? reinterpret_cast<float*>((unsigned char*)texels->ptr + tl.bmax_off) : nullptr, tl.bw8};
     hipLaunchKernelGGL(k_vbo_normals_f32, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("kfx_depth_to_vbo_normals_f32");
 }
@@ -887,10 +742,10 @@ int kfx::depth_to_vbo_normals_texels(const kfx_image* vbo, const kfx_image* nrm,
 // BoxReduceIgnoreInvalid (levels 1 .. L-1 from level 0) followed by DepthToVbo + NormalsFromVbo on every level are 2 L - 1
 // launches of 3-5 us each (seven per frame of the tracked loop, profiles/r05_tracked: latency, not work).  Here a workgroup owns
 // a 32 x 32 tile of level 0 and the 16 x 16 / 8 x 8 / 4 x 4 tiles below it: it stages the tile with an apron of 8 pixels to the
-// right and below in LDS, halves it level by level there (k_box_half_ignore_invalid_f32's expression, same order of additions)
-// -- the apron is what the next level's one-pixel apron is averaged from, and a level's one-pixel apron holds the neighbours its
-// normals need -- writes each level's depth tile, and evaluates vertex_of / the normal's expression of k_vbo_normals_f32 from the
-// LDS values.  Every output is the per-level launches' bit for bit.
+// right and below in LDS, halves it level by level there (box_half, as k_box_half_ignore_invalid_f32) -- the apron is what the
+// next level's one-pixel apron is averaged from, and a level's one-pixel apron holds the neighbours its normals need -- writes
+// each level's depth tile, and evaluates depth_vertex / vertex_normal, as k_vbo_normals_f32 does, from the LDS values.  Every
+// output is the per-level launches' bit for bit.
 struct PyrParams {
     const unsigned char* d0;
     size_t d0_pitch;
@@ -903,11 +758,6 @@ struct PyrParams {
     int levels;
     float scale;
 };
-__device__ __forceinline__ float4 pyr_vertex(const Intr& K, float scale, float depth, int u, int v)
-{
-    const float kz = scale * depth;
-    return make_float4(kz * ((float)u - K.u0) / K.fu, kz * ((float)v - K.v0) / K.fv, kz, 1.0f);
-}
 __global__ __launch_bounds__(256) void k_depth_pyramid_vbo_normals(const PyrParams p)
 {
     constexpr int E0 = 40, E1 = 20, E2 = 10, E3 = 5;   // staged extents: tile + apron
@@ -931,14 +781,7 @@ __global__ __launch_bounds__(256) void k_depth_pyramid_vbo_normals(const PyrPara
             const float* f = sl[l - 1];
             for (int t = tid; t < E * E; t += 256) {
                 const int ly = t / E, lx = t - ly * E;
-                const float tx = f[(2 * ly) * Ef + 2 * lx], ty = f[(2 * ly) * Ef + 2 * lx + 1], bx = f[(2 * ly + 1) * Ef + 2 * lx], by = f[(2 * ly + 1) * Ef + 2 * lx + 1];
-                int n = 0;
-                float sum = 0;
-                if (isfinite(tx)) { sum += tx; n++; }
-                if (isfinite(ty)) { sum += ty; n++; }
-                if (isfinite(bx)) { sum += bx; n++; }
-                if (isfinite(by)) { sum += by; n++; }
-                const float m = n > 0 ? (sum / n) : __builtin_nanf("");
+                const float m = box_half(f[(2 * ly) * Ef + 2 * lx], f[(2 * ly) * Ef + 2 * lx + 1], f[(2 * ly + 1) * Ef + 2 * lx], f[(2 * ly + 1) * Ef + 2 * lx + 1]);
                 sl[l][t] = m;
                 const int x = x0 + lx, y = y0 + ly;
                 if (lx < S && ly < S && x < p.w[l] && y < p.h[l]) reinterpret_cast<float*>(p.d[l] + (size_t)y * p.dpitch[l])[x] = m;
@@ -956,17 +799,11 @@ __global__ __launch_bounds__(256) void k_depth_pyramid_vbo_normals(const PyrPara
         for (int t = tid; t < S * S; t += 256) {
             const int ly = t / S, lx = t - ly * S, u = x0 + lx, v = y0 + ly;
             if (u >= w || v >= h) continue;
-            const float4 Vc = pyr_vertex(K, p.scale, d[ly * E + lx], u, v);
+            const float4 Vc = depth_vertex(K, p.scale * d[ly * E + lx], u, v);
             reinterpret_cast<float4*>(p.vbo[l] + (size_t)v * p.vpitch[l])[u] = Vc;
             float4 N = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (u + 1 < w && v + 1 < h) {
-                const float4 Vr = pyr_vertex(K, p.scale, d[ly * E + lx + 1], u + 1, v), Vu = pyr_vertex(K, p.scale, d[(ly + 1) * E + lx], u, v + 1);
-                const V3 a = v3(Vr.x - Vc.x, Vr.y - Vc.y, Vr.z - Vc.z);
-                const V3 b = v3(Vu.x - Vc.x, Vu.y - Vc.y, Vu.z - Vc.z);
-                const V3 axb = v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
-                const float mag = length(axb);
-                N = make_float4(-axb.x / mag, -axb.y / mag, -axb.z / mag, 1.0f);
-            }
+            if (u + 1 < w && v + 1 < h)
+                N = vertex_normal(Vc, depth_vertex(K, p.scale * d[ly * E + lx + 1], u + 1, v), depth_vertex(K, p.scale * d[(ly + 1) * E + lx], u, v + 1));
             reinterpret_cast<float4*>(p.nrm[l] + (size_t)v * p.npitch[l])[u] = N;
         }
     }

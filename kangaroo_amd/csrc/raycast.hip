@@ -459,12 +459,10 @@ __device__ __forceinline__ RayParams level_params(const RayParams& base, const R
     p.K = lv.K;
     return p;
 }
-// the application's DepthToVbo(ray_v[l], ray_d[l], K[l]) (main.cpp:286), same expression, for a pixel whose depth image holds kz
+// the application's DepthToVbo(ray_v[l], ray_d[l], K[l]) (main.cpp:286) for a pixel whose depth image holds kz: depth_vertex
 __device__ __forceinline__ void write_vertex(const RayLevel& lv, const RayParams& p, const int u, const int v, const float kz)
 {
-    if (lv.vptr && u < p.w && v < p.h)
-        reinterpret_cast<float4*>(lv.vptr + (size_t)v * lv.vpitch)[u] =
-            make_float4(kz * ((float)u - p.K.u0) / p.K.fu, kz * ((float)v - p.K.v0) / p.K.fv, kz, 1.0f);
+    if (lv.vptr && u < p.w && v < p.h) reinterpret_cast<float4*>(lv.vptr + (size_t)v * lv.vpitch)[u] = depth_vertex(p.K, kz, u, v);
 }
 
 template <typename CELL>

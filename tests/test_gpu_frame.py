@@ -96,6 +96,41 @@ def test_gpu_frame_step_equals_the_separate_calls(roo, math, track):
         roo.set_math_mode(prev)
 
 
+def test_gpu_frame_step_ragged_texel_blocks(roo):
+    """The packed texel image of the frame's fused preprocess against the one SdfFuse packs for itself, where the 8 x 4 pixel blocks
+    are ragged: 203 x 150 -- the last 8-pixel block of a row holds 3 pixels, the last row of tiles 2 image rows (240 x 180 above has
+    whole blocks only).  Fast numerics, untracked: fuse.hip's launch rule gives every z-range of this even-sized, aligned volume a
+    tiled kernel that stages from the packed image (the difference-tile kernel, which does not, exists in exact numerics only), the
+    frame's own image on one side and the library's scratch on the other.  Three whole-frame steps, everything bit for bit."""
+    import torch
+    N, w, h = 96, 203, 150
+    scene = "room"
+    bmin, bmax, near, far = scenes.SCENES[scene]
+    K = scenes.intrinsics(w, h)
+    tr = scenes.trunc_dist(bmin, bmax, (N, N, N))
+    prev = roo.set_math_mode("fast")
+    try:
+        va, vb = roo.BoundedVolume(N, N, N, bmin, bmax), roo.BoundedVolume(N, N, N, bmin, bmax)
+        mk = lambda: [roo.Image(w, h), roo.Image(w, h, "f32x4"), roo.Image(w, h, "f32x4"), roo.Image(w, h), roo.Image(w, h, "f32x4"), roo.Image(w, h)]
+        ia, ib = mk(), mk()
+        fr = roo.Frame(vb, roo.Image(w, h), ib[0], ib[1], ib[2], ib[3], ib[4], ib[5], K, scenes.BILATERAL, near, far, tr, scenes.MAX_W, scenes.MIN_COS_THETA)
+        roo.SdfReset(va, float("nan"))
+        fr.set_track(False)
+        fr.reset()
+        for i in range(3):
+            T_wc = scenes.orbit_pose(i, 30)
+            raw = T.upload_image(roo, scenes.render_depth(scene, w, h, T_wc, K))
+            _operators_frame(roo, va, ia, K, T_wc, raw, tr, near, far)
+            fr.step(T_wc, scenes.se3_inverse(T_wc), raw)
+            torch.cuda.synchronize()
+            for a, b in zip(ia, ib):
+                assert T.nan_equal(a.MemcpyToHost(), b.MemcpyToHost()), (i, a.kind)
+            assert T.nan_equal(va.MemcpyToHost(), vb.MemcpyToHost()), i
+        assert np.isfinite(va.MemcpyToHost()).any()   # the frames fused something
+    finally:
+        roo.set_math_mode(prev)
+
+
 def test_gpu_frame_track_off_and_on_again(roo):
     """The auto policy's block pattern: tracked frames, plain frames (the summary goes stale), tracked frames again after
     kfx_sdf_summary_rebuild -- the volume equals an always-plain pipeline's bit for bit and, in exact numerics, so do the images

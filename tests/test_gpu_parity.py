@@ -245,33 +245,43 @@ def test_gpu_reset_fills_padding(roo):
     assert (host[3:5, 2:, 1:, 0] == -1.0).any() and host[0, 0, 0, 0] == 0.25
 
 
-@pytest.mark.parametrize("kind,minval", [("f32", 0.2), ("f32", None), ("u16", 200), ("u8", None)])
-@pytest.mark.parametrize("size", [1, 3, 5])
-def test_gpu_bilateral_variants(roo, kind, minval, size):
-    w, h = 70, 45  # not multiples of the tile
+def bilateral_variant_input(kind):
+    """(image, gr) of test_gpu_bilateral_variants: 70 x 45, a multiple of no tile"""
+    w, h = 70, 45
     rng = np.random.default_rng(11)
     base = scenes.render_depth("room", w, h)
     if kind == "f32":
         a = base.copy()
         a[5:9, 10:20] = np.nan
         a[20:22, :] = 0.05
-        gr = 0.1
-    elif kind == "u16":
+        return a, 0.1
+    if kind == "u16":
         a = np.nan_to_num(base * 1000.0).astype(np.uint16)
         a[5:9, 10:20] = 0
-        gr = 100.0
-    else:
-        a = rng.integers(0, 255, (h, w)).astype(np.uint8)
-        gr = 30.0
-    oin = oracle.Image.from_numpy(a)
+        return a, 100.0
+    return rng.integers(0, 255, (h, w)).astype(np.uint8), 30.0
+
+
+def check_bilateral_variant(roo, kind, minval, size):
+    """BilateralFilter against oracle.bilateral: the NaN pattern equal, values within BILATERAL_RTOL; the output starts out full of a
+    finite value no result can have, and none of it survives (a row or column the launch did not cover would keep it)"""
+    a, gr = bilateral_variant_input(kind)
+    h, w = a.shape
     oout = oracle.Image(w, h)
-    oracle.bilateral(oout, oin, 1.5, gr, size, minval)
-    gout = roo.Image(w, h)
+    oracle.bilateral(oout, oracle.Image.from_numpy(a), 1.5, gr, size, minval)
+    gout = roo.Image(w, h).MemcpyFromHost(np.full((h, w), -1.0, np.float32))
     roo.BilateralFilter(gout, T.upload_image(roo, a), 1.5, gr, size, minval)
     got, exp = gout.MemcpyToHost(), oout.data
+    assert not (got == -1.0).any(), (kind, size, np.argwhere(got == -1.0)[:4])
     assert np.array_equal(np.isnan(got), np.isnan(exp))
     ok = np.isfinite(exp)
     assert np.allclose(got[ok], exp[ok], rtol=BILATERAL_RTOL, atol=1e-30), np.abs(got[ok] / exp[ok] - 1).max()
+
+
+@pytest.mark.parametrize("kind,minval", [("f32", 0.2), ("f32", None), ("u16", 200), ("u8", None)])
+@pytest.mark.parametrize("size", [1, 3, 5])
+def test_gpu_bilateral_variants(roo, kind, minval, size):
+    check_bilateral_variant(roo, kind, minval, size)
 
 
 def test_gpu_bilateral_large_window_fallback(roo):

@@ -108,9 +108,12 @@ def test_gpu_scale_bias_u16_is_the_reference_expression(roo):
 
 
 def _tile_child():
-    """Run in a fresh interpreter per KFX_BILATERAL_TILE: the LDS kernel's shapes (size 5 in both modes, 3 in exact mode)"""
+    """Run in a fresh interpreter per KFX_BILATERAL_TILE: the LDS kernel's shapes (size 5 in both modes, 3 in exact mode).  Both sides
+    of check_kernel's equality go through one dispatch, so a grid or an LDS size that is wrong for a shape would cancel there: plain
+    BilateralFilter is also held against the oracle in exact numerics (test_gpu_bilateral_variants' inputs, comparison and tolerance)."""
     import torch
     from kangaroo_amd import roo
+    from test_gpu_parity import check_bilateral_variant
     assert torch.cuda.is_available()
     for math in ("exact", "fast"):
         roo.set_math_mode(math)
@@ -118,6 +121,10 @@ def _tile_child():
             for size in (3, 5):
                 check_kernel(roo, fmt, size)
             check_kernel(roo, fmt, 5, "sub")
+    roo.set_math_mode("exact")
+    for kind, minval in (("f32", 0.2), ("u8", None)):
+        for size in (3, 5):
+            check_bilateral_variant(roo, kind, minval, size)
     print("tile child ok", os.environ.get("KFX_BILATERAL_TILE"))
 
 
