@@ -1,7 +1,9 @@
-// composite.hip -- per-pixel glue of the multi-GPU raycast composite (kangaroo_amd/pipeline.py): every
-// rank ray-casts its own Z-slab; the nearest hit over all slabs wins.  Two collectives (RCCL, issued by
-// the host through torch.distributed) carry the data; these kernels pack / select / unpack around them so
-// that a frame costs three small launches instead of a dozen elementwise tensor ops.
+// composite.hip -- the kernels of the multi-GPU raycast composite and their launchers (kfx_composite_*, include/kfx.h): every
+// rank ray-casts its own Z-slab; the nearest hit over all slabs wins.  Two collectives carry the data; these kernels pack / select /
+// unpack around them, so that a frame costs three small launches instead of a dozen elementwise tensor ops.  The collectives are
+// not issued here.  Two drivers order launches and collectives: kfx_slab_composite / kfx_slab_composite_direct (slab.hip) through
+// whatever transport stands behind a kfx_comm, and kangaroo_amd/pipeline.py through torch.distributed.  The three images go to the
+// kernels as one RenderImages; a pixel's addresses, and what is stored there, through ray_out / write_hit (raycast_ray.h).
 //   key     = (depth bits << 8) | rank     positive floats order like their bit patterns; misses = +inf
 //   all_reduce(MIN, key)                   -> winner rank and its depth, per pixel
 //   payload = winner ? {n.x, n.y, n.z, shade} : 0           all_reduce(SUM, payload)   (n.w = hit ? 1 : 0 comes out of the key)
@@ -17,64 +19,63 @@
 // No reference counterpart (the reference is single-GPU).
 #include "kfx_device.h"
 #include "host_args.h"
+#include "raycast_ray.h"
 
 namespace kfx {
 
 struct CompParams {
-    unsigned char *dptr, *nptr, *iptr;
-    size_t dpitch, npitch, ipitch;
+    RenderImages im;  // w x h: the launch
     long long* key;   // w*h, dense
     float* payload;   // w*h*4, dense (KFX_COMPOSITE_PAYLOAD floats per pixel)
-    int w, h, rank;
+    int rank;
 };
 
 __global__ __launch_bounds__(256) void k_composite_pack(const CompParams p)
 {
-    const int u = blockIdx.x * 64 + (threadIdx.x & 63), v = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (u >= p.w || v >= p.h) return;
-    const float d = reinterpret_cast<const float*>(p.dptr + (size_t)v * p.dpitch)[u];
+    int u, v;
+    pixel_xy(u, v);
+    if (u >= p.im.w || v >= p.im.h) return;
+    const float d = *ray_out(p.im, u, v).depth;
     const float dd = isfinite(d) ? d : __builtin_inff();
-    p.key[(size_t)v * p.w + u] = ((long long)__float_as_uint(dd) << 8) | (long long)p.rank;
+    p.key[(size_t)v * p.im.w + u] = ((long long)__float_as_uint(dd) << 8) | (long long)p.rank;
 }
 
 // after the MIN all-reduce of `key`: keep this rank's normal / shade only where it won
 __global__ __launch_bounds__(256) void k_composite_select(const CompParams p)
 {
-    const int u = blockIdx.x * 64 + (threadIdx.x & 63), v = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (u >= p.w || v >= p.h) return;
-    const size_t i = (size_t)v * p.w + u;
+    int u, v;
+    pixel_xy(u, v);
+    if (u >= p.im.w || v >= p.im.h) return;
+    const size_t i = (size_t)v * p.im.w + u;
     const long long k = p.key[i];
-    const float d = reinterpret_cast<const float*>(p.dptr + (size_t)v * p.dpitch)[u];
+    const RayOut o = ray_out(p.im, u, v);
+    const float d = *o.depth;
     const bool mine = isfinite(d) && (int)(k & 0xff) == p.rank && (unsigned)(k >> 8) == __float_as_uint(d);
     float4 n = make_float4(0.f, 0.f, 0.f, 0.f);
     float s = 0.f;
-    if (mine) {
-        n = reinterpret_cast<const float4*>(p.nptr + (size_t)v * p.npitch)[u];
-        s = reinterpret_cast<const float*>(p.iptr + (size_t)v * p.ipitch)[u];
-    }
+    if (mine) { n = *o.normal; s = *o.shade; }
     reinterpret_cast<float4*>(p.payload)[i] = make_float4(n.x, n.y, n.z, s); // n.w of a hit is 1 (Q8): it travels as the key's hit bit
 }
 
-// after the SUM all-reduce of `payload`: write the composite images (depth comes back out of the key)
+// after the SUM all-reduce of `payload`: write the composite images (depth comes back out of the key).  A miss carries the summed
+// payload as it is -- zeros -- with n.w = 0
 __global__ __launch_bounds__(256) void k_composite_unpack(const CompParams p)
 {
-    const int u = blockIdx.x * 64 + (threadIdx.x & 63), v = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (u >= p.w || v >= p.h) return;
-    const size_t i = (size_t)v * p.w + u;
+    int u, v;
+    pixel_xy(u, v);
+    if (u >= p.im.w || v >= p.im.h) return;
+    const size_t i = (size_t)v * p.im.w + u;
     const unsigned bits = (unsigned)(p.key[i] >> 8);
     const bool hit = bits < 0x7f800000u;
     const float4 o = reinterpret_cast<const float4*>(p.payload)[i];
-    reinterpret_cast<float*>(p.dptr + (size_t)v * p.dpitch)[u] = hit ? __uint_as_float(bits) : __builtin_nanf("");
-    reinterpret_cast<float4*>(p.nptr + (size_t)v * p.npitch)[u] = make_float4(o.x, o.y, o.z, hit ? 1.0f : 0.0f);
-    reinterpret_cast<float*>(p.iptr + (size_t)v * p.ipitch)[u] = o.w;
+    write_hit(ray_out(p.im, u, v), hit ? __uint_as_float(bits) : __builtin_nanf(""), make_float4(o.x, o.y, o.z, hit ? 1.0f : 0.0f), o.w);
 }
 
 struct StripParams {
-    unsigned char *dptr, *nptr, *iptr;
-    size_t dpitch, npitch, ipitch;
+    RenderImages im;
     float* buf;      // strip j: KFX_COMPOSITE_STRIP_PLANES planes of S floats at buf + j * stride
     size_t stride;
-    int w, h, world;
+    int world;
     unsigned S;
 };
 
@@ -86,14 +87,11 @@ __global__ __launch_bounds__(256) void k_strips_pack(const StripParams p)
     float d = __builtin_inff();
     float4 n = make_float4(0.f, 0.f, 0.f, 0.f);
     float s = 0.f;
-    if (pix < (size_t)p.w * p.h) {
-        const int v = (int)(pix / p.w), u = (int)(pix - (size_t)v * p.w);
-        const float dd = reinterpret_cast<const float*>(p.dptr + (size_t)v * p.dpitch)[u];
-        if (isfinite(dd)) {
-            d = dd;
-            n = reinterpret_cast<const float4*>(p.nptr + (size_t)v * p.npitch)[u];
-            s = reinterpret_cast<const float*>(p.iptr + (size_t)v * p.ipitch)[u];
-        }
+    if (pix < (size_t)p.im.w * p.im.h) {
+        const int v = (int)(pix / p.im.w), u = (int)(pix - (size_t)v * p.im.w);
+        const RayOut in = ray_out(p.im, u, v);
+        const float dd = *in.depth;
+        if (isfinite(dd)) { d = dd; n = *in.normal; s = *in.shade; }
     }
     float* o = p.buf + (size_t)j * p.stride + q;
     o[0] = d; o[p.S] = n.x; o[2 * (size_t)p.S] = n.y; o[3 * (size_t)p.S] = n.z; o[4 * (size_t)p.S] = s;
@@ -117,18 +115,18 @@ __global__ __launch_bounds__(256) void k_strips_merge(const float* __restrict__ 
     for (int c = 0; c < 4; ++c) out[(size_t)(1 + c) * S + q] = v[c];
 }
 
+// (a miss carries the merged strip's normal and shade as they are -- zeros -- with n.w = 0)
 __global__ __launch_bounds__(256) void k_strips_unpack(const StripParams p)
 {
-    const int u = blockIdx.x * 64 + (threadIdx.x & 63), v = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (u >= p.w || v >= p.h) return;
-    const size_t pix = (size_t)v * p.w + u;
+    int u, v;
+    pixel_xy(u, v);
+    if (u >= p.im.w || v >= p.im.h) return;
+    const size_t pix = (size_t)v * p.im.w + u;
     const unsigned j = (unsigned)(pix / p.S), q = (unsigned)(pix - (size_t)j * p.S);
     const float* o = p.buf + (size_t)j * p.stride + q;
     const float d = o[0];
     const bool hit = __float_as_uint(d) < 0x7f800000u;
-    reinterpret_cast<float*>(p.dptr + (size_t)v * p.dpitch)[u] = hit ? d : __builtin_nanf("");
-    reinterpret_cast<float4*>(p.nptr + (size_t)v * p.npitch)[u] = make_float4(o[p.S], o[2 * (size_t)p.S], o[3 * (size_t)p.S], hit ? 1.0f : 0.0f);
-    reinterpret_cast<float*>(p.iptr + (size_t)v * p.ipitch)[u] = o[4 * (size_t)p.S];
+    write_hit(ray_out(p.im, u, v), hit ? d : __builtin_nanf(""), make_float4(o[p.S], o[2 * (size_t)p.S], o[3 * (size_t)p.S], hit ? 1.0f : 0.0f), o[4 * (size_t)p.S]);
 }
 
 } // namespace kfx
@@ -142,8 +140,7 @@ static int comp_params(CompParams& p, const kfx_image* depth, const kfx_image* n
     if (rank < 0 || rank > 255) return set_error(KFX_E_RANGE, "composite: rank must fit 8 bits");
     if (int e = check_render_images(depth, norm, img, depth, "composite")) return e;
     if (((uintptr_t)key & 7) || ((uintptr_t)payload & 15)) return set_error(KFX_E_ALIGN, "composite: alignment");
-    p = CompParams{(unsigned char*)depth->ptr, (unsigned char*)norm->ptr, (unsigned char*)img->ptr, depth->pitch, norm->pitch, img->pitch,
-                   key, payload, (int)depth->w, (int)depth->h, rank};
+    p = CompParams{render_images(depth, norm, img, depth), key, payload, rank};
     return 0;
 }
 
@@ -151,8 +148,8 @@ extern "C" int kfx_composite_pack(const kfx_image* depth, const kfx_image* norm,
 {
     CompParams p;
     if (int e = comp_params(p, depth, norm, img, key, nullptr, rank)) return e;
-    if (p.w == 0 || p.h == 0) return 0;
-    hipLaunchKernelGGL(k_composite_pack, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
+    if (p.im.w == 0 || p.im.h == 0) return 0;
+    hipLaunchKernelGGL(k_composite_pack, pixel_grid(p.im.w, p.im.h), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("kfx_composite_pack");
 }
 
@@ -162,8 +159,8 @@ extern "C" int kfx_composite_select(const kfx_image* depth, const kfx_image* nor
     CompParams p;
     if (!payload) return set_error(KFX_E_NULL, "composite: null payload");
     if (int e = comp_params(p, depth, norm, img, const_cast<long long*>(key), payload, rank)) return e;
-    if (p.w == 0 || p.h == 0) return 0;
-    hipLaunchKernelGGL(k_composite_select, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
+    if (p.im.w == 0 || p.im.h == 0) return 0;
+    hipLaunchKernelGGL(k_composite_select, pixel_grid(p.im.w, p.im.h), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("kfx_composite_select");
 }
 
@@ -173,8 +170,8 @@ extern "C" int kfx_composite_unpack(const kfx_image* depth, const kfx_image* nor
     CompParams p;
     if (!payload) return set_error(KFX_E_NULL, "composite: null payload");
     if (int e = comp_params(p, depth, norm, img, const_cast<long long*>(key), const_cast<float*>(payload), 0)) return e;
-    if (p.w == 0 || p.h == 0) return 0;
-    hipLaunchKernelGGL(k_composite_unpack, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
+    if (p.im.w == 0 || p.im.h == 0) return 0;
+    hipLaunchKernelGGL(k_composite_unpack, pixel_grid(p.im.w, p.im.h), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("kfx_composite_unpack");
 }
 
@@ -195,8 +192,7 @@ static int strip_params(StripParams& p, const kfx_image* depth, const kfx_image*
     const size_t S = kfx_composite_strip_pixels(depth->w, depth->h, world);
     if (S > 0x7fffffffull) return set_error(KFX_E_RANGE, "composite strips: image too large");
     if (stride && stride < KFX_COMPOSITE_STRIP_PLANES * S) return set_error(KFX_E_SHAPE, "composite strips: rank stride smaller than a strip");
-    p = StripParams{(unsigned char*)depth->ptr, (unsigned char*)norm->ptr, (unsigned char*)img->ptr, depth->pitch, norm->pitch, img->pitch,
-                    buf, stride ? stride : KFX_COMPOSITE_STRIP_PLANES * S, (int)depth->w, (int)depth->h, world, (unsigned)S};
+    p = StripParams{render_images(depth, norm, img, depth), buf, stride ? stride : KFX_COMPOSITE_STRIP_PLANES * S, world, (unsigned)S};
     return 0;
 }
 
@@ -227,7 +223,7 @@ extern "C" int kfx_composite_strips_unpack(const kfx_image* depth, const kfx_ima
 {
     StripParams p;
     if (int e = strip_params(p, depth, norm, img, const_cast<float*>(strips), rank_stride, world)) return e;
-    if (p.w == 0 || p.h == 0) return 0;
-    hipLaunchKernelGGL(k_strips_unpack, pixel_grid(p.w, p.h), dim3(256), 0, (hipStream_t)stream, p);
+    if (p.im.w == 0 || p.im.h == 0) return 0;
+    hipLaunchKernelGGL(k_strips_unpack, pixel_grid(p.im.w, p.im.h), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("kfx_composite_strips_unpack");
 }

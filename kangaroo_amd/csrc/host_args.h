@@ -1,5 +1,6 @@
 // host_args.h -- what the launchers decide alike on the host: what a usable kfx_volume and a usable kfx_image are, the grid of a
-// per-pixel launch, how a Z-slab is seen through the whole volume's geometry, how a process-wide knob is read.
+// per-pixel launch, how a Z-slab is seen through the whole volume's geometry, how a process-wide knob is read, how a sequence of
+// steps that must all be entered keeps its first error.
 #pragma once
 
 #include <cstdio>
@@ -71,6 +72,12 @@ inline int check_render_images(const kfx_image* depth, const kfx_image* norm, co
     return check_image(img, 4, lead->w, lead->h, what);
 }
 
+// the device's view of a usable rendering trio; `lead` bounds the launch
+inline RenderImages render_images(const kfx_image* depth, const kfx_image* norm, const kfx_image* img, const kfx_image* lead)
+{
+    return RenderImages{(unsigned char*)depth->ptr, (unsigned char*)norm->ptr, (unsigned char*)img->ptr, depth->pitch, norm->pitch, img->pitch, (int)lead->w, (int)lead->h};
+}
+
 // the grid of a per-pixel launch: workgroups of 256 = PIX_W x PIX_H pixels, whose threads find their pixel with pixel_xy (kfx_device.h)
 inline dim3 pixel_grid(int w, int h) { return dim3(ceil_div(w, PIX_W), ceil_div(h, PIX_H)); }
 
@@ -133,5 +140,18 @@ inline float env_float(const char* name, float dflt)
     const char* e = getenv(name);
     return e ? (float)atof(e) : dflt;
 }
+// whether the knob is set to something that begins with `prefix`
+inline bool env_begins(const char* name, const char* prefix)
+{
+    const char* e = getenv(name);
+    return e && strncmp(e, prefix, strlen(prefix)) == 0;
+}
+
+// "First error wins, go on regardless": a rank must not skip a collective its peers enter (they would wait for ever), so a step's
+// failure is noted, the steps after it are entered all the same, and the first error is what the caller returns at the end.
+struct FirstError {
+    int status = 0;
+    void operator()(int e) { if (e && !status) status = e; }
+};
 
 } // namespace kfx

@@ -209,6 +209,10 @@ __device__ __forceinline__ const T* row(const ImgView& im, size_t y)
     return reinterpret_cast<const T*>(im.ptr + y * im.pitch);
 }
 
+// Device view of the rendering trio -- depth (float), normals (float4), shading image (float) -- and the size of the launch that
+// reads or writes it (raycast_ray.h: ray_out finds a pixel's three addresses in it, as in a RayParams)
+struct RenderImages { unsigned char *dptr, *nptr, *iptr; size_t dpitch, npitch, ipitch; int w, h; };
+
 // Device view of BoundedVolume<SDF_t>.
 struct VolView {
     unsigned char* ptr;

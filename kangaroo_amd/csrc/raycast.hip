@@ -721,20 +721,16 @@ __global__ __launch_bounds__(256) void k_raycast_sdf_slab(const RayParams p, con
 // state -> the three output images (hit: depth / normal / shade; otherwise NaN / 0 / 0)
 __global__ __launch_bounds__(256) void k_raycast_state_to_images(const RayParams p, const float* __restrict__ state)
 {
-    const int u = blockIdx.x * 64 + (threadIdx.x & 63), v = blockIdx.y * 4 + (threadIdx.x >> 6);
+    int u, v;
+    pixel_xy(u, v);
     if (u >= p.w || v >= p.h) return;
     const size_t plane = (size_t)p.w * p.h;
     const float* st = state + (size_t)v * p.w + u;
     const float depth = st[0];
     const bool hit = st[3 * plane] == 1.f && depth > 0.f;
     const RayOut o = ray_out(p, u, v);
-    if (hit) {
-        *o.depth = depth;
-        *o.shade = st[8 * plane];
-        *o.normal = make_float4(st[5 * plane], st[6 * plane], st[7 * plane], 1.0f);
-    } else {
-        write_no_hit(o);
-    }
+    if (hit) write_hit(o, depth, make_float4(st[5 * plane], st[6 * plane], st[7 * plane], 1.0f), st[8 * plane]);
+    else write_no_hit(o);
 }
 
 } // namespace kfx

@@ -105,9 +105,10 @@ __device__ __forceinline__ V3 normal_c(const RayParams& p, const V3 pos_w)
     return normal_of(p.T, gradient<CELL>(p, pos_w));
 }
 
-// where pixel (u, v) of the three output images lies
+// where pixel (u, v) of the three output images lies; p: a RayParams, or a RenderImages (kfx_device.h) -- the same eight members
 struct RayOut { float* depth; float* shade; float4* normal; };
-__device__ __forceinline__ RayOut ray_out(const RayParams& p, const int u, const int v)
+template <typename IMAGES>
+__device__ __forceinline__ RayOut ray_out(const IMAGES& p, const int u, const int v)
 {
     return RayOut{reinterpret_cast<float*>(p.dptr + (size_t)v * p.dpitch) + u, reinterpret_cast<float*>(p.iptr + (size_t)v * p.ipitch) + u,
                   reinterpret_cast<float4*>(p.nptr + (size_t)v * p.npitch) + u};
@@ -118,6 +119,13 @@ __device__ __forceinline__ void write_no_hit(const RayOut& o)
     *o.depth = __builtin_nanf("");
     *o.shade = 0.f;
     *o.normal = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+// ... and a pixel that has something to show: the caller's values as they are (normal.w = 1 marks a hit: cu_raycast.cu:101)
+__device__ __forceinline__ void write_hit(const RayOut& o, const float depth, const float4 normal, const float shade)
+{
+    *o.depth = depth;
+    *o.shade = shade;
+    *o.normal = normal;
 }
 
 // The plain march of a ray that enters the box (cu_raycast.cu:58-88) over any sampler, float sample(p, pos_w) -- p a RayParams or a
@@ -164,7 +172,7 @@ __device__ __forceinline__ void write_ray(const RayParams& q, const int u, const
     if (depth > 0) {
         const RayBox r = ray_box(q, u, v);
         const V3 n_c = normal_of(q.T, gradient_at(r.c_w + r.ray_w * depth));
-        *o.depth = depth;
+        *o.depth = depth;   // (write_hit's stores, the depth ahead of the shade's arithmetic: the order the march kernels were scheduled with)
         if constexpr (std::is_same<SHADE, PhongShade>::value) *o.shade = phong(r.ray_c * depth, n_c);
         else *o.shade = shade(r.c_w + r.ray_w * depth);
         *o.normal = make_float4(n_c.x, n_c.y, n_c.z, 1.0f);

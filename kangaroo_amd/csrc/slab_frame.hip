@@ -19,7 +19,7 @@ constexpr int EV = 5;          // events per frame: before preprocess, before Sd
 constexpr int OPEN_SLOTS = 8;  // exact march: frames whose "rays left open" word may still be on its way to the host
 constexpr int PIPE_MAX = KFX_SLAB_PIPE_MAX;
 // a frame of the pipelined exact raycast whose final exchange has not been enqueued yet (host-blocking transports trail by pipe - 1 frames)
-struct PendingFinal { long long frame; int set, os, tiles; };
+struct PendingFinal { long long frame; int set, os; };
 }
 
 struct kfx_slab_frame {
@@ -52,7 +52,7 @@ struct kfx_slab_frame {
     int pipe;                                // buffer / image sets in use (2 .. PIPE_MAX; 0: not pipelined)
     void* fin_mem[PIPE_MAX];
     kfx::ExactFinalBufs fin[PIPE_MAX];
-    size_t fin_bytes;
+    size_t fin_bytes[PIPE_MAX];
     hipEvent_t marched_ev[PIPE_MAX], fin_done[PIPE_MAX];
     int fin_inflight[PIPE_MAX];              // fin_done[set] has been recorded and the caller's stream has not waited for it since
     PendingFinal pending[PIPE_MAX];
@@ -71,6 +71,9 @@ struct kfx_slab_frame {
 };
 
 using namespace kfx;
+
+// buffer / image sets of the pipelined exact raycast under configuration `c` (0: not pipelined)
+static int pipe_of(const kfx_slab_frame_config& c, int world) { return (c.overlap && c.raycast == KFX_SLAB_RAYCAST_EXACT && world > 1) ? c.pipe_depth : 0; }
 
 static int check_policies(const kfx_slab_frame_config& c, int world)
 {
@@ -126,19 +129,14 @@ static int ensure_scratch(kfx_slab_frame* f, const kfx_slab_frame_config& c)
         if (int e = grow(&f->bcast, &f->bcast_bytes, c.filtered.w * c.filtered.h * 20 + 256)) return e;
     if (c.raycast == KFX_SLAB_RAYCAST_EXACT && c.overlap && world > 1) {
         // the sets of the final exchange's buffers, the events between the two streams, the second communicator
-        const size_t need = kfx::exact_final_bytes(w, h, world);
+        kfx::ExactFinalBufs sizes_only;
+        const size_t need = kfx::exact_final_carve(sizes_only, nullptr, w, h, world) * sizeof(int);
         for (int k = 0; k < c.pipe_depth; ++k) {
-            if (need > f->fin_bytes || !f->fin_mem[k]) {
-                void* q = nullptr;
-                if (int e = hip_status(hipMalloc(&q, need), "kfx_slab_frame: hipMalloc")) return e;
-                if (f->fin_mem[k]) (void)hipFree(f->fin_mem[k]);
-                f->fin_mem[k] = q;
-            }
+            if (int e = grow(&f->fin_mem[k], &f->fin_bytes[k], need)) return e;
             kfx::exact_final_carve(f->fin[k], f->fin_mem[k], w, h, world);
             if (!f->marched_ev[k]) if (int e = hip_status(hipEventCreateWithFlags(&f->marched_ev[k], hipEventDisableTiming), "kfx_slab_frame: hipEventCreate")) return e;
             if (!f->fin_done[k]) if (int e = hip_status(hipEventCreateWithFlags(&f->fin_done[k], hipEventDisableTiming), "kfx_slab_frame: hipEventCreate")) return e;
         }
-        if (need > f->fin_bytes) f->fin_bytes = need;
         if (!f->have_side_comm) {
             if (!f->comm->dup) return set_error(KFX_E_RANGE, "kfx_slab_frame: the exact raycast's overlap needs a transport that can duplicate its communicator (kfx_comm::dup)");
             if (int e = f->comm->dup(f->comm, &f->side_comm)) return set_error(e, "kfx_slab_frame: kfx_comm::dup");
@@ -154,13 +152,13 @@ static int ranks_agree(kfx_slab_frame* f, int local_status)
 {
     if (f->comm->world == 1 || !f->agree) return local_status;
     int flag = local_status ? 1 : 0, sum = 0;
-    int e = hip_status(hipMemcpy(f->agree, &flag, sizeof(int), hipMemcpyHostToDevice), "kfx_slab_frame: hipMemcpy");
-    const int c = f->comm->all_reduce(f->comm, f->agree, 1, KFX_COMM_SUM_I32, nullptr);
-    if (c && !e) e = c;
-    if (!e) e = hip_status(hipStreamSynchronize(nullptr), "kfx_slab_frame");
-    if (!e) e = hip_status(hipMemcpy(&sum, f->agree, sizeof(int), hipMemcpyDeviceToHost), "kfx_slab_frame: hipMemcpy");
+    FirstError note;
+    note(hip_status(hipMemcpy(f->agree, &flag, sizeof(int), hipMemcpyHostToDevice), "kfx_slab_frame: hipMemcpy"));
+    note(f->comm->all_reduce(f->comm, f->agree, 1, KFX_COMM_SUM_I32, nullptr));
+    if (!note.status) note(hip_status(hipStreamSynchronize(nullptr), "kfx_slab_frame"));
+    if (!note.status) note(hip_status(hipMemcpy(&sum, f->agree, sizeof(int), hipMemcpyDeviceToHost), "kfx_slab_frame: hipMemcpy"));
     if (local_status) return local_status;
-    if (e) return e;
+    if (note.status) return note.status;
     return sum ? set_error(KFX_E_RANGE, "kfx_slab_frame: another rank could not adopt the configuration (kept the previous one on every rank)") : 0;
 }
 
@@ -172,9 +170,7 @@ extern "C" int kfx_slab_frame_create(kfx_slab_frame** out, const kfx_slab_frame_
     if (int e = check_frame_views(cfg->raw, cfg->filtered, cfg->vbo, cfg->normals, cfg->ray_depth, cfg->ray_norm, cfg->ray_img, "kfx_slab_frame_create")) return e;
     if (cfg->ray_depth.w < cfg->ray_img.w || cfg->ray_depth.h < cfg->ray_img.h || cfg->ray_norm.w < cfg->ray_img.w || cfg->ray_norm.h < cfg->ray_img.h)
         return set_error(KFX_E_SHAPE, "kfx_slab_frame_create: rendering images smaller than ray_img");
-    const kfx_slab_layout& L = cfg->layout;
-    if (L.rank != comm->rank || L.world != comm->world || cfg->local.d != L.s1 - L.s0)
-        return set_error(KFX_E_SHAPE, "kfx_slab_frame_create: volume / communicator do not match the layout");
+    if (int e = check_layout(&cfg->local, &cfg->layout, comm, "kfx_slab_frame_create")) return e;
     if (cfg->timing_slots < 0 || cfg->timing_slots > (1 << 20)) return set_error(KFX_E_RANGE, "kfx_slab_frame_create: timing_slots");
     if (int e = check_policies(*cfg, comm->world)) return e;
     kfx_slab_frame* f = new (std::nothrow) kfx_slab_frame();
@@ -184,7 +180,7 @@ extern "C" int kfx_slab_frame_create(kfx_slab_frame** out, const kfx_slab_frame_
     f->timing = 31u;
     for (int i = 0; i < OPEN_SLOTS; ++i) f->open_frame[i] = -1;
     f->rendered = -1;
-    f->pipe = (cfg->overlap && cfg->raycast == KFX_SLAB_RAYCAST_EXACT && comm->world > 1) ? cfg->pipe_depth : 0;
+    f->pipe = pipe_of(*cfg, comm->world);
     f->texels = texel_image_alloc(cfg->filtered.w, cfg->filtered.h);
     int e = hip_status(hipMalloc((void**)&f->agree, 64), "kfx_slab_frame_create: hipMalloc");
     if (!e) e = ensure_scratch(f, f->cfg);
@@ -246,21 +242,36 @@ extern "C" int kfx_slab_frame_set_timing(kfx_slab_frame* f, unsigned mask)
     return 0;
 }
 
+// Slot i's "rays left open" word, if a march's is on its way there: waits for it (`wait`) or takes it only if it has arrived, and
+// frees the slot.  Returns whether it arrived saying that the march left rays without a final status.
+static bool take_open_slot(kfx_slab_frame* f, int i, bool wait)
+{
+    if (f->open_frame[i] < 0) return false;
+    if (wait) (void)hipEventSynchronize(f->open_done[i]);
+    else if (hipEventQuery(f->open_done[i]) != hipSuccess) { (void)hipGetLastError(); return false; }
+    f->open_frame[i] = -1;
+    return ((volatile int*)f->h_open)[i] != 0 && !f->cfg.unchecked;
+}
+
+static int open_rays_error() { return set_error(KFX_E_RANGE, "kfx_slab_frame: an exact march left rays without a final status"); }
+
 // the exact marches whose "rays left open" word has arrived; all of them when `all` (after a synchronisation)
 static int check_open(kfx_slab_frame* f, bool all)
 {
-    for (int i = 0; i < OPEN_SLOTS; ++i) {
-        if (f->open_frame[i] < 0) continue;
-        if (!all && hipEventQuery(f->open_done[i]) != hipSuccess) { (void)hipGetLastError(); continue; }
-        if (all) (void)hipEventSynchronize(f->open_done[i]);
-        if (((volatile int*)f->h_open)[i] != 0 && !f->cfg.unchecked) f->failed = 1;
-        f->open_frame[i] = -1;
-    }
+    for (int i = 0; i < OPEN_SLOTS; ++i)
+        if (take_open_slot(f, i, all)) f->failed = 1;
     if (f->failed) {
         f->failed = 0;
-        return set_error(KFX_E_RANGE, "kfx_slab_frame: an exact march left rays without a final status");
+        return open_rays_error();
     }
     return 0;
+}
+
+// after a synchronisation of everything this frame object had in flight: nothing is left to wait for
+static void settle(kfx_slab_frame* f)
+{
+    f->merge_pending = 0;
+    for (int k = 0; k < PIPE_MAX; ++k) f->fin_inflight[k] = 0;
 }
 
 // where frame `frame`'s rendering lives: set frame % pipe of the pipelined exact raycast (set 0 = the configuration's ray_* images)
@@ -279,49 +290,41 @@ static int finalise_oldest(kfx_slab_frame* f)
     const PendingFinal P = f->pending[0];
     for (int k = 1; k < f->n_pending; ++k) f->pending[k - 1] = f->pending[k];
     f->n_pending -= 1;
-    int status = 0;
-    const auto note = [&](int e) { if (e && !status) status = e; };
+    FirstError note;
     note(hip_status(hipStreamWaitEvent(f->side, f->marched_ev[P.set], 0), "kfx_slab_frame: hipStreamWaitEvent"));
     const kfx_image *d, *n, *i;
     images_of(f, P.set, &d, &n, &i);
-    note(kfx::exact_tiled_finalise(d, n, i, f->exact, &f->fin[P.set], P.tiles, &f->side_comm, (kfx_stream)f->side, f->h_open + P.os));
+    note(kfx::exact_tiled_finalise(d, n, i, f->fin[P.set], &f->side_comm, (kfx_stream)f->side, f->h_open + P.os));
     if (hipEventRecord(f->open_done[P.os], f->side) == hipSuccess) f->open_frame[P.os] = P.frame;
     else (void)hipGetLastError();
     (void)ring_record(f->ring, P.frame, 4, f->side);   // (if the frame still holds its slot of the ring)
     note(hip_status(hipEventRecord(f->fin_done[P.set], f->side), "kfx_slab_frame: hipEventRecord"));
     f->fin_inflight[P.set] = 1;
     f->rendered = P.frame;
-    return status;
+    return note.status;
 }
 
 static int flush_pending(kfx_slab_frame* f)
 {
-    int status = 0;
-    while (f->n_pending > 0) {
-        const int e = finalise_oldest(f);
-        if (e && !status) status = e;
-    }
-    return status;
+    FirstError note;
+    while (f->n_pending > 0) note(finalise_oldest(f));
+    return note.status;
 }
 
 extern "C" int kfx_slab_frame_wait(kfx_slab_frame* f, kfx_stream stream)
 {
     if (!f) return set_error(KFX_E_NULL, "kfx_slab_frame_wait: null frame");
-    int e = 0;
+    FirstError note;
     if (f->merge_pending) {
-        e = hip_status(hipStreamWaitEvent((hipStream_t)stream, f->merged, 0), "kfx_slab_frame_wait: hipStreamWaitEvent");
+        note(hip_status(hipStreamWaitEvent((hipStream_t)stream, f->merged, 0), "kfx_slab_frame_wait: hipStreamWaitEvent"));
         f->merge_pending = 0;
     }
     // pipelined exact raycast: every frame stepped so far gets its final exchange enqueued, and `stream` waits for all of them
-    const int p = flush_pending(f);
-    if (p && !e) e = p;
+    note(flush_pending(f));
     for (int k = 0; k < PIPE_MAX; ++k)
-        if (f->fin_inflight[k]) {
-            const int w = hip_status(hipStreamWaitEvent((hipStream_t)stream, f->fin_done[k], 0), "kfx_slab_frame_wait: hipStreamWaitEvent");
-            if (w && !e) e = w;
-        }
-    const int o = check_open(f, false);
-    return e ? e : o;
+        if (f->fin_inflight[k]) note(hip_status(hipStreamWaitEvent((hipStream_t)stream, f->fin_done[k], 0), "kfx_slab_frame_wait: hipStreamWaitEvent"));
+    note(check_open(f, false));
+    return note.status;
 }
 
 extern "C" int kfx_slab_frame_wait_frame(kfx_slab_frame* f, long long frame, kfx_stream stream)
@@ -358,19 +361,17 @@ extern "C" int kfx_slab_frame_configure(kfx_slab_frame* f, int halo, int raycast
     if (int e = check_policies(c, f->comm->world)) return e;   // (argument errors: every rank makes them alike)
     // the scratch may be replaced: nothing of this frame object may still be in flight (pending final exchanges are enqueued first:
     // collectives, entered by every rank alike)
-    int st = flush_pending(f);
-    const int y = hip_status(hipDeviceSynchronize(), "kfx_slab_frame_configure");
-    if (y && !st) st = y;
-    f->merge_pending = 0;
-    for (int k = 0; k < PIPE_MAX; ++k) f->fin_inflight[k] = 0;
+    FirstError note;
+    note(flush_pending(f));
+    note(hip_status(hipDeviceSynchronize(), "kfx_slab_frame_configure"));
+    settle(f);
     const int o = check_open(f, true);
     // A failed allocation (or a communicator that could not be duplicated) is rank-local; the ranks agree on the outcome before
     // anybody adopts the new policies, and a rank that fails keeps its old buffers (grow allocates before it frees): round-5 advice
-    if (!st) st = ensure_scratch(f, c);
-    st = ranks_agree(f, st);
-    if (st) return st;
+    if (!note.status) note(ensure_scratch(f, c));
+    if (int e = ranks_agree(f, note.status)) return e;
     f->cfg = c;
-    f->pipe = (c.overlap && c.raycast == KFX_SLAB_RAYCAST_EXACT && f->comm->world > 1) ? c.pipe_depth : 0;
+    f->pipe = pipe_of(c, f->comm->world);
     return o;
 }
 
@@ -423,8 +424,7 @@ extern "C" int kfx_slab_frame_step(kfx_slab_frame* f, const kfx_image* raw, cons
         return set_error(KFX_E_NULL, "kfx_slab_frame_step: no scratch for the input broadcast (a failed kfx_slab_frame_configure)");
     const hipStream_t s = (hipStream_t)stream;
     // From here on nothing returns early: a local failure must not keep this rank out of a collective its peers enter
-    int status = 0;
-    const auto note = [&](int e) { if (e && !status) status = e; };
+    FirstError note;
     ring_begin(f->ring, f->frames, f->timing);
     const auto record = [&](int k, hipStream_t on) {
         if (ring_record(f->ring, f->frames, k, on) != hipSuccess) note(set_error(KFX_E_RANGE, "kfx_slab_frame_step: hipEventRecord"));
@@ -454,14 +454,11 @@ extern "C" int kfx_slab_frame_step(kfx_slab_frame* f, const kfx_image* raw, cons
         // volume); ghost planes integrated here too (recompute) or fetched from the neighbours afterwards (exchange)
         const bool own_only = c.halo == KFX_SLAB_HALO_EXCHANGE && world > 1;
         const size_t first = own_only ? L.z0 : L.s0, count = own_only ? L.z1 - L.z0 : L.s1 - L.s0;
-        kfx_volume v = c.local;
-        v.ptr = (unsigned char*)v.ptr + (first - L.s0) * v.img_pitch;
-        v.d = count;
+        const auto planes = [&](kfx_volume v) { v.ptr = (unsigned char*)v.ptr + (first - L.s0) * v.img_pitch; v.d = count; return v; };
+        const kfx_volume v = planes(c.local);
         const kfx_slab sl = {L.full_d, first, L.full_zmin, L.full_zmax};
         if (f->color) {
-            kfx_volume cv = f->cvol;
-            cv.ptr = (unsigned char*)cv.ptr + (first - L.s0) * cv.img_pitch;
-            cv.d = count;
+            const kfx_volume cv = planes(f->cvol);
             // T_iw = T_cd * T_cw in float, row by row as a 4 x 4 float product with the rows (0, 0, 0, 1) evaluates it
             float T_iw[12];
             for (int i = 0; i < 3; ++i)
@@ -483,11 +480,7 @@ extern "C" int kfx_slab_frame_step(kfx_slab_frame* f, const kfx_image* raw, cons
     if (parts & KFX_FRAME_RAYCAST) {
         if (c.raycast == KFX_SLAB_RAYCAST_EXACT) {
             const int os = (int)(f->frames % OPEN_SLOTS);
-            if (f->open_frame[os] >= 0) {   // (eight frames old: long done)
-                (void)hipEventSynchronize(f->open_done[os]);
-                if (((volatile int*)f->h_open)[os] != 0 && !c.unchecked) note(set_error(KFX_E_RANGE, "kfx_slab_frame: an exact march left rays without a final status"));
-                f->open_frame[os] = -1;
-            }
+            if (take_open_slot(f, os, true)) note(open_rays_error());   // (eight frames old: long done)
             int steps = 0;
             const int tiles = c.tiles ? c.tiles : 4;
             if (f->pipe > 0) {
@@ -499,23 +492,21 @@ extern "C" int kfx_slab_frame_step(kfx_slab_frame* f, const kfx_image* raw, cons
                     note(hip_status(hipStreamWaitEvent(s, f->fin_done[set], 0), "kfx_slab_frame_step: hipStreamWaitEvent"));
                     f->fin_inflight[set] = 0;
                 }
-                note(kfx::exact_tiled_march(f->exact, &f->fin[set], &c.local, &L, T_wc, c.K, c.near, c.far, c.trunc_dist, 1, tiles, (int)c.ray_img.w,
-                                            (int)c.ray_img.h, comm, stream, &steps, f->color ? &f->cvol : nullptr));
+                kfx::TiledScratch t;
+                kfx::tiled_layout(t, f->exact, c.ray_img.w, c.ray_img.h, tiles, world);
+                note(kfx::exact_tiled_march(t, f->fin[set], &c.local, &L, T_wc, c.K, c.near, c.far, c.trunc_dist, 1, (int)c.ray_img.w, (int)c.ray_img.h, comm,
+                                            stream, &steps, f->color ? &f->cvol : nullptr));
                 f->last_steps = steps;
                 record(3, s);
                 note(hip_status(hipEventRecord(f->marched_ev[set], s), "kfx_slab_frame_step: hipEventRecord"));
-                f->pending[f->n_pending++] = PendingFinal{f->frames, set, os, tiles};
+                f->pending[f->n_pending++] = PendingFinal{f->frames, set, os};
                 // a host that blocks in collectives trails the final exchange by pipe - 1 frames (it meets its peers there: the last
                 // rank of the token chain is that far behind the first); RCCL enqueues and goes on
                 const int lag = (f->side_comm.flags & KFX_COMM_HOST_BLOCKING) ? f->pipe - 1 : 0;
                 while (f->n_pending > lag) note(finalise_oldest(f));
             } else {
-                if (f->color)
-                    note(kfx_slab_raycast_exact_tiled_color(&c.ray_depth, &c.ray_norm, &c.ray_img, f->exact, &c.local, &f->cvol, &L, T_wc, c.K, c.near, c.far,
-                                                            c.trunc_dist, 1, tiles, comm, stream, f->h_open + os, &steps));
-                else
-                    note(kfx_slab_raycast_exact_tiled(&c.ray_depth, &c.ray_norm, &c.ray_img, f->exact, &c.local, &L, T_wc, c.K, c.near, c.far, c.trunc_dist, 1,
-                                                      tiles, comm, stream, f->h_open + os, &steps));
+                note(kfx::exact_tiled(&c.ray_depth, &c.ray_norm, &c.ray_img, f->exact, &c.local, f->color ? &f->cvol : nullptr, &L, T_wc, c.K, c.near, c.far,
+                                      c.trunc_dist, 1, tiles, comm, stream, f->h_open + os, &steps));
                 f->last_steps = steps;
                 if (hipEventRecord(f->open_done[os], s) == hipSuccess) f->open_frame[os] = f->frames;
                 else (void)hipGetLastError();
@@ -550,7 +541,7 @@ extern "C" int kfx_slab_frame_step(kfx_slab_frame* f, const kfx_image* raw, cons
         }
     }
     f->frames += 1;
-    return status;
+    return note.status;
 }
 
 // preprocess, SdfFuse (+ ghost planes), the march, the merge, first to last recorded event, the period to the next frame
@@ -572,12 +563,11 @@ extern "C" int kfx_slab_frame_timings(kfx_slab_frame* f, long long first_frame, 
 extern "C" int kfx_slab_frame_sync(kfx_slab_frame* f, kfx_stream stream)
 {
     if (!f) return set_error(KFX_E_NULL, "kfx_slab_frame_sync: null frame");
-    int e = flush_pending(f);
-    const int y = hip_status(hipStreamSynchronize((hipStream_t)stream), "kfx_slab_frame_sync");
-    if (y && !e) e = y;
-    if (!e) e = hip_status(hipStreamSynchronize(f->side), "kfx_slab_frame_sync");
-    f->merge_pending = 0;
-    for (int k = 0; k < PIPE_MAX; ++k) f->fin_inflight[k] = 0;
-    const int o = check_open(f, true);
-    return e ? e : o;
+    FirstError note;
+    note(flush_pending(f));
+    note(hip_status(hipStreamSynchronize((hipStream_t)stream), "kfx_slab_frame_sync"));
+    if (!note.status) note(hip_status(hipStreamSynchronize(f->side), "kfx_slab_frame_sync"));
+    settle(f);
+    note(check_open(f, true));
+    return note.status;
 }
