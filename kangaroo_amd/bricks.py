@@ -66,10 +66,11 @@ def box_brick_ids(origin_cells, start, size, keys):
 
 class BrickStore:
     """Host memory for the bricks of one volume that are outside its box: world brick key (bx, by, bz) -> the brick's bytes
-    (512 cells, x fastest).  No limit and no eviction."""
+    (512 cells, x fastest).  No limit and no eviction.  spill() / restore() / all_items() are DeviceBrickStore's calls (ops: the
+    operator set they pack and unpack with, default kangaroo_amd.roo); the rest is plain host memory."""
 
-    def __init__(self, kind="f32"):
-        self.kind = kind
+    def __init__(self, kind="f32", ops=None):
+        self.kind, self.ops = kind, ops
         self.brick_bytes = BRICK ** 3 * {"f32": 8, "f16": 4, "c32": 4}[kind]
         self._bricks = {}
 
@@ -113,13 +114,43 @@ class BrickStore:
             return np.empty((0, 3), np.int64), np.empty((0, self.brick_bytes), np.uint8)
         return np.asarray(found, np.int64), np.stack(cells)
 
+    def _ops(self):
+        if self.ops is None:
+            from . import roo
+            self.ops = roo
+        return self.ops
+
+    def spill(self, view, fill, key0):
+        """the live bricks of `view` (ops.BrickPack) go to the host under the keys key0 + (bx, by, bz); a key already present is replaced"""
+        ids, cells = self._ops().BrickPack(view, fill)
+        if ids.numel():
+            size = (view.w, view.h, view.d)
+            self.put(world_keys(np.asarray(key0, np.int64) * BRICK, (0, 0, 0), size)[ids.cpu().numpy()], cells.cpu().numpy())
+
+    def restore(self, view, key0):
+        """the bricks the store holds of the key range of `view` go back into it (ops.BrickUnpack) and leave the store; returns how
+        many.  An empty store has nothing to look up."""
+        if not len(self):
+            return 0
+        origin, size = np.asarray(key0, np.int64) * BRICK, (view.w, view.h, view.d)
+        keys, cells = self.take(world_keys(origin, (0, 0, 0), size))
+        if len(keys):
+            self._ops().BrickUnpack(view, box_brick_ids(origin, (0, 0, 0), size, keys), cells)
+        return len(keys)
+
+    def all_items(self):
+        """what bricks.world_bricks asks either store for: (keys (m, 3) int64, cells (m, brick bytes) uint8), the cells where the
+        store keeps them -- here on the host"""
+        return self.items()
+
 
 class DeviceBrickStore:
     """Device memory for the bricks of one volume that are outside its box: a brick pool (include/kfx_brick_pool.h) of `capacity`
     bricks in one uint8 tensor, and the scratch of its calls.  spill() and restore() enqueue launches on torch's current stream and
     never touch the host.  A spill that finds the pool full DROPS the bricks that do not fit -- they are lost, as every brick is
     without a store -- and counts them: `dropped` > 0 says that the pool was too small.  No eviction.
-    What it shares with BrickStore: kind, brick_bytes, len() and nbytes (blocking: they read the pool's counters), clear(), items()."""
+    What it shares with BrickStore: kind, brick_bytes, len() and nbytes (blocking: they read the pool's counters), clear(), items(),
+    all_items(), spill() and restore()."""
 
     def __init__(self, kind, capacity, ops=None, device="cuda"):
         import torch
@@ -168,7 +199,8 @@ class DeviceBrickStore:
         self.ops.BrickPoolSpill(self.pool, self.capacity, view, fill, key0, self._scratch_for(view))
 
     def restore(self, view, key0):
-        """the bricks the pool holds of the key range of `view` go back into it and leave the pool"""
+        """the bricks the pool holds of the key range of `view` go back into it and leave the pool; returns None: how many is not
+        known on the host"""
         self.ops.BrickPoolRestore(self.pool, self.capacity, view, key0, self._scratch_for(view))
 
     def keys(self):
@@ -180,6 +212,10 @@ class DeviceBrickStore:
         Blocking: the keys block is copied to the host; the payload stays on the device."""
         slots, keys = self.ops.BrickPoolKeys(self.pool, self.capacity)
         return keys, self.ops.BrickPoolGather(self.pool, self.kind, self.capacity, slots)
+
+    def all_items(self):
+        """what bricks.world_bricks asks either store for: device_items(), the cells where the store keeps them -- on the device"""
+        return self.device_items()
 
     def items(self):
         """(every key (m, 3) int64, their cells (m, brick bytes) uint8) on the host, copies: for checkpoints and tests"""
@@ -240,10 +276,8 @@ def world_bricks(store, vol, origin, fill, ops=None, cover=None):
     live_keys = np.stack([lid % nbx, (lid // nbx) % nby, lid // (nbx * nby)], 1)
     if store is None:
         store_keys, store_cells = np.empty((0, 3), np.int64), None
-    elif hasattr(store, "device_items"):   # a device store: its payload is gathered where it is, never uploaded
-        store_keys, store_cells = store.device_items()
-    else:
-        store_keys, store_cells = store.items()
+    else:   # (a device store's payload is gathered where it is, never uploaded; a host store's is uploaded below)
+        store_keys, store_cells = store.all_items()
     lo, fdims, boxmin, boxmax, ids, order = world_frame(store_keys, live_keys, origin, dims, vol.boxmin, vol.boxmax, cover)
     cells = live_cells
     if len(store_keys):

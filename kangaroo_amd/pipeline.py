@@ -170,8 +170,8 @@ class FramePipeline:
                     self.store = bricks.DeviceBrickStore(self.kind, n, ops)
                     self.cstore = bricks.DeviceBrickStore("c32", n, ops) if self.color else None
                 else:
-                    self.store = bricks.BrickStore(self.kind)
-                    self.cstore = bricks.BrickStore("c32") if self.color else None
+                    self.store = bricks.BrickStore(self.kind, ops)
+                    self.cstore = bricks.BrickStore("c32", ops) if self.color else None
         if sensor is not None:
             if not hasattr(ops, "DepthInput"):
                 raise ValueError("FramePipeline: sensor= needs an operator set with DepthInput")
@@ -222,7 +222,7 @@ class FramePipeline:
 
     # -- overridable pieces ------------------------------------------------------
     def _alloc_volume(self, boxmin, boxmax):
-        if self.kind != "f32":
+        if self.kind != "f32":   # (the CPU tests' oracle-backed volumes are fp32 and take no kind)
             return self.ops.BoundedVolume(self.dims[0], self.dims[1], self.dims[2], boxmin, boxmax, kind=self.kind)
         return self.ops.BoundedVolume(self.dims[0], self.dims[1], self.dims[2], boxmin, boxmax)
 
@@ -268,48 +268,69 @@ class FramePipeline:
             self._cal = {"first": self.cal_first, "t": [], "clock": None} if self.cal_first >= 0 else None
             if not self.track:
                 self.set_track(True)
+        self._reset_model()
+
+    def _summary_kw(self):
+        """the keyword that makes an operator keep (SdfFuse, SdfReset) or use (RaycastSdf) the brick summary, when tracking"""
+        return {"summary": self.summary} if self.track else {}
+
+    def _reset_model(self):
+        """SdfReset(vol, NaN) (main.cpp:229) with the brick summary set to match -- the one-call frame: its reset() --, SdfReset(colorVol)
+        (main.cpp:233); the model starts over, so what its predecessor left outside the box (the stores) is not part of it."""
         if self.kframe is not None:
             self.kframe.reset()
-        elif self.track:
-            self.ops.SdfReset(self.vol, float("nan"), summary=self.summary)
         else:
-            self.ops.SdfReset(self.vol, float("nan"))
+            self.ops.SdfReset(self.vol, float("nan"), **self._summary_kw())
         if self.color:
-            self.ops.ColorReset(self.cvol)   # SdfReset(colorVol) (main.cpp:233)
-        self._forget_spilled()
-
-    def _forget_spilled(self):
-        """the model starts over: what its predecessor left outside the box is not part of it"""
+            self.ops.ColorReset(self.cvol)
         for store in (self.store, self.cstore):
             if store is not None:
                 store.clear()
 
     def shift_volume(self, shift):
         """Shift the model by whole cells (ops.VolumeShift): the SDF volume with fill NaN -- through the one-call frame where it is in
-        use -- the colour volume with fill 0.5, the summary rebuilt when tracking; vol.boxmin / boxmax (and cvol's) move."""
+        use -- the colour volume with fill 0.5, the summary rebuilt when tracking; vol.boxmin / boxmax (and cvol's) move.
+        follow=dict(spill=): before the shift the live bricks of the boxes that leave go to the stores under their world keys, after it
+        (self.origin is the new one) the bricks the stores hold of the boxes that entered go back into them.  A host store says how
+        many: the shift runs tracked, and only a restore that put something back rebuilds the summary once more.  A device pool cannot
+        say (launches only, nothing read back): the shift runs untracked and the summary is rebuilt once, after the restores,
+        whatever they put back."""
         shift = tuple(int(s) for s in shift)
         if self.spill and any(s % bricks.BRICK for s in shift):
             raise ValueError("FramePipeline: with follow=dict(spill=True) a shift is whole bricks (multiples of 8), not %s" % (shift,))
         if self._shift_scratch is None:   # one scratch for both volumes: 16 packed planes of the SDF volume's cells
             self._shift_scratch = self.ops.shift_scratch(self.vol, shift)
         volumes = [(self.vol, self.store, float("nan"))] + ([(self.cvol, self.cstore, 0.5)] if self.color else [])
-        if self.spill == "device":
-            return self._shift_with_pools(shift, volumes)
+        key = lambda start: tuple((o + s) // bricks.BRICK for o, s in zip(self.origin, start))
+        pool = self.spill == "device"
         if self.spill:
             for vol, store, fill in volumes:
-                self._spill(vol, store, fill, shift)
+                for start, size in bricks.leaving_boxes(self.dims, shift):
+                    store.spill(vol.SubVolume(start, size), fill, key(start))
+        untrack = pool and self.track and self.kframe is not None and self.kframe.track
+        if untrack:
+            self.kframe.set_track(False)   # (host state only: the frame's summary goes stale, and set_track(True) below rebuilds it)
         if self.kframe is not None:
             self.kframe.shift(shift, self._shift_scratch)
         else:
-            self.ops.VolumeShift(self.vol, shift, float("nan"), self._shift_scratch, summary=self.summary if self.track else None)
+            kw = {} if pool else {"summary": self.summary if self.track else None}   # (a pool: the shift runs untracked)
+            self.ops.VolumeShift(self.vol, shift, float("nan"), self._shift_scratch, **kw)
         if self.color:
             self.ops.VolumeShift(self.cvol, shift, 0.5, self._shift_scratch)
         self.origin = tuple(o + s for o, s in zip(self.origin, shift))
-        if self.spill:
-            restored = sum([self._restore(vol, store, shift) for vol, store, _ in volumes])
-            self._restored += restored
-            if restored and self.track:   # the summary and the class tables describe the volume as it is after the restore
-                self.summary.rebuild()
+        if not self.spill:
+            return
+        restored = [store.restore(vol.SubVolume(start, size), key(start)) for vol, store, _ in volumes
+                    for start, size in bricks.entering_boxes(self.dims, shift)]
+        if pool:
+            rebuild = self.track and self.kframe is None
+        else:
+            self._restored += sum(restored)
+            rebuild = self.track and sum(restored) > 0
+        if untrack:
+            self.kframe.set_track(True)
+        elif rebuild:   # the summary and the class tables describe the volume as it is after the restore
+            self.summary.rebuild()
 
     @property
     def restored(self):
@@ -317,51 +338,6 @@ class FramePipeline:
         if self.spill == "device":
             return sum(store.restored for store in (self.store, self.cstore) if store is not None)
         return self._restored
-
-    def _shift_with_pools(self, shift, volumes):
-        """follow=dict(spill="device"): one spill call per leaving box, the shift, one restore call per entering box -- launches only.
-        The summary is rebuilt once, after the restores, whatever they put back: the shift itself runs untracked."""
-        key = lambda start: tuple((o + s) // bricks.BRICK for o, s in zip(self.origin, start))
-        for vol, store, fill in volumes:
-            for start, size in bricks.leaving_boxes(self.dims, shift):
-                store.spill(vol.SubVolume(start, size), fill, key(start))
-        tracked = self.track and self.kframe is not None and self.kframe.track
-        if self.kframe is not None:
-            if tracked:
-                self.kframe.set_track(False)   # (host state only: the frame's summary goes stale, and set_track(True) below rebuilds it)
-            self.kframe.shift(shift, self._shift_scratch)
-        else:
-            self.ops.VolumeShift(self.vol, shift, float("nan"), self._shift_scratch)
-        if self.color:
-            self.ops.VolumeShift(self.cvol, shift, 0.5, self._shift_scratch)
-        self.origin = tuple(o + s for o, s in zip(self.origin, shift))
-        for vol, store, _ in volumes:
-            for start, size in bricks.entering_boxes(self.dims, shift):
-                store.restore(vol.SubVolume(start, size), key(start))
-        if tracked:
-            self.kframe.set_track(True)
-        elif self.track and self.kframe is None:
-            self.summary.rebuild()
-
-    def _spill(self, vol, store, fill, shift):
-        """follow=dict(spill=True), before the shift: the live bricks of the boxes that leave go to the host, under their world keys"""
-        for start, size in bricks.leaving_boxes(self.dims, shift):
-            ids, cells = self.ops.BrickPack(vol.SubVolume(start, size), fill)
-            if ids.numel():
-                store.put(bricks.world_keys(self.origin, start, size)[ids.cpu().numpy()], cells.cpu().numpy())
-
-    def _restore(self, vol, store, shift):
-        """after the shift (self.origin is the new one): the bricks the store holds of the boxes that entered go back into them;
-        returns how many"""
-        n = 0
-        for start, size in bricks.entering_boxes(self.dims, shift):
-            if not len(store):
-                break
-            keys, cells = store.take(bricks.world_keys(self.origin, start, size))
-            if len(keys):
-                self.ops.BrickUnpack(vol.SubVolume(start, size), bricks.box_brick_ids(self.origin, start, size, keys), cells)
-                n += len(keys)
-        return n
 
     def world_bricks(self):
         """Everything the model holds as brick lists on one frame: (sdf, colour) with each bricks.world_bricks()'s tuple (lo, dims,
@@ -450,8 +426,22 @@ class FramePipeline:
 
     def _fuse_color(self, maps_d, maps_n, T_cw):
         """SdfFuse(vol, colorVol, ...) of the given maps and the current RGB image (main.cpp:238 / :353)"""
-        self._timed_fuse(lambda kw: self.ops.SdfFuseColor(self.vol, self.cvol, maps_d, maps_n, T_cw, self.K, self._rgb_now, self.color_pose(T_cw), self.Kimg,
-                                                          self.trunc, self.max_w, self.mincostheta, **kw))
+        self.ops.SdfFuseColor(self.vol, self.cvol, maps_d, maps_n, T_cw, self.K, self._rgb_now, self.color_pose(T_cw), self.Kimg,
+                              self.trunc, self.max_w, self.mincostheta, **self._summary_kw())
+
+    def _integrate(self, maps_d, maps_n, T_cw):
+        """SdfFuse of the given maps at T_cw (3x4 float32) into the model (main.cpp:345-356), keeping the summary when tracking"""
+        if self.color:
+            self._fuse_color(maps_d, maps_n, T_cw)
+        else:
+            self.ops.SdfFuse(self.vol, maps_d, maps_n, T_cw, self.K, self.trunc, self.max_w, self.mincostheta, **self._summary_kw())
+
+    def _march(self, d, n, i, T_wc, K, **kw):
+        """RaycastSdf of the model from T_wc into d / n / i; color=True: RaycastSdf(..., vol, colorVol, ...) (main.cpp:284), the colour into i"""
+        if self.color:
+            self.ops.RaycastSdfColor(d, n, i, self.vol, self.cvol, T_wc, K, self.near, self.far, self.trunc, True, **kw)
+        else:
+            self.ops.RaycastSdf(d, n, i, self.vol, T_wc, K, self.near, self.far, self.trunc, True, **kw)
 
     def submit(self, array):
         """sensor=: the next frame's raw image (h x w, the sensor's type) into the upload ring; its copy is enqueued at once."""
@@ -530,34 +520,17 @@ class FramePipeline:
         if not keep:
             self.set_track(False)
 
-    def _timed_fuse(self, integrate):
-        """integrate(kw) launches the frame's SdfFuse with kw = {"summary": ...} or {} (loops that issue their own operators)."""
-        integrate({"summary": self.summary} if self.track else {})
-
-    def _timed_raycast(self, render):
-        """render(kw) launches the frame's rendering(s) of the model."""
-        render({"summary": self.summary} if self.track else {})
-
     def fuse(self, T_wc):
         if self.kframe is not None:
             self.kframe.step(T_wc, scenes.se3_inverse(T_wc), None, self.kframe.FUSE)
             return
-        if self.color:
-            self._fuse_color(self.filtered, self.normals, scenes.se3_inverse(T_wc))
-            return
-        self._timed_fuse(lambda kw: self.ops.SdfFuse(self.vol, self.filtered, self.normals, scenes.se3_inverse(T_wc), self.K, self.trunc,
-                                                     self.max_w, self.mincostheta, **kw))
+        self._integrate(self.filtered, self.normals, scenes.se3_inverse(T_wc))
 
     def raycast(self, T_wc):
         if self.kframe is not None:
             self.kframe.step(T_wc, None, None, self.kframe.RAYCAST)
             return
-        if self.color:   # RaycastSdf(..., vol, colorVol, ...) (main.cpp:284)
-            self._timed_raycast(lambda kw: self.ops.RaycastSdfColor(self.ray_d, self.ray_n, self.ray_i, self.vol, self.cvol, T_wc, self.K, self.near,
-                                                                    self.far, self.trunc, True, **kw))
-            return
-        self._timed_raycast(lambda kw: self.ops.RaycastSdf(self.ray_d, self.ray_n, self.ray_i, self.vol, T_wc, self.K, self.near, self.far,
-                                                           self.trunc, True, **kw))
+        self._march(self.ray_d, self.ray_n, self.ray_i, T_wc, self.K, **self._summary_kw())
 
     def step(self, T_wc, raw_image=None, rgb_image=None):
         """One frame: preprocess the new depth image, integrate it, render the model.  rgb_image (color=True): the frame's RGB
@@ -586,35 +559,30 @@ _IDENTITY = np.array([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, 0]], np.float32)
 FROM_SENSOR = "the next image of the upload ring"
 
 
-class TrackingPipeline(FramePipeline):
-    """The reference application's loop with pose estimation switched on (main.cpp:200-356): depth pyramid,
-    per-level vertex / normal maps, raycast of the model at the last pose on every level that has ICP
-    iterations, coarse-to-fine projective point-plane ICP (kangaroo_amd/tracking.py around the HIP operator),
-    then SdfFuse at the refined pose when tracking is good."""
+class _TrackingLoop:
+    """The reference application's loop with pose estimation switched on (main.cpp:200-356), written once for TrackingPipeline and
+    TrackingSlabPipeline (a mixin in front of FramePipeline / SlabPipeline): depth pyramid, per-level vertex / normal maps, raycast
+    of the model at the last pose on every level that has ICP iterations, coarse-to-fine projective point-plane ICP, then SdfFuse at
+    the refined pose when tracking is good.  It owns the tracker's state and step(); a class supplies what really differs:
+    _render_levels (how the model is rendered into pyr_*), _refine (where the refinement comes from; default: the host loop of
+    kangaroo_amd/tracking.py around the HIP operator) and _fuse_at (how a pose is integrated)."""
 
     LEVELS = 4
-    USE_FRAME = False   # its frame has the pose estimation between rendering and integration: the operators are issued here
 
-    def __init__(self, ops, dims, boxmin, boxmax, w, h, its=None, icp_c=0.1, max_rmse=0.10, device_icp=False, one_raycast=None, **kw):
-        """device_icp: run the whole refinement loop on the GPU (ops.IcpRefine, one synchronisation per frame) instead
-        of one PoseRefinementProjectiveIcpPointPlane call + host solve per iteration.  one_raycast: render all pyramid
-        levels with one launch (ops.RaycastSdfLevels; default: when the operator set has it).  color=True (see FramePipeline):
-        SdfFuseColor at the tracked pose and colour renderings of every level (ops.RaycastSdfColorLevels, or the per-level calls)."""
+    def _init_tracker(self, its, icp_c, max_rmse, pose_step):
+        """pose_step: update the pose with ops.PoseStep (one host call that also returns the inverse SdfFuse needs) and hand that
+        inverse to _fuse_at"""
         from . import tracking
-        super().__init__(ops, dims, boxmin, boxmax, w, h, **kw)
+        ops, w, h, L = self.ops, self.w, self.h, self.LEVELS
         self.tracking = tracking
-        self.device_icp = bool(device_icp) and hasattr(ops, "IcpRefine")
-        self.one_raycast = hasattr(ops, "RaycastSdfLevels") if one_raycast is None else (bool(one_raycast) and hasattr(ops, "RaycastSdfLevels"))
         self.its = tuple(tracking.DEFAULT_ITS if its is None else its)
-        self.icp_c, self.max_rmse = float(icp_c), float(max_rmse)
-        L = self.LEVELS
+        self.icp_c, self.max_rmse, self._pose_step = float(icp_c), float(max_rmse), bool(pose_step)
         P = ops.Pyramid
         self.kin_d, self.kin_v, self.kin_n = P(w, h, L, "f32"), P(w, h, L, "f32x4"), P(w, h, L, "f32x4")
         # a second set for the NEXT frame's pre-amble (step(..., next_image=...)): enqueued while the pose of this frame is on
         # its way to the host, it must not overwrite the maps SdfFuse is about to read
         self._kin_back = None
         self._prefetched = None   # the image whose pre-amble the back set holds
-        self._bound = {}          # SdfFuseBound per set of maps
         self.pyr_d, self.pyr_i = P(w, h, L, "f32"), P(w, h, L, "f32")
         self.pyr_n, self.pyr_v = P(w, h, L, "f32x4"), P(w, h, L, "f32x4")
         self.K_levels = [scenes.intrinsics_level(self.K, l) for l in range(L)]
@@ -645,6 +613,12 @@ class TrackingPipeline(FramePipeline):
         self.preprocess(image, into=self._kin_back)
         self._prefetched = image
 
+    def _refine(self, next_image):
+        """(T_lp, rmse, tracking_good) of the frame's maps against the rendered model: main.cpp:301-336 on the host, one
+        PoseRefinementProjectiveIcpPointPlane call + solve per iteration"""
+        return self.tracking.refine_pose(self.ops, self.kin_v, self.pyr_v, self.pyr_n, self.K_levels, self.scratch, self.debug, self.its,
+                                         self.icp_c, self.max_rmse)
+
     def step(self, T_wl_init=None, raw_image=None, next_image=None, rgb_image=None):
         """One frame.  The first frame is fused at T_wl_init (identity if None); later frames are tracked
         against the model.  Returns the current T_wl (4x4 float64).
@@ -653,8 +627,9 @@ class TrackingPipeline(FramePipeline):
         refinement its pre-amble -- which does not depend on any pose -- is enqueued behind the refinement, before this thread
         waits for the pose: the device works on it while the thread wakes up instead of idling until SdfFuse arrives.  The
         next step finds its maps ready when it is given the same image object; same images, same poses.
-        rgb_image (color=True): the frame's RGB image (default self.rgb)."""
-        o, tr = self.ops, self.tracking
+        rgb_image (color=True): the frame's RGB image (default self.rgb).
+        TrackingSlabPipeline: next_image and rgb_image are accepted and ignored (no prefetch hook, no colour); follow=, track=, color=
+        and sensor= are refused there, so those branches never run.)"""
         if self.color:
             self._rgb_now = self.rgb if rgb_image is None else rgb_image
         if self.follow is not None and self.frame > 0:   # the previous frame's pose: this frame's is not known yet
@@ -673,6 +648,7 @@ class TrackingPipeline(FramePipeline):
         # (rmse = sqrt(0 / 0): a frame without depth, a model out of view) the application starts over -- T_wl = identity (the world
         # frame restarts at the current camera; T_wl_init if the caller gives one), the volume back to "never observed", the current
         # frame fused -- and the frame then goes on like any other: it is tracked against the model it has just founded.
+        # (On slabs every rank sees the same rmse.)
         recover = self.frame > 0 and not np.isfinite(self.rmse)
         if recover:
             self.T_wl = np.eye(4)
@@ -684,49 +660,62 @@ class TrackingPipeline(FramePipeline):
                 self.T_wl = np.vstack([np.asarray(T_wl_init, np.float64).reshape(3, 4), [0, 0, 0, 1]])
             self._fuse_at(self.T_wl)
         if self.frame > 0:
-            T34 = self.T_wl[:3].astype(np.float32)
-            lv = [l for l in range(self.LEVELS) if self.its[l] > 0]
-
-            def render(kw):
-                if self.color:   # main.cpp:284 on every level, the colour image into pyr_i
-                    outs = [(self.pyr_d[l], self.pyr_n[l], self.pyr_i[l], self.pyr_v[l]) for l in lv]
-                    if self.one_raycast:
-                        o.RaycastSdfColorLevels(outs, self.vol, self.cvol, T34, [self.K_levels[l] for l in lv], self.near, self.far, self.trunc, True, **kw)
-                    else:
-                        for l in lv:
-                            o.RaycastSdfColor(self.pyr_d[l], self.pyr_n[l], self.pyr_i[l], self.vol, self.cvol, T34, self.K_levels[l], self.near,
-                                              self.far, self.trunc, True, **kw)
-                            o.DepthToVbo(self.pyr_v[l], self.pyr_d[l], self.K_levels[l])
-                elif self.one_raycast:   # the per-level RaycastSdf + DepthToVbo calls as one launch: same images, overlapping marches
-                    o.RaycastSdfLevels([(self.pyr_d[l], self.pyr_n[l], self.pyr_i[l], self.pyr_v[l]) for l in lv], self.vol, T34,
-                                       [self.K_levels[l] for l in lv], self.near, self.far, self.trunc, True, **kw)
-                else:
-                    for l in lv:
-                        o.RaycastSdf(self.pyr_d[l], self.pyr_n[l], self.pyr_i[l], self.vol, T34, self.K_levels[l], self.near,
-                                     self.far, self.trunc, True, **kw)
-                        o.DepthToVbo(self.pyr_v[l], self.pyr_d[l], self.K_levels[l])
-            self._timed_raycast(render)
-            if self.device_icp:
-                hook = (lambda: self._prefetch(next_image)) if next_image is not None else None
-                T_lp, self.rmse, _, self.tracking_good = o.IcpRefine(self.kin_v, self.pyr_v, self.pyr_n, self.K_levels, self.its,
-                                                                     self.icp_c, self.max_rmse, self.scratch, self.debug, before_wait=hook)
-            else:
-                T_lp, self.rmse, self.tracking_good = tr.refine_pose(o, self.kin_v, self.pyr_v, self.pyr_n, self.K_levels,
-                                                                     self.scratch, self.debug, self.its, self.icp_c, self.max_rmse)
-            if self.tracking_good:
-                if hasattr(o, "PoseStep") and hasattr(o, "SdfFuseBound") and not self.color:
-                    # the device idles from the pose's arrival to the SdfFuse launch: the update in one host call, the launch with
-                    # its arguments bound beforehand
-                    self.T_wl, T_cw = o.PoseStep(self.T_wl, T_lp)
-                    self._fuse_bound(T_cw)
-                else:
-                    self.T_wl = self.T_wl @ tr.se3_inv(T_lp)
-                    self._fuse_at(self.T_wl)
+            self._render_levels([l for l in range(self.LEVELS) if self.its[l] > 0], self.T_wl[:3].astype(np.float32))
+            T_lp, self.rmse, self.tracking_good = self._refine(next_image)
+            if self.tracking_good and self._pose_step:
+                # the device idles from the pose's arrival to the SdfFuse launch: the update in one host call (kfx_pose_step; the
+                # same arithmetic as the lines below: the same poses, bit for bit)
+                self.T_wl, T_cw = self.ops.PoseStep(self.T_wl, T_lp)
+                self._fuse_at(self.T_wl, T_cw)
+            elif self.tracking_good:
+                self.T_wl = self.T_wl @ self.tracking.se3_inv(T_lp)
+                self._fuse_at(self.T_wl)
         self.frame += 1
         self.frames_done += 1
         if cal:
             self._policy_after()
         return self.T_wl
+
+
+class TrackingPipeline(_TrackingLoop, FramePipeline):
+    """The tracking loop (_TrackingLoop) on one volume."""
+
+    USE_FRAME = False   # its frame has the pose estimation between rendering and integration: the operators are issued here
+
+    def __init__(self, ops, dims, boxmin, boxmax, w, h, its=None, icp_c=0.1, max_rmse=0.10, device_icp=False, one_raycast=None, **kw):
+        """device_icp: run the whole refinement loop on the GPU (ops.IcpRefine, one synchronisation per frame) instead
+        of one PoseRefinementProjectiveIcpPointPlane call + host solve per iteration.  one_raycast: render all pyramid
+        levels with one launch (ops.RaycastSdfLevels; default: when the operator set has it).  color=True (see FramePipeline):
+        SdfFuseColor at the tracked pose and colour renderings of every level (ops.RaycastSdfColorLevels, or the per-level calls)."""
+        super().__init__(ops, dims, boxmin, boxmax, w, h, **kw)
+        self.device_icp = bool(device_icp) and hasattr(ops, "IcpRefine")
+        self.one_raycast = hasattr(ops, "RaycastSdfLevels") if one_raycast is None else (bool(one_raycast) and hasattr(ops, "RaycastSdfLevels"))
+        self._bound = {}          # SdfFuseBound per set of maps
+        # (PoseStep's inverse goes to the SdfFuse call whose other arguments are bound beforehand; the colour fuse has no such call)
+        self._init_tracker(its, icp_c, max_rmse, pose_step=hasattr(ops, "PoseStep") and hasattr(ops, "SdfFuseBound") and not self.color)
+
+    def _render_levels(self, lv, T34):
+        """RaycastSdf + DepthToVbo of the levels lv (main.cpp:280-288; color=True: main.cpp:284, the colour image into pyr_i): one launch
+        -- same images, overlapping marches -- or the per-level calls"""
+        o, kw = self.ops, self._summary_kw()
+        if not self.one_raycast:
+            for l in lv:
+                self._march(self.pyr_d[l], self.pyr_n[l], self.pyr_i[l], T34, self.K_levels[l], **kw)
+                o.DepthToVbo(self.pyr_v[l], self.pyr_d[l], self.K_levels[l])
+            return
+        outs, Ks = [(self.pyr_d[l], self.pyr_n[l], self.pyr_i[l], self.pyr_v[l]) for l in lv], [self.K_levels[l] for l in lv]
+        if self.color:
+            o.RaycastSdfColorLevels(outs, self.vol, self.cvol, T34, Ks, self.near, self.far, self.trunc, True, **kw)
+        else:
+            o.RaycastSdfLevels(outs, self.vol, T34, Ks, self.near, self.far, self.trunc, True, **kw)
+
+    def _refine(self, next_image):
+        if not self.device_icp:
+            return super()._refine(next_image)
+        hook = (lambda: self._prefetch(next_image)) if next_image is not None else None
+        T_lp, rmse, _, good = self.ops.IcpRefine(self.kin_v, self.pyr_v, self.pyr_n, self.K_levels, self.its, self.icp_c, self.max_rmse,
+                                                 self.scratch, self.debug, before_wait=hook)
+        return T_lp, rmse, good
 
     def shift_volume(self, shift):
         super().shift_volume(shift)
@@ -742,23 +731,12 @@ class TrackingPipeline(FramePipeline):
                                                          summary=self.summary if self.track else None)
         b(T_cw)
 
-    def _fuse_at(self, T_wl):
-        T_cw = self.tracking.se3_inv(T_wl)[:3].astype(np.float32)
-        if self.color:
-            self._fuse_color(self.kin_d[0], self.kin_n[0], T_cw)
-            return
-        self._timed_fuse(lambda kw: self.ops.SdfFuse(self.vol, self.kin_d[0], self.kin_n[0], T_cw, self.K, self.trunc, self.max_w,
-                                                     self.mincostheta, **kw))
-
-    def _reset_model(self):
-        """SdfReset(vol, NaN) (main.cpp:229), the brick summary set to match."""
-        if self.track:
-            self.ops.SdfReset(self.vol, float("nan"), summary=self.summary)
+    def _fuse_at(self, T_wl, T_cw=None):
+        """T_cw: PoseStep's inverse of T_wl (the bound call); None: inverted here in float64 (main.cpp:345-356)"""
+        if T_cw is not None:
+            self._fuse_bound(T_cw)
         else:
-            self.ops.SdfReset(self.vol, float("nan"))
-        if self.color:
-            self.ops.ColorReset(self.cvol)
-        self._forget_spilled()
+            self._integrate(self.kin_d[0], self.kin_n[0], self.tracking.se3_inv(T_wl)[:3].astype(np.float32))
 
 
 def slab_range(d, rank, world):
@@ -1074,14 +1052,11 @@ class SlabPipeline(FramePipeline):
             self.raycast_exact_allreduce(T_wc, d, n, i, K)
             return
         self.wait_composite()   # the previous frame's merge still reads these images
-        if self.color:   # each rank renders its local view in colour; the merge carries img as it carries the shade
-            self.ops.RaycastSdfColor(d, n, i, self.vol, self.cvol, T_wc, K, self.near, self.far, self.trunc, True)
-        else:
-            self.ops.RaycastSdf(d, n, i, self.vol, T_wc, K, self.near, self.far, self.trunc, True)
+        self._march(d, n, i, T_wc, K)   # (color=True: each rank renders its local view in colour; the merge carries img as it carries the shade)
         if self.world > 1:
             if self.overlap and (self.halo == "exchange" or self.inputs == "broadcast"):
                 raise RuntimeError("SlabPipeline: overlapped merge with halo='exchange' or inputs='broadcast' (see __init__)")
-            if self.overlap and hasattr(self.ops, "CompositePack"):
+            if self.overlap:
                 import torch
                 if self._side is None:
                     self._side = torch.cuda.Stream()
@@ -1121,30 +1096,8 @@ class SlabPipeline(FramePipeline):
         else:
             for (d, n, i), K in zip(outputs, K_levels):
                 self.ops.RaycastSdf(d, n, i, self.vol, T_wc, K, self.near, self.far, self.trunc, True)
-        if self.world == 1:
-            return
-        if self.merge == "direct" and hasattr(self.ops, "CompositeStripsPack"):
-            self.composite_direct_levels(outputs)
-            return
-        if not hasattr(self.ops, "CompositePack"):
-            for d, n, i in outputs:
-                self.composite(d, n, i)
-            return
-        import torch
-        sizes = [d.w * d.h for d, _, _ in outputs]
-        total = sum(sizes)
-        key = self._scratch("keys", (total,), torch.int64, outputs[0][0])
-        payload = self._scratch("payloads", (total * 4,), torch.float32, outputs[0][0])
-        offs = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
-        parts = [(key[offs[k]:offs[k + 1]], payload[4 * offs[k]:4 * offs[k + 1]]) for k in range(len(outputs))]
-        for (d, n, i), (kk, _) in zip(outputs, parts):
-            self.ops.CompositePack(d, n, i, kk, self.rank)
-        self.dist.all_reduce(key, op=self.dist.ReduceOp.MIN)
-        for (d, n, i), (kk, pp) in zip(outputs, parts):
-            self.ops.CompositeSelect(d, n, i, kk, pp, self.rank)
-        self._sum_payload(payload)
-        for (d, n, i), (kk, pp) in zip(outputs, parts):
-            self.ops.CompositeUnpack(d, n, i, kk, pp)
+        if self.world > 1:
+            self.composite_levels(outputs)
 
     def _sum_payload(self, payload):
         """The winners' normals / shade, summed over the ranks: on every rank, or (images = "root") on rank 0 only."""
@@ -1162,6 +1115,16 @@ class SlabPipeline(FramePipeline):
             cache[key] = torch.empty(shape, dtype=dtype, device=like.tensor().device)
         return cache[key]
 
+    def _exact_setup(self, d, n, i, K):
+        """What both exact marches start from: the images and intrinsics (default: the frame's), the slab tuple of the operators, the
+        state scratch (9 planes) and its march planes as integers"""
+        import torch
+        d, n, i = (self.ray_d, self.ray_n, self.ray_i) if d is None else (d, n, i)
+        K = self.K if K is None else K
+        slab = (self.dims[2], self.s0, float(self.full_boxmin[2]), float(self.full_boxmax[2]))
+        st = self._scratch("state", (9, d.h, d.w), torch.float32, d)
+        return d, n, i, K, d.w, d.h, slab, st, st[0:5].view(torch.int32)   # (march: contiguous planes 0..4)
+
     def raycast_exact(self, T_wc, d=None, n=None, i=None, K=None):
         """The march state travels with the ray (the exact variant): world + 1 stages of kfx_raycast_sdf_slab
         -- a rank advances the rays whose current sample lies in the planes it owns --, between them the march planes
@@ -1174,13 +1137,7 @@ class SlabPipeline(FramePipeline):
         shade equal RaycastSdf on the whole volume bit for bit."""
         import torch
         dist, o = self.dist, self.ops
-        d, n, i = (self.ray_d, self.ray_n, self.ray_i) if d is None else (d, n, i)
-        K = self.K if K is None else K
-        w, h = d.w, d.h
-        D = self.dims[2]
-        slab = (D, self.s0, float(self.full_boxmin[2]), float(self.full_boxmax[2]))
-        st = self._scratch("state", (9, h, w), torch.float32, d)
-        march = st[0:5].view(torch.int32)   # contiguous planes 0..4
+        d, n, i, K, w, h, slab, st, march = self._exact_setup(d, n, i, K)
         stages = self.world + 1 if self.world > 1 else 1
         fin = torch.zeros((h, w), dtype=torch.bool, device=st.device)
         from_lo = self._scratch("from_lo", (5, h, w), torch.int32, d) if self.rank > 0 else None
@@ -1231,13 +1188,7 @@ class SlabPipeline(FramePipeline):
         round (at most world + 2 of them).  The normals (planes 5-8, written by one rank per pixel) are merged once at the end."""
         import torch
         dist, o = self.dist, self.ops
-        d, n, i = (self.ray_d, self.ray_n, self.ray_i) if d is None else (d, n, i)
-        K = self.K if K is None else K
-        w, h = d.w, d.h
-        D = self.dims[2]
-        slab = (D, self.s0, float(self.full_boxmin[2]), float(self.full_boxmax[2]))
-        st = self._scratch("state", (9, h, w), torch.float32, d)
-        march = st[0:5].view(torch.int32)   # contiguous planes 0..4
+        d, n, i, K, w, h, slab, st, march = self._exact_setup(d, n, i, K)
         rounds = 0
         while True:
             o.RaycastSdfSlab(st, rounds == 0, self.vol, slab, self.z0, self.z1, w, h, T_wc, K,
@@ -1258,51 +1209,53 @@ class SlabPipeline(FramePipeline):
         self.rounds = rounds
         o.RaycastStateToImages(d, n, i, st)
 
+    def _gloo_table(self, mine):
+        """gloo with device tensors (the tests' ranks sharing one GPU): its point-to-point path takes ~0.1 s per message, its
+        all-reduce does not -- every rank's `mine` summed as integers into one table, (world,) + mine's shape (bits survive)"""
+        import torch
+        table = torch.zeros((self.world,) + tuple(mine.shape), dtype=torch.int32, device=mine.device)
+        table[self.rank] = mine.view(torch.int32)
+        self.dist.all_reduce(table)
+        return table.view(torch.float32)
+
+    def _gloo_ring(self, send_to, recv_from):
+        """gloo, host tensors (the CPU tests): one batch in which this rank sends send_to(r) to every other rank r and receives
+        into recv_from(r) from it (None: nothing to send / to receive)"""
+        dist, ops = self.dist, []
+        for k in range(1, self.world):
+            to, frm = (self.rank + k) % self.world, (self.rank - k) % self.world
+            out, into = send_to(to), recv_from(frm)
+            if out is not None:
+                ops.append(dist.P2POp(dist.isend, out, to))
+            if into is not None:
+                ops.append(dist.P2POp(dist.irecv, into, frm))
+        self._p2p(ops)
+
     def _all_to_all(self, recv, send):
         """recv[r] = rank r's send[self.rank] (dense tensors of shape (world, ...))."""
-        dist = self.dist
-        if dist.get_backend() == "nccl":
-            dist.all_to_all_single(recv, send)   # RCCL: one grouped send / recv per peer, every link of the mesh at once
-            return
-        if send.is_cuda:   # gloo with device tensors (the tests' ranks sharing one GPU): its point-to-point path takes ~0.1 s per
-            import torch   # message, its all-reduce does not -- every rank's strips summed as integers into one table (bits survive)
-            table = torch.zeros((self.world,) + tuple(send.shape), dtype=torch.int32, device=send.device)
-            table[self.rank] = send.view(torch.int32)
-            dist.all_reduce(table)
-            recv.copy_(table[:, self.rank].view(torch.float32))
-            return
-        recv[self.rank].copy_(send[self.rank])
-        ops = []
-        for k in range(1, self.world):   # gloo, host tensors (the CPU tests)
-            to, frm = (self.rank + k) % self.world, (self.rank - k) % self.world
-            ops += [dist.P2POp(dist.isend, send[to], to), dist.P2POp(dist.irecv, recv[frm], frm)]
-        self._p2p(ops)
+        if self.dist.get_backend() == "nccl":
+            self.dist.all_to_all_single(recv, send)   # RCCL: one grouped send / recv per peer, every link of the mesh at once
+        elif send.is_cuda:
+            recv.copy_(self._gloo_table(send)[:, self.rank])
+        else:
+            recv[self.rank].copy_(send[self.rank])
+            self._gloo_ring(lambda to: send[to], lambda frm: recv[frm])
 
     def _gather_strips(self, full, part):
         """full[r] = rank r's part: on every rank, or (images = "root") on rank 0 only."""
-        dist = self.dist
+        dist, root = self.dist, self.images == "root"
         if dist.get_backend() == "nccl":
-            if self.images == "root":
+            if root:
                 dist.gather(part, [full[r] for r in range(self.world)] if self.rank == 0 else None, dst=0)
             else:
                 dist.all_gather_into_tensor(full, part)
-            return
-        if part.is_cuda:   # (gloo with device tensors: as in _all_to_all; every rank ends up with the strips)
-            import torch
-            table = torch.zeros(tuple(full.shape), dtype=torch.int32, device=part.device)
-            table[self.rank] = part.view(torch.int32).reshape(table[self.rank].shape)
-            dist.all_reduce(table)
-            full.copy_(table.view(torch.float32))
-            return
-        full[self.rank].copy_(part)
-        ops = []
-        for k in range(1, self.world):
-            to, frm = (self.rank + k) % self.world, (self.rank - k) % self.world
-            if self.images != "root" or to == 0:
-                ops.append(dist.P2POp(dist.isend, part, to))
-            if self.images != "root" or self.rank == 0:
-                ops.append(dist.P2POp(dist.irecv, full[frm], frm))
-        self._p2p(ops)
+        elif part.is_cuda:   # (every rank ends up with the strips)
+            full.copy_(self._gloo_table(part.reshape(full[self.rank].shape)))
+        else:
+            full[self.rank].copy_(part)
+            sends = (lambda to: part if to == 0 else None) if root else (lambda to: part)   # (images = "root": to rank 0 only ...
+            recvs = (lambda frm: None) if root and self.rank != 0 else (lambda frm: full[frm])   # ... and only rank 0 receives)
+            self._gloo_ring(sends, recvs)
 
     def composite_direct_levels(self, outputs):
         """The direct-send merge of several images at once (pyramid levels: outputs = [(d, n, i), ...]): a rank's strips of all
@@ -1329,95 +1282,49 @@ class SlabPipeline(FramePipeline):
             for (d, n, i), off in zip(outputs, offs):
                 o.CompositeStripsUnpack(d, n, i, recv, W, offset=off, rank_stride=total)
 
-    def composite_direct(self, d, n, i):
-        """The direct-send merge (include/kfx.h, kfx_composite_strips_*): strips to their owners, nearest hit per pixel, strips
-        back.  Operator sets without the kernels (the oracle-backed CPU stand-in of the tests) use the tensor expressions."""
-        if hasattr(self.ops, "CompositeStripsPack"):
-            self.composite_direct_levels([(d, n, i)])
-            return
+    def composite_allreduce_levels(self, outputs, scratch=("keys", "payloads")):
+        """The all-reduce merge of several images at once: key = depth bits (positive floats order like ints) in the high word, rank in
+        the low byte; misses use +inf.  One MIN all-reduce picks the winners, one SUM all-reduce (images = "root": a reduce, only rank
+        0's payload is the sum) broadcasts their normal / shade (four floats per pixel; the depth and the hit flag travel in the key).
+        The keys and payloads of all images lie side by side, so the whole set costs ONE pair of collectives.  scratch: the names
+        of the key / payload scratch (composite(), whose overlapped merge runs on the side stream, keeps its own pair)."""
         import torch
-        W = self.world
-        w, h = d.w, d.h
-        planes = 5
-        dt, nt, it = d.tensor(), n.tensor(), i.tensor()
-        P = w * h
-        S = ((P + W - 1) // W + 63) // 64 * 64   # kfx_composite_strip_pixels
-        hit = torch.isfinite(dt)
-        img = torch.zeros((planes, W * S), dtype=torch.float32, device=dt.device)
-        img[0] = float("inf")
-        img[0, :P] = torch.where(hit, dt, torch.full_like(dt, float("inf"))).reshape(-1)
-        for c in range(3):
-            img[1 + c, :P] = torch.where(hit, nt[..., c], torch.zeros_like(dt)).reshape(-1)
-        img[4, :P] = torch.where(hit, it, torch.zeros_like(it)).reshape(-1)
-        send = img.reshape(planes, W, S).permute(1, 0, 2).contiguous()
-        recv = torch.empty_like(send)
-        self._all_to_all(recv, send)
-        bits = recv[:, 0].contiguous().view(torch.int32).to(torch.int64)
-        win = torch.argmin((bits << 8) | torch.arange(W, device=dt.device).reshape(W, 1), dim=0)
-        merged = torch.gather(recv, 0, win.reshape(1, 1, S).expand(1, planes, S))[0].contiguous()
-        full = torch.empty_like(send)
-        self._gather_strips(full, merged)
-        if self.images == "root" and self.rank != 0:
-            return
-        out = full.permute(1, 0, 2).reshape(planes, W * S)[:, :P]
-        any_hit = torch.isfinite(out[0]).reshape(h, w)
-        dt.copy_(torch.where(any_hit, out[0].reshape(h, w), torch.full_like(dt, float("nan"))))
-        for c in range(3):
-            nt[..., c].copy_(out[1 + c].reshape(h, w))
-        nt[..., 3].copy_(any_hit.to(torch.float32))
-        it.copy_(out[4].reshape(h, w))
+        sizes = [d.w * d.h for d, _, _ in outputs]
+        total = sum(sizes)
+        key = self._scratch(scratch[0], (total,), torch.int64, outputs[0][0])
+        payload = self._scratch(scratch[1], (total * 4,), torch.float32, outputs[0][0])
+        offs = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
+        parts = [(key[offs[k]:offs[k + 1]], payload[4 * offs[k]:4 * offs[k + 1]]) for k in range(len(outputs))]
+        for (d, n, i), (kk, _) in zip(outputs, parts):
+            self.ops.CompositePack(d, n, i, kk, self.rank)
+        self.dist.all_reduce(key, op=self.dist.ReduceOp.MIN)
+        for (d, n, i), (kk, pp) in zip(outputs, parts):
+            self.ops.CompositeSelect(d, n, i, kk, pp, self.rank)
+        self._sum_payload(payload)
+        for (d, n, i), (kk, pp) in zip(outputs, parts):
+            self.ops.CompositeUnpack(d, n, i, kk, pp)
+
+    def composite_levels(self, outputs, **kw):
+        """Nearest hit over all slabs for each of outputs = [(d, n, i), ...], by the pipeline's merge: same winner per pixel, same
+        images either way.  The per-pixel glue is the operator set's fused kernels (kfx_composite_*, kfx_composite_strips_*)."""
+        if self.merge == "direct":
+            self.composite_direct_levels(outputs)
+        else:
+            self.composite_allreduce_levels(outputs, **kw)
 
     def composite(self, d=None, n=None, i=None):
-        """Nearest hit over all slabs (merge = "direct": composite_direct above).  key = depth bits (positive floats order like ints) in the
-        high word, rank in the low byte; misses use +inf.  One MIN all-reduce picks the winner,
-        one SUM all-reduce broadcasts its normal / shade (four floats per pixel; the depth and the hit flag travel in the key).  With the HIP
-        operator set the per-pixel glue is three fused kernels; operator sets without them (the
-        oracle-backed CPU stand-in of the tests) use the equivalent tensor expressions below."""
-        import torch
-        dist = self.dist
-        d, n, i = (self.ray_d, self.ray_n, self.ray_i) if d is None else (d, n, i)
-        w, h = d.w, d.h
-        if self.merge == "direct":
-            self.composite_direct(d, n, i)
-            return
-        if hasattr(self.ops, "CompositePack"):
-            key = self._scratch("key", (w * h,), torch.int64, d)
-            payload = self._scratch("payload", (w * h * 4,), torch.float32, d)
-            self.ops.CompositePack(d, n, i, key, self.rank)
-            dist.all_reduce(key, op=dist.ReduceOp.MIN)
-            self.ops.CompositeSelect(d, n, i, key, payload, self.rank)
-            self._sum_payload(payload)
-            self.ops.CompositeUnpack(d, n, i, key, payload)   # (images = "root": only rank 0's payload is the sum)
-            return
-        dt, nt, it = d.tensor(), n.tensor(), i.tensor()
-        hit = torch.isfinite(dt)
-        bits = torch.where(hit, dt, torch.full_like(dt, float("inf"))).contiguous().view(torch.int32).to(torch.int64)
-        key = (bits << 8) | self.rank
-        dist.all_reduce(key, op=dist.ReduceOp.MIN)
-        mine = hit & ((key & 0xFF) == self.rank) & ((key >> 8) == bits)
-        payload = torch.zeros((h, w, 4), dtype=torch.float32, device=dt.device)   # {n.x, n.y, n.z, shade}; n.w = hit ? 1 : 0 comes out of the key
-        payload[..., 0:3] = torch.where(mine.unsqueeze(-1), nt[..., 0:3], torch.zeros_like(nt[..., 0:3]))
-        payload[..., 3] = torch.where(mine, it, torch.zeros_like(it))
-        self._sum_payload(payload)
-        win_bits = (key >> 8).to(torch.int32)
-        any_hit = win_bits < 0x7F800000
-        dt.copy_(torch.where(any_hit, win_bits.view(torch.float32), torch.full_like(dt, float("nan"))))
-        nt[..., 0:3].copy_(payload[..., 0:3])
-        nt[..., 3].copy_(any_hit.to(torch.float32))
-        it.copy_(payload[..., 3])
+        """composite_levels of one image (default: the frame's)"""
+        self.composite_levels([(self.ray_d, self.ray_n, self.ray_i) if d is None else (d, n, i)], scratch=("key", "payload"))
 
 
-class TrackingSlabPipeline(SlabPipeline):
-    """Tracked KinectFusion on Z-slabs: the loop of TrackingPipeline with the model spread over the ranks.  The
-    raycast of every pyramid level is merged across ranks (raycast_into), after which all ranks hold the same model
+class TrackingSlabPipeline(_TrackingLoop, SlabPipeline):
+    """Tracked KinectFusion on Z-slabs: the tracking loop (_TrackingLoop) with the model spread over the ranks.  The
+    raycast of every pyramid level is merged across ranks (raycast_levels_into), after which all ranks hold the same model
     images; the ICP normal equations are image-space work of < 0.1 ms and are evaluated redundantly on every rank
     (deterministic: every rank derives the same pose without a broadcast); SdfFuse then integrates each rank's slab.
     With raycast="exact" the poses and the fused slabs equal the single-GPU TrackingPipeline bit for bit."""
 
-    LEVELS = TrackingPipeline.LEVELS
-
     def __init__(self, ops, dist, dims, boxmin, boxmax, w, h, its=None, icp_c=0.1, max_rmse=0.10, **kw):
-        from . import tracking
         if kw.get("color"):
             raise ValueError("TrackingSlabPipeline: color=True is not built (tracked colour slabs: the tracker fuses its pyramids' level 0 and renders "
                              "pyramid levels, the colour slab path fuses and renders the frame's own images)")
@@ -1431,69 +1338,28 @@ class TrackingSlabPipeline(SlabPipeline):
             raise ValueError("TrackingSlabPipeline: driver='c' is for known-pose streams (kfx_slab_frame_step integrates the images it was created "
                              "with, not the tracker's pyramids); use driver='python'")
         super().__init__(ops, dist, dims, boxmin, boxmax, w, h, **kw)
-        self.tracking = tracking
-        self.its = tuple(tracking.DEFAULT_ITS if its is None else its)
-        self.icp_c, self.max_rmse = float(icp_c), float(max_rmse)
-        L, P = self.LEVELS, ops.Pyramid
-        self.kin_d, self.kin_v, self.kin_n = P(w, h, L, "f32"), P(w, h, L, "f32x4"), P(w, h, L, "f32x4")
-        self.pyr_d, self.pyr_i = P(w, h, L, "f32"), P(w, h, L, "f32")
-        self.pyr_n, self.pyr_v = P(w, h, L, "f32x4"), P(w, h, L, "f32x4")
-        self.K_levels = [scenes.intrinsics_level(self.K, l) for l in range(L)]
-        self.debug = ops.Image(w, h, "f32x4")
-        self.scratch = ops.Image(w * 232, h, "u8")
-        self.T_wl = np.eye(4)
-        self.frame = 0
-        self.rmse, self.tracking_good = 0.0, True
-        self.resets = 0
+        self._init_tracker(its, icp_c, max_rmse, pose_step=hasattr(ops, "PoseStep"))
 
-    preprocess = TrackingPipeline.preprocess
+    def _render_levels(self, lv, T34):
+        self.raycast_levels_into([(self.pyr_d[l], self.pyr_n[l], self.pyr_i[l]) for l in lv], [self.K_levels[l] for l in lv], T34)
+        for l in lv:
+            self.ops.DepthToVbo(self.pyr_v[l], self.pyr_d[l], self.K_levels[l])
 
-    def step(self, T_wl_init=None, raw_image=None):
-        o, tr = self.ops, self.tracking
-        self.preprocess(raw_image)
-        recover = self.frame > 0 and not np.isfinite(self.rmse)   # main.cpp:223-242, as TrackingPipeline.step (every rank sees the same rmse)
-        if recover:
-            self.T_wl = np.eye(4)
-            self.ops.SdfReset(self.vol, float("nan"))
-            self.rmse, self.tracking_good = 0.0, True
-            self.resets += 1
-        if self.frame == 0 or recover:
-            if T_wl_init is not None:
-                self.T_wl = np.vstack([np.asarray(T_wl_init, np.float64).reshape(3, 4), [0, 0, 0, 1]])
-            self._fuse_at(self.T_wl)
-        if self.frame > 0:
-            T34 = self.T_wl[:3].astype(np.float32)
-            lv = [l for l in range(self.LEVELS) if self.its[l] > 0]
-            self.raycast_levels_into([(self.pyr_d[l], self.pyr_n[l], self.pyr_i[l]) for l in lv], [self.K_levels[l] for l in lv], T34)
-            for l in lv:
-                o.DepthToVbo(self.pyr_v[l], self.pyr_d[l], self.K_levels[l])
-            if self.images == "root" and self.world > 1:
-                # only rank 0 holds the merged model images: it solves, the others receive the pose (and the verdict)
-                import torch
-                msg = torch.zeros(18, dtype=torch.float64)
-                if self.rank == 0:
-                    T_lp, self.rmse, self.tracking_good = tr.refine_pose(o, self.kin_v, self.pyr_v, self.pyr_n, self.K_levels,
-                                                                         self.scratch, self.debug, self.its, self.icp_c, self.max_rmse)
-                    msg[:16] = torch.from_numpy(np.asarray(T_lp, np.float64).reshape(16))
-                    msg[16], msg[17] = float(self.rmse), 1.0 if self.tracking_good else 0.0
-                if self.dist.get_backend() == "nccl":
-                    msg = msg.to(self.pyr_d[0].tensor().device)
-                self.dist.broadcast(msg, src=0)
-                msg = msg.cpu()
-                T_lp = msg[:16].numpy().reshape(4, 4).copy()
-                self.rmse, self.tracking_good = float(msg[16]), bool(msg[17] != 0)
-            else:
-                T_lp, self.rmse, self.tracking_good = tr.refine_pose(o, self.kin_v, self.pyr_v, self.pyr_n, self.K_levels,
-                                                                     self.scratch, self.debug, self.its, self.icp_c, self.max_rmse)
-            if self.tracking_good:
-                if hasattr(o, "PoseStep"):   # the same host arithmetic as TrackingPipeline.step (kfx_pose_step): the same poses, bit for bit
-                    self.T_wl, T_cw = o.PoseStep(self.T_wl, T_lp)
-                    self._fuse_at(self.T_wl, T_cw)
-                else:
-                    self.T_wl = self.T_wl @ tr.se3_inv(T_lp)
-                    self._fuse_at(self.T_wl)
-        self.frame += 1
-        return self.T_wl
+    def _refine(self, next_image):
+        if self.images != "root" or self.world == 1:
+            return super()._refine(next_image)
+        # only rank 0 holds the merged model images: it solves, the others receive the pose (and the verdict)
+        import torch
+        msg = torch.zeros(18, dtype=torch.float64)
+        if self.rank == 0:
+            T_lp, rmse, good = super()._refine(next_image)
+            msg[:16] = torch.from_numpy(np.asarray(T_lp, np.float64).reshape(16))
+            msg[16], msg[17] = float(rmse), 1.0 if good else 0.0
+        if self.dist.get_backend() == "nccl":
+            msg = msg.to(self.pyr_d[0].tensor().device)
+        self.dist.broadcast(msg, src=0)
+        msg = msg.cpu()
+        return msg[:16].numpy().reshape(4, 4).copy(), float(msg[16]), bool(msg[17] != 0)
 
     def _fuse_at(self, T_wl, T_cw=None):
         # SlabPipeline.fuse integrates self.filtered / self.normals at T_wc; point them at pyramid level 0

@@ -144,3 +144,89 @@ def BoxHalfIgnoreInvalid(out, inp):
 def BoxReduceIgnoreInvalid(pyramid):
     for l in range(1, len(pyramid)):
         BoxHalfIgnoreInvalid(pyramid[l], pyramid[l - 1])
+
+
+# -- the merges of the per-slab images (kangaroo_amd.roo's Composite* kernels as tensor expressions: same signatures, same layouts) --
+def _inf_where_miss(dt):
+    return torch.where(torch.isfinite(dt), dt, torch.full_like(dt, float("inf")))
+
+
+def CompositePack(depth, norm, img, key, rank):
+    """key (int64, w*h) = (depth bits << 8) | rank -- positive floats order like ints --, +inf for misses"""
+    bits = _inf_where_miss(depth.tensor()).contiguous().view(torch.int32).to(torch.int64)
+    key.copy_(((bits << 8) | rank).reshape(-1))
+
+
+def CompositeSelect(depth, norm, img, key, payload, rank):
+    """payload (float32, w*h*4) = {n.x, n.y, n.z, shade} where this rank holds the winning hit, zero elsewhere; n.w = hit ? 1 : 0
+    comes out of the key"""
+    dt, nt, it = depth.tensor(), norm.tensor(), img.tensor()
+    bits = _inf_where_miss(dt).contiguous().view(torch.int32).to(torch.int64)
+    k = key.reshape(dt.shape)
+    mine = torch.isfinite(dt) & ((k & 0xFF) == rank) & ((k >> 8) == bits)
+    p = payload.reshape(dt.shape + (4,))
+    p[..., 0:3] = torch.where(mine.unsqueeze(-1), nt[..., 0:3], torch.zeros_like(nt[..., 0:3]))
+    p[..., 3] = torch.where(mine, it, torch.zeros_like(it))
+
+
+def CompositeUnpack(depth, norm, img, key, payload):
+    dt, nt, it = depth.tensor(), norm.tensor(), img.tensor()
+    win_bits = (key.reshape(dt.shape) >> 8).to(torch.int32)
+    any_hit = win_bits < 0x7F800000
+    p = payload.reshape(dt.shape + (4,))
+    dt.copy_(torch.where(any_hit, win_bits.view(torch.float32), torch.full_like(dt, float("nan"))))
+    nt[..., 0:3].copy_(p[..., 0:3])
+    nt[..., 3].copy_(any_hit.to(torch.float32))
+    it.copy_(p[..., 3])
+
+
+STRIP_PLANES = 5   # depth (+inf: miss), n.x, n.y, n.z, shade
+
+
+def CompositeStripPixels(w, h, world):
+    """pixels per strip of the direct-send merge (kfx_composite_strip_pixels: the last strip is padded)"""
+    return ((w * h + world - 1) // world + 63) // 64 * 64
+
+
+def _strips(t, S, world, offset, rank_stride):
+    """the views (5, S) of the world strips in the float tensor t: strip j's planes start at float offset + j * rank_stride
+    (rank_stride 0: dense, world x 5 x S)"""
+    flat, stride = t.reshape(-1), rank_stride or STRIP_PLANES * S
+    return [flat[offset + j * stride: offset + j * stride + STRIP_PLANES * S].view(STRIP_PLANES, S) for j in range(world)]
+
+
+def CompositeStripsPack(depth, norm, img, send, world, offset=0, rank_stride=0):
+    dt, nt, it = depth.tensor(), norm.tensor(), img.tensor()
+    P, S = depth.w * depth.h, CompositeStripPixels(depth.w, depth.h, world)
+    hit = torch.isfinite(dt)
+    planes = torch.zeros((STRIP_PLANES, world * S), dtype=torch.float32)
+    planes[0] = float("inf")
+    planes[0, :P] = _inf_where_miss(dt).reshape(-1)
+    for c in range(3):
+        planes[1 + c, :P] = torch.where(hit, nt[..., c], torch.zeros_like(dt)).reshape(-1)
+    planes[4, :P] = torch.where(hit, it, torch.zeros_like(it)).reshape(-1)
+    for j, strip in enumerate(_strips(send, S, world, offset, rank_stride)):
+        strip.copy_(planes[:, j * S:(j + 1) * S])
+
+
+def CompositeStripsMerge(recv, merged, strip_pixels, world, offset=0, rank_stride=0, merged_offset=0):
+    """merged (5 x S at float merged_offset) = per pixel the nearest of the world copies in recv, the lowest rank among equals"""
+    S = strip_pixels
+    copies = torch.stack(_strips(recv, S, world, offset, rank_stride))
+    bits = copies[:, 0].contiguous().view(torch.int32).to(torch.int64)
+    win = torch.argmin((bits << 8) | torch.arange(world).reshape(world, 1), dim=0)
+    out = torch.gather(copies, 0, win.reshape(1, 1, S).expand(1, STRIP_PLANES, S))[0]
+    merged.reshape(-1)[merged_offset:merged_offset + STRIP_PLANES * S].view(STRIP_PLANES, S).copy_(out)
+
+
+def CompositeStripsUnpack(depth, norm, img, strips, world, offset=0, rank_stride=0):
+    dt, nt, it = depth.tensor(), norm.tensor(), img.tensor()
+    w, h = depth.w, depth.h
+    S = CompositeStripPixels(w, h, world)
+    out = torch.cat(_strips(strips, S, world, offset, rank_stride), dim=1)[:, :w * h]
+    any_hit = torch.isfinite(out[0]).reshape(h, w)
+    dt.copy_(torch.where(any_hit, out[0].reshape(h, w), torch.full_like(dt, float("nan"))))
+    for c in range(3):
+        nt[..., c].copy_(out[1 + c].reshape(h, w))
+    nt[..., 3].copy_(any_hit.to(torch.float32))
+    it.copy_(out[4].reshape(h, w))
