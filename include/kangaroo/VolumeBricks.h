@@ -24,6 +24,7 @@
 #include <kangaroo/cu_raycast.h>
 #include <kfx_bricks.h>
 #include <kfx_mesh_bricks.h>
+#include <kfx_mesh_bricks_index.h>
 #include <kfx_raycast_bricks.h>
 #include <kfx_brick_pool.h>
 
@@ -124,6 +125,7 @@ inline void BrickPoolGather(const void* pool, size_t pool_bytes, size_t capacity
 //   const kfx_volume frame = roo::BrickFrame(w, h, d, boxmin, boxmax);
 //   roo::SaveMeshBricks("world", frame, KFX_CELL_F32, ids.ptr, cells.ptr, n);                         // -> world.ply
 //   roo::SaveMeshBricks("world", frame, KFX_CELL_F32, ids.ptr, cells.ptr, n, cids.ptr, ccells.ptr, nc);   // with colours
+//   roo::SaveMeshBricksIndexed("world", frame, KFX_CELL_F32, ids.ptr, cells.ptr, n);                  // one vertex per lattice edge, a face list
 
 // a frame: only the dimensions and the box of the kfx_volume are read
 inline kfx_volume BrickFrame(size_t w, size_t h, size_t d, float3 boxmin, float3 boxmax)
@@ -152,8 +154,61 @@ inline void MeshBricksEmit(const kfx_volume& frame, int cell, const unsigned* id
                                         tri_offset, verts, norms, colors, 0));
 }
 
+// ---- the same mesh welded by lattice edge on the device (kfx_mesh_bricks_index_*, include/kfx_mesh_bricks_index.h): after MeshBricksPlan,
+// with its scratch unchanged and its totals.
+inline size_t MeshBricksIndexScratchBytes(size_t n, const unsigned long long totals[2]) { return kfx_mesh_bricks_index_scratch_bytes(n, totals); }
+
+// the number of vertices V; the index scratch then belongs to the MeshBricksEmitIndexed that follows
+inline size_t MeshBricksIndexPlan(const kfx_volume& frame, int cell, const unsigned* ids, const void* cells, size_t n, const void* scratch,
+                                  size_t scratch_bytes, const unsigned long long totals[2], void* index_scratch, size_t index_scratch_bytes)
+{
+    unsigned long long nvert = 0;
+    GpuCheckStatus(kfx_mesh_bricks_index_plan(&frame, cell, ids, cells, n, scratch, scratch_bytes, totals, index_scratch, index_scratch_bytes, &nvert, 0));
+    return (size_t)nvert;
+}
+
+// verts[V][3], norms[V][3], colors[V][4] or null, faces[T][3]
+inline void MeshBricksEmitIndexed(const kfx_volume& frame, int cell, const unsigned* ids, const void* cells, size_t n, const unsigned* color_ids,
+                                  const void* color_cells, size_t n_color, void* scratch, size_t scratch_bytes, const void* index_scratch,
+                                  size_t index_scratch_bytes, const unsigned long long totals[2], size_t n_verts, float* verts, float* norms,
+                                  float* colors, unsigned* faces)
+{
+    GpuCheckStatus(kfx_mesh_bricks_emit_indexed(&frame, cell, ids, cells, n, color_ids, color_cells, n_color, scratch, scratch_bytes, index_scratch,
+                                                index_scratch_bytes, totals, n_verts, verts, norms, colors, faces, 0));
+}
+
 namespace mesh_detail
 {
+// the indexed brick mesh as host arrays
+inline HostMesh ExtractBricksIndexed(const kfx_volume& frame, int cell, const unsigned* ids, const void* cells, size_t n, const unsigned* color_ids,
+                                     const void* color_cells, size_t n_color, bool color)
+{
+    const size_t nbytes = MeshBricksScratchBytes(n, color ? n_color : 0);
+    DeviceBuffer scratch(nbytes);
+    unsigned long long totals[2] = {0, 0};
+    MeshBricksPlan(frame, cell, ids, cells, n, scratch.get(), nbytes, totals);
+    const size_t xbytes = MeshBricksIndexScratchBytes(n, totals);
+    DeviceBuffer xscratch(xbytes);
+    HostMesh m;
+    m.ntri = totals[1];
+    m.nvert = MeshBricksIndexPlan(frame, cell, ids, cells, n, scratch.get(), nbytes, totals, xscratch.get(), xbytes);
+    m.color = color && frame.w >= 8 && frame.h >= 8 && frame.d >= 8;
+    m.faces.resize(3 * m.ntri);
+    const size_t nv = m.nvert;
+    DeviceBuffer dv(nv * 12), dn(nv * 12), dc, df(m.faces.size() * 4);
+    if (m.color) dc = DeviceBuffer(nv * 16);
+    if (totals[0])
+        MeshBricksEmitIndexed(frame, cell, ids, cells, n, m.color ? color_ids : nullptr, m.color ? color_cells : nullptr, m.color ? n_color : 0,
+                              scratch.get(), nbytes, xscratch.get(), xbytes, totals, nv, dv.get<float>(), dn.get<float>(), dc.get<float>(),
+                              df.get<unsigned>());
+    m.v.resize(nv * 3); m.n.resize(nv * 3); m.c.resize(m.color ? nv * 4 : 0);
+    dv.CopyTo(m.v.data(), nv * 12);
+    dn.CopyTo(m.n.data(), nv * 12);
+    dc.CopyTo(m.c.data(), m.c.size() * 4);
+    df.CopyTo(m.faces.data(), m.faces.size() * 4);
+    return m;
+}
+
 // the brick mesh as host arrays; cube_index, if given, receives every active cube's dense index in the list's order
 inline HostMesh ExtractBricks(const kfx_volume& frame, int cell, const unsigned* ids, const void* cells, size_t n, const unsigned* color_ids,
                               const void* color_cells, size_t n_color, bool color, std::vector<long long>* cube_index = nullptr,
@@ -194,6 +249,25 @@ inline size_t SaveMeshBricks(std::string filename, const kfx_volume& frame, int 
                              const unsigned* color_ids, const void* color_cells, size_t n_color)
 {
     return mesh_detail::WritePly(filename + ".ply", mesh_detail::ExtractBricks(frame, cell, ids, cells, n, color_ids, color_cells, n_color, true));
+}
+
+// SaveMeshBricksIndexed(filename, frame, cell, ids, cells, n[, color_ids, color_cells, n_color]): SaveMeshBricks' mesh welded by lattice edge
+// -- its first-occurrence vertices and a face list in its triangle order.  Returns the number of triangles written; nvert, if given,
+// receives the number of vertices.
+inline size_t SaveMeshBricksIndexed(std::string filename, const kfx_volume& frame, int cell, const unsigned* ids, const void* cells, size_t n,
+                                    size_t* nvert = nullptr)
+{
+    const mesh_detail::HostMesh m = mesh_detail::ExtractBricksIndexed(frame, cell, ids, cells, n, nullptr, nullptr, 0, false);
+    if (nvert) *nvert = m.nvert;
+    return mesh_detail::WritePly(filename + ".ply", m);
+}
+
+inline size_t SaveMeshBricksIndexed(std::string filename, const kfx_volume& frame, int cell, const unsigned* ids, const void* cells, size_t n,
+                                    const unsigned* color_ids, const void* color_cells, size_t n_color, size_t* nvert = nullptr)
+{
+    const mesh_detail::HostMesh m = mesh_detail::ExtractBricksIndexed(frame, cell, ids, cells, n, color_ids, color_cells, n_color, true);
+    if (nvert) *nvert = m.nvert;
+    return mesh_detail::WritePly(filename + ".ply", m);
 }
 
 // ---- RaycastSdf of packed bricks (kfx_raycast_bricks_*, include/kfx_raycast_bricks.h): RaycastSdf's images of the volume the bricks

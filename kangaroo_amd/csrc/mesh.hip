@@ -426,7 +426,8 @@ static MeshScratch mesh_scratch(const MeshRange& r, const void* scratch)
 //   k_mesh_vertex_base  every active cube's first vertex id (4 bytes)
 //   k_mc_emit_indexed   one lane per active cube: owned edges write their vertex at base + rank, rank = first use among the owned
 //                       edges in c_tris[flag]; every triangle corner writes base(owner) + rank(edge in owner)
-constexpr int MESH_IDX_BLOCK = 256;
+// How an edge is named in its owner and ranked among the owner's edges, and k_mesh_vertex_base, are mesh_cube.h's: the index of
+// packed bricks (mesh_bricks.hip) shares them and differs in the owner rule alone.
 
 // position of cube c in the ascending cube_index[0, n), -1 if it is not listed
 __device__ __forceinline__ long long find_cube(const long long* __restrict__ cube_index, long long n, long long c)
@@ -440,17 +441,16 @@ __device__ __forceinline__ long long find_cube(const long long* __restrict__ cub
     return lo < n && cube_index[lo] == c ? lo : -1;
 }
 
-// The owner of the lattice edge under edge e of active cube t = (x, y, z), index ci: its position in cube_index, and in owner_e the
+// The owner of the lattice edge under edge e of active cube t = (x, y, z), index ci: its position in cube_index, and in oe the
 // edge's number there.  The edge's axis is a; along the other two axes u < w (x before y before z: the emission order's
 // significance) the four cubes around it sit at the edge's minimum corner minus (su, sw) in {0, 1}^2, this cube at its own
-// minimum-corner offsets.  The candidates before this cube are looked up in ascending order; without one the cube owns the edge.
+// minimum-corner offsets (mesh_cube.h: lattice_edge).  The candidates before this cube are looked up in ascending order; without one the cube owns the edge.
 __device__ __forceinline__ long long edge_owner(const MeshParams& p, const long long* __restrict__ cube_index, long long t, long long ci,
-                                                int x, int y, int z, int e, int& owner_e)
+                                                int x, int y, int z, int e, int& oe)
 {
-    const int c0 = edge_c0(e), c1 = edge_c1(e);
-    const int m[3] = {min(corner_dx(c0), corner_dx(c1)), min(corner_dy(c0), corner_dy(c1)), min(corner_dz(c0), corner_dz(c1))};
-    const int a = corner_dx(c0) != corner_dx(c1) ? 0 : (corner_dy(c0) != corner_dy(c1) ? 1 : 2);
-    const int u = a == 0 ? 1 : 0, w = a == 2 ? 1 : 2;
+    const LatticeEdge l = lattice_edge(e);
+    const int a = l.a, u = l.u, w = l.w;
+    const int* const m = l.m;
     const int at[3] = {x, y, z}, cubes[3] = {p.cx, p.cy, p.cz};
     const long long stride[3] = {(long long)p.cy * p.cz, (long long)p.cz, 1};
 #pragma unroll
@@ -464,30 +464,14 @@ __device__ __forceinline__ long long edge_owner(const MeshParams& p, const long 
             const long long j = find_cube(cube_index, t, ci + du * stride[u] + dw * stride[w]);
             if (j >= 0) {
                 // the edge of axis a with minimum corner (su, sw) in the owner
-                owner_e = a == 0 ? 2 * su + 4 * sw : (a == 1 ? (su ? 1 : 3) + 4 * sw : 8 + (sw ? 3 - su : su));
+                oe = owner_e(a, su, sw);
                 return j;
             }
         }
     }
-    owner_e = e;
+    oe = e;
     return t;
 }
-
-// ranks of a cube's owned edges by first use in its triangle list, 4 bits per edge
-__device__ __forceinline__ unsigned long long edge_ranks(int flag, unsigned own)
-{
-    unsigned long long ranks = 0;
-    unsigned seen = 0, r = 0;
-    const int n = c_num_tris[flag] * 3;
-    for (int k = 0; k < n; ++k) {
-        const int q = c_tris[flag][k];
-        if ((seen >> q) & 1u) continue;
-        seen |= 1u << q;
-        if ((own >> q) & 1u) ranks |= (unsigned long long)(r++) << (4 * q);
-    }
-    return ranks;
-}
-__device__ __forceinline__ unsigned rank_of(unsigned long long ranks, int e) { return (unsigned)(ranks >> (4 * e)) & 15u; }
 
 // info[t] = flag | owned edges << 8; part[2 b] = vertices, part[2 b + 1] = triangles of block b's cubes.  hdr[2], hdr[3]: the totals
 // this index was planned for (hdr[0], hdr[1] are the scan's: vertices, triangles).
@@ -518,17 +502,6 @@ __global__ __launch_bounds__(MESH_IDX_BLOCK) void k_mesh_own(const MeshParams p,
     if (threadIdx.x == 0 && blockIdx.x == 0) { hdr[2] = (unsigned long long)n_active; hdr[3] = n_tris; }
 }
 
-__global__ __launch_bounds__(MESH_IDX_BLOCK) void k_mesh_vertex_base(const unsigned* __restrict__ info, const long long n_active,
-                                                                     const unsigned long long* __restrict__ base, unsigned* __restrict__ vbase)
-{
-    __shared__ unsigned lds[MESH_IDX_BLOCK / 64];
-    const long long t = (long long)blockIdx.x * MESH_IDX_BLOCK + threadIdx.x;
-    const unsigned n = t < n_active ? __popc(info[t] >> 8) : 0u;
-    unsigned total;
-    const unsigned ex = block_exclusive_scan<unsigned, MESH_IDX_BLOCK / 64>(n, lds, &total);
-    if (t < n_active) vbase[t] = (unsigned)base[2 * (size_t)blockIdx.x] + ex;
-}
-
 // k_mc_emit with shared vertices: positions, normals and colours by k_mc_emit's expressions, computed by the owner only
 template <typename CELL, bool SLAB>
 __global__ __launch_bounds__(128) void k_mc_emit_indexed(const MeshParams p, const ColorGeom cv, const int has_color,
@@ -543,7 +516,7 @@ __global__ __launch_bounds__(128) void k_mc_emit_indexed(const MeshParams p, con
     ActiveCube c;
     if (!active_cube<CELL>(p, ci, c)) return;
     const unsigned own = info[t_id] >> 8, first = vbase[t_id];
-    const unsigned long long ranks = edge_ranks(c.flag, own);
+    const unsigned long long ranks = edge_ranks(c_tris[c.flag], c.ntri, own);
     const V3 p0 = cube_origin(p, c.x, c.y, c.z);
     unsigned id[12];
 #pragma unroll
@@ -563,7 +536,7 @@ __global__ __launch_bounds__(128) void k_mc_emit_indexed(const MeshParams p, con
             int oe;
             const long long j = edge_owner(p, cube_index, t_id, ci, c.x, c.y, c.z, e, oe);
             const unsigned oi = info[j];
-            id[e] = vbase[j] + rank_of(edge_ranks((int)(oi & 255u), oi >> 8), oe);
+            id[e] = vbase[j] + rank_of(edge_ranks(c_tris[oi & 255u], c_num_tris[oi & 255u], oi >> 8), oe);
         }
     }
     size_t o = (size_t)tri_offset[t_id] * 3; // first face corner of this cube

@@ -16,7 +16,10 @@
 //                     (lane t holds cubes 2 t, 2 t + 1 of the brick in x-major order = ascending ci) and writes cube_index / tri_offset
 //   k_bm_emit         one lane per ACTIVE cube, as k_mc_emit: the cube's brick by binary search, corners and stencils through the
 //                     neighbour table
-// Memory: the lists, about 112 (colour: 220) bytes of scratch per listed brick, the outputs.  Nothing in proportion to the frame.
+//   k_bm_first, k_bm_own, k_bm_emit_indexed   the indexed output (include/kfx_mesh_bricks_index.h): that soup welded by lattice edge;
+//                     described where they stand, below the soup's kernels
+// Memory: the lists, about 112 (colour: 220) bytes of scratch per listed brick, the outputs; with the index 20 bytes per active cube
+// and 4 per listed brick more.  Nothing in proportion to the frame.
 // No global atomics, nothing between workgroups of one launch: ordering comes from the stream.
 #include "mesh_cube.h"
 #include "mesh_bricks_host.h"
@@ -243,6 +246,27 @@ __global__ __launch_bounds__(256) void k_bm_compact(const MeshParams p, const Br
     }
 }
 
+// Normal and grey colour of the vertex at pos of a cube whose cells `sdf` reads, home brick at position `home` of the list: mesh.hip's
+// edge_attributes over the brick lists (multiply-by-reciprocal normalisation, zero where that is not finite).  For k_bm_emit and
+// k_bm_emit_indexed, so that an owner's vertex has the soup's bits.
+template <typename CELL>
+__device__ __forceinline__ void brick_edge_attributes(const MeshParams& p, const ColorGeom& cv, const int has_color, const BrickCells<CELL>& sdf,
+                                                      const unsigned char* __restrict__ color_cells, const int* __restrict__ cnbr, const int home,
+                                                      const V3& pos, V3& normal, float& grey)
+{
+    const V3 deriv = gradient_over(p, sdf, pos);
+    V3 nrm = div_s(deriv, length(deriv));
+    if (!isfinite(nrm.x) || !isfinite(nrm.y) || !isfinite(nrm.z)) nrm = v3(0.f, 0.f, 0.f);
+    normal = nrm;
+    grey = 0.f;
+    if (has_color && cnbr) {
+        const BrickCells<RayC32> col{color_cells, cnbr + (size_t)home * BRICK_NEIGHBOURS, sdf.bx0, sdf.by0, sdf.bz0, 0.5f};
+        grey = trilinear_over(cv, col, pos);
+    } else if (has_color) {   // (no colour bricks at all: every cell reads 0.5)
+        grey = trilinear_over(cv, [](int, int, int) { return 0.5f; }, pos);
+    }
+}
+
 // k_mc_emit over bricks: one thread per active cube, the same steps and expressions
 template <typename CELL>
 __global__ __launch_bounds__(128) void k_bm_emit(const MeshParams p, const ColorGeom cv, const int has_color, const BrickGrid g,
@@ -276,18 +300,7 @@ __global__ __launch_bounds__(128) void k_bm_emit(const MeshParams p, const Color
     for (int e = 0; e < 12; ++e) {
         if (!(mask & (1u << e))) continue;
         ev[e] = edge_position(p, p0, v, e);
-        // (mesh.hip's edge_attributes: multiply-by-reciprocal normalisation, zero where that is not finite)
-        const V3 deriv = gradient_over(p, sdf, ev[e]);
-        V3 nrm = div_s(deriv, length(deriv));
-        if (!isfinite(nrm.x) || !isfinite(nrm.y) || !isfinite(nrm.z)) nrm = v3(0.f, 0.f, 0.f);
-        en[e] = nrm;
-        ec[e] = 0.f;
-        if (has_color && cnbr) {
-            const BrickCells<RayC32> grey{color_cells, cnbr + (size_t)home * BRICK_NEIGHBOURS, bx0, by0, bz0, 0.5f};
-            ec[e] = trilinear_over(cv, grey, ev[e]);
-        } else if (has_color) {   // (no colour bricks at all: every cell reads 0.5)
-            ec[e] = trilinear_over(cv, [](int, int, int) { return 0.5f; }, ev[e]);
-        }
+        brick_edge_attributes(p, cv, has_color, sdf, color_cells, cnbr, home, ev[e], en[e], ec[e]);
     }
     // The cube's slots are those the plan counted for it: [tri_offset[t_id], the next cube's offset or the total).  With ascending ids
     // that is ntri triangles.  With repeated or unsorted ids the search above may land on another entry than the one the cube was
@@ -304,6 +317,211 @@ __global__ __launch_bounds__(128) void k_bm_emit(const MeshParams p, const Color
         for (int k = 0; k < 12; ++k)   // select without dynamic register indexing
             if (k == e) { P = ev[k]; N = en[k]; C = ec[k]; }
         store_vertex(verts, norms, colors, o, P, N, C, has_color);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Indexed extraction (include/kfx_mesh_bricks_index.h): the brick soup welded by lattice edge into its sequential first-occurrence
+// mesh.  As mesh.hip's index, with the soup's order the bricks': the compacted cube list is in that order, so "first in brick-soup
+// order" is "lowest list position".  A lattice edge belongs to up to four cubes, in up to four bricks; each is found in two
+// dependent steps -- the home brick's 27-neighbour row gives the brick's list position, a binary search in that brick's segment
+// [first[b], first[b + 1]) of the cube list gives the cube's -- and the lowest position among those found owns the edge.  (The dense
+// rule looks only at the cubes before this one in dense order and stops at the first: here the componentwise-minimum cube may be
+// missing and the two diagonal ones are ordered by their bricks.)
+//   k_bm_compact         as above, into the index scratch
+//   k_bm_first           every listed brick's first cube position (4 bytes)
+//   k_bm_own             one lane per active cube: case flag and the 12-bit mask of the edges it owns (4 bytes), block sums
+//   k_bm_scan            as above: the blocks' first vertex ids, the vertex total
+//   k_mesh_vertex_base   mesh_cube.h's: every active cube's first vertex id (4 bytes)
+//   k_bm_emit_indexed    one lane per active cube: owned edges write their vertex at base + rank; every triangle corner writes
+//                        base(owner) + rank(edge in owner)
+// Every list position read from the scratches is compared with its list's length before use, and every vertex id with V and face
+// slot with the plan's before the store: lists that are not ascending give an unspecified mesh, no access out of bounds.
+
+// first[i] = the position in the compacted cube list of brick i's first cube = its scan block's offset + the active cubes of the
+// bricks before it in the block (k_bm_compact's rule)
+__global__ __launch_bounds__(256) void k_bm_first(const unsigned* __restrict__ cnt, const unsigned n, const unsigned long long* __restrict__ base,
+                                                  unsigned* __restrict__ first)
+{
+    static_assert(BRICK_MESH_BLOCK == 256, "one brick per thread of the block");
+    __shared__ unsigned lds[4];
+    const unsigned i = blockIdx.x * BRICK_MESH_BLOCK + threadIdx.x;
+    unsigned total;
+    const unsigned ex = block_exclusive_scan<unsigned, 4>(i < n ? bm_active(cnt[i]) : 0u, lds, &total);
+    if (i < n) first[i] = (unsigned)base[2 * (size_t)blockIdx.x] + ex;
+}
+
+// the lists an index kernel finds cubes in
+struct BrickCubeList {
+    const long long* cube_index;   // [n_active], brick by brick
+    const unsigned* first;         // [n]: every listed brick's first cube
+    long long n_active;
+    unsigned n;
+};
+
+// A listed cube as its thread sees it (mesh.hip's ActiveCube): position, home brick, case, triangle count, the mask of its edges
+// with a vertex, corner values
+struct BrickCube {
+    int x, y, z, home, flag, ntri;
+    unsigned mask;
+    float v[8];
+};
+
+// cube ci through the lists, k_bm_emit's steps; false if it is no cube of the frame, its brick is not listed, it has no triangles or a
+// corner that is not finite (a cube of a plan's list over ascending ids is none of these)
+template <typename CELL>
+__device__ __forceinline__ bool brick_active_cube(const MeshParams& p, const BrickGrid& g, const unsigned* __restrict__ ids, const unsigned n,
+                                                  const unsigned char* __restrict__ cells, const int* __restrict__ nbr, const long long ci, BrickCube& c)
+{
+    c.flag = c.ntri = 0;
+    c.mask = 0;
+    c.home = -1;
+    cube_xyz(p, ci, c.x, c.y, c.z);
+    if (ci < 0 || (unsigned)c.x >= (unsigned)p.cx || (unsigned)c.y >= (unsigned)p.cy || (unsigned)c.z >= (unsigned)p.cz) return false;
+    const int bx0 = c.x >> 3, by0 = c.y >> 3, bz0 = c.z >> 3;
+    c.home = find_brick(ids, n, ((unsigned)bz0 * (unsigned)g.nby + (unsigned)by0) * (unsigned)g.nbx + (unsigned)bx0);
+    if (c.home < 0) return false;
+    const BrickCells<CELL> sdf{cells, nbr + (size_t)c.home * BRICK_NEIGHBOURS, bx0, by0, bz0, __builtin_nanf("")};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) c.v[k] = sdf(c.x + corner_dx(k), c.y + corner_dy(k), c.z + corner_dz(k));
+    const bool finite = corner_case(c.v, c.flag);
+    c.ntri = c_bm_num_tris[c.flag];
+    c.mask = c_bm_edge_mask[c.flag];
+    return finite && c.ntri != 0;
+}
+
+// The owner of the lattice edge under edge e of active cube c, position t of the cube list, index ci: its position in the list, and
+// in oe the edge's number there.  Every other cube around the edge (mesh_cube.h: lattice_edge) that lies in the frame is looked up:
+// its brick is the home's or one of its neighbours (the cube is one cell away), whose list position the home's row holds.
+__device__ __forceinline__ long long brick_edge_owner(const MeshParams& p, const int* __restrict__ nbr27, const BrickCubeList& l, const long long t,
+                                                      const long long ci, const BrickCube& c, const int e, int& oe)
+{
+    const LatticeEdge le = lattice_edge(e);
+    const int a = le.a, u = le.u, w = le.w;
+    const int at[3] = {c.x, c.y, c.z}, cubes[3] = {p.cx, p.cy, p.cz};
+    const long long stride[3] = {(long long)p.cy * p.cz, (long long)p.cz, 1};
+    long long best = t;
+    oe = e;
+#pragma unroll
+    for (int su = 0; su < 2; ++su) {
+#pragma unroll
+        for (int sw = 0; sw < 2; ++sw) {
+            const int du = le.m[u] - su, dw = le.m[w] - sw;
+            if (du == 0 && dw == 0) continue;   // this cube
+            int q[3] = {at[0], at[1], at[2]};
+            q[u] += du;
+            q[w] += dw;
+            if (q[u] < 0 || q[u] >= cubes[u] || q[w] < 0 || q[w] >= cubes[w]) continue;
+            const int k = (((q[2] >> 3) - (at[2] >> 3) + 1) * 3 + (q[1] >> 3) - (at[1] >> 3) + 1) * 3 + (q[0] >> 3) - (at[0] >> 3) + 1;
+            const int b = nbr27[k];
+            if (b < 0 || (unsigned)b >= l.n) continue;   // an absent brick: the cube touches unobserved cells
+            // the brick's cubes: [first[b], first[b + 1]) of the list, kept inside it
+            long long lo = l.first[b], hi = (unsigned)b + 1 < l.n ? (long long)l.first[b + 1] : l.n_active;
+            if (hi > l.n_active) hi = l.n_active;
+            const long long want = ci + du * stride[u] + dw * stride[w], end = hi;
+            while (lo < hi) {
+                const long long mid = lo + ((hi - lo) >> 1);
+                if (l.cube_index[mid] < want) lo = mid + 1;
+                else hi = mid;
+            }
+            if (lo < end && lo < best && l.cube_index[lo] == want) {
+                best = lo;
+                oe = owner_e(a, su, sw);
+            }
+        }
+    }
+    return best;
+}
+
+// info[t] = flag | owned edges << 8; part[2 b] = vertices, part[2 b + 1] = triangles of block b's cubes (the slots the plan counted:
+// the next cube's first triangle minus this one's).  hdr[2], hdr[3]: the totals this index was planned for (hdr[0], hdr[1] are the
+// scan's: vertices, triangles).
+template <typename CELL>
+__global__ __launch_bounds__(MESH_IDX_BLOCK) void k_bm_own(const MeshParams p, const BrickGrid g, const unsigned* __restrict__ ids, const unsigned n,
+                                                           const unsigned char* __restrict__ cells, const int* __restrict__ nbr,
+                                                           const BrickCubeList l, const unsigned* __restrict__ tri_offset,
+                                                           const unsigned long long n_tris, unsigned* __restrict__ info,
+                                                           unsigned* __restrict__ part, unsigned long long* __restrict__ hdr)
+{
+    static_assert(MESH_IDX_BLOCK == 256, "store_block_sums");
+    const long long t = (long long)blockIdx.x * MESH_IDX_BLOCK + threadIdx.x;
+    unsigned nv = 0, nt = 0;
+    if (t < l.n_active) {
+        const long long ci = l.cube_index[t];
+        BrickCube c;
+        unsigned own = 0;
+        if (brick_active_cube<CELL>(p, g, ids, n, cells, nbr, ci, c)) {
+            const int* const nbr27 = nbr + (size_t)c.home * BRICK_NEIGHBOURS;
+#pragma unroll
+            for (int e = 0; e < 12; ++e) {
+                if (!(c.mask & (1u << e))) continue;
+                int oe;
+                if (brick_edge_owner(p, nbr27, l, t, ci, c, e, oe) == t) own |= 1u << e;
+            }
+        }
+        info[t] = (unsigned)c.flag | (own << 8);
+        nv = __popc(own);
+        const unsigned long long first = tri_offset[t], next = t + 1 < l.n_active ? (unsigned long long)tri_offset[t + 1] : n_tris;
+        nt = next >= first && next <= n_tris ? (unsigned)(next - first) : 0u;
+    }
+    store_block_sums(nv, nt, part);
+    if (threadIdx.x == 0 && blockIdx.x == 0) { hdr[2] = (unsigned long long)l.n_active; hdr[3] = n_tris; }
+}
+
+// k_bm_emit with shared vertices: positions, normals and colours by k_bm_emit's expressions, computed by the owner only
+template <typename CELL>
+__global__ __launch_bounds__(128) void k_bm_emit_indexed(const MeshParams p, const ColorGeom cv, const int has_color, const BrickGrid g,
+                                                         const unsigned* __restrict__ ids, const unsigned n, const unsigned char* __restrict__ cells,
+                                                         const int* __restrict__ nbr, const unsigned char* __restrict__ color_cells,
+                                                         const int* __restrict__ cnbr, const BrickCubeList l,
+                                                         const unsigned* __restrict__ tri_offset, const unsigned* __restrict__ info,
+                                                         const unsigned* __restrict__ vbase, const unsigned long long cap_tris,
+                                                         const unsigned long long n_verts, float* __restrict__ verts, float* __restrict__ norms,
+                                                         float* __restrict__ colors, unsigned* __restrict__ faces)
+{
+    const long long t_id = (long long)blockIdx.x * 128 + threadIdx.x;
+    if (t_id >= l.n_active) return;
+    const long long ci = l.cube_index[t_id];
+    BrickCube c;
+    if (!brick_active_cube<CELL>(p, g, ids, n, cells, nbr, ci, c)) return;
+    const int* const nbr27 = nbr + (size_t)c.home * BRICK_NEIGHBOURS;
+    const BrickCells<CELL> sdf{cells, nbr27, c.x >> 3, c.y >> 3, c.z >> 3, __builtin_nanf("")};
+    const unsigned own = info[t_id] >> 8, first_id = vbase[t_id];
+    const unsigned long long ranks = edge_ranks(c_bm_tris[c.flag], c.ntri, own);
+    const V3 p0 = cube_origin(p, c.x, c.y, c.z);
+    unsigned id[12];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) {
+        id[e] = 0;
+        if (!(c.mask & (1u << e))) continue;
+        if (own & (1u << e)) {
+            const size_t i = (size_t)first_id + rank_of(ranks, e);
+            id[e] = (unsigned)i;
+            if (i >= n_verts) continue;
+            const V3 pos = edge_position(p, p0, c.v, e);
+            V3 nrm;
+            float grey;
+            brick_edge_attributes(p, cv, has_color, sdf, color_cells, cnbr, c.home, pos, nrm, grey);
+            store_vertex(verts, norms, colors, i, pos, nrm, grey, has_color);
+        } else {
+            int oe;
+            const long long j = brick_edge_owner(p, nbr27, l, t_id, ci, c, e, oe);   // (in [0, n_active): t_id or a position found)
+            const unsigned oi = info[j];
+            id[e] = vbase[j] + rank_of(edge_ranks(c_bm_tris[oi & 255u], c_bm_num_tris[oi & 255u], oi >> 8), oe);
+        }
+    }
+    // the cube's slots are those the plan counted for it (k_bm_emit's rule): nothing is written outside them
+    const unsigned long long first = tri_offset[t_id], next = t_id + 1 < l.n_active ? (unsigned long long)tri_offset[t_id + 1] : cap_tris;
+    if (next < first || next > cap_tris) return;
+    const int planned = (int)(next - first < 5 ? next - first : 5);
+    size_t o = (size_t)first * 3;   // first face corner of this cube
+    for (int t = 0; t < min(c.ntri, planned) * 3; ++t, ++o) {
+        const int e = c_bm_tris[c.flag][t];
+        unsigned I = 0;
+#pragma unroll
+        for (int k = 0; k < 12; ++k)   // select without dynamic register indexing
+            if (k == e) I = id[k];
+        faces[o] = I;
     }
 }
 
@@ -431,6 +649,124 @@ extern "C" int kfx_mesh_bricks_emit(const kfx_volume* frame, int cell, const uns
         hipLaunchKernelGGL(k_bm_emit<CELL>, dim3((unsigned)((n_active + 127) / 128)), dim3(128), 0, st, c.p, cv, has_color, c.grid, ids, nn,
                            (const unsigned char*)cells, nbr, (const unsigned char*)color_cells, (const int*)cnbr, (const long long*)cube_index,
                            (const unsigned*)tri_offset, n_active, totals[1], verts, norms, has_color ? colors : nullptr);
+    });
+    return check_launch(what);
+}
+
+// ---- indexed extraction (include/kfx_mesh_bricks_index.h) ----
+
+static_assert(BRICK_MESH_MAX_TRIS == MESH_MAX_TRIS && BRICK_MESH_IDX_BLOCK == MESH_IDX_BLOCK, "mesh_bricks_host.h states mesh_cube.h's limits");
+
+// The checks of an index plan or an indexed emit after bm_call's, in one order: the totals (null, range, with V), then the index
+// scratch (null, short, misaligned); the carved index scratch in x.
+static int bm_index_call(BrickMeshIndexScratch& x, const char* what, unsigned long long n, const unsigned long long* totals, unsigned long long n_verts,
+                         const void* index_scratch, size_t index_scratch_bytes)
+{
+    if (int e = refuse(brick_mesh_check_totals(totals, n_verts), what)) return e;
+    if (int e = refuse(brick_mesh_index_check_scratch(n, totals, index_scratch, index_scratch_bytes), what)) return e;
+    x = brick_mesh_index_scratch(n, totals[0]);
+    return 0;
+}
+
+extern "C" size_t kfx_mesh_bricks_index_scratch_bytes(unsigned long long n, const unsigned long long totals[2])
+{
+    if (brick_check_counts(n, 0).code || brick_mesh_check_totals(totals, 0).code) return 0;
+    return brick_mesh_index_scratch(n, totals[0]).bytes;
+}
+
+extern "C" int kfx_mesh_bricks_index_plan(const kfx_volume* frame, int cell, const unsigned* ids, const void* cells, unsigned long long n,
+                                          const void* scratch, size_t scratch_bytes, const unsigned long long totals[2], void* index_scratch,
+                                          size_t index_scratch_bytes, unsigned long long* n_verts, kfx_stream stream)
+{
+    const char* const what = "kfx_mesh_bricks_index_plan";
+    BrickMeshCall c;
+    BrickMeshIndexScratch x;
+    if (int e = bm_call(c, what, frame, cell, ids, cells, n, nullptr, nullptr, 0, scratch, scratch_bytes, totals)) return e;
+    if (int e = bm_index_call(x, what, n, totals, 0, index_scratch, index_scratch_bytes)) return e;
+    if (!n_verts) return fail_rule(what, KFX_E_NULL, "null n_verts");
+    if (n == 0 && (totals[0] || totals[1])) return fail_rule(what, KFX_E_RANGE, "totals are not the plan's");
+    *n_verts = 0;
+    if (n == 0 || totals[0] == 0) return 0;
+    if (int e = bm_load_tables()) return e;
+    const unsigned char* const s = (const unsigned char*)scratch;
+    const int* const nbr = (const int*)(s + c.lay.nbr);
+    const unsigned* const cnt = (const unsigned*)(s + c.lay.cnt);
+    const unsigned long long* const base = (const unsigned long long*)(s + c.lay.base);
+    unsigned char* const xs = (unsigned char*)index_scratch;
+    unsigned long long* const xhdr = (unsigned long long*)(xs + x.hdr);
+    long long* const cube_index = (long long*)(xs + x.cube_index);
+    unsigned* const tri_offset = (unsigned*)(xs + x.tri_offset);
+    unsigned* const info = (unsigned*)(xs + x.info);
+    unsigned* const vbase = (unsigned*)(xs + x.vbase);
+    unsigned* const first = (unsigned*)(xs + x.first);
+    unsigned* const xpart = (unsigned*)(xs + x.part);
+    unsigned long long* const xbase = (unsigned long long*)(xs + x.base);
+    const hipStream_t st = (hipStream_t)stream;
+    if (int e = check_planned((const unsigned long long*)(s + c.lay.hdr), totals, 2, what, st)) return e;
+    const unsigned nn = (unsigned)n;
+    const long long n_active = (long long)totals[0];
+    const BrickCubeList l{cube_index, first, n_active, nn};
+    for_sdf_cell(cell, [&](auto kind) {
+        using CELL = decltype(kind);
+        hipLaunchKernelGGL(k_bm_compact<CELL>, dim3(nn), dim3(256), 0, st, c.p, c.grid, ids, (const unsigned char*)cells, nbr, cnt, base, cube_index,
+                           tri_offset, totals[0], totals[1]);
+        hipLaunchKernelGGL(k_bm_first, dim3((unsigned)c.lay.nblk), dim3(256), 0, st, cnt, nn, base, first);
+        hipLaunchKernelGGL(k_bm_own<CELL>, dim3((unsigned)x.nblk), dim3(MESH_IDX_BLOCK), 0, st, c.p, c.grid, ids, nn, (const unsigned char*)cells, nbr, l,
+                           (const unsigned*)tri_offset, totals[1], info, xpart, xhdr);
+        hipLaunchKernelGGL(k_bm_scan, dim3(1), dim3(MESH_SCAN_THREADS), 0, st, (const unsigned*)xpart, (long long)x.nblk, xbase, xhdr);
+        hipLaunchKernelGGL(k_mesh_vertex_base, dim3((unsigned)x.nblk), dim3(MESH_IDX_BLOCK), 0, st, (const unsigned*)info, n_active,
+                           (const unsigned long long*)xbase, vbase);
+    });
+    if (int e = check_launch(what)) return e;
+    unsigned long long host[2];
+    if (int e = read_header(host, xhdr, 2, st)) return e;
+    *n_verts = host[0];
+    return 0;
+}
+
+extern "C" int kfx_mesh_bricks_emit_indexed(const kfx_volume* frame, int cell, const unsigned* ids, const void* cells, unsigned long long n,
+                                            const unsigned* color_ids, const void* color_cells, unsigned long long n_color, void* scratch,
+                                            size_t scratch_bytes, const void* index_scratch, size_t index_scratch_bytes,
+                                            const unsigned long long totals[2], unsigned long long n_verts, float* verts, float* norms,
+                                            float* colors, unsigned* faces, kfx_stream stream)
+{
+    const char* const what = "kfx_mesh_bricks_emit_indexed";
+    BrickMeshCall c;
+    BrickMeshIndexScratch x;
+    if (int e = bm_call(c, what, frame, cell, ids, cells, n, color_ids, color_cells, n_color, scratch, scratch_bytes, totals)) return e;
+    if (int e = bm_index_call(x, what, n, totals, n_verts, index_scratch, index_scratch_bytes)) return e;
+    if (n == 0) return totals[0] || totals[1] || n_verts ? fail_rule(what, KFX_E_RANGE, "totals are not the plan's") : 0;
+    if (totals[0] == 0) return 0;
+    if (int e = refuse(brick_mesh_check_indexed_outputs(verts, norms, colors, faces), what)) return e;
+    const int has_color = brick_mesh_has_color(c.geom, colors) ? 1 : 0;
+    ColorGeom cv{};
+    if (has_color) {   // the colour frame: the SDF frame's dimensions and box
+        kfx_volume f = *frame;
+        f.ptr = nullptr;
+        f.pitch = f.img_pitch = 0;
+        set_geometry(cv, &f);
+    }
+    if (int e = bm_load_tables()) return e;
+    unsigned char* const s = (unsigned char*)scratch;
+    const int* const nbr = (const int*)(s + c.lay.nbr);
+    int* const cnbr = has_color && n_color ? (int*)(s + c.lay.cnbr) : nullptr;
+    const unsigned char* const xs = (const unsigned char*)index_scratch;
+    const hipStream_t st = (hipStream_t)stream;
+    // (the index plan's header: vertices, triangles, and the totals it was planned for)
+    const unsigned long long planned[4] = {n_verts, totals[1], totals[0], totals[1]};
+    if (int e = check_planned((const unsigned long long*)(xs + x.hdr), planned, 4, what, st)) return e;
+    const unsigned nn = (unsigned)n;
+    const long long n_active = (long long)totals[0];
+    const BrickCubeList l{(const long long*)(xs + x.cube_index), (const unsigned*)(xs + x.first), n_active, nn};
+    if (cnbr)
+        hipLaunchKernelGGL(k_bm_neighbours<false>, dim3((unsigned)((n * BRICK_NEIGHBOURS + 255) / 256)), dim3(256), 0, st, c.grid, ids, nn, color_ids,
+                           (unsigned)n_color, cnbr);
+    for_sdf_cell(cell, [&](auto kind) {
+        using CELL = decltype(kind);
+        hipLaunchKernelGGL(k_bm_emit_indexed<CELL>, dim3((unsigned)((n_active + 127) / 128)), dim3(128), 0, st, c.p, cv, has_color, c.grid, ids, nn,
+                           (const unsigned char*)cells, nbr, (const unsigned char*)color_cells, (const int*)cnbr, l,
+                           (const unsigned*)(xs + x.tri_offset), (const unsigned*)(xs + x.info), (const unsigned*)(xs + x.vbase), totals[1], n_verts,
+                           verts, norms, has_color ? colors : nullptr, faces);
     });
     return check_launch(what);
 }

@@ -2,7 +2,9 @@
 // packed bricks' (mesh_bricks.hip: kfx_mesh_bricks_*).  The case tables, a cube's corners and case, a vertex's position on its edge,
 // the normalisation of its normal and its store -- one definition each, so that a brick mesh stays the dense mesh of the volume its
 // bricks unpack into, bit for bit -- and the host helpers of the two-step calls: the scratch carver, the scan of the block sums, the
-// read-back of a plan's totals.  How a CELL is read (pitched rows, or bricks through a neighbour table) is the including file's.
+// read-back of a plan's totals; and of the two indexed extractions how a lattice edge is named in its owner, how a cube ranks the edges
+// it owns, and the kernel that turns the owned-edge counts into first vertex ids.  How a CELL is read (pitched rows, or bricks through
+// a neighbour table) is the including file's.
 #pragma once
 
 #include "kfx_device.h"
@@ -148,6 +150,63 @@ __device__ __forceinline__ void scan_block_sums(const unsigned* __restrict__ par
         totals[0] = run_a;
         totals[1] = run_t;
     }
+}
+
+// ---- what the indexed extractions share (mesh.hip: kfx_mesh_index_*; mesh_bricks.hip: kfx_mesh_bricks_index_*): a vertex is keyed by
+// the LATTICE EDGE under its cube edge, and numbered by the cube that owns that edge.  Which cube owns it is each file's own rule (the
+// first in ITS emission order); how an edge is named inside its owner and how a cube numbers the edges it owns is written here.
+constexpr int MESH_IDX_BLOCK = 256;   // active cubes per scan block of an index plan
+
+// The lattice edge under cube edge e: its axis a, the other two axes u < w (x before y before z), and m[3], the offsets of the edge's
+// minimum corner from the cube's.  The four cubes around the edge sit at that minimum corner minus (su, sw) in {0, 1}^2 along u and w,
+// i.e. at this cube plus (m[u] - su, m[w] - sw).
+struct LatticeEdge {
+    int m[3], a, u, w;
+};
+__device__ __forceinline__ LatticeEdge lattice_edge(int e)
+{
+    const int c0 = edge_c0(e), c1 = edge_c1(e);
+    LatticeEdge l;
+    l.m[0] = min(corner_dx(c0), corner_dx(c1));
+    l.m[1] = min(corner_dy(c0), corner_dy(c1));
+    l.m[2] = min(corner_dz(c0), corner_dz(c1));
+    l.a = corner_dx(c0) != corner_dx(c1) ? 0 : (corner_dy(c0) != corner_dy(c1) ? 1 : 2);
+    l.u = l.a == 0 ? 1 : 0;
+    l.w = l.a == 2 ? 1 : 2;
+    return l;
+}
+// the number, in the cube that sits at the edge's minimum corner minus (su, sw), of the edge of axis a
+__device__ __forceinline__ int owner_e(int a, int su, int sw)
+{
+    return a == 0 ? 2 * su + 4 * sw : (a == 1 ? (su ? 1 : 3) + 4 * sw : 8 + (sw ? 3 - su : su));
+}
+
+// ranks of a cube's owned edges by first use in its triangle list (tris: the case's row of MC_TRIS, ntri triangles), 4 bits per edge
+__device__ __forceinline__ unsigned long long edge_ranks(const signed char* tris, int ntri, unsigned own)
+{
+    unsigned long long ranks = 0;
+    unsigned seen = 0, r = 0;
+    const int n = ntri * 3;
+    for (int k = 0; k < n; ++k) {
+        const int q = tris[k];
+        if ((seen >> q) & 1u) continue;
+        seen |= 1u << q;
+        if ((own >> q) & 1u) ranks |= (unsigned long long)(r++) << (4 * q);
+    }
+    return ranks;
+}
+__device__ __forceinline__ unsigned rank_of(unsigned long long ranks, int e) { return (unsigned)(ranks >> (4 * e)) & 15u; }
+
+// every active cube's first vertex id: info[t] >> 8 is the mask of the edges cube t owns, base[2 b] the vertices before block b
+static __global__ __launch_bounds__(MESH_IDX_BLOCK) void k_mesh_vertex_base(const unsigned* __restrict__ info, const long long n_active,
+                                                                            const unsigned long long* __restrict__ base, unsigned* __restrict__ vbase)
+{
+    __shared__ unsigned lds[MESH_IDX_BLOCK / 64];
+    const long long t = (long long)blockIdx.x * MESH_IDX_BLOCK + threadIdx.x;
+    const unsigned n = t < n_active ? __popc(info[t] >> 8) : 0u;
+    unsigned total;
+    const unsigned ex = block_exclusive_scan<unsigned, MESH_IDX_BLOCK / 64>(n, lds, &total);
+    if (t < n_active) vbase[t] = (unsigned)base[2 * (size_t)blockIdx.x] + ex;
 }
 
 // A caller's scratch handed out front to back, every sub-buffer on a 256-byte boundary of it; `bytes` is what has been taken.

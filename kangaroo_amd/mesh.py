@@ -19,7 +19,9 @@ A slab's indexed mesh is the weld of that rank's soup: vertices on a slab bounda
 
 Brick mesh (include/kfx_mesh_bricks.h), ExtractBrickMesh / SaveBrickMesh: the soup of packed 8 x 8 x 8 bricks (roo.BrickPack's lists, the
 bricks a moving volume spilled) on a frame of any size -- what ExtractMesh returns for the dense volume those bricks would unpack into,
-cube by cube and bit for bit, listed brick by brick -- with memory in proportion to the bricks, not the frame.
+cube by cube and bit for bit, listed brick by brick -- with memory in proportion to the bricks, not the frame.  indexed=True
+(include/kfx_mesh_bricks_index.h): the first-occurrence weld of THAT soup by lattice edge, welded on the device across brick faces,
+edges and corners -- the vertex set of ExtractMesh(D, indexed=True) in the bricks' order, still without D.
 
 Case tables: kangaroo_amd/csrc/mc_tables.inc, derived by scripts/gen_mc_tables.py.  Their boundary loops and
 winding agree with the classic tables the reference uses in all 256 cases; 158 cases split a polygon along a
@@ -131,7 +133,7 @@ def BrickMeshScratchBytes(n, n_color=0):
     return int(_lib.load().kfx_mesh_bricks_scratch_bytes(int(n), int(n_color)))
 
 
-def ExtractBrickMesh(dims, boxmin, boxmax, kind, ids, cells, color_ids=None, color_cells=None, with_index=False, stream=None):
+def ExtractBrickMesh(dims, boxmin, boxmax, kind, ids, cells, color_ids=None, color_cells=None, with_index=False, stream=None, indexed=False):
     """The mesh of packed 8 x 8 x 8 bricks (include/kfx_mesh_bricks.h): what ExtractMesh returns for the dense volume of `dims` cells and
     the box (boxmin, boxmax) that is NaN everywhere and then gets BrickUnpack(ids, cells) -- the same cubes, each with the same triangles
     bit for bit -- without that volume; memory in proportion to the bricks and the mesh.  Only the order differs: brick by brick in
@@ -139,10 +141,16 @@ def ExtractBrickMesh(dims, boxmin, boxmax, kind, ids, cells, color_ids=None, col
 
     kind "f32" or "f16"; ids / cells as roo.BrickPack returns them for a view of these dimensions: torch tensors, or host arrays, which
     are uploaded (host ids are checked to ascend strictly).  color_ids / color_cells: a second list of "c32" bricks on the same frame;
-    an absent colour brick reads 0.5.  Colours are returned when color_ids is given and every dimension is >= 8."""
+    an absent colour brick reads 0.5.  Colours are returned when color_ids is given and every dimension is >= 8.
+
+    indexed=True: (verts, norms, colors, faces) with V rows each and faces (T, 3), uint32 ids held in an int32 tensor, as ExtractMesh:
+    the sequential first-occurrence weld, by lattice edge, of the arrays above in their (brick) order (include/kfx_mesh_bricks_index.h).
+    Not with with_index=True, which lists the soup's cubes."""
     L = _lib.load()
     if kind not in CELL:
         raise ValueError("ExtractBrickMesh: cell kind %r (fp32 or half SDF cells)" % (kind,))
+    if indexed and with_index:
+        raise ValueError("ExtractBrickMesh: with_index lists the soup's cubes; not with indexed=True")
     if (color_ids is None) != (color_cells is None):
         raise ValueError("ExtractBrickMesh: color_ids and color_cells come together (both, or neither)")
     device = ids.device if torch.is_tensor(ids) else (cells.device if torch.is_tensor(cells) else torch.device("cuda", torch.cuda.current_device()))
@@ -165,11 +173,26 @@ def ExtractBrickMesh(dims, boxmin, boxmax, kind, ids, cells, color_ids=None, col
         raise ValueError("mesh too large for 32-bit vertex offsets")
     _lib.check(code)
     na, ntri = int(totals[0]), int(totals[1])
+    clists = (_ptr(cids) if nc else None, _ptr(ccells) if nc else None, nc)
+    if indexed:
+        xbytes = L.kfx_mesh_bricks_index_scratch_bytes(n, totals)
+        xscratch = empty(max(xbytes, 256), torch.uint8)
+        nvert = C.c_ulonglong(0)
+        _lib.check(L.kfx_mesh_bricks_index_plan(C.byref(frame), CELL[kind], *lists, _ptr(scratch), nbytes, totals, _ptr(xscratch), xbytes,
+                                                C.byref(nvert), st))
+        nv = int(nvert.value)
+        verts, norms = empty((nv, 3), torch.float32), empty((nv, 3), torch.float32)
+        colors = empty((nv, 4), torch.float32) if want_color else None
+        faces = empty((ntri, 3), torch.int32)
+        if na:
+            _lib.check(L.kfx_mesh_bricks_emit_indexed(C.byref(frame), CELL[kind], *lists, *clists, _ptr(scratch), nbytes, _ptr(xscratch), xbytes,
+                                                      totals, nv, _ptr(verts), _ptr(norms), _ptr(colors), _ptr(faces), st))
+        return verts, norms, colors, faces
     verts, norms = empty((3 * ntri, 3), torch.float32), empty((3 * ntri, 3), torch.float32)
     colors = empty((3 * ntri, 4), torch.float32) if want_color else None
     cube_index, tri_offset = empty(na, torch.int64), empty(na, torch.int32)
     if na:
-        _lib.check(L.kfx_mesh_bricks_emit(C.byref(frame), CELL[kind], *lists, _ptr(cids) if nc else None, _ptr(ccells) if nc else None, nc,
+        _lib.check(L.kfx_mesh_bricks_emit(C.byref(frame), CELL[kind], *lists, *clists,
                                           _ptr(scratch), nbytes, totals, _ptr(cube_index), _ptr(tri_offset), _ptr(verts), _ptr(norms),
                                           _ptr(colors), st))
     if with_index:
@@ -177,12 +200,19 @@ def ExtractBrickMesh(dims, boxmin, boxmax, kind, ids, cells, color_ids=None, col
     return verts, norms, colors
 
 
-def SaveBrickMesh(filename, dims, boxmin, boxmax, kind, ids, cells, color_ids=None, color_cells=None, binary=True):
-    """ExtractBrickMesh's mesh as filename + ".ply" (write_ply); returns the triangle count."""
-    verts, norms, colors = ExtractBrickMesh(dims, boxmin, boxmax, kind, ids, cells, color_ids, color_cells)
+def SaveBrickMesh(filename, dims, boxmin, boxmax, kind, ids, cells, color_ids=None, color_cells=None, binary=True, indexed=False):
+    """ExtractBrickMesh's mesh as filename + ".ply" (write_ply); returns the triangle count.  indexed=True: V welded vertices and T faces
+    instead of 3T vertices."""
+    return _save_mesh(filename, ExtractBrickMesh(dims, boxmin, boxmax, kind, ids, cells, color_ids, color_cells, indexed=indexed), binary, indexed)
+
+
+def _save_mesh(filename, arrays, binary, indexed):
+    """(verts, norms, colors[, faces]) of an Extract*Mesh as filename + ".ply"; returns the triangle count"""
+    verts, norms, colors, *faces = arrays
     torch.cuda.synchronize() if verts.is_cuda else None
-    write_ply(filename + ".ply", verts.cpu().numpy(), norms.cpu().numpy(), None if colors is None else colors.cpu().numpy(), binary)
-    return len(verts) // 3
+    faces = faces[0].cpu().numpy().view(np.uint32) if indexed else None
+    write_ply(filename + ".ply", verts.cpu().numpy(), norms.cpu().numpy(), None if colors is None else colors.cpu().numpy(), binary, faces)
+    return len(verts) // 3 if faces is None else len(faces)
 
 
 def write_ply(path, verts, norms, colors=None, binary=True, faces=None):
@@ -215,8 +245,4 @@ def write_ply(path, verts, norms, colors=None, binary=True, faces=None):
 def SaveMesh(filename, vol, colorVol=None, binary=True, slab=None, indexed=False):
     """SaveMesh(filename, vol[, volColor]) (MarchingCubes.h:246-262): writes filename + ".ply"; returns the triangle count.
     fp32 or half volumes; slab: ExtractMesh's.  indexed=True: V welded vertices and T faces (ExtractMesh's) instead of 3T vertices."""
-    verts, norms, colors, *faces = ExtractMesh(vol, colorVol, slab=slab, indexed=indexed)
-    torch.cuda.synchronize() if verts.is_cuda else None
-    faces = faces[0].cpu().numpy().view(np.uint32) if indexed else None
-    write_ply(filename + ".ply", verts.cpu().numpy(), norms.cpu().numpy(), None if colors is None else colors.cpu().numpy(), binary, faces)
-    return len(verts) // 3 if faces is None else len(faces)
+    return _save_mesh(filename, ExtractMesh(vol, colorVol, slab=slab, indexed=indexed), binary, indexed)

@@ -352,22 +352,19 @@ class FramePipeline:
         skeys = self.store.keys() if self.store is not None else None
         return sdf, bricks.world_bricks(self.cstore, self.cvol, self.origin, 0.5, ops=self.ops, cover=skeys)
 
-    def ExtractWorldMesh(self, with_index=False):
+    def ExtractWorldMesh(self, with_index=False, indexed=False):
         """The mesh of everything the model has seen -- the live volume and what it spilled -- as mesh.ExtractBrickMesh returns it:
-        continuous across the faces of the volume that no longer exist.  Without a store: the brick mesh of the live volume."""
+        continuous across the faces of the volume that no longer exist.  Without a store: the brick mesh of the live volume.
+        indexed=True: (verts, norms, colors, faces), welded by lattice edge on the device (mesh.ExtractBrickMesh's)."""
         from . import mesh
         (lo, dims, bmin, bmax, ids, cells), col = self.world_bricks()
         cids, ccells = (col[4], col[5]) if col is not None else (None, None)
-        return mesh.ExtractBrickMesh(dims, bmin, bmax, self.kind, ids, cells, cids, ccells, with_index=with_index)
+        return mesh.ExtractBrickMesh(dims, bmin, bmax, self.kind, ids, cells, cids, ccells, with_index=with_index, indexed=indexed)
 
-    def SaveWorldMesh(self, filename, binary=True):
-        """ExtractWorldMesh's mesh as filename + ".ply"; returns the triangle count."""
-        import torch
+    def SaveWorldMesh(self, filename, binary=True, indexed=False):
+        """ExtractWorldMesh's mesh as filename + ".ply"; returns the triangle count.  indexed=True: V welded vertices and T faces."""
         from . import mesh
-        verts, norms, colors = self.ExtractWorldMesh()
-        torch.cuda.synchronize() if verts.is_cuda else None
-        mesh.write_ply(filename + ".ply", verts.cpu().numpy(), norms.cpu().numpy(), None if colors is None else colors.cpu().numpy(), binary)
-        return len(verts) // 3
+        return mesh._save_mesh(filename, self.ExtractWorldMesh(indexed=indexed), binary, indexed)
 
     def world_view(self):
         """Everything the model holds, ready to be rendered (include/kfx_raycast_bricks.h): world_bricks() packed and planned once.
