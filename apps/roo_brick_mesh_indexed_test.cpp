@@ -149,7 +149,7 @@ int main()
     const kfx_volume frame = BrickFrame(w, h, d, lo, hi);
     std::vector<long long> ci;
     std::vector<unsigned> to;
-    const mesh_detail::HostMesh soup = mesh_detail::ExtractBricks(frame, KFX_CELL_F32, ids.ptr, packed.ptr, n, nullptr, nullptr, 0, false, &ci, &to);
+    const mesh_detail::HostMesh soup = mesh_detail::ExtractBricks(frame, KFX_CELL_F32, ids.ptr, packed.ptr, n, nullptr, nullptr, 0, false, false, &ci, &to);
     const Welded want = Weld(soup, ci, to, cells, w, h, d);
     CHECK(soup.ntri > 1000 && want.faces.size() == 3 * soup.ntri && want.v.size() < 9 * soup.ntri);
     printf("T = %zu, V = %zu, %zu lattice edges with another first cube than in dense order\n", (size_t)soup.ntri, want.v.size() / 3, want.other);
@@ -194,8 +194,8 @@ int main()
             for (int x = 0; x < w; ++x)
                 if (!std::binary_search(half_ids.begin(), half_ids.end(), (unsigned)(((z >> 3) * nby + (y >> 3)) * nbx + (x >> 3))))
                     cells[((size_t)z * h + y) * w + x].val = NAN;
-    const mesh_detail::HostMesh fewer_soup = mesh_detail::ExtractBricks(frame, KFX_CELL_F32, ids.ptr, packed.ptr, m2, nullptr, nullptr, 0, false, &ci, &to);
-    const mesh_detail::HostMesh fewer = mesh_detail::ExtractBricksIndexed(frame, KFX_CELL_F32, ids.ptr, packed.ptr, m2, nullptr, nullptr, 0, false);
+    const mesh_detail::HostMesh fewer_soup = mesh_detail::ExtractBricks(frame, KFX_CELL_F32, ids.ptr, packed.ptr, m2, nullptr, nullptr, 0, false, false, &ci, &to);
+    const mesh_detail::HostMesh fewer = mesh_detail::ExtractBricks(frame, KFX_CELL_F32, ids.ptr, packed.ptr, m2, nullptr, nullptr, 0, false, true);
     CHECK(fewer.ntri > 0 && fewer.ntri < soup.ntri && fewer.ntri == fewer_soup.ntri);
     CHECK(IsTheWeld(fewer, Weld(fewer_soup, ci, to, cells, w, h, d)));
 

@@ -103,7 +103,7 @@ int main()
 
     const kfx_volume frame = BrickFrame(w, h, d, lo, hi);
     Soup bricks;
-    bricks.m = mesh_detail::ExtractBricks(frame, KFX_CELL_F32, ids.ptr, packed.ptr, n, nullptr, nullptr, 0, false, &bricks.ci, &bricks.to);
+    bricks.m = mesh_detail::ExtractBricks(frame, KFX_CELL_F32, ids.ptr, packed.ptr, n, nullptr, nullptr, 0, false, false, &bricks.ci, &bricks.to);
     Compare(bricks, Dense(vol), w, h, d, host_ids);
 
     // every other brick: the list is the front of a compacted copy; the comparator is the volume reset and those bricks unpacked
@@ -120,7 +120,7 @@ int main()
     SdfReset(vol, NAN);
     BrickUnpack(vol, ids.ptr, packed.ptr, m);
     Soup fewer;
-    fewer.m = mesh_detail::ExtractBricks(frame, KFX_CELL_F32, ids.ptr, packed.ptr, m, nullptr, nullptr, 0, false, &fewer.ci, &fewer.to);
+    fewer.m = mesh_detail::ExtractBricks(frame, KFX_CELL_F32, ids.ptr, packed.ptr, m, nullptr, nullptr, 0, false, false, &fewer.ci, &fewer.to);
     CHECK(fewer.ci.size() < bricks.ci.size());
     Compare(fewer, Dense(vol), w, h, d, half_ids);
 

@@ -179,61 +179,50 @@ inline void MeshBricksEmitIndexed(const kfx_volume& frame, int cell, const unsig
 
 namespace mesh_detail
 {
-// the indexed brick mesh as host arrays
-inline HostMesh ExtractBricksIndexed(const kfx_volume& frame, int cell, const unsigned* ids, const void* cells, size_t n, const unsigned* color_ids,
-                                     const void* color_cells, size_t n_color, bool color)
-{
-    const size_t nbytes = MeshBricksScratchBytes(n, color ? n_color : 0);
-    DeviceBuffer scratch(nbytes);
-    unsigned long long totals[2] = {0, 0};
-    MeshBricksPlan(frame, cell, ids, cells, n, scratch.get(), nbytes, totals);
-    const size_t xbytes = MeshBricksIndexScratchBytes(n, totals);
-    DeviceBuffer xscratch(xbytes);
-    HostMesh m;
-    m.ntri = totals[1];
-    m.nvert = MeshBricksIndexPlan(frame, cell, ids, cells, n, scratch.get(), nbytes, totals, xscratch.get(), xbytes);
-    m.color = color && frame.w >= 8 && frame.h >= 8 && frame.d >= 8;
-    m.faces.resize(3 * m.ntri);
-    const size_t nv = m.nvert;
-    DeviceBuffer dv(nv * 12), dn(nv * 12), dc, df(m.faces.size() * 4);
-    if (m.color) dc = DeviceBuffer(nv * 16);
-    if (totals[0])
-        MeshBricksEmitIndexed(frame, cell, ids, cells, n, m.color ? color_ids : nullptr, m.color ? color_cells : nullptr, m.color ? n_color : 0,
-                              scratch.get(), nbytes, xscratch.get(), xbytes, totals, nv, dv.get<float>(), dn.get<float>(), dc.get<float>(),
-                              df.get<unsigned>());
-    m.v.resize(nv * 3); m.n.resize(nv * 3); m.c.resize(m.color ? nv * 4 : 0);
-    dv.CopyTo(m.v.data(), nv * 12);
-    dn.CopyTo(m.n.data(), nv * 12);
-    dc.CopyTo(m.c.data(), m.c.size() * 4);
-    df.CopyTo(m.faces.data(), m.faces.size() * 4);
-    return m;
-}
-
-// the brick mesh as host arrays; cube_index, if given, receives every active cube's dense index in the list's order
+// The brick mesh as host arrays (MarchingCubes.h's Extract over the brick lists): the soup, or with `indexed` its weld by lattice
+// edge.  cube_index and tri_offset, if given, receive every active cube's dense index and first triangle in the list's order (soup).
 inline HostMesh ExtractBricks(const kfx_volume& frame, int cell, const unsigned* ids, const void* cells, size_t n, const unsigned* color_ids,
-                              const void* color_cells, size_t n_color, bool color, std::vector<long long>* cube_index = nullptr,
+                              const void* color_cells, size_t n_color, bool color, bool indexed = false, std::vector<long long>* cube_index = nullptr,
                               std::vector<unsigned>* tri_offset = nullptr)
 {
     const size_t nbytes = MeshBricksScratchBytes(n, color ? n_color : 0);
-    DeviceBuffer scratch(nbytes);
+    DeviceBuffer scratch(nbytes), xscratch, active, offsets, faces;
     unsigned long long totals[2] = {0, 0};
     MeshBricksPlan(frame, cell, ids, cells, n, scratch.get(), nbytes, totals);
     HostMesh m;
     m.ntri = totals[1];
     m.nvert = 3 * m.ntri;
     m.color = color && frame.w >= 8 && frame.h >= 8 && frame.d >= 8;
+    size_t xbytes = 0;
+    if (indexed) {
+        xbytes = MeshBricksIndexScratchBytes(n, totals);
+        xscratch = DeviceBuffer(xbytes);
+        m.nvert = MeshBricksIndexPlan(frame, cell, ids, cells, n, scratch.get(), nbytes, totals, xscratch.get(), xbytes);
+        m.faces.resize(3 * m.ntri);
+        faces = DeviceBuffer(m.faces.size() * 4);
+    } else {
+        active = DeviceBuffer(totals[0] * 8);
+        offsets = DeviceBuffer(totals[0] * 4);
+    }
     const size_t nv = m.nvert;
-    DeviceBuffer active(totals[0] * 8), offsets(totals[0] * 4), dv(nv * 12), dn(nv * 12), dc;
+    DeviceBuffer dv(nv * 12), dn(nv * 12), dc;
     if (m.color) dc = DeviceBuffer(nv * 16);
-    if (totals[0])
-        MeshBricksEmit(frame, cell, ids, cells, n, m.color ? color_ids : nullptr, m.color ? color_cells : nullptr, m.color ? n_color : 0, scratch.get(),
-                       nbytes, totals, active.get<long long>(), offsets.get<unsigned>(), dv.get<float>(), dn.get<float>(), dc.get<float>());
+    const unsigned* const cids = m.color ? color_ids : nullptr;
+    const void* const ccells = m.color ? color_cells : nullptr;
+    const size_t nc = m.color ? n_color : 0;
+    if (totals[0] && indexed)   // (the indexed emit reads the plan's scratch too: the bricks' neighbours)
+        MeshBricksEmitIndexed(frame, cell, ids, cells, n, cids, ccells, nc, scratch.get(), nbytes, xscratch.get(), xbytes, totals, nv, dv.get<float>(),
+                              dn.get<float>(), dc.get<float>(), faces.get<unsigned>());
+    else if (totals[0])
+        MeshBricksEmit(frame, cell, ids, cells, n, cids, ccells, nc, scratch.get(), nbytes, totals, active.get<long long>(), offsets.get<unsigned>(),
+                       dv.get<float>(), dn.get<float>(), dc.get<float>());
     m.v.resize(nv * 3); m.n.resize(nv * 3); m.c.resize(m.color ? nv * 4 : 0);
     dv.CopyTo(m.v.data(), nv * 12);
     dn.CopyTo(m.n.data(), nv * 12);
     dc.CopyTo(m.c.data(), m.c.size() * 4);
-    if (cube_index) { cube_index->resize(totals[0]); active.CopyTo(cube_index->data(), totals[0] * 8); }
-    if (tri_offset) { tri_offset->resize(totals[0]); offsets.CopyTo(tri_offset->data(), totals[0] * 4); }
+    faces.CopyTo(m.faces.data(), m.faces.size() * 4);
+    if (cube_index && !indexed) { cube_index->resize(totals[0]); active.CopyTo(cube_index->data(), totals[0] * 8); }
+    if (tri_offset && !indexed) { tri_offset->resize(totals[0]); offsets.CopyTo(tri_offset->data(), totals[0] * 4); }
     return m;
 }
 }
@@ -257,7 +246,7 @@ inline size_t SaveMeshBricks(std::string filename, const kfx_volume& frame, int 
 inline size_t SaveMeshBricksIndexed(std::string filename, const kfx_volume& frame, int cell, const unsigned* ids, const void* cells, size_t n,
                                     size_t* nvert = nullptr)
 {
-    const mesh_detail::HostMesh m = mesh_detail::ExtractBricksIndexed(frame, cell, ids, cells, n, nullptr, nullptr, 0, false);
+    const mesh_detail::HostMesh m = mesh_detail::ExtractBricks(frame, cell, ids, cells, n, nullptr, nullptr, 0, false, true);
     if (nvert) *nvert = m.nvert;
     return mesh_detail::WritePly(filename + ".ply", m);
 }
@@ -265,7 +254,7 @@ inline size_t SaveMeshBricksIndexed(std::string filename, const kfx_volume& fram
 inline size_t SaveMeshBricksIndexed(std::string filename, const kfx_volume& frame, int cell, const unsigned* ids, const void* cells, size_t n,
                                     const unsigned* color_ids, const void* color_cells, size_t n_color, size_t* nvert = nullptr)
 {
-    const mesh_detail::HostMesh m = mesh_detail::ExtractBricksIndexed(frame, cell, ids, cells, n, color_ids, color_cells, n_color, true);
+    const mesh_detail::HostMesh m = mesh_detail::ExtractBricks(frame, cell, ids, cells, n, color_ids, color_cells, n_color, true, true);
     if (nvert) *nvert = m.nvert;
     return mesh_detail::WritePly(filename + ".ply", m);
 }

@@ -17,20 +17,18 @@
 //               compacted on the device, then k_mc_emit.  fp32 and half cells, whole volumes and Z-slabs.
 //   indexed (kfx_mesh_index.h: kfx_mesh_index_plan / kfx_mesh_emit_indexed)   the soup's plan, then its vertices welded by lattice edge:
 //               one vertex per edge and a face list, k_mc_emit_indexed.
-// What the emit kernels and the ownership pass share -- the cube's decode and corner read, the vertex's position, attributes and
-// store -- is defined once, so that the indexed mesh stays the weld of the soup bit for bit; the part that does not depend on how a
-// cell is read lives in mesh_cube.h, which the extractor of packed bricks (mesh_bricks.hip, kfx_mesh_bricks.h) includes too.
+// k_mc_emit, k_mesh_own, k_mc_emit_indexed, the scan kernel and the case tables are mesh_cube.h's, written over a cube source and
+// shared with the extractor of packed bricks (mesh_bricks.hip).  This file has the dense source, DenseCubes -- the corner read from
+// pitched rows, the normal and grey with a slab's stored-plane rule, the dense owner rule --, the plan passes over segments of a
+// column, the byte-per-cube count, and the host side of the three ABIs.
 // The case tables (mc_tables.inc) are derived by scripts/gen_mc_tables.py from the cube's topology; their boundary
 // loops and winding equal the classic tables' in all 256 cases (tests/test_mesh_cpu.py).
-#include "mesh_cube.h"   // the case tables and everything about one cube that the brick extractor (mesh_bricks.hip) shares
+#define KFX_MESH_UNIT dense_mesh
+#include "mesh_cube.h"
 #include "../../include/kfx_mesh.h"
 #include "../../include/kfx_mesh_index.h"
 
 namespace kfx {
-
-__constant__ unsigned char c_num_tris[256];
-__constant__ unsigned short c_edge_mask[256];
-__constant__ signed char c_tris[256][15];
 
 // values at the 8 corners and their corner_case.  Half cells are widened
 // exactly (SDF_h's operator float), so a half volume's cubes are those of the widened fp32 volume.
@@ -105,82 +103,6 @@ __device__ __forceinline__ void edge_attributes(const MeshParams& p, const Color
     grey = (has_color && stored) ? trilinear<RayC32>(cv, pos) : 0.f;
 }
 
-// A listed cube as its thread sees it: position, case, triangle count, the mask of its edges with a vertex, corner values
-struct ActiveCube {
-    int x, y, z, flag, ntri;
-    unsigned mask;
-    float v[8];
-};
-
-// cube ci; false if it has no triangles or a corner that is not finite (a cube of a plan's list has neither).  For k_mc_emit_indexed
-// and k_mesh_own; k_mc_emit keeps the same steps in locals.
-template <typename CELL>
-__device__ __forceinline__ bool active_cube(const MeshParams& p, long long ci, ActiveCube& c)
-{
-    cube_xyz(p, ci, c.x, c.y, c.z);
-    const bool finite = cube_case<CELL>(p, c.x, c.y, c.z, c.v, c.flag);
-    c.ntri = c_num_tris[c.flag];
-    c.mask = c_edge_mask[c.flag];
-    return finite && c.ntri != 0;
-}
-
-// One thread per ACTIVE cube (cube_index lists the cubes with triangles in emission order; tri_offset their first
-// triangle): dense lanes instead of the ~1 % active lanes of a thread-per-cube sweep.  CELL: fp32 or half cells; SLAB: p holds
-// the full volume's geometry over a slab's planes [avail_lo, avail_hi) (virtual base pointer, slab_full_volume), and so does cv for
-// the rank's colour slab, which has the SDF slab's geometry.
-template <typename CELL, bool SLAB>
-__global__ __launch_bounds__(128) void k_mc_emit(const MeshParams p, const ColorGeom cv, const int has_color,
-                                                 const long long* __restrict__ cube_index, const unsigned* __restrict__ tri_offset,
-                                                 const long long n_active, float* __restrict__ verts,
-                                                 float* __restrict__ norms, float* __restrict__ colors)
-{
-    const long long t_id = (long long)blockIdx.x * 128 + threadIdx.x;
-    if (t_id >= n_active) return;
-    // active_cube's steps in locals: through the struct this kernel -- 36 per-edge values live -- compiles to other code, which
-    // measured 1 % slower at 1024^3 (profiles/mesh_refactor/ab_timing.txt)
-    int x, y, z, flag;
-    cube_xyz(p, cube_index[t_id], x, y, z);
-    float v[8];
-    if (!cube_case<CELL>(p, x, y, z, v, flag)) return;
-    const int ntri = c_num_tris[flag];
-    if (ntri == 0) return;
-    const unsigned mask = c_edge_mask[flag];
-    const V3 p0 = cube_origin(p, x, y, z);
-    V3 ev[12], en[12];
-    float ec[12];
-#pragma unroll
-    for (int e = 0; e < 12; ++e) {
-        if (!(mask & (1u << e))) continue;
-        ev[e] = edge_position(p, p0, v, e);
-        edge_attributes<CELL, SLAB>(p, cv, has_color, ev[e], en[e], ec[e]);
-    }
-    size_t o = (size_t)tri_offset[t_id] * 3; // first output vertex of this cube
-    for (int t = 0; t < ntri * 3; ++t, ++o) {
-        const int e = c_tris[flag][t];
-        V3 P = v3(0.f, 0.f, 0.f), N = P;
-        float C = 0.f;
-#pragma unroll
-        for (int k = 0; k < 12; ++k)   // select without dynamic register indexing (one loop for the three arrays: a shared
-            if (k == e) { P = ev[k]; N = en[k]; C = ec[k]; }   // per-array select measured slower here, same file)
-        store_vertex(verts, norms, colors, o, P, N, C, has_color);
-    }
-}
-
-static bool g_tables_loaded[64] = {};
-
-static int load_tables()
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (g_tables_loaded[dev]) return 0;
-    hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(c_num_tris), MC_NUM_TRIS, sizeof(MC_NUM_TRIS));
-    if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(c_edge_mask), MC_EDGE_MASK, sizeof(MC_EDGE_MASK));
-    if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(c_tris), MC_TRIS, sizeof(MC_TRIS));
-    if (e != hipSuccess) return set_error((int)e, hipGetErrorString(e));
-    g_tables_loaded[dev] = true;
-    return 0;
-}
-
 // the colour volume of an emit: sampled only when it IsValid(), every dimension >= 8 (BoundedVolume.h:84-87)
 static int color_params(ColorGeom& cv, int& has_color, const kfx_volume* colorvol, const float* colors)
 {
@@ -200,10 +122,10 @@ static int color_params(ColorGeom& cv, int& has_color, const kfx_volume* colorvo
 //   k_mesh_count     one lane per segment, lanes of a wave on x-adjacent columns (coalesced corner rows); the lane walks z and
 //                    keeps plane z+1's corner pairs as the next cube's plane z.  Writes seg_pack(active cubes, triangles), 16 bits.
 //   k_mesh_reduce    sums of MESH_BLOCK consecutive segments (the scan's upsweep)
-//   k_mesh_scan_partials  one workgroup: exclusive 64-bit scan of the block sums, and the totals
+//   k_mesh_scan_partials  mesh_cube.h's: exclusive 64-bit scan of the block sums, and the totals
 //   k_mesh_compact   the downsweep inside each block (LDS), then one lane per ACTIVE segment re-walks its cubes and writes the
 //                    active cubes' global indices (int64) and first triangles (uint32) at the scanned offsets
-//   k_mc_emit        as kfx_mc_emit
+//   k_mc_emit        mesh_cube.h's, as kfx_mc_emit
 // Kernel boundaries order the passes: no in-launch hand-off between workgroups.
 constexpr int MESH_SEG = 64;         // cubes per segment: 8 segments per column at 512^3, 32 at 2048^3
 constexpr int MESH_SEG_TILE = 32;    // segments per column and count workgroup (grid z covers the rest)
@@ -292,13 +214,6 @@ __global__ __launch_bounds__(256) void k_mesh_reduce(const unsigned short* __res
         t += seg_tris(n);
     }
     store_block_sums(a, t, part);
-}
-
-// one workgroup: exclusive 64-bit offsets of the blocks (base[2 b] cubes, base[2 b + 1] triangles) and the totals
-__global__ __launch_bounds__(MESH_SCAN_THREADS) void k_mesh_scan_partials(const unsigned* __restrict__ part, const long long nblk,
-                                                                          unsigned long long* __restrict__ base, unsigned long long* __restrict__ totals)
-{
-    scan_block_sums(part, nblk, base, totals);
 }
 
 // One workgroup per block of MESH_BLOCK segments: the block's exclusive offsets in LDS (thread t scans its MESH_PER_THREAD
@@ -426,8 +341,8 @@ static MeshScratch mesh_scratch(const MeshRange& r, const void* scratch)
 //   k_mesh_vertex_base  every active cube's first vertex id (4 bytes)
 //   k_mc_emit_indexed   one lane per active cube: owned edges write their vertex at base + rank, rank = first use among the owned
 //                       edges in c_tris[flag]; every triangle corner writes base(owner) + rank(edge in owner)
-// How an edge is named in its owner and ranked among the owner's edges, and k_mesh_vertex_base, are mesh_cube.h's: the index of
-// packed bricks (mesh_bricks.hip) shares them and differs in the owner rule alone.
+// All but k_mesh_compact are mesh_cube.h's, as is how an edge is named in its owner and ranked among the owner's edges: the index of
+// packed bricks (mesh_bricks.hip) differs in the owner rule alone.  The dense rule is edge_owner, below.
 
 // position of cube c in the ascending cube_index[0, n), -1 if it is not listed
 __device__ __forceinline__ long long find_cube(const long long* __restrict__ cube_index, long long n, long long c)
@@ -473,82 +388,40 @@ __device__ __forceinline__ long long edge_owner(const MeshParams& p, const long 
     return t;
 }
 
-// info[t] = flag | owned edges << 8; part[2 b] = vertices, part[2 b + 1] = triangles of block b's cubes.  hdr[2], hdr[3]: the totals
-// this index was planned for (hdr[0], hdr[1] are the scan's: vertices, triangles).
-template <typename CELL>
-__global__ __launch_bounds__(MESH_IDX_BLOCK) void k_mesh_own(const MeshParams p, const long long* __restrict__ cube_index, const long long n_active,
-                                                             const unsigned long long n_tris, unsigned* __restrict__ info,
-                                                             unsigned* __restrict__ part, unsigned long long* __restrict__ hdr)
-{
-    static_assert(MESH_IDX_BLOCK == 256, "store_block_sums");
-    const long long t = (long long)blockIdx.x * MESH_IDX_BLOCK + threadIdx.x;
-    unsigned nv = 0, nt = 0;
-    if (t < n_active) {
-        const long long ci = cube_index[t];
-        ActiveCube c;
-        active_cube<CELL>(p, ci, c);   // (listed by the plan: it is active)
-        unsigned own = 0;
-#pragma unroll
-        for (int e = 0; e < 12; ++e) {
-            if (!(c.mask & (1u << e))) continue;
-            int oe;
-            if (edge_owner(p, cube_index, t, ci, c.x, c.y, c.z, e, oe) == t) own |= 1u << e;
-        }
-        info[t] = (unsigned)c.flag | (own << 8);
-        nv = __popc(own);
-        nt = c.ntri;
-    }
-    store_block_sums(nv, nt, part);
-    if (threadIdx.x == 0 && blockIdx.x == 0) { hdr[2] = (unsigned long long)n_active; hdr[3] = n_tris; }
-}
-
-// k_mc_emit with shared vertices: positions, normals and colours by k_mc_emit's expressions, computed by the owner only
+// The dense volume as mesh_cube.h's cube source: every listed cube can be read.  CELL: fp32 or half cells; SLAB: p holds the full
+// volume's geometry over a slab's planes [avail_lo, avail_hi) (virtual base pointer, slab_full_volume), and so does cv for the rank's
+// colour slab, which has the SDF slab's geometry.
 template <typename CELL, bool SLAB>
-__global__ __launch_bounds__(128) void k_mc_emit_indexed(const MeshParams p, const ColorGeom cv, const int has_color,
-                                                         const long long* __restrict__ cube_index, const unsigned* __restrict__ tri_offset,
-                                                         const unsigned* __restrict__ info, const unsigned* __restrict__ vbase,
-                                                         const long long n_active, const unsigned long long n_verts, float* __restrict__ verts,
-                                                         float* __restrict__ norms, float* __restrict__ colors, unsigned* __restrict__ faces)
-{
-    const long long t_id = (long long)blockIdx.x * 128 + threadIdx.x;
-    if (t_id >= n_active) return;
-    const long long ci = cube_index[t_id];
-    ActiveCube c;
-    if (!active_cube<CELL>(p, ci, c)) return;
-    const unsigned own = info[t_id] >> 8, first = vbase[t_id];
-    const unsigned long long ranks = edge_ranks(c_tris[c.flag], c.ntri, own);
-    const V3 p0 = cube_origin(p, c.x, c.y, c.z);
-    unsigned id[12];
-#pragma unroll
-    for (int e = 0; e < 12; ++e) {
-        id[e] = 0;
-        if (!(c.mask & (1u << e))) continue;
-        if (own & (1u << e)) {
-            const size_t i = first + rank_of(ranks, e);
-            id[e] = (unsigned)i;
-            if (i >= n_verts) continue;
-            const V3 pos = edge_position(p, p0, c.v, e);
-            V3 n;
-            float grey;
-            edge_attributes<CELL, SLAB>(p, cv, has_color, pos, n, grey);
-            store_vertex(verts, norms, colors, i, pos, n, grey, has_color);
-        } else {
-            int oe;
-            const long long j = edge_owner(p, cube_index, t_id, ci, c.x, c.y, c.z, e, oe);
-            const unsigned oi = info[j];
-            id[e] = vbase[j] + rank_of(edge_ranks(c_tris[oi & 255u], c_num_tris[oi & 255u], oi >> 8), oe);
-        }
+struct DenseCubes {
+    MeshParams p;
+    ColorGeom cv;
+    int has_color;
+    struct Home {};
+    static constexpr bool VERIFIES_LIST = false;
+    __device__ __forceinline__ bool position(long long ci, int& x, int& y, int& z) const
+    {
+        cube_xyz(p, ci, x, y, z);
+        return true;
     }
-    size_t o = (size_t)tri_offset[t_id] * 3; // first face corner of this cube
-    for (int t = 0; t < c.ntri * 3; ++t, ++o) {
-        const int e = c_tris[c.flag][t];
-        unsigned I = 0;
-#pragma unroll
-        for (int k = 0; k < 12; ++k)   // select without dynamic register indexing
-            if (k == e) I = id[k];
-        faces[o] = I;
+    __device__ __forceinline__ bool locate(int, int, int, Home&) const { return true; }
+    __device__ __forceinline__ bool corners(const Home&, int x, int y, int z, float v[8], int& flag) const { return cube_case<CELL>(p, x, y, z, v, flag); }
+    __device__ __forceinline__ void attributes(const Home&, const V3& pos, V3& normal, float& grey) const
+    {
+        edge_attributes<CELL, SLAB>(p, cv, has_color, pos, normal, grey);
     }
-}
+    // (the plan counted this cube from these cells: its slots are its triangles)
+    __device__ __forceinline__ bool slots(const unsigned* tri_offset, long long t, long long, int ntri, unsigned long long& first, int& planned) const
+    {
+        first = tri_offset[t];
+        planned = ntri;
+        return true;
+    }
+    __device__ __forceinline__ long long owner(const long long* cube_index, long long, long long t, long long ci, int x, int y, int z, const Home&,
+                                               int e, int& oe) const
+    {
+        return edge_owner(p, cube_index, t, ci, x, y, z, e, oe);
+    }
+};
 
 // index scratch: [header: vertices, triangles, planned cubes, planned triangles][cube_index, 8 B][tri_offset, 4 B][info, 4 B]
 // [vbase, 4 B] per active cube, [block sums, 8 B][block offsets, 16 B] per MESH_IDX_BLOCK active cubes
@@ -626,7 +499,7 @@ static int mesh_call(MeshCall& c, const char* what, int takes, const kfx_volume*
 }
 
 // One call of f with the tag of a (cell, slab) pair: the template arguments of the kernels
-template <typename CELL_, bool SLAB_> struct MeshKind { using CELL = CELL_; static constexpr bool SLAB = SLAB_; };
+template <typename CELL_, bool SLAB> struct MeshKind { using CELL = CELL_; using Cubes = DenseCubes<CELL_, SLAB>; };
 template <typename F>
 static void for_mesh_kind(int cell, bool slab, F f)
 {
@@ -665,7 +538,8 @@ extern "C" int kfx_mc_emit(const kfx_volume* vol, const kfx_volume* colorvol, co
     int has_color = 0;
     if (int e = color_params(cv, has_color, colorvol, colors)) return e;
     if (n_active > 0x7fffffffLL * 128) return set_error(KFX_E_RANGE, "SaveMesh: too many active cubes");
-    hipLaunchKernelGGL((k_mc_emit<RayF32, false>), dim3((unsigned)((n_active + 127) / 128)), dim3(128), 0, (hipStream_t)stream, p, cv, has_color,
+    using Cubes = DenseCubes<RayF32, false>;
+    hipLaunchKernelGGL(k_mc_emit<Cubes>, dim3((unsigned)((n_active + 127) / 128)), dim3(128), 0, (hipStream_t)stream, (Cubes{p, cv, has_color}),
                        cube_index, tri_offset, n_active, verts, norms, colors);
     return check_launch("kfx_mc_emit");
 }
@@ -735,8 +609,8 @@ extern "C" int kfx_mesh_emit(const kfx_volume* vol, int cell, const kfx_slab* sl
         using K = decltype(kind);
         hipLaunchKernelGGL(k_mesh_compact<typename K::CELL>, dim3((unsigned)c.r.nblk), dim3(256), 0, st, c.p, c.r, c.s.seg, c.s.base, cube_index,
                            tri_offset, totals[0], totals[1]);
-        hipLaunchKernelGGL((k_mc_emit<typename K::CELL, K::SLAB>), dim3((unsigned)((n_active + 127) / 128)), dim3(128), 0, st, c.p, cv, has_color,
-                           cube_index, tri_offset, n_active, verts, norms, has_color ? colors : nullptr);
+        hipLaunchKernelGGL(k_mc_emit<typename K::Cubes>, dim3((unsigned)((n_active + 127) / 128)), dim3(128), 0, st,
+                           (typename K::Cubes{c.p, cv, has_color}), cube_index, tri_offset, n_active, verts, norms, has_color ? colors : nullptr);
     });
     return check_launch("kfx_mesh_emit");
 }
@@ -771,8 +645,9 @@ extern "C" int kfx_mesh_index_plan(const kfx_volume* vol, int cell, const kfx_sl
         using CELL = typename decltype(kind)::CELL;
         hipLaunchKernelGGL(k_mesh_compact<CELL>, dim3((unsigned)c.r.nblk), dim3(256), 0, st, c.p, c.r, c.s.seg, c.s.base, x.cube_index,
                            x.tri_offset, totals[0], totals[1]);
-        hipLaunchKernelGGL(k_mesh_own<CELL>, dim3((unsigned)x.nblk), dim3(MESH_IDX_BLOCK), 0, st, c.p, x.cube_index, n_active, totals[1], x.info,
-                           x.part, x.hdr);
+        using Cubes = DenseCubes<CELL, false>;
+        hipLaunchKernelGGL(k_mesh_own<Cubes>, dim3((unsigned)x.nblk), dim3(MESH_IDX_BLOCK), 0, st, (Cubes{c.p, ColorGeom{}, 0}), x.cube_index,
+                           x.tri_offset, n_active, totals[1], x.info, x.part, x.hdr);
         hipLaunchKernelGGL(k_mesh_scan_partials, dim3(1), dim3(MESH_SCAN_THREADS), 0, st, x.part, x.nblk, x.base, x.hdr);
         hipLaunchKernelGGL(k_mesh_vertex_base, dim3((unsigned)x.nblk), dim3(MESH_IDX_BLOCK), 0, st, x.info, n_active, x.base, x.vbase);
     });
@@ -806,9 +681,9 @@ extern "C" int kfx_mesh_emit_indexed(const kfx_volume* vol, int cell, const kfx_
     const long long n_active = (long long)totals[0];
     for_mesh_kind(cell, slab != nullptr, [&](auto kind) {   // (colours: as kfx_mesh_emit)
         using K = decltype(kind);
-        hipLaunchKernelGGL((k_mc_emit_indexed<typename K::CELL, K::SLAB>), dim3((unsigned)((n_active + 127) / 128)), dim3(128), 0, st, c.p, cv,
-                           has_color, x.cube_index, x.tri_offset, x.info, x.vbase, n_active, n_verts, verts, norms, has_color ? colors : nullptr,
-                           faces);
+        hipLaunchKernelGGL(k_mc_emit_indexed<typename K::Cubes>, dim3((unsigned)((n_active + 127) / 128)), dim3(128), 0, st,
+                           (typename K::Cubes{c.p, cv, has_color}), x.cube_index, x.tri_offset, x.info, x.vbase, n_active, n_verts, verts, norms,
+                           has_color ? colors : nullptr, faces);
     });
     return check_launch("kfx_mesh_emit_indexed");
 }

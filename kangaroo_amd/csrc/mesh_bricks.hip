@@ -1,9 +1,11 @@
 // mesh_bricks.hip -- marching cubes straight from packed 8 x 8 x 8 bricks (include/kfx_mesh_bricks.h): the mesh of a FRAME, a virtual
 // dense volume of which only the listed bricks exist and every other cell is NaN (colour: 0.5), without that volume.  The result is
-// the dense extractor's (mesh.hip) on the volume the bricks would unpack into, bit for bit: a cube's case, a vertex's position, the
-// normalisation and the store are mesh_cube.h's, shared with it; the frame's geometry is a MeshParams filled by the same set_geometry;
-// the gradient stencil and the colour blend are sampling.h's own (gradient_over, trilinear_over: the dense samplers' base cell and blend)
-// over a cell accessor that goes through the brick lists.
+// the dense extractor's (mesh.hip) on the volume the bricks would unpack into, bit for bit, because the kernels that make vertices
+// and faces are the dense extractor's own: mesh_cube.h's k_mc_emit, k_mesh_own and k_mc_emit_indexed, instantiated here over
+// BrickCubes, the cube source that reads a cube's cells through the brick lists.  The frame's geometry is a MeshParams filled by the
+// same set_geometry; the gradient stencil and the colour blend are sampling.h's own (gradient_over, trilinear_over: the dense
+// samplers' base cell and blend) over BrickCells.  This file has that source -- with the slot clamp and the brick owner rule --, the
+// plan passes over bricks, and the host side of the two ABIs.
 //
 //   k_bm_neighbours   one lane per (listed brick, neighbour): the neighbour's position in the ascending id list by binary search, -1
 //                     if absent -- 27 positions per brick, the brick's own among them.  After this a frame cell within 8 cells of a
@@ -11,38 +13,21 @@
 //   k_bm_count        one workgroup per listed brick: its 9 x 9 x 9 corner values in LDS (2916 bytes) -- its own 8^3 by one 16- / 8-byte
 //                     load per lane, the +1 faces, edges and corner from up to seven neighbours -- then two cubes per lane, those
 //                     inside the frame's (w - 1, h - 1, d - 1); active cubes and triangles of the brick, 4 bytes.
-//   k_bm_reduce, k_bm_scan   sums of 256 bricks, their exclusive offsets and the totals (mesh_cube.h's scan)
+//   k_bm_reduce, k_mesh_scan_partials   sums of 256 bricks, their exclusive offsets and the totals (mesh_cube.h's scan)
 //   k_bm_compact      one workgroup per listed brick with cubes: stages and classifies again, ranks its active cubes in dense order
 //                     (lane t holds cubes 2 t, 2 t + 1 of the brick in x-major order = ascending ci) and writes cube_index / tri_offset
-//   k_bm_emit         one lane per ACTIVE cube, as k_mc_emit: the cube's brick by binary search, corners and stencils through the
-//                     neighbour table
-//   k_bm_first, k_bm_own, k_bm_emit_indexed   the indexed output (include/kfx_mesh_bricks_index.h): that soup welded by lattice edge;
-//                     described where they stand, below the soup's kernels
+//   k_mc_emit         mesh_cube.h's, one lane per ACTIVE cube: the cube's brick by binary search (BrickCubes::locate), corners and
+//                     stencils through the neighbour table
+//   k_bm_first, k_mesh_own, k_mc_emit_indexed   the indexed output (include/kfx_mesh_bricks_index.h): that soup welded by lattice
+//                     edge; described above k_bm_first
 // Memory: the lists, about 112 (colour: 220) bytes of scratch per listed brick, the outputs; with the index 20 bytes per active cube
 // and 4 per listed brick more.  Nothing in proportion to the frame.
 // No global atomics, nothing between workgroups of one launch: ordering comes from the stream.
+#define KFX_MESH_UNIT brick_mesh
 #include "mesh_cube.h"
 #include "mesh_bricks_host.h"
 
 namespace kfx {
-
-__constant__ unsigned char c_bm_num_tris[256];
-__constant__ unsigned short c_bm_edge_mask[256];
-__constant__ signed char c_bm_tris[256][15];
-
-static bool g_bm_tables_loaded[64] = {};
-static int bm_load_tables()
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (g_bm_tables_loaded[dev]) return 0;
-    hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(c_bm_num_tris), MC_NUM_TRIS, sizeof(MC_NUM_TRIS));
-    if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(c_bm_edge_mask), MC_EDGE_MASK, sizeof(MC_EDGE_MASK));
-    if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(c_bm_tris), MC_TRIS, sizeof(MC_TRIS));
-    if (e != hipSuccess) return set_error((int)e, hipGetErrorString(e));
-    g_bm_tables_loaded[dev] = true;
-    return 0;
-}
 
 // the frame's brick grid as the kernels see it
 struct BrickGrid {
@@ -161,7 +146,7 @@ __device__ __forceinline__ void brick_cube_counts(const MeshParams& p, const uns
 #pragma unroll
             for (int c = 0; c < 8; ++c) v[c] = lds[((lz + corner_dz(c)) * BM_HALO + ly + corner_dy(c)) * BM_HALO + lx + corner_dx(c)];
             int flag;
-            if (corner_case(v, flag)) nt = c_bm_num_tris[flag];
+            if (corner_case(v, flag)) nt = c_num_tris[flag];
         }
         n_tri[j] = nt;
     }
@@ -202,12 +187,6 @@ __global__ __launch_bounds__(256) void k_bm_reduce(const unsigned* __restrict__ 
     store_block_sums(bm_active(c), bm_tris(c), part);
 }
 
-__global__ __launch_bounds__(MESH_SCAN_THREADS) void k_bm_scan(const unsigned* __restrict__ part, const long long nblk,
-                                                               unsigned long long* __restrict__ base, unsigned long long* __restrict__ totals)
-{
-    scan_block_sums(part, nblk, base, totals);
-}
-
 // grid: one workgroup per listed brick.  The brick's first cube and triangle = its scan block's offsets + the counts of the bricks
 // before it in the block; its active cubes follow in dense order.  Writes stop at the caller's capacities.
 template <typename CELL>
@@ -246,80 +225,6 @@ __global__ __launch_bounds__(256) void k_bm_compact(const MeshParams p, const Br
     }
 }
 
-// Normal and grey colour of the vertex at pos of a cube whose cells `sdf` reads, home brick at position `home` of the list: mesh.hip's
-// edge_attributes over the brick lists (multiply-by-reciprocal normalisation, zero where that is not finite).  For k_bm_emit and
-// k_bm_emit_indexed, so that an owner's vertex has the soup's bits.
-template <typename CELL>
-__device__ __forceinline__ void brick_edge_attributes(const MeshParams& p, const ColorGeom& cv, const int has_color, const BrickCells<CELL>& sdf,
-                                                      const unsigned char* __restrict__ color_cells, const int* __restrict__ cnbr, const int home,
-                                                      const V3& pos, V3& normal, float& grey)
-{
-    const V3 deriv = gradient_over(p, sdf, pos);
-    V3 nrm = div_s(deriv, length(deriv));
-    if (!isfinite(nrm.x) || !isfinite(nrm.y) || !isfinite(nrm.z)) nrm = v3(0.f, 0.f, 0.f);
-    normal = nrm;
-    grey = 0.f;
-    if (has_color && cnbr) {
-        const BrickCells<RayC32> col{color_cells, cnbr + (size_t)home * BRICK_NEIGHBOURS, sdf.bx0, sdf.by0, sdf.bz0, 0.5f};
-        grey = trilinear_over(cv, col, pos);
-    } else if (has_color) {   // (no colour bricks at all: every cell reads 0.5)
-        grey = trilinear_over(cv, [](int, int, int) { return 0.5f; }, pos);
-    }
-}
-
-// k_mc_emit over bricks: one thread per active cube, the same steps and expressions
-template <typename CELL>
-__global__ __launch_bounds__(128) void k_bm_emit(const MeshParams p, const ColorGeom cv, const int has_color, const BrickGrid g,
-                                                 const unsigned* __restrict__ ids, const unsigned n, const unsigned char* __restrict__ cells,
-                                                 const int* __restrict__ nbr, const unsigned char* __restrict__ color_cells,
-                                                 const int* __restrict__ cnbr, const long long* __restrict__ cube_index,
-                                                 const unsigned* __restrict__ tri_offset, const long long n_active,
-                                                 const unsigned long long cap_tris, float* __restrict__ verts, float* __restrict__ norms,
-                                                 float* __restrict__ colors)
-{
-    const long long t_id = (long long)blockIdx.x * 128 + threadIdx.x;
-    if (t_id >= n_active) return;
-    int x, y, z, flag;
-    cube_xyz(p, cube_index[t_id], x, y, z);
-    if ((unsigned)x >= (unsigned)p.cx || (unsigned)y >= (unsigned)p.cy || (unsigned)z >= (unsigned)p.cz) return;
-    const int bx0 = x >> 3, by0 = y >> 3, bz0 = z >> 3;
-    const int home = find_brick(ids, n, ((unsigned)bz0 * (unsigned)g.nby + (unsigned)by0) * (unsigned)g.nbx + (unsigned)bx0);
-    if (home < 0) return;   // (a cube of a plan's list has its brick listed)
-    const BrickCells<CELL> sdf{cells, nbr + (size_t)home * BRICK_NEIGHBOURS, bx0, by0, bz0, __builtin_nanf("")};
-    float v[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) v[c] = sdf(x + corner_dx(c), y + corner_dy(c), z + corner_dz(c));
-    if (!corner_case(v, flag)) return;
-    const int ntri = c_bm_num_tris[flag];
-    if (ntri == 0) return;
-    const unsigned mask = c_bm_edge_mask[flag];
-    const V3 p0 = cube_origin(p, x, y, z);
-    V3 ev[12], en[12];
-    float ec[12];
-#pragma unroll
-    for (int e = 0; e < 12; ++e) {
-        if (!(mask & (1u << e))) continue;
-        ev[e] = edge_position(p, p0, v, e);
-        brick_edge_attributes(p, cv, has_color, sdf, color_cells, cnbr, home, ev[e], en[e], ec[e]);
-    }
-    // The cube's slots are those the plan counted for it: [tri_offset[t_id], the next cube's offset or the total).  With ascending ids
-    // that is ntri triangles.  With repeated or unsorted ids the search above may land on another entry than the one the cube was
-    // counted from (k_bm_count and k_bm_compact go by list position), and ntri may differ: nothing is written outside the cube's slots.
-    const unsigned long long first = tri_offset[t_id], next = t_id + 1 < n_active ? (unsigned long long)tri_offset[t_id + 1] : cap_tris;
-    if (next < first || next > cap_tris) return;
-    const int planned = (int)(next - first < 5 ? next - first : 5);
-    size_t o = (size_t)first * 3; // first output vertex of this cube
-    for (int t = 0; t < min(ntri, planned) * 3; ++t, ++o) {
-        const int e = c_bm_tris[flag][t];
-        V3 P = v3(0.f, 0.f, 0.f), N = P;
-        float C = 0.f;
-#pragma unroll
-        for (int k = 0; k < 12; ++k)   // select without dynamic register indexing
-            if (k == e) { P = ev[k]; N = en[k]; C = ec[k]; }
-        store_vertex(verts, norms, colors, o, P, N, C, has_color);
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // Indexed extraction (include/kfx_mesh_bricks_index.h): the brick soup welded by lattice edge into its sequential first-occurrence
 // mesh.  As mesh.hip's index, with the soup's order the bricks': the compacted cube list is in that order, so "first in brick-soup
@@ -328,13 +233,13 @@ __global__ __launch_bounds__(128) void k_bm_emit(const MeshParams p, const Color
 // [first[b], first[b + 1]) of the cube list gives the cube's -- and the lowest position among those found owns the edge.  (The dense
 // rule looks only at the cubes before this one in dense order and stops at the first: here the componentwise-minimum cube may be
 // missing and the two diagonal ones are ordered by their bricks.)
-//   k_bm_compact         as above, into the index scratch
-//   k_bm_first           every listed brick's first cube position (4 bytes)
-//   k_bm_own             one lane per active cube: case flag and the 12-bit mask of the edges it owns (4 bytes), block sums
-//   k_bm_scan            as above: the blocks' first vertex ids, the vertex total
-//   k_mesh_vertex_base   mesh_cube.h's: every active cube's first vertex id (4 bytes)
-//   k_bm_emit_indexed    one lane per active cube: owned edges write their vertex at base + rank; every triangle corner writes
-//                        base(owner) + rank(edge in owner)
+//   k_bm_compact           as above, into the index scratch
+//   k_bm_first             every listed brick's first cube position (4 bytes)
+//   k_mesh_own             mesh_cube.h's, one lane per active cube: case flag and the 12-bit mask of the edges it owns, block sums
+//   k_mesh_scan_partials   as above: the blocks' first vertex ids, the vertex total
+//   k_mesh_vertex_base     mesh_cube.h's: every active cube's first vertex id (4 bytes)
+//   k_mc_emit_indexed      mesh_cube.h's, one lane per active cube: owned edges write their vertex at base + rank; every triangle
+//                          corner writes base(owner) + rank(edge in owner)
 // Every list position read from the scratches is compared with its list's length before use, and every vertex id with V and face
 // slot with the plan's before the store: lists that are not ascending give an unspecified mesh, no access out of bounds.
 
@@ -351,179 +256,118 @@ __global__ __launch_bounds__(256) void k_bm_first(const unsigned* __restrict__ c
     if (i < n) first[i] = (unsigned)base[2 * (size_t)blockIdx.x] + ex;
 }
 
-// the lists an index kernel finds cubes in
-struct BrickCubeList {
-    const long long* cube_index;   // [n_active], brick by brick
-    const unsigned* first;         // [n]: every listed brick's first cube
-    long long n_active;
+// The brick lists as mesh_cube.h's cube source.  A cube's Home is its brick: the position `at` of the list, and the cell accessor
+// through that brick's 27-neighbour row.
+template <typename CELL>
+struct BrickCubes {
+    MeshParams p;
+    ColorGeom cv;
+    int has_color;
+    BrickGrid g;
+    const unsigned* ids;                // [n], ascending
     unsigned n;
+    const unsigned char* cells;
+    const int* nbr;                     // [n][27]: k_bm_neighbours<true>'s
+    const unsigned char* color_cells;   // an emit's colour list and the SDF bricks' neighbours in it, or null
+    const int* cnbr;
+    unsigned long long cap_tris;        // the plan's triangle total
+    const unsigned* first;              // an index kernel's: [n], every listed brick's first cube in the cube list
+    static constexpr bool VERIFIES_LIST = true;
+    struct Home {
+        int at;
+        BrickCells<CELL> sdf;
+    };
+
+    // false if ci is no cube of the frame (a negative ci has a negative coordinate)
+    __device__ __forceinline__ bool position(long long ci, int& x, int& y, int& z) const
+    {
+        cube_xyz(p, ci, x, y, z);
+        return (unsigned)x < (unsigned)p.cx && (unsigned)y < (unsigned)p.cy && (unsigned)z < (unsigned)p.cz;
+    }
+    // false if the cube's brick is not listed (a cube of a plan's list has its brick listed)
+    __device__ __forceinline__ bool locate(int x, int y, int z, Home& h) const
+    {
+        const int bx0 = x >> 3, by0 = y >> 3, bz0 = z >> 3;
+        h.at = find_brick(ids, n, ((unsigned)bz0 * (unsigned)g.nby + (unsigned)by0) * (unsigned)g.nbx + (unsigned)bx0);
+        if (h.at < 0) return false;
+        h.sdf = BrickCells<CELL>{cells, nbr + (size_t)h.at * BRICK_NEIGHBOURS, bx0, by0, bz0, __builtin_nanf("")};
+        return true;
+    }
+    __device__ __forceinline__ bool corners(const Home& h, int x, int y, int z, float v[8], int& flag) const
+    {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) v[c] = h.sdf(x + corner_dx(c), y + corner_dy(c), z + corner_dz(c));
+        return corner_case(v, flag);
+    }
+    // mesh.hip's edge_attributes over the brick lists: multiply-by-reciprocal normalisation, zero where that is not finite
+    __device__ __forceinline__ void attributes(const Home& h, const V3& pos, V3& normal, float& grey) const
+    {
+        const V3 deriv = gradient_over(p, h.sdf, pos);
+        V3 nrm = div_s(deriv, length(deriv));
+        if (!isfinite(nrm.x) || !isfinite(nrm.y) || !isfinite(nrm.z)) nrm = v3(0.f, 0.f, 0.f);
+        normal = nrm;
+        grey = 0.f;
+        if (has_color && cnbr) {
+            const BrickCells<RayC32> col{color_cells, cnbr + (size_t)h.at * BRICK_NEIGHBOURS, h.sdf.bx0, h.sdf.by0, h.sdf.bz0, 0.5f};
+            grey = trilinear_over(cv, col, pos);
+        } else if (has_color) {   // (no colour bricks at all: every cell reads 0.5)
+            grey = trilinear_over(cv, [](int, int, int) { return 0.5f; }, pos);
+        }
+    }
+    // The cube's slots are those the plan counted for it: [tri_offset[t], the next cube's offset or the total).  With ascending ids
+    // that is ntri triangles.  With repeated or unsorted ids locate's search may land on another entry than the one the cube was
+    // counted from (k_bm_count and k_bm_compact go by list position), and ntri may differ: nothing is written outside the cube's slots.
+    __device__ __forceinline__ bool slots(const unsigned* tri_offset, long long t, long long n_active, int, unsigned long long& first_tri,
+                                          int& planned) const
+    {
+        first_tri = tri_offset[t];
+        const unsigned long long next = t + 1 < n_active ? (unsigned long long)tri_offset[t + 1] : cap_tris;
+        if (next < first_tri || next > cap_tris) return false;
+        planned = (int)(next - first_tri);   // (< 2^31: cap_tris < MESH_MAX_TRIS)
+        return true;
+    }
+    // Every other cube around the lattice edge (mesh_cube.h: lattice_edge) that lies in the frame is looked up: its brick is the
+    // home's or one of its neighbours (the cube is one cell away), whose list position the home's row holds.
+    __device__ __forceinline__ long long owner(const long long* cube_index, long long n_active, long long t, long long ci, int x, int y, int z,
+                                               const Home& h, int e, int& oe) const
+    {
+        const LatticeEdge le = lattice_edge(e);
+        const int a = le.a, u = le.u, w = le.w;
+        const int at[3] = {x, y, z}, cubes[3] = {p.cx, p.cy, p.cz};
+        const long long stride[3] = {(long long)p.cy * p.cz, (long long)p.cz, 1};
+        long long best = t;
+        oe = e;
+#pragma unroll
+        for (int su = 0; su < 2; ++su) {
+#pragma unroll
+            for (int sw = 0; sw < 2; ++sw) {
+                const int du = le.m[u] - su, dw = le.m[w] - sw;
+                if (du == 0 && dw == 0) continue;   // this cube
+                int q[3] = {at[0], at[1], at[2]};
+                q[u] += du;
+                q[w] += dw;
+                if (q[u] < 0 || q[u] >= cubes[u] || q[w] < 0 || q[w] >= cubes[w]) continue;
+                const int k = (((q[2] >> 3) - (at[2] >> 3) + 1) * 3 + (q[1] >> 3) - (at[1] >> 3) + 1) * 3 + (q[0] >> 3) - (at[0] >> 3) + 1;
+                const int b = h.sdf.nbr[k];
+                if (b < 0 || (unsigned)b >= n) continue;   // an absent brick: the cube touches unobserved cells
+                // the brick's cubes: [first[b], first[b + 1]) of the list, kept inside it
+                long long lo = first[b], hi = (unsigned)b + 1 < n ? (long long)first[b + 1] : n_active;
+                if (hi > n_active) hi = n_active;
+                const long long want = ci + du * stride[u] + dw * stride[w], end = hi;
+                while (lo < hi) {
+                    const long long mid = lo + ((hi - lo) >> 1);
+                    if (cube_index[mid] < want) lo = mid + 1;
+                    else hi = mid;
+                }
+                if (lo < end && lo < best && cube_index[lo] == want) {
+                    best = lo;
+                    oe = owner_e(a, su, sw);
+                }
+            }
+        }
+        return best;
+    }
 };
-
-// A listed cube as its thread sees it (mesh.hip's ActiveCube): position, home brick, case, triangle count, the mask of its edges
-// with a vertex, corner values
-struct BrickCube {
-    int x, y, z, home, flag, ntri;
-    unsigned mask;
-    float v[8];
-};
-
-// cube ci through the lists, k_bm_emit's steps; false if it is no cube of the frame, its brick is not listed, it has no triangles or a
-// corner that is not finite (a cube of a plan's list over ascending ids is none of these)
-template <typename CELL>
-__device__ __forceinline__ bool brick_active_cube(const MeshParams& p, const BrickGrid& g, const unsigned* __restrict__ ids, const unsigned n,
-                                                  const unsigned char* __restrict__ cells, const int* __restrict__ nbr, const long long ci, BrickCube& c)
-{
-    c.flag = c.ntri = 0;
-    c.mask = 0;
-    c.home = -1;
-    cube_xyz(p, ci, c.x, c.y, c.z);
-    if (ci < 0 || (unsigned)c.x >= (unsigned)p.cx || (unsigned)c.y >= (unsigned)p.cy || (unsigned)c.z >= (unsigned)p.cz) return false;
-    const int bx0 = c.x >> 3, by0 = c.y >> 3, bz0 = c.z >> 3;
-    c.home = find_brick(ids, n, ((unsigned)bz0 * (unsigned)g.nby + (unsigned)by0) * (unsigned)g.nbx + (unsigned)bx0);
-    if (c.home < 0) return false;
-    const BrickCells<CELL> sdf{cells, nbr + (size_t)c.home * BRICK_NEIGHBOURS, bx0, by0, bz0, __builtin_nanf("")};
-#pragma unroll
-    for (int k = 0; k < 8; ++k) c.v[k] = sdf(c.x + corner_dx(k), c.y + corner_dy(k), c.z + corner_dz(k));
-    const bool finite = corner_case(c.v, c.flag);
-    c.ntri = c_bm_num_tris[c.flag];
-    c.mask = c_bm_edge_mask[c.flag];
-    return finite && c.ntri != 0;
-}
-
-// The owner of the lattice edge under edge e of active cube c, position t of the cube list, index ci: its position in the list, and
-// in oe the edge's number there.  Every other cube around the edge (mesh_cube.h: lattice_edge) that lies in the frame is looked up:
-// its brick is the home's or one of its neighbours (the cube is one cell away), whose list position the home's row holds.
-__device__ __forceinline__ long long brick_edge_owner(const MeshParams& p, const int* __restrict__ nbr27, const BrickCubeList& l, const long long t,
-                                                      const long long ci, const BrickCube& c, const int e, int& oe)
-{
-    const LatticeEdge le = lattice_edge(e);
-    const int a = le.a, u = le.u, w = le.w;
-    const int at[3] = {c.x, c.y, c.z}, cubes[3] = {p.cx, p.cy, p.cz};
-    const long long stride[3] = {(long long)p.cy * p.cz, (long long)p.cz, 1};
-    long long best = t;
-    oe = e;
-#pragma unroll
-    for (int su = 0; su < 2; ++su) {
-#pragma unroll
-        for (int sw = 0; sw < 2; ++sw) {
-            const int du = le.m[u] - su, dw = le.m[w] - sw;
-            if (du == 0 && dw == 0) continue;   // this cube
-            int q[3] = {at[0], at[1], at[2]};
-            q[u] += du;
-            q[w] += dw;
-            if (q[u] < 0 || q[u] >= cubes[u] || q[w] < 0 || q[w] >= cubes[w]) continue;
-            const int k = (((q[2] >> 3) - (at[2] >> 3) + 1) * 3 + (q[1] >> 3) - (at[1] >> 3) + 1) * 3 + (q[0] >> 3) - (at[0] >> 3) + 1;
-            const int b = nbr27[k];
-            if (b < 0 || (unsigned)b >= l.n) continue;   // an absent brick: the cube touches unobserved cells
-            // the brick's cubes: [first[b], first[b + 1]) of the list, kept inside it
-            long long lo = l.first[b], hi = (unsigned)b + 1 < l.n ? (long long)l.first[b + 1] : l.n_active;
-            if (hi > l.n_active) hi = l.n_active;
-            const long long want = ci + du * stride[u] + dw * stride[w], end = hi;
-            while (lo < hi) {
-                const long long mid = lo + ((hi - lo) >> 1);
-                if (l.cube_index[mid] < want) lo = mid + 1;
-                else hi = mid;
-            }
-            if (lo < end && lo < best && l.cube_index[lo] == want) {
-                best = lo;
-                oe = owner_e(a, su, sw);
-            }
-        }
-    }
-    return best;
-}
-
-// info[t] = flag | owned edges << 8; part[2 b] = vertices, part[2 b + 1] = triangles of block b's cubes (the slots the plan counted:
-// the next cube's first triangle minus this one's).  hdr[2], hdr[3]: the totals this index was planned for (hdr[0], hdr[1] are the
-// scan's: vertices, triangles).
-template <typename CELL>
-__global__ __launch_bounds__(MESH_IDX_BLOCK) void k_bm_own(const MeshParams p, const BrickGrid g, const unsigned* __restrict__ ids, const unsigned n,
-                                                           const unsigned char* __restrict__ cells, const int* __restrict__ nbr,
-                                                           const BrickCubeList l, const unsigned* __restrict__ tri_offset,
-                                                           const unsigned long long n_tris, unsigned* __restrict__ info,
-                                                           unsigned* __restrict__ part, unsigned long long* __restrict__ hdr)
-{
-    static_assert(MESH_IDX_BLOCK == 256, "store_block_sums");
-    const long long t = (long long)blockIdx.x * MESH_IDX_BLOCK + threadIdx.x;
-    unsigned nv = 0, nt = 0;
-    if (t < l.n_active) {
-        const long long ci = l.cube_index[t];
-        BrickCube c;
-        unsigned own = 0;
-        if (brick_active_cube<CELL>(p, g, ids, n, cells, nbr, ci, c)) {
-            const int* const nbr27 = nbr + (size_t)c.home * BRICK_NEIGHBOURS;
-#pragma unroll
-            for (int e = 0; e < 12; ++e) {
-                if (!(c.mask & (1u << e))) continue;
-                int oe;
-                if (brick_edge_owner(p, nbr27, l, t, ci, c, e, oe) == t) own |= 1u << e;
-            }
-        }
-        info[t] = (unsigned)c.flag | (own << 8);
-        nv = __popc(own);
-        const unsigned long long first = tri_offset[t], next = t + 1 < l.n_active ? (unsigned long long)tri_offset[t + 1] : n_tris;
-        nt = next >= first && next <= n_tris ? (unsigned)(next - first) : 0u;
-    }
-    store_block_sums(nv, nt, part);
-    if (threadIdx.x == 0 && blockIdx.x == 0) { hdr[2] = (unsigned long long)l.n_active; hdr[3] = n_tris; }
-}
-
-// k_bm_emit with shared vertices: positions, normals and colours by k_bm_emit's expressions, computed by the owner only
-template <typename CELL>
-__global__ __launch_bounds__(128) void k_bm_emit_indexed(const MeshParams p, const ColorGeom cv, const int has_color, const BrickGrid g,
-                                                         const unsigned* __restrict__ ids, const unsigned n, const unsigned char* __restrict__ cells,
-                                                         const int* __restrict__ nbr, const unsigned char* __restrict__ color_cells,
-                                                         const int* __restrict__ cnbr, const BrickCubeList l,
-                                                         const unsigned* __restrict__ tri_offset, const unsigned* __restrict__ info,
-                                                         const unsigned* __restrict__ vbase, const unsigned long long cap_tris,
-                                                         const unsigned long long n_verts, float* __restrict__ verts, float* __restrict__ norms,
-                                                         float* __restrict__ colors, unsigned* __restrict__ faces)
-{
-    const long long t_id = (long long)blockIdx.x * 128 + threadIdx.x;
-    if (t_id >= l.n_active) return;
-    const long long ci = l.cube_index[t_id];
-    BrickCube c;
-    if (!brick_active_cube<CELL>(p, g, ids, n, cells, nbr, ci, c)) return;
-    const int* const nbr27 = nbr + (size_t)c.home * BRICK_NEIGHBOURS;
-    const BrickCells<CELL> sdf{cells, nbr27, c.x >> 3, c.y >> 3, c.z >> 3, __builtin_nanf("")};
-    const unsigned own = info[t_id] >> 8, first_id = vbase[t_id];
-    const unsigned long long ranks = edge_ranks(c_bm_tris[c.flag], c.ntri, own);
-    const V3 p0 = cube_origin(p, c.x, c.y, c.z);
-    unsigned id[12];
-#pragma unroll
-    for (int e = 0; e < 12; ++e) {
-        id[e] = 0;
-        if (!(c.mask & (1u << e))) continue;
-        if (own & (1u << e)) {
-            const size_t i = (size_t)first_id + rank_of(ranks, e);
-            id[e] = (unsigned)i;
-            if (i >= n_verts) continue;
-            const V3 pos = edge_position(p, p0, c.v, e);
-            V3 nrm;
-            float grey;
-            brick_edge_attributes(p, cv, has_color, sdf, color_cells, cnbr, c.home, pos, nrm, grey);
-            store_vertex(verts, norms, colors, i, pos, nrm, grey, has_color);
-        } else {
-            int oe;
-            const long long j = brick_edge_owner(p, nbr27, l, t_id, ci, c, e, oe);   // (in [0, n_active): t_id or a position found)
-            const unsigned oi = info[j];
-            id[e] = vbase[j] + rank_of(edge_ranks(c_bm_tris[oi & 255u], c_bm_num_tris[oi & 255u], oi >> 8), oe);
-        }
-    }
-    // the cube's slots are those the plan counted for it (k_bm_emit's rule): nothing is written outside them
-    const unsigned long long first = tri_offset[t_id], next = t_id + 1 < l.n_active ? (unsigned long long)tri_offset[t_id + 1] : cap_tris;
-    if (next < first || next > cap_tris) return;
-    const int planned = (int)(next - first < 5 ? next - first : 5);
-    size_t o = (size_t)first * 3;   // first face corner of this cube
-    for (int t = 0; t < min(c.ntri, planned) * 3; ++t, ++o) {
-        const int e = c_bm_tris[c.flag][t];
-        unsigned I = 0;
-#pragma unroll
-        for (int k = 0; k < 12; ++k)   // select without dynamic register indexing
-            if (k == e) I = id[k];
-        faces[o] = I;
-    }
-}
 
 // what every entry point derives from its arguments, after the checks; 0 or the refusal
 struct BrickMeshCall {
@@ -531,13 +375,20 @@ struct BrickMeshCall {
     BrickGrid grid;
     MeshParams p;
     BrickMeshScratch lay;
+    int has_color;   // an emit's: colours are asked for and the frame IsValid()
+    ColorGeom cv;    // then the colour frame: the SDF frame's dimensions and box
+    int* cnbr;       // with colour bricks to read besides: the SDF bricks' neighbours in the colour list (scratch), else null
 };
 
+// the sub-buffer at byte offset `off` of a scratch (mesh_bricks_host.h's layouts)
+template <typename T>
+static T* at(const void* scratch, size_t off) { return (T*)((uintptr_t)scratch + off); }
+
 // The checks of a plan or an emit in one order: the frame and the cell kind, the counts, the lists, the scratch (null, short,
-// misaligned), the totals pointer.
+// misaligned), the totals pointer.  `colors`: an emit's colour output, null for a plan.
 static int bm_call(BrickMeshCall& c, const char* what, const kfx_volume* frame, int cell, const unsigned* ids, const void* cells, unsigned long long n,
                    const unsigned* color_ids, const void* color_cells, unsigned long long n_color, const void* scratch, size_t scratch_bytes,
-                   const unsigned long long* totals)
+                   const unsigned long long* totals, const float* colors = nullptr)
 {
     if (int e = refuse(brick_check_frame(frame, cell, c.geom), what)) return e;
     if (int e = refuse(brick_check_counts(n, n_color), what)) return e;
@@ -556,7 +407,29 @@ static int bm_call(BrickMeshCall& c, const char* what, const kfx_volume* frame, 
     c.p.avail_lo = 0;
     c.p.avail_hi = (int)f.d;
     c.lay = brick_mesh_scratch(n, n_color);
+    c.has_color = brick_mesh_has_color(c.geom, colors) ? 1 : 0;
+    c.cv = ColorGeom{};
+    if (c.has_color) set_geometry(c.cv, &f);
+    c.cnbr = c.has_color && n_color ? at<int>(scratch, c.lay.cnbr) : nullptr;
     return 0;
+}
+
+// the lists of a call as the kernels' cube source; `first`: an index kernel's (index scratch), else null
+template <typename CELL>
+static BrickCubes<CELL> brick_cubes(const BrickMeshCall& c, const unsigned* ids, unsigned long long n, const void* cells, const void* color_cells,
+                                    const void* scratch, const unsigned long long* totals, const unsigned* first)
+{
+    return {c.p, c.cv, c.has_color, c.grid, ids, (unsigned)n, (const unsigned char*)cells, at<const int>(scratch, c.lay.nbr),
+            (const unsigned char*)color_cells, c.cnbr, totals[1], first};
+}
+
+// an emit's first launch, with colour bricks to read: the SDF bricks' neighbours in the colour list
+static void launch_color_neighbours(const BrickMeshCall& c, const unsigned* ids, unsigned long long n, const unsigned* color_ids,
+                                    unsigned long long n_color, hipStream_t st)
+{
+    if (c.cnbr)
+        hipLaunchKernelGGL(k_bm_neighbours<false>, dim3((unsigned)((n * BRICK_NEIGHBOURS + 255) / 256)), dim3(256), 0, st, c.grid, ids, (unsigned)n,
+                           color_ids, (unsigned)n_color, c.cnbr);
 }
 
 template <typename F>
@@ -564,6 +437,16 @@ static void for_sdf_cell(int cell, F f)
 {
     if (cell == KFX_CELL_F32) f(RayF32{});
     else f(RayF16{});
+}
+
+// k_bm_compact of a planned scratch into an emit's or an index plan's lists
+template <typename CELL>
+static void launch_compact(const BrickMeshCall& c, const unsigned* ids, unsigned long long n, const void* cells, const void* scratch,
+                           const unsigned long long* totals, long long* cube_index, unsigned* tri_offset, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_bm_compact<CELL>, dim3((unsigned)n), dim3(256), 0, st, c.p, c.grid, ids, (const unsigned char*)cells,
+                       at<const int>(scratch, c.lay.nbr), at<const unsigned>(scratch, c.lay.cnt), at<const unsigned long long>(scratch, c.lay.base),
+                       cube_index, tri_offset, totals[0], totals[1]);
 }
 
 } // namespace kfx
@@ -584,13 +467,11 @@ extern "C" int kfx_mesh_bricks_plan(const kfx_volume* frame, int cell, const uns
     if (int e = bm_call(c, what, frame, cell, ids, cells, n, nullptr, nullptr, 0, scratch, scratch_bytes, totals)) return e;
     totals[0] = totals[1] = 0;
     if (n == 0) return 0;
-    if (int e = bm_load_tables()) return e;
-    unsigned char* const s = (unsigned char*)scratch;
-    int* const nbr = (int*)(s + c.lay.nbr);
-    unsigned* const cnt = (unsigned*)(s + c.lay.cnt);
-    unsigned* const part = (unsigned*)(s + c.lay.part);
-    unsigned long long* const base = (unsigned long long*)(s + c.lay.base);
-    unsigned long long* const hdr = (unsigned long long*)(s + c.lay.hdr);
+    if (int e = load_tables()) return e;
+    int* const nbr = at<int>(scratch, c.lay.nbr);
+    unsigned* const cnt = at<unsigned>(scratch, c.lay.cnt);
+    unsigned* const part = at<unsigned>(scratch, c.lay.part);
+    unsigned long long* const hdr = at<unsigned long long>(scratch, c.lay.hdr);
     const hipStream_t st = (hipStream_t)stream;
     const unsigned nn = (unsigned)n;
     hipLaunchKernelGGL(k_bm_neighbours<true>, dim3((unsigned)((n * BRICK_NEIGHBOURS + 255) / 256)), dim3(256), 0, st, c.grid, ids, nn, ids, nn, nbr);
@@ -599,7 +480,8 @@ extern "C" int kfx_mesh_bricks_plan(const kfx_volume* frame, int cell, const uns
         hipLaunchKernelGGL(k_bm_count<CELL>, dim3(nn), dim3(256), 0, st, c.p, c.grid, ids, (const unsigned char*)cells, (const int*)nbr, cnt);
     });
     hipLaunchKernelGGL(k_bm_reduce, dim3((unsigned)c.lay.nblk), dim3(256), 0, st, (const unsigned*)cnt, nn, part);
-    hipLaunchKernelGGL(k_bm_scan, dim3(1), dim3(MESH_SCAN_THREADS), 0, st, (const unsigned*)part, (long long)c.lay.nblk, base, hdr);
+    hipLaunchKernelGGL(k_mesh_scan_partials, dim3(1), dim3(MESH_SCAN_THREADS), 0, st, (const unsigned*)part, (long long)c.lay.nblk,
+                       at<unsigned long long>(scratch, c.lay.base), hdr);
     if (int e = check_launch(what)) return e;
     unsigned long long host[2];
     if (int e = read_header(host, hdr, 2, st)) return e;
@@ -616,39 +498,22 @@ extern "C" int kfx_mesh_bricks_emit(const kfx_volume* frame, int cell, const uns
 {
     const char* const what = "kfx_mesh_bricks_emit";
     BrickMeshCall c;
-    if (int e = bm_call(c, what, frame, cell, ids, cells, n, color_ids, color_cells, n_color, scratch, scratch_bytes, totals)) return e;
+    if (int e = bm_call(c, what, frame, cell, ids, cells, n, color_ids, color_cells, n_color, scratch, scratch_bytes, totals, colors)) return e;
     if (!totals_in_range(totals)) return fail_rule(what, KFX_E_RANGE, "totals out of range");
     if (n == 0) return totals[0] || totals[1] ? fail_rule(what, KFX_E_RANGE, "totals are not the plan's") : 0;
     if (totals[0] == 0) return 0;
     if (int e = refuse(brick_mesh_check_outputs(cube_index, tri_offset, verts, norms, colors), what)) return e;
-    const int has_color = brick_mesh_has_color(c.geom, colors) ? 1 : 0;
-    ColorGeom cv{};
-    if (has_color) {   // the colour frame: the SDF frame's dimensions and box
-        kfx_volume f = *frame;
-        f.ptr = nullptr;
-        f.pitch = f.img_pitch = 0;
-        set_geometry(cv, &f);
-    }
-    if (int e = bm_load_tables()) return e;
-    unsigned char* const s = (unsigned char*)scratch;
-    const int* const nbr = (const int*)(s + c.lay.nbr);
-    const unsigned* const cnt = (const unsigned*)(s + c.lay.cnt);
-    const unsigned long long* const base = (const unsigned long long*)(s + c.lay.base);
-    int* const cnbr = has_color && n_color ? (int*)(s + c.lay.cnbr) : nullptr;
+    if (int e = load_tables()) return e;
     const hipStream_t st = (hipStream_t)stream;
-    if (int e = check_planned((const unsigned long long*)(s + c.lay.hdr), totals, 2, what, st)) return e;
-    const unsigned nn = (unsigned)n;
+    if (int e = check_planned(at<const unsigned long long>(scratch, c.lay.hdr), totals, 2, what, st)) return e;
     const long long n_active = (long long)totals[0];
-    if (cnbr)
-        hipLaunchKernelGGL(k_bm_neighbours<false>, dim3((unsigned)((n * BRICK_NEIGHBOURS + 255) / 256)), dim3(256), 0, st, c.grid, ids, nn, color_ids,
-                           (unsigned)n_color, cnbr);
+    launch_color_neighbours(c, ids, n, color_ids, n_color, st);
     for_sdf_cell(cell, [&](auto kind) {
         using CELL = decltype(kind);
-        hipLaunchKernelGGL(k_bm_compact<CELL>, dim3(nn), dim3(256), 0, st, c.p, c.grid, ids, (const unsigned char*)cells, nbr, cnt, base, cube_index,
-                           tri_offset, totals[0], totals[1]);
-        hipLaunchKernelGGL(k_bm_emit<CELL>, dim3((unsigned)((n_active + 127) / 128)), dim3(128), 0, st, c.p, cv, has_color, c.grid, ids, nn,
-                           (const unsigned char*)cells, nbr, (const unsigned char*)color_cells, (const int*)cnbr, (const long long*)cube_index,
-                           (const unsigned*)tri_offset, n_active, totals[1], verts, norms, has_color ? colors : nullptr);
+        launch_compact<CELL>(c, ids, n, cells, scratch, totals, cube_index, tri_offset, st);
+        hipLaunchKernelGGL(k_mc_emit<BrickCubes<CELL>>, dim3((unsigned)((n_active + 127) / 128)), dim3(128), 0, st,
+                           brick_cubes<CELL>(c, ids, n, cells, color_cells, scratch, totals, nullptr), (const long long*)cube_index,
+                           (const unsigned*)tri_offset, n_active, verts, norms, c.has_color ? colors : nullptr);
     });
     return check_launch(what);
 }
@@ -687,35 +552,28 @@ extern "C" int kfx_mesh_bricks_index_plan(const kfx_volume* frame, int cell, con
     if (n == 0 && (totals[0] || totals[1])) return fail_rule(what, KFX_E_RANGE, "totals are not the plan's");
     *n_verts = 0;
     if (n == 0 || totals[0] == 0) return 0;
-    if (int e = bm_load_tables()) return e;
-    const unsigned char* const s = (const unsigned char*)scratch;
-    const int* const nbr = (const int*)(s + c.lay.nbr);
-    const unsigned* const cnt = (const unsigned*)(s + c.lay.cnt);
-    const unsigned long long* const base = (const unsigned long long*)(s + c.lay.base);
-    unsigned char* const xs = (unsigned char*)index_scratch;
-    unsigned long long* const xhdr = (unsigned long long*)(xs + x.hdr);
-    long long* const cube_index = (long long*)(xs + x.cube_index);
-    unsigned* const tri_offset = (unsigned*)(xs + x.tri_offset);
-    unsigned* const info = (unsigned*)(xs + x.info);
-    unsigned* const vbase = (unsigned*)(xs + x.vbase);
-    unsigned* const first = (unsigned*)(xs + x.first);
-    unsigned* const xpart = (unsigned*)(xs + x.part);
-    unsigned long long* const xbase = (unsigned long long*)(xs + x.base);
+    if (int e = load_tables()) return e;
+    unsigned long long* const xhdr = at<unsigned long long>(index_scratch, x.hdr);
+    long long* const cube_index = at<long long>(index_scratch, x.cube_index);
+    unsigned* const tri_offset = at<unsigned>(index_scratch, x.tri_offset);
+    unsigned* const info = at<unsigned>(index_scratch, x.info);
+    unsigned* const first = at<unsigned>(index_scratch, x.first);
+    unsigned* const xpart = at<unsigned>(index_scratch, x.part);
+    unsigned long long* const xbase = at<unsigned long long>(index_scratch, x.base);
     const hipStream_t st = (hipStream_t)stream;
-    if (int e = check_planned((const unsigned long long*)(s + c.lay.hdr), totals, 2, what, st)) return e;
-    const unsigned nn = (unsigned)n;
+    if (int e = check_planned(at<const unsigned long long>(scratch, c.lay.hdr), totals, 2, what, st)) return e;
     const long long n_active = (long long)totals[0];
-    const BrickCubeList l{cube_index, first, n_active, nn};
     for_sdf_cell(cell, [&](auto kind) {
         using CELL = decltype(kind);
-        hipLaunchKernelGGL(k_bm_compact<CELL>, dim3(nn), dim3(256), 0, st, c.p, c.grid, ids, (const unsigned char*)cells, nbr, cnt, base, cube_index,
-                           tri_offset, totals[0], totals[1]);
-        hipLaunchKernelGGL(k_bm_first, dim3((unsigned)c.lay.nblk), dim3(256), 0, st, cnt, nn, base, first);
-        hipLaunchKernelGGL(k_bm_own<CELL>, dim3((unsigned)x.nblk), dim3(MESH_IDX_BLOCK), 0, st, c.p, c.grid, ids, nn, (const unsigned char*)cells, nbr, l,
-                           (const unsigned*)tri_offset, totals[1], info, xpart, xhdr);
-        hipLaunchKernelGGL(k_bm_scan, dim3(1), dim3(MESH_SCAN_THREADS), 0, st, (const unsigned*)xpart, (long long)x.nblk, xbase, xhdr);
+        launch_compact<CELL>(c, ids, n, cells, scratch, totals, cube_index, tri_offset, st);
+        hipLaunchKernelGGL(k_bm_first, dim3((unsigned)c.lay.nblk), dim3(256), 0, st, at<const unsigned>(scratch, c.lay.cnt), (unsigned)n,
+                           at<const unsigned long long>(scratch, c.lay.base), first);
+        hipLaunchKernelGGL(k_mesh_own<BrickCubes<CELL>>, dim3((unsigned)x.nblk), dim3(MESH_IDX_BLOCK), 0, st,
+                           brick_cubes<CELL>(c, ids, n, cells, nullptr, scratch, totals, first), (const long long*)cube_index,
+                           (const unsigned*)tri_offset, n_active, totals[1], info, xpart, xhdr);
+        hipLaunchKernelGGL(k_mesh_scan_partials, dim3(1), dim3(MESH_SCAN_THREADS), 0, st, (const unsigned*)xpart, (long long)x.nblk, xbase, xhdr);
         hipLaunchKernelGGL(k_mesh_vertex_base, dim3((unsigned)x.nblk), dim3(MESH_IDX_BLOCK), 0, st, (const unsigned*)info, n_active,
-                           (const unsigned long long*)xbase, vbase);
+                           (const unsigned long long*)xbase, at<unsigned>(index_scratch, x.vbase));
     });
     if (int e = check_launch(what)) return e;
     unsigned long long host[2];
@@ -733,40 +591,25 @@ extern "C" int kfx_mesh_bricks_emit_indexed(const kfx_volume* frame, int cell, c
     const char* const what = "kfx_mesh_bricks_emit_indexed";
     BrickMeshCall c;
     BrickMeshIndexScratch x;
-    if (int e = bm_call(c, what, frame, cell, ids, cells, n, color_ids, color_cells, n_color, scratch, scratch_bytes, totals)) return e;
+    if (int e = bm_call(c, what, frame, cell, ids, cells, n, color_ids, color_cells, n_color, scratch, scratch_bytes, totals, colors)) return e;
     if (int e = bm_index_call(x, what, n, totals, n_verts, index_scratch, index_scratch_bytes)) return e;
     if (n == 0) return totals[0] || totals[1] || n_verts ? fail_rule(what, KFX_E_RANGE, "totals are not the plan's") : 0;
     if (totals[0] == 0) return 0;
     if (int e = refuse(brick_mesh_check_indexed_outputs(verts, norms, colors, faces), what)) return e;
-    const int has_color = brick_mesh_has_color(c.geom, colors) ? 1 : 0;
-    ColorGeom cv{};
-    if (has_color) {   // the colour frame: the SDF frame's dimensions and box
-        kfx_volume f = *frame;
-        f.ptr = nullptr;
-        f.pitch = f.img_pitch = 0;
-        set_geometry(cv, &f);
-    }
-    if (int e = bm_load_tables()) return e;
-    unsigned char* const s = (unsigned char*)scratch;
-    const int* const nbr = (const int*)(s + c.lay.nbr);
-    int* const cnbr = has_color && n_color ? (int*)(s + c.lay.cnbr) : nullptr;
-    const unsigned char* const xs = (const unsigned char*)index_scratch;
+    if (int e = load_tables()) return e;
     const hipStream_t st = (hipStream_t)stream;
     // (the index plan's header: vertices, triangles, and the totals it was planned for)
     const unsigned long long planned[4] = {n_verts, totals[1], totals[0], totals[1]};
-    if (int e = check_planned((const unsigned long long*)(xs + x.hdr), planned, 4, what, st)) return e;
-    const unsigned nn = (unsigned)n;
+    if (int e = check_planned(at<const unsigned long long>(index_scratch, x.hdr), planned, 4, what, st)) return e;
     const long long n_active = (long long)totals[0];
-    const BrickCubeList l{(const long long*)(xs + x.cube_index), (const unsigned*)(xs + x.first), n_active, nn};
-    if (cnbr)
-        hipLaunchKernelGGL(k_bm_neighbours<false>, dim3((unsigned)((n * BRICK_NEIGHBOURS + 255) / 256)), dim3(256), 0, st, c.grid, ids, nn, color_ids,
-                           (unsigned)n_color, cnbr);
+    launch_color_neighbours(c, ids, n, color_ids, n_color, st);
     for_sdf_cell(cell, [&](auto kind) {
         using CELL = decltype(kind);
-        hipLaunchKernelGGL(k_bm_emit_indexed<CELL>, dim3((unsigned)((n_active + 127) / 128)), dim3(128), 0, st, c.p, cv, has_color, c.grid, ids, nn,
-                           (const unsigned char*)cells, nbr, (const unsigned char*)color_cells, (const int*)cnbr, l,
-                           (const unsigned*)(xs + x.tri_offset), (const unsigned*)(xs + x.info), (const unsigned*)(xs + x.vbase), totals[1], n_verts,
-                           verts, norms, has_color ? colors : nullptr, faces);
+        hipLaunchKernelGGL(k_mc_emit_indexed<BrickCubes<CELL>>, dim3((unsigned)((n_active + 127) / 128)), dim3(128), 0, st,
+                           brick_cubes<CELL>(c, ids, n, cells, color_cells, scratch, totals, at<const unsigned>(index_scratch, x.first)),
+                           at<const long long>(index_scratch, x.cube_index), at<const unsigned>(index_scratch, x.tri_offset),
+                           at<const unsigned>(index_scratch, x.info), at<const unsigned>(index_scratch, x.vbase), n_active, n_verts, verts, norms,
+                           c.has_color ? colors : nullptr, faces);
     });
     return check_launch(what);
 }

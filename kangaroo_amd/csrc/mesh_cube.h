@@ -1,10 +1,16 @@
-// mesh_cube.h -- what the marching-cubes extractors share: the dense volume's (mesh.hip: kfx_mc_*, kfx_mesh_*, kfx_mesh_index_*) and the
-// packed bricks' (mesh_bricks.hip: kfx_mesh_bricks_*).  The case tables, a cube's corners and case, a vertex's position on its edge,
-// the normalisation of its normal and its store -- one definition each, so that a brick mesh stays the dense mesh of the volume its
-// bricks unpack into, bit for bit -- and the host helpers of the two-step calls: the scratch carver, the scan of the block sums, the
-// read-back of a plan's totals; and of the two indexed extractions how a lattice edge is named in its owner, how a cube ranks the edges
-// it owns, and the kernel that turns the owned-edge counts into first vertex ids.  How a CELL is read (pitched rows, or bricks through
-// a neighbour table) is the including file's.
+// mesh_cube.h -- marching cubes over a CUBE SOURCE: everything the dense volume's extractor (mesh.hip: kfx_mc_*, kfx_mesh_*,
+// kfx_mesh_index_*) and the packed bricks' (mesh_bricks.hip: kfx_mesh_bricks_*) do alike, written once, so that a brick mesh is the
+// dense mesh of the volume its bricks unpack into, and a brick index the weld of that soup, because one text computes both:
+//   * the case tables in __constant__ memory and their loader (every translation unit has its own device symbols, see below);
+//   * a cube's corners' case, a vertex's position on its edge, its store;
+//   * the kernels that run one thread per ACTIVE cube -- k_mc_emit (the soup), k_mesh_own (which edges a cube owns) and
+//     k_mc_emit_indexed (the weld), the last two over the ActiveCube prologue -- as templates over the source, instantiated by each file;
+//   * of the indexed extractions how a lattice edge is named in its owner, how a cube ranks the edges it owns, k_mesh_vertex_base;
+//   * of the two-step calls the block sums, their scan kernel, the scratch carver and the read-back of a plan's totals.
+// What a source answers -- where a listed cube is, its corner values, a vertex's normal and grey, the triangle slots it may write,
+// the owner of a lattice edge -- is stated above k_mc_emit; DenseCubes (mesh.hip: pitched rows, slabs) and BrickCubes
+// (mesh_bricks.hip: bricks through a neighbour table) are the two.  The plan passes (counting and compaction) differ in substance
+// and stay each file's.
 #pragma once
 
 #include "kfx_device.h"
@@ -14,8 +20,34 @@
 
 namespace kfx {
 
-// (the case tables -- mc_tables.inc in __constant__ memory -- are each translation unit's own: a device symbol belongs to one code object)
+// The case tables (mc_tables.inc) in __constant__ memory.  A device symbol belongs to one code object, so each translation unit that
+// includes this has, and loads, its own -- in a namespace it names with KFX_MESH_UNIT before the include, so that the host's shadows
+// of the two do not clash.  (Not static: a static __constant__ that the host names is reached through the GOT, one more dependent
+// scalar load per table in every kernel; profiles/mesh_shared/codegen.txt.)
+#ifndef KFX_MESH_UNIT
+#error "define KFX_MESH_UNIT, this translation unit's name for its case tables, before including mesh_cube.h"
+#endif
 #include "mc_tables.inc"
+namespace KFX_MESH_UNIT {
+__constant__ unsigned char c_num_tris[256];
+__constant__ unsigned short c_edge_mask[256];
+__constant__ signed char c_tris[256][15];
+}
+using namespace KFX_MESH_UNIT;
+static bool g_tables_loaded[64] = {};
+
+static int load_tables()
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    if (g_tables_loaded[dev]) return 0;
+    hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(c_num_tris), MC_NUM_TRIS, sizeof(MC_NUM_TRIS));
+    if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(c_edge_mask), MC_EDGE_MASK, sizeof(MC_EDGE_MASK));
+    if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(c_tris), MC_TRIS, sizeof(MC_TRIS));
+    if (e != hipSuccess) return set_error((int)e, hipGetErrorString(e));
+    g_tables_loaded[dev] = true;
+    return 0;
+}
 
 struct MeshParams {
     VolView vol;
@@ -111,10 +143,10 @@ __device__ __forceinline__ void store_block_sums(unsigned a, unsigned t, unsigne
     }
 }
 
-// one workgroup of MESH_SCAN_THREADS: exclusive 64-bit offsets of the blocks (base[2 b] cubes, base[2 b + 1] triangles) and the
-// totals; the body of each file's scan kernel
-__device__ __forceinline__ void scan_block_sums(const unsigned* __restrict__ part, const long long nblk, unsigned long long* __restrict__ base,
-                                                unsigned long long* __restrict__ totals)
+// one workgroup: exclusive 64-bit offsets of the blocks (base[2 b] cubes or vertices, base[2 b + 1] triangles) and the totals
+static __global__ __launch_bounds__(MESH_SCAN_THREADS) void k_mesh_scan_partials(const unsigned* __restrict__ part, const long long nblk,
+                                                                                 unsigned long long* __restrict__ base,
+                                                                                 unsigned long long* __restrict__ totals)
 {
     __shared__ unsigned long long lds[2][MESH_SCAN_THREADS / 64];
     unsigned long long run_a = 0, run_t = 0;
@@ -207,6 +239,173 @@ static __global__ __launch_bounds__(MESH_IDX_BLOCK) void k_mesh_vertex_base(cons
     unsigned total;
     const unsigned ex = block_exclusive_scan<unsigned, MESH_IDX_BLOCK / 64>(n, lds, &total);
     if (t < n_active) vbase[t] = (unsigned)base[2 * (size_t)blockIdx.x] + ex;
+}
+
+// ---- the kernels with one thread per ACTIVE cube (cube_index lists the cubes with triangles in emission order, tri_offset their
+// first triangle): dense lanes instead of the ~1 % active lanes of a thread-per-cube sweep.  They are written over a cube source SRC,
+// a kernel argument that holds the geometry `p` (MeshParams) and answers, with a per-cube Home of its own (where the cube's cells are):
+//   position(ci, x, y, z)           cube ci's position; false if it is no cube of the source (a dense list's always is)
+//   locate(x, y, z, home)           where the cube's cells are; false if the source cannot read around it (bricks: its brick is not
+//                                   listed).  Two steps, two early returns: one test of both measured an occupancy step lost in
+//                                   the soup emit over bricks (profiles/mesh_shared/codegen.txt)
+//   corners(home, x, y, z, v, flag) the 8 corner values and their corner_case
+//   attributes(home, pos, n, grey)  normal and grey of the vertex at pos
+//   slots(tri_offset, t, n_active, ntri, first, planned)   the triangle slots list position t may write: `planned` from `first` on,
+//                                   of which a cube with ntri triangles uses min(ntri, planned); false if it has none.  Dense: ntri.
+//   VERIFIES_LIST                   whether k_mesh_own looks a cube's neighbours up only once it has found the cube active: the brick
+//                                   lists are the caller's device memory; a dense list is the plan's own, and the test costs there
+//   owner(cube_index, n_active, t, ci, x, y, z, home, e, oe)   the list position of the cube that owns the lattice edge under edge e
+//                                   of the cube at position t, and in oe the edge's number there.  Each source's own rule: the first
+//                                   cube around the edge in ITS emission order.
+
+// A listed cube as its thread sees it: position, case, triangle count, the mask of its edges with a vertex, corner values
+struct ActiveCube {
+    int x, y, z, flag, ntri;
+    unsigned mask;
+    float v[8];
+};
+
+// cube ci; false if the source cannot place or locate it, it has no triangles or a corner that is not finite (a cube of a plan's list over a
+// valid source is none of these).  For k_mc_emit_indexed and k_mesh_own; k_mc_emit keeps the same steps in locals.
+template <typename SRC>
+__device__ __forceinline__ bool active_cube(const SRC& s, long long ci, ActiveCube& c, typename SRC::Home& home)
+{
+    if (!s.position(ci, c.x, c.y, c.z) || !s.locate(c.x, c.y, c.z, home)) return false;
+    const bool finite = s.corners(home, c.x, c.y, c.z, c.v, c.flag);
+    c.ntri = c_num_tris[c.flag];
+    c.mask = c_edge_mask[c.flag];
+    return finite && c.ntri != 0;
+}
+
+// The soup: three fresh vertices per triangle of every listed cube.
+template <typename SRC>
+static __global__ __launch_bounds__(128) void k_mc_emit(const SRC s, const long long* __restrict__ cube_index, const unsigned* __restrict__ tri_offset,
+                                                        const long long n_active, float* __restrict__ verts, float* __restrict__ norms,
+                                                        float* __restrict__ colors)
+{
+    const long long t_id = (long long)blockIdx.x * 128 + threadIdx.x;
+    if (t_id >= n_active) return;
+    // active_cube's steps in locals: through the struct this kernel -- 36 per-edge values live -- compiles to other code, which
+    // measured 1 % slower at 1024^3 over a dense volume (profiles/mesh_refactor/ab_timing.txt)
+    int x, y, z, flag;
+    if (!s.position(cube_index[t_id], x, y, z)) return;
+    typename SRC::Home home;
+    if (!s.locate(x, y, z, home)) return;
+    float v[8];
+    if (!s.corners(home, x, y, z, v, flag)) return;
+    const int ntri = c_num_tris[flag];
+    if (ntri == 0) return;
+    const unsigned mask = c_edge_mask[flag];
+    const V3 p0 = cube_origin(s.p, x, y, z);
+    V3 ev[12], en[12];
+    float ec[12];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) {
+        if (!(mask & (1u << e))) continue;
+        ev[e] = edge_position(s.p, p0, v, e);
+        s.attributes(home, ev[e], en[e], ec[e]);
+    }
+    unsigned long long first;
+    int planned;
+    if (!s.slots(tri_offset, t_id, n_active, ntri, first, planned)) return;
+    size_t o = (size_t)first * 3; // first output vertex of this cube
+    for (int t = 0; t < min(ntri, planned) * 3; ++t, ++o) {
+        const int e = c_tris[flag][t];
+        V3 P = v3(0.f, 0.f, 0.f), N = P;
+        float C = 0.f;
+#pragma unroll
+        for (int k = 0; k < 12; ++k)   // select without dynamic register indexing (one loop for the three arrays: a shared
+            if (k == e) { P = ev[k]; N = en[k]; C = ec[k]; }   // per-array select measured slower here, same file)
+        store_vertex(verts, norms, colors, o, P, N, C, s.has_color);
+    }
+}
+
+// info[t] = flag | owned edges << 8; part[2 b] = vertices, part[2 b + 1] = triangles (the slots planned) of block b's cubes.
+// hdr[2], hdr[3]: the totals this index was planned for (hdr[0], hdr[1] are the scan's: vertices, triangles).
+template <typename SRC>
+static __global__ __launch_bounds__(MESH_IDX_BLOCK) void k_mesh_own(const SRC s, const long long* __restrict__ cube_index,
+                                                                    const unsigned* __restrict__ tri_offset, const long long n_active,
+                                                                    const unsigned long long n_tris, unsigned* __restrict__ info,
+                                                                    unsigned* __restrict__ part, unsigned long long* __restrict__ hdr)
+{
+    static_assert(MESH_IDX_BLOCK == 256, "store_block_sums");
+    const long long t = (long long)blockIdx.x * MESH_IDX_BLOCK + threadIdx.x;
+    unsigned nv = 0, nt = 0;
+    if (t < n_active) {
+        const long long ci = cube_index[t];
+        ActiveCube c;
+        typename SRC::Home home;
+        c.flag = c.ntri = 0;   // (of a cube the source cannot locate)
+        unsigned own = 0;
+        if (active_cube(s, ci, c, home) || !SRC::VERIFIES_LIST) {
+#pragma unroll
+            for (int e = 0; e < 12; ++e) {
+                if (!(c.mask & (1u << e))) continue;
+                int oe;
+                if (s.owner(cube_index, n_active, t, ci, c.x, c.y, c.z, home, e, oe) == t) own |= 1u << e;
+            }
+        }
+        info[t] = (unsigned)c.flag | (own << 8);
+        nv = __popc(own);
+        unsigned long long first;
+        int planned;
+        if (s.slots(tri_offset, t, n_active, c.ntri, first, planned)) nt = (unsigned)planned;
+    }
+    store_block_sums(nv, nt, part);
+    if (threadIdx.x == 0 && blockIdx.x == 0) { hdr[2] = (unsigned long long)n_active; hdr[3] = n_tris; }
+}
+
+// k_mc_emit with shared vertices: positions, normals and colours by k_mc_emit's calls, made by the owner only; every triangle
+// corner writes base(owner) + rank(edge in owner).  Every vertex id is compared with n_verts before its store.
+template <typename SRC>
+static __global__ __launch_bounds__(128) void k_mc_emit_indexed(const SRC s, const long long* __restrict__ cube_index,
+                                                                const unsigned* __restrict__ tri_offset, const unsigned* __restrict__ info,
+                                                                const unsigned* __restrict__ vbase, const long long n_active,
+                                                                const unsigned long long n_verts, float* __restrict__ verts,
+                                                                float* __restrict__ norms, float* __restrict__ colors, unsigned* __restrict__ faces)
+{
+    const long long t_id = (long long)blockIdx.x * 128 + threadIdx.x;
+    if (t_id >= n_active) return;
+    const long long ci = cube_index[t_id];
+    ActiveCube c;
+    typename SRC::Home home;
+    if (!active_cube(s, ci, c, home)) return;
+    const unsigned own = info[t_id] >> 8, first_id = vbase[t_id];
+    const unsigned long long ranks = edge_ranks(c_tris[c.flag], c.ntri, own);
+    const V3 p0 = cube_origin(s.p, c.x, c.y, c.z);
+    unsigned id[12];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) {
+        id[e] = 0;
+        if (!(c.mask & (1u << e))) continue;
+        if (own & (1u << e)) {
+            const size_t i = first_id + rank_of(ranks, e);   // (a 32-bit sum: whatever a scratch holds, i is checked next)
+            id[e] = (unsigned)i;
+            if (i >= n_verts) continue;
+            const V3 pos = edge_position(s.p, p0, c.v, e);
+            V3 n;
+            float grey;
+            s.attributes(home, pos, n, grey);
+            store_vertex(verts, norms, colors, i, pos, n, grey, s.has_color);
+        } else {
+            int oe;
+            const long long j = s.owner(cube_index, n_active, t_id, ci, c.x, c.y, c.z, home, e, oe);   // (in [0, n_active))
+            const unsigned oi = info[j];
+            id[e] = vbase[j] + rank_of(edge_ranks(c_tris[oi & 255u], c_num_tris[oi & 255u], oi >> 8), oe);
+        }
+    }
+    unsigned long long first;
+    int planned;
+    if (!s.slots(tri_offset, t_id, n_active, c.ntri, first, planned)) return;
+    size_t o = (size_t)first * 3;   // first face corner of this cube
+    for (int t = 0; t < min(c.ntri, planned) * 3; ++t, ++o) {
+        const int e = c_tris[c.flag][t];
+        unsigned I = 0;
+#pragma unroll
+        for (int k = 0; k < 12; ++k)   // select without dynamic register indexing
+            if (k == e) I = id[k];
+        faces[o] = I;
+    }
 }
 
 // A caller's scratch handed out front to back, every sub-buffer on a 256-byte boundary of it; `bytes` is what has been taken.

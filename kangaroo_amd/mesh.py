@@ -49,6 +49,41 @@ def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _extract(dev, stream, nbytes, floor, has_color, indexed, with_index, plan, index_bytes, index_plan, emit, emit_indexed):
+    """plan -> [index plan ->] allocate -> emit, for ExtractMesh and ExtractBrickMesh.  plan ... emit_indexed: the ABI calls with their
+    leading arguments (the volume, or the frame and the lists) bound; each takes what follows those in its signature, the plan's scratch
+    first.  nbytes: the plan's scratch; floor: the least size a scratch is allocated with."""
+    empty = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+    scratch = empty(max(nbytes, floor), torch.uint8)
+    totals = (C.c_ulonglong * 2)()
+    st = _stream(stream)
+    code = plan(_ptr(scratch), nbytes, totals, st)
+    if code == -4 and totals[1] >= 2 ** 32 // 3:   # KFX_E_RANGE
+        raise ValueError("mesh too large for 32-bit vertex offsets")
+    _lib.check(code)
+    na, ntri = int(totals[0]), int(totals[1])
+    nv = 3 * ntri
+    if indexed:
+        xbytes = index_bytes(totals)
+        xscratch = empty(max(xbytes, floor), torch.uint8)
+        nvert = C.c_ulonglong(0)
+        _lib.check(index_plan(_ptr(scratch), nbytes, totals, _ptr(xscratch), xbytes, C.byref(nvert), st))
+        nv = int(nvert.value)
+    verts, norms = empty((nv, 3), torch.float32), empty((nv, 3), torch.float32)
+    colors = empty((nv, 4), torch.float32) if has_color else None
+    if indexed:
+        faces = empty((ntri, 3), torch.int32)
+        if na:
+            _lib.check(emit_indexed(_ptr(scratch), nbytes, _ptr(xscratch), xbytes, totals, nv, _ptr(verts), _ptr(norms), _ptr(colors), _ptr(faces), st))
+        return verts, norms, colors, faces
+    cube_index, tri_offset = empty(na, torch.int64), empty(na, torch.int32)
+    if na:
+        _lib.check(emit(_ptr(scratch), nbytes, totals, _ptr(cube_index), _ptr(tri_offset), _ptr(verts), _ptr(norms), _ptr(colors), st))
+    if with_index:
+        return verts, norms, colors, cube_index, tri_offset
+    return verts, norms, colors
+
+
 def ExtractMesh(vol, colorVol=None, stream=None, slab=None, with_index=False, indexed=False):
     """Returns (verts, norms, colors): float32 device tensors of shape (3T, 3), (3T, 3) and (3T, 4) or None.
     indexed=True: (verts, norms, colors, faces) with V rows each and faces (T, 3), uint32 ids held in an int32 tensor (the weld
@@ -71,42 +106,17 @@ def ExtractMesh(vol, colorVol=None, stream=None, slab=None, with_index=False, in
     nbytes = L.kfx_mesh_scratch_bytes(*args)
     if nbytes == 0:
         _lib.check(L.kfx_mesh_plan(*args, None, 0, None, None))   # the reason
-    empty = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
-    scratch = empty(nbytes, torch.uint8)
-    totals = (C.c_ulonglong * 2)()
-    st = _stream(stream)
-    code = L.kfx_mesh_plan(*args, _ptr(scratch), nbytes, totals, st)
-    if code == -4 and totals[1] >= 2 ** 32 // 3:   # KFX_E_RANGE
-        raise ValueError("mesh too large for 32-bit vertex offsets")
-    _lib.check(code)
-    na, ntri = int(totals[0]), int(totals[1])
+    if indexed and with_index:
+        raise ValueError("ExtractMesh: with_index lists the soup's cubes; not with indexed=True")
     # IsValid() of the colour volume -- of the FULL one where colorVol is a slab of it
     has_color = colorVol is not None and min(colorVol.w, colorVol.h, colorVol.d if slab is None else int(slab[0])) >= 8
     cref = colorVol.ref() if has_color else None
-    nv = 3 * ntri
-    if indexed:
-        if with_index:
-            raise ValueError("ExtractMesh: with_index lists the soup's cubes; not with indexed=True")
-        xbytes = L.kfx_mesh_index_scratch_bytes(*args, totals)
-        xscratch = empty(xbytes, torch.uint8)
-        nvert = C.c_ulonglong(0)
-        _lib.check(L.kfx_mesh_index_plan(*args, _ptr(scratch), nbytes, totals, _ptr(xscratch), xbytes, C.byref(nvert), st))
-        nv = int(nvert.value)
-    verts, norms = empty((nv, 3), torch.float32), empty((nv, 3), torch.float32)
-    colors = empty((nv, 4), torch.float32) if has_color else None
-    if indexed:
-        faces = empty((ntri, 3), torch.int32)
-        if na:
-            _lib.check(L.kfx_mesh_emit_indexed(*args, cref, _ptr(xscratch), xbytes, totals, nv, _ptr(verts), _ptr(norms), _ptr(colors),
-                                               _ptr(faces), st))
-        return verts, norms, colors, faces
-    cube_index, tri_offset = empty(na, torch.int64), empty(na, torch.int32)
-    if na:
-        _lib.check(L.kfx_mesh_emit(*args, cref, _ptr(scratch), nbytes, totals, _ptr(cube_index), _ptr(tri_offset), _ptr(verts), _ptr(norms),
-                                   _ptr(colors), st))
-    if with_index:
-        return verts, norms, colors, cube_index, tri_offset
-    return verts, norms, colors
+    return _extract(dev, stream, nbytes, 0, has_color, indexed, with_index,
+                    plan=lambda *a: L.kfx_mesh_plan(*args, *a),
+                    index_bytes=lambda totals: L.kfx_mesh_index_scratch_bytes(*args, totals),
+                    index_plan=lambda *a: L.kfx_mesh_index_plan(*args, *a),
+                    emit=lambda *a: L.kfx_mesh_emit(*args, cref, *a),
+                    emit_indexed=lambda scratch, nbytes, *a: L.kfx_mesh_emit_indexed(*args, cref, *a))   # (reads the index scratch alone)
 
 
 BRICK_BYTES = {"f32": 4096, "f16": 2048, "c32": 2048}   # one packed 8 x 8 x 8 brick of each cell kind
@@ -162,42 +172,15 @@ def ExtractBrickMesh(dims, boxmin, boxmax, kind, ids, cells, color_ids=None, col
     frame = _lib.KfxVolume(0, None, int(dims[0]), int(dims[1]), 0, int(dims[2]))
     for i in range(3):
         frame.boxmin[i], frame.boxmax[i] = float(np.float32(boxmin[i])), float(np.float32(boxmax[i]))
-    empty = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=device)
     nbytes = BrickMeshScratchBytes(n, nc)   # (0: the counts are refused -- the plan says why)
-    scratch = empty(max(nbytes, 256), torch.uint8)
-    totals = (C.c_ulonglong * 2)()
-    st = _stream(stream)
-    lists = (_ptr(ids) if n else None, _ptr(cells) if n else None, n)
-    code = L.kfx_mesh_bricks_plan(C.byref(frame), CELL[kind], *lists, _ptr(scratch), nbytes, totals, st)
-    if code == -4 and totals[1] >= 2 ** 32 // 3:   # KFX_E_RANGE
-        raise ValueError("mesh too large for 32-bit vertex offsets")
-    _lib.check(code)
-    na, ntri = int(totals[0]), int(totals[1])
-    clists = (_ptr(cids) if nc else None, _ptr(ccells) if nc else None, nc)
-    if indexed:
-        xbytes = L.kfx_mesh_bricks_index_scratch_bytes(n, totals)
-        xscratch = empty(max(xbytes, 256), torch.uint8)
-        nvert = C.c_ulonglong(0)
-        _lib.check(L.kfx_mesh_bricks_index_plan(C.byref(frame), CELL[kind], *lists, _ptr(scratch), nbytes, totals, _ptr(xscratch), xbytes,
-                                                C.byref(nvert), st))
-        nv = int(nvert.value)
-        verts, norms = empty((nv, 3), torch.float32), empty((nv, 3), torch.float32)
-        colors = empty((nv, 4), torch.float32) if want_color else None
-        faces = empty((ntri, 3), torch.int32)
-        if na:
-            _lib.check(L.kfx_mesh_bricks_emit_indexed(C.byref(frame), CELL[kind], *lists, *clists, _ptr(scratch), nbytes, _ptr(xscratch), xbytes,
-                                                      totals, nv, _ptr(verts), _ptr(norms), _ptr(colors), _ptr(faces), st))
-        return verts, norms, colors, faces
-    verts, norms = empty((3 * ntri, 3), torch.float32), empty((3 * ntri, 3), torch.float32)
-    colors = empty((3 * ntri, 4), torch.float32) if want_color else None
-    cube_index, tri_offset = empty(na, torch.int64), empty(na, torch.int32)
-    if na:
-        _lib.check(L.kfx_mesh_bricks_emit(C.byref(frame), CELL[kind], *lists, *clists,
-                                          _ptr(scratch), nbytes, totals, _ptr(cube_index), _ptr(tri_offset), _ptr(verts), _ptr(norms),
-                                          _ptr(colors), st))
-    if with_index:
-        return verts, norms, colors, cube_index, tri_offset
-    return verts, norms, colors
+    sdf = (C.byref(frame), CELL[kind], _ptr(ids) if n else None, _ptr(cells) if n else None, n)
+    both = sdf + (_ptr(cids) if nc else None, _ptr(ccells) if nc else None, nc)
+    return _extract(device, stream, nbytes, 256, want_color, indexed, with_index,
+                    plan=lambda *a: L.kfx_mesh_bricks_plan(*sdf, *a),
+                    index_bytes=lambda totals: L.kfx_mesh_bricks_index_scratch_bytes(n, totals),
+                    index_plan=lambda *a: L.kfx_mesh_bricks_index_plan(*sdf, *a),
+                    emit=lambda *a: L.kfx_mesh_bricks_emit(*both, *a),
+                    emit_indexed=lambda *a: L.kfx_mesh_bricks_emit_indexed(*both, *a))
 
 
 def SaveBrickMesh(filename, dims, boxmin, boxmax, kind, ids, cells, color_ids=None, color_cells=None, binary=True, indexed=False):
