@@ -102,6 +102,8 @@ int main(int argc, char** argv)
     int drop_frame = -1;   // --drop-frame F: frame F arrives with no valid depth at all (a sensor drop-out): tracking is lost, the next frame recovers
     const char* save_mesh = nullptr;   // --save-mesh PREFIX: roo::SaveMesh of the model after the last frame (the application's 's' key) -> PREFIX.ply
     bool mesh_indexed = false;         // --mesh-indexed: ... through roo::SaveMeshIndexed: welded vertices and a face list
+    long mesh_min_faces = 0;           // --mesh-min-faces N (with --mesh-indexed): ... without the components of fewer than N faces, removed on the device
+    bool mesh_largest = false;         // --mesh-largest (with --mesh-indexed): ... only the component with the most faces
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--res") && i + 1 < argc) volres = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--frames") && i + 1 < argc) frames = atoi(argv[++i]);
@@ -118,6 +120,12 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--warmup") && i + 1 < argc) warm = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--save-mesh") && i + 1 < argc) save_mesh = argv[++i];
         else if (!strcmp(argv[i], "--mesh-indexed")) mesh_indexed = true;
+        else if (!strcmp(argv[i], "--mesh-min-faces") && i + 1 < argc) mesh_min_faces = atol(argv[++i]);
+        else if (!strcmp(argv[i], "--mesh-largest")) mesh_largest = true;
+    }
+    if (mesh_min_faces < 0 || ((mesh_min_faces || mesh_largest) && !mesh_indexed)) {
+        fprintf(stderr, "--mesh-min-faces N (N >= 0) and --mesh-largest filter the indexed mesh: they need --mesh-indexed\n");
+        return 2;
     }
     if (warm < 0 || warm >= frames) warm = 0;
     if (kfx_device_count() < 1) { fprintf(stderr, "no HIP device\n"); return 2; }
@@ -429,8 +437,13 @@ int main(int argc, char** argv)
                       1e3 * worst_pos_err, 1e3 * 0.0105, rmse, lost, resets);
     if (save_mesh && mesh_indexed) {
         size_t nvert = 0;
-        const size_t ntri = use_colour ? SaveMeshIndexed(save_mesh, vol, colorVol, &nvert) : SaveMeshIndexed(save_mesh, vol, &nvert);
+        const bool clean = mesh_min_faces || mesh_largest;
+        const size_t min_faces = (size_t)mesh_min_faces;
+        const size_t ntri = clean ? (use_colour ? SaveMeshIndexed(save_mesh, vol, colorVol, min_faces, mesh_largest, &nvert)
+                                                : SaveMeshIndexed(save_mesh, vol, min_faces, mesh_largest, &nvert))
+                                  : (use_colour ? SaveMeshIndexed(save_mesh, vol, colorVol, &nvert) : SaveMeshIndexed(save_mesh, vol, &nvert));
         printf("  mesh: %zu triangles, %zu vertices written to %s.ply\n", ntri, nvert, save_mesh);
+        if (clean) printf("  mesh clean-up: components of at least %zu faces%s\n", min_faces, mesh_largest ? ", the largest only" : "");
     } else if (save_mesh) {
         const size_t ntri = use_colour ? SaveMesh(save_mesh, vol, colorVol) : SaveMesh(save_mesh, vol);   // main.cpp:187
         printf("  mesh: %zu triangles written to %s.ply\n", ntri, save_mesh);

@@ -8,6 +8,8 @@
 // cases).  PLY layout: x y z nx ny nz [red green blue alpha] floats, one face per three consecutive vertices, binary little endian.
 // roo::SaveMeshIndexed (an addition; SaveMesh keeps the reference's signature and output) writes the same surface with one vertex per
 // lattice edge and a face list, welded on the device (include/kfx_mesh_index.h): about a third of the bytes, usable for adjacency.
+// roo::MeshComponents / roo::MeshFilter (include/kfx_mesh_clean.h) use that adjacency on the device: the connected components of an
+// indexed mesh, and the mesh without its small ones -- the floaters around the surface; SaveMeshIndexed takes min_faces / largest.
 #pragma once
 
 #include <cstdint>
@@ -17,6 +19,7 @@
 
 #include <kfx_mesh.h>
 #include <kfx_mesh_index.h>
+#include <kfx_mesh_clean.h>
 
 #include <kangaroo/BoundedVolume.h>
 #include <kangaroo/Sdf.h>
@@ -68,8 +71,35 @@ struct HostMesh {
     bool color = false;
 };
 
-// The mesh of `vol` (slab: its cubes [own_lo, own_hi) of the volume `slab` describes)
-inline HostMesh Extract(const kfx_volume* vol, int cell, const kfx_slab* slab, int own_lo, int own_hi, const kfx_volume* colorvol, bool indexed = false)
+// What a clean-up keeps (include/kfx_mesh_clean.h): the components with at least min_faces faces; largest: only the one with the most.
+struct MeshKeep {
+    size_t min_faces = 0;
+    bool largest = false;
+    explicit operator bool() const { return min_faces || largest; }
+};
+
+// An indexed mesh in device memory -- nv rows of dv, dn and (where dc holds any) dc, nt rows of faces -- replaced by what `keep` keeps
+// of it: kfx_mesh_components_plan, kfx_mesh_filter_plan, kfx_mesh_filter_emit.
+inline void FilterBuffers(DeviceBuffer& dv, DeviceBuffer& dn, DeviceBuffer& dc, DeviceBuffer& faces, size_t& nv, size_t& nt, const MeshKeep& keep)
+{
+    const size_t nbytes = kfx_mesh_components_scratch_bytes(nv, nt);
+    DeviceBuffer scratch(nbytes);
+    unsigned long long counts[2] = {0, 0}, kept[2] = {0, 0};
+    GpuCheckStatus(kfx_mesh_components_plan(faces.get<unsigned>(), nt, nv, scratch.get(), nbytes, counts, 0));   // (nbytes 0: the reason)
+    GpuCheckStatus(kfx_mesh_filter_plan(scratch.get(), nbytes, nv, nt, faces.get<unsigned>(), keep.min_faces, keep.largest, kept, 0));
+    DeviceBuffer ov(kept[0] * 12), on, oc, of(kept[1] * 12);
+    if (dn.get()) on = DeviceBuffer(kept[0] * 12);
+    if (dc.get()) oc = DeviceBuffer(kept[0] * 16);
+    GpuCheckStatus(kfx_mesh_filter_emit(scratch.get(), nbytes, nv, nt, kept, dv.get<float>(), dn.get<float>(), dc.get<float>(), faces.get<unsigned>(),
+                                        ov.get<float>(), on.get<float>(), oc.get<float>(), of.get<unsigned>(), 0));
+    dv = std::move(ov); dn = std::move(on); dc = std::move(oc); faces = std::move(of);
+    nv = kept[0];
+    nt = kept[1];
+}
+
+// The mesh of `vol` (slab: its cubes [own_lo, own_hi) of the volume `slab` describes); keep: an indexed mesh without its small components
+inline HostMesh Extract(const kfx_volume* vol, int cell, const kfx_slab* slab, int own_lo, int own_hi, const kfx_volume* colorvol, bool indexed = false,
+                        const MeshKeep& keep = MeshKeep())
 {
     const size_t nbytes = kfx_mesh_scratch_bytes(vol, cell, slab, own_lo, own_hi);
     if (!nbytes) GpuCheckStatus(kfx_mesh_plan(vol, cell, slab, own_lo, own_hi, nullptr, 0, nullptr, 0));   // the reason
@@ -93,7 +123,7 @@ inline HostMesh Extract(const kfx_volume* vol, int cell, const kfx_slab* slab, i
         active = DeviceBuffer(totals[0] * 8);
         offsets = DeviceBuffer(totals[0] * 4);
     }
-    const size_t nv = m.nvert;
+    size_t nv = m.nvert;
     DeviceBuffer dv(nv * 12), dn(nv * 12), dc;
     if (m.color) dc = DeviceBuffer(nv * 16);
     if (totals[0] && indexed)
@@ -102,6 +132,11 @@ inline HostMesh Extract(const kfx_volume* vol, int cell, const kfx_slab* slab, i
     else if (totals[0])
         GpuCheckStatus(kfx_mesh_emit(vol, cell, slab, own_lo, own_hi, colorvol, scratch.get(), nbytes, totals, active.get<long long>(),
                                      offsets.get<unsigned>(), dv.get<float>(), dn.get<float>(), dc.get<float>(), 0));
+    if (keep && indexed && m.ntri) {
+        FilterBuffers(dv, dn, dc, faces, nv, m.ntri, keep);
+        m.nvert = nv;
+        m.faces.resize(3 * m.ntri);
+    }
     m.v.resize(nv * 3); m.n.resize(nv * 3); m.c.resize(m.color ? nv * 4 : 0);
     dv.CopyTo(m.v.data(), nv * 12);
     dn.CopyTo(m.n.data(), nv * 12);
@@ -136,10 +171,11 @@ inline size_t WritePly(const std::string& path, const HostMesh& m)
 
 // SaveMesh / SaveMeshIndexed of a BoundedVolume<T>; a T without a Cell<T> does not compile
 template<typename T, typename Manage1, typename Manage2>
-inline size_t Save(const std::string& filename, BoundedVolume<T,TargetDevice,Manage1>& vol, BoundedVolume<float,TargetDevice,Manage2>* volColor, bool indexed, size_t* nvert)
+inline size_t Save(const std::string& filename, BoundedVolume<T,TargetDevice,Manage1>& vol, BoundedVolume<float,TargetDevice,Manage2>* volColor, bool indexed, size_t* nvert,
+                   const MeshKeep& keep = MeshKeep())
 {
     const bool color = volColor && volColor->IsValid();
-    const HostMesh m = Extract(vol.abi(), Cell<T>::kind, nullptr, 0, 0, color ? volColor->abi() : nullptr, indexed);
+    const HostMesh m = Extract(vol.abi(), Cell<T>::kind, nullptr, 0, 0, color ? volColor->abi() : nullptr, indexed, keep);
     if (nvert) *nvert = m.nvert;
     return WritePly(filename + ".ply", m);
 }
@@ -184,6 +220,71 @@ template<typename T, typename Manage1, typename Manage2>
 inline size_t SaveMeshIndexed(std::string filename, BoundedVolume<T,TargetDevice,Manage1>& vol, BoundedVolume<float,TargetDevice,Manage2>& volColor, size_t* nvert = nullptr)
 {
     return SaveMeshIndexed<T,Manage1,Manage2>(filename, vol, &volColor, nvert);
+}
+
+// SaveMeshIndexed(filename, vol[, volColor], min_faces, largest): the indexed mesh without its small components, filtered on the device
+// (include/kfx_mesh_clean.h) -- the components with at least min_faces faces; largest: only the one with the most, min_faces on top.
+template<typename T, typename Manage1, typename Manage2>
+inline size_t SaveMeshIndexed(std::string filename, BoundedVolume<T,TargetDevice,Manage1>& vol, BoundedVolume<float,TargetDevice,Manage2>* volColor, size_t min_faces,
+                              bool largest, size_t* nvert = nullptr)
+{
+    return mesh_detail::Save(filename, vol, volColor, true, nvert, mesh_detail::MeshKeep{min_faces, largest});
+}
+
+template<typename T, typename Manage>
+inline size_t SaveMeshIndexed(std::string filename, BoundedVolume<T,TargetDevice,Manage>& vol, size_t min_faces, bool largest, size_t* nvert = nullptr)
+{
+    return SaveMeshIndexed<T,Manage,Manage>(filename, vol, nullptr, min_faces, largest, nvert);
+}
+
+template<typename T, typename Manage1, typename Manage2>
+inline size_t SaveMeshIndexed(std::string filename, BoundedVolume<T,TargetDevice,Manage1>& vol, BoundedVolume<float,TargetDevice,Manage2>& volColor, size_t min_faces,
+                              bool largest, size_t* nvert = nullptr)
+{
+    return SaveMeshIndexed<T,Manage1,Manage2>(filename, vol, &volColor, min_faces, largest, nvert);
+}
+
+// MeshComponents(faces, n_faces, n_verts, vertex_component, component_faces): the connected components of an indexed mesh whose faces
+// (n_faces x 3 ids < n_verts) are in device memory, labelled on the device (include/kfx_mesh_clean.h).  The host vectors receive every
+// vertex's component and every component's face count; components are numbered by their smallest vertex id.  Returns their number.
+inline size_t MeshComponents(const uint32_t* faces, size_t n_faces, size_t n_verts, std::vector<uint32_t>& vertex_component, std::vector<uint32_t>& component_faces)
+{
+    const size_t nbytes = kfx_mesh_components_scratch_bytes(n_verts, n_faces);
+    mesh_detail::DeviceBuffer scratch(nbytes);
+    unsigned long long counts[2] = {0, 0};
+    GpuCheckStatus(kfx_mesh_components_plan(faces, n_faces, n_verts, scratch.get(), nbytes, counts, 0));   // (nbytes 0: the reason)
+    vertex_component.resize(n_verts);
+    component_faces.resize(counts[0]);
+    mesh_detail::DeviceBuffer vc(n_verts * 4), cf(counts[0] * 4);
+    GpuCheckStatus(kfx_mesh_components_emit(scratch.get(), nbytes, n_verts, n_faces, counts, vc.get<unsigned>(), cf.get<unsigned>(), 0));
+    vc.CopyTo(vertex_component.data(), n_verts * 4);
+    cf.CopyTo(component_faces.data(), counts[0] * 4);
+    return counts[0];
+}
+
+// MeshFilter(verts, norms, colors, faces, n_verts, n_faces, min_faces, largest): an indexed mesh in device memory (norms and colors may be
+// null) without its small components, as host arrays: kept vertices and faces in their order, rows bit for bit, ids renumbered.
+inline mesh_detail::HostMesh MeshFilter(const float* verts, const float* norms, const float* colors, const uint32_t* faces, size_t n_verts, size_t n_faces,
+                                        size_t min_faces, bool largest)
+{
+    const size_t nbytes = kfx_mesh_components_scratch_bytes(n_verts, n_faces);
+    mesh_detail::DeviceBuffer scratch(nbytes);
+    unsigned long long counts[2] = {0, 0}, kept[2] = {0, 0};
+    GpuCheckStatus(kfx_mesh_components_plan(faces, n_faces, n_verts, scratch.get(), nbytes, counts, 0));
+    GpuCheckStatus(kfx_mesh_filter_plan(scratch.get(), nbytes, n_verts, n_faces, faces, min_faces, largest, kept, 0));
+    mesh_detail::HostMesh m;
+    m.nvert = kept[0];
+    m.ntri = kept[1];
+    m.color = colors != nullptr;
+    mesh_detail::DeviceBuffer ov(kept[0] * 12), on(norms ? kept[0] * 12 : 0), oc(colors ? kept[0] * 16 : 0), of(kept[1] * 12);
+    GpuCheckStatus(kfx_mesh_filter_emit(scratch.get(), nbytes, n_verts, n_faces, kept, verts, norms, colors, faces, ov.get<float>(),
+                                        norms ? on.get<float>() : nullptr, colors ? oc.get<float>() : nullptr, of.get<unsigned>(), 0));
+    m.v.resize(m.nvert * 3); m.n.resize(norms ? m.nvert * 3 : 0); m.c.resize(colors ? m.nvert * 4 : 0); m.faces.resize(m.ntri * 3);
+    ov.CopyTo(m.v.data(), m.v.size() * 4);
+    on.CopyTo(m.n.data(), m.n.size() * 4);
+    oc.CopyTo(m.c.data(), m.c.size() * 4);
+    of.CopyTo(m.faces.data(), m.faces.size() * 4);
+    return m;
 }
 
 }

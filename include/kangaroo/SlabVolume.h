@@ -15,6 +15,7 @@
 #pragma once
 
 #include <memory>
+#include <stdexcept>
 
 #include <kfx_slab.h>
 #include <kfx_slab_color.h>
@@ -185,6 +186,16 @@ public:
     // SaveMesh's part of the mesh welded by lattice edge (include/kfx_mesh_index.h): the weld of this rank's triangles, so a vertex on a
     // slab boundary exists once per rank that uses it.  nvert, if given, receives the vertex count; returns the triangle count.
     size_t SaveMeshIndexed(std::string filename, size_t* nvert = nullptr) { return SaveRankMesh(filename, true, nvert); }
+
+    // ... without its small components (MarchingCubes.h: SaveMeshIndexed(filename, vol, min_faces, largest)): refused.  A rank's mesh is
+    // welded within the rank, so its components are cut at the slab boundaries: a surface that crosses one would count as two parts, each
+    // smaller than the whole.  Filter the whole volume's mesh instead.
+    size_t SaveMeshIndexed(std::string filename, size_t min_faces, bool largest, size_t* nvert = nullptr)
+    {
+        if (!min_faces && !largest) return SaveMeshIndexed(filename, nvert);
+        throw std::invalid_argument("SlabVolume::SaveMeshIndexed: min_faces / largest are refused: a rank's mesh is welded within its rank, so its "
+                                    "components are cut at the slab boundaries; filter the whole volume's mesh (roo::SaveMeshIndexed)");
+    }
 
 private:
     size_t SaveRankMesh(const std::string& filename, bool indexed, size_t* nvert)

@@ -183,7 +183,7 @@ namespace mesh_detail
 // edge.  cube_index and tri_offset, if given, receive every active cube's dense index and first triangle in the list's order (soup).
 inline HostMesh ExtractBricks(const kfx_volume& frame, int cell, const unsigned* ids, const void* cells, size_t n, const unsigned* color_ids,
                               const void* color_cells, size_t n_color, bool color, bool indexed = false, std::vector<long long>* cube_index = nullptr,
-                              std::vector<unsigned>* tri_offset = nullptr)
+                              std::vector<unsigned>* tri_offset = nullptr, const MeshKeep& keep = MeshKeep())
 {
     const size_t nbytes = MeshBricksScratchBytes(n, color ? n_color : 0);
     DeviceBuffer scratch(nbytes), xscratch, active, offsets, faces;
@@ -204,7 +204,7 @@ inline HostMesh ExtractBricks(const kfx_volume& frame, int cell, const unsigned*
         active = DeviceBuffer(totals[0] * 8);
         offsets = DeviceBuffer(totals[0] * 4);
     }
-    const size_t nv = m.nvert;
+    size_t nv = m.nvert;
     DeviceBuffer dv(nv * 12), dn(nv * 12), dc;
     if (m.color) dc = DeviceBuffer(nv * 16);
     const unsigned* const cids = m.color ? color_ids : nullptr;
@@ -216,6 +216,11 @@ inline HostMesh ExtractBricks(const kfx_volume& frame, int cell, const unsigned*
     else if (totals[0])
         MeshBricksEmit(frame, cell, ids, cells, n, cids, ccells, nc, scratch.get(), nbytes, totals, active.get<long long>(), offsets.get<unsigned>(),
                        dv.get<float>(), dn.get<float>(), dc.get<float>());
+    if (keep && indexed && m.ntri) {   // (MarchingCubes.h: the indexed mesh without its small components)
+        FilterBuffers(dv, dn, dc, faces, nv, m.ntri, keep);
+        m.nvert = nv;
+        m.faces.resize(3 * m.ntri);
+    }
     m.v.resize(nv * 3); m.n.resize(nv * 3); m.c.resize(m.color ? nv * 4 : 0);
     dv.CopyTo(m.v.data(), nv * 12);
     dn.CopyTo(m.n.data(), nv * 12);
@@ -255,6 +260,26 @@ inline size_t SaveMeshBricksIndexed(std::string filename, const kfx_volume& fram
                                     const unsigned* color_ids, const void* color_cells, size_t n_color, size_t* nvert = nullptr)
 {
     const mesh_detail::HostMesh m = mesh_detail::ExtractBricks(frame, cell, ids, cells, n, color_ids, color_cells, n_color, true, true);
+    if (nvert) *nvert = m.nvert;
+    return mesh_detail::WritePly(filename + ".ply", m);
+}
+
+// ... min_faces, largest: without its small components, filtered on the device (MarchingCubes.h: SaveMeshIndexed's)
+inline size_t SaveMeshBricksIndexed(std::string filename, const kfx_volume& frame, int cell, const unsigned* ids, const void* cells, size_t n,
+                                    size_t min_faces, bool largest, size_t* nvert = nullptr)
+{
+    const mesh_detail::HostMesh m = mesh_detail::ExtractBricks(frame, cell, ids, cells, n, nullptr, nullptr, 0, false, true, nullptr, nullptr,
+                                                               mesh_detail::MeshKeep{min_faces, largest});
+    if (nvert) *nvert = m.nvert;
+    return mesh_detail::WritePly(filename + ".ply", m);
+}
+
+inline size_t SaveMeshBricksIndexed(std::string filename, const kfx_volume& frame, int cell, const unsigned* ids, const void* cells, size_t n,
+                                    const unsigned* color_ids, const void* color_cells, size_t n_color, size_t min_faces, bool largest,
+                                    size_t* nvert = nullptr)
+{
+    const mesh_detail::HostMesh m = mesh_detail::ExtractBricks(frame, cell, ids, cells, n, color_ids, color_cells, n_color, true, true, nullptr,
+                                                               nullptr, mesh_detail::MeshKeep{min_faces, largest});
     if (nvert) *nvert = m.nvert;
     return mesh_detail::WritePly(filename + ".ply", m);
 }

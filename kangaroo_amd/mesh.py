@@ -23,6 +23,11 @@ cube by cube and bit for bit, listed brick by brick -- with memory in proportion
 (include/kfx_mesh_bricks_index.h): the first-occurrence weld of THAT soup by lattice edge, welded on the device across brick faces,
 edges and corners -- the vertex set of ExtractMesh(D, indexed=True) in the bricks' order, still without D.
 
+Clean-up (include/kfx_mesh_clean.h), on an indexed mesh in device memory: MeshComponents labels its connected components (two vertices are
+connected when a face contains both; numbered by their smallest vertex id), FilterMesh drops the components with fewer than min_faces
+faces -- the floaters depth noise and unobserved cells leave around the surface -- or all but the largest, and compacts what is left,
+order and bits kept.  min_faces= / largest= on the Extract / Save calls apply it to their indexed=True mesh before anything is downloaded.
+
 Case tables: kangaroo_amd/csrc/mc_tables.inc, derived by scripts/gen_mc_tables.py.  Their boundary loops and
 winding agree with the classic tables the reference uses in all 256 cases; 158 cases split a polygon along a
 different interior diagonal (an equally valid triangulation of the same loop), so meshes are the same surface
@@ -84,7 +89,75 @@ def _extract(dev, stream, nbytes, floor, has_color, indexed, with_index, plan, i
     return verts, norms, colors
 
 
-def ExtractMesh(vol, colorVol=None, stream=None, slab=None, with_index=False, indexed=False):
+def _filter_args(what, indexed, slab, min_faces, largest):
+    """whether a filter is asked for; it is honoured on an indexed mesh of a whole volume"""
+    if int(min_faces) < 0:
+        raise ValueError("%s: min_faces is a face count" % what)
+    if not (min_faces or largest):
+        return False
+    if not indexed:
+        raise ValueError("%s: min_faces / largest filter the indexed mesh (indexed=True)" % what)
+    if slab is not None:
+        raise ValueError("%s: a slab's mesh is welded within its rank, so its components are cut at the slab boundaries; "
+                         "min_faces / largest need the whole volume's mesh" % what)
+    return True
+
+
+def _clean_plan(L, faces, n_verts, st):
+    """(scratch, nbytes, V, T, counts) of a labelled face list: kfx_mesh_components_plan"""
+    if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("faces: a (T, 3) int32 tensor of uint32 ids")
+    faces = faces.contiguous()
+    nv, nt = int(n_verts), int(faces.shape[0])
+    nbytes = L.kfx_mesh_components_scratch_bytes(nv, nt)
+    scratch = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=faces.device)
+    counts = (C.c_ulonglong * 2)()
+    _lib.check(L.kfx_mesh_components_plan(_ptr(faces) if nt else None, nt, nv, _ptr(scratch), nbytes, counts, st))   # (nbytes 0: the reason)
+    return faces, scratch, nbytes, nv, nt, counts
+
+
+def MeshComponents(faces, n_verts, stream=None):
+    """The connected components of an indexed mesh (include/kfx_mesh_clean.h): faces (T, 3) int32 device tensor of uint32 ids < n_verts.
+    Returns (vertex_component (V,), component_faces (C,)), int32 device tensors of uint32 bits: components are numbered in ascending
+    order of their smallest vertex id; a vertex in no face is a component of its own with 0 faces."""
+    L = _lib.load()
+    st = _stream(stream)
+    faces, scratch, nbytes, nv, nt, counts = _clean_plan(L, faces, n_verts, st)
+    vc = torch.empty(nv, dtype=torch.int32, device=faces.device)
+    cf = torch.empty(int(counts[0]), dtype=torch.int32, device=faces.device)
+    if nt:
+        _lib.check(L.kfx_mesh_components_emit(_ptr(scratch), nbytes, nv, nt, counts, _ptr(vc), _ptr(cf), st))
+    return vc, cf
+
+
+def FilterMesh(verts, norms, colors, faces, min_faces=0, largest=False, stream=None):
+    """The indexed mesh (verts, norms, colors, faces) without its small components (include/kfx_mesh_clean.h): min_faces keeps the
+    components with at least that many faces, largest only the one with the most (ties: the smaller component id; min_faces still
+    applies).  Kept vertices and faces keep their order, faces are renumbered, rows are copied bit for bit; norms / colors may be None.
+    Returns new tensors (verts, norms, colors, faces); min_faces=0, largest=False returns the input's bits."""
+    L = _lib.load()
+    if int(min_faces) < 0:
+        raise ValueError("FilterMesh: min_faces is a face count")
+    st = _stream(stream)
+    verts = verts.contiguous()
+    norms = None if norms is None else norms.contiguous()
+    colors = None if colors is None else colors.contiguous()
+    for t, w, name in ((verts, 3, "verts"), (norms, 3, "norms"), (colors, 4, "colors")):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (len(verts), w)):
+            raise ValueError("FilterMesh: %s is a (V, %d) float32 tensor" % (name, w))
+    faces, scratch, nbytes, nv, nt, counts = _clean_plan(L, faces, len(verts), st)
+    kept = (C.c_ulonglong * 2)()
+    _lib.check(L.kfx_mesh_filter_plan(_ptr(scratch), nbytes, nv, nt, _ptr(faces) if nt else None, int(min_faces), int(bool(largest)), kept, st))
+    kv, kt = int(kept[0]), int(kept[1])
+    new = lambda t, rows: None if t is None else torch.empty((rows,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+    out = (new(verts, kv), new(norms, kv), new(colors, kv), new(faces, kt))
+    if kv:
+        _lib.check(L.kfx_mesh_filter_emit(_ptr(scratch), nbytes, nv, nt, kept, _ptr(verts), _ptr(norms), _ptr(colors), _ptr(faces),
+                                          *[_ptr(t) if t is not None and t.numel() else None for t in out], st))
+    return out
+
+
+def ExtractMesh(vol, colorVol=None, stream=None, slab=None, with_index=False, indexed=False, min_faces=0, largest=False):
     """Returns (verts, norms, colors): float32 device tensors of shape (3T, 3), (3T, 3) and (3T, 4) or None.
     indexed=True: (verts, norms, colors, faces) with V rows each and faces (T, 3), uint32 ids held in an int32 tensor (the weld
     of the arrays above by lattice edge, see the module docstring).
@@ -93,8 +166,10 @@ def ExtractMesh(vol, colorVol=None, stream=None, slab=None, with_index=False, in
     [z_offset, z_offset + vol.d) of that volume and the cubes with lower plane in [own_lo, min(own_hi, full_d - 1)) are meshed,
     each triangle bit-identical to the single-volume mesh's; colorVol is then the rank's colour slab (kind "c32", the planes and the
     box of `vol`; fp32 SDF cells) and the colours equal the single-volume mesh's too.  with_index: also return cube_index (int64, global) and
-    tri_offset (int32: the first triangle of each active cube, uint32 bits)."""
+    tri_offset (int32: the first triangle of each active cube, uint32 bits).
+    min_faces / largest (with indexed=True, whole volumes): FilterMesh's, applied on the device to the mesh returned."""
     L = _lib.load()
+    clean = _filter_args("ExtractMesh", indexed, slab, min_faces, largest)
     if vol.kind not in CELL:
         raise ValueError("ExtractMesh: volume kind %r (fp32 or half SDF cells)" % vol.kind)
     cell, dev = CELL[vol.kind], vol.storage.device
@@ -111,12 +186,13 @@ def ExtractMesh(vol, colorVol=None, stream=None, slab=None, with_index=False, in
     # IsValid() of the colour volume -- of the FULL one where colorVol is a slab of it
     has_color = colorVol is not None and min(colorVol.w, colorVol.h, colorVol.d if slab is None else int(slab[0])) >= 8
     cref = colorVol.ref() if has_color else None
-    return _extract(dev, stream, nbytes, 0, has_color, indexed, with_index,
+    got = _extract(dev, stream, nbytes, 0, has_color, indexed, with_index,
                     plan=lambda *a: L.kfx_mesh_plan(*args, *a),
                     index_bytes=lambda totals: L.kfx_mesh_index_scratch_bytes(*args, totals),
                     index_plan=lambda *a: L.kfx_mesh_index_plan(*args, *a),
                     emit=lambda *a: L.kfx_mesh_emit(*args, cref, *a),
                     emit_indexed=lambda scratch, nbytes, *a: L.kfx_mesh_emit_indexed(*args, cref, *a))   # (reads the index scratch alone)
+    return FilterMesh(*got, min_faces=min_faces, largest=largest, stream=stream) if clean else got
 
 
 BRICK_BYTES = {"f32": 4096, "f16": 2048, "c32": 2048}   # one packed 8 x 8 x 8 brick of each cell kind
@@ -143,7 +219,8 @@ def BrickMeshScratchBytes(n, n_color=0):
     return int(_lib.load().kfx_mesh_bricks_scratch_bytes(int(n), int(n_color)))
 
 
-def ExtractBrickMesh(dims, boxmin, boxmax, kind, ids, cells, color_ids=None, color_cells=None, with_index=False, stream=None, indexed=False):
+def ExtractBrickMesh(dims, boxmin, boxmax, kind, ids, cells, color_ids=None, color_cells=None, with_index=False, stream=None, indexed=False,
+                     min_faces=0, largest=False):
     """The mesh of packed 8 x 8 x 8 bricks (include/kfx_mesh_bricks.h): what ExtractMesh returns for the dense volume of `dims` cells and
     the box (boxmin, boxmax) that is NaN everywhere and then gets BrickUnpack(ids, cells) -- the same cubes, each with the same triangles
     bit for bit -- without that volume; memory in proportion to the bricks and the mesh.  Only the order differs: brick by brick in
@@ -155,8 +232,10 @@ def ExtractBrickMesh(dims, boxmin, boxmax, kind, ids, cells, color_ids=None, col
 
     indexed=True: (verts, norms, colors, faces) with V rows each and faces (T, 3), uint32 ids held in an int32 tensor, as ExtractMesh:
     the sequential first-occurrence weld, by lattice edge, of the arrays above in their (brick) order (include/kfx_mesh_bricks_index.h).
-    Not with with_index=True, which lists the soup's cubes."""
+    Not with with_index=True, which lists the soup's cubes.
+    min_faces / largest (with indexed=True): FilterMesh's, applied on the device to the mesh returned."""
     L = _lib.load()
+    clean = _filter_args("ExtractBrickMesh", indexed, None, min_faces, largest)
     if kind not in CELL:
         raise ValueError("ExtractBrickMesh: cell kind %r (fp32 or half SDF cells)" % (kind,))
     if indexed and with_index:
@@ -175,18 +254,21 @@ def ExtractBrickMesh(dims, boxmin, boxmax, kind, ids, cells, color_ids=None, col
     nbytes = BrickMeshScratchBytes(n, nc)   # (0: the counts are refused -- the plan says why)
     sdf = (C.byref(frame), CELL[kind], _ptr(ids) if n else None, _ptr(cells) if n else None, n)
     both = sdf + (_ptr(cids) if nc else None, _ptr(ccells) if nc else None, nc)
-    return _extract(device, stream, nbytes, 256, want_color, indexed, with_index,
+    got = _extract(device, stream, nbytes, 256, want_color, indexed, with_index,
                     plan=lambda *a: L.kfx_mesh_bricks_plan(*sdf, *a),
                     index_bytes=lambda totals: L.kfx_mesh_bricks_index_scratch_bytes(n, totals),
                     index_plan=lambda *a: L.kfx_mesh_bricks_index_plan(*sdf, *a),
                     emit=lambda *a: L.kfx_mesh_bricks_emit(*both, *a),
                     emit_indexed=lambda *a: L.kfx_mesh_bricks_emit_indexed(*both, *a))
+    return FilterMesh(*got, min_faces=min_faces, largest=largest, stream=stream) if clean else got
 
 
-def SaveBrickMesh(filename, dims, boxmin, boxmax, kind, ids, cells, color_ids=None, color_cells=None, binary=True, indexed=False):
+def SaveBrickMesh(filename, dims, boxmin, boxmax, kind, ids, cells, color_ids=None, color_cells=None, binary=True, indexed=False, min_faces=0,
+                  largest=False):
     """ExtractBrickMesh's mesh as filename + ".ply" (write_ply); returns the triangle count.  indexed=True: V welded vertices and T faces
-    instead of 3T vertices."""
-    return _save_mesh(filename, ExtractBrickMesh(dims, boxmin, boxmax, kind, ids, cells, color_ids, color_cells, indexed=indexed), binary, indexed)
+    instead of 3T vertices; min_faces / largest: ExtractBrickMesh's."""
+    arrays = ExtractBrickMesh(dims, boxmin, boxmax, kind, ids, cells, color_ids, color_cells, indexed=indexed, min_faces=min_faces, largest=largest)
+    return _save_mesh(filename, arrays, binary, indexed)
 
 
 def _save_mesh(filename, arrays, binary, indexed):
@@ -225,7 +307,8 @@ def write_ply(path, verts, norms, colors=None, binary=True, faces=None):
                 f.write(("3 %d %d %d\n" % (a, b, c)).encode())
 
 
-def SaveMesh(filename, vol, colorVol=None, binary=True, slab=None, indexed=False):
+def SaveMesh(filename, vol, colorVol=None, binary=True, slab=None, indexed=False, min_faces=0, largest=False):
     """SaveMesh(filename, vol[, volColor]) (MarchingCubes.h:246-262): writes filename + ".ply"; returns the triangle count.
-    fp32 or half volumes; slab: ExtractMesh's.  indexed=True: V welded vertices and T faces (ExtractMesh's) instead of 3T vertices."""
-    return _save_mesh(filename, ExtractMesh(vol, colorVol, slab=slab, indexed=indexed), binary, indexed)
+    fp32 or half volumes; slab: ExtractMesh's.  indexed=True: V welded vertices and T faces (ExtractMesh's) instead of 3T vertices;
+    min_faces / largest: ExtractMesh's."""
+    return _save_mesh(filename, ExtractMesh(vol, colorVol, slab=slab, indexed=indexed, min_faces=min_faces, largest=largest), binary, indexed)
