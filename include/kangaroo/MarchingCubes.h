@@ -10,6 +10,8 @@
 // lattice edge and a face list, welded on the device (include/kfx_mesh_index.h): about a third of the bytes, usable for adjacency.
 // roo::MeshComponents / roo::MeshFilter (include/kfx_mesh_clean.h) use that adjacency on the device: the connected components of an
 // indexed mesh, and the mesh without its small ones -- the floaters around the surface; SaveMeshIndexed takes min_faces / largest.
+// roo::MeshSimplify (include/kfx_mesh_simplify.h) is the level of detail after them: the vertices of one cell of a world-anchored grid
+// become one, on the device; SaveMeshIndexed(..., min_faces, largest, nvert, cell) applies it after the filter.
 #pragma once
 
 #include <cstdint>
@@ -20,6 +22,7 @@
 #include <kfx_mesh.h>
 #include <kfx_mesh_index.h>
 #include <kfx_mesh_clean.h>
+#include <kfx_mesh_simplify.h>
 
 #include <kangaroo/BoundedVolume.h>
 #include <kangaroo/Sdf.h>
@@ -97,9 +100,29 @@ inline void FilterBuffers(DeviceBuffer& dv, DeviceBuffer& dn, DeviceBuffer& dc, 
     nt = kept[1];
 }
 
-// The mesh of `vol` (slab: its cubes [own_lo, own_hi) of the volume `slab` describes); keep: an indexed mesh without its small components
+// An indexed mesh in device memory replaced by its simplification on a grid of `cell` world units anchored at the world origin
+// (include/kfx_mesh_simplify.h): kfx_mesh_simplify_plan, kfx_mesh_simplify_emit.
+inline void SimplifyBuffers(DeviceBuffer& dv, DeviceBuffer& dn, DeviceBuffer& dc, DeviceBuffer& faces, size_t& nv, size_t& nt, float cell)
+{
+    const size_t nbytes = kfx_mesh_simplify_scratch_bytes(nv, nt);
+    DeviceBuffer scratch(nbytes);
+    const float origin[3] = {0.0f, 0.0f, 0.0f};
+    unsigned long long kept[2] = {0, 0};
+    GpuCheckStatus(kfx_mesh_simplify_plan(dv.get<float>(), faces.get<unsigned>(), nt, nv, origin, cell, scratch.get(), nbytes, kept, 0));   // (nbytes 0: the reason)
+    DeviceBuffer ov(kept[0] * 12), on, oc, of(kept[1] * 12);
+    if (dn.get()) on = DeviceBuffer(kept[0] * 12);
+    if (dc.get()) oc = DeviceBuffer(kept[0] * 16);
+    GpuCheckStatus(kfx_mesh_simplify_emit(scratch.get(), nbytes, nv, nt, kept, dv.get<float>(), dn.get<float>(), dc.get<float>(), faces.get<unsigned>(),
+                                          ov.get<float>(), on.get<float>(), oc.get<float>(), of.get<unsigned>(), nullptr, 0));
+    dv = std::move(ov); dn = std::move(on); dc = std::move(oc); faces = std::move(of);
+    nv = kept[0];
+    nt = kept[1];
+}
+
+// The mesh of `vol` (slab: its cubes [own_lo, own_hi) of the volume `slab` describes); keep: an indexed mesh without its small components;
+// simplify_cell > 0: then simplified on a grid of that cell (0: off)
 inline HostMesh Extract(const kfx_volume* vol, int cell, const kfx_slab* slab, int own_lo, int own_hi, const kfx_volume* colorvol, bool indexed = false,
-                        const MeshKeep& keep = MeshKeep())
+                        const MeshKeep& keep = MeshKeep(), float simplify_cell = 0.0f)
 {
     const size_t nbytes = kfx_mesh_scratch_bytes(vol, cell, slab, own_lo, own_hi);
     if (!nbytes) GpuCheckStatus(kfx_mesh_plan(vol, cell, slab, own_lo, own_hi, nullptr, 0, nullptr, 0));   // the reason
@@ -134,6 +157,11 @@ inline HostMesh Extract(const kfx_volume* vol, int cell, const kfx_slab* slab, i
                                      offsets.get<unsigned>(), dv.get<float>(), dn.get<float>(), dc.get<float>(), 0));
     if (keep && indexed && m.ntri) {
         FilterBuffers(dv, dn, dc, faces, nv, m.ntri, keep);
+        m.nvert = nv;
+        m.faces.resize(3 * m.ntri);
+    }
+    if (simplify_cell != 0.0f && indexed && m.ntri) {   // (floaters go first: clustering changes face counts)
+        SimplifyBuffers(dv, dn, dc, faces, nv, m.ntri, simplify_cell);
         m.nvert = nv;
         m.faces.resize(3 * m.ntri);
     }
@@ -172,10 +200,10 @@ inline size_t WritePly(const std::string& path, const HostMesh& m)
 // SaveMesh / SaveMeshIndexed of a BoundedVolume<T>; a T without a Cell<T> does not compile
 template<typename T, typename Manage1, typename Manage2>
 inline size_t Save(const std::string& filename, BoundedVolume<T,TargetDevice,Manage1>& vol, BoundedVolume<float,TargetDevice,Manage2>* volColor, bool indexed, size_t* nvert,
-                   const MeshKeep& keep = MeshKeep())
+                   const MeshKeep& keep = MeshKeep(), float simplify_cell = 0.0f)
 {
     const bool color = volColor && volColor->IsValid();
-    const HostMesh m = Extract(vol.abi(), Cell<T>::kind, nullptr, 0, 0, color ? volColor->abi() : nullptr, indexed, keep);
+    const HostMesh m = Extract(vol.abi(), Cell<T>::kind, nullptr, 0, 0, color ? volColor->abi() : nullptr, indexed, keep, simplify_cell);
     if (nvert) *nvert = m.nvert;
     return WritePly(filename + ".ply", m);
 }
@@ -224,24 +252,26 @@ inline size_t SaveMeshIndexed(std::string filename, BoundedVolume<T,TargetDevice
 
 // SaveMeshIndexed(filename, vol[, volColor], min_faces, largest): the indexed mesh without its small components, filtered on the device
 // (include/kfx_mesh_clean.h) -- the components with at least min_faces faces; largest: only the one with the most, min_faces on top.
+// cell > 0: what is left is then simplified on the device on a grid of `cell` world units anchored at the world origin
+// (include/kfx_mesh_simplify.h); 0 means off, and min_faces = 0, largest = false filters nothing.
 template<typename T, typename Manage1, typename Manage2>
 inline size_t SaveMeshIndexed(std::string filename, BoundedVolume<T,TargetDevice,Manage1>& vol, BoundedVolume<float,TargetDevice,Manage2>* volColor, size_t min_faces,
-                              bool largest, size_t* nvert = nullptr)
+                              bool largest, size_t* nvert = nullptr, float cell = 0.0f)
 {
-    return mesh_detail::Save(filename, vol, volColor, true, nvert, mesh_detail::MeshKeep{min_faces, largest});
+    return mesh_detail::Save(filename, vol, volColor, true, nvert, mesh_detail::MeshKeep{min_faces, largest}, cell);
 }
 
 template<typename T, typename Manage>
-inline size_t SaveMeshIndexed(std::string filename, BoundedVolume<T,TargetDevice,Manage>& vol, size_t min_faces, bool largest, size_t* nvert = nullptr)
+inline size_t SaveMeshIndexed(std::string filename, BoundedVolume<T,TargetDevice,Manage>& vol, size_t min_faces, bool largest, size_t* nvert = nullptr, float cell = 0.0f)
 {
-    return SaveMeshIndexed<T,Manage,Manage>(filename, vol, nullptr, min_faces, largest, nvert);
+    return SaveMeshIndexed<T,Manage,Manage>(filename, vol, nullptr, min_faces, largest, nvert, cell);
 }
 
 template<typename T, typename Manage1, typename Manage2>
 inline size_t SaveMeshIndexed(std::string filename, BoundedVolume<T,TargetDevice,Manage1>& vol, BoundedVolume<float,TargetDevice,Manage2>& volColor, size_t min_faces,
-                              bool largest, size_t* nvert = nullptr)
+                              bool largest, size_t* nvert = nullptr, float cell = 0.0f)
 {
-    return SaveMeshIndexed<T,Manage1,Manage2>(filename, vol, &volColor, min_faces, largest, nvert);
+    return SaveMeshIndexed<T,Manage1,Manage2>(filename, vol, &volColor, min_faces, largest, nvert, cell);
 }
 
 // MeshComponents(faces, n_faces, n_verts, vertex_component, component_faces): the connected components of an indexed mesh whose faces
@@ -284,6 +314,38 @@ inline mesh_detail::HostMesh MeshFilter(const float* verts, const float* norms, 
     on.CopyTo(m.n.data(), m.n.size() * 4);
     oc.CopyTo(m.c.data(), m.c.size() * 4);
     of.CopyTo(m.faces.data(), m.faces.size() * 4);
+    return m;
+}
+
+// MeshSimplify(verts, norms, colors, faces, n_verts, n_faces, cell, origin[, vertex_cluster]): an indexed mesh in device memory (norms and
+// colors may be null) at the level of detail of a grid of `cell` world units anchored at `origin` (null: the world origin), as host
+// arrays (include/kfx_mesh_simplify.h): one vertex a cell -- the one nearest its centre, its row bit for bit --, the faces that collapse
+// or repeat dropped.  vertex_cluster, if given, receives every input vertex's new id (0xffffffff: its cluster is not written).
+inline mesh_detail::HostMesh MeshSimplify(const float* verts, const float* norms, const float* colors, const uint32_t* faces, size_t n_verts, size_t n_faces,
+                                          float cell, const float* origin = nullptr, std::vector<uint32_t>* vertex_cluster = nullptr)
+{
+    const float zero[3] = {0.0f, 0.0f, 0.0f};
+    const size_t nbytes = kfx_mesh_simplify_scratch_bytes(n_verts, n_faces);
+    mesh_detail::DeviceBuffer scratch(nbytes);
+    unsigned long long kept[2] = {0, 0};
+    GpuCheckStatus(kfx_mesh_simplify_plan(verts, faces, n_faces, n_verts, origin ? origin : zero, cell, scratch.get(), nbytes, kept, 0));   // (nbytes 0: the reason)
+    mesh_detail::HostMesh m;
+    m.nvert = kept[0];
+    m.ntri = kept[1];
+    m.color = colors != nullptr;
+    mesh_detail::DeviceBuffer ov(kept[0] * 12), on(norms ? kept[0] * 12 : 0), oc(colors ? kept[0] * 16 : 0), of(kept[1] * 12), map(vertex_cluster ? n_verts * 4 : 0);
+    GpuCheckStatus(kfx_mesh_simplify_emit(scratch.get(), nbytes, n_verts, n_faces, kept, verts, norms, colors, faces, ov.get<float>(),
+                                          norms ? on.get<float>() : nullptr, colors ? oc.get<float>() : nullptr, of.get<unsigned>(),
+                                          vertex_cluster ? map.get<unsigned>() : nullptr, 0));
+    m.v.resize(m.nvert * 3); m.n.resize(norms ? m.nvert * 3 : 0); m.c.resize(colors ? m.nvert * 4 : 0); m.faces.resize(m.ntri * 3);
+    ov.CopyTo(m.v.data(), m.v.size() * 4);
+    on.CopyTo(m.n.data(), m.n.size() * 4);
+    oc.CopyTo(m.c.data(), m.c.size() * 4);
+    of.CopyTo(m.faces.data(), m.faces.size() * 4);
+    if (vertex_cluster) {
+        vertex_cluster->resize(n_verts);
+        map.CopyTo(vertex_cluster->data(), n_verts * 4);
+    }
     return m;
 }
 

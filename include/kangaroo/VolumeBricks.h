@@ -183,7 +183,7 @@ namespace mesh_detail
 // edge.  cube_index and tri_offset, if given, receive every active cube's dense index and first triangle in the list's order (soup).
 inline HostMesh ExtractBricks(const kfx_volume& frame, int cell, const unsigned* ids, const void* cells, size_t n, const unsigned* color_ids,
                               const void* color_cells, size_t n_color, bool color, bool indexed = false, std::vector<long long>* cube_index = nullptr,
-                              std::vector<unsigned>* tri_offset = nullptr, const MeshKeep& keep = MeshKeep())
+                              std::vector<unsigned>* tri_offset = nullptr, const MeshKeep& keep = MeshKeep(), float simplify_cell = 0.0f)
 {
     const size_t nbytes = MeshBricksScratchBytes(n, color ? n_color : 0);
     DeviceBuffer scratch(nbytes), xscratch, active, offsets, faces;
@@ -218,6 +218,11 @@ inline HostMesh ExtractBricks(const kfx_volume& frame, int cell, const unsigned*
                        dv.get<float>(), dn.get<float>(), dc.get<float>());
     if (keep && indexed && m.ntri) {   // (MarchingCubes.h: the indexed mesh without its small components)
         FilterBuffers(dv, dn, dc, faces, nv, m.ntri, keep);
+        m.nvert = nv;
+        m.faces.resize(3 * m.ntri);
+    }
+    if (simplify_cell != 0.0f && indexed && m.ntri) {   // (... and then simplified on a grid of that cell, anchored at the world origin)
+        SimplifyBuffers(dv, dn, dc, faces, nv, m.ntri, simplify_cell);
         m.nvert = nv;
         m.faces.resize(3 * m.ntri);
     }
@@ -264,22 +269,23 @@ inline size_t SaveMeshBricksIndexed(std::string filename, const kfx_volume& fram
     return mesh_detail::WritePly(filename + ".ply", m);
 }
 
-// ... min_faces, largest: without its small components, filtered on the device (MarchingCubes.h: SaveMeshIndexed's)
+// ... min_faces, largest: without its small components, filtered on the device (MarchingCubes.h: SaveMeshIndexed's); simplify_cell > 0:
+// then simplified on a grid of that cell anchored at the world origin (include/kfx_mesh_simplify.h), 0: off
 inline size_t SaveMeshBricksIndexed(std::string filename, const kfx_volume& frame, int cell, const unsigned* ids, const void* cells, size_t n,
-                                    size_t min_faces, bool largest, size_t* nvert = nullptr)
+                                    size_t min_faces, bool largest, size_t* nvert = nullptr, float simplify_cell = 0.0f)
 {
     const mesh_detail::HostMesh m = mesh_detail::ExtractBricks(frame, cell, ids, cells, n, nullptr, nullptr, 0, false, true, nullptr, nullptr,
-                                                               mesh_detail::MeshKeep{min_faces, largest});
+                                                               mesh_detail::MeshKeep{min_faces, largest}, simplify_cell);
     if (nvert) *nvert = m.nvert;
     return mesh_detail::WritePly(filename + ".ply", m);
 }
 
 inline size_t SaveMeshBricksIndexed(std::string filename, const kfx_volume& frame, int cell, const unsigned* ids, const void* cells, size_t n,
                                     const unsigned* color_ids, const void* color_cells, size_t n_color, size_t min_faces, bool largest,
-                                    size_t* nvert = nullptr)
+                                    size_t* nvert = nullptr, float simplify_cell = 0.0f)
 {
     const mesh_detail::HostMesh m = mesh_detail::ExtractBricks(frame, cell, ids, cells, n, color_ids, color_cells, n_color, true, true, nullptr,
-                                                               nullptr, mesh_detail::MeshKeep{min_faces, largest});
+                                                               nullptr, mesh_detail::MeshKeep{min_faces, largest}, simplify_cell);
     if (nvert) *nvert = m.nvert;
     return mesh_detail::WritePly(filename + ".ply", m);
 }

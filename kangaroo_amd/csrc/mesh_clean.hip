@@ -19,9 +19,8 @@
 // Positions are handed out by scans alone (block_scan.h; partials -> base -> apply, as mesh.hip): no atomic orders anything, the
 // atomics that remain are integer sums, maxima and links whose result does not depend on arrival order, so every output is a
 // function of (V, faces) and the filter's parameters.
-#include "block_scan.h"
 #include "host_args.h"
-#include "mesh_clean_host.h"
+#include "mesh_clean_device.h"   // raise, block_sum, k_clean_validate, k_clean_scan: shared with mesh_simplify.hip
 
 namespace kfx {
 
@@ -40,24 +39,6 @@ struct AgentParent {
         return expected;   // (the value found)
     }
 };
-
-__device__ __forceinline__ void raise(u64* hdr, u64 bits) { __hip_atomic_fetch_or(hdr + CLEAN_W_ERROR, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the sum of one value per thread over a workgroup of 256, in every thread
-__device__ __forceinline__ unsigned block_sum(unsigned v)
-{
-    __shared__ unsigned lds[4];
-    unsigned total;
-    block_exclusive_scan<unsigned, 4>(v, lds, &total);
-    return total;
-}
-
-__global__ __launch_bounds__(256) void k_clean_validate(const unsigned* __restrict__ faces, const u64 n_ids, const unsigned n_verts, u64* __restrict__ hdr)
-{
-    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
-    const bool bad = i < n_ids && faces[i] >= n_verts;
-    if (__ballot(bad) && (threadIdx.x & 63) == 0) raise(hdr, CLEAN_ERR_FACE_ID);
-}
 
 __global__ __launch_bounds__(256) void k_clean_init(unsigned* __restrict__ parent, unsigned* __restrict__ cnt, const unsigned n_verts,
                                                     const unsigned n_faces, u64* __restrict__ hdr)
@@ -164,35 +145,6 @@ __global__ __launch_bounds__(256) void k_clean_roots(const unsigned* __restrict_
         for (int i = 1; i < 4; ++i) best = s_best[i] > best ? s_best[i] : best;
         if (best) __hip_atomic_fetch_max(hdr + CLEAN_W_BEST, best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-}
-
-// one workgroup: the exclusive offsets of n blocks and their total (< 2^32: they count vertices or faces)
-constexpr int CLEAN_SCAN_THREADS = 1024, CLEAN_SCAN_PER_THREAD = 8;
-__global__ __launch_bounds__(CLEAN_SCAN_THREADS) void k_clean_scan(const unsigned* __restrict__ part, const unsigned n, unsigned* __restrict__ base,
-                                                                   u64* __restrict__ hdr, const int total_word)
-{
-    if (hdr[CLEAN_W_ERROR]) return;
-    __shared__ unsigned lds[CLEAN_SCAN_THREADS / 64];
-    unsigned run = 0;
-    constexpr unsigned CHUNK = CLEAN_SCAN_THREADS * CLEAN_SCAN_PER_THREAD;
-    for (u64 c0 = 0; c0 < n; c0 += CHUNK) {
-        const u64 b0 = c0 + (u64)threadIdx.x * CLEAN_SCAN_PER_THREAD;
-        unsigned v[CLEAN_SCAN_PER_THREAD], sum = 0;
-#pragma unroll
-        for (int j = 0; j < CLEAN_SCAN_PER_THREAD; ++j) {
-            v[j] = b0 + j < n ? part[b0 + j] : 0u;
-            sum += v[j];
-        }
-        unsigned total;
-        unsigned ex = block_exclusive_scan<unsigned, CLEAN_SCAN_THREADS / 64>(sum, lds, &total) + run;
-#pragma unroll
-        for (int j = 0; j < CLEAN_SCAN_PER_THREAD; ++j) {
-            if (b0 + j < n) base[b0 + j] = ex;
-            ex += v[j];
-        }
-        run += total;
-    }
-    if (threadIdx.x == 0) hdr[total_word] = run;
 }
 
 // the stage a plan has reached and, of a filter plan, its parameters -- unless an error was raised

@@ -28,6 +28,11 @@ connected when a face contains both; numbered by their smallest vertex id), Filt
 faces -- the floaters depth noise and unobserved cells leave around the surface -- or all but the largest, and compacts what is left,
 order and bits kept.  min_faces= / largest= on the Extract / Save calls apply it to their indexed=True mesh before anything is downloaded.
 
+Level of detail (include/kfx_mesh_simplify.h), on an indexed mesh in device memory: SimplifyMesh clusters the vertices on a grid anchored
+in the world -- one vertex a cell, the one nearest its centre -- and drops the faces that collapse or repeat; every output bit is a
+function of the mesh and the grid.  simplify_cell= on the Extract / Save calls applies it after the filter: the mesh's resolution is
+no longer tied to the volume's.
+
 Case tables: kangaroo_amd/csrc/mc_tables.inc, derived by scripts/gen_mc_tables.py.  Their boundary loops and
 winding agree with the classic tables the reference uses in all 256 cases; 158 cases split a polygon along a
 different interior diagonal (an equally valid triangulation of the same loop), so meshes are the same surface
@@ -157,7 +162,64 @@ def FilterMesh(verts, norms, colors, faces, min_faces=0, largest=False, stream=N
     return out
 
 
-def ExtractMesh(vol, colorVol=None, stream=None, slab=None, with_index=False, indexed=False, min_faces=0, largest=False):
+def _simplify_args(what, indexed, slab, simplify_cell):
+    """whether a simplification is asked for (simplify_cell: None or 0 is off); it is honoured on an indexed mesh of a whole volume"""
+    if simplify_cell is None or simplify_cell == 0:
+        return False
+    if not indexed:
+        raise ValueError("%s: simplify_cell clusters the vertices of the indexed mesh (indexed=True)" % what)
+    if slab is not None:
+        raise ValueError("%s: a slab's mesh is welded within its rank: a cluster that straddles a slab boundary would be two; "
+                         "simplify_cell needs the whole volume's mesh" % what)
+    return True
+
+
+def _finish(got, clean, simplify, min_faces, largest, simplify_cell, stream):
+    """an indexed mesh after the steps its Extract call was asked for: floaters go first, because clustering changes face counts"""
+    if clean:
+        got = FilterMesh(*got, min_faces=min_faces, largest=largest, stream=stream)
+    if simplify:
+        got = SimplifyMesh(*got, cell=simplify_cell, stream=stream)
+    return got
+
+
+def SimplifyMesh(verts, norms, colors, faces, cell, origin=(0.0, 0.0, 0.0), stream=None, with_map=False):
+    """The indexed mesh (verts, norms, colors, faces) at the level of detail of a grid of `cell` world units anchored at `origin`
+    (include/kfx_mesh_simplify.h): the vertices of one grid cell become one vertex -- the one nearest the cell's centre, ties to the
+    smaller id, its row copied bit for bit --, faces that lose a corner that way are dropped, and so are all but the first of the faces
+    with one set of corners.  Every output bit is a function of the arrays, cell and origin; norms / colors may be None.
+    Returns new tensors (verts, norms, colors, faces); with_map=True: also vertex_cluster (V,), every input vertex's new id (uint32 bits
+    in an int32 tensor, 0xffffffff where its cluster is not written)."""
+    L = _lib.load()
+    st = _stream(stream)
+    verts = verts.contiguous()
+    norms = None if norms is None else norms.contiguous()
+    colors = None if colors is None else colors.contiguous()
+    for t, w, name in ((verts, 3, "verts"), (norms, 3, "norms"), (colors, 4, "colors")):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (len(verts), w)):
+            raise ValueError("SimplifyMesh: %s is a (V, %d) float32 tensor" % (name, w))
+    if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("SimplifyMesh: faces is a (T, 3) int32 tensor of uint32 ids")
+    faces = faces.contiguous()
+    nv, nt = len(verts), int(faces.shape[0])
+    nbytes = L.kfx_mesh_simplify_scratch_bytes(nv, nt)
+    scratch = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=faces.device)
+    kept = (C.c_ulonglong * 2)()
+    org = (C.c_float * 3)(*[float(x) for x in origin])
+    _lib.check(L.kfx_mesh_simplify_plan(_ptr(verts) if nv else None, _ptr(faces) if nt else None, nt, nv, org, float(cell), _ptr(scratch), nbytes,
+                                        kept, st))   # (nbytes 0: the reason)
+    kv, kt = int(kept[0]), int(kept[1])
+    new = lambda t, rows: None if t is None else torch.empty((rows,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+    out = (new(verts, kv), new(norms, kv), new(colors, kv), new(faces, kt))
+    vmap = torch.full((nv,), -1, dtype=torch.int32, device=faces.device) if with_map else None
+    if nt:
+        _lib.check(L.kfx_mesh_simplify_emit(_ptr(scratch), nbytes, nv, nt, kept, _ptr(verts), _ptr(norms), _ptr(colors), _ptr(faces),
+                                            *[_ptr(t) if t is not None and t.numel() else None for t in out],
+                                            _ptr(vmap) if with_map and nv else None, st))
+    return out + (vmap,) if with_map else out
+
+
+def ExtractMesh(vol, colorVol=None, stream=None, slab=None, with_index=False, indexed=False, min_faces=0, largest=False, simplify_cell=None):
     """Returns (verts, norms, colors): float32 device tensors of shape (3T, 3), (3T, 3) and (3T, 4) or None.
     indexed=True: (verts, norms, colors, faces) with V rows each and faces (T, 3), uint32 ids held in an int32 tensor (the weld
     of the arrays above by lattice edge, see the module docstring).
@@ -167,9 +229,11 @@ def ExtractMesh(vol, colorVol=None, stream=None, slab=None, with_index=False, in
     each triangle bit-identical to the single-volume mesh's; colorVol is then the rank's colour slab (kind "c32", the planes and the
     box of `vol`; fp32 SDF cells) and the colours equal the single-volume mesh's too.  with_index: also return cube_index (int64, global) and
     tri_offset (int32: the first triangle of each active cube, uint32 bits).
-    min_faces / largest (with indexed=True, whole volumes): FilterMesh's, applied on the device to the mesh returned."""
+    min_faces / largest (with indexed=True, whole volumes): FilterMesh's, applied on the device to the mesh returned.
+    simplify_cell (with indexed=True, whole volumes): SimplifyMesh's cell, anchored at the world origin, applied after the filter."""
     L = _lib.load()
     clean = _filter_args("ExtractMesh", indexed, slab, min_faces, largest)
+    simplify = _simplify_args("ExtractMesh", indexed, slab, simplify_cell)
     if vol.kind not in CELL:
         raise ValueError("ExtractMesh: volume kind %r (fp32 or half SDF cells)" % vol.kind)
     cell, dev = CELL[vol.kind], vol.storage.device
@@ -192,7 +256,7 @@ def ExtractMesh(vol, colorVol=None, stream=None, slab=None, with_index=False, in
                     index_plan=lambda *a: L.kfx_mesh_index_plan(*args, *a),
                     emit=lambda *a: L.kfx_mesh_emit(*args, cref, *a),
                     emit_indexed=lambda scratch, nbytes, *a: L.kfx_mesh_emit_indexed(*args, cref, *a))   # (reads the index scratch alone)
-    return FilterMesh(*got, min_faces=min_faces, largest=largest, stream=stream) if clean else got
+    return _finish(got, clean, simplify, min_faces, largest, simplify_cell, stream)
 
 
 BRICK_BYTES = {"f32": 4096, "f16": 2048, "c32": 2048}   # one packed 8 x 8 x 8 brick of each cell kind
@@ -220,7 +284,7 @@ def BrickMeshScratchBytes(n, n_color=0):
 
 
 def ExtractBrickMesh(dims, boxmin, boxmax, kind, ids, cells, color_ids=None, color_cells=None, with_index=False, stream=None, indexed=False,
-                     min_faces=0, largest=False):
+                     min_faces=0, largest=False, simplify_cell=None):
     """The mesh of packed 8 x 8 x 8 bricks (include/kfx_mesh_bricks.h): what ExtractMesh returns for the dense volume of `dims` cells and
     the box (boxmin, boxmax) that is NaN everywhere and then gets BrickUnpack(ids, cells) -- the same cubes, each with the same triangles
     bit for bit -- without that volume; memory in proportion to the bricks and the mesh.  Only the order differs: brick by brick in
@@ -233,9 +297,11 @@ def ExtractBrickMesh(dims, boxmin, boxmax, kind, ids, cells, color_ids=None, col
     indexed=True: (verts, norms, colors, faces) with V rows each and faces (T, 3), uint32 ids held in an int32 tensor, as ExtractMesh:
     the sequential first-occurrence weld, by lattice edge, of the arrays above in their (brick) order (include/kfx_mesh_bricks_index.h).
     Not with with_index=True, which lists the soup's cubes.
-    min_faces / largest (with indexed=True): FilterMesh's, applied on the device to the mesh returned."""
+    min_faces / largest (with indexed=True): FilterMesh's, applied on the device to the mesh returned.
+    simplify_cell (with indexed=True): SimplifyMesh's cell, anchored at the origin of the box's coordinates, applied after the filter."""
     L = _lib.load()
     clean = _filter_args("ExtractBrickMesh", indexed, None, min_faces, largest)
+    simplify = _simplify_args("ExtractBrickMesh", indexed, None, simplify_cell)
     if kind not in CELL:
         raise ValueError("ExtractBrickMesh: cell kind %r (fp32 or half SDF cells)" % (kind,))
     if indexed and with_index:
@@ -260,14 +326,15 @@ def ExtractBrickMesh(dims, boxmin, boxmax, kind, ids, cells, color_ids=None, col
                     index_plan=lambda *a: L.kfx_mesh_bricks_index_plan(*sdf, *a),
                     emit=lambda *a: L.kfx_mesh_bricks_emit(*both, *a),
                     emit_indexed=lambda *a: L.kfx_mesh_bricks_emit_indexed(*both, *a))
-    return FilterMesh(*got, min_faces=min_faces, largest=largest, stream=stream) if clean else got
+    return _finish(got, clean, simplify, min_faces, largest, simplify_cell, stream)
 
 
 def SaveBrickMesh(filename, dims, boxmin, boxmax, kind, ids, cells, color_ids=None, color_cells=None, binary=True, indexed=False, min_faces=0,
-                  largest=False):
+                  largest=False, simplify_cell=None):
     """ExtractBrickMesh's mesh as filename + ".ply" (write_ply); returns the triangle count.  indexed=True: V welded vertices and T faces
-    instead of 3T vertices; min_faces / largest: ExtractBrickMesh's."""
-    arrays = ExtractBrickMesh(dims, boxmin, boxmax, kind, ids, cells, color_ids, color_cells, indexed=indexed, min_faces=min_faces, largest=largest)
+    instead of 3T vertices; min_faces / largest / simplify_cell: ExtractBrickMesh's."""
+    arrays = ExtractBrickMesh(dims, boxmin, boxmax, kind, ids, cells, color_ids, color_cells, indexed=indexed, min_faces=min_faces, largest=largest,
+                              simplify_cell=simplify_cell)
     return _save_mesh(filename, arrays, binary, indexed)
 
 
@@ -307,8 +374,9 @@ def write_ply(path, verts, norms, colors=None, binary=True, faces=None):
                 f.write(("3 %d %d %d\n" % (a, b, c)).encode())
 
 
-def SaveMesh(filename, vol, colorVol=None, binary=True, slab=None, indexed=False, min_faces=0, largest=False):
+def SaveMesh(filename, vol, colorVol=None, binary=True, slab=None, indexed=False, min_faces=0, largest=False, simplify_cell=None):
     """SaveMesh(filename, vol[, volColor]) (MarchingCubes.h:246-262): writes filename + ".ply"; returns the triangle count.
     fp32 or half volumes; slab: ExtractMesh's.  indexed=True: V welded vertices and T faces (ExtractMesh's) instead of 3T vertices;
-    min_faces / largest: ExtractMesh's."""
-    return _save_mesh(filename, ExtractMesh(vol, colorVol, slab=slab, indexed=indexed, min_faces=min_faces, largest=largest), binary, indexed)
+    min_faces / largest / simplify_cell: ExtractMesh's."""
+    arrays = ExtractMesh(vol, colorVol, slab=slab, indexed=indexed, min_faces=min_faces, largest=largest, simplify_cell=simplify_cell)
+    return _save_mesh(filename, arrays, binary, indexed)

@@ -352,23 +352,26 @@ class FramePipeline:
         skeys = self.store.keys() if self.store is not None else None
         return sdf, bricks.world_bricks(self.cstore, self.cvol, self.origin, 0.5, ops=self.ops, cover=skeys)
 
-    def ExtractWorldMesh(self, with_index=False, indexed=False, min_faces=0, largest=False):
+    def ExtractWorldMesh(self, with_index=False, indexed=False, min_faces=0, largest=False, simplify_cell=None):
         """The mesh of everything the model has seen -- the live volume and what it spilled -- as mesh.ExtractBrickMesh returns it:
         continuous across the faces of the volume that no longer exist.  Without a store: the brick mesh of the live volume.
         indexed=True: (verts, norms, colors, faces), welded by lattice edge on the device (mesh.ExtractBrickMesh's); min_faces / largest:
-        without its small components (mesh.FilterMesh's)."""
+        without its small components (mesh.FilterMesh's); simplify_cell: then clustered on a grid of that cell anchored at the world origin
+        (mesh.SimplifyMesh's) -- two world meshes taken at different times simplify to the same vertices where the surface has not changed."""
         from . import mesh
         mesh._filter_args("ExtractWorldMesh", indexed, None, min_faces, largest)   # (before the bricks are packed)
+        mesh._simplify_args("ExtractWorldMesh", indexed, None, simplify_cell)
         (lo, dims, bmin, bmax, ids, cells), col = self.world_bricks()
         cids, ccells = (col[4], col[5]) if col is not None else (None, None)
         return mesh.ExtractBrickMesh(dims, bmin, bmax, self.kind, ids, cells, cids, ccells, with_index=with_index, indexed=indexed,
-                                     min_faces=min_faces, largest=largest)
+                                     min_faces=min_faces, largest=largest, simplify_cell=simplify_cell)
 
-    def SaveWorldMesh(self, filename, binary=True, indexed=False, min_faces=0, largest=False):
+    def SaveWorldMesh(self, filename, binary=True, indexed=False, min_faces=0, largest=False, simplify_cell=None):
         """ExtractWorldMesh's mesh as filename + ".ply"; returns the triangle count.  indexed=True: V welded vertices and T faces;
-        min_faces / largest: ExtractWorldMesh's."""
+        min_faces / largest / simplify_cell: ExtractWorldMesh's."""
         from . import mesh
-        return mesh._save_mesh(filename, self.ExtractWorldMesh(indexed=indexed, min_faces=min_faces, largest=largest), binary, indexed)
+        arrays = self.ExtractWorldMesh(indexed=indexed, min_faces=min_faces, largest=largest, simplify_cell=simplify_cell)
+        return mesh._save_mesh(filename, arrays, binary, indexed)
 
     def world_view(self):
         """Everything the model holds, ready to be rendered (include/kfx_raycast_bricks.h): world_bricks() packed and planned once.
@@ -1006,7 +1009,7 @@ class SlabPipeline(FramePipeline):
         raise ValueError("SlabPipeline: the world view belongs to a volume that follows the camera (follow=), a single-volume option; "
                          "the model's rendering is the frame's composite")
 
-    def ExtractMesh(self, indexed=False, min_faces=0, largest=False):
+    def ExtractMesh(self, indexed=False, min_faces=0, largest=False, simplify_cell=None):
         """This rank's part of the model's mesh (include/kfx_mesh.h): the cubes whose lower plane it owns, [z0, min(z1, D - 1)),
         every triangle bit-identical to the single-volume mesh's, in emission order; (verts, norms) device tensors, or -- color=True --
         (verts, norms, colors) with the single-volume mesh's colours.
@@ -1018,6 +1021,8 @@ class SlabPipeline(FramePipeline):
         if min_faces or largest:
             raise ValueError("SlabPipeline.ExtractMesh: a rank's mesh is welded within its rank, so its components are cut at the slab "
                              "boundaries; min_faces / largest need the whole volume's mesh")
+        if simplify_cell:   # (refused as the filter is: a cluster that straddles a slab boundary would be two)
+            raise ValueError("SlabPipeline.ExtractMesh: a rank's mesh is welded within its rank; simplify_cell needs the whole volume's mesh")
         if self.sframe is not None:
             self.wait_composite()
         elif self.halo == "exchange" and self.world > 1:
@@ -1027,11 +1032,11 @@ class SlabPipeline(FramePipeline):
         verts, norms, colors, *faces = mesh.ExtractMesh(self.vol, self.cvol if self.color else None, slab=slab, indexed=indexed)
         return ((verts, norms, colors) if self.color else (verts, norms)) + tuple(faces)
 
-    def SaveMesh(self, prefix, binary=True, indexed=False, min_faces=0, largest=False):
+    def SaveMesh(self, prefix, binary=True, indexed=False, min_faces=0, largest=False, simplify_cell=None):
         """Writes this rank's part as prefix.r<rank>.ply (with colours when color=True); returns its triangle count.
         indexed=True: welded vertices and a face list (ExtractMesh's).  min_faces / largest: refused, as ExtractMesh's."""
         from . import mesh
-        verts, norms, *rest = self.ExtractMesh(indexed=indexed, min_faces=min_faces, largest=largest)
+        verts, norms, *rest = self.ExtractMesh(indexed=indexed, min_faces=min_faces, largest=largest, simplify_cell=simplify_cell)
         faces = rest.pop().cpu().numpy().view("uint32") if indexed else None
         mesh.write_ply("%s.r%d.ply" % (prefix, self.rank), verts.cpu().numpy(), norms.cpu().numpy(),
                        rest[0].cpu().numpy() if rest and rest[0] is not None else None, binary, faces)
