@@ -105,6 +105,7 @@ int main(int argc, char** argv)
     long mesh_min_faces = 0;           // --mesh-min-faces N (with --mesh-indexed): ... without the components of fewer than N faces, removed on the device
     bool mesh_largest = false;         // --mesh-largest (with --mesh-indexed): ... only the component with the most faces
     float mesh_cell = 0.0f;            // --mesh-cell X (with --mesh-indexed): ... then simplified on the device on a grid of X metres anchored at the world origin
+    int mesh_smooth = 0;               // --mesh-smooth N (with --mesh-indexed): ... then smoothed on the device by N Taubin iterations, the normals recomputed from the faces
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--res") && i + 1 < argc) volres = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--frames") && i + 1 < argc) frames = atoi(argv[++i]);
@@ -124,6 +125,11 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--mesh-min-faces") && i + 1 < argc) mesh_min_faces = atol(argv[++i]);
         else if (!strcmp(argv[i], "--mesh-largest")) mesh_largest = true;
         else if (!strcmp(argv[i], "--mesh-cell") && i + 1 < argc) mesh_cell = (float)atof(argv[++i]);
+        else if (!strcmp(argv[i], "--mesh-smooth") && i + 1 < argc) mesh_smooth = atoi(argv[++i]);
+    }
+    if (mesh_smooth < 0 || (mesh_smooth != 0 && !mesh_indexed)) {
+        fprintf(stderr, "--mesh-smooth N (N >= 0 iterations) smooths the indexed mesh: it needs --mesh-indexed\n");
+        return 2;
     }
     if (!(mesh_cell >= 0.0f) || !std::isfinite(mesh_cell) || (mesh_cell != 0.0f && !mesh_indexed)) {
         fprintf(stderr, "--mesh-cell X (a length, X > 0) simplifies the indexed mesh: it needs --mesh-indexed\n");
@@ -445,13 +451,14 @@ int main(int argc, char** argv)
         size_t nvert = 0;
         const bool clean = mesh_min_faces || mesh_largest;
         const size_t min_faces = (size_t)mesh_min_faces;
-        const size_t ntri = clean || mesh_cell != 0.0f
-                                ? (use_colour ? SaveMeshIndexed(save_mesh, vol, colorVol, min_faces, mesh_largest, &nvert, mesh_cell)
-                                              : SaveMeshIndexed(save_mesh, vol, min_faces, mesh_largest, &nvert, mesh_cell))
+        const size_t ntri = clean || mesh_cell != 0.0f || mesh_smooth != 0
+                                ? (use_colour ? SaveMeshIndexed(save_mesh, vol, colorVol, min_faces, mesh_largest, &nvert, mesh_cell, mesh_smooth)
+                                              : SaveMeshIndexed(save_mesh, vol, min_faces, mesh_largest, &nvert, mesh_cell, mesh_smooth))
                                 : (use_colour ? SaveMeshIndexed(save_mesh, vol, colorVol, &nvert) : SaveMeshIndexed(save_mesh, vol, &nvert));
         printf("  mesh: %zu triangles, %zu vertices written to %s.ply\n", ntri, nvert, save_mesh);
         if (clean) printf("  mesh clean-up: components of at least %zu faces%s\n", min_faces, mesh_largest ? ", the largest only" : "");
         if (mesh_cell != 0.0f) printf("  mesh simplification: one vertex per cell of %g m\n", (double)mesh_cell);
+        if (mesh_smooth != 0) printf("  mesh smoothing: %d Taubin iterations, normals from the faces\n", mesh_smooth);
     } else if (save_mesh) {
         const size_t ntri = use_colour ? SaveMesh(save_mesh, vol, colorVol) : SaveMesh(save_mesh, vol);   // main.cpp:187
         printf("  mesh: %zu triangles written to %s.ply\n", ntri, save_mesh);

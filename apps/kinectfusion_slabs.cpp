@@ -49,6 +49,7 @@ struct Options {
     std::string save_mesh;    // --save-mesh PREFIX: after the last frame every rank writes its part of the mesh as PREFIX.r<rank>.ply
     long mesh_min_faces = 0;     // --mesh-min-faces N (with --mesh-indexed, one rank): ... without the components of fewer than N faces
     bool mesh_largest = false;   // --mesh-largest (with --mesh-indexed, one rank): ... only the component with the most faces
+    int mesh_smooth = 0;         // --mesh-smooth N (with --mesh-indexed, one rank): ... then smoothed by N Taubin iterations, the normals recomputed from the faces
     float mesh_cell = 0.0f;      // --mesh-cell X (with --mesh-indexed, one rank): ... then simplified on a grid of X metres anchored at the world origin
     bool mesh_indexed = false;   // --mesh-indexed: ... through SlabVolume::SaveMeshIndexed: welded vertices and a face list, per rank
     bool color = false;       // --color: colour volume, colour SdfFuse, colour renderings
@@ -370,10 +371,10 @@ static void RunRank(const Options& o, kfx_comm* comm, const std::vector<std::vec
     kfx_free(dsum);
     res->chk_vol = (unsigned)hsum[0];
     res->chk_col = (unsigned)hsum[1];
-    if (!o.save_mesh.empty() && (o.mesh_min_faces || o.mesh_largest || o.mesh_cell != 0.0f)) {   // (one rank: its slab is the whole volume, so roo::SaveMeshIndexed's filter and cell apply)
+    if (!o.save_mesh.empty() && (o.mesh_min_faces || o.mesh_largest || o.mesh_cell != 0.0f || o.mesh_smooth)) {   // (one rank: its slab is the whole volume, so roo::SaveMeshIndexed's filter, cell and smoothing apply)
         const std::string name = o.save_mesh + ".r" + std::to_string(comm->rank);
-        res->mesh_tris = slab.color ? SaveMeshIndexed(name, slab.local, *slab.color, (size_t)o.mesh_min_faces, o.mesh_largest, &res->mesh_verts, o.mesh_cell)
-                                    : SaveMeshIndexed(name, slab.local, (size_t)o.mesh_min_faces, o.mesh_largest, &res->mesh_verts, o.mesh_cell);
+        res->mesh_tris = slab.color ? SaveMeshIndexed(name, slab.local, *slab.color, (size_t)o.mesh_min_faces, o.mesh_largest, &res->mesh_verts, o.mesh_cell, o.mesh_smooth)
+                                    : SaveMeshIndexed(name, slab.local, (size_t)o.mesh_min_faces, o.mesh_largest, &res->mesh_verts, o.mesh_cell, o.mesh_smooth);
     } else if (!o.save_mesh.empty())   // this rank's cubes; the ghost planes the normals read are current after the last fuse
         res->mesh_tris = o.mesh_indexed ? slab.SaveMeshIndexed(o.save_mesh + ".r" + std::to_string(comm->rank), &res->mesh_verts)
                                         : slab.SaveMesh(o.save_mesh + ".r" + std::to_string(comm->rank));
@@ -381,7 +382,7 @@ static void RunRank(const Options& o, kfx_comm* comm, const std::vector<std::vec
 
 // a rank's mesh is welded within its rank (SlabVolume::SaveMeshIndexed refuses the filter for that reason)
 static const char* const kMeshFilterNeedsOneRank =
-    "--mesh-min-faces / --mesh-largest / --mesh-cell: a rank's mesh is welded within its rank, so its components are cut at the slab boundaries; "
+    "--mesh-min-faces / --mesh-largest / --mesh-cell / --mesh-smooth: a rank's mesh is welded within its rank, so its components are cut at the slab boundaries; "
     "run with one rank, or filter the whole volume's mesh (kinectfusion_headless)\n";
 
 int main(int argc, char** argv)
@@ -413,6 +414,7 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--mesh-min-faces") && i + 1 < argc) o.mesh_min_faces = atol(argv[++i]);
         else if (!strcmp(argv[i], "--mesh-largest")) o.mesh_largest = true;
         else if (!strcmp(argv[i], "--mesh-cell") && i + 1 < argc) o.mesh_cell = (float)atof(argv[++i]);
+        else if (!strcmp(argv[i], "--mesh-smooth") && i + 1 < argc) o.mesh_smooth = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--color") || !strcmp(argv[i], "--colour")) o.color = true;
         else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
@@ -422,6 +424,10 @@ int main(int argc, char** argv)
     }
     if (!(o.mesh_cell >= 0.0f) || !std::isfinite(o.mesh_cell) || (o.mesh_cell != 0.0f && !o.mesh_indexed)) {
         fprintf(stderr, "--mesh-cell X (a length, X > 0) simplifies the indexed mesh: it needs --mesh-indexed\n");
+        return 2;
+    }
+    if (o.mesh_smooth < 0 || (o.mesh_smooth != 0 && !o.mesh_indexed)) {
+        fprintf(stderr, "--mesh-smooth N (N >= 0 iterations) smooths the indexed mesh: it needs --mesh-indexed\n");
         return 2;
     }
     const int ndev = kfx_device_count();
@@ -446,7 +452,7 @@ int main(int argc, char** argv)
         const char* er = getenv("RANK"); const char* ew = getenv("WORLD_SIZE"); const char* el = getenv("LOCAL_RANK");
         rank = er ? atoi(er) : 0;
         world = ew ? atoi(ew) : 1;
-        if (world > 1 && (o.mesh_min_faces || o.mesh_largest || o.mesh_cell != 0.0f)) { fprintf(stderr, "%s", kMeshFilterNeedsOneRank); return 2; }
+        if (world > 1 && (o.mesh_min_faces || o.mesh_largest || o.mesh_cell != 0.0f || o.mesh_smooth)) { fprintf(stderr, "%s", kMeshFilterNeedsOneRank); return 2; }
         const int local = el ? atoi(el) : rank;
         if (world > ndev) { fprintf(stderr, "kinectfusion_slabs: %d ranks need %d GPUs, this node shows %d\n", world, world, ndev); return 2; }
         GpuCheckStatus(kfx_set_device(local % ndev));
@@ -461,7 +467,7 @@ int main(int argc, char** argv)
         RunRank(o, &comm, depth_mm, rgb, poses, &r0);
         comm.destroy(&comm);
     } else {
-        if (world > 1 && (o.mesh_min_faces || o.mesh_largest || o.mesh_cell != 0.0f)) { fprintf(stderr, "%s", kMeshFilterNeedsOneRank); return 2; }
+        if (world > 1 && (o.mesh_min_faces || o.mesh_largest || o.mesh_cell != 0.0f || o.mesh_smooth)) { fprintf(stderr, "%s", kMeshFilterNeedsOneRank); return 2; }
         std::vector<kfx_comm> comms(world);
         if (o.p2p) GpuCheckStatus(kfx_comm_create_threads_p2p(comms.data(), world, 20000));
         else GpuCheckStatus(kfx_comm_create_threads(comms.data(), world));

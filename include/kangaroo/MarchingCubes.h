@@ -12,6 +12,9 @@
 // indexed mesh, and the mesh without its small ones -- the floaters around the surface; SaveMeshIndexed takes min_faces / largest.
 // roo::MeshSimplify (include/kfx_mesh_simplify.h) is the level of detail after them: the vertices of one cell of a world-anchored grid
 // become one, on the device; SaveMeshIndexed(..., min_faces, largest, nvert, cell) applies it after the filter.
+// roo::MeshAdjacency / roo::MeshSmooth / roo::MeshVertexNormals (include/kfx_mesh_smooth.h) come last: every vertex's face corners in
+// ascending order, Laplacian / Taubin passes that sum in that order, and normals recomputed from the faces;
+// SaveMeshIndexed(..., min_faces, largest, nvert, cell, smooth_iterations) applies them after the other two.
 #pragma once
 
 #include <cstdint>
@@ -23,6 +26,7 @@
 #include <kfx_mesh_index.h>
 #include <kfx_mesh_clean.h>
 #include <kfx_mesh_simplify.h>
+#include <kfx_mesh_smooth.h>
 
 #include <kangaroo/BoundedVolume.h>
 #include <kangaroo/Sdf.h>
@@ -119,10 +123,58 @@ inline void SimplifyBuffers(DeviceBuffer& dv, DeviceBuffer& dn, DeviceBuffer& dc
     nt = kept[1];
 }
 
+// The parameters of a smoothing (include/kfx_mesh_smooth.h): Taubin's by default, the open boundary pinned
+struct MeshSmoothing {
+    int iterations = 5;
+    float lambda = 0.5f, mu = -0.53f;
+    bool pin_boundary = true;
+};
+
+// The incidence lists of nt faces over nv vertices in device memory: start (nv + 1 words), inc (3 nt words) and, if asked for, flags (nv words)
+struct DeviceAdjacency {
+    DeviceBuffer start, inc, flags;
+};
+inline DeviceAdjacency Adjacency(const unsigned* faces, size_t nv, size_t nt, bool with_flags)
+{
+    DeviceAdjacency a;
+    const size_t nbytes = kfx_mesh_adjacency_scratch_bytes(nv, nt);
+    DeviceBuffer scratch(nbytes);
+    a.start = DeviceBuffer((nv + 1) * 4);
+    a.inc = DeviceBuffer(nt * 12);
+    if (with_flags) a.flags = DeviceBuffer(nv * 4);
+    GpuCheckStatus(kfx_mesh_adjacency(faces, nt, nv, a.start.get<unsigned>(), a.inc.get<unsigned>(), a.flags.get<unsigned>(), scratch.get(), nbytes, 0));   // (nbytes 0: the reason)
+    return a;
+}
+
+// nv vertices in device memory after a smoothing, in a new buffer; and their normals from the faces
+inline DeviceBuffer SmoothedVertices(const float* verts, const unsigned* faces, size_t nv, size_t nt, const DeviceAdjacency& a, const MeshSmoothing& how)
+{
+    const size_t nbytes = kfx_mesh_smooth_scratch_bytes(nv, nt);
+    DeviceBuffer scratch(nbytes), out(nv * 12);
+    GpuCheckStatus(kfx_mesh_smooth(verts, faces, nt, nv, a.start.get<unsigned>(), a.inc.get<unsigned>(), how.pin_boundary ? a.flags.get<unsigned>() : nullptr,
+                                   how.iterations, how.lambda, how.mu, how.pin_boundary ? KFX_MESH_BOUNDARY : 0u, out.get<float>(), scratch.get(), nbytes, 0));
+    return out;
+}
+inline DeviceBuffer Normals(const float* verts, const unsigned* faces, size_t nv, size_t nt, const DeviceAdjacency& a)
+{
+    DeviceBuffer scratch(256), out(nv * 12);
+    GpuCheckStatus(kfx_mesh_vertex_normals(verts, faces, nt, nv, a.start.get<unsigned>(), a.inc.get<unsigned>(), out.get<float>(), scratch.get(), 256, 0));
+    return out;
+}
+
+// An indexed mesh in device memory with its vertices smoothed and its normals (where it has any) recomputed from the faces; colours and
+// faces stay as they are
+inline void SmoothBuffers(DeviceBuffer& dv, DeviceBuffer& dn, const DeviceBuffer& faces, size_t nv, size_t nt, const MeshSmoothing& how)
+{
+    const DeviceAdjacency a = Adjacency(faces.get<unsigned>(), nv, nt, how.pin_boundary);
+    dv = SmoothedVertices(dv.get<float>(), faces.get<unsigned>(), nv, nt, a, how);
+    if (dn.get()) dn = Normals(dv.get<float>(), faces.get<unsigned>(), nv, nt, a);
+}
+
 // The mesh of `vol` (slab: its cubes [own_lo, own_hi) of the volume `slab` describes); keep: an indexed mesh without its small components;
-// simplify_cell > 0: then simplified on a grid of that cell (0: off)
+// simplify_cell > 0: then simplified on a grid of that cell (0: off); smooth_iterations > 0: then smoothed, MeshSmoothing's defaults (0: off)
 inline HostMesh Extract(const kfx_volume* vol, int cell, const kfx_slab* slab, int own_lo, int own_hi, const kfx_volume* colorvol, bool indexed = false,
-                        const MeshKeep& keep = MeshKeep(), float simplify_cell = 0.0f)
+                        const MeshKeep& keep = MeshKeep(), float simplify_cell = 0.0f, int smooth_iterations = 0)
 {
     const size_t nbytes = kfx_mesh_scratch_bytes(vol, cell, slab, own_lo, own_hi);
     if (!nbytes) GpuCheckStatus(kfx_mesh_plan(vol, cell, slab, own_lo, own_hi, nullptr, 0, nullptr, 0));   // the reason
@@ -165,6 +217,11 @@ inline HostMesh Extract(const kfx_volume* vol, int cell, const kfx_slab* slab, i
         m.nvert = nv;
         m.faces.resize(3 * m.ntri);
     }
+    if (smooth_iterations != 0 && indexed && m.ntri) {   // (last: it moves what the other two copy)
+        MeshSmoothing how;
+        how.iterations = smooth_iterations;
+        SmoothBuffers(dv, dn, faces, nv, m.ntri, how);
+    }
     m.v.resize(nv * 3); m.n.resize(nv * 3); m.c.resize(m.color ? nv * 4 : 0);
     dv.CopyTo(m.v.data(), nv * 12);
     dn.CopyTo(m.n.data(), nv * 12);
@@ -200,10 +257,10 @@ inline size_t WritePly(const std::string& path, const HostMesh& m)
 // SaveMesh / SaveMeshIndexed of a BoundedVolume<T>; a T without a Cell<T> does not compile
 template<typename T, typename Manage1, typename Manage2>
 inline size_t Save(const std::string& filename, BoundedVolume<T,TargetDevice,Manage1>& vol, BoundedVolume<float,TargetDevice,Manage2>* volColor, bool indexed, size_t* nvert,
-                   const MeshKeep& keep = MeshKeep(), float simplify_cell = 0.0f)
+                   const MeshKeep& keep = MeshKeep(), float simplify_cell = 0.0f, int smooth_iterations = 0)
 {
     const bool color = volColor && volColor->IsValid();
-    const HostMesh m = Extract(vol.abi(), Cell<T>::kind, nullptr, 0, 0, color ? volColor->abi() : nullptr, indexed, keep, simplify_cell);
+    const HostMesh m = Extract(vol.abi(), Cell<T>::kind, nullptr, 0, 0, color ? volColor->abi() : nullptr, indexed, keep, simplify_cell, smooth_iterations);
     if (nvert) *nvert = m.nvert;
     return WritePly(filename + ".ply", m);
 }
@@ -254,24 +311,27 @@ inline size_t SaveMeshIndexed(std::string filename, BoundedVolume<T,TargetDevice
 // (include/kfx_mesh_clean.h) -- the components with at least min_faces faces; largest: only the one with the most, min_faces on top.
 // cell > 0: what is left is then simplified on the device on a grid of `cell` world units anchored at the world origin
 // (include/kfx_mesh_simplify.h); 0 means off, and min_faces = 0, largest = false filters nothing.
+// smooth_iterations > 0: what is left is then smoothed on the device by that many Taubin iterations (lambda 0.5, mu -0.53, the open
+// boundary pinned) and the normals are recomputed from the faces (include/kfx_mesh_smooth.h); 0 means off.
 template<typename T, typename Manage1, typename Manage2>
 inline size_t SaveMeshIndexed(std::string filename, BoundedVolume<T,TargetDevice,Manage1>& vol, BoundedVolume<float,TargetDevice,Manage2>* volColor, size_t min_faces,
-                              bool largest, size_t* nvert = nullptr, float cell = 0.0f)
+                              bool largest, size_t* nvert = nullptr, float cell = 0.0f, int smooth_iterations = 0)
 {
-    return mesh_detail::Save(filename, vol, volColor, true, nvert, mesh_detail::MeshKeep{min_faces, largest}, cell);
+    return mesh_detail::Save(filename, vol, volColor, true, nvert, mesh_detail::MeshKeep{min_faces, largest}, cell, smooth_iterations);
 }
 
 template<typename T, typename Manage>
-inline size_t SaveMeshIndexed(std::string filename, BoundedVolume<T,TargetDevice,Manage>& vol, size_t min_faces, bool largest, size_t* nvert = nullptr, float cell = 0.0f)
+inline size_t SaveMeshIndexed(std::string filename, BoundedVolume<T,TargetDevice,Manage>& vol, size_t min_faces, bool largest, size_t* nvert = nullptr, float cell = 0.0f,
+                              int smooth_iterations = 0)
 {
-    return SaveMeshIndexed<T,Manage,Manage>(filename, vol, nullptr, min_faces, largest, nvert, cell);
+    return SaveMeshIndexed<T,Manage,Manage>(filename, vol, nullptr, min_faces, largest, nvert, cell, smooth_iterations);
 }
 
 template<typename T, typename Manage1, typename Manage2>
 inline size_t SaveMeshIndexed(std::string filename, BoundedVolume<T,TargetDevice,Manage1>& vol, BoundedVolume<float,TargetDevice,Manage2>& volColor, size_t min_faces,
-                              bool largest, size_t* nvert = nullptr, float cell = 0.0f)
+                              bool largest, size_t* nvert = nullptr, float cell = 0.0f, int smooth_iterations = 0)
 {
-    return SaveMeshIndexed<T,Manage1,Manage2>(filename, vol, &volColor, min_faces, largest, nvert, cell);
+    return SaveMeshIndexed<T,Manage1,Manage2>(filename, vol, &volColor, min_faces, largest, nvert, cell, smooth_iterations);
 }
 
 // MeshComponents(faces, n_faces, n_verts, vertex_component, component_faces): the connected components of an indexed mesh whose faces
@@ -347,6 +407,52 @@ inline mesh_detail::HostMesh MeshSimplify(const float* verts, const float* norms
         map.CopyTo(vertex_cluster->data(), n_verts * 4);
     }
     return m;
+}
+
+// MeshAdjacency(faces, n_faces, n_verts, inc_start, inc[, vertex_flags]): the incidence lists of an indexed mesh whose faces are in device
+// memory, built on the device (include/kfx_mesh_smooth.h).  The host vectors receive inc_start (n_verts + 1), inc (3 n_faces: every vertex's
+// corner slots 3 f + c, ascending) and, if given, the flags KFX_MESH_BOUNDARY / NONMANIFOLD / DEGENERATE / ISOLATED of every vertex.
+inline void MeshAdjacency(const uint32_t* faces, size_t n_faces, size_t n_verts, std::vector<uint32_t>& inc_start, std::vector<uint32_t>& inc,
+                          std::vector<uint32_t>* vertex_flags = nullptr)
+{
+    const mesh_detail::DeviceAdjacency a = mesh_detail::Adjacency(faces, n_verts, n_faces, vertex_flags != nullptr);
+    inc_start.assign(n_verts + 1, 0);
+    inc.resize(3 * n_faces);
+    if (n_faces) a.start.CopyTo(inc_start.data(), inc_start.size() * 4);
+    a.inc.CopyTo(inc.data(), inc.size() * 4);
+    if (vertex_flags) {
+        vertex_flags->resize(n_verts);
+        a.flags.CopyTo(vertex_flags->data(), n_verts * 4);
+    }
+}
+
+// MeshSmooth(verts, faces, n_verts, n_faces[, how, normals]): the vertices of an indexed mesh in device memory after how.iterations
+// smoothing iterations (include/kfx_mesh_smooth.h), as a host array of 3 n_verts floats; normals, if given, receives the normals of the
+// smoothed mesh, recomputed from the faces.
+inline std::vector<float> MeshSmooth(const float* verts, const uint32_t* faces, size_t n_verts, size_t n_faces,
+                                     const mesh_detail::MeshSmoothing& how = mesh_detail::MeshSmoothing(), std::vector<float>* normals = nullptr)
+{
+    std::vector<float> out(3 * n_verts);
+    if (!n_faces) return out;
+    const mesh_detail::DeviceAdjacency a = mesh_detail::Adjacency(faces, n_verts, n_faces, how.pin_boundary);
+    const mesh_detail::DeviceBuffer moved = mesh_detail::SmoothedVertices(verts, faces, n_verts, n_faces, a, how);
+    moved.CopyTo(out.data(), out.size() * 4);
+    if (normals) {
+        normals->resize(3 * n_verts);
+        mesh_detail::Normals(moved.get<float>(), faces, n_verts, n_faces, a).CopyTo(normals->data(), normals->size() * 4);
+    }
+    return out;
+}
+
+// MeshVertexNormals(verts, faces, n_verts, n_faces): per-vertex normals of an indexed mesh in device memory from its faces, on the side the
+// extraction's normals lie on (include/kfx_mesh_smooth.h), as a host array of 3 n_verts floats; zero for a vertex in no face.
+inline std::vector<float> MeshVertexNormals(const float* verts, const uint32_t* faces, size_t n_verts, size_t n_faces)
+{
+    std::vector<float> out(3 * n_verts, 0.0f);
+    if (!n_faces) return out;
+    const mesh_detail::DeviceAdjacency a = mesh_detail::Adjacency(faces, n_verts, n_faces, false);
+    mesh_detail::Normals(verts, faces, n_verts, n_faces, a).CopyTo(out.data(), out.size() * 4);
+    return out;
 }
 
 }

@@ -183,7 +183,8 @@ namespace mesh_detail
 // edge.  cube_index and tri_offset, if given, receive every active cube's dense index and first triangle in the list's order (soup).
 inline HostMesh ExtractBricks(const kfx_volume& frame, int cell, const unsigned* ids, const void* cells, size_t n, const unsigned* color_ids,
                               const void* color_cells, size_t n_color, bool color, bool indexed = false, std::vector<long long>* cube_index = nullptr,
-                              std::vector<unsigned>* tri_offset = nullptr, const MeshKeep& keep = MeshKeep(), float simplify_cell = 0.0f)
+                              std::vector<unsigned>* tri_offset = nullptr, const MeshKeep& keep = MeshKeep(), float simplify_cell = 0.0f,
+                              int smooth_iterations = 0)
 {
     const size_t nbytes = MeshBricksScratchBytes(n, color ? n_color : 0);
     DeviceBuffer scratch(nbytes), xscratch, active, offsets, faces;
@@ -225,6 +226,11 @@ inline HostMesh ExtractBricks(const kfx_volume& frame, int cell, const unsigned*
         SimplifyBuffers(dv, dn, dc, faces, nv, m.ntri, simplify_cell);
         m.nvert = nv;
         m.faces.resize(3 * m.ntri);
+    }
+    if (smooth_iterations != 0 && indexed && m.ntri) {   // (... and then smoothed, the normals recomputed from the faces)
+        MeshSmoothing how;
+        how.iterations = smooth_iterations;
+        SmoothBuffers(dv, dn, faces, nv, m.ntri, how);
     }
     m.v.resize(nv * 3); m.n.resize(nv * 3); m.c.resize(m.color ? nv * 4 : 0);
     dv.CopyTo(m.v.data(), nv * 12);
@@ -270,22 +276,23 @@ inline size_t SaveMeshBricksIndexed(std::string filename, const kfx_volume& fram
 }
 
 // ... min_faces, largest: without its small components, filtered on the device (MarchingCubes.h: SaveMeshIndexed's); simplify_cell > 0:
-// then simplified on a grid of that cell anchored at the world origin (include/kfx_mesh_simplify.h), 0: off
+// then simplified on a grid of that cell anchored at the world origin (include/kfx_mesh_simplify.h), 0: off; smooth_iterations > 0: then
+// smoothed by that many Taubin iterations, the normals recomputed from the faces (include/kfx_mesh_smooth.h), 0: off
 inline size_t SaveMeshBricksIndexed(std::string filename, const kfx_volume& frame, int cell, const unsigned* ids, const void* cells, size_t n,
-                                    size_t min_faces, bool largest, size_t* nvert = nullptr, float simplify_cell = 0.0f)
+                                    size_t min_faces, bool largest, size_t* nvert = nullptr, float simplify_cell = 0.0f, int smooth_iterations = 0)
 {
     const mesh_detail::HostMesh m = mesh_detail::ExtractBricks(frame, cell, ids, cells, n, nullptr, nullptr, 0, false, true, nullptr, nullptr,
-                                                               mesh_detail::MeshKeep{min_faces, largest}, simplify_cell);
+                                                               mesh_detail::MeshKeep{min_faces, largest}, simplify_cell, smooth_iterations);
     if (nvert) *nvert = m.nvert;
     return mesh_detail::WritePly(filename + ".ply", m);
 }
 
 inline size_t SaveMeshBricksIndexed(std::string filename, const kfx_volume& frame, int cell, const unsigned* ids, const void* cells, size_t n,
                                     const unsigned* color_ids, const void* color_cells, size_t n_color, size_t min_faces, bool largest,
-                                    size_t* nvert = nullptr, float simplify_cell = 0.0f)
+                                    size_t* nvert = nullptr, float simplify_cell = 0.0f, int smooth_iterations = 0)
 {
     const mesh_detail::HostMesh m = mesh_detail::ExtractBricks(frame, cell, ids, cells, n, color_ids, color_cells, n_color, true, true, nullptr,
-                                                               nullptr, mesh_detail::MeshKeep{min_faces, largest}, simplify_cell);
+                                                               nullptr, mesh_detail::MeshKeep{min_faces, largest}, simplify_cell, smooth_iterations);
     if (nvert) *nvert = m.nvert;
     return mesh_detail::WritePly(filename + ".ply", m);
 }

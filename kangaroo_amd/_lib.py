@@ -66,7 +66,7 @@ class KfxError(RuntimeError):
 
 PI, PV, PF = C.POINTER(KfxImage), C.POINTER(KfxVolume), C.POINTER(C.c_float)
 
-# name -> (restype, argtypes); every symbol include/kfx.h declares (and kfx_summary_h.h, kfx_mesh.h, kfx_mesh_index.h, kfx_color.h, kfx_slab_color.h, kfx_sensor.h, kfx_shift.h, kfx_bricks.h, kfx_mesh_bricks.h, kfx_mesh_bricks_index.h, kfx_raycast_bricks.h, kfx_brick_pool.h, kfx_mesh_clean.h, kfx_mesh_simplify.h)
+# name -> (restype, argtypes); every symbol include/kfx.h declares (and kfx_summary_h.h, kfx_mesh.h, kfx_mesh_index.h, kfx_color.h, kfx_slab_color.h, kfx_sensor.h, kfx_shift.h, kfx_bricks.h, kfx_mesh_bricks.h, kfx_mesh_bricks_index.h, kfx_raycast_bricks.h, kfx_brick_pool.h, kfx_mesh_clean.h, kfx_mesh_simplify.h, kfx_mesh_smooth.h)
 SIGNATURES = {
     "kfx_sdf_fuse": (C.c_int, [PV, PI, PI, PF, PF, C.c_float, C.c_float, C.c_float, C.c_uint, C.c_void_p]),
     "kfx_sdf_fuse_slab": (C.c_int, [PV, C.POINTER(KfxSlab), PI, PI, PF, PF, C.c_float, C.c_float, C.c_float, C.c_uint, C.c_void_p]),
@@ -252,6 +252,15 @@ SIGNATURES = {
                                          C.POINTER(C.c_ulonglong), C.c_void_p]),
     "kfx_mesh_simplify_emit": (C.c_int, [C.c_void_p, C.c_size_t, C.c_ulonglong, C.c_ulonglong, C.POINTER(C.c_ulonglong), C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # include/kfx_mesh_smooth.h
+    "kfx_mesh_adjacency_scratch_bytes": (C.c_size_t, [C.c_ulonglong, C.c_ulonglong]),
+    "kfx_mesh_smooth_scratch_bytes": (C.c_size_t, [C.c_ulonglong, C.c_ulonglong]),
+    "kfx_mesh_vertex_normals_scratch_bytes": (C.c_size_t, [C.c_ulonglong, C.c_ulonglong]),
+    "kfx_mesh_adjacency": (C.c_int, [C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "kfx_mesh_smooth": (C.c_int, [C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float,
+                                  C.c_uint, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "kfx_mesh_vertex_normals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                          C.c_void_p]),
 }
 
 _lib = None

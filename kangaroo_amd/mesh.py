@@ -33,6 +33,11 @@ in the world -- one vertex a cell, the one nearest its centre -- and drops the f
 function of the mesh and the grid.  simplify_cell= on the Extract / Save calls applies it after the filter: the mesh's resolution is
 no longer tied to the volume's.
 
+Smoothing (include/kfx_mesh_smooth.h), on an indexed mesh in device memory: MeshAdjacency lists every vertex's face corners in ascending
+order (and classes the vertices: boundary, non-manifold, degenerate, isolated), SmoothMesh runs Laplacian / Taubin passes over those lists
+-- every float sum in the lists' order, so every output bit is a function of the mesh -- and VertexNormals recomputes the normals from the
+faces.  smooth= on the Extract / Save calls applies it last, after the filter and the simplification, and replaces the normals.
+
 Case tables: kangaroo_amd/csrc/mc_tables.inc, derived by scripts/gen_mc_tables.py.  Their boundary loops and
 winding agree with the classic tables the reference uses in all 256 cases; 158 cases split a polygon along a
 different interior diagonal (an equally valid triangulation of the same loop), so meshes are the same surface
@@ -174,13 +179,113 @@ def _simplify_args(what, indexed, slab, simplify_cell):
     return True
 
 
-def _finish(got, clean, simplify, min_faces, largest, simplify_cell, stream):
-    """an indexed mesh after the steps its Extract call was asked for: floaters go first, because clustering changes face counts"""
+def _finish(got, clean, simplify, min_faces, largest, simplify_cell, stream, smooth=None):
+    """an indexed mesh after the steps its Extract call was asked for: floaters go first, because clustering changes face counts;
+    smoothing (smooth: _smooth_args's keywords, or None) goes last, because it moves what the other two copy"""
     if clean:
         got = FilterMesh(*got, min_faces=min_faces, largest=largest, stream=stream)
     if simplify:
         got = SimplifyMesh(*got, cell=simplify_cell, stream=stream)
+    if smooth is not None:
+        verts, norms, colors, faces = got
+        verts, norms = SmoothMesh(verts, faces, normals=True, stream=stream, **smooth)
+        got = (verts, norms, colors, faces)
     return got
+
+
+SMOOTH_KEYS = ("iterations", "lam", "mu", "pin_boundary")
+
+
+def _smooth_args(what, indexed, slab, smooth):
+    """SmoothMesh's keywords of a smooth= argument -- None: off (returns None); an int: that many iterations; a dict with keys of
+    SMOOTH_KEYS --; it is honoured on an indexed mesh of a whole volume"""
+    if smooth is None:
+        return None
+    if isinstance(smooth, dict):
+        kw = dict(smooth)
+        if set(kw) - set(SMOOTH_KEYS):
+            raise ValueError("%s: smooth takes the keys %s (the normals are always recomputed)" % (what, ", ".join(SMOOTH_KEYS)))
+    elif isinstance(smooth, (int, np.integer)) and not isinstance(smooth, bool):
+        kw = dict(iterations=int(smooth))
+    else:
+        raise ValueError("%s: smooth is None, an iteration count or a dict of SmoothMesh's keywords" % what)
+    if int(kw.get("iterations", 5)) < 0:
+        raise ValueError("%s: smooth's iterations is a count" % what)
+    if not indexed:
+        raise ValueError("%s: smooth moves the vertices of the indexed mesh (indexed=True)" % what)
+    if slab is not None:
+        raise ValueError("%s: a slab's mesh is welded within its rank, so its components are cut at the slab boundaries; "
+                         "smooth needs the whole volume's mesh" % what)
+    return kw
+
+
+def _mesh_faces(what, faces):
+    if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("%s: faces is a (T, 3) int32 tensor of uint32 ids" % what)
+    return faces.contiguous()
+
+
+def MeshAdjacency(faces, n_verts, with_flags=False, stream=None):
+    """The incidence lists of an indexed mesh (include/kfx_mesh_smooth.h): faces (T, 3) int32 device tensor of uint32 ids < n_verts.
+    Returns (inc_start (V + 1,), inc (3T,)), int32 device tensors of uint32 bits: inc[inc_start[v]:inc_start[v + 1]] are the corner
+    slots 3 f + c with faces[f][c] == v, ascending.  with_flags=True: also vertex_flags (V,): bit 0 boundary, 1 non-manifold,
+    2 degenerate, 3 isolated.  A function of (n_verts, faces) alone."""
+    L = _lib.load()
+    faces = _mesh_faces("MeshAdjacency", faces)
+    nv, nt = int(n_verts), int(faces.shape[0])
+    dev = faces.device
+    nbytes = L.kfx_mesh_adjacency_scratch_bytes(nv, nt)
+    scratch = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+    start = torch.zeros(nv + 1, dtype=torch.int32, device=dev) if nt == 0 else torch.empty(nv + 1, dtype=torch.int32, device=dev)
+    inc = torch.empty(3 * nt, dtype=torch.int32, device=dev)
+    flags = torch.empty(nv, dtype=torch.int32, device=dev) if with_flags else None
+    _lib.check(L.kfx_mesh_adjacency(_ptr(faces) if nt else None, nt, nv, _ptr(start), _ptr(inc) if nt else None, _ptr(flags) if with_flags and nv else None,
+                                    _ptr(scratch), nbytes, _stream(stream)))   # (nbytes 0: the reason)
+    return (start, inc, flags) if with_flags else (start, inc)
+
+
+def _mesh_verts(what, verts):
+    verts = verts.contiguous()
+    if verts.dtype != torch.float32 or verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError("%s: verts is a (V, 3) float32 tensor" % what)
+    return verts
+
+
+def VertexNormals(verts, faces, stream=None, adjacency=None):
+    """Per-vertex normals of an indexed mesh from its faces (include/kfx_mesh_smooth.h): the sum of the cross products of every incident
+    face, in the order of the vertex's incidence list, normalised; on the side the extraction's normals lie on; zero for a vertex in no
+    face or with a sum of zero or non-finite length.  adjacency: MeshAdjacency's (inc_start, inc[, flags]), if the caller has it."""
+    L = _lib.load()
+    verts, faces = _mesh_verts("VertexNormals", verts), _mesh_faces("VertexNormals", faces)
+    nv, nt = len(verts), int(faces.shape[0])
+    start, inc = (adjacency if adjacency is not None else MeshAdjacency(faces, nv, stream=stream))[:2]
+    norms = torch.zeros_like(verts) if nt == 0 else torch.empty_like(verts)
+    scratch = torch.empty(256, dtype=torch.uint8, device=verts.device)
+    _lib.check(L.kfx_mesh_vertex_normals(_ptr(verts) if nv else None, _ptr(faces) if nt else None, nt, nv, _ptr(start), _ptr(inc) if nt else None,
+                                         _ptr(norms) if nv else None, _ptr(scratch), 256, _stream(stream)))
+    return norms
+
+
+def SmoothMesh(verts, faces, iterations=5, lam=0.5, mu=-0.53, pin_boundary=True, normals=False, stream=None):
+    """The vertices of an indexed mesh after `iterations` smoothing iterations (include/kfx_mesh_smooth.h): each a pass that moves every
+    vertex by lam towards the mean of its neighbour entries, then one by mu (< 0: Taubin's, which holds the volume; 0: plain Laplacian
+    smoothing, which shrinks).  pin_boundary: vertices on an open boundary stay where they are, bit for bit; so do vertices in no face
+    and vertices whose new position would not be finite.  Every sum runs in the order of the vertex's incidence list: the output is a
+    function of the arrays and the parameters.  Returns new vertices; normals=True: (verts, norms) with VertexNormals of the new ones."""
+    L = _lib.load()
+    verts, faces = _mesh_verts("SmoothMesh", verts), _mesh_faces("SmoothMesh", faces)
+    nv, nt = len(verts), int(faces.shape[0])
+    adjacency = MeshAdjacency(faces, nv, with_flags=bool(pin_boundary), stream=stream)
+    flags = adjacency[2] if pin_boundary else None
+    nbytes = L.kfx_mesh_smooth_scratch_bytes(nv, nt)
+    scratch = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=verts.device)
+    out = verts.clone() if nt == 0 else torch.empty_like(verts)
+    _lib.check(L.kfx_mesh_smooth(_ptr(verts) if nv else None, _ptr(faces) if nt else None, nt, nv, _ptr(adjacency[0]), _ptr(adjacency[1]) if nt else None,
+                                 _ptr(flags) if flags is not None and nv else None, int(iterations), float(lam), float(mu), 1 if pin_boundary else 0,
+                                 _ptr(out) if nv else None, _ptr(scratch), nbytes, _stream(stream)))
+    if not normals:
+        return out
+    return out, VertexNormals(out, faces, stream=stream, adjacency=adjacency)
 
 
 def SimplifyMesh(verts, norms, colors, faces, cell, origin=(0.0, 0.0, 0.0), stream=None, with_map=False):
@@ -219,7 +324,8 @@ def SimplifyMesh(verts, norms, colors, faces, cell, origin=(0.0, 0.0, 0.0), stre
     return out + (vmap,) if with_map else out
 
 
-def ExtractMesh(vol, colorVol=None, stream=None, slab=None, with_index=False, indexed=False, min_faces=0, largest=False, simplify_cell=None):
+def ExtractMesh(vol, colorVol=None, stream=None, slab=None, with_index=False, indexed=False, min_faces=0, largest=False, simplify_cell=None,
+                smooth=None):
     """Returns (verts, norms, colors): float32 device tensors of shape (3T, 3), (3T, 3) and (3T, 4) or None.
     indexed=True: (verts, norms, colors, faces) with V rows each and faces (T, 3), uint32 ids held in an int32 tensor (the weld
     of the arrays above by lattice edge, see the module docstring).
@@ -230,10 +336,13 @@ def ExtractMesh(vol, colorVol=None, stream=None, slab=None, with_index=False, in
     box of `vol`; fp32 SDF cells) and the colours equal the single-volume mesh's too.  with_index: also return cube_index (int64, global) and
     tri_offset (int32: the first triangle of each active cube, uint32 bits).
     min_faces / largest (with indexed=True, whole volumes): FilterMesh's, applied on the device to the mesh returned.
-    simplify_cell (with indexed=True, whole volumes): SimplifyMesh's cell, anchored at the world origin, applied after the filter."""
+    simplify_cell (with indexed=True, whole volumes): SimplifyMesh's cell, anchored at the world origin, applied after the filter.
+    smooth (with indexed=True, whole volumes): None, an iteration count or a dict of SmoothMesh's iterations / lam / mu / pin_boundary,
+    applied last; the normals returned are then VertexNormals of the smoothed mesh, the colours are left as they are."""
     L = _lib.load()
     clean = _filter_args("ExtractMesh", indexed, slab, min_faces, largest)
     simplify = _simplify_args("ExtractMesh", indexed, slab, simplify_cell)
+    smooth = _smooth_args("ExtractMesh", indexed, slab, smooth)
     if vol.kind not in CELL:
         raise ValueError("ExtractMesh: volume kind %r (fp32 or half SDF cells)" % vol.kind)
     cell, dev = CELL[vol.kind], vol.storage.device
@@ -256,7 +365,7 @@ def ExtractMesh(vol, colorVol=None, stream=None, slab=None, with_index=False, in
                     index_plan=lambda *a: L.kfx_mesh_index_plan(*args, *a),
                     emit=lambda *a: L.kfx_mesh_emit(*args, cref, *a),
                     emit_indexed=lambda scratch, nbytes, *a: L.kfx_mesh_emit_indexed(*args, cref, *a))   # (reads the index scratch alone)
-    return _finish(got, clean, simplify, min_faces, largest, simplify_cell, stream)
+    return _finish(got, clean, simplify, min_faces, largest, simplify_cell, stream, smooth)
 
 
 BRICK_BYTES = {"f32": 4096, "f16": 2048, "c32": 2048}   # one packed 8 x 8 x 8 brick of each cell kind
@@ -284,7 +393,7 @@ def BrickMeshScratchBytes(n, n_color=0):
 
 
 def ExtractBrickMesh(dims, boxmin, boxmax, kind, ids, cells, color_ids=None, color_cells=None, with_index=False, stream=None, indexed=False,
-                     min_faces=0, largest=False, simplify_cell=None):
+                     min_faces=0, largest=False, simplify_cell=None, smooth=None):
     """The mesh of packed 8 x 8 x 8 bricks (include/kfx_mesh_bricks.h): what ExtractMesh returns for the dense volume of `dims` cells and
     the box (boxmin, boxmax) that is NaN everywhere and then gets BrickUnpack(ids, cells) -- the same cubes, each with the same triangles
     bit for bit -- without that volume; memory in proportion to the bricks and the mesh.  Only the order differs: brick by brick in
@@ -298,10 +407,12 @@ def ExtractBrickMesh(dims, boxmin, boxmax, kind, ids, cells, color_ids=None, col
     the sequential first-occurrence weld, by lattice edge, of the arrays above in their (brick) order (include/kfx_mesh_bricks_index.h).
     Not with with_index=True, which lists the soup's cubes.
     min_faces / largest (with indexed=True): FilterMesh's, applied on the device to the mesh returned.
-    simplify_cell (with indexed=True): SimplifyMesh's cell, anchored at the origin of the box's coordinates, applied after the filter."""
+    simplify_cell (with indexed=True): SimplifyMesh's cell, anchored at the origin of the box's coordinates, applied after the filter.
+    smooth (with indexed=True): ExtractMesh's, applied last."""
     L = _lib.load()
     clean = _filter_args("ExtractBrickMesh", indexed, None, min_faces, largest)
     simplify = _simplify_args("ExtractBrickMesh", indexed, None, simplify_cell)
+    smooth = _smooth_args("ExtractBrickMesh", indexed, None, smooth)
     if kind not in CELL:
         raise ValueError("ExtractBrickMesh: cell kind %r (fp32 or half SDF cells)" % (kind,))
     if indexed and with_index:
@@ -326,15 +437,15 @@ def ExtractBrickMesh(dims, boxmin, boxmax, kind, ids, cells, color_ids=None, col
                     index_plan=lambda *a: L.kfx_mesh_bricks_index_plan(*sdf, *a),
                     emit=lambda *a: L.kfx_mesh_bricks_emit(*both, *a),
                     emit_indexed=lambda *a: L.kfx_mesh_bricks_emit_indexed(*both, *a))
-    return _finish(got, clean, simplify, min_faces, largest, simplify_cell, stream)
+    return _finish(got, clean, simplify, min_faces, largest, simplify_cell, stream, smooth)
 
 
 def SaveBrickMesh(filename, dims, boxmin, boxmax, kind, ids, cells, color_ids=None, color_cells=None, binary=True, indexed=False, min_faces=0,
-                  largest=False, simplify_cell=None):
+                  largest=False, simplify_cell=None, smooth=None):
     """ExtractBrickMesh's mesh as filename + ".ply" (write_ply); returns the triangle count.  indexed=True: V welded vertices and T faces
-    instead of 3T vertices; min_faces / largest / simplify_cell: ExtractBrickMesh's."""
+    instead of 3T vertices; min_faces / largest / simplify_cell / smooth: ExtractBrickMesh's."""
     arrays = ExtractBrickMesh(dims, boxmin, boxmax, kind, ids, cells, color_ids, color_cells, indexed=indexed, min_faces=min_faces, largest=largest,
-                              simplify_cell=simplify_cell)
+                              simplify_cell=simplify_cell, smooth=smooth)
     return _save_mesh(filename, arrays, binary, indexed)
 
 
@@ -374,9 +485,9 @@ def write_ply(path, verts, norms, colors=None, binary=True, faces=None):
                 f.write(("3 %d %d %d\n" % (a, b, c)).encode())
 
 
-def SaveMesh(filename, vol, colorVol=None, binary=True, slab=None, indexed=False, min_faces=0, largest=False, simplify_cell=None):
+def SaveMesh(filename, vol, colorVol=None, binary=True, slab=None, indexed=False, min_faces=0, largest=False, simplify_cell=None, smooth=None):
     """SaveMesh(filename, vol[, volColor]) (MarchingCubes.h:246-262): writes filename + ".ply"; returns the triangle count.
     fp32 or half volumes; slab: ExtractMesh's.  indexed=True: V welded vertices and T faces (ExtractMesh's) instead of 3T vertices;
-    min_faces / largest / simplify_cell: ExtractMesh's."""
-    arrays = ExtractMesh(vol, colorVol, slab=slab, indexed=indexed, min_faces=min_faces, largest=largest, simplify_cell=simplify_cell)
+    min_faces / largest / simplify_cell / smooth: ExtractMesh's."""
+    arrays = ExtractMesh(vol, colorVol, slab=slab, indexed=indexed, min_faces=min_faces, largest=largest, simplify_cell=simplify_cell, smooth=smooth)
     return _save_mesh(filename, arrays, binary, indexed)

@@ -352,25 +352,27 @@ class FramePipeline:
         skeys = self.store.keys() if self.store is not None else None
         return sdf, bricks.world_bricks(self.cstore, self.cvol, self.origin, 0.5, ops=self.ops, cover=skeys)
 
-    def ExtractWorldMesh(self, with_index=False, indexed=False, min_faces=0, largest=False, simplify_cell=None):
+    def ExtractWorldMesh(self, with_index=False, indexed=False, min_faces=0, largest=False, simplify_cell=None, smooth=None):
         """The mesh of everything the model has seen -- the live volume and what it spilled -- as mesh.ExtractBrickMesh returns it:
         continuous across the faces of the volume that no longer exist.  Without a store: the brick mesh of the live volume.
         indexed=True: (verts, norms, colors, faces), welded by lattice edge on the device (mesh.ExtractBrickMesh's); min_faces / largest:
         without its small components (mesh.FilterMesh's); simplify_cell: then clustered on a grid of that cell anchored at the world origin
-        (mesh.SimplifyMesh's) -- two world meshes taken at different times simplify to the same vertices where the surface has not changed."""
+        (mesh.SimplifyMesh's) -- two world meshes taken at different times simplify to the same vertices where the surface has not changed;
+        smooth: then smoothed, the normals recomputed from the faces (mesh.SmoothMesh's: None, an iteration count or a dict of its keywords)."""
         from . import mesh
         mesh._filter_args("ExtractWorldMesh", indexed, None, min_faces, largest)   # (before the bricks are packed)
         mesh._simplify_args("ExtractWorldMesh", indexed, None, simplify_cell)
+        mesh._smooth_args("ExtractWorldMesh", indexed, None, smooth)
         (lo, dims, bmin, bmax, ids, cells), col = self.world_bricks()
         cids, ccells = (col[4], col[5]) if col is not None else (None, None)
         return mesh.ExtractBrickMesh(dims, bmin, bmax, self.kind, ids, cells, cids, ccells, with_index=with_index, indexed=indexed,
-                                     min_faces=min_faces, largest=largest, simplify_cell=simplify_cell)
+                                     min_faces=min_faces, largest=largest, simplify_cell=simplify_cell, smooth=smooth)
 
-    def SaveWorldMesh(self, filename, binary=True, indexed=False, min_faces=0, largest=False, simplify_cell=None):
+    def SaveWorldMesh(self, filename, binary=True, indexed=False, min_faces=0, largest=False, simplify_cell=None, smooth=None):
         """ExtractWorldMesh's mesh as filename + ".ply"; returns the triangle count.  indexed=True: V welded vertices and T faces;
-        min_faces / largest / simplify_cell: ExtractWorldMesh's."""
+        min_faces / largest / simplify_cell / smooth: ExtractWorldMesh's."""
         from . import mesh
-        arrays = self.ExtractWorldMesh(indexed=indexed, min_faces=min_faces, largest=largest, simplify_cell=simplify_cell)
+        arrays = self.ExtractWorldMesh(indexed=indexed, min_faces=min_faces, largest=largest, simplify_cell=simplify_cell, smooth=smooth)
         return mesh._save_mesh(filename, arrays, binary, indexed)
 
     def world_view(self):
@@ -1009,7 +1011,7 @@ class SlabPipeline(FramePipeline):
         raise ValueError("SlabPipeline: the world view belongs to a volume that follows the camera (follow=), a single-volume option; "
                          "the model's rendering is the frame's composite")
 
-    def ExtractMesh(self, indexed=False, min_faces=0, largest=False, simplify_cell=None):
+    def ExtractMesh(self, indexed=False, min_faces=0, largest=False, simplify_cell=None, smooth=None):
         """This rank's part of the model's mesh (include/kfx_mesh.h): the cubes whose lower plane it owns, [z0, min(z1, D - 1)),
         every triangle bit-identical to the single-volume mesh's, in emission order; (verts, norms) device tensors, or -- color=True --
         (verts, norms, colors) with the single-volume mesh's colours.
@@ -1023,6 +1025,9 @@ class SlabPipeline(FramePipeline):
                              "boundaries; min_faces / largest need the whole volume's mesh")
         if simplify_cell:   # (refused as the filter is: a cluster that straddles a slab boundary would be two)
             raise ValueError("SlabPipeline.ExtractMesh: a rank's mesh is welded within its rank; simplify_cell needs the whole volume's mesh")
+        if smooth is not None:   # (refused as the filter is: a vertex on a slab boundary would be smoothed as a boundary vertex, once per rank)
+            raise ValueError("SlabPipeline.ExtractMesh: a rank's mesh is welded within its rank, so its components are cut at the slab "
+                             "boundaries; smooth needs the whole volume's mesh")
         if self.sframe is not None:
             self.wait_composite()
         elif self.halo == "exchange" and self.world > 1:
@@ -1032,11 +1037,11 @@ class SlabPipeline(FramePipeline):
         verts, norms, colors, *faces = mesh.ExtractMesh(self.vol, self.cvol if self.color else None, slab=slab, indexed=indexed)
         return ((verts, norms, colors) if self.color else (verts, norms)) + tuple(faces)
 
-    def SaveMesh(self, prefix, binary=True, indexed=False, min_faces=0, largest=False, simplify_cell=None):
+    def SaveMesh(self, prefix, binary=True, indexed=False, min_faces=0, largest=False, simplify_cell=None, smooth=None):
         """Writes this rank's part as prefix.r<rank>.ply (with colours when color=True); returns its triangle count.
         indexed=True: welded vertices and a face list (ExtractMesh's).  min_faces / largest: refused, as ExtractMesh's."""
         from . import mesh
-        verts, norms, *rest = self.ExtractMesh(indexed=indexed, min_faces=min_faces, largest=largest, simplify_cell=simplify_cell)
+        verts, norms, *rest = self.ExtractMesh(indexed=indexed, min_faces=min_faces, largest=largest, simplify_cell=simplify_cell, smooth=smooth)
         faces = rest.pop().cpu().numpy().view("uint32") if indexed else None
         mesh.write_ply("%s.r%d.ply" % (prefix, self.rank), verts.cpu().numpy(), norms.cpu().numpy(),
                        rest[0].cpu().numpy() if rest and rest[0] is not None else None, binary, faces)
